@@ -1,7 +1,18 @@
 #!/usr/bin/env python3
 """Headline benchmark: stabilized frames/s of the Video Stabilizer Flow hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times K steps, writes the last timed step's outputs if --dump-outputs is given
+and prints one JSON line (`value` frames/s, `ms_per_step`).  Everything else the bench measures or checks outside the timed
+steps (the per-stage passes, CPU baselines, accuracy / parity checks, host round trips, Motion Apply rates, the c4 / c5
+objects of a multi-GPU line) runs with --full only.
+
+--dump-outputs DIR: after the timed steps, what the timed path handed back in its last step goes to DIR/<name>.npy
+(float32 / float64, ~32 MB in all; rank 0's shard when N > 1): `frames` and `masks` as a fixed, seeded sample of output
+pixel positions (dump_outputs below), and the arrays of the returned meta (fitted transitions, confidences, residuals,
+camera / target paths, applied matrices, padding fractions).  The clip is synthesised from fixed seeds, so two builds run
+with the same arguments can be compared file by file.
 
 One "step" = one full pass of the hot path over the clip with the input frames already resident in HBM and the
 outputs left in HBM, entered at the node boundary (`_normalize_video_input` on the resident tensor):
@@ -14,7 +25,7 @@ Workloads (BASELINE.json configs):
          (1-frame halo, RCCL all-gather of the fit records, the plan over the whole clip on every rank): per-GPU work
          fixed -> "scaling": "weak".  `--total-frames T` fixes the clip instead ("strong"; also at N = 1:
          `--gpus 1 --total-frames 1024` is the C4 clip on one GPU), `--frames F` picks another per-GPU share.
-         The default N > 1 line also carries, measured after the timed loop on the same ranks:
+         With --full the N > 1 line also carries, measured after the timed loop on the same ranks:
            `c4`  BASELINE configs[3]: one 1024-frame clip over the N ranks, total work fixed ("strong"), with the one-GPU
                  time of the same clip next to it (static record under profiles/);
            `c5`  BASELINE configs[4] (below).
@@ -29,6 +40,11 @@ anything touches the GPU and relays its output (never an exec).
 Also on the JSON line (rank 0):
   roofline       the warp kernel (dominant HBM stream): algorithmic 28 B per output pixel x pixels per launch /
                  average launch time from HIP events on the launch stream
+  config.rank0_host_ms   (N > 1) host wall-clock per phase of rank 0's step: the gathers and plan+meta are the
+                 replicated/serial part that bounds strong scaling
+With --full only:
+  config.stage_ms gray / dis / fit and config.dis_ms: three + one extra passes after the timed steps with events around
+                 every stage (a plain run's stage_ms holds the warp alone, from the timed steps)
   cpu_baseline   (N = 1 only) decided at run time: if `import cv2` works, the reference's own OpenCV calls with its
                  arguments timed on this host (kind "opencv", cv2 version / threads / IPP stated) plus a `cv2_parity` object
                  (HIP vs cv2: gray levels, flow EPE, matrices, pixels under both sub-pixel conventions, masks) and the port's
@@ -45,8 +61,6 @@ Also on the JSON line (rank 0):
                  8-bit video holds (such chunks cross PCIe as bytes)
   motion_apply   Motion Apply rates for C3 (1080p, bicubic, blur 0.5, S=17) and C5's per-GPU share (4K, bilinear,
                  blur 0.5, S=33), device-resident (N = 1 only; measured outside the timed loop)
-  config.rank0_host_ms   (N > 1) host wall-clock per phase of rank 0's step: the gathers and plan+meta are the
-                 replicated/serial part that bounds strong scaling
 """
 
 from __future__ import annotations
@@ -410,6 +424,64 @@ def warp_traffic_record(frames: int, w: int, h: int):
                                             f"sources sha256 {have[:12]} -- on this workload; static, not collected in this run)")
 
 
+DUMP_SAMPLE_PIXELS = 1 << 21   # output pixel positions drawn for --dump-outputs: <= 24 MB of frames + 8 MB of masks
+DUMP_SEED = 4242
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def meta_arrays(meta) -> dict:
+    """The numeric arrays of a Flow / Motion Apply meta by name, float64 (keys the meta does not have are left out)."""
+    out = {}
+    if not meta:
+        return out
+    em = meta.get("estimated_motion") or {}
+    per = em.get("per_transition") or []
+    if per:
+        out["transition_matrices"] = np.array([t["matrix"] for t in per], np.float64)
+        out["transition_confidences"] = np.array([t["confidence"] for t in per], np.float64)
+        if all("residual" in t for t in per):
+            out["transition_residuals"] = np.array([t["residual"] for t in per], np.float64)
+    for key in ("path", "target_path", "target_path_effective"):
+        if em.get(key) is not None:
+            out[key] = np.asarray(em[key], np.float64)
+    per_frame = (meta.get("stabilization_warp") or {}).get("per_frame") or []
+    if per_frame:
+        out["applied_matrices"] = np.array([e["applied_matrix"] for e in per_frame], np.float64)
+    motion = (meta.get("motion_meta") or {}).get("per_frame") or []
+    if motion:
+        out["motion_meta_matrices"] = np.array([e["matrix"] for e in motion], np.float64)
+    if meta.get("padding_fraction_mean") is not None:
+        out["padding_fraction"] = np.array([meta["padding_fraction_mean"], meta["padding_fraction_max"]], np.float64)
+    return out
+
+
+def dump_outputs(out_dir, frames, masks, meta) -> dict:
+    """--dump-outputs: one step's outputs as DIR/<name>.npy.  `frames` [S, C] float32 and `masks` [S, 1] float32 hold the
+    output pixels at S = DUMP_SAMPLE_PIXELS positions (frame, y, x) drawn from the whole output clip without repeats by a
+    fixed seed, in raster order (every pixel of a smaller clip), so the same output shape gives the same positions;
+    the meta's arrays follow (meta_arrays).  Returns {name: bytes}."""
+    import torch
+
+    n, h, w = (int(v) for v in frames.shape[:3])
+    total = n * h * w
+    if total <= DUMP_SAMPLE_PIXELS:
+        flat = np.arange(total, dtype=np.int64)
+    else:
+        flat = np.sort(np.random.default_rng(DUMP_SEED).choice(total, DUMP_SAMPLE_PIXELS, replace=False, shuffle=False))
+    idx = [torch.from_numpy(np.ascontiguousarray(a)).to(frames.device) for a in np.unravel_index(flat, (n, h, w))]
+    arrays = {"frames": frames[idx[0], idx[1], idx[2]].reshape(flat.size, -1).float().cpu().numpy(),
+              "masks": masks[idx[0], idx[1], idx[2]].reshape(flat.size, -1).float().cpu().numpy(),
+              **meta_arrays(meta)}
+    size = sum(a.nbytes for a in arrays.values())
+    if size > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {size} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+    return {name: int(a.nbytes) for name, a in arrays.items()}
+
+
 def launch_children(args, argv) -> int:
     """--gpus N > 1 without a torchrun environment: run the ranks as children of this (GPU-free) process."""
     import socket
@@ -531,14 +603,16 @@ CHAINS = {
 }
 
 
-def run_c5(ctx, torch, dist, device, rank, world, use_dist, total, h, w, steps, warmup, chain: str = "c5") -> dict:
+def run_c5(ctx, torch, dist, device, rank, world, use_dist, total, h, w, steps, warmup, chain: str = "c5",
+           dump_dir=None) -> dict:
     """A Flow -> Motion Apply chain as ONE timed step.  chain "c5" = BASELINE configs[4]: Flow (DIS, similarity) with expand
     framing, then Motion Apply (expand, bilinear, motion_blur 0.5, Ultra = 33 samples); chain "c3" = BASELINE configs[2]:
     Flow perspective + crop_and_pad, then Motion Apply (crop_and_pad, bicubic, motion_blur 0.5, High = 17 samples) -- on the
     ORIGINAL frames with the returned meta (call shapes: video_stabilizer_flow.py:734-763,
     video_stabilizer_motion_apply.py:86-129), one `total`-frame clip sharded contiguously over the ranks.  The Flow half
     has the one all-gather of fit records (+ the pad counts); the replay half has no collective (distributed.py).
-    Timed like the headline: barrier + synchronize on both sides, MAX over ranks."""
+    Timed like the headline: barrier + synchronize on both sides, MAX over ranks.  dump_dir: rank 0 writes the last timed
+    step's Motion Apply outputs there after the timing (dump_outputs)."""
     C5_FLOW_ARGS, C5_APPLY, tag, what = CHAINS[chain]   # (shadows the module constants: the body below is the same for both)
     from vstab_amd import apply_pipeline as ap
     from vstab_amd import distributed as vd
@@ -613,16 +687,20 @@ def run_c5(ctx, torch, dist, device, rank, world, use_dist, total, h, w, steps, 
     plan_seen.clear()
     lap["flow"] = lap["apply"] = 0.0
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for i in range(steps):
         out = step()
         shape, ameta = list(out[0].shape), out[2]
-        del out
+        if i + 1 < steps:   # the last step's outputs are kept for --dump-outputs
+            del out
     fence()
     elapsed = time.perf_counter() - t0
     if use_dist:
         t = torch.tensor([elapsed], device=device if dist.get_backend() == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, *out)
+    del out
     stage_ms = {}
     for kind in ("gray", "dis", "fit", "warp", "warp_blur"):
         total_ms, launches = ctx.kernel_ms_stats(kind)
@@ -666,7 +744,16 @@ def main() -> int:
                      help="N > 1 ranks that all use cuda:0 with a gloo control plane (RCCL refuses two ranks on a device): runs the "
                           "multi-rank bench code on a one-GPU box; the numbers mean nothing, the line says so")
     ap_.add_argument("--no-checks", action="store_true", help="skip accuracy / batch_invariance / parity_at_size (profiling runs: keeps the timed steps last in a trace)")
+    ap_.add_argument("--full", action="store_true",
+                     help="also run what the headline figure does not need, outside the timed steps: the per-stage passes (stage_ms gray / "
+                          "dis / fit, dis_ms), the CPU baselines, accuracy / batch_invariance / parity_at_size, host_roundtrip, motion_apply "
+                          "(N = 1) and the c4 / c5 objects (N > 1, --force-dist); --no-extras / --no-checks / --cpu-frames trim them")
+    ap_.add_argument("--dump-outputs", metavar="DIR", default=None,
+                     help="after the timed steps, write what the last timed step returned to DIR/<name>.npy (float32 / float64, "
+                          "a seeded sample of the output pixels plus the meta's arrays; rank 0's shard when N > 1)")
     args = ap_.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap_.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_children(args, sys.argv[1:])
@@ -724,7 +811,8 @@ def main() -> int:
             h, w = args.height or 1080, args.width or 1920
             total5 = args.total_frames or 256
             metric = "stabilized + motion-blurred frames/sec (1080p, Flow perspective -> Motion Apply bicubic High; BASELINE configs[2])"
-        c5 = run_c5(ctx, torch, dist, device, rank, world, use_dist, total5, h, w, args.steps, args.warmup, chain=args.workload)
+        c5 = run_c5(ctx, torch, dist, device, rank, world, use_dist, total5, h, w, args.steps, args.warmup, chain=args.workload,
+                    dump_dir=args.dump_outputs)
         if rank == 0:
             line = {"metric": metric,
                     "value": c5["value"], "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -750,9 +838,11 @@ def main() -> int:
         # fixed) is timed after it and rides on the same line as the `c4` object.
         total, scaling, label = 256 * world, "weak", f"C2-sized shard per GPU: one {256 * world}-frame clip"
 
-    def time_flow(total_frames: int, steps: int, warmup: int) -> dict:
+    def time_flow(total_frames: int, steps: int, warmup: int, stage_passes: bool, dump_dir=None) -> dict:
         """warmup + `steps` timed Flow steps on this rank's shard of one `total_frames`-frame clip, between fences;
-        max over ranks.  The shard's frames stay allocated in the result (the one-GPU extras re-use them)."""
+        max over ranks.  The shard's frames stay allocated in the result (the one-GPU extras re-use them).
+        stage_passes: the extra passes for stage_ms gray / dis / fit and dis_ms after the timed steps (--full).
+        dump_dir: rank 0 writes the last timed step's outputs there after the timing (dump_outputs)."""
         start, end = vd.shard_range(total_frames, world, rank)
         n_local = end - start
         halo = 1 if (rank > 0 and n_local > 0) else 0
@@ -796,16 +886,20 @@ def main() -> int:
         plan_log.update(steps=0, used=0, mismatched_frames=0)
         meta = None
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for i in range(steps):
             out = step()
             meta = out[2]
-            del out
+            if i + 1 < steps:   # the last step's outputs are kept for --dump-outputs
+                del out
         fence()
         elapsed = time.perf_counter() - t0
         if use_dist:
             t = torch.tensor([elapsed], device=device if dist.get_backend() == "nccl" else "cpu", dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
+        if dump_dir is not None and rank == 0:
+            dump_outputs(dump_dir, *out)
+        del out
         # HIP events recorded by the library on the launch stream around every call; summed without host
         # synchronisation inside the timed loop, read here after the closing fence
         warp_total_ms, warp_launches = ctx.kernel_ms_stats("warp")
@@ -817,22 +911,24 @@ def main() -> int:
                              dtype=torch.int64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             device_plan["mismatched_frames_max_per_step"] = int(t.item())
-        # where DIS goes (HIP events around its stages; collected in ONE extra pass outside the timed region: the events
-        # sit between dependent kernels of the coarse-to-fine chain, where they would lengthen the timed steps)
-        ctx.set_timing(True)
-        for _ in range(3):   # gray / DIS / fit: HIP events around every stage, three passes outside the timed region
+        dis_ms = None
+        if stage_passes:
+            # where DIS goes (HIP events around its stages; collected in ONE extra pass outside the timed region: the events
+            # sit between dependent kernels of the coarse-to-fine chain, where they would lengthen the timed steps)
+            ctx.set_timing(True)
+            for _ in range(3):   # gray / DIS / fit: HIP events around every stage, three passes outside the timed region
+                out = step()
+                del out
+            torch.cuda.synchronize()
+            for kind in ("gray", "dis", "fit"):
+                total_ms, launches = ctx.kernel_ms_stats(kind)
+                stage_ms[kind] = total_ms / max(launches, 1)
+            ctx.set_timing(True, detail=True)
             out = step()
             del out
-        torch.cuda.synchronize()
-        for kind in ("gray", "dis", "fit"):
-            total_ms, launches = ctx.kernel_ms_stats(kind)
-            stage_ms[kind] = total_ms / max(launches, 1)
-        ctx.set_timing(True, detail=True)
-        out = step()
-        del out
-        torch.cuda.synchronize()
-        dis_ms = ctx.dis_stage_ms()
-        ctx.set_timing(True)
+            torch.cuda.synchronize()
+            dis_ms = ctx.dis_stage_ms()
+            ctx.set_timing(True)
         return {"elapsed": elapsed, "n_local": n_local, "frames": frames, "meta": meta, "step": step, "stage_ms": stage_ms,
                 "host_ms": {k: round(v / steps, 3) for k, v in stats.items() if isinstance(v, (int, float))},
                 "device_plan": device_plan, "dis_ms": dis_ms}
@@ -849,7 +945,7 @@ def main() -> int:
                 "source": f"profiles/{refs[-1].name} (static: `bench.py --gpus 1 --total-frames {total_frames}` on one MI355X, "
                           "not measured in this run)"}
 
-    run = time_flow(total, args.steps, args.warmup)
+    run = time_flow(total, args.steps, args.warmup, args.full, dump_dir=args.dump_outputs)
     elapsed, n_local, frames, meta, step, stage_ms = (run[k] for k in ("elapsed", "n_local", "frames", "meta", "step", "stage_ms"))
     del run["frames"], run["step"]   # `frames` and `step` (whose closure holds the clip) are the only references left
 
@@ -869,7 +965,8 @@ def main() -> int:
             "total_frames": total,
             "sharding": "single GPU" if world == 1 else f"contiguous frame shards x{world}, 1-frame halo, RCCL all-gather of fit records",
             "stage_ms": {k: round(float(v), 3) for k, v in stage_ms.items()},
-            "stage_ms_note": "warp: HIP events inside the timed steps; gray / dis / fit: three extra passes after them (events cost stream time)",
+            "stage_ms_note": "warp: HIP events inside the timed steps; gray / dis / fit and dis_ms (--full only): three + one extra passes "
+                             "after them (events cost stream time)",
             "dis_ms": run["dis_ms"],
             "device_plan": run["device_plan"],
         }
@@ -915,7 +1012,7 @@ def main() -> int:
                                          "time is a mixed average, no roofline figure is derived from it")
         if world > 1:
             line["scaling"] = scaling      # means nothing on a one-GPU line
-        if world == 1 and not use_dist:
+        if args.full and world == 1 and not use_dist:
             cam = camera_matrices(n_local, 0, w, h)
             work = hm._working_estimation_size(w, h)
             checks = not args.no_checks
@@ -980,14 +1077,14 @@ def main() -> int:
                 except Exception as exc:  # the headline line must survive a failure of the extras
                     line["extras_error"] = f"{type(exc).__name__}: {exc}"
     c4 = c5 = None
-    if use_dist and not args.no_extras:
+    if args.full and use_dist and not args.no_extras:
         # BASELINE configs[3] and configs[4] on the same ranks, outside the timed loop above (every rank takes part: both
         # have collectives).  `--gpus 1 --force-dist` rehearses exactly this path on one GPU's share of the clips.
         del frames, step
         torch.cuda.empty_cache()
         if world > 1 and args.frames is None and args.total_frames is None:
             try:
-                c4_run = time_flow(1024, args.steps, max(1, args.warmup))
+                c4_run = time_flow(1024, args.steps, max(1, args.warmup), True)
                 c4 = {"workload": f"C4: one 1024-frame clip, {w}x{h}, Flow similarity + crop_and_pad, sharded over {world} GPUs "
                                   "(BASELINE configs[3]; total work fixed)",
                       "scaling": "strong", "value": round(1024 * args.steps / c4_run["elapsed"], 2), "unit": "frames/s",

@@ -363,6 +363,43 @@ def test_bench_multi_gpu_launcher_spawns_children_not_exec(monkeypatch, tmp_path
     assert "os.exec" not in src and "execv" not in src
 
 
+def test_bench_dump_outputs_writes_a_seeded_float_sample(tmp_path):
+    """bench.dump_outputs (`--dump-outputs DIR`): frames / masks at a fixed sample of output pixel positions plus the meta's
+    arrays, float32 / float64 only, within 64 MB; the same output shape gives the same positions, so two runs compare file
+    by file.  Pixel values here encode their own position, which pins that frames and masks were read at the same places."""
+    import torch
+
+    import bench
+
+    n, h, w = 3, 1100, 1000   # 3.3 M pixels > DUMP_SAMPLE_PIXELS: sampled
+    frames = torch.arange(n * h * w * 3, dtype=torch.float32).reshape(n, h, w, 3)   # < 2^24: exact in float32
+    masks = (torch.arange(n * h * w) % 7 == 0).float().reshape(n, h, w, 1)
+    path = [[0.5 * i, 0.0, 0.0, 1.0] for i in range(n)]
+    meta = {"estimated_motion": {"per_transition": [{"index": i, "mode": "similarity", "confidence": 0.5, "residual": 0.1 * i,
+                                                     "matrix": np.eye(3).tolist()} for i in range(n - 1)],
+                                 "path": path, "target_path": path, "target_path_effective": path},
+            "stabilization_warp": {"per_frame": [{"index": i, "applied_matrix": np.eye(3).tolist()} for i in range(n)]},
+            "motion_meta": {"per_frame": [{"index": i, "matrix": np.eye(3).tolist()} for i in range(n)]},
+            "padding_fraction_mean": 0.25, "padding_fraction_max": 0.5}
+    sizes = bench.dump_outputs(tmp_path / "a", frames, masks, meta)
+    bench.dump_outputs(tmp_path / "b", frames, masks, meta)
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    assert set(got) == set(sizes) == {"frames", "masks", "transition_matrices", "transition_confidences", "transition_residuals",
+                                      "path", "target_path", "target_path_effective", "applied_matrices", "motion_meta_matrices",
+                                      "padding_fraction"}
+    for name, arr in got.items():
+        assert arr.dtype in (np.float32, np.float64), name
+        assert np.array_equal(arr, np.load(tmp_path / "b" / f"{name}.npy")), name
+    assert sum(sizes.values()) <= 64 << 20
+    f = got["frames"]
+    assert f.shape == (bench.DUMP_SAMPLE_PIXELS, 3)
+    pos = f[:, 0].astype(np.int64) // 3
+    assert np.all(np.diff(pos) > 0) and np.array_equal(f[:, 2] - f[:, 0], np.full(len(pos), 2.0, np.float32))
+    assert got["masks"].shape == (len(pos), 1) and np.array_equal(got["masks"][:, 0], (pos % 7 == 0).astype(np.float32))
+    assert got["transition_matrices"].shape == (n - 1, 3, 3) and got["applied_matrices"].shape == (n, 3, 3)
+    assert got["padding_fraction"].tolist() == [0.25, 0.5]
+
+
 def test_one_hip_runtime_in_the_process(pkg):
     """libvstab.so and torch must share ONE libamdhip64: torch's wheel bundles its own copy under the same SONAME, and
     whichever is loaded first wins.  If libvstab came first (e.g. build() followed by smoke() in one process), torch would

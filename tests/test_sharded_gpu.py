@@ -319,13 +319,13 @@ def test_c4_sized_clip_two_ranks_equal_single_process(pkg, ctx, tmp_path):
 
 
 def test_bench_default_multi_rank_line_rehearsed_on_one_gpu():
-    """`bench.py --gpus 2` as the driver's scaling run starts it, except that both ranks share this box's GPU (gloo control plane,
-    `--rehearse-on-one-gpu`): the child launcher, the default workload (the metric's 256 frames per GPU as one 512-frame clip, weak
-    scaling), the `c4` object (BASELINE configs[3], strong scaling, with the same clip's one-GPU record) and the `c5` object all
+    """`bench.py --gpus 2 --full` as the driver's scaling run starts it, except that both ranks share this box's GPU (gloo control
+    plane, `--rehearse-on-one-gpu`): the child launcher, the default workload (the metric's 256 frames per GPU as one 512-frame clip,
+    weak scaling), the `c4` object (BASELINE configs[3], strong scaling, with the same clip's one-GPU record) and the `c5` object all
     have to produce their part of the ONE JSON line.  The numbers mean nothing here; the structure is what a multi-GPU run prints."""
     root = ROOT
     proc = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu", "--steps", "1", "--warmup", "1",
-                           "--c5-frames", "4"], capture_output=True, text=True, timeout=600, cwd=str(root))
+                           "--c5-frames", "4", "--full"], capture_output=True, text=True, timeout=600, cwd=str(root))
     assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-4000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, proc.stdout[-2000:]
@@ -339,6 +339,37 @@ def test_bench_default_multi_rank_line_rehearsed_on_one_gpu():
     assert c4["same_clip_on_one_gpu"]["ms_per_step"] > 0 and "rank0_host_ms" in c4
     c5 = line["c5"]
     assert "error" not in c5 and c5["total_frames"] == 4 and c5["n_gpus"] == 2 and c5["value"] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` run (no --full) prints the headline line without the extras, and `--dump-outputs DIR`
+    writes what its last timed step returned as float32 / float64 .npy files within 64 MB; two runs with the same arguments
+    write the same values (the clip is synthesised from fixed seeds and the path is deterministic)."""
+    dumps = []
+    for k in range(2):
+        out_dir = tmp_path / f"run{k}"
+        proc = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--frames", "8",
+                               "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=300, cwd=str(ROOT))
+        assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-4000:]
+        lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, proc.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["metric"] == "stabilized frames/sec (1080p, similarity mode)" and line["unit"] == "frames/s"
+        assert line["higher_is_better"] is True and line["dtype"] == "f32" and line["steps"] == 2
+        assert line["value"] > 0 and abs(line["value"] - 8 / (line["ms_per_step"] * 1e-3)) <= 0.01 * line["value"]
+        for key in ("cpu_baseline", "accuracy", "batch_invariance", "parity_at_size", "host_roundtrip", "motion_apply", "c4", "c5"):
+            assert key not in line, key
+        assert set(line["config"]["stage_ms"]) == {"warp"} and line["config"]["dis_ms"] is None
+        files = sorted(out_dir.glob("*.npy"))
+        assert sum(p.stat().st_size for p in files) <= 64 << 20
+        arrays = {p.stem: np.load(p) for p in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert arrays["frames"].shape[1] == 3 and arrays["masks"].shape == (arrays["frames"].shape[0], 1)
+        assert arrays["transition_matrices"].shape == (7, 3, 3) and arrays["applied_matrices"].shape == (8, 3, 3)
+        dumps.append(arrays)
+    assert set(dumps[0]) == set(dumps[1])
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
 
 
 def _failing_worker(rank, world, port, out_dir, where, form):

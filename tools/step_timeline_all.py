@@ -1,6 +1,6 @@
 """Everything the GPU did in the LAST bench step, in time order: every kernel (the library's, torch's, the runtime's fill /
 copy kernels; memory copies too if the trace has them -- rocprofv3's --memory-copy-trace crashed on this pool), with the idle time before each -- from a rocprofv3 trace taken with
-    rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --steps 5 --warmup 2 --no-extras --no-checks --cpu-frames 0
+    rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --steps 5 --warmup 2 --full --no-extras --no-checks --cpu-frames 0
     python3 tools/step_timeline_all.py DIR"""
 import csv, glob, sys
 d = sys.argv[1]
@@ -15,7 +15,7 @@ for f in glob.glob(f'{d}/**/*_memory_copy_trace.csv', recursive=True):
 ev.sort()
 starts = [i for i, e in enumerate(ev) if e[2] == 'K' and 'gray_area' in e[3]]
 last_warp = max(i for i, e in enumerate(ev) if e[2] == 'K' and e[3].startswith('warp_kernel'))
-# bench.py runs four more passes after its timed steps (three with every stage's events, one with the DIS detail events): the
+# bench.py --full runs four more passes after its timed steps (three with every stage's events, one with the DIS detail events): the
 # last TIMED step is the fifth from the end (argv[2] = how many steps to go back; 0 = the very last one)
 back = int(sys.argv[2]) if len(sys.argv) > 2 else 4
 first = starts[-1 - back]

@@ -36,8 +36,8 @@ c3, c5m = ma["c3_1080p_bicubic_blur0.5_S17"], ma["c5_4k_expand_bilinear_blur0.5_
 st, cb, rf = j["config"]["stage_ms"], j["cpu_baseline"], j["roofline"]
 (P / f"{TAG}_bench_c2.md").write_text(f"""# C2 bench line and kernel times, {TAG} final build
 
-Command (one MI355X box, `tools/final_profiles.sh {TAG}`): `python bench.py --steps 20 --warmup 5` -> `profiles/{TAG}_bench_c2.log`;
-`rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-extras --no-checks
+Command (one MI355X box, `tools/final_profiles.sh {TAG}`): `python bench.py --steps 20 --warmup 5 --full` -> `profiles/{TAG}_bench_c2.log`;
+`rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 20 --warmup 5 --full --no-extras --no-checks
 --cpu-frames 0` -> `profiles/{TAG}_bench_c2_kernel_stats.csv` ({steps} steps incl. warm-up).
 
 **{j["value"]:.0f} frames/s, {j["ms_per_step"]} ms per 256-frame 1080p clip** (round 4's driver line: 34 499 / 7.421 ms; the boxes of the pool
@@ -48,7 +48,7 @@ Device plan in the timed steps: {j["config"]["device_plan"]}.  Roofline of the w
 {rf["achieved"]} GB/s = **{rf["frac"]} of 8 TB/s** on this box; PMC traffic per launch `profiles/warp_traffic.json` (FETCH_SIZE x 2 + WRITE_SIZE,
 re-collected on this round's final warp sources, hash-tied): {TRAFFIC}.
 
-Round-4 tree and this tree on the same box, interleaved (`bench.py --steps 20 --warmup 5 --no-extras --no-checks --cpu-frames 0`; value, ms per
+Round-4 tree and this tree on the same box, interleaved (`bench.py --steps 20 --warmup 5 --full --no-extras --no-checks --cpu-frames 0`; value, ms per
 step, stage ms):
 
 ```
@@ -121,7 +121,7 @@ em = (G / f"{TAG}_emulate_c4.log").read_text().strip()
 dev = {int(m.group(1)): float(m.group(2)) for m in re.finditer(r"world (\d+) \(device plan\): ([0-9.]+) ms/step", em)}
 hostp = {int(m.group(1)): float(m.group(2)) for m in re.finditer(r"world (\d+): ([0-9.]+) ms/step", em)}
 one = c4["ms_per_step"]
-json.dump({"command": "python bench.py --gpus 1 --total-frames 1024 --steps 10 --warmup 3 --no-extras --no-checks --cpu-frames 0",
+json.dump({"command": "python bench.py --gpus 1 --total-frames 1024 --steps 10 --warmup 3 --full --no-extras --no-checks --cpu-frames 0",
            "total_frames": 1024, "size": [1920, 1080], "frames_per_s": c4["value"], "ms_per_step": one, "stage_ms": c4["config"]["stage_ms"],
            "note": "the C4 clip (BASELINE configs[3]) on ONE MI355X, device-resident: the denominator of the strong-scaling ratio",
            "source": f"{TAG} final build, tools/final_profiles.sh {TAG}"}, open(P / f"{TAG}_c4_single_gpu.json", "w"), indent=1)
