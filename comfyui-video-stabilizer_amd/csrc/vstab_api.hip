@@ -96,6 +96,9 @@ int vstab_check_device_status(vstab_ctx* ctx, const char* who)
     return 3;
 }
 
+// vstab_tvl1.hip: frees the TV-L1 workspace and host mirror of a context
+void vstab_tvl1_release(vstab_ctx* ctx);
+
 extern "C" {
 
 int vstab_abi_version(void) { return VSTAB_ABI_VERSION; }
@@ -148,6 +151,7 @@ int vstab_destroy(vstab_ctx* ctx)
     ctx->h_params.release();
     ctx->d_params.release();
     ctx->d_dis.release();
+    vstab_tvl1_release(ctx);
     ctx->d_fit.release();
     ctx->h_fit.release();
     ctx->d_gray_tmp.release();

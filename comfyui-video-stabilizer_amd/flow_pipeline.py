@@ -50,8 +50,13 @@ class _gc_paused:
 # "flow_phase_correlate" is the Flow node running on its fallback estimator (flow.py:90-130).  The reference takes
 # that branch when cv2.DISOpticalFlow cannot be created and cv2.optflow (TV-L1, contrib) is missing; here DIS
 # always exists, so the branch is selected only by VSTAB_FLOW_BACKEND=phase_correlate (see resolve_flow_backend).
-_META_SOURCE = {"flow": "estimated_flow", "flow_phase_correlate": "estimated_flow", "classic": "estimated_classic"}
+#
+# "flow_tvl1" is the Flow node on its second dense backend, cv2.optflow.DualTVL1OpticalFlow (flow.py:76-80), which the
+# reference picks when DIS cannot be created; here it is chosen by the caller (_stabilize_frames(estimator="flow_tvl1")).
+_META_SOURCE = {"flow": "estimated_flow", "flow_phase_correlate": "estimated_flow", "flow_tvl1": "estimated_flow",
+                "classic": "estimated_classic"}
 _PHASE_REASON = "DIS unavailable (disabled by VSTAB_FLOW_BACKEND); cv2.optflow missing; using phase correlation."
+_TVL1_REASON = "DIS unavailable (disabled by the caller); using TV-L1."
 
 
 def resolve_flow_backend(estimator: str) -> str:
@@ -72,6 +77,8 @@ def _backend_fields(estimator: str) -> Dict[str, Any]:
         return {"flow_backend": "DIS", "flow_fallback_reason": None}
     if estimator == "flow_phase_correlate":
         return {"flow_backend": "phase_correlate", "flow_fallback_reason": _PHASE_REASON}
+    if estimator == "flow_tvl1":
+        return {"flow_backend": "TVL1", "flow_fallback_reason": _TVL1_REASON}
     return {}
 
 
@@ -171,7 +178,16 @@ def estimate_transitions_phase(ctx, device_frames, working_size, transform_mode:
     return table
 
 
-_ESTIMATORS = {}   # filled below the three estimator functions
+def estimate_transitions_tvl1(ctx, device_frames, working_size, transform_mode: str, clip_start: bool = True, peaks_out=None):
+    """Second dense estimator (flow.py:76-80, 140-147): Dual TV-L1 flow with OpenCV's default parameters on the
+    estimation images, sampled and fitted exactly as the DIS flow is.  Pairs are independent (no initial flow), so
+    clip_start does not matter."""
+    gray = _gray(ctx, device_frames, working_size, peaks_out)
+    _, grid, _ = ctx.tvl1_flow_batch(gray, sample_step=SAMPLE_STEP, want_full=False, want_grid=True)
+    return ctx.sample_fit_batch(grid, SAMPLE_STEP, transform_mode)
+
+
+_ESTIMATORS = {}   # filled below the four estimator functions
 
 
 # classic.py:76-96: cv2.goodFeaturesToTrack / cv2.calcOpticalFlowPyrLK arguments of the Classic node
@@ -189,7 +205,7 @@ def estimate_transitions_classic(ctx, device_frames, working_size, transform_mod
 
 
 _ESTIMATORS.update({"flow": estimate_transitions, "flow_phase_correlate": estimate_transitions_phase,
-                    "classic": estimate_transitions_classic})
+                    "flow_tvl1": estimate_transitions_tvl1, "classic": estimate_transitions_classic})
 
 
 def _fps_fields(context: hm.VideoContext, frame_rate) -> Tuple[float, Optional[float]]:

@@ -42,6 +42,27 @@ class FitRecord(C.Structure):
     ]
 
 
+class Tvl1Params(C.Structure):
+    """vstab_tvl1_params (include/vstab.h): cv2.optflow.DualTVL1OpticalFlow's parameters."""
+    _fields_ = [
+        ("tau", C.c_double), ("lambda_", C.c_double), ("theta", C.c_double), ("epsilon", C.c_double),
+        ("scale_step", C.c_double), ("gamma", C.c_double),
+        ("nscales", C.c_int), ("warps", C.c_int), ("inner_iterations", C.c_int), ("outer_iterations", C.c_int),
+        ("median_filtering", C.c_int), ("use_initial_flow", C.c_int), ("chunk_pairs", C.c_int), ("poll_interval", C.c_int),
+    ]
+
+
+def tvl1_params(**overrides) -> Tvl1Params:
+    """The library's defaults (OpenCV's DualTVL1OpticalFlow_create()) with `overrides` applied; `lambda_` is lambda."""
+    prm = Tvl1Params()
+    load_library().vstab_tvl1_default_params(C.byref(prm))
+    for key, value in overrides.items():
+        if key not in dict(Tvl1Params._fields_):
+            raise ValueError(f"unknown TV-L1 parameter {key!r}")
+        setattr(prm, key, value)
+    return prm
+
+
 # numpy view of vstab_fit_record (include/vstab.h): same layout as the ctypes structure above
 FIT_DTYPE = np.dtype({
     "names": ["matrix", "confidence", "residual", "accepted", "computed", "valid_points", "total_points"],
@@ -164,6 +185,9 @@ _SIGNATURES = {
         C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vstab_phase_correlate_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vstab_tvl1_default_params": (None, [C.c_void_p]),
+    "vstab_tvl1_flow_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "vstab_host_math": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "vstab_transitions_to_params": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vstab_params_to_matrices": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -578,6 +602,41 @@ class Context:
             "vstab_dis_flow_batch",
         )
         return flow, grid
+
+    def tvl1_flow_batch(self, gray, params=None, sample_step=8, want_full=False, want_grid=True, want_iterations=False):
+        """Dual TV-L1 flow of every consecutive pair: gray u8 [N,h,w] (device) -> (flow [N-1,h,w,2] | None,
+        grid_flow [N-1,gh,gw,2] | None, iterations int32 [N-1,nscales,warps] | None).  params: a Tvl1Params, a dict of
+        overrides of the defaults, or None (OpenCV's defaults)."""
+        torch = self.torch
+        if gray.device != self.device:
+            gray = gray.to(self.device)
+        gray = gray.contiguous()
+        if gray.dtype != torch.uint8 or gray.dim() != 3:
+            raise ValueError("tvl1_flow_batch expects a uint8 [N,h,w] tensor")
+        n, h, w = gray.shape
+        if n < 2:
+            raise ValueError("tvl1_flow_batch needs at least two frames")
+        if params is None:
+            prm = tvl1_params()
+        elif isinstance(params, Tvl1Params):
+            prm = params
+        else:
+            prm = tvl1_params(**params)
+        pairs = n - 1
+        gh, gw = (h + sample_step - 1) // sample_step, (w + sample_step - 1) // sample_step
+        flow = torch.empty((pairs, h, w, 2), dtype=torch.float32, device=self.device) if want_full else None
+        grid = torch.empty((pairs, gh, gw, 2), dtype=torch.float32, device=self.device) if want_grid else None
+        iters = (torch.empty((pairs, max(prm.nscales, 1), max(prm.warps, 1)), dtype=torch.int32, device=self.device)
+                 if want_iterations else None)
+        self.use_torch_stream()
+        _check(
+            self.lib.vstab_tvl1_flow_batch(
+                self.handle, _dev_ptr(gray), n, h, w, C.byref(prm), _dev_ptr(flow) if flow is not None else None,
+                _dev_ptr(grid) if grid is not None else None, int(sample_step), _dev_ptr(iters) if iters is not None else None,
+            ),
+            "vstab_tvl1_flow_batch",
+        )
+        return flow, grid, iters
 
     def sample_fit_batch(self, grid_flow, step, requested_mode):
         """grid_flow [P,gh,gw,2] (device) -> structured table [P,3] (FIT_DTYPE), one row per pair and mode."""

@@ -302,6 +302,35 @@ int vstab_points_fit_batch(vstab_ctx* ctx, const float* point_pairs, const int* 
 int vstab_phase_correlate_batch(vstab_ctx* ctx, const uint8_t* gray, int n, int h, int w,
                                 vstab_fit_record* results, double* shifts);
 
+/* ---- N2 (second dense estimator): Dual TV-L1 optical flow ------------------------------------
+ * Replaces cv2.optflow.DualTVL1OpticalFlow_create() (nodes/video_stabilizer_flow.py:76-80, the backend
+ * _select_flow_backend tries after DIS, :90-107) and its calc(prev, curr, None) in the pair loop (:140) for the
+ * pairs (i, i+1), i in [0, n-1).  Restated from OpenCV 4.x contrib optflow/src/tvl1flow.cpp in
+ * tests/tvl1_restatement.py (unpinned against OpenCV); the HIP kernels follow it bit for bit.  The error sum of
+ * each inner iteration is a stated deviation: a pairwise tree in double over each row, then over the rows.
+ * The fields of vstab_tvl1_params are OpenCV's, with its defaults (vstab_tvl1_default_params):
+ *   tau 0.25, lambda 0.15, theta 0.3, epsilon 0.01, scale_step 0.8, gamma 0, nscales 5, warps 5,
+ *   inner_iterations 30, outer_iterations 10, median_filtering 5, use_initial_flow 0.
+ * gamma != 0 and use_initial_flow != 0 are rejected (the reference uses neither); median_filtering is 1 (off) or 5.
+ * chunk_pairs: pairs per workspace chunk (0: as many as fit ~4 GB; results do not depend on it).
+ * poll_interval: inner launches between two reads of the host-mirrored active count (0: 8).
+ *   gray        dev [n,h,w] u8, 16 <= h, w <= 2048 (the finest level; coarser levels below 16 end the pyramid)
+ *   flow        dev [n-1,h,w,2] f32 or NULL (full field)
+ *   grid_flow   dev [n-1,gh,gw,2] f32 or NULL: the flow at y=0,step,.. x=0,step,.. (as vstab_dis_flow_batch)
+ *   iterations  dev [n-1,nscales,warps] int32 or NULL: inner iterations run at each (scale, warp), scale 0 = finest
+ *               (0 for the scales the pyramid does not reach)
+ * Asynchronous apart from a bounded host wait every poll_interval inner launches.  Timing kind: "tvl1".
+ */
+typedef struct vstab_tvl1_params {
+    double tau, lambda, theta, epsilon, scale_step, gamma;
+    int nscales, warps, inner_iterations, outer_iterations, median_filtering, use_initial_flow;
+    int chunk_pairs, poll_interval;
+} vstab_tvl1_params;
+void vstab_tvl1_default_params(vstab_tvl1_params* params);
+/* params NULL: the defaults */
+int vstab_tvl1_flow_batch(vstab_ctx* ctx, const uint8_t* gray, int n, int h, int w, const vstab_tvl1_params* params,
+                          float* flow, float* grid_flow, int sample_step, int32_t* iterations);
+
 /* ---- F7 + F8: trajectory (prefix sum, box smoothing, strength blend), fp64 ---
  * Replaces nodes/video_stabilizer_flow.py:356-371 and
  * nodes/stabilizer_utils.py:361-383 (_smooth_path: moving average, edge padded,
