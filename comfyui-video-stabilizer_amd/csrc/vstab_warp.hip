@@ -15,6 +15,7 @@
 #include "vstab_internal.h"
 #include <type_traits>
 #include <cstdlib>
+#include <cmath>
 
 namespace {
 
@@ -208,6 +209,86 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned b, unsigned nblk)
     return base + i;
 }
 
+// One transform record in registers, as warp_kernel and temporal_fill_kernel use it for all pixels of a thread.
+template <int INTERP, int SUBPIX>
+struct XformRegs {
+    static constexpr bool EXACT = SUBPIX == VSTAB_SUBPIX_EXACT && INTERP == VSTAB_INTERP_BILINEAR;
+    double m0, m1, m2, m3, m4, m5, m6, m7, m8;
+    float mf[9];      // EXACT only
+    bool affine, fast_ok;
+    __device__ __forceinline__ explicit XformRegs(const WarpXform* __restrict__ xf)
+        : m0(xf->m[0]), m1(xf->m[1]), m2(xf->m[2]), m3(xf->m[3]), m4(xf->m[4]), m5(xf->m[5]), m6(xf->m[6]), m7(xf->m[7]),
+          m8(xf->m[8]), affine(xf->affine != 0)
+    {
+        if (EXACT) {
+#pragma unroll
+            for (int i = 0; i < 9; i++) mf[i] = (float)xf->m[i];
+        }
+        fast_ok = affine && !EXACT;
+    }
+};
+
+// The plain warp's source position of output pixel (x, y) under one transform, and what is sampled there: THE definition
+// of the coordinate arithmetic (f64 row-start terms per OpenCV column block, Q5 rounding or the float32 `exact` chain),
+// shared by warp_kernel and temporal_fill_kernel.  `q5(X, Y)` samples at the 1/32-px coordinates, `exact(fsx, fsy)` at the
+// float32 ones; `c` receives the nearest-neighbour coverage (WITH_MASK only).
+template <int INTERP, int SUBPIX, bool WITH_MASK, class SampleQ5, class SampleExact>
+__device__ __forceinline__ Px warp_pixel(const WarpXform* __restrict__ xf, const XformRegs<INTERP, SUBPIX>& r, int sh, int sw,
+                                         int dw, int bw0, int bw0_pow2, int x, int y, double dy, SampleQ5&& q5,
+                                         SampleExact&& exact, float& c)
+{
+    // OpenCV evaluates the row-start terms X0, Y0, W0 once per 64-wide column block (xb) and adds m * (x - xb)
+    // per pixel; a thread's pixels lie in up to TILE_PX different blocks, so the terms are formed per pixel.
+    int xb;
+    if (bw0 >= dw) xb = 0;
+    else if (bw0_pow2) xb = x & ~(bw0 - 1);
+    else xb = (x / bw0) * bw0;
+    const double dxb = (double)xb;
+    const double X0 = r.m0 * dxb + r.m1 * dy + r.m2;
+    const double Y0 = r.m3 * dxb + r.m4 * dy + r.m5;
+    const double W0 = r.m6 * dxb + r.m7 * dy + r.m8;
+    const double dx1 = (double)(x - xb);
+    const double Xn = X0 + r.m0 * dx1, Yn = Y0 + r.m3 * dx1;
+    Px v;
+    // Fast path (the common case): affine map whose 1/32-px coordinates stay far inside the range where
+    // OpenCV's INT clamp and short saturation are no-ops.
+    const bool small = r.fast_ok && __builtin_fabs(Xn * xf->wq) < 1.0e6 && __builtin_fabs(Yn * xf->wq) < 1.0e6;
+    if (small) {
+        const int X = round_small(Xn * xf->wq), Y = round_small(Yn * xf->wq);
+        v = q5(X, Y);
+        if (WITH_MASK) {
+            const int nx = round_small(Xn * xf->wn), ny = round_small(Yn * xf->wn);
+            c = ((unsigned)nx < (unsigned)sw && (unsigned)ny < (unsigned)sh) ? 1.f : 0.f;
+        }
+    } else {
+        double Wq, Wn;
+        if (r.affine) { Wq = xf->wq; Wn = xf->wn; }
+        else {
+            // one fp64 division serves both: 32/W == 32 * (1/W) bit for bit (scaling a correctly rounded
+            // quotient by a power of two is exact)
+            const double W = W0 + r.m6 * dx1;
+            Wn = (W != 0.0) ? 1.0 / W : 0.0;
+            Wq = 32.0 * Wn;
+        }
+        if (XformRegs<INTERP, SUBPIX>::EXACT) {
+            const float w = x * r.mf[6] + y * r.mf[7] + r.mf[8];
+            const float fsx = (x * r.mf[0] + y * r.mf[1] + r.mf[2]) / w;
+            const float fsy = (x * r.mf[3] + y * r.mf[4] + r.mf[5]) / w;
+            v = exact(fsx, fsy);
+        } else {
+            const int X = clamp_round_i32(Xn * Wq);
+            const int Y = clamp_round_i32(Yn * Wq);
+            v = q5(X, Y);
+        }
+        if (WITH_MASK) {
+            const int nx = sat_short(clamp_round_i32(Xn * Wn));
+            const int ny = sat_short(clamp_round_i32(Yn * Wn));
+            c = ((unsigned)nx < (unsigned)sw && (unsigned)ny < (unsigned)sh) ? 1.f : 0.f;
+        }
+    }
+    return v;
+}
+
 template <int INTERP, int SUBPIX, bool WITH_MASK, int TILE_TX>
 __global__ __launch_bounds__(256) void warp_kernel(WarpArgs a)
 {
@@ -249,70 +330,16 @@ __global__ __launch_bounds__(256) void warp_kernel(WarpArgs a)
 
         for (int k = 0; k < nxf; k++) {
             const WarpXform* __restrict__ xf = a.xf + (size_t)frame * nxf + k;
-            const double m0 = xf->m[0], m1 = xf->m[1], m2 = xf->m[2];
-            const double m3 = xf->m[3], m4 = xf->m[4], m5 = xf->m[5];
-            const double m6 = xf->m[6], m7 = xf->m[7], m8 = xf->m[8];
-            const bool affine = xf->affine != 0;
-            // OpenCV evaluates the row-start terms X0, Y0, W0 once per 64-wide column block (xb) and adds m * (x - xb)
-            // per pixel; a thread's pixels lie in up to TILE_PX different blocks, so the terms are formed per pixel.
-            float mf[9];
-            if (SUBPIX == VSTAB_SUBPIX_EXACT && INTERP == VSTAB_INTERP_BILINEAR) {
-#pragma unroll
-                for (int i = 0; i < 9; i++) mf[i] = (float)xf->m[i];
-            }
-            const bool fast_ok = affine && !(SUBPIX == VSTAB_SUBPIX_EXACT && INTERP == VSTAB_INTERP_BILINEAR);
+            const XformRegs<INTERP, SUBPIX> r(xf);
 #pragma unroll
             for (int p = 0; p < TILE_PX; p++) {
                 if (p >= npx) continue;
                 const int x = x0 + p * TILE_TX;
-                int xb;
-                if (a.bw0 >= a.dw) xb = 0;
-                else if (a.bw0_pow2) xb = x & ~(a.bw0 - 1);
-                else xb = (x / a.bw0) * a.bw0;
-                const double dxb = (double)xb;
-                const double X0 = m0 * dxb + m1 * dy + m2;
-                const double Y0 = m3 * dxb + m4 * dy + m5;
-                const double W0 = m6 * dxb + m7 * dy + m8;
-                const double dx1 = (double)(x - xb);
-                const double Xn = X0 + m0 * dx1, Yn = Y0 + m3 * dx1;
-                Px v;
                 float c = 0.f;
-                // Fast path (the common case): affine map whose 1/32-px coordinates stay far inside the range where
-                // OpenCV's INT clamp and short saturation are no-ops.
-                const bool small = fast_ok && __builtin_fabs(Xn * xf->wq) < 1.0e6 && __builtin_fabs(Yn * xf->wq) < 1.0e6;
-                if (small) {
-                    const int X = round_small(Xn * xf->wq), Y = round_small(Yn * xf->wq);
-                    v = sample_q5<INTERP>(S, a.sh, a.sw, X, Y, a.b0, a.b1, a.b2, cub_tab);
-                    if (WITH_MASK) {
-                        const int nx = round_small(Xn * xf->wn), ny = round_small(Yn * xf->wn);
-                        c = ((unsigned)nx < (unsigned)a.sw && (unsigned)ny < (unsigned)a.sh) ? 1.f : 0.f;
-                    }
-                } else {
-                    double Wq, Wn;
-                    if (affine) { Wq = xf->wq; Wn = xf->wn; }
-                    else {
-                        // one fp64 division serves both: 32/W == 32 * (1/W) bit for bit (scaling a correctly rounded
-                        // quotient by a power of two is exact)
-                        const double W = W0 + m6 * dx1;
-                        Wn = (W != 0.0) ? 1.0 / W : 0.0;
-                        Wq = 32.0 * Wn;
-                    }
-                    if (SUBPIX == VSTAB_SUBPIX_EXACT && INTERP == VSTAB_INTERP_BILINEAR) {
-                        const float w = x * mf[6] + y * mf[7] + mf[8];
-                        const float fsx = (x * mf[0] + y * mf[1] + mf[2]) / w;
-                        const float fsy = (x * mf[3] + y * mf[4] + mf[5]) / w;
-                        v = sample_exact(S, a.sh, a.sw, fsx, fsy, a.b0, a.b1, a.b2);
-                    } else {
-                        const int X = clamp_round_i32(Xn * Wq);
-                        const int Y = clamp_round_i32(Yn * Wq);
-                        v = sample_q5<INTERP>(S, a.sh, a.sw, X, Y, a.b0, a.b1, a.b2, cub_tab);
-                    }
-                    if (WITH_MASK) {
-                        const int nx = sat_short(clamp_round_i32(Xn * Wn));
-                        const int ny = sat_short(clamp_round_i32(Yn * Wn));
-                        c = ((unsigned)nx < (unsigned)a.sw && (unsigned)ny < (unsigned)a.sh) ? 1.f : 0.f;
-                    }
-                }
+                const Px v = warp_pixel<INTERP, SUBPIX, WITH_MASK>(
+                    xf, r, a.sh, a.sw, a.dw, a.bw0, a.bw0_pow2, x, y, dy,
+                    [&](int X, int Y) { return sample_q5<INTERP>(S, a.sh, a.sw, X, Y, a.b0, a.b1, a.b2, cub_tab); },
+                    [&](float fsx, float fsy) { return sample_exact(S, a.sh, a.sw, fsx, fsy, a.b0, a.b1, a.b2); }, c);
                 acc[p][0] = v.r; acc[p][1] = v.g; acc[p][2] = v.b;
                 if (WITH_MASK) cov[p] = c;
             }
@@ -1083,4 +1110,202 @@ extern "C" int vstab_warp_blur_batch(vstab_ctx* ctx, const float* src, int n, in
 {
     return vstab_warp_blur_clip_batch(ctx, src, n, src_h, src_w, matrices, n, 0, ts, samples, out_h, out_w, interp, border_rgb,
                                       subpix, dst, mask);
+}
+
+// ---- temporal fill: padding pixels taken from neighbouring frames ----------------------------------------------------
+//
+// After a warp, an output pixel whose mask is 1 saw no source content in its own frame.  For each such pixel the kernel
+// walks up to K candidate (frame, matrix) pairs in order and takes the first one whose source position -- warp_pixel's,
+// the plain warp's own arithmetic -- has EVERY interpolation tap inside that frame: the value written is then the one
+// vstab_warp_batch would have written for that frame and matrix, and no border colour can enter it.
+//
+// Shape: the warp's 64 x 8 tile and XCD remap.  A tile reads its mask (4 B per pixel); if none of its pixels is padded the
+// block returns -- the common case, so the pass over a mostly covered clip is close to a plain read of the mask.  The
+// candidate records are block-uniform (a `const T* __restrict__` kernel parameter: scalar loads).  A wavefront leaves the
+// candidate loop as soon as none of its pixels is waiting.  Only filled pixels are stored.  dst is read by nobody
+// (candidates sample src), so working in place is free of races.
+namespace {
+
+struct FillCand {
+    WarpXform xf;
+    int frame;     // clip frame the candidate samples, -1: none (out of the clip, cut chain, singular matrix)
+    int pad_;
+};
+
+struct FillArgs {
+    const float* src;
+    float* dst;
+    float* mask;
+    signed char* filled_from;
+    unsigned* fill_count;
+    unsigned* pad_count;
+    int n, K, sh, sw, dh, dw;
+    int bw0, bw0_pow2;
+    int tiles_x, tiles_y;
+};
+
+template <int INTERP, int SUBPIX>
+__global__ __launch_bounds__(256) void temporal_fill_kernel(FillArgs a, const FillCand* __restrict__ cands)
+{
+    constexpr int TILE_TX = 32, TILE_W = TILE_TX * TILE_PX, TILE_H = 256 / TILE_TX;
+    __shared__ unsigned s_cnt[2][4];
+    __shared__ __attribute__((aligned(16))) float s_cub[32 * 4];
+    const unsigned t = xcd_remap(blockIdx.x, gridDim.x);
+    const unsigned tiles_per_frame = (unsigned)a.tiles_x * a.tiles_y;
+    const int frame = t / tiles_per_frame;
+    const unsigned tr = t - frame * tiles_per_frame;
+    const int tile_y = tr / a.tiles_x, tile_x = tr - tile_y * a.tiles_x;
+    const int tx = threadIdx.x % TILE_TX, ty = threadIdx.x / TILE_TX;
+    const int x0 = tile_x * TILE_W + tx;
+    const int y = tile_y * TILE_H + ty;
+    const bool active = (y < a.dh) && (x0 < a.dw);
+    const int npx = active ? (a.dw - x0 + TILE_TX - 1) / TILE_TX : 0;
+
+    float* __restrict__ Mk = a.mask + (size_t)frame * a.dh * a.dw;
+    const unsigned row = (unsigned)y * (unsigned)a.dw;
+    bool need[TILE_PX];
+    bool any = false;
+#pragma unroll
+    for (int p = 0; p < TILE_PX; p++) {
+        need[p] = (p < npx) && Mk[row + (unsigned)(x0 + p * TILE_TX)] == 1.0f;
+        any = any || need[p];
+    }
+    if (!__syncthreads_or(any)) return;   // nothing padded in this tile: nothing to fill, nothing to count
+
+    const float* cub_tab = nullptr;
+    if (INTERP == VSTAB_INTERP_BICUBIC) {
+        if (threadIdx.x < 32) cubic_coeffs((int)threadIdx.x, s_cub + threadIdx.x * 4);
+        __syncthreads();
+        cub_tab = s_cub;
+    }
+
+    float* __restrict__ D = a.dst + (size_t)frame * a.dh * a.dw * 3;
+    signed char* __restrict__ From = a.filled_from ? a.filled_from + (size_t)frame * a.dh * a.dw : nullptr;
+    const size_t src_frame = (size_t)a.sh * a.sw * 3;
+    const double dy = (double)y;
+    unsigned filled = 0;
+    typedef float f3 __attribute__((ext_vector_type(3)));
+
+    for (int k = 0; k < a.K; k++) {
+        if (!__any(any)) break;                       // wave-uniform: no pixel of this wavefront is waiting
+        const FillCand* __restrict__ cd = cands + (size_t)frame * a.K + k;
+        if (cd->frame < 0) continue;                  // block-uniform
+        const float* __restrict__ S = a.src + (size_t)cd->frame * src_frame;
+        const WarpXform* __restrict__ xf = &cd->xf;
+        const XformRegs<INTERP, SUBPIX> r(xf);
+        any = false;
+#pragma unroll
+        for (int p = 0; p < TILE_PX; p++) {
+            if (!need[p]) continue;
+            const int x = x0 + p * TILE_TX;
+            bool valid = false;
+            float c_unused = 0.f;
+            // validity = the samplers' own "all taps inside" branches (sample_q5's interior tests, sample_exact's four
+            // in-range flags): the sample is taken only then, so the border arguments are never read
+            const Px v = warp_pixel<INTERP, SUBPIX, false>(
+                xf, r, a.sh, a.sw, a.dw, a.bw0, a.bw0_pow2, x, y, dy,
+                [&](int X, int Y) {
+                    const int sx = sat_short(X >> 5), sy = sat_short(Y >> 5);
+                    if (INTERP == VSTAB_INTERP_BILINEAR) {
+                        valid = (unsigned)sx < (unsigned)(a.sw - 1) && (unsigned)sy < (unsigned)(a.sh - 1);
+                    } else {
+                        const unsigned width1 = (unsigned)(a.sw - 3 > 0 ? a.sw - 3 : 0);
+                        const unsigned height1 = (unsigned)(a.sh - 3 > 0 ? a.sh - 3 : 0);
+                        valid = (unsigned)(sx - 1) < width1 && (unsigned)(sy - 1) < height1;
+                    }
+                    return valid ? sample_q5<INTERP>(S, a.sh, a.sw, X, Y, 0.f, 0.f, 0.f, cub_tab) : Px{0.f, 0.f, 0.f};
+                },
+                [&](float fsx, float fsy) {
+                    const float flx = __builtin_floorf(fsx), fly = __builtin_floorf(fsy);   // NaN / inf compare false
+                    valid = flx >= 0.f && flx < (float)(a.sw - 1) && fly >= 0.f && fly < (float)(a.sh - 1);
+                    return valid ? sample_exact(S, a.sh, a.sw, fsx, fsy, 0.f, 0.f, 0.f) : Px{0.f, 0.f, 0.f};
+                },
+                c_unused);
+            if (valid) {
+                const unsigned pix = row + (unsigned)x;
+                f3 rgb = {v.r, v.g, v.b};
+                __builtin_memcpy(D + pix * 3u, &rgb, 12);
+                Mk[pix] = 0.f;
+                if (From) From[pix] = (signed char)k;
+                need[p] = false;
+                filled += 1u;
+            }
+            any = any || need[p];
+        }
+    }
+
+    if (a.fill_count != nullptr || a.pad_count != nullptr) {
+        unsigned left = 0;
+#pragma unroll
+        for (int p = 0; p < TILE_PX; p++) left += need[p] ? 1u : 0u;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { filled += __shfl_down(filled, off); left += __shfl_down(left, off); }
+        if ((threadIdx.x & 63) == 0) { s_cnt[0][threadIdx.x >> 6] = filled; s_cnt[1][threadIdx.x >> 6] = left; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const unsigned f = s_cnt[0][0] + s_cnt[0][1] + s_cnt[0][2] + s_cnt[0][3];
+            const unsigned l = s_cnt[1][0] + s_cnt[1][1] + s_cnt[1][2] + s_cnt[1][3];
+            if (f && a.fill_count) atomicAdd(a.fill_count + frame, f);
+            if (l && a.pad_count) atomicAdd(a.pad_count + frame, l);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int vstab_temporal_fill_batch(vstab_ctx* ctx, const float* src, int clip_frames, int src_h, int src_w, int first,
+                                         int n, const float* matrices, const int32_t* cand_frame, int K, int out_h, int out_w,
+                                         int interp, int subpix, float* dst, float* mask, int8_t* filled_from,
+                                         uint32_t* fill_count, uint32_t* pad_count)
+{
+    const char* who = "vstab_temporal_fill_batch";
+    const float no_border[3] = {0.f, 0.f, 0.f};
+    if (int rc = check_common(who, ctx, src, n, src_h, src_w, matrices, out_h, out_w, interp, no_border, subpix, dst)) return rc;
+    VSTAB_REQUIRE(mask != nullptr && cand_frame != nullptr, "%s: NULL pointer argument", who);
+    VSTAB_REQUIRE(K >= 1 && K <= 64, "%s: K=%d outside [1,64]", who, K);
+    VSTAB_REQUIRE(clip_frames > 0 && first >= 0 && first + n <= clip_frames, "%s: frames [%d, %d) outside a clip of %d frames", who,
+                  first, first + n, clip_frames);
+    VSTAB_REQUIRE((const void*)src != (const void*)dst, "%s: dst must not alias src (candidates read src while dst is written)", who);
+    std::vector<FillCand> cd((size_t)n * K);
+    for (size_t i = 0; i < cd.size(); i++) {
+        const int f = cand_frame[i];
+        VSTAB_REQUIRE(f >= -1 && f < clip_frames, "%s: cand_frame[%zu]=%d outside [-1, %d)", who, i, f, clip_frames);
+        const float* m32 = matrices + i * 9;
+        fill_xform(m32, &cd[i].xf);
+        // a matrix that cv::invert would refuse (zero or non-finite determinant) has no source position: no candidate
+        double M[9], inv[9];
+        bool finite = true;
+        for (int j = 0; j < 9; j++) { M[j] = (double)m32[j]; finite = finite && std::isfinite(M[j]); }
+        bool ok = f >= 0 && finite && vstab_invert3x3_hd(M, inv);
+        for (int j = 0; ok && j < 9; j++) ok = std::isfinite(inv[j]);
+        cd[i].frame = ok ? f : -1;
+        cd[i].pad_ = 0;
+    }
+    VSTAB_HIP(hipSetDevice(ctx->device));
+    void* d_cd = nullptr;
+    if (vstab_stage_params(ctx, cd.data(), cd.size() * sizeof(FillCand), &d_cd)) return 1;
+
+    WarpArgs g{};
+    fill_geometry(g, n, src_h, src_w, out_h, out_w, no_border, dst, mask);
+    FillArgs a{};
+    a.src = src; a.dst = dst; a.mask = mask; a.filled_from = reinterpret_cast<signed char*>(filled_from);
+    a.fill_count = fill_count; a.pad_count = pad_count;
+    a.n = n; a.K = K; a.sh = src_h; a.sw = src_w; a.dh = out_h; a.dw = out_w;
+    a.bw0 = g.bw0; a.bw0_pow2 = g.bw0_pow2;
+    a.tiles_x = (out_w + 32 * TILE_PX - 1) / (32 * TILE_PX);
+    a.tiles_y = (out_h + 7) / 8;
+    const unsigned long long blocks = (unsigned long long)a.tiles_x * a.tiles_y * n;
+    VSTAB_REQUIRE(blocks > 0 && blocks < 0x7fffffffULL, "%s: grid of %llu blocks is out of range", who, blocks);
+    const size_t px = (size_t)n * out_h * out_w;
+    if (filled_from) VSTAB_HIP(hipMemsetAsync(filled_from, 0xff, px, ctx->stream));   // -1: not filled
+    if (fill_count) VSTAB_HIP(hipMemsetAsync(fill_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
+    if (pad_count) VSTAB_HIP(hipMemsetAsync(pad_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
+    const FillCand* cands = static_cast<const FillCand*>(d_cd);
+    KernelTimer timer(ctx, "fill");
+    const dim3 grid((unsigned)blocks), block(256);
+    if (interp == VSTAB_INTERP_BICUBIC) hipLaunchKernelGGL((temporal_fill_kernel<VSTAB_INTERP_BICUBIC, VSTAB_SUBPIX_Q5>), grid, block, 0, ctx->stream, a, cands);
+    else if (subpix == VSTAB_SUBPIX_EXACT) hipLaunchKernelGGL((temporal_fill_kernel<VSTAB_INTERP_BILINEAR, VSTAB_SUBPIX_EXACT>), grid, block, 0, ctx->stream, a, cands);
+    else hipLaunchKernelGGL((temporal_fill_kernel<VSTAB_INTERP_BILINEAR, VSTAB_SUBPIX_Q5>), grid, block, 0, ctx->stream, a, cands);
+    VSTAB_HIP(hipGetLastError());
+    return 0;
 }

@@ -215,7 +215,7 @@ def _lap(stats, key, t0):
 def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, transform_mode: str, camera_lock: bool,
                       strength: float, smooth: float, keep_fov: float, padding_rgb, frame_rate: float, group=None,
                       estimator: str = "flow", stats: Optional[Dict[str, float]] = None, want_meta: bool = True,
-                      check_value_range: bool = True):
+                      check_value_range: bool = True, temporal_fill: int = 0):
     """Sharded equivalent of `_stabilize_frames` (flow.py:213-640).
 
     local_frames: device tensor [n_local (+1 halo for rank > 0 that owns frames), H, W, 3] float32 -- this rank's frames
@@ -233,6 +233,11 @@ def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, t
     from . import native
 
     rank, world = dist.get_rank(group), dist.get_world_size(group)
+    if int(temporal_fill) != 0:
+        # a rank would need the `temporal_fill` source frames before and after its shard (a halo it does not hold); every
+        # rank raises alike, before any collective
+        raise ValueError(f"stabilize_sharded does not support temporal_fill={temporal_fill}: the sharded path holds no "
+                         "halo of neighbouring source frames; run the single-GPU pipeline for the temporal fill")
     if total_frames < 2:
         # flow.py:242-310 (empty / single-frame passthrough) has nothing to shard; every rank raises alike, before
         # any collective

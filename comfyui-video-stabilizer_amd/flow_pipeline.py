@@ -23,6 +23,7 @@ import numpy as np
 
 from . import host_math as hm
 from . import native
+from . import temporal_fill as temporal_fill_mod
 from .comfy_compat import ProgressBar, check_interrupt
 from .meta_v2 import applied_motion_meta_from_arrays, applied_motion_meta_from_stabilization_warp
 
@@ -511,9 +512,19 @@ def _rewarp_mismatched(ctx, device_frames, plan, final_dev, dst, mask, counts, p
     return int(bad.size)
 
 
+def _temporal_fill(ctx, device_frames, dst, mask, plan, meta, radius: int) -> None:
+    """Fills the warp's padding from neighbouring frames in place (temporal_fill.py) and adds meta["temporal_fill"]; the
+    other meta keys keep describing the warp.  `crop` framing has no padding: nothing to do."""
+    if radius <= 0 or plan.framing_mode == "crop":
+        return
+    em = plan.estimated_motion
+    meta["temporal_fill"] = temporal_fill_mod.fill_on_device(
+        ctx, device_frames, dst, mask, plan.final_matrices, np.asarray(em["matrices"], dtype=np.float32), em["confidences"], radius)
+
+
 def _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode, camera_lock,
                                 strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested, pbar, progress_total,
-                                keep_on_device):
+                                keep_on_device, temporal_fill=0):
     """F2-F14 with the plan formed on the device (see above).  Returns None when F0 found 0..255 float data: the
     speculative run used the unscaled frames and is discarded; the caller takes the regular path on the rescaled clip."""
     size = (context.width, context.height)
@@ -556,6 +567,7 @@ def _stabilize_with_device_plan(ctx, context, device_frames, working_size, total
     # the warp's counts: mirrored to the host behind the kernel (native.last_pad_counts) -- unless frames were warped again,
     # whose counts went into the device tensor only
     meta = complete_meta(meta, plan, _counts_to_host(counts, mirrored=mirror_ok))
+    _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill)   # on the host plan's verified matrices
     check_interrupt()
     if keep_on_device:
         return hm.StabilizationResult(dst, mask.unsqueeze(-1), meta, verdict)
@@ -576,12 +588,19 @@ def _stabilize_frames(
     ctx: Optional[native.Context] = None,
     keep_on_device: bool = False,
     estimator: str = "flow",
+    temporal_fill: int = 0,
 ) -> hm.StabilizationResult:
     """Positional signature of the reference (flow.py:213-223); keyword-only extras select the GPU
     context, keep outputs resident in HBM (multi-GPU sharding lives in distributed.py) or switch the
-    motion estimator to the Classic node's sparse tracker (classic.py:163-173, same signature)."""
+    motion estimator to the Classic node's sparse tracker (classic.py:163-173, same signature).
+    temporal_fill = R > 0 (beyond the reference, off by default): after the final warp the padded pixels are filled from
+    the up to R frames before and after that saw them (temporal_fill.py); `padding_mask` keeps what no frame saw and
+    meta["temporal_fill"] describes the fill.  0: the reference's behaviour and meta.  Bypass paths ignore it."""
     if estimator not in _META_SOURCE:
         raise ValueError(f"Unknown estimator {estimator!r}; expected 'flow' or 'classic'.")
+    temporal_fill = int(temporal_fill)
+    if not 0 <= temporal_fill <= temporal_fill_mod.MAX_RADIUS:
+        raise ValueError(f"temporal_fill={temporal_fill} outside [0, {temporal_fill_mod.MAX_RADIUS}]")
     estimator = resolve_flow_backend(estimator)
     total_frames = len(context.frames)
     fps_effective, fps_requested = _fps_fields(context, frame_rate)
@@ -641,7 +660,7 @@ def _stabilize_frames(
     if device_plan_applies(estimator, framing_mode, transform_mode, total_frames):
         done = _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode,
                                            camera_lock, strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested,
-                                           pbar, progress_total, keep_on_device)
+                                           pbar, progress_total, keep_on_device, temporal_fill)
         if done is not None:
             return done
         device_frames = context.device_batch(ctx)   # F0 rescaled the clip: everything is redone on the rescaled frames below
@@ -676,6 +695,7 @@ def _stabilize_frames(
     meta = prepare_meta(plan)  # host JSON work overlaps the warp kernel
     progress_done = _replay_progress(pbar, progress_done, total_frames, progress_total)
     meta = complete_meta(meta, plan, _counts_to_host(counts))
+    _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill)
     check_interrupt()
     verdict = {"used": False, "mismatched_frames": 0}
     if keep_on_device:

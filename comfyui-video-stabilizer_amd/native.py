@@ -174,6 +174,9 @@ _SIGNATURES = {
     "vstab_warp_batch_planned": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vstab_temporal_fill_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                  C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vstab_gftt_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p,
                   C.c_void_p]),
@@ -764,6 +767,43 @@ class Context:
         if counts is not None:
             counts._vstab_fetch = lambda n=n: self.last_pad_counts(n)   # valid until the next warp with counts of this context
         return dst, mask, counts
+
+    # ------------------------------------------------------------------ temporal fill
+    def temporal_fill_batch(self, clip_frames, matrices, cand_frame, dst, mask, first=0, interp="bilinear", subpix=None,
+                            want_filled_from=False, want_counts=True):
+        """Fills the padded pixels (mask == 1) of output frames [first, first + n) from neighbouring source frames, in place.
+        clip_frames [N,H,W,3] f32 device (the whole clip), matrices [n,K,3,3] f32 forward (candidate source -> output canvas),
+        cand_frame [n,K] i32 (-1: none), dst [n,h,w,3] / mask [n,h,w] f32 device and contiguous (see include/vstab.h for the
+        rule).  -> (filled_from i8 [n,h,w] | None, fill_count i32 [n] | None, pad_count i32 [n] | None), device tensors."""
+        torch = self.torch
+        src = self._as_device_frames(clip_frames)
+        total, sh, sw, ch = src.shape
+        if ch != 3:
+            raise VstabError(f"temporal_fill_batch expects 3-channel frames, got {ch}")
+        for name, t in (("dst", dst), ("mask", mask)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()):
+                raise VstabError(f"temporal_fill_batch: {name} must be a contiguous float32 tensor on {self.device}")
+        if dst.dim() != 4 or dst.shape[3] != 3 or mask.numel() * 3 != dst.numel():
+            raise VstabError(f"temporal_fill_batch: dst {tuple(dst.shape)} / mask {tuple(mask.shape)} do not match")
+        n, out_h, out_w = int(dst.shape[0]), int(dst.shape[1]), int(dst.shape[2])
+        cf = np.ascontiguousarray(cand_frame, dtype=np.int32)
+        if cf.ndim != 2 or cf.shape[0] != n:
+            raise VstabError(f"temporal_fill_batch: cand_frame {cf.shape} is not [n={n}, K]")
+        k = int(cf.shape[1])
+        m = np.ascontiguousarray(matrices, dtype=np.float32)
+        if m.size != n * k * 9:
+            raise VstabError(f"temporal_fill_batch: matrices {m.shape} are not [n={n}, K={k}, 3, 3]")
+        filled_from = torch.empty((n, out_h, out_w), dtype=torch.int8, device=self.device) if want_filled_from else None
+        fill_count = torch.empty((n,), dtype=torch.int32, device=self.device) if want_counts else None
+        pad_count = torch.empty((n,), dtype=torch.int32, device=self.device) if want_counts else None
+        self.use_torch_stream()
+        _check(self.lib.vstab_temporal_fill_batch(
+            self.handle, _dev_ptr(src), total, sh, sw, int(first), n, m.ctypes.data, cf.ctypes.data, k, out_h, out_w,
+            INTERP[interp], SUBPIX[subpix or DEFAULT_SUBPIX], _dev_ptr(dst), _dev_ptr(mask),
+            _dev_ptr(filled_from) if filled_from is not None else None,
+            _dev_ptr(fill_count) if fill_count is not None else None,
+            _dev_ptr(pad_count) if pad_count is not None else None), "vstab_temporal_fill_batch")
+        return filled_from, fill_count, pad_count
 
     # ------------------------------------------------------------------ Classic estimator (sparse features + LK)
     def gftt_batch(self, gray, max_corners=400, quality=0.01, min_distance=7.0, block_size=21):

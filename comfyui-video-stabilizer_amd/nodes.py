@@ -11,6 +11,8 @@ from typing import Any
 
 import os
 
+import numpy as np
+
 from . import host_math as hm
 from .apply_pipeline import apply_motion
 from .meta_v2 import resolve_motion_meta
@@ -349,13 +351,84 @@ class VideoStabilizerShakeGeneratorManual(io.ComfyNode):
         return _shake_block(frames_context, frame_rate, recipe, amount, speed, seed, "shake_generator_manual", "manual")
 
 
+class VideoStabilizerTemporalFill(io.ComfyNode):
+    """Fills the padding of a Flow / Classic result from neighbouring frames (temporal_fill.py), from the meta JSON alone:
+    `stabilization_warp` gives the applied matrices, `estimated_motion.per_transition` the frame-to-frame motion.  Not one
+    of the reference's nodes: it is registered by the extension but kept out of NODE_CLASSES."""
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        schema = io.Schema(
+            node_id="video_stabilizer_temporal_fill",
+            display_name="Video Stabilizer Temporal Fill",
+            category="Video/Stabilization",
+            description=("Fills padded pixels of stabilized frames with what neighbouring frames saw there, using the "
+                         "stabilizer's own motion metadata; the remaining mask marks what no frame within the radius saw."),
+        )
+        schema.inputs = [
+            io.Image.Input("frames", display_name="Frames", tooltip="The original (unstabilized) frames."),
+            io.Image.Input("frames_stabilized", display_name="Stabilized Frames"),
+            io.Mask.Input("padding_mask", display_name="Padding Mask"),
+            JSONType.Input("meta", display_name="Motion Meta"),
+            io.Int.Input("radius", default=8, min=1, max=32, display_name="Radius",
+                         tooltip="Frames before and after each frame that may supply its missing pixels."),
+            io.Combo.Input("interpolation", options=["bilinear", "bicubic"], default="bilinear", display_name="Interpolation"),
+        ]
+        schema.outputs = [
+            io.Image.Output("frames", display_name="Frames"),
+            io.Mask.Output("padding_mask", display_name="Padding Mask"),
+            JSONType.Output("meta", display_name="Meta"),
+        ]
+        return schema
+
+    @classmethod
+    def execute(cls, frames: Any, frames_stabilized: Any, padding_mask: Any, meta: dict, radius: int,
+                interpolation: str) -> io.NodeOutput:
+        from . import native, temporal_fill
+
+        plan = temporal_fill.plan_from_meta(meta)   # ValueError naming the missing key, before any GPU work
+        if interpolation not in native.INTERP:
+            raise ValueError(f"Unknown interpolation {interpolation!r}; expected 'bilinear' or 'bicubic'.")
+        context = hm._normalize_video_input(frames)
+        out_context = hm._normalize_video_input(frames_stabilized)
+        n = len(plan["final_matrices"])
+        if len(context.frames) != n or len(out_context.frames) != n:
+            raise ValueError(f"temporal fill: meta describes {n} frames, got {len(context.frames)} original and "
+                             f"{len(out_context.frames)} stabilized frames")
+        if (context.width, context.height) != plan["source_size"] or (out_context.width, out_context.height) != plan["output_size"]:
+            raise ValueError(f"temporal fill: frame sizes {(context.width, context.height)} -> "
+                             f"{(out_context.width, out_context.height)} do not match the meta's "
+                             f"{plan['source_size']} -> {plan['output_size']}")
+        ctx = native.default_context()
+        torch = ctx.torch
+        src = context.device_batch(ctx)
+        if context.range_pending:   # F0's value-range rule, as the stabilizer applied it to these frames
+            if hm.resolve_value_range(context, hm.prefetch_peaks(ctx.frame_range(src)), ctx):
+                src = context.device_batch(ctx)
+        # the fill works in place: on copies, so the caller's tensors (another node's cached outputs) stay as they are
+        dst = out_context.device_batch(ctx).clone()
+        mask = padding_mask if isinstance(padding_mask, torch.Tensor) else torch.from_numpy(np.asarray(padding_mask, dtype=np.float32))
+        mask = mask.to(device=ctx.device, dtype=torch.float32)
+        if mask.ndim == 4:
+            mask = mask[..., 0]
+        if tuple(mask.shape) != tuple(dst.shape[:3]):
+            raise ValueError(f"temporal fill: padding_mask {tuple(mask.shape)} does not match the stabilized frames {tuple(dst.shape[:3])}")
+        mask = mask.contiguous().clone()
+        block = temporal_fill.fill_on_device(ctx, src, dst, mask, plan["final_matrices"], plan["transitions"],
+                                             plan["confidences"], int(radius), interp=interpolation)
+        block["interpolation"] = interpolation
+        out_meta = dict(meta)
+        out_meta["temporal_fill"] = block
+        return io.NodeOutput(_image_out(dst, out_context), _mask_out(mask), out_meta)
+
+
 NODE_CLASSES = [VideoStabilizerClassic, VideoStabilizerFlow, VideoStabilizerMotionApply, VideoStabilizerShakeGenerator,
                 VideoStabilizerShakeGeneratorManual, VideoStabilizerInverse]
 
 
 class VideoStabilizerAmdExtension(ComfyExtension):
     async def get_node_list(self) -> list:
-        return list(NODE_CLASSES)
+        return list(NODE_CLASSES) + [VideoStabilizerTemporalFill]   # the six reference nodes + the temporal fill
 
     async def on_load(self) -> None:
         """Graph migration Inverse -> Motion Apply, as nodes/node_replacements.py:8-27 registers it (only inside

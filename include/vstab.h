@@ -384,6 +384,30 @@ int vstab_warp_batch_planned(vstab_ctx* ctx, const float* src, int first, int n,
  * without a copy or a stream synchronisation of the caller's. */
 int vstab_last_pad_counts(vstab_ctx* ctx, int n, uint32_t* out);
 
+/* ---- temporal fill: padding pixels taken from neighbouring frames (beyond the reference, off by default) ----
+ * After a warp, an output pixel with mask == 1.0f saw no content of its own frame.  Per output pixel of frame first + f:
+ *   - mask != 1.0f: pixel, mask and every other output are left untouched (nothing is stored).
+ *   - otherwise the candidates k = 0 .. K-1 are walked in order.  A candidate with cand_frame == -1, or whose float32 matrix
+ *     has a zero / non-finite fp64 determinant or inverse (cv::invert would refuse it), is skipped.  Candidate k is VALID at
+ *     the pixel iff the source coordinate -- computed exactly as vstab_warp_batch computes it for that matrix (float32
+ *     forward matrix inverted in fp64, fp64 coordinate terms per OpenCV column block, 1/32-px rounding, or the float32
+ *     coordinates of VSTAB_SUBPIX_EXACT) -- has every interpolation tap inside the source frame:
+ *     bilinear 0 <= sx < src_w-1 && 0 <= sy < src_h-1, bicubic 1 <= sx < src_w-2 && 1 <= sy < src_h-2 (sx, sy the integer
+ *     parts).  No border colour can enter a filled pixel.
+ *   - the first valid candidate wins: dst = the bits vstab_warp_batch(src[cand_frame], that matrix) writes at that pixel,
+ *     mask = 0, filled_from = k.  No valid candidate: untouched, filled_from = -1.
+ * src         dev  [clip_frames, src_h, src_w, 3] f32: the whole clip (must not alias dst)
+ * first, n    output frames [first, first + n) of the clip; matrices / cand_frame / dst / mask / outputs hold those n frames
+ * matrices    host [n, K, 9] f32 FORWARD (source frame cand_frame[f][k] -> output canvas of frame first + f)
+ * cand_frame  host [n, K] i32 clip frame index, -1 = no candidate;  K in 1..64
+ * dst, mask   dev  [n, out_h, out_w, 3] / [n, out_h, out_w] f32, in and out
+ * filled_from dev  [n, out_h, out_w] i8 or NULL;  fill_count / pad_count dev [n] u32 or NULL: pixels filled per frame /
+ *             pixels whose mask is still 1.0f afterwards.  Timing kind "fill". */
+int vstab_temporal_fill_batch(vstab_ctx* ctx, const float* src, int clip_frames, int src_h, int src_w, int first, int n,
+                              const float* matrices, const int32_t* cand_frame, int K, int out_h, int out_w, int interp,
+                              int subpix, float* dst, float* mask, int8_t* filled_from, uint32_t* fill_count,
+                              uint32_t* pad_count);
+
 /* ---- F6 / F9 host helper: element-wise libm over fp64 arrays (host pointers, no GPU involved) ----
  * nodes/stabilizer_utils.py:300-358 (_matrix_to_params / _params_to_matrix) call math.sqrt/atan2/log and
  * math.exp/cos/sin per frame; this runs the same libm functions over a whole clip in one call.
