@@ -8,6 +8,6 @@ __version__ = "0.1.0"
 
 
 async def comfy_entrypoint():
-    from .nodes import VideoStabilizerAmdExtension
+    from .nodes import VideoStabilizerAmdMaskedExtension
 
-    return VideoStabilizerAmdExtension()
+    return VideoStabilizerAmdMaskedExtension()

@@ -74,6 +74,7 @@ struct FitArgs {
     int pairs, gh, gw, step, requested_mode;
     const int* counts;        // point-pair mode (gw == 0): detected features per pair, rows of `cap` entries
     int cap;
+    const uint8_t* blocked;   // masked grid mode only: [pairs+1][gh*gw], non-zero = sample blocked in that frame
 };
 
 // gw > 0: stride-`step` grid over a flow field (F = [gh][gw][2] displacements, flow.py:141-147);
@@ -149,6 +150,10 @@ __device__ unsigned radix_select(const unsigned* keys, int n, int r, int* hist /
     return prefix;
 }
 
+// MASKED (grid mode, vstab_sample_fit_batch_masked): a sample of pair i takes part only if it is blocked neither in frame i
+// nor in frame i+1 (a.blocked); the admitted samples are the pair's `total`.  A template instance of its own, so that the
+// unmasked kernel keeps its instructions.
+template <bool MASKED>
 __global__ __launch_bounds__(FIT_THREADS) void fit_kernel(FitArgs a)
 {
     __shared__ unsigned s_sort[MAX_SORT];
@@ -167,20 +172,30 @@ __global__ __launch_bounds__(FIT_THREADS) void fit_kernel(FitArgs a)
 
     const int pair = blockIdx.x, tid = threadIdx.x;
     const bool points = a.gw == 0;
-    const int total = points ? a.counts[pair] : a.gh * a.gw;
+    const int scan = points ? a.counts[pair] : a.gh * a.gw;
+    const uint8_t* __restrict__ B0 = MASKED ? a.blocked + (size_t)pair * a.cap : nullptr;
+    const uint8_t* __restrict__ B1 = MASKED ? B0 + a.cap : nullptr;
     const float* __restrict__ F = a.grid_flow + (size_t)pair * a.cap * (points ? 4 : 2);
     int* __restrict__ vmap = a.vmap + (size_t)pair * a.cap;
     vstab_fit_record* out = a.out + (size_t)pair * 3;
 
     // ---- validity scan (ordered compaction, flow.py:150-152) ----
-    const int per = (total + FIT_THREADS - 1) / FIT_THREADS;
-    const int g0 = tid * per, g1 = min(g0 + per, total);
-    int local = 0;
+    const int per = (scan + FIT_THREADS - 1) / FIT_THREADS;
+    const int g0 = tid * per, g1 = min(g0 + per, scan);
+    int local = 0, admitted = 0;
     for (int g = g0; g < g1; g++) {
         float px, py, cx, cy;
         load_point(F, a.gw, a.step, g, px, py, cx, cy);
-        local += (isfinite(cx) && isfinite(cy)) ? 1 : 0;
+        if (MASKED) {
+            const bool adm = (B0[g] | B1[g]) == 0;
+            admitted += adm ? 1 : 0;
+            local += (adm && isfinite(cx) && isfinite(cy)) ? 1 : 0;
+        } else {
+            local += (isfinite(cx) && isfinite(cy)) ? 1 : 0;
+        }
     }
+    int total = scan;
+    if (MASKED) total = block_sum(admitted, s_redi);
     {   // exclusive prefix sum of `local` over the block: wavefront scan, then the wavefront totals
         int incl = local;
 #pragma unroll
@@ -202,7 +217,7 @@ __global__ __launch_bounds__(FIT_THREADS) void fit_kernel(FitArgs a)
         for (int g = g0; g < g1; g++) {
             float px, py, cx, cy;
             load_point(F, a.gw, a.step, g, px, py, cx, cy);
-            if (isfinite(cx) && isfinite(cy)) vmap[o++] = g;
+            if ((!MASKED || (B0[g] | B1[g]) == 0) && isfinite(cx) && isfinite(cy)) vmap[o++] = g;
         }
     }
     __syncthreads();
@@ -422,7 +437,7 @@ int vstab_fit_homography(vstab_ctx* ctx, const float* grid_flow, const int* vmap
 // behind the kernels with an event, and vstab_sample_fit_batch_end collects it (the speculative plan and the warp are
 // queued in between, flow_pipeline.py).
 static int run_fit(vstab_ctx* ctx, const float* data, const int* counts, int pairs, int gh, int gw, int step, int cap,
-                   int requested_mode, vstab_fit_record* results)
+                   int requested_mode, vstab_fit_record* results, const uint8_t* blocked = nullptr)
 {
     VSTAB_HIP(hipSetDevice(ctx->device));
     // a pending fit whose records were downloaded on the side stream but never collected (a call abandoned between _begin
@@ -438,8 +453,9 @@ static int run_fit(vstab_ctx* ctx, const float* data, const int* counts, int pai
     int* d_map = reinterpret_cast<int*>(base + ((rec_bytes + 255) & ~size_t(255)));
     {
         KernelTimer timer(ctx, "fit");
-        FitArgs a{data, d_map, d_out, pairs, gh, gw, step, requested_mode, counts, cap};
-        hipLaunchKernelGGL(fit_kernel, dim3((unsigned)pairs), dim3(FIT_THREADS), 0, ctx->stream, a);
+        FitArgs a{data, d_map, d_out, pairs, gh, gw, step, requested_mode, counts, cap, blocked};
+        if (blocked) hipLaunchKernelGGL(fit_kernel<true>, dim3((unsigned)pairs), dim3(FIT_THREADS), 0, ctx->stream, a);
+        else hipLaunchKernelGGL(fit_kernel<false>, dim3((unsigned)pairs), dim3(FIT_THREADS), 0, ctx->stream, a);
         VSTAB_HIP(hipGetLastError());
         if (requested_mode >= VSTAB_MODE_PERSPECTIVE) {
             if (int rc = vstab_fit_homography(ctx, data, d_map, pairs, gh, gw, step, cap, d_out)) return rc;
@@ -482,6 +498,33 @@ extern "C" int vstab_sample_fit_batch_begin(vstab_ctx* ctx, const float* grid_fl
     VSTAB_REQUIRE(requested_mode >= VSTAB_MODE_TRANSLATION && requested_mode <= VSTAB_MODE_PERSPECTIVE, "vstab_sample_fit_batch_begin: unknown mode %d", requested_mode);
     VSTAB_REQUIRE((long long)gh * gw <= MAX_SORT, "vstab_sample_fit_batch_begin: %d sample points exceed the supported %d", gh * gw, MAX_SORT);
     return run_fit(ctx, grid_flow, nullptr, pairs, gh, gw, step, gh * gw, requested_mode, nullptr);
+}
+
+// The masked forms: the same checks and the same run, with the block grid handed to the kernel's masked instance.
+static int masked_check(const char* who, vstab_ctx* ctx, const float* grid_flow, const uint8_t* blocked, int pairs, int gh, int gw, int step,
+                        int requested_mode)
+{
+    VSTAB_REQUIRE(ctx != nullptr, "%s: ctx is NULL", who);
+    VSTAB_REQUIRE(grid_flow && blocked, "%s: NULL pointer argument", who);
+    VSTAB_REQUIRE(pairs > 0 && gh > 0 && gw > 0 && step > 0, "%s: non-positive size", who);
+    VSTAB_REQUIRE(requested_mode >= VSTAB_MODE_TRANSLATION && requested_mode <= VSTAB_MODE_PERSPECTIVE, "%s: unknown mode %d", who, requested_mode);
+    VSTAB_REQUIRE((long long)gh * gw <= MAX_SORT, "%s: %d sample points exceed the supported %d", who, gh * gw, MAX_SORT);
+    return 0;
+}
+
+extern "C" int vstab_sample_fit_batch_masked(vstab_ctx* ctx, const float* grid_flow, int pairs, int gh, int gw, int step,
+                                             int requested_mode, const uint8_t* blocked, vstab_fit_record* results)
+{
+    if (int rc = masked_check("vstab_sample_fit_batch_masked", ctx, grid_flow, blocked, pairs, gh, gw, step, requested_mode)) return rc;
+    VSTAB_REQUIRE(results != nullptr, "vstab_sample_fit_batch_masked: NULL pointer argument");
+    return run_fit(ctx, grid_flow, nullptr, pairs, gh, gw, step, gh * gw, requested_mode, results, blocked);
+}
+
+extern "C" int vstab_sample_fit_batch_begin_masked(vstab_ctx* ctx, const float* grid_flow, int pairs, int gh, int gw, int step,
+                                                   int requested_mode, const uint8_t* blocked)
+{
+    if (int rc = masked_check("vstab_sample_fit_batch_begin_masked", ctx, grid_flow, blocked, pairs, gh, gw, step, requested_mode)) return rc;
+    return run_fit(ctx, grid_flow, nullptr, pairs, gh, gw, step, gh * gw, requested_mode, nullptr, blocked);
 }
 
 extern "C" const vstab_fit_record* vstab_fit_records_device(vstab_ctx* ctx)

@@ -215,7 +215,7 @@ def _lap(stats, key, t0):
 def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, transform_mode: str, camera_lock: bool,
                       strength: float, smooth: float, keep_fov: float, padding_rgb, frame_rate: float, group=None,
                       estimator: str = "flow", stats: Optional[Dict[str, float]] = None, want_meta: bool = True,
-                      check_value_range: bool = True, temporal_fill: int = 0):
+                      check_value_range: bool = True, temporal_fill: int = 0, estimation_mask=None):
     """Sharded equivalent of `_stabilize_frames` (flow.py:213-640).
 
     local_frames: device tensor [n_local (+1 halo for rank > 0 that owns frames), H, W, 3] float32 -- this rank's frames
@@ -228,6 +228,10 @@ def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, t
     a driver that needs the dict once asks rank 0 only.  check_value_range: F0's per-frame `max > 1.5 -> /255` rule
     (stabilizer_utils.py:127-131) is applied to this rank's frames from the maxima the gray pass reports; it is a
     per-frame rule, so no rank needs to know another rank's verdict."""
+    if estimation_mask is not None:
+        # the mask would have to be sharded with the frames, halo frame included; every rank raises alike, before any collective
+        raise ValueError("stabilize_sharded does not support estimation_mask: the sharded path does not distribute a mask "
+                         "with each rank's frames and halo; run the single-GPU pipeline for a masked estimation")
     import torch.distributed as dist
 
     from . import native

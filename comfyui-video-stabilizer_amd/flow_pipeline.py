@@ -163,12 +163,15 @@ def _gray(ctx, device_frames, working_size, peaks_out):
     return gray
 
 
-def estimate_transitions(ctx, device_frames, working_size, transform_mode: str, clip_start: bool = True, peaks_out=None):
+def estimate_transitions(ctx, device_frames, working_size, transform_mode: str, clip_start: bool = True, peaks_out=None,
+                         blocked=None):
     """F2-F5 for frames [N,H,W,3] on the device -> per-pair candidate fits (structured table [N-1,3]).
-    peaks_out: a list that receives the device tensor of per-frame maxima (see host_math.resolve_value_range)."""
+    peaks_out: a list that receives the device tensor of per-frame maxima (see host_math.resolve_value_range).
+    blocked: the estimation mask's block grid (u8 [N,gh,gw], Context.mask_block_grid); the flow itself is computed on the
+    unmasked images."""
     gray = _gray(ctx, device_frames, working_size, peaks_out)
     _, grid = ctx.dis_flow_batch(gray, sample_step=SAMPLE_STEP, want_full=False, want_grid=True, clip_start=clip_start)
-    return ctx.sample_fit_batch(grid, SAMPLE_STEP, transform_mode)
+    return ctx.sample_fit_batch(grid, SAMPLE_STEP, transform_mode, blocked=blocked)
 
 
 def estimate_transitions_phase(ctx, device_frames, working_size, transform_mode: str, clip_start: bool = True, peaks_out=None):
@@ -179,13 +182,14 @@ def estimate_transitions_phase(ctx, device_frames, working_size, transform_mode:
     return table
 
 
-def estimate_transitions_tvl1(ctx, device_frames, working_size, transform_mode: str, clip_start: bool = True, peaks_out=None):
+def estimate_transitions_tvl1(ctx, device_frames, working_size, transform_mode: str, clip_start: bool = True, peaks_out=None,
+                              blocked=None):
     """Second dense estimator (flow.py:76-80, 140-147): Dual TV-L1 flow with OpenCV's default parameters on the
     estimation images, sampled and fitted exactly as the DIS flow is.  Pairs are independent (no initial flow), so
     clip_start does not matter."""
     gray = _gray(ctx, device_frames, working_size, peaks_out)
     _, grid, _ = ctx.tvl1_flow_batch(gray, sample_step=SAMPLE_STEP, want_full=False, want_grid=True)
-    return ctx.sample_fit_batch(grid, SAMPLE_STEP, transform_mode)
+    return ctx.sample_fit_batch(grid, SAMPLE_STEP, transform_mode, blocked=blocked)
 
 
 _ESTIMATORS = {}   # filled below the four estimator functions
@@ -522,16 +526,61 @@ def _temporal_fill(ctx, device_frames, dst, mask, plan, meta, radius: int) -> No
         ctx, device_frames, dst, mask, plan.final_matrices, np.asarray(em["matrices"], dtype=np.float32), em["confidences"], radius)
 
 
+# ---- estimation mask (beyond the reference; the rule is in include/vstab.h) --------------------------------------------
+MASK_MARGIN_MAX = 64
+_MASK_LIMITS = {
+    "classic": "the Classic estimator fits tracked corners, not grid samples: it needs a masked corner detector, which does not exist yet.",
+    "flow_phase_correlate": "phase correlation yields one global transform per pair: it has no samples to drop.",
+}
+
+
+def check_estimation_mask_request(estimator: str, mask_margin) -> int:
+    """The checks of an estimation-mask request that need neither the clip nor a GPU -> the margin as an int."""
+    margin = int(mask_margin)
+    if not 0 <= margin <= MASK_MARGIN_MAX:
+        raise ValueError(f"mask_margin={margin} outside [0, {MASK_MARGIN_MAX}] (working pixels)")
+    if estimator in _MASK_LIMITS:
+        raise ValueError(f"estimation_mask is not supported with estimator {estimator!r}: {_MASK_LIMITS[estimator]}")
+    return margin
+
+
+def check_estimation_mask_shape(estimation_mask, total_frames: int, size) -> None:
+    """[N,H,W], [1,H,W] or [H,W] at the frames' full resolution, else a ValueError naming both shapes."""
+    width, height = size
+    shape = tuple(int(v) for v in estimation_mask.shape)
+    ok = (shape == (height, width)) or (len(shape) == 3 and shape[1:] == (height, width) and shape[0] in (1, total_frames))
+    if not ok:
+        raise ValueError(f"estimation_mask of shape {shape} does not match the clip [{total_frames},{height},{width}]: expected "
+                         f"[{total_frames},{height},{width}], [1,{height},{width}] or [{height},{width}]")
+
+
+def _block_grid(ctx, estimation_mask, total_frames, working_size, margin):
+    """The mask on the device (a float32 host tensor goes through the pinned ring) -> block grid u8 [N,gh,gw]."""
+    torch = ctx.torch
+    mask = estimation_mask if isinstance(estimation_mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(estimation_mask, dtype=np.float32))
+    if mask.device.type == "cpu" and mask.dtype == torch.float32:
+        mask = ctx.upload(mask)
+    return ctx.mask_block_grid(mask, total_frames, working_size, SAMPLE_STEP, margin), 1 if mask.dim() == 2 else int(mask.shape[0])
+
+
+def estimation_mask_meta(fit_records, margin: int, mask_frames: int, grid_samples: int) -> Dict[str, Any]:
+    """meta["estimation_mask"] from the fits' own counts (total_points = admitted samples of the pair)."""
+    admitted = np.asarray(fit_records["total_points"][:, 0], dtype=np.int64)
+    fraction = (grid_samples - admitted) / float(grid_samples)
+    return {"margin": int(margin), "mask_frames": int(mask_frames), "blocked_fraction_mean": float(fraction.mean()),
+            "blocked_fraction_max": float(fraction.max()), "admitted_points_min": int(admitted.min())}
+
+
 def _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode, camera_lock,
                                 strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested, pbar, progress_total,
-                                keep_on_device, temporal_fill=0):
+                                keep_on_device, temporal_fill=0, blocked=None, mask_info=None):
     """F2-F14 with the plan formed on the device (see above).  Returns None when F0 found 0..255 float data: the
     speculative run used the unscaled frames and is discarded; the caller takes the regular path on the rescaled clip."""
     size = (context.width, context.height)
     peaks = [] if context.range_pending else None
     gray = _gray(ctx, device_frames, working_size, peaks)
     _, grid = ctx.dis_flow_batch(gray, sample_step=SAMPLE_STEP, want_full=False, want_grid=True)
-    pairs = ctx.sample_fit_batch_begin(grid, SAMPLE_STEP, transform_mode)
+    pairs = ctx.sample_fit_batch_begin(grid, SAMPLE_STEP, transform_mode, blocked=blocked)
     ctx.flow_plan_device(ctx.fit_records_device(), pairs, transform_mode, size, working_size, smooth, fps_effective, strength,
                          bool(camera_lock), warp_frames=total_frames, framing=framing_mode)
     out_size = size
@@ -567,6 +616,8 @@ def _stabilize_with_device_plan(ctx, context, device_frames, working_size, total
     # the warp's counts: mirrored to the host behind the kernel (native.last_pad_counts) -- unless frames were warped again,
     # whose counts went into the device tensor only
     meta = complete_meta(meta, plan, _counts_to_host(counts, mirrored=mirror_ok))
+    if mask_info is not None:
+        meta["estimation_mask"] = estimation_mask_meta(fit_records, *mask_info)
     _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill)   # on the host plan's verified matrices
     check_interrupt()
     if keep_on_device:
@@ -589,19 +640,27 @@ def _stabilize_frames(
     keep_on_device: bool = False,
     estimator: str = "flow",
     temporal_fill: int = 0,
+    estimation_mask=None,
+    mask_margin: int = 16,
 ) -> hm.StabilizationResult:
     """Positional signature of the reference (flow.py:213-223); keyword-only extras select the GPU
     context, keep outputs resident in HBM (multi-GPU sharding lives in distributed.py) or switch the
     motion estimator to the Classic node's sparse tracker (classic.py:163-173, same signature).
     temporal_fill = R > 0 (beyond the reference, off by default): after the final warp the padded pixels are filled from
     the up to R frames before and after that saw them (temporal_fill.py); `padding_mask` keeps what no frame saw and
-    meta["temporal_fill"] describes the fill.  0: the reference's behaviour and meta.  Bypass paths ignore it."""
+    meta["temporal_fill"] describes the fill.  0: the reference's behaviour and meta.  Bypass paths ignore it.
+    estimation_mask (beyond the reference, None by default): [N,H,W], [1,H,W] or [H,W] float at the frames' resolution, > 0.5
+    or not finite where a moving subject (or a burnt-in logo) is; the DIS / TV-L1 flow samples within mask_margin working
+    pixels of it in either frame of a pair stay out of that pair's fit (include/vstab.h states the rule) and
+    meta["estimation_mask"] reports how many.  None: the reference's behaviour and meta.  Bypass paths ignore it."""
     if estimator not in _META_SOURCE:
         raise ValueError(f"Unknown estimator {estimator!r}; expected 'flow' or 'classic'.")
     temporal_fill = int(temporal_fill)
     if not 0 <= temporal_fill <= temporal_fill_mod.MAX_RADIUS:
         raise ValueError(f"temporal_fill={temporal_fill} outside [0, {temporal_fill_mod.MAX_RADIUS}]")
     estimator = resolve_flow_backend(estimator)
+    if estimation_mask is not None:
+        mask_margin = check_estimation_mask_request(estimator, mask_margin)
     total_frames = len(context.frames)
     fps_effective, fps_requested = _fps_fields(context, frame_rate)
     size = (context.width, context.height)
@@ -653,14 +712,22 @@ def _stabilize_frames(
         masks_out = np.zeros((1, context.height, context.width, 1), np.float32)
         return hm.StabilizationResult(frames_out, masks_out, _attach_motion_meta(meta, fps_effective, estimator))
 
+    if estimation_mask is not None:
+        check_estimation_mask_shape(estimation_mask, total_frames, size)
     ctx = ctx or native.default_context()
     device_frames = context.device_batch(ctx)
     working_size = hm._working_estimation_size(context.width, context.height)
+    blocked = mask_info = None
+    masked = {}
+    if estimation_mask is not None:   # reduced once per call: the block grid serves every estimation pass below
+        blocked, mask_frames = _block_grid(ctx, estimation_mask, total_frames, working_size, mask_margin)
+        mask_info = (mask_margin, mask_frames, int(blocked.shape[1] * blocked.shape[2]))
+        masked = {"blocked": blocked}
 
     if device_plan_applies(estimator, framing_mode, transform_mode, total_frames):
         done = _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode,
                                            camera_lock, strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested,
-                                           pbar, progress_total, keep_on_device, temporal_fill)
+                                           pbar, progress_total, keep_on_device, temporal_fill, blocked, mask_info)
         if done is not None:
             return done
         device_frames = context.device_batch(ctx)   # F0 rescaled the clip: everything is redone on the rescaled frames below
@@ -668,14 +735,14 @@ def _stabilize_frames(
     # ---- estimation (F2-F5) -------------------------------------------------
     estimate = _ESTIMATORS[estimator]
     peaks = [] if context.range_pending else None
-    fit_records = estimate(ctx, device_frames, working_size, transform_mode, peaks_out=peaks)
+    fit_records = estimate(ctx, device_frames, working_size, transform_mode, peaks_out=peaks, **masked)
     if peaks and hm.resolve_value_range(context, peaks[0], ctx):
         # F0 (stabilizer_utils.py:127-131): some frame turned out to be 0..255 float data.  The estimation above ran
         # optimistically on the tensor as given (the gray pass reported the per-frame maxima for free); the frames
         # have been rescaled now, so it is repeated on the rescaled clip.  0..1 input -- the ComfyUI IMAGE contract --
         # never takes this branch.
         device_frames = context.device_batch(ctx)
-        fit_records = estimate(ctx, device_frames, working_size, transform_mode)
+        fit_records = estimate(ctx, device_frames, working_size, transform_mode, **masked)
     progress_done = _replay_progress(pbar, 0, total_frames - 1, progress_total)
     check_interrupt()
 
@@ -695,6 +762,8 @@ def _stabilize_frames(
     meta = prepare_meta(plan)  # host JSON work overlaps the warp kernel
     progress_done = _replay_progress(pbar, progress_done, total_frames, progress_total)
     meta = complete_meta(meta, plan, _counts_to_host(counts))
+    if mask_info is not None:
+        meta["estimation_mask"] = estimation_mask_meta(fit_records, *mask_info)
     _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill)
     check_interrupt()
     verdict = {"used": False, "mismatched_frames": 0}

@@ -164,6 +164,12 @@ _SIGNATURES = {
     "vstab_sample_fit_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vstab_sample_fit_batch_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vstab_mask_block_grid": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vstab_sample_fit_batch_masked": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vstab_sample_fit_batch_begin_masked": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vstab_fit_records_device": (C.c_void_p, [C.c_void_p]),
     "vstab_sample_fit_batch_end": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "vstab_flow_plan_device": (
@@ -641,14 +647,55 @@ class Context:
         )
         return flow, grid, iters
 
-    def sample_fit_batch(self, grid_flow, step, requested_mode):
-        """grid_flow [P,gh,gw,2] (device) -> structured table [P,3] (FIT_DTYPE), one row per pair and mode."""
+    def mask_block_grid(self, mask, n_frames, working_size, step, margin):
+        """Estimation mask -> the grid samples the fit must not use (vstab_mask_block_grid; the rule is in include/vstab.h).
+        mask [n_frames,H,W], [1,H,W] or [H,W] float (device or host; > 0.5 or not finite = subject), working_size = (w, h) or
+        None for no downscale, margin in working pixels (0..64) -> blocked u8 [n_frames,gh,gw] on the device."""
+        torch = self.torch
+        if not isinstance(mask, torch.Tensor):
+            mask = torch.from_numpy(np.ascontiguousarray(mask, dtype=np.float32))
+        if mask.dim() == 2:
+            mask = mask.unsqueeze(0)
+        if mask.dim() != 3 or mask.shape[0] not in (1, int(n_frames)):
+            raise ValueError(f"mask_block_grid: mask {tuple(mask.shape)} is not [{int(n_frames)},H,W], [1,H,W] or [H,W]")
+        if not 0 <= int(margin) <= 64:
+            raise ValueError(f"mask_block_grid: margin {margin} outside [0, 64]")
+        mask = mask.to(device=self.device, dtype=torch.float32).contiguous()
+        n_masks, sh, sw = (int(v) for v in mask.shape)
+        ww, wh = (sw, sh) if working_size is None else (int(working_size[0]), int(working_size[1]))
+        gh, gw = (wh + step - 1) // step, (ww + step - 1) // step
+        blocked = torch.empty((int(n_frames), gh, gw), dtype=torch.uint8, device=self.device)
+        self.use_torch_stream()
+        _check(self.lib.vstab_mask_block_grid(self.handle, _dev_ptr(mask), n_masks, int(n_frames), sh, sw, wh, ww, int(step),
+                                              int(margin), _dev_ptr(blocked)), "vstab_mask_block_grid")
+        return blocked
+
+    def _fit_inputs(self, grid_flow, blocked):
         if grid_flow.device != self.device:
             grid_flow = grid_flow.to(self.device)
         grid_flow = grid_flow.contiguous()
         pairs, gh, gw, _ = grid_flow.shape
+        if blocked is not None:
+            if blocked.dtype != self.torch.uint8 or tuple(blocked.shape) != (pairs + 1, gh, gw):
+                raise ValueError(f"sample_fit_batch: blocked {tuple(blocked.shape)} {blocked.dtype} is not uint8 "
+                                 f"[{pairs + 1},{gh},{gw}] (one row per frame of the {pairs} pairs)")
+            blocked = blocked.to(self.device).contiguous()
+        return grid_flow, blocked, pairs, gh, gw
+
+    def sample_fit_batch(self, grid_flow, step, requested_mode, blocked=None):
+        """grid_flow [P,gh,gw,2] (device) -> structured table [P,3] (FIT_DTYPE), one row per pair and mode.
+        blocked (u8 [P+1,gh,gw], mask_block_grid): the fit uses the samples blocked in neither frame of a pair."""
+        grid_flow, blocked, pairs, gh, gw = self._fit_inputs(grid_flow, blocked)
         table = np.zeros((pairs, 3), FIT_DTYPE)
         self.use_torch_stream()
+        if blocked is not None:
+            _check(
+                self.lib.vstab_sample_fit_batch_masked(
+                    self.handle, _dev_ptr(grid_flow), pairs, gh, gw, int(step), MODES[requested_mode], _dev_ptr(blocked),
+                    table.ctypes.data),
+                "vstab_sample_fit_batch_masked",
+            )
+            return table
         _check(
             self.lib.vstab_sample_fit_batch(
                 self.handle, _dev_ptr(grid_flow), pairs, gh, gw, int(step), MODES[requested_mode], table.ctypes.data),
@@ -656,18 +703,20 @@ class Context:
         )
         return table
 
-    def sample_fit_batch_begin(self, grid_flow, step, requested_mode):
+    def sample_fit_batch_begin(self, grid_flow, step, requested_mode, blocked=None):
         """Launch the fits of sample_fit_batch without waiting: the records stay on the device (fit_records_device) and
         their download is queued; sample_fit_batch_end(pairs) collects the host table.  Work queued in between (the
         device plan, the warp) does not delay that download."""
-        if grid_flow.device != self.device:
-            grid_flow = grid_flow.to(self.device)
-        grid_flow = grid_flow.contiguous()
-        pairs, gh, gw, _ = grid_flow.shape
+        grid_flow, blocked, pairs, gh, gw = self._fit_inputs(grid_flow, blocked)
         self.use_torch_stream()
-        _check(self.lib.vstab_sample_fit_batch_begin(self.handle, _dev_ptr(grid_flow), pairs, gh, gw, int(step), MODES[requested_mode]),
-               "vstab_sample_fit_batch_begin")
-        self._fit_grid = grid_flow   # keep the input alive until the kernels have run
+        if blocked is not None:
+            _check(self.lib.vstab_sample_fit_batch_begin_masked(self.handle, _dev_ptr(grid_flow), pairs, gh, gw, int(step),
+                                                                MODES[requested_mode], _dev_ptr(blocked)),
+                   "vstab_sample_fit_batch_begin_masked")
+        else:
+            _check(self.lib.vstab_sample_fit_batch_begin(self.handle, _dev_ptr(grid_flow), pairs, gh, gw, int(step), MODES[requested_mode]),
+                   "vstab_sample_fit_batch_begin")
+        self._fit_grid = (grid_flow, blocked)   # keep the inputs alive until the kernels have run
         return pairs
 
     def fit_records_device(self) -> int:

@@ -422,6 +422,44 @@ class VideoStabilizerTemporalFill(io.ComfyNode):
         return io.NodeOutput(_image_out(dst, out_context), _mask_out(mask), out_meta)
 
 
+class VideoStabilizerFlowMasked(io.ComfyNode):
+    """The Flow node with an estimation mask: the pixels of `exclude_mask` (a segmentation of the moving subject, or one mask
+    for a burnt-in logo) take no part in the camera-motion fit.  Not one of the reference's nodes: it is registered by the
+    extension but kept out of NODE_CLASSES."""
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        schema = io.Schema(
+            node_id="video_stabilizer_flow_masked",
+            display_name="Video Stabilizer Flow (Masked)",
+            category="Video/Stabilization",
+            description=("Video Stabilizer Flow that estimates the camera motion from the pixels outside a mask, so that a "
+                         "moving subject in front of the camera does not become the motion that is removed."),
+        )
+        base = VideoStabilizerFlow.define_schema()
+        schema.inputs = list(base.inputs) + [
+            io.Mask.Input("exclude_mask", display_name="Exclude Mask",
+                          tooltip=("Per-frame mask (or one mask for the whole clip) at the frames' resolution; values above "
+                                   "0.5 mark pixels the motion estimate must not use.")),
+            io.Int.Input("mask_margin", default=16, min=0, max=64, display_name="Mask Margin",
+                         tooltip="Safety margin around the mask, in pixels of the estimation image (long side 960)."),
+        ]
+        schema.outputs = _estimator_outputs()
+        return schema
+
+    @classmethod
+    def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
+                strength: float, smooth: float, keep_fov: float, padding_color: str, exclude_mask: Any,
+                mask_margin: int) -> io.NodeOutput:
+        context = hm._normalize_video_input(frames)
+        result = _stabilize_frames(
+            context, framing_mode, transform_mode, camera_lock, strength, smooth, keep_fov,
+            hm._parse_padding_color(padding_color), frame_rate, keep_on_device=True, estimator="flow",
+            estimation_mask=exclude_mask, mask_margin=int(mask_margin),
+        )
+        return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
+
+
 NODE_CLASSES = [VideoStabilizerClassic, VideoStabilizerFlow, VideoStabilizerMotionApply, VideoStabilizerShakeGenerator,
                 VideoStabilizerShakeGeneratorManual, VideoStabilizerInverse]
 
@@ -453,3 +491,11 @@ class VideoStabilizerAmdExtension(ComfyExtension):
                 output_mapping=[{"new_idx": 0, "old_idx": 0}, {"new_idx": 1, "old_idx": 1}, {"new_idx": 2, "old_idx": 2}],
             )
         )
+
+
+class VideoStabilizerAmdMaskedExtension(VideoStabilizerAmdExtension):
+    """What comfy_entrypoint() hands to ComfyUI: the base extension's seven nodes plus Video Stabilizer Flow (Masked).  The
+    base class keeps its own list, so code that instantiates it sees what it saw before the masked node existed."""
+
+    async def get_node_list(self) -> list:
+        return await super().get_node_list() + [VideoStabilizerFlowMasked]

@@ -234,6 +234,36 @@ int vstab_sample_fit_batch_begin(vstab_ctx* ctx, const float* grid_flow, int pai
 const vstab_fit_record* vstab_fit_records_device(vstab_ctx* ctx);
 int vstab_sample_fit_batch_end(vstab_ctx* ctx, int pairs, vstab_fit_record* results);
 
+/* ---- Estimation mask (not a reference feature): keep moving subjects out of the fit ------------
+ * The fit answers "what does the largest coherent set of samples do"; a subject that owns more samples than the
+ * background becomes the estimate.  A caller that knows where the subject is (a segmentation MASK per frame, or one
+ * mask for a burnt-in logo) names the samples the fit must not use.  The rule:
+ *   - a full-resolution pixel is SUBJECT iff its mask value is > 0.5 or is not finite;
+ *   - a working pixel (X, Y) is COVERED iff a subject pixel lies in its INTER_AREA footprint
+ *     x in [floor(X*src_w/work_w), ceil((X+1)*src_w/work_w)), y likewise (the pixel itself without a downscale);
+ *   - grid sample (gx*step, gy*step) of a frame is BLOCKED iff a covered working pixel lies in the square
+ *     |dX| <= margin, |dY| <= margin around it, clipped to the image (margin in working pixels, 0..64);
+ *   - sample g of pair (i, i+1) is ADMITTED iff it is blocked neither in frame i nor in frame i+1.
+ * vstab_mask_block_grid: mask dev [n_masks,src_h,src_w] f32 with n_masks == n_frames, or 1 (one mask for the whole
+ * clip: reduced once, written to every frame) -> blocked dev [n_frames,gh,gw] u8 (0 / 1; gh = ceil(work_h/step),
+ * gw = ceil(work_w/step)).  Every mask value is read once; asynchronous on the context's stream; timing kind "mask".
+ * src_w <= 8192.
+ */
+int vstab_mask_block_grid(vstab_ctx* ctx, const float* mask, int n_masks, int n_frames, int src_h, int src_w,
+                          int work_h, int work_w, int step, int margin, uint8_t* blocked);
+/* vstab_sample_fit_batch / _begin on the admitted samples only: blocked dev [pairs+1,gh,gw] u8 (frame i of the clip
+ * at row i).  The fit is flow.py:141-210 with prev_points restricted to the admitted grid positions, order kept: same
+ * validity filter, same `< 12` rule, same RANSAC sample sequence for that point count; total_points = admitted samples
+ * (translation confidence = valid / admitted).  With nothing blocked the records are those of vstab_sample_fit_batch,
+ * byte for byte; otherwise matrix, accepted, residual, valid_points and the similarity / perspective confidence are
+ * what vstab_sample_fit_batch returns for the same grid with NaN written into the samples that are not admitted.
+ * The records of _begin_masked are collected as those of _begin (vstab_fit_records_device, vstab_fit_records_copy,
+ * vstab_sample_fit_batch_end). */
+int vstab_sample_fit_batch_masked(vstab_ctx* ctx, const float* grid_flow, int pairs, int gh, int gw,
+                                  int step, int requested_mode, const uint8_t* blocked, vstab_fit_record* results);
+int vstab_sample_fit_batch_begin_masked(vstab_ctx* ctx, const float* grid_flow, int pairs, int gh, int gw,
+                                        int step, int requested_mode, const uint8_t* blocked);
+
 /* ---- N1 (crop framing): coverage analysis for the keep_fov crop solver ---------
  * Replaces the per-frame cv2 calls of nodes/stabilizer_utils.py:611-643
  * (finalize_with_masks: warpPerspective(ones, NEAREST) > 0.5, dilate 3x3, erode 3x3, bounding box of
