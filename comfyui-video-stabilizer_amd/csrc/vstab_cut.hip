@@ -1,0 +1,128 @@
+// vstab_cut.hip -- scene cuts: the motion-compensated residual of every consecutive pair of estimation images
+// (vstab_pair_residual_batch).  Not a reference feature; the rule is stated in include/vstab.h.
+//
+// One kernel.  A workgroup owns CUT_ROWS rows of one pair; a lane takes 16 pixels of a row of the FROM image with one
+// 16-byte load, maps each through the pair's transition (fp64 from the float32 matrix, the rule's association), rounds
+// half-to-even and looks the TO image up there with a byte load.  A shake-sized transition keeps those lookups within a
+// few rows of the pixel, so both images of a pair cross HBM about once: ~2 * h * w bytes per pair.  Everything that is
+// summed is an integer (|a - b| <= 255, counts), so lane order, wave order and the order of the atomics do not show in
+// the result: lane sums (u32) -> wave reduction by shuffles -> LDS -> one atomic per workgroup and array.
+#include "vstab_internal.h"
+
+namespace {
+
+constexpr int CUT_ROWS = 16;      // rows of a pair per workgroup (960x540: 34 workgroups per pair, 3.75 loads per lane)
+constexpr int CUT_THREADS = 256;
+constexpr int CUT_WAVES = CUT_THREADS / 64;
+
+struct CutMatrix {
+    double m[9];
+};
+
+// one pixel of the rule: returns 1 and *q (index into the TO image) if p = (x, y) lands inside
+__device__ __forceinline__ bool cut_lookup(const CutMatrix& A, int x, int y, int h, int w, int* q)
+{
+    const double dx = (double)x, dy = (double)y;
+    const double X = (A.m[0] * dx + A.m[1] * dy) + A.m[2];
+    const double Y = (A.m[3] * dx + A.m[4] * dy) + A.m[5];
+    const double W = (A.m[6] * dx + A.m[7] * dy) + A.m[8];
+    if (!(W > 0.0 && W <= 1.7976931348623157e308)) return false;   // w <= 0 or not finite
+    // (X / 1.0 is X: the division is skipped where it changes no bit)
+    const double qx = (W == 1.0) ? X : X / W, qy = (W == 1.0) ? Y : Y / W;
+    const double rx = rint(qx), ry = rint(qy);          // half-to-even; NaN / inf fail the comparisons below
+    if (!(rx >= 0.0 && rx <= (double)(w - 1) && ry >= 0.0 && ry <= (double)(h - 1))) return false;
+    *q = (int)ry * w + (int)rx;
+    return true;
+}
+
+// VEC: w % 16 == 0 and the base 16-byte aligned (every row then is)
+template <bool VEC>
+__global__ __launch_bounds__(CUT_THREADS) void pair_residual_kernel(const uint8_t* __restrict__ gray, const float* __restrict__ mats,
+                                                                    int h, int w, int tiles, unsigned long long* __restrict__ sum_abs,
+                                                                    unsigned* __restrict__ inside)
+{
+    __shared__ unsigned s_sum[CUT_WAVES], s_in[CUT_WAVES];
+    const int pair = (int)blockIdx.x / tiles, tile = (int)blockIdx.x - pair * tiles;
+    const int y0 = tile * CUT_ROWS, rows = min(CUT_ROWS, h - y0);
+    CutMatrix A;
+    for (int k = 0; k < 9; k++) A.m[k] = (double)mats[(size_t)pair * 9 + k];
+    const uint8_t* __restrict__ from = gray + (size_t)pair * h * w;
+    const uint8_t* __restrict__ to = from + (size_t)h * w;
+    const int chunks = (w + 15) >> 4;                   // 16-pixel pieces of a row
+    unsigned acc = 0, cnt = 0;                          // <= 255 * 16 * (CUT_ROWS * chunks / CUT_THREADS + 1): far below 2^32
+    for (int item = threadIdx.x; item < rows * chunks; item += CUT_THREADS) {
+        const int r = item / chunks, c = item - r * chunks;
+        const int y = y0 + r, x0 = c << 4;
+        const uint8_t* __restrict__ row = from + (size_t)y * w;
+        if (VEC) {
+            const uint4 v = *reinterpret_cast<const uint4*>(row + x0);
+            const unsigned word[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                int q;
+                if (cut_lookup(A, x0 + k, y, h, w, &q)) {
+                    const int a = (int)((word[k >> 2] >> ((k & 3) * 8)) & 0xffu), b = (int)to[q];
+                    acc += (unsigned)abs(a - b);
+                    cnt += 1;
+                }
+            }
+        } else {
+            const int x1 = min(w, x0 + 16);
+            for (int x = x0; x < x1; x++) {
+                int q;
+                if (cut_lookup(A, x, y, h, w, &q)) {
+                    acc += (unsigned)abs((int)row[x] - (int)to[q]);
+                    cnt += 1;
+                }
+            }
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        acc += __shfl_down(acc, off, 64);
+        cnt += __shfl_down(cnt, off, 64);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        s_sum[wave] = acc;
+        s_in[wave] = cnt;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long total = 0;
+        unsigned count = 0;
+        for (int k = 0; k < CUT_WAVES; k++) {
+            total += s_sum[k];
+            count += s_in[k];
+        }
+        if (count) {
+            atomicAdd(&sum_abs[pair], total);
+            atomicAdd(&inside[pair], count);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int vstab_pair_residual_batch(vstab_ctx* ctx, const uint8_t* gray, int n, int h, int w, const float* transitions,
+                                         uint64_t* sum_abs, uint32_t* inside)
+{
+    VSTAB_REQUIRE(ctx != nullptr, "vstab_pair_residual_batch: ctx is NULL");
+    VSTAB_REQUIRE(gray && transitions && sum_abs && inside, "vstab_pair_residual_batch: NULL pointer argument");
+    VSTAB_REQUIRE(n >= 2 && h > 0 && w > 0, "vstab_pair_residual_batch: needs at least two frames of a positive size (n=%d, %dx%d)", n, w, h);
+    VSTAB_REQUIRE((long long)h * w < 0x7fffffffLL, "vstab_pair_residual_batch: %dx%d image too large", w, h);
+    const int pairs = n - 1, tiles = (h + CUT_ROWS - 1) / CUT_ROWS;
+    VSTAB_REQUIRE((long long)pairs * tiles < 0x7fffffffLL, "vstab_pair_residual_batch: clip too large");
+    VSTAB_HIP(hipSetDevice(ctx->device));
+    void* d_mats = nullptr;
+    if (int rc = vstab_stage_params(ctx, transitions, (size_t)pairs * 9 * sizeof(float), &d_mats)) return rc;
+    VSTAB_HIP(hipMemsetAsync(sum_abs, 0, (size_t)pairs * sizeof(uint64_t), ctx->stream));
+    VSTAB_HIP(hipMemsetAsync(inside, 0, (size_t)pairs * sizeof(uint32_t), ctx->stream));
+    KernelTimer timer(ctx, "cut");
+    const bool vec = (w % 16 == 0) && (reinterpret_cast<uintptr_t>(gray) % 16 == 0);
+    const dim3 grid((unsigned)(pairs * tiles)), block(CUT_THREADS);
+    unsigned long long* sums = reinterpret_cast<unsigned long long*>(sum_abs);
+    if (vec) hipLaunchKernelGGL(pair_residual_kernel<true>, grid, block, 0, ctx->stream, gray, static_cast<const float*>(d_mats), h, w, tiles, sums, inside);
+    else hipLaunchKernelGGL(pair_residual_kernel<false>, grid, block, 0, ctx->stream, gray, static_cast<const float*>(d_mats), h, w, tiles, sums, inside);
+    VSTAB_HIP(hipGetLastError());
+    return 0;
+}

@@ -215,7 +215,7 @@ def _lap(stats, key, t0):
 def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, transform_mode: str, camera_lock: bool,
                       strength: float, smooth: float, keep_fov: float, padding_rgb, frame_rate: float, group=None,
                       estimator: str = "flow", stats: Optional[Dict[str, float]] = None, want_meta: bool = True,
-                      check_value_range: bool = True, temporal_fill: int = 0, estimation_mask=None):
+                      check_value_range: bool = True, temporal_fill: int = 0, estimation_mask=None, scene_cuts=None):
     """Sharded equivalent of `_stabilize_frames` (flow.py:213-640).
 
     local_frames: device tensor [n_local (+1 halo for rank > 0 that owns frames), H, W, 3] float32 -- this rank's frames
@@ -232,6 +232,11 @@ def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, t
         # the mask would have to be sharded with the frames, halo frame included; every rank raises alike, before any collective
         raise ValueError("stabilize_sharded does not support estimation_mask: the sharded path does not distribute a mask "
                          "with each rank's frames and halo; run the single-GPU pipeline for a masked estimation")
+    if scene_cuts is not None:
+        # a shot may span ranks: the per-shot mode walk and trajectory would need every rank's records before the plan, which
+        # the sharded plan (one continuous camera move) does not form; every rank raises alike, before any collective
+        raise ValueError("stabilize_sharded does not support scene_cuts: scene cuts are not sharded (the sharded plan treats the "
+                         "clip as one continuous camera move); run the single-GPU pipeline for a scene-aware stabilization")
     import torch.distributed as dist
 
     from . import native

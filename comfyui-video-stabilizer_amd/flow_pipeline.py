@@ -23,6 +23,7 @@ import numpy as np
 
 from . import host_math as hm
 from . import native
+from . import scene_cuts as scene_cuts_mod
 from . import temporal_fill as temporal_fill_mod
 from .comfy_compat import ProgressBar, check_interrupt
 from .meta_v2 import applied_motion_meta_from_arrays, applied_motion_meta_from_stabilization_warp
@@ -154,40 +155,45 @@ def select_transitions(fit_records, requested_mode: str):
     return mats, modes, confs.tolist(), resids.tolist(), _MODE_NAME[active]
 
 
-def _gray(ctx, device_frames, working_size, peaks_out):
-    """F2, plus the per-frame maxima of the same pass when the caller still owes the value-range sniff (F0)."""
+def _gray(ctx, device_frames, working_size, peaks_out, gray_out=None):
+    """F2, plus the per-frame maxima of the same pass when the caller still owes the value-range sniff (F0).
+    gray_out: a list that receives the estimation images themselves (the scene-cut score reads them after the fits)."""
     if peaks_out is None:
-        return ctx.gray_downscale(device_frames, working_size)
-    gray, peaks = ctx.gray_downscale(device_frames, working_size, want_range=True)
-    peaks_out.append(hm.prefetch_peaks(peaks))
+        gray = ctx.gray_downscale(device_frames, working_size)
+    else:
+        gray, peaks = ctx.gray_downscale(device_frames, working_size, want_range=True)
+        peaks_out.append(hm.prefetch_peaks(peaks))
+    if gray_out is not None:
+        gray_out.append(gray)
     return gray
 
 
 def estimate_transitions(ctx, device_frames, working_size, transform_mode: str, clip_start: bool = True, peaks_out=None,
-                         blocked=None):
+                         blocked=None, gray_out=None):
     """F2-F5 for frames [N,H,W,3] on the device -> per-pair candidate fits (structured table [N-1,3]).
     peaks_out: a list that receives the device tensor of per-frame maxima (see host_math.resolve_value_range).
     blocked: the estimation mask's block grid (u8 [N,gh,gw], Context.mask_block_grid); the flow itself is computed on the
     unmasked images."""
-    gray = _gray(ctx, device_frames, working_size, peaks_out)
+    gray = _gray(ctx, device_frames, working_size, peaks_out, gray_out)
     _, grid = ctx.dis_flow_batch(gray, sample_step=SAMPLE_STEP, want_full=False, want_grid=True, clip_start=clip_start)
     return ctx.sample_fit_batch(grid, SAMPLE_STEP, transform_mode, blocked=blocked)
 
 
-def estimate_transitions_phase(ctx, device_frames, working_size, transform_mode: str, clip_start: bool = True, peaks_out=None):
+def estimate_transitions_phase(ctx, device_frames, working_size, transform_mode: str, clip_start: bool = True, peaks_out=None,
+                               gray_out=None):
     """Fallback estimator (flow.py:110-130, 325-330): phase correlation of consecutive estimation images.  Every pair
     is reported as a "translation" fit whatever `transform_mode` asks for; confidence = peak response, residual 0."""
-    gray = _gray(ctx, device_frames, working_size, peaks_out)
+    gray = _gray(ctx, device_frames, working_size, peaks_out, gray_out)
     table, _ = ctx.phase_correlate_batch(gray)
     return table
 
 
 def estimate_transitions_tvl1(ctx, device_frames, working_size, transform_mode: str, clip_start: bool = True, peaks_out=None,
-                              blocked=None):
+                              blocked=None, gray_out=None):
     """Second dense estimator (flow.py:76-80, 140-147): Dual TV-L1 flow with OpenCV's default parameters on the
     estimation images, sampled and fitted exactly as the DIS flow is.  Pairs are independent (no initial flow), so
     clip_start does not matter."""
-    gray = _gray(ctx, device_frames, working_size, peaks_out)
+    gray = _gray(ctx, device_frames, working_size, peaks_out, gray_out)
     _, grid, _ = ctx.tvl1_flow_batch(gray, sample_step=SAMPLE_STEP, want_full=False, want_grid=True)
     return ctx.sample_fit_batch(grid, SAMPLE_STEP, transform_mode, blocked=blocked)
 
@@ -200,10 +206,11 @@ CLASSIC_GFTT = dict(max_corners=400, quality=0.01, min_distance=7.0, block_size=
 CLASSIC_LK = dict(win=31, max_level=3, max_count=50, epsilon=0.01)
 
 
-def estimate_transitions_classic(ctx, device_frames, working_size, transform_mode: str, clip_start: bool = True, peaks_out=None):
+def estimate_transitions_classic(ctx, device_frames, working_size, transform_mode: str, clip_start: bool = True, peaks_out=None,
+                                 gray_out=None):
     """Classic estimator (classic.py:69-160) for frames [N,H,W,3] on the device -> candidate fits [N-1,3]:
     corners of frame i (HIP) -> pyramidal LK into frame i+1 (HIP) -> model fits on the tracked pairs (HIP)."""
-    gray = _gray(ctx, device_frames, working_size, peaks_out)
+    gray = _gray(ctx, device_frames, working_size, peaks_out, gray_out)
     corners, counts = ctx.gftt_batch(gray[:-1], **CLASSIC_GFTT)
     pairs = ctx.lk_track_batch(gray, corners, counts, **CLASSIC_LK)
     return ctx.points_fit_batch(pairs, counts, transform_mode)
@@ -256,22 +263,54 @@ def plan_stabilization(*args, **kwargs) -> "FlowPlan":
         return _plan_stabilization(*args, **kwargs)
 
 
+def _select_per_segment(fit_records, transform_mode: str, segments):
+    """select_transitions run shot by shot: the sticky walk restarts at the requested mode in every segment, and the pair
+    across each cut is reported in the "no candidate" form (identity, confidence 0, residual 0, "translation").
+    -> the five values of select_transitions for the whole clip; the active mode is the last segment's."""
+    table = fit_records if isinstance(fit_records, np.ndarray) else native.fit_table_from_dicts(fit_records)
+    pairs = table.shape[0]
+    work_mats = np.tile(np.eye(3, dtype=np.float32), (pairs, 1, 1))
+    modes, confs, resids = ["translation"] * pairs, [0.0] * pairs, [0.0] * pairs
+    active = transform_mode
+    for s, e in segments:
+        if e - s < 2:           # a one-frame shot has no transition of its own
+            active = transform_mode
+            continue
+        m, md, cf, rs, active = select_transitions(table[s:e - 1], transform_mode)
+        work_mats[s:e - 1] = m
+        modes[s:e - 1], confs[s:e - 1], resids[s:e - 1] = md, cf, rs
+    return work_mats, modes, confs, resids, active
+
+
 def _plan_stabilization(ctx, fit_records, size, total_frames, framing_mode, transform_mode, camera_lock, strength, smooth,
-                       keep_fov, padding_rgb, fps_effective, fps_requested, estimator: str = "flow") -> FlowPlan:
+                       keep_fov, padding_rgb, fps_effective, fps_requested, estimator: str = "flow", segments=None) -> FlowPlan:
     """flow.py:324-546 for a whole clip: sticky-mode selection, parameter deltas, trajectory (HIP fp64),
-    framing geometry.  `fit_records` covers all N-1 transitions of the clip."""
+    framing geometry.  `fit_records` covers all N-1 transitions of the clip.
+    segments (scene cuts; None: one continuous camera move, the reference's behaviour): frame ranges [s, e) of the shots.
+    Selection and trajectory run per shot -- every shot's path starts at 0 -- and are concatenated; the framing below stays
+    global, so there is one output geometry."""
     width, height = size
     rgb_list = [int(c) for c in padding_rgb]
     base_mode = transform_mode
     working_size = hm._working_estimation_size(width, height)
-    work_mats, modes_used, confidences, residuals, active_mode = select_transitions(fit_records, transform_mode)
+    if segments is None:
+        work_mats, modes_used, confidences, residuals, active_mode = select_transitions(fit_records, transform_mode)
+    else:
+        work_mats, modes_used, confidences, residuals, active_mode = _select_per_segment(fit_records, transform_mode, segments)
     # rescale to full resolution + parameter deltas (flow.py:340-346), one library call over the clip
     matrices, delta_params = native.transitions_to_params(work_mats, base_mode, size, working_size)
 
     # ---- trajectory (F7-F8) --------------------------------------------------
     strength = float(np.clip(strength, 0.0, 1.0))
     smooth = float(np.clip(smooth, 0.0, 1.0))
-    path, target_path = ctx.trajectory(delta_params, smooth, fps_effective, strength, bool(camera_lock))
+    if segments is None:
+        path, target_path = ctx.trajectory(delta_params, smooth, fps_effective, strength, bool(camera_lock))
+    else:
+        path = np.zeros((total_frames, delta_params.shape[1]), np.float64)
+        target_path = np.zeros_like(path)
+        for s, e in segments:
+            if e - s >= 2:      # (the transitions are converted pair by pair, so a shot's deltas are its slice of the clip's)
+                path[s:e], target_path[s:e] = ctx.trajectory(delta_params[s:e - 1], smooth, fps_effective, strength, bool(camera_lock))
     if camera_lock:
         smooth = max(smooth, 0.85)
     diffs = target_path - path
@@ -571,6 +610,19 @@ def estimation_mask_meta(fit_records, margin: int, mask_frames: int, grid_sample
             "blocked_fraction_max": float(fraction.max()), "admitted_points_min": int(admitted.min())}
 
 
+# ---- scene cuts (beyond the reference; scene_cuts.py, the rule is in include/vstab.h) -----------------------------------
+def _scene_segments(ctx, scene, fit_records, gray_out, transform_mode: str, total_frames: int):
+    """-> (segments [s, e) of frames, meta["scene_cuts"]).  "auto": one launch of the residual kernel over the estimation
+    images the estimator made, scored with each pair's own best candidate; "given": the caller's edit list."""
+    if scene.mode == "given":
+        return scene_cuts_mod.segments_from_cuts(scene.cuts, total_frames), scene_cuts_mod.meta_block(scene, scene.cuts)
+    gray = gray_out[0]
+    sum_abs, inside = ctx.pair_residual_batch(gray, scene_cuts_mod.scoring_transitions(fit_records, transform_mode))
+    scores, overlap = scene_cuts_mod.scores_and_overlap(sum_abs, inside, int(gray.shape[1]), int(gray.shape[2]))
+    cuts = scene_cuts_mod.cuts_from_pairs(scene_cuts_mod.is_cut(scores, overlap, scene.threshold))
+    return scene_cuts_mod.segments_from_cuts(cuts, total_frames), scene_cuts_mod.meta_block(scene, cuts, scores, overlap)
+
+
 def _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode, camera_lock,
                                 strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested, pbar, progress_total,
                                 keep_on_device, temporal_fill=0, blocked=None, mask_info=None):
@@ -642,6 +694,8 @@ def _stabilize_frames(
     temporal_fill: int = 0,
     estimation_mask=None,
     mask_margin: int = 16,
+    scene_cuts=None,
+    cut_threshold=None,
 ) -> hm.StabilizationResult:
     """Positional signature of the reference (flow.py:213-223); keyword-only extras select the GPU
     context, keep outputs resident in HBM (multi-GPU sharding lives in distributed.py) or switch the
@@ -652,7 +706,13 @@ def _stabilize_frames(
     estimation_mask (beyond the reference, None by default): [N,H,W], [1,H,W] or [H,W] float at the frames' resolution, > 0.5
     or not finite where a moving subject (or a burnt-in logo) is; the DIS / TV-L1 flow samples within mask_margin working
     pixels of it in either frame of a pair stay out of that pair's fit (include/vstab.h states the rule) and
-    meta["estimation_mask"] reports how many.  None: the reference's behaviour and meta.  Bypass paths ignore it."""
+    meta["estimation_mask"] reports how many.  None: the reference's behaviour and meta.  Bypass paths ignore it.
+    scene_cuts (beyond the reference, None by default): "auto" finds the hard cuts of the clip from the motion-compensated
+    residual of every pair (scene_cuts.py; include/vstab.h states the rule; cut_threshold None: the calibrated default), a
+    strictly increasing sequence of frame indices in 1..N-1 names the first frames of the shots instead.  Mode selection
+    and trajectory then run per shot, the transition across a cut is reported as "no candidate", framing stays global and
+    meta["scene_cuts"] reports cuts and scores.  None: the reference's behaviour and meta.  Bypass paths ignore it."""
+    scene = scene_cuts_mod.check_request(scene_cuts, cut_threshold)
     if estimator not in _META_SOURCE:
         raise ValueError(f"Unknown estimator {estimator!r}; expected 'flow' or 'classic'.")
     temporal_fill = int(temporal_fill)
@@ -714,6 +774,8 @@ def _stabilize_frames(
 
     if estimation_mask is not None:
         check_estimation_mask_shape(estimation_mask, total_frames, size)
+    if scene is not None and scene.mode == "given":
+        scene_cuts_mod.check_given_cuts(scene.cuts, total_frames)
     ctx = ctx or native.default_context()
     device_frames = context.device_batch(ctx)
     working_size = hm._working_estimation_size(context.width, context.height)
@@ -724,7 +786,8 @@ def _stabilize_frames(
         mask_info = (mask_margin, mask_frames, int(blocked.shape[1] * blocked.shape[2]))
         masked = {"blocked": blocked}
 
-    if device_plan_applies(estimator, framing_mode, transform_mode, total_frames):
+    # (scene-aware calls form the plan on the host: plan_kernel knows one continuous camera move)
+    if scene is None and device_plan_applies(estimator, framing_mode, transform_mode, total_frames):
         done = _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode,
                                            camera_lock, strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested,
                                            pbar, progress_total, keep_on_device, temporal_fill, blocked, mask_info)
@@ -735,6 +798,8 @@ def _stabilize_frames(
     # ---- estimation (F2-F5) -------------------------------------------------
     estimate = _ESTIMATORS[estimator]
     peaks = [] if context.range_pending else None
+    if scene is not None and scene.mode == "auto":
+        masked = dict(masked, gray_out=[])     # the estimation images stay alive for the score below
     fit_records = estimate(ctx, device_frames, working_size, transform_mode, peaks_out=peaks, **masked)
     if peaks and hm.resolve_value_range(context, peaks[0], ctx):
         # F0 (stabilizer_utils.py:127-131): some frame turned out to be 0..255 float data.  The estimation above ran
@@ -742,12 +807,17 @@ def _stabilize_frames(
         # have been rescaled now, so it is repeated on the rescaled clip.  0..1 input -- the ComfyUI IMAGE contract --
         # never takes this branch.
         device_frames = context.device_batch(ctx)
+        if "gray_out" in masked:
+            masked["gray_out"] = []
         fit_records = estimate(ctx, device_frames, working_size, transform_mode, **masked)
     progress_done = _replay_progress(pbar, 0, total_frames - 1, progress_total)
     check_interrupt()
 
+    segments = scene_block = None
+    if scene is not None:
+        segments, scene_block = _scene_segments(ctx, scene, fit_records, masked.get("gray_out"), transform_mode, total_frames)
     plan = plan_stabilization(ctx, fit_records, size, total_frames, framing_mode, transform_mode, camera_lock, strength,
-                              smooth, keep_fov, padding_rgb, fps_effective, fps_requested, estimator=estimator)
+                              smooth, keep_fov, padding_rgb, fps_effective, fps_requested, estimator=estimator, segments=segments)
     if plan.bypass_meta is not None:  # crop + keep_fov ~ 1 (flow.py:387-429): original frames
         pbar.update_absolute(progress_total, progress_total)
         frames_out = device_frames if keep_on_device else _host_frames(context)
@@ -764,6 +834,8 @@ def _stabilize_frames(
     meta = complete_meta(meta, plan, _counts_to_host(counts))
     if mask_info is not None:
         meta["estimation_mask"] = estimation_mask_meta(fit_records, *mask_info)
+    if scene_block is not None:
+        meta["scene_cuts"] = scene_block
     _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill)
     check_interrupt()
     verdict = {"used": False, "mismatched_frames": 0}

@@ -170,6 +170,8 @@ _SIGNATURES = {
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vstab_sample_fit_batch_begin_masked": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vstab_pair_residual_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vstab_fit_records_device": (C.c_void_p, [C.c_void_p]),
     "vstab_sample_fit_batch_end": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "vstab_flow_plan_device": (
@@ -669,6 +671,27 @@ class Context:
         _check(self.lib.vstab_mask_block_grid(self.handle, _dev_ptr(mask), n_masks, int(n_frames), sh, sw, wh, ww, int(step),
                                               int(margin), _dev_ptr(blocked)), "vstab_mask_block_grid")
         return blocked
+
+    def pair_residual_batch(self, gray, transitions):
+        """Scene cuts: the motion-compensated residual of every consecutive pair (vstab_pair_residual_batch; the rule is in
+        include/vstab.h).  gray u8 [N,h,w] (device), transitions f32 [N-1,3,3] at working resolution (x_{i+1} = A_i x_i) ->
+        (sum_abs int64 [N-1], inside int64 [N-1]) on the host: integers, equal to the NumPy restatement exactly."""
+        torch = self.torch
+        if gray.dtype != torch.uint8 or gray.dim() != 3:
+            raise ValueError("pair_residual_batch expects a uint8 [N,h,w] tensor")
+        gray = gray.to(self.device).contiguous()
+        n, h, w = (int(v) for v in gray.shape)
+        if n < 2:
+            raise ValueError("pair_residual_batch needs at least two frames")
+        m = np.ascontiguousarray(transitions, dtype=np.float32)
+        if m.size != (n - 1) * 9:
+            raise ValueError(f"pair_residual_batch: transitions {m.shape} are not [{n - 1},3,3] for {n} frames")
+        sums = torch.empty((n - 1,), dtype=torch.int64, device=self.device)      # the library's u64 / u32, in torch's containers
+        inside = torch.empty((n - 1,), dtype=torch.int32, device=self.device)
+        self.use_torch_stream()
+        _check(self.lib.vstab_pair_residual_batch(self.handle, _dev_ptr(gray), n, h, w, m.ctypes.data, _dev_ptr(sums),
+                                                  _dev_ptr(inside)), "vstab_pair_residual_batch")
+        return sums.cpu().numpy(), inside.cpu().numpy().astype(np.int64)
 
     def _fit_inputs(self, grid_flow, blocked):
         if grid_flow.device != self.device:

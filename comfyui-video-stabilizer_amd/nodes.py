@@ -460,6 +460,44 @@ class VideoStabilizerFlowMasked(io.ComfyNode):
         return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
 
 
+class VideoStabilizerFlowScenes(io.ComfyNode):
+    """The Flow node on an edited clip: hard cuts are found from the motion-compensated residual of every pair
+    (scene_cuts.py) and every shot is stabilized on its own path, under one common framing.  Not one of the reference's
+    nodes: it is listed by an extension but kept out of NODE_CLASSES."""
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        from .scene_cuts import DEFAULT_CUT_THRESHOLD
+
+        schema = io.Schema(
+            node_id="video_stabilizer_flow_scenes",
+            display_name="Video Stabilizer Flow (Scene-Aware)",
+            category="Video/Stabilization",
+            description=("Video Stabilizer Flow that detects hard cuts and stabilizes each shot separately, so that a cut "
+                         "neither enters the camera path nor pushes the frames on both sides of it out of place."),
+        )
+        base = VideoStabilizerFlow.define_schema()
+        schema.inputs = list(base.inputs) + [
+            io.Float.Input("cut_threshold", default=DEFAULT_CUT_THRESHOLD, min=0.0, max=255.0, step=0.1, display_name="Cut Threshold",
+                           tooltip=("Mean absolute difference (0..255) of two consecutive frames after motion compensation at "
+                                    "and above which the pair is a cut.  0 uses the default, which was calibrated on "
+                                    "synthetic clips only: lower it if cuts between similar scenes are missed.")),
+        ]
+        schema.outputs = _estimator_outputs()
+        return schema
+
+    @classmethod
+    def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
+                strength: float, smooth: float, keep_fov: float, padding_color: str, cut_threshold: float) -> io.NodeOutput:
+        context = hm._normalize_video_input(frames)
+        result = _stabilize_frames(
+            context, framing_mode, transform_mode, camera_lock, strength, smooth, keep_fov,
+            hm._parse_padding_color(padding_color), frame_rate, keep_on_device=True, estimator="flow",
+            scene_cuts="auto", cut_threshold=float(cut_threshold) if cut_threshold else None,
+        )
+        return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
+
+
 NODE_CLASSES = [VideoStabilizerClassic, VideoStabilizerFlow, VideoStabilizerMotionApply, VideoStabilizerShakeGenerator,
                 VideoStabilizerShakeGeneratorManual, VideoStabilizerInverse]
 
@@ -499,3 +537,11 @@ class VideoStabilizerAmdMaskedExtension(VideoStabilizerAmdExtension):
 
     async def get_node_list(self) -> list:
         return await super().get_node_list() + [VideoStabilizerFlowMasked]
+
+
+class VideoStabilizerAmdScenesExtension(VideoStabilizerAmdMaskedExtension):
+    """The masked extension's eight nodes plus Video Stabilizer Flow (Scene-Aware).  A class of its own for the reason the
+    masked one is: the extensions before it keep the lists they had."""
+
+    async def get_node_list(self) -> list:
+        return await super().get_node_list() + [VideoStabilizerFlowScenes]

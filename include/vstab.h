@@ -264,6 +264,26 @@ int vstab_sample_fit_batch_masked(vstab_ctx* ctx, const float* grid_flow, int pa
 int vstab_sample_fit_batch_begin_masked(vstab_ctx* ctx, const float* grid_flow, int pairs, int gh, int gw,
                                         int step, int requested_mode, const uint8_t* blocked);
 
+/* ---- Scene cuts (not a reference feature): the motion-compensated residual of every consecutive pair ------------
+ * A hard cut is the one pair whose two images no camera move explains.  The score of pair i is the mean absolute
+ * difference of its two estimation images AFTER the pair's own transition A_i (x_{i+1} = A_i x_i, the direction the
+ * fit reports, flow.py:133-210): frame i is the FROM image, frame i+1 the TO image, and no matrix is inverted.  The rule,
+ * for pair i and every pixel p = (x, y) of frame i (x, y as fp64 integers, A = the float32 matrix widened to fp64):
+ *   - X = (A0*x + A1*y) + A2,  Y = (A3*x + A4*y) + A5,  W = (A6*x + A7*y) + A8  -- separate IEEE multiplies and adds in
+ *     exactly this association, nothing fused;
+ *   - W <= 0 or W not finite: the pixel does not count.  Otherwise q = (X / W, Y / W), each coordinate rounded to the
+ *     nearest integer, ties to even (rint); a coordinate that is not finite does not count (so a matrix with a non-finite
+ *     entry counts nothing);
+ *   - q inside frame i+1 (0 <= qx <= w-1 and 0 <= qy <= h-1): inside_i += 1 and sum_abs_i += |gray_i[p] - gray_{i+1}[q]|.
+ * Both accumulators are integers, so the result does not depend on the order of the reduction.
+ * vstab_pair_residual_batch: gray dev [n,h,w] u8 (n >= 2), transitions host [n-1,9] f32 at working resolution ->
+ * sum_abs dev [n-1] u64, inside dev [n-1] u32 (both zeroed by the call).  One streaming pass of about 2*h*w bytes per pair;
+ * asynchronous on the context's stream; timing kind "cut".  What is decided from the two numbers (scene_cuts.py):
+ * score = sum_abs / inside, overlap = inside / (h*w), a cut iff overlap < 0.25 or score >= the threshold.
+ */
+int vstab_pair_residual_batch(vstab_ctx* ctx, const uint8_t* gray, int n, int h, int w, const float* transitions,
+                              uint64_t* sum_abs, uint32_t* inside);
+
 /* ---- N1 (crop framing): coverage analysis for the keep_fov crop solver ---------
  * Replaces the per-frame cv2 calls of nodes/stabilizer_utils.py:611-643
  * (finalize_with_masks: warpPerspective(ones, NEAREST) > 0.5, dilate 3x3, erode 3x3, bounding box of
