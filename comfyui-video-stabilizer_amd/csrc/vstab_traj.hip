@@ -330,7 +330,8 @@ extern "C" int vstab_trajectory(vstab_ctx* ctx, const double* deltas, int n, int
 {
     (void)ctx;   // host arithmetic (kept in the signature: the entry point predates the host form)
     VSTAB_REQUIRE(deltas && path && target, "vstab_trajectory: NULL pointer argument");
-    VSTAB_REQUIRE(n >= 2 && p >= 1 && p <= 8, "vstab_trajectory: unsupported shape n=%d p=%d", n, p);
+    // (any column count: the columns are independent -- 2 / 4 / 8 for the global models, 2 * mw * mh for the mesh warp's vertex paths)
+    VSTAB_REQUIRE(n >= 2 && p >= 1, "vstab_trajectory: unsupported shape n=%d p=%d", n, p);
     smooth = smooth < 0.0 ? 0.0 : (smooth > 1.0 ? 1.0 : smooth);
     strength = strength < 0.0 ? 0.0 : (strength > 1.0 ? 1.0 : strength);
     const int do_smooth = !(smooth <= 0.0 || n <= 2);

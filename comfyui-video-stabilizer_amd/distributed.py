@@ -215,7 +215,8 @@ def _lap(stats, key, t0):
 def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, transform_mode: str, camera_lock: bool,
                       strength: float, smooth: float, keep_fov: float, padding_rgb, frame_rate: float, group=None,
                       estimator: str = "flow", stats: Optional[Dict[str, float]] = None, want_meta: bool = True,
-                      check_value_range: bool = True, temporal_fill: int = 0, estimation_mask=None, scene_cuts=None):
+                      check_value_range: bool = True, temporal_fill: int = 0, estimation_mask=None, scene_cuts=None,
+                      mesh_warp=None):
     """Sharded equivalent of `_stabilize_frames` (flow.py:213-640).
 
     local_frames: device tensor [n_local (+1 halo for rank > 0 that owns frames), H, W, 3] float32 -- this rank's frames
@@ -237,6 +238,11 @@ def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, t
         # the sharded plan (one continuous camera move) does not form; every rank raises alike, before any collective
         raise ValueError("stabilize_sharded does not support scene_cuts: scene cuts are not sharded (the sharded plan treats the "
                          "clip as one continuous camera move); run the single-GPU pipeline for a scene-aware stabilization")
+    if mesh_warp is not None:
+        # every vertex path runs through the whole clip: the residuals of every rank's flow grid would have to be gathered
+        # before the warp, which the sharded path does not do; every rank raises alike, before any collective
+        raise ValueError("stabilize_sharded does not support mesh_warp: the mesh warp is not sharded (vertex paths need every "
+                         "rank's flow grid); run the single-GPU pipeline for a mesh-warped stabilization")
     import torch.distributed as dist
 
     from . import native

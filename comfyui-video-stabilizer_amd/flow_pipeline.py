@@ -22,6 +22,7 @@ from typing import Any, Dict, Optional, Tuple
 import numpy as np
 
 from . import host_math as hm
+from . import mesh_warp as mesh_warp_mod
 from . import native
 from . import scene_cuts as scene_cuts_mod
 from . import temporal_fill as temporal_fill_mod
@@ -169,13 +170,15 @@ def _gray(ctx, device_frames, working_size, peaks_out, gray_out=None):
 
 
 def estimate_transitions(ctx, device_frames, working_size, transform_mode: str, clip_start: bool = True, peaks_out=None,
-                         blocked=None, gray_out=None):
+                         blocked=None, gray_out=None, grid_out=None):
     """F2-F5 for frames [N,H,W,3] on the device -> per-pair candidate fits (structured table [N-1,3]).
     peaks_out: a list that receives the device tensor of per-frame maxima (see host_math.resolve_value_range).
     blocked: the estimation mask's block grid (u8 [N,gh,gw], Context.mask_block_grid); the flow itself is computed on the
-    unmasked images."""
+    unmasked images.  grid_out: a list that receives the grid of flow samples itself (the mesh warp reads it after the fits)."""
     gray = _gray(ctx, device_frames, working_size, peaks_out, gray_out)
     _, grid = ctx.dis_flow_batch(gray, sample_step=SAMPLE_STEP, want_full=False, want_grid=True, clip_start=clip_start)
+    if grid_out is not None:
+        grid_out.append(grid)
     return ctx.sample_fit_batch(grid, SAMPLE_STEP, transform_mode, blocked=blocked)
 
 
@@ -189,12 +192,14 @@ def estimate_transitions_phase(ctx, device_frames, working_size, transform_mode:
 
 
 def estimate_transitions_tvl1(ctx, device_frames, working_size, transform_mode: str, clip_start: bool = True, peaks_out=None,
-                              blocked=None, gray_out=None):
+                              blocked=None, gray_out=None, grid_out=None):
     """Second dense estimator (flow.py:76-80, 140-147): Dual TV-L1 flow with OpenCV's default parameters on the
     estimation images, sampled and fitted exactly as the DIS flow is.  Pairs are independent (no initial flow), so
     clip_start does not matter."""
     gray = _gray(ctx, device_frames, working_size, peaks_out, gray_out)
     _, grid, _ = ctx.tvl1_flow_batch(gray, sample_step=SAMPLE_STEP, want_full=False, want_grid=True)
+    if grid_out is not None:
+        grid_out.append(grid)
     return ctx.sample_fit_batch(grid, SAMPLE_STEP, transform_mode, blocked=blocked)
 
 
@@ -430,6 +435,7 @@ def _plan_stabilization(ctx, fit_records, size, total_frames, framing_mode, tran
     }
     estimated_motion = {   # arrays; turned into JSON lists by prepare_meta (off the critical path)
         "modes": modes_used, "confidences": confidences, "residuals": residuals, "matrices": matrices,
+        "work_matrices": work_mats,   # (not a meta key: what the mesh warp measures its residual against)
         "path": path, "target_path": target_path, "target_path_effective": effective_target_path,
     }
     return FlowPlan(final_matrices, output_size, meta_head, framing_meta, estimated_motion, framing_mode, size, fps_effective,
@@ -623,6 +629,24 @@ def _scene_segments(ctx, scene, fit_records, gray_out, transform_mode: str, tota
     return scene_cuts_mod.segments_from_cuts(cuts, total_frames), scene_cuts_mod.meta_block(scene, cuts, scores, overlap)
 
 
+# ---- mesh warp (beyond the reference; mesh_warp.py, the rules are in include/vstab.h) -----------------------------------
+def _mesh_offsets(ctx, mesh, plan, grid, blocked, working_size, size, segments, strength, smooth, camera_lock, fps_effective):
+    """-> (the warp's vertex offsets f32 [N,mh,mw,2] in full-resolution px, meta["mesh_warp"]).  One launch of the residual
+    kernel over the grid the estimator made, against the working-resolution transitions the plan itself used; the vertex
+    paths go through the trajectory routine with the plan's own (clipped) smooth / strength."""
+    width, height = size
+    work = working_size if working_size is not None else size
+    mw, mh = mesh.vertices
+    em = plan.estimated_motion
+    residual, count = ctx.mesh_residual_batch(grid, SAMPLE_STEP, work, em["work_matrices"], mw, mh, blocked=blocked)
+    residual, count = residual.cpu().numpy(), count.cpu().numpy()
+    max_shift = mesh.max_shift_px(width)
+    offsets, _ = mesh_warp_mod.plan_offsets(
+        ctx.trajectory, residual, em["confidences"], segments, float(np.clip(smooth, 0.0, 1.0)), fps_effective,
+        float(np.clip(strength, 0.0, 1.0)), bool(camera_lock), (1.0 / (work[0] / float(width)), 1.0 / (work[1] / float(height))), max_shift)   # the plan's own up-scale factors
+    return offsets, mesh_warp_mod.meta_block(mesh, max_shift, residual, count, offsets, native.MESH_MIN_SAMPLES)
+
+
 def _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode, camera_lock,
                                 strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested, pbar, progress_total,
                                 keep_on_device, temporal_fill=0, blocked=None, mask_info=None):
@@ -696,6 +720,8 @@ def _stabilize_frames(
     mask_margin: int = 16,
     scene_cuts=None,
     cut_threshold=None,
+    mesh_warp=None,
+    mesh_max_shift=None,
 ) -> hm.StabilizationResult:
     """Positional signature of the reference (flow.py:213-223); keyword-only extras select the GPU
     context, keep outputs resident in HBM (multi-GPU sharding lives in distributed.py) or switch the
@@ -711,8 +737,16 @@ def _stabilize_frames(
     residual of every pair (scene_cuts.py; include/vstab.h states the rule; cut_threshold None: the calibrated default), a
     strictly increasing sequence of frame indices in 1..N-1 names the first frames of the shots instead.  Mode selection
     and trajectory then run per shot, the transition across a cut is reported as "no candidate", framing stays global and
-    meta["scene_cuts"] reports cuts and scores.  None: the reference's behaviour and meta.  Bypass paths ignore it."""
+    meta["scene_cuts"] reports cuts and scores.  None: the reference's behaviour and meta.  Bypass paths ignore it.
+    mesh_warp (beyond the reference, None by default): True (16 x 9 cells) or a (cols, rows) pair, each in 2..64.  The
+    residual of the pairs' global fits is measured per mesh vertex from the flow grid (mesh_warp.py; include/vstab.h states
+    the rules), its vertex paths are smoothed as the global path is, and the final warp displaces the source by the
+    per-vertex correction, clamped to mesh_max_shift full-resolution px per axis (None: 1/64 of the width).  For the DIS and
+    TV-L1 estimators under crop_and_pad / expand framing, without temporal_fill; meta["mesh_warp"] reports residuals and
+    corrections, motion_meta keeps describing the global part.  None: the reference's behaviour and meta.  Bypass paths
+    ignore it."""
     scene = scene_cuts_mod.check_request(scene_cuts, cut_threshold)
+    mesh = mesh_warp_mod.check_request(mesh_warp, mesh_max_shift)
     if estimator not in _META_SOURCE:
         raise ValueError(f"Unknown estimator {estimator!r}; expected 'flow' or 'classic'.")
     temporal_fill = int(temporal_fill)
@@ -721,6 +755,8 @@ def _stabilize_frames(
     estimator = resolve_flow_backend(estimator)
     if estimation_mask is not None:
         mask_margin = check_estimation_mask_request(estimator, mask_margin)
+    if mesh is not None:
+        mesh_warp_mod.check_pipeline(estimator, framing_mode, temporal_fill)
     total_frames = len(context.frames)
     fps_effective, fps_requested = _fps_fields(context, frame_rate)
     size = (context.width, context.height)
@@ -786,8 +822,9 @@ def _stabilize_frames(
         mask_info = (mask_margin, mask_frames, int(blocked.shape[1] * blocked.shape[2]))
         masked = {"blocked": blocked}
 
-    # (scene-aware calls form the plan on the host: plan_kernel knows one continuous camera move)
-    if scene is None and device_plan_applies(estimator, framing_mode, transform_mode, total_frames):
+    # (scene-aware calls form the plan on the host: plan_kernel knows one continuous camera move; so do mesh-warp calls: the
+    # vertex paths need the plan's own transitions before the warp can be queued)
+    if scene is None and mesh is None and device_plan_applies(estimator, framing_mode, transform_mode, total_frames):
         done = _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode,
                                            camera_lock, strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested,
                                            pbar, progress_total, keep_on_device, temporal_fill, blocked, mask_info)
@@ -800,6 +837,8 @@ def _stabilize_frames(
     peaks = [] if context.range_pending else None
     if scene is not None and scene.mode == "auto":
         masked = dict(masked, gray_out=[])     # the estimation images stay alive for the score below
+    if mesh is not None:
+        masked = dict(masked, grid_out=[])     # so does the grid of flow samples, for the vertex residuals
     fit_records = estimate(ctx, device_frames, working_size, transform_mode, peaks_out=peaks, **masked)
     if peaks and hm.resolve_value_range(context, peaks[0], ctx):
         # F0 (stabilizer_utils.py:127-131): some frame turned out to be 0..255 float data.  The estimation above ran
@@ -807,8 +846,9 @@ def _stabilize_frames(
         # have been rescaled now, so it is repeated on the rescaled clip.  0..1 input -- the ComfyUI IMAGE contract --
         # never takes this branch.
         device_frames = context.device_batch(ctx)
-        if "gray_out" in masked:
-            masked["gray_out"] = []
+        for kept in ("gray_out", "grid_out"):
+            if kept in masked:
+                masked[kept] = []
         fit_records = estimate(ctx, device_frames, working_size, transform_mode, **masked)
     progress_done = _replay_progress(pbar, 0, total_frames - 1, progress_total)
     check_interrupt()
@@ -826,9 +866,17 @@ def _stabilize_frames(
         return hm.StabilizationResult(frames_out, masks_out, _attach_motion_meta(plan.bypass_meta, fps_effective, estimator))
 
     # ---- warp (F13) ------------------------------------------------------------
-    dst, mask, counts = ctx.warp_batch(
-        device_frames, plan.final_matrices, plan.output_size, interp="bilinear",
-        border=hm.border_value(padding_rgb), want_mask=True, want_count=True)
+    mesh_block = None
+    if mesh is not None:
+        offsets, mesh_block = _mesh_offsets(ctx, mesh, plan, masked["grid_out"][0], blocked, working_size, size, segments,
+                                            strength, smooth, camera_lock, fps_effective)
+        dst, mask, counts = ctx.mesh_warp_batch(
+            device_frames, plan.final_matrices, plan.output_size, offsets, border=hm.border_value(padding_rgb),
+            want_mask=True, want_count=True)
+    else:
+        dst, mask, counts = ctx.warp_batch(
+            device_frames, plan.final_matrices, plan.output_size, interp="bilinear",
+            border=hm.border_value(padding_rgb), want_mask=True, want_count=True)
     meta = prepare_meta(plan)  # host JSON work overlaps the warp kernel
     progress_done = _replay_progress(pbar, progress_done, total_frames, progress_total)
     meta = complete_meta(meta, plan, _counts_to_host(counts))
@@ -836,6 +884,8 @@ def _stabilize_frames(
         meta["estimation_mask"] = estimation_mask_meta(fit_records, *mask_info)
     if scene_block is not None:
         meta["scene_cuts"] = scene_block
+    if mesh_block is not None:
+        meta["mesh_warp"] = mesh_block
     _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill)
     check_interrupt()
     verdict = {"used": False, "mismatched_frames": 0}

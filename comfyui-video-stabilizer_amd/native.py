@@ -21,6 +21,8 @@ INTERP = {"bilinear": 0, "bicubic": 1}
 SUBPIX = {"q5": 0, "exact": 1}
 MODES = {"translation": 0, "similarity": 1, "perspective": 2}
 MODE_NAMES = ("translation", "similarity", "perspective")
+MESH_MAX_VERTS = 65      # vertices per axis of a mesh warp (64 cells; include/vstab.h)
+MESH_MIN_SAMPLES = 4     # VSTAB_MESH_MIN_SAMPLES
 
 # Sub-pixel model used by the node path; see include/vstab.h (vstab_subpix) and DESIGN.md.
 DEFAULT_SUBPIX = os.environ.get("VSTAB_SUBPIX", "q5")
@@ -172,6 +174,12 @@ _SIGNATURES = {
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vstab_pair_residual_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vstab_mesh_residual_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                  C.c_int, C.c_void_p, C.c_void_p]),
+    "vstab_mesh_warp_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                  C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vstab_fit_records_device": (C.c_void_p, [C.c_void_p]),
     "vstab_sample_fit_batch_end": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "vstab_flow_plan_device": (
@@ -692,6 +700,67 @@ class Context:
         _check(self.lib.vstab_pair_residual_batch(self.handle, _dev_ptr(gray), n, h, w, m.ctypes.data, _dev_ptr(sums),
                                                   _dev_ptr(inside)), "vstab_pair_residual_batch")
         return sums.cpu().numpy(), inside.cpu().numpy().astype(np.int64)
+
+    # ------------------------------------------------------------------ mesh warp
+    @staticmethod
+    def _check_mesh(who, mw, mh):
+        if not (2 <= int(mw) <= MESH_MAX_VERTS and 2 <= int(mh) <= MESH_MAX_VERTS):
+            raise ValueError(f"{who}: {mw}x{mh} vertices outside 2..{MESH_MAX_VERTS} per axis")
+        return int(mw), int(mh)
+
+    def mesh_residual_batch(self, grid_flow, step, work_size, transitions, mw, mh, blocked=None):
+        """Per-vertex residual of the global fit (vstab_mesh_residual_batch; the rule is in include/vstab.h).
+        grid_flow f32 [P,gh,gw,2] (device), work_size = (w, h) of the estimation images, transitions f32 [P,3,3] at working
+        resolution, mw x mh vertices, blocked u8 [P+1,gh,gw] or None -> (residual f32 [P,mh,mw,2], count i32 [P,mh,mw]),
+        device tensors."""
+        torch = self.torch
+        mw, mh = self._check_mesh("mesh_residual_batch", mw, mh)
+        if grid_flow.dtype != torch.float32 or grid_flow.dim() != 4 or grid_flow.shape[3] != 2:
+            raise ValueError("mesh_residual_batch expects a float32 [P,gh,gw,2] tensor")
+        grid_flow, blocked, pairs, gh, gw = self._fit_inputs(grid_flow, blocked)
+        ww, wh, step = int(work_size[0]), int(work_size[1]), int(step)
+        if step < 1 or (gh, gw) != ((wh + step - 1) // step, (ww + step - 1) // step):
+            raise ValueError(f"mesh_residual_batch: a grid of {gw}x{gh} samples is not a {ww}x{wh} image at step {step}")
+        m = np.ascontiguousarray(transitions, dtype=np.float32)
+        if m.size != pairs * 9:
+            raise ValueError(f"mesh_residual_batch: transitions {m.shape} are not [{pairs},3,3]")
+        residual = torch.empty((pairs, mh, mw, 2), dtype=torch.float32, device=self.device)
+        count = torch.empty((pairs, mh, mw), dtype=torch.int32, device=self.device)
+        self.use_torch_stream()
+        _check(self.lib.vstab_mesh_residual_batch(
+            self.handle, _dev_ptr(grid_flow), pairs, gh, gw, step, wh, ww, m.ctypes.data,
+            _dev_ptr(blocked) if blocked is not None else None, mw, mh, _dev_ptr(residual), _dev_ptr(count)),
+            "vstab_mesh_residual_batch")
+        return residual, count
+
+    def mesh_warp_batch(self, frames, matrices, out_size, offsets, border=(0.0, 0.0, 0.0), subpix=None, want_mask=True,
+                        want_count=False):
+        """warp_batch (bilinear) with a per-vertex displacement of the source frame (vstab_mesh_warp_batch; the rule is in
+        include/vstab.h).  offsets f32 [N,mh,mw,2] in full-resolution px (host or device) ->
+        (dst [N,h,w,3], mask [N,h,w] | None, counts [N] | None).  All-zero offsets give warp_batch's bits."""
+        torch = self.torch
+        src = self._as_device_frames(frames)
+        n, sh, sw, ch = src.shape
+        if ch != 3:
+            raise VstabError(f"mesh_warp_batch expects 3-channel frames, got {ch}")
+        if not isinstance(offsets, torch.Tensor):
+            offsets = torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.float32))
+        if offsets.dim() != 4 or offsets.shape[0] != n or offsets.shape[3] != 2 or offsets.dtype != torch.float32:
+            raise ValueError(f"mesh_warp_batch: offsets {tuple(offsets.shape)} {offsets.dtype} are not float32 [{n},mh,mw,2]")
+        mw, mh = self._check_mesh("mesh_warp_batch", offsets.shape[2], offsets.shape[1])
+        offsets = offsets.to(self.device).contiguous()
+        out_w, out_h = int(out_size[0]), int(out_size[1])
+        m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(n, 9)
+        b = np.ascontiguousarray(border, dtype=np.float32).reshape(3)
+        dst = torch.empty((n, out_h, out_w, 3), dtype=torch.float32, device=self.device)
+        mask = torch.empty((n, out_h, out_w), dtype=torch.float32, device=self.device) if want_mask else None
+        counts = torch.empty((n,), dtype=torch.int32, device=self.device) if (want_count and want_mask) else None
+        self.use_torch_stream()
+        _check(self.lib.vstab_mesh_warp_batch(
+            self.handle, _dev_ptr(src), n, sh, sw, m.ctypes.data, out_h, out_w, b.ctypes.data, SUBPIX[subpix or DEFAULT_SUBPIX],
+            _dev_ptr(offsets), mw, mh, _dev_ptr(dst), _dev_ptr(mask) if mask is not None else None,
+            _dev_ptr(counts) if counts is not None else None), "vstab_mesh_warp_batch")
+        return dst, mask, counts
 
     def _fit_inputs(self, grid_flow, blocked):
         if grid_flow.device != self.device:

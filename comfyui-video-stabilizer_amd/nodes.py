@@ -498,6 +498,48 @@ class VideoStabilizerFlowScenes(io.ComfyNode):
         return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
 
 
+class VideoStabilizerFlowMesh(io.ComfyNode):
+    """The Flow node with a mesh warp behind the global fit: the residual motion one matrix per frame cannot express
+    (parallax, rolling-shutter skew, lens breathing) is measured per mesh vertex and smoothed like the global path
+    (mesh_warp.py).  Not one of the reference's nodes: it is listed by an extension but kept out of NODE_CLASSES."""
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        from .mesh_warp import CELLS_MAX, CELLS_MIN, DEFAULT_CELLS
+
+        schema = io.Schema(
+            node_id="video_stabilizer_flow_mesh",
+            display_name="Video Stabilizer Flow (Mesh)",
+            category="Video/Stabilization",
+            description=("Video Stabilizer Flow that also removes the slow local wobble a single global transform per frame "
+                         "leaves behind, with a coarse mesh of per-vertex corrections."),
+        )
+        base = VideoStabilizerFlow.define_schema()
+        schema.inputs = list(base.inputs) + [
+            io.Int.Input("mesh_cols", default=DEFAULT_CELLS[0], min=CELLS_MIN, max=CELLS_MAX, display_name="Mesh Columns",
+                         tooltip="Cells of the mesh across the frame."),
+            io.Int.Input("mesh_rows", default=DEFAULT_CELLS[1], min=CELLS_MIN, max=CELLS_MAX, display_name="Mesh Rows",
+                         tooltip="Cells of the mesh down the frame."),
+            io.Float.Input("max_shift", default=0.0, min=0.0, max=512.0, step=0.5, display_name="Max Shift",
+                           tooltip=("Largest per-vertex correction in pixels, per axis.  0 uses the default, 1/64 of the frame's "
+                                    "width, which has been tried on synthetic clips only: lower it if the picture warps.")),
+        ]
+        schema.outputs = _estimator_outputs()
+        return schema
+
+    @classmethod
+    def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
+                strength: float, smooth: float, keep_fov: float, padding_color: str, mesh_cols: int, mesh_rows: int,
+                max_shift: float) -> io.NodeOutput:
+        context = hm._normalize_video_input(frames)
+        result = _stabilize_frames(
+            context, framing_mode, transform_mode, camera_lock, strength, smooth, keep_fov,
+            hm._parse_padding_color(padding_color), frame_rate, keep_on_device=True, estimator="flow",
+            mesh_warp=(int(mesh_cols), int(mesh_rows)), mesh_max_shift=float(max_shift) if max_shift else None,
+        )
+        return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
+
+
 NODE_CLASSES = [VideoStabilizerClassic, VideoStabilizerFlow, VideoStabilizerMotionApply, VideoStabilizerShakeGenerator,
                 VideoStabilizerShakeGeneratorManual, VideoStabilizerInverse]
 
@@ -545,3 +587,11 @@ class VideoStabilizerAmdScenesExtension(VideoStabilizerAmdMaskedExtension):
 
     async def get_node_list(self) -> list:
         return await super().get_node_list() + [VideoStabilizerFlowScenes]
+
+
+class VideoStabilizerAmdMeshExtension(VideoStabilizerAmdScenesExtension):
+    """The scene-aware extension's nine nodes plus Video Stabilizer Flow (Mesh).  A class of its own for the reason the two
+    before it are: the extensions before it keep the lists they had, and comfy_entrypoint() keeps handing out its own."""
+
+    async def get_node_list(self) -> list:
+        return await super().get_node_list() + [VideoStabilizerFlowMesh]

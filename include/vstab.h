@@ -384,7 +384,8 @@ int vstab_tvl1_flow_batch(vstab_ctx* ctx, const uint8_t* gray, int n, int h, int
 /* ---- F7 + F8: trajectory (prefix sum, box smoothing, strength blend), fp64 ---
  * Replaces nodes/video_stabilizer_flow.py:356-371 and
  * nodes/stabilizer_utils.py:361-383 (_smooth_path: moving average, edge padded,
- * window from fps).  deltas host [n-1,p]; path/target host [n,p].
+ * window from fps).  deltas host [n-1,p]; path/target host [n,p]; any p >= 1 (the columns are independent: the mesh
+ * warp sends its 2 * mw * mh vertex-path columns through the same call).
  * Host arithmetic since round 4 (a few thousand doubles; ctx is not used): the same operation order as the
  * device plan below, so the two agree bit for bit on equal deltas.
  */
@@ -457,6 +458,63 @@ int vstab_temporal_fill_batch(vstab_ctx* ctx, const float* src, int clip_frames,
                               const float* matrices, const int32_t* cand_frame, int K, int out_h, int out_w, int interp,
                               int subpix, float* dst, float* mask, int8_t* filled_from, uint32_t* fill_count,
                               uint32_t* pad_count);
+
+/* ---- mesh warp (not a reference feature, off by default): the residual motion one global fit leaves ------------
+ * One matrix per frame cannot express parallax, rolling-shutter skew or lens breathing.  What it leaves is measured on a
+ * coarse mesh of mw x mh vertices (MeshFlow, Liu et al., ECCV 2016: per-vertex motion profiles) and taken out by a second,
+ * per-vertex displacement inside the warp.
+ *
+ * vstab_mesh_residual_batch -- the rule, for pair i (frames i, i+1; x_{i+1} = A_i x_i) of a work_w x work_h estimation image:
+ *   - vertex (a, b), a in 0..mw-1, b in 0..mh-1, sits at vx = (double)a * (work_w - 1) / (mw - 1), vy = (double)b * (work_h - 1)
+ *     / (mh - 1) (fp64: the multiply, then the divide); a cell is cw = (double)(work_w - 1) / (mw - 1) wide and
+ *     ch = (double)(work_h - 1) / (mh - 1) high.
+ *   - grid sample (gx, gy) sits at (x, y) = (gx*step, gy*step) and has flow (u, v).  With A = the float32 matrix widened to
+ *     fp64 and x, y as fp64 integers: X = (A0*x + A1*y) + A2, Y = (A3*x + A4*y) + A5, W = (A6*x + A7*y) + A8 (separate IEEE
+ *     multiplies and adds in this association, nothing fused), and the residual is
+ *     r = ( (float)((x + (double)u) - X / W), (float)((y + (double)v) - Y / W) ); it lives at (x, y) of frame i.
+ *   - the sample is ADMITTED to vertex (a, b) iff u, v and both components of r are finite, it is blocked neither in frame i
+ *     nor in frame i+1 (the estimation mask's pair rule; blocked == NULL: nothing is), and |x - vx| < cw and |y - vy| < ch
+ *     (fp64, strict): the samples inside the four cells that touch the vertex, MeshFlow's neighbourhood.
+ *   - count = the number of admitted samples.  count >= VSTAB_MESH_MIN_SAMPLES: the vertex value is, per axis, the median
+ *     of the admitted residuals as numpy.median gives it on float32: the middle element of the sorted values for an odd
+ *     count, (lo + hi) / 2 in float32 of the two middle elements for an even one.  Fewer: residual (0, 0), true count.
+ * A median does not depend on the order of its inputs, so the result equals the NumPy restatement exactly.
+ *   grid_flow   dev  [pairs, gh, gw, 2] f32, gh = ceil(work_h/step), gw = ceil(work_w/step)
+ *   transitions host [pairs, 9] f32, working resolution: the matrices the plan used (after the sticky-mode selection)
+ *   blocked     dev  [pairs+1, gh, gw] u8 (vstab_mask_block_grid) or NULL
+ *   residual    dev  [pairs, mh, mw, 2] f32;  count dev [pairs, mh, mw] i32
+ * 2 <= mw, mh <= 65; work_w, work_h >= 2.  One workgroup per (pair, vertex), rank counting in LDS; a neighbourhood of
+ * more than 16384 grid positions is refused.  Asynchronous on the context's stream; timing kind "mesh_residual".
+ */
+#define VSTAB_MESH_MIN_SAMPLES 4
+int vstab_mesh_residual_batch(vstab_ctx* ctx, const float* grid_flow, int pairs, int gh, int gw, int step, int work_h,
+                              int work_w, const float* transitions, const uint8_t* blocked, int mw, int mh,
+                              float* residual, int32_t* count);
+/* vstab_mesh_warp_batch -- vstab_warp_batch (bilinear) with a per-vertex displacement of the SOURCE frame: the content at
+ * source position x is moved to x + c(x) before the frame's matrix is applied.  The rule, per output pixel (x, y):
+ *   - Xn, Yn, W (fp64 coordinate terms per OpenCV column block) and Wn = 1/W, Wq = 32 * Wn (affine: the two constants of the
+ *     frame) are formed exactly as vstab_warp_batch forms them from the float32 forward matrix inverted in fp64.
+ *   - q = (Xn*Wn, Yn*Wn) is the unrounded source coordinate.  For the lookup only, each coordinate is clamped to the frame:
+ *     t = (q > 0) ? q : 0 (a NaN becomes 0), t = (t < S-1) ? t : S-1 with S = src_w / src_h.  Vertex (a, b) sits at
+ *     (a*(src_w-1)/(mw-1), b*(src_h-1)/(mh-1)); g = t * (double)(m-1) / (double)(S-1) (multiply, then divide),
+ *     i = min((int)g, m-2), f = g - i with m = mw / mh -> cell (ia, ib), fractions (fa, fb).  With c00 = offsets[ib][ia],
+ *     c10 = offsets[ib][ia+1], c01 = offsets[ib+1][ia], c11 = offsets[ib+1][ia+1] widened to fp64, per axis:
+ *     c = (c00*(1-fa) + c10*fa) * (1-fb) + (c01*(1-fa) + c11*fa) * fb -- IEEE fp64, this association, nothing fused.
+ *   - s = q - c(q), a one-step inverse of the forward map x -> x + c(x): exact for a constant c, otherwise an approximation
+ *     whose error is of order |c| * |grad c|.  It enters the plain warp's three roundings as
+ *       1/32-px coordinate:  cvRound(Xn*Wq - 32.0*cx), cvRound(Yn*Wq - 32.0*cy)   (VSTAB_SUBPIX_Q5)
+ *       float32 coordinate:  (float)((double)fsx - cx), (float)((double)fsy - cy)  (VSTAB_SUBPIX_EXACT; fsx, fsy the plain
+ *                            warp's float32 chain)
+ *       nearest (mask):      cvRound(Xn*Wn - cx), cvRound(Yn*Wn - cy)
+ *     and everything behind them is vstab_warp_batch's: INT clamp and short saturation, taps, border colour, the mask rule,
+ *     pad_count.
+ * Invariant: all-zero offsets give dst, mask and pad_count bit-identical to vstab_warp_batch (c = +0.0, and v - 0.0 == v).
+ *   offsets dev [n, mh, mw, 2] f32 (x, y), full-resolution px;  2 <= mw, mh <= 65;  src_w, src_h >= 2.
+ * The other arguments are vstab_warp_batch's, interp fixed to bilinear.  Each workgroup stages its frame's vertex table in
+ * LDS; apart from that it is the same HBM stream as the plain warp (same tile, same XCD remap).  Timing kind "mesh_warp". */
+int vstab_mesh_warp_batch(vstab_ctx* ctx, const float* src, int n, int src_h, int src_w, const float* matrices,
+                          int out_h, int out_w, const float* border_rgb, int subpix, const float* offsets, int mw, int mh,
+                          float* dst, float* mask, uint32_t* pad_count);
 
 /* ---- F6 / F9 host helper: element-wise libm over fp64 arrays (host pointers, no GPU involved) ----
  * nodes/stabilizer_utils.py:300-358 (_matrix_to_params / _params_to_matrix) call math.sqrt/atan2/log and
