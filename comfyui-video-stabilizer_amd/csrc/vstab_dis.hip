@@ -77,7 +77,6 @@ __device__ __forceinline__ int sat_u8_round(float v)
     int i = (int)__builtin_rintf(v);
     return i < 0 ? 0 : (i > 255 ? 255 : i);
 }
-__device__ __forceinline__ int sat_short(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
 __device__ __forceinline__ int reflect101(int p, int len)
 {
     if (len == 1) return 0;

@@ -215,3 +215,42 @@ __host__ __device__ inline void vstab_fill_xform(const float* m32, WarpXform* xf
     xf->wn = (W != 0.0) ? 1.0 / W : 0.0;
     xf->pad_ = 0;
 }
+// float32 matrices [count, 9] -> WarpXform table -> the call's staged parameters on the device (vstab_warp.hip).
+int vstab_stage_xforms(vstab_ctx* ctx, const float* m32, size_t count, const WarpXform** dev_out);
+
+// ---- mesh warp ----
+constexpr int MESH_MAX_VERTS = 65;   // vertices per axis (64 cells): the residual (vstab_mesh.hip) and the warp (vstab_warp.hip)
+
+// ---- the scalar pieces of the warp's arithmetic that other translation units use too (the rest: vstab_warp.hip) ----
+
+// std::max((double)INT_MIN, std::min((double)INT_MAX, v)) followed by cvRound
+__device__ __forceinline__ int clamp_round_i32(double v)
+{
+    const double hi = 2147483647.0, lo = -2147483648.0;
+    double m = (v < hi) ? v : hi;
+    double r = (lo < m) ? m : lo;
+    return (int)__builtin_rint(r);
+}
+
+// cv::saturate_cast<short>(int)
+__device__ __forceinline__ int sat_short(int v)
+{
+    return v < -32768 ? -32768 : (v > 32767 ? 32767 : v);
+}
+
+// OpenCV's WarpPerspectiveInvoker evaluates its row-start terms once per block of this many output columns.
+inline int vstab_warp_block_width(int dh, int dw)
+{
+    const int BLOCK_SZ = 32;
+    const int bh0 = BLOCK_SZ / 2 < dh ? BLOCK_SZ / 2 : dh;
+    return BLOCK_SZ * BLOCK_SZ / bh0 < dw ? BLOCK_SZ * BLOCK_SZ / bh0 : dw;
+}
+
+// INTER_NEAREST coverage of the source position (qx, qy) = (Xn * Wn, Yn * Wn) by an sw x sh source: the warp's mask rule
+// in its general form (the plain warp's affine fast path gives the same answer where it applies).
+__device__ __forceinline__ bool vstab_nn_covered(double qx, double qy, int sh, int sw)
+{
+    const int nx = sat_short(clamp_round_i32(qx));
+    const int ny = sat_short(clamp_round_i32(qy));
+    return (unsigned)nx < (unsigned)sw && (unsigned)ny < (unsigned)sh;
+}

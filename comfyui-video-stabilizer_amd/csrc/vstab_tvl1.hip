@@ -81,7 +81,6 @@ dim3 tvl1_grid(long long per_item, int items)
     for (unsigned t = blockIdx.x * blockDim.x + threadIdx.x; t < (unsigned)(per_item); t += gridDim.x * blockDim.x)
 
 __device__ __forceinline__ int t_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ int t_sat_short(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
 
 // ---- resize INTER_LINEAR (cv::resize generic path: horizontal pass into float rows, then vertical) ----
 __device__ __forceinline__ void lin_tap(int d, double scale, int& s, float& f)
@@ -168,7 +167,7 @@ __global__ __launch_bounds__(TVL1_NT) void tvl1_upsample_kernel(const float* __r
 // ---- remap INTER_CUBIC, BORDER_CONSTANT 0, float maps rounded to 1/32 px ----
 __device__ __forceinline__ float cubic_sample(const float* __restrict__ S, int sh, int sw, int X, int Y, const float* cub)
 {
-    const int sx = t_sat_short(X >> 5), sy = t_sat_short(Y >> 5);
+    const int sx = sat_short(X >> 5), sy = sat_short(Y >> 5);
     const float* cx = cub + (X & 31) * 4;
     const float* cy = cub + (Y & 31) * 4;
     const int x0 = sx - 1, y0 = sy - 1;

@@ -1,4 +1,8 @@
-// vstab_warp.hip -- perspective/similarity warp with padding mask and multi-sample motion blur.
+// vstab_warp.hip -- perspective/similarity warp with padding mask, its mesh-displaced form (mesh_warp_kernel), the
+// multi-sample motion blur and the temporal fill.  All of them take their coordinates from ONE definition, warp_pixel, and
+// share one tile shell (TileShell, warp_kernel's body, block_count_add); the scalar pieces that vstab_crop / vstab_dis / vstab_tvl1
+// use too are in vstab_internal.h.  profiles/warp_traffic.json is tied to the hash of these two files: the warp's arithmetic
+// stays in them.
 //
 // Replaces the OpenCV calls of nodes/video_stabilizer_flow.py:560-588 (F13) and
 // nodes/motion_apply.py:75-202 (A3, A5) of the reference.  Arithmetic follows OpenCV's
@@ -40,14 +44,7 @@ struct WarpArgs {
     float b0, b1, b2;   // border colour
 };
 
-__device__ __forceinline__ int clamp_round_i32(double v)
-{
-    // std::max((double)INT_MIN, std::min((double)INT_MAX, v)) followed by cvRound
-    const double hi = 2147483647.0, lo = -2147483648.0;
-    double m = (v < hi) ? v : hi;
-    double r = (lo < m) ? m : lo;
-    return (int)__builtin_rint(r);
-}
+// clamp_round_i32, sat_short, vstab_nn_covered (used by other translation units too): vstab_internal.h
 
 // Round-half-even of an fp64 value known to satisfy |v| < 2^31: adding 1.5*2^52 leaves the integer in the
 // low 32 bits of the sum's bit pattern (one fp64 add instead of clamp + rint + convert).  Exactly what
@@ -55,11 +52,6 @@ __device__ __forceinline__ int clamp_round_i32(double v)
 __device__ __forceinline__ int round_small(double v)
 {
     return (int)(unsigned)__double_as_longlong(v + 6755399441055744.0);
-}
-
-__device__ __forceinline__ int sat_short(int v)
-{
-    return v < -32768 ? -32768 : (v > 32767 ? 32767 : v);
 }
 
 // initInterTab1D(INTER_CUBIC): A = -0.75, x = i/32, same operation order as OpenCV's interpolateCubic
@@ -209,6 +201,107 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned b, unsigned nblk)
     return base + i;
 }
 
+// Column-block origin of output column x (OpenCV evaluates the row-start terms once per block of bw0 columns).
+__device__ __forceinline__ int block_origin(int x, int dw, int bw0, int bw0_pow2)
+{
+    if (bw0 >= dw) return 0;
+    if (bw0_pow2) return x & ~(bw0 - 1);
+    return (x / bw0) * bw0;
+}
+
+// The tile shell of every warp kernel: block -> (frame, tile) through the XCD remap, thread -> row y and first pixel x0 of
+// its npx pixels.  Pixel p of a thread is x0 + p * TILE_TX: the lanes of a wavefront cover CONSECUTIVE output pixels, so
+// one load instruction of the bilinear taps touches ~13 cache lines (24 B per lane at a 12-B lane stride) instead of 48 (at
+// the 48-B stride of 4 consecutive pixels per thread) -- the texture addresser was 83 % busy that way (PMC TA_BUSY) and
+// limited the read side to 2.8 TB/s -- and the stores are whole lines (12 B per lane, contiguous).
+template <int TILE_TX, int NT = 256>
+struct TileShell {
+    static constexpr int TILE_W = TILE_TX * TILE_PX, TILE_H = NT / TILE_TX;
+    int frame, tile_x, tile_y, x0, y, npx;
+    bool active;
+    __device__ __forceinline__ TileShell(int tiles_x, int tiles_y, int dh, int dw)
+    {
+        const unsigned t = xcd_remap(blockIdx.x, gridDim.x);
+        const unsigned tiles_per_frame = (unsigned)tiles_x * tiles_y;
+        frame = t / tiles_per_frame;
+        const unsigned tr = t - frame * tiles_per_frame;
+        tile_y = tr / tiles_x;
+        tile_x = tr - tile_y * tiles_x;
+        const int tx = threadIdx.x % TILE_TX, ty = threadIdx.x / TILE_TX;
+        x0 = tile_x * TILE_W + tx;
+        y = tile_y * TILE_H + ty;
+        active = (y < dh) && (x0 < dw);
+        npx = active ? (int)((unsigned)(dw - x0 + TILE_TX - 1) / TILE_TX) : 0;   // pixels x0 + p*TILE_TX < dw (callers cap it at TILE_PX); active: dw > x0
+    }
+};
+
+// Per-thread counts of an NT-thread block -> wave shuffle -> LDS -> one atomic per counter and block, only if non-zero
+// and asked for (out[c] != nullptr); out[c] is a per-frame array.
+template <int NC, int NT = 256>
+__device__ __forceinline__ void block_count_add(unsigned (&v)[NC], unsigned* const (&out)[NC], int frame)
+{
+    static_assert(NT % 64 == 0, "whole wavefronts");
+    constexpr int WAVES = NT / 64;
+    __shared__ unsigned s_cnt[NC][WAVES];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int c = 0; c < NC; c++) v[c] += __shfl_down(v[c], off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < NC; c++) s_cnt[c][threadIdx.x >> 6] = v[c];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            unsigned total = s_cnt[c][0];
+#pragma unroll
+            for (int w = 1; w < WAVES; w++) total += s_cnt[c][w];
+            if (total && out[c]) atomicAdd(out[c] + frame, total);
+        }
+    }
+}
+
+// warp_pixel's displacement hook: a functor evaluated at the source position q = (Xn * Wn, Yn * Wn) that gives the
+// offset (cx, cy) taken off it before the roundings.  NoDisplacement is the plain warp: nothing of the hook is compiled.
+struct NoDisplacement {
+    static constexpr bool ACTIVE = false;
+};
+
+// one axis of the mesh lookup: clamped coordinate -> cell index and fraction (the rule's operation order, include/vstab.h)
+__device__ __forceinline__ void mesh_cell(double q, int size, int verts, int* cell, double* frac)
+{
+    double t = (q > 0.0) ? q : 0.0;                 // NaN -> 0
+    const double top = (double)(size - 1);
+    t = (t < top) ? t : top;
+    const double g = t * (double)(verts - 1) / top;
+    int i = (int)g;
+    i = i < verts - 2 ? i : verts - 2;
+    *cell = i;
+    *frac = g - (double)i;
+}
+
+// The mesh warp's displacement: bilinear in the frame's mw x mh vertex table (staged in LDS, [mh][mw][2]).
+struct MeshDisplacement {
+    static constexpr bool ACTIVE = true;
+    const float* off;
+    int sh, sw, mw, mh;
+    __device__ __forceinline__ void operator()(double qx, double qy, double& cx, double& cy) const
+    {
+        int ia, ib;
+        double fa, fb;
+        mesh_cell(qx, sw, mw, &ia, &fa);
+        mesh_cell(qy, sh, mh, &ib, &fb);
+        const float* __restrict__ c0 = off + (ib * mw + ia) * 2;
+        const float* __restrict__ c1 = c0 + mw * 2;
+        const double ga = 1.0 - fa, gb = 1.0 - fb;
+        cx = ((double)c0[0] * ga + (double)c0[2] * fa) * gb + ((double)c1[0] * ga + (double)c1[2] * fa) * fb;
+        cy = ((double)c0[1] * ga + (double)c0[3] * fa) * gb + ((double)c1[1] * ga + (double)c1[3] * fa) * fb;
+    }
+};
+
 // One transform record in registers, as warp_kernel and temporal_fill_kernel use it for all pixels of a thread.
 template <int INTERP, int SUBPIX>
 struct XformRegs {
@@ -228,21 +321,19 @@ struct XformRegs {
     }
 };
 
-// The plain warp's source position of output pixel (x, y) under one transform, and what is sampled there: THE definition
-// of the coordinate arithmetic (f64 row-start terms per OpenCV column block, Q5 rounding or the float32 `exact` chain),
-// shared by warp_kernel and temporal_fill_kernel.  `q5(X, Y)` samples at the 1/32-px coordinates, `exact(fsx, fsy)` at the
-// float32 ones; `c` receives the nearest-neighbour coverage (WITH_MASK only).
-template <int INTERP, int SUBPIX, bool WITH_MASK, class SampleQ5, class SampleExact>
+// The warp's source position of output pixel (x, y) under one transform, and what is sampled there: THE definition of the
+// coordinate arithmetic (f64 row-start terms per OpenCV column block, Q5 rounding or the float32 `exact` chain), shared by
+// warp_kernel, mesh_warp_kernel and temporal_fill_kernel.  `q5(X, Y)` samples at the 1/32-px coordinates, `exact(fsx, fsy)`
+// at the float32 ones; `c` receives the nearest-neighbour coverage (WITH_MASK only).  `disp` (see NoDisplacement) moves
+// the source position: s = q - disp(q), applied to the unrounded value in front of each of the three roundings.
+template <int INTERP, int SUBPIX, bool WITH_MASK, class SampleQ5, class SampleExact, class Disp>
 __device__ __forceinline__ Px warp_pixel(const WarpXform* __restrict__ xf, const XformRegs<INTERP, SUBPIX>& r, int sh, int sw,
                                          int dw, int bw0, int bw0_pow2, int x, int y, double dy, SampleQ5&& q5,
-                                         SampleExact&& exact, float& c)
+                                         SampleExact&& exact, const Disp& disp, float& c)
 {
     // OpenCV evaluates the row-start terms X0, Y0, W0 once per 64-wide column block (xb) and adds m * (x - xb)
     // per pixel; a thread's pixels lie in up to TILE_PX different blocks, so the terms are formed per pixel.
-    int xb;
-    if (bw0 >= dw) xb = 0;
-    else if (bw0_pow2) xb = x & ~(bw0 - 1);
-    else xb = (x / bw0) * bw0;
+    const int xb = block_origin(x, dw, bw0, bw0_pow2);
     const double dxb = (double)xb;
     const double X0 = r.m0 * dxb + r.m1 * dy + r.m2;
     const double Y0 = r.m3 * dxb + r.m4 * dy + r.m5;
@@ -251,8 +342,9 @@ __device__ __forceinline__ Px warp_pixel(const WarpXform* __restrict__ xf, const
     const double Xn = X0 + r.m0 * dx1, Yn = Y0 + r.m3 * dx1;
     Px v;
     // Fast path (the common case): affine map whose 1/32-px coordinates stay far inside the range where
-    // OpenCV's INT clamp and short saturation are no-ops.
-    const bool small = r.fast_ok && __builtin_fabs(Xn * xf->wq) < 1.0e6 && __builtin_fabs(Yn * xf->wq) < 1.0e6;
+    // OpenCV's INT clamp and short saturation are no-ops.  A displaced pixel takes the general branch.
+    bool small = false;
+    if constexpr (!Disp::ACTIVE) small = r.fast_ok && __builtin_fabs(Xn * xf->wq) < 1.0e6 && __builtin_fabs(Yn * xf->wq) < 1.0e6;
     if (small) {
         const int X = round_small(Xn * xf->wq), Y = round_small(Yn * xf->wq);
         v = q5(X, Y);
@@ -270,30 +362,55 @@ __device__ __forceinline__ Px warp_pixel(const WarpXform* __restrict__ xf, const
             Wn = (W != 0.0) ? 1.0 / W : 0.0;
             Wq = 32.0 * Wn;
         }
+        double cx = 0.0, cy = 0.0;
+        if constexpr (Disp::ACTIVE) disp(Xn * Wn, Yn * Wn, cx, cy);
         if (XformRegs<INTERP, SUBPIX>::EXACT) {
             const float w = x * r.mf[6] + y * r.mf[7] + r.mf[8];
-            const float fsx = (x * r.mf[0] + y * r.mf[1] + r.mf[2]) / w;
-            const float fsy = (x * r.mf[3] + y * r.mf[4] + r.mf[5]) / w;
+            float fsx = (x * r.mf[0] + y * r.mf[1] + r.mf[2]) / w;
+            float fsy = (x * r.mf[3] + y * r.mf[4] + r.mf[5]) / w;
+            if constexpr (Disp::ACTIVE) { fsx = (float)((double)fsx - cx); fsy = (float)((double)fsy - cy); }
             v = exact(fsx, fsy);
         } else {
-            const int X = clamp_round_i32(Xn * Wq);
-            const int Y = clamp_round_i32(Yn * Wq);
-            v = q5(X, Y);
+            double Xq = Xn * Wq, Yq = Yn * Wq;
+            if constexpr (Disp::ACTIVE) { Xq = Xq - 32.0 * cx; Yq = Yq - 32.0 * cy; }
+            v = q5(clamp_round_i32(Xq), clamp_round_i32(Yq));
         }
         if (WITH_MASK) {
-            const int nx = sat_short(clamp_round_i32(Xn * Wn));
-            const int ny = sat_short(clamp_round_i32(Yn * Wn));
-            c = ((unsigned)nx < (unsigned)sw && (unsigned)ny < (unsigned)sh) ? 1.f : 0.f;
+            double qx = Xn * Wn, qy = Yn * Wn;
+            if constexpr (Disp::ACTIVE) { qx = qx - cx; qy = qy - cy; }
+            c = vstab_nn_covered(qx, qy, sh, sw) ? 1.f : 0.f;
         }
     }
     return v;
 }
 
-template <int INTERP, int SUBPIX, bool WITH_MASK, int TILE_TX>
-__global__ __launch_bounds__(256) void warp_kernel(WarpArgs a)
+// The mesh warp's arguments: the plain warp's plus the per-frame vertex tables.
+struct MeshWarpArgs : WarpArgs {
+    const float* offsets;   // [n, mh, mw, 2]
+    int mw, mh;
+};
+
+// The displacement a kernel's arguments ask for.  Plain warp: none.  Mesh warp: the frame's vertex table (mw * mh * 8 bytes:
+// 1.4 KB by default) is staged in LDS once per workgroup.
+__device__ __forceinline__ NoDisplacement make_displacement(const WarpArgs&, int) { return {}; }
+__device__ __forceinline__ MeshDisplacement make_displacement(const MeshWarpArgs& a, int frame)
 {
-    constexpr int TILE_W = TILE_TX * TILE_PX, TILE_H = 256 / TILE_TX;
-    __shared__ unsigned s_cnt[4];
+    extern __shared__ float s_off[];      // this frame's vertex table [mh][mw][2]
+    const int table = a.mw * a.mh * 2;
+    const float* __restrict__ O = a.offsets + (size_t)frame * table;
+    for (int i = threadIdx.x; i < table; i += 256) s_off[i] = O[i];
+    __syncthreads();
+    return MeshDisplacement{s_off, a.sh, a.sw, a.mw, a.mh};
+}
+
+// One 64 x 8 (TILE_TX = 32) tile of the warp: every pixel through warp_pixel, RGB + mask stored, padded pixels counted.
+// Args = WarpArgs is the plain warp, Args = MeshWarpArgs the mesh warp (the rule is in include/vstab.h): the same body with
+// the displacement its arguments ask for.  The body stays in the kernel: inlined from a device function that receives the
+// arguments by reference, the compiler issued the two epilogue stores in another order and the plain warp ran 0.3-1 %
+// slower (profiles/r11_one_warp_arithmetic.md).
+template <int INTERP, int SUBPIX, bool WITH_MASK, int TILE_TX, class Args>
+__global__ __launch_bounds__(256) void warp_kernel(Args a)
+{
     __shared__ __attribute__((aligned(16))) float s_cub[32 * 4];
     const float* cub_tab = nullptr;
     if (INTERP == VSTAB_INTERP_BICUBIC) {
@@ -301,62 +418,45 @@ __global__ __launch_bounds__(256) void warp_kernel(WarpArgs a)
         __syncthreads();
         cub_tab = s_cub;
     }
-    const unsigned nblk = gridDim.x;
-    const unsigned t = xcd_remap(blockIdx.x, nblk);
-    const unsigned tiles_per_frame = (unsigned)a.tiles_x * a.tiles_y;
-    const int frame = t / tiles_per_frame;
-    const unsigned tr = t - frame * tiles_per_frame;
-    const int tile_y = tr / a.tiles_x, tile_x = tr - tile_y * a.tiles_x;
-    const int tx = threadIdx.x % TILE_TX, ty = threadIdx.x / TILE_TX;
-    // Pixel p of a thread is x0 + p * TILE_TX: the lanes of a wavefront cover CONSECUTIVE output pixels, so one load
-    // instruction of the bilinear taps touches ~13 cache lines (24 B per lane at a 12-B lane stride) instead of 48
-    // (at the 48-B stride of 4 consecutive pixels per thread) -- the texture addresser was 83 % busy that way (PMC
-    // TA_BUSY) and limited the read side to 2.8 TB/s -- and the stores are whole lines (12 B per lane, contiguous).
-    const int x0 = tile_x * TILE_W + tx;
-    const int y = tile_y * TILE_H + ty;
-    const bool active = (y < a.dh) && (x0 < a.dw);
-    const int npx = active ? (a.dw - x0 + TILE_TX - 1) / TILE_TX : 0;   // pixels x0 + p*TILE_TX < dw (capped at TILE_PX below)
-
+    const TileShell<TILE_TX> t(a.tiles_x, a.tiles_y, a.dh, a.dw);
+    const int frame = t.frame, x0 = t.x0, y = t.y, npx = t.npx;
+    const auto disp = make_displacement(a, frame);
     const float* __restrict__ S = a.src + (size_t)frame * a.sh * a.sw * 3;
-    constexpr int nxf = 1;   // one matrix per frame (the S-sample blur is warp_blur_kernel)
 
     float acc[TILE_PX][3];
     float cov[TILE_PX];
 #pragma unroll
     for (int p = 0; p < TILE_PX; p++) { acc[p][0] = acc[p][1] = acc[p][2] = 0.f; cov[p] = 0.f; }
 
-    if (active) {
+    if (t.active) {
         const double dy = (double)y;
-
-        for (int k = 0; k < nxf; k++) {
-            const WarpXform* __restrict__ xf = a.xf + (size_t)frame * nxf + k;
-            const XformRegs<INTERP, SUBPIX> r(xf);
+        const WarpXform* __restrict__ xf = a.xf + frame;   // one matrix per frame (the S-sample blur is warp_blur_kernel)
+        const XformRegs<INTERP, SUBPIX> r(xf);
 #pragma unroll
-            for (int p = 0; p < TILE_PX; p++) {
-                if (p >= npx) continue;
-                const int x = x0 + p * TILE_TX;
-                float c = 0.f;
-                const Px v = warp_pixel<INTERP, SUBPIX, WITH_MASK>(
-                    xf, r, a.sh, a.sw, a.dw, a.bw0, a.bw0_pow2, x, y, dy,
-                    [&](int X, int Y) { return sample_q5<INTERP>(S, a.sh, a.sw, X, Y, a.b0, a.b1, a.b2, cub_tab); },
-                    [&](float fsx, float fsy) { return sample_exact(S, a.sh, a.sw, fsx, fsy, a.b0, a.b1, a.b2); }, c);
-                acc[p][0] = v.r; acc[p][1] = v.g; acc[p][2] = v.b;
-                if (WITH_MASK) cov[p] = c;
-            }
+        for (int p = 0; p < TILE_PX; p++) {
+            if (p >= npx) continue;
+            const int x = x0 + p * TILE_TX;
+            float c = 0.f;
+            const Px v = warp_pixel<INTERP, SUBPIX, WITH_MASK>(
+                xf, r, a.sh, a.sw, a.dw, a.bw0, a.bw0_pow2, x, y, dy,
+                [&](int X, int Y) { return sample_q5<INTERP>(S, a.sh, a.sw, X, Y, a.b0, a.b1, a.b2, cub_tab); },
+                [&](float fsx, float fsy) { return sample_exact(S, a.sh, a.sw, fsx, fsy, a.b0, a.b1, a.b2); }, disp, c);
+            acc[p][0] = v.r; acc[p][1] = v.g; acc[p][2] = v.b;
+            if (WITH_MASK) cov[p] = c;
         }
     }
 
     // ---- epilogue ----
     float mk[TILE_PX];
-    unsigned padded = 0;
+    unsigned padded[1] = {0};
 #pragma unroll
     for (int p = 0; p < TILE_PX; p++) {
         float m = 1.0f - cov[p];
         mk[p] = (m < 1e-3f) ? 0.f : m;
-        if (WITH_MASK && p < npx) padded += (mk[p] > 0.5f) ? 1u : 0u;
+        if (WITH_MASK && p < npx) padded[0] += (mk[p] > 0.5f) ? 1u : 0u;
     }
 
-    if (active) {
+    if (t.active) {
         // per-frame bases are uniform (scalar registers); inside a frame 32-bit element offsets suffice (the host checks
         // that a frame has fewer than 2^30 pixels), which keeps the address arithmetic out of 64-bit VALU multiplies
         float* __restrict__ D = a.dst + (size_t)frame * a.dh * a.dw * 3;
@@ -374,17 +474,11 @@ __global__ __launch_bounds__(256) void warp_kernel(WarpArgs a)
         }
     }
 
-    if (WITH_MASK && a.pad_count != nullptr) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) padded += __shfl_down(padded, off);
-        if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = padded;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-            if (total) atomicAdd(a.pad_count + frame, total);
-        }
-    }
+    if (WITH_MASK && a.pad_count != nullptr) block_count_add<1>(padded, {a.pad_count}, frame);
 }
+
+template <int SUBPIX, bool WITH_MASK>
+constexpr auto mesh_warp_kernel = warp_kernel<VSTAB_INTERP_BILINEAR, SUBPIX, WITH_MASK, 32, MeshWarpArgs>;
 
 // ---- motion blur: S samples per output pixel (motion_apply.py:137-202) ---------------------------------------------
 //
@@ -458,25 +552,12 @@ __global__ __launch_bounds__((BlurGeom<INTERP, SUBPIX>::NT)) __attribute__((amdg
     if (threadIdx.x == 0) { s_box[0] = s_box[1] = 0x7fffffff; s_box[2] = s_box[3] = (int)0x80000000; }
     __syncthreads();
 
-    const unsigned t = xcd_remap(blockIdx.x, gridDim.x);
-    const unsigned tiles_per_frame = (unsigned)a.tiles_x * a.tiles_y;
-    const int frame = t / tiles_per_frame;
-    const unsigned tr = t - frame * tiles_per_frame;
-    const int tile_y = tr / a.tiles_x, tile_x = tr - tile_y * a.tiles_x;
-    const int tx = threadIdx.x % TILE_TX, ty = threadIdx.x / TILE_TX;
-    const int x0 = tile_x * TILE_W + tx;
-    const int y = tile_y * TILE_H + ty;
-    const bool active = (y < a.dh) && (x0 < a.dw);
-    const int npx = active ? (a.dw - x0 + TILE_TX - 1) / TILE_TX : 0;
+    const TileShell<TILE_TX, NT> t(a.tiles_x, a.tiles_y, a.dh, a.dw);
+    const int frame = t.frame, tile_x = t.tile_x, tile_y = t.tile_y, x0 = t.x0, y = t.y, npx = t.npx;
+    const bool active = t.active;
     const float* __restrict__ S = a.src + (size_t)frame * a.sh * a.sw * 3;
     const int nxf = a.nxf_per_frame;
     const WarpXform* __restrict__ xf0 = xfs + (size_t)frame * nxf;
-
-    auto block_origin = [&](int x) {
-        if (a.bw0 >= a.dw) return 0;
-        if (a.bw0_pow2) return x & ~(a.bw0 - 1);
-        return (x / a.bw0) * a.bw0;
-    };
 
     // ---- the source window this tile can touch, over all samples
     bool fast = G::FAST && a.blur_fast != 0;
@@ -491,7 +572,7 @@ __global__ __launch_bounds__((BlurGeom<INTERP, SUBPIX>::NT)) __attribute__((amdg
             const WarpXform* __restrict__ xf = xf0 + k;
             const int cx_ = (c & 1) ? min(tile_x * TILE_W + TILE_W, a.dw) - 1 : tile_x * TILE_W;
             const int cy_ = (c & 2) ? min(tile_y * TILE_H + TILE_H, a.dh) - 1 : tile_y * TILE_H;
-            const int xb = block_origin(cx_);
+            const int xb = block_origin(cx_, a.dw, a.bw0, a.bw0_pow2);
             const double dxb = (double)xb, dyc = (double)cy_, dx1 = (double)(cx_ - xb);
             const double Xn = (xf->m[0] * dxb + xf->m[1] * dyc + xf->m[2]) + xf->m[0] * dx1;
             const double Yn = (xf->m[3] * dxb + xf->m[4] * dyc + xf->m[5]) + xf->m[3] * dx1;
@@ -585,7 +666,7 @@ __global__ __launch_bounds__((BlurGeom<INTERP, SUBPIX>::NT)) __attribute__((amdg
         // formula border + sum over the VALID taps of (tap - border) * weight), and the nearest-neighbour coverage test.
         // Round 3 ran these tiles (the ring along the content's edge: ~10 % of a crop_and_pad clip's tiles) through the
         // general loop, at the L1-bound rate of round 2.
-        const int xb = block_origin(x0);
+        const int xb = block_origin(x0, a.dw, a.bw0, a.bw0_pow2);
         const double dy = (double)y, dxb = (double)xb;
         double dx1[TILE_PX];
 #pragma unroll
@@ -695,7 +776,7 @@ __global__ __launch_bounds__((BlurGeom<INTERP, SUBPIX>::NT)) __attribute__((amdg
         // pixel-sample is the contract, W's tile-uniform part W0 is formed once per thread and sample like X0 / Y0 -- and
         // nothing else of the border-capable loop: no bounds tests, no per-tap validity, no coverage arithmetic
         // (C3's blur warp: see profiles/r05_c3_chain.md).
-        const int xb = block_origin(x0);                 // == block_origin(x0 + TILE_TX): blur_fast
+        const int xb = block_origin(x0, a.dw, a.bw0, a.bw0_pow2);                 // == block_origin(x0 + TILE_TX): blur_fast
         const double dy = (double)y, dxb = (double)xb;
         // a pixel of this thread beyond the right edge (ragged last tile) re-evaluates pixel 0 instead of being skipped:
         // no divergent branch inside the sample loop, its sum is never stored
@@ -774,7 +855,7 @@ __global__ __launch_bounds__((BlurGeom<INTERP, SUBPIX>::NT)) __attribute__((amdg
             for (int p = 0; p < TILE_PX; p++) {
                 if (p >= npx) continue;
                 const int x = x0 + p * TILE_TX;
-                const int xb = block_origin(x);
+                const int xb = block_origin(x, a.dw, a.bw0, a.bw0_pow2);
                 const double dxb = (double)xb;
                 const double X0 = m0 * dxb + m1 * dy + m2;
                 const double Y0 = m3 * dxb + m4 * dy + m5;
@@ -800,11 +881,7 @@ __global__ __launch_bounds__((BlurGeom<INTERP, SUBPIX>::NT)) __attribute__((amdg
                     v = sample_q5<INTERP>(S, a.sh, a.sw, X, Y, a.b0, a.b1, a.b2, cub_tab);
                 }
                 acc[p][0] += v.r; acc[p][1] += v.g; acc[p][2] += v.b;
-                if (WITH_MASK) {
-                    const int nx = sat_short(clamp_round_i32(Xn * Wn));
-                    const int ny = sat_short(clamp_round_i32(Yn * Wn));
-                    cov[p] += ((unsigned)nx < (unsigned)a.sw && (unsigned)ny < (unsigned)a.sh) ? 1.f : 0.f;
-                }
+                if (WITH_MASK) cov[p] += vstab_nn_covered(Xn * Wn, Yn * Wn, a.sh, a.sw) ? 1.f : 0.f;
             }
         }
     }
@@ -829,15 +906,24 @@ __global__ __launch_bounds__((BlurGeom<INTERP, SUBPIX>::NT)) __attribute__((amdg
     }
 }
 
+// Tiles of tx * TILE_PX x nt / tx output pixels over n frames of dw x dh: the tile counts and the launch grid.
+int tile_grid(const char* who, int n, int dh, int dw, int tx, int nt, int* tiles_x, int* tiles_y, unsigned* grid)
+{
+    *tiles_x = (dw + tx * TILE_PX - 1) / (tx * TILE_PX);
+    *tiles_y = (dh + nt / tx - 1) / (nt / tx);
+    const unsigned long long blocks = (unsigned long long)*tiles_x * *tiles_y * n;
+    VSTAB_REQUIRE(blocks > 0 && blocks < 0x7fffffffULL, "%s: grid of %llu blocks is out of range", who, blocks);
+    *grid = (unsigned)blocks;
+    return 0;
+}
+
 template <int INTERP, int SUBPIX>
 int launch_blur(WarpArgs a, bool with_mask, hipStream_t st)
 {
     using G = BlurGeom<INTERP, SUBPIX>;
-    constexpr int TILE_W = 32 * TILE_PX, TILE_H = G::NT / 32;
-    a.tiles_x = (a.dw + TILE_W - 1) / TILE_W;
-    a.tiles_y = (a.dh + TILE_H - 1) / TILE_H;
-    const unsigned long long blocks = (unsigned long long)a.tiles_x * a.tiles_y * a.n;
-    VSTAB_REQUIRE(blocks > 0 && blocks < 0x7fffffffULL, "warp: grid of %llu blocks is out of range", blocks);
+    constexpr int TILE_W = 32 * TILE_PX;
+    unsigned blocks = 0;
+    if (int rc = tile_grid("warp", a.n, a.dh, a.dw, 32, G::NT, &a.tiles_x, &a.tiles_y, &blocks)) return rc;
     // staged-path precondition that does not depend on the block: a thread's two pixels share OpenCV's column block (the
     // u24 multiply of the window index is exact: check_common has sh, sw <= 32767 and the window is at most 4864 texels)
     a.blur_fast = ((a.bw0 >= a.dw) || (a.bw0 % TILE_W == 0)) ? 1 : 0;
@@ -873,8 +959,8 @@ int launch_blur(WarpArgs a, bool with_mask, hipStream_t st)
         a.blur_fast = 0;
         lds = sizeof(float) * 32 * 4;
     }
-    if (with_mask) hipLaunchKernelGGL((warp_blur_kernel<INTERP, SUBPIX, true>), dim3((unsigned)blocks), dim3(G::NT), lds, st, a, a.xf);
-    else hipLaunchKernelGGL((warp_blur_kernel<INTERP, SUBPIX, false>), dim3((unsigned)blocks), dim3(G::NT), lds, st, a, a.xf);
+    if (with_mask) hipLaunchKernelGGL((warp_blur_kernel<INTERP, SUBPIX, true>), dim3(blocks), dim3(G::NT), lds, st, a, a.xf);
+    else hipLaunchKernelGGL((warp_blur_kernel<INTERP, SUBPIX, false>), dim3(blocks), dim3(G::NT), lds, st, a, a.xf);
     VSTAB_HIP(hipGetLastError());
     return 0;
 }
@@ -884,8 +970,8 @@ void launch_mask(const WarpArgs& a, bool with_mask, unsigned grid, hipStream_t s
 {
 #define LAUNCH_TX(TX)                                                                                              \
     do {                                                                                                           \
-        if (with_mask) hipLaunchKernelGGL((warp_kernel<INTERP, SUBPIX, true, TX>), dim3(grid), dim3(256), 0, st, a);  \
-        else hipLaunchKernelGGL((warp_kernel<INTERP, SUBPIX, false, TX>), dim3(grid), dim3(256), 0, st, a);  \
+        if (with_mask) hipLaunchKernelGGL((warp_kernel<INTERP, SUBPIX, true, TX, WarpArgs>), dim3(grid), dim3(256), 0, st, a);  \
+        else hipLaunchKernelGGL((warp_kernel<INTERP, SUBPIX, false, TX, WarpArgs>), dim3(grid), dim3(256), 0, st, a);  \
     } while (0)
     if (tx == 16) LAUNCH_TX(16);
     else if (tx == 64) LAUNCH_TX(64);
@@ -900,11 +986,8 @@ int launch_warp(WarpArgs a, int interp, int subpix, bool with_mask, hipStream_t 
     // (profiles/r01_warp_tile_sweep.md)
     int tx = 32;
     if (const char* e = getenv("VSTAB_WARP_TX")) { const int v = atoi(e); if (v == 8 || v == 16 || v == 64) tx = v; }
-    a.tiles_x = (a.dw + tx * TILE_PX - 1) / (tx * TILE_PX);
-    a.tiles_y = (a.dh + 256 / tx - 1) / (256 / tx);
-    const unsigned long long blocks = (unsigned long long)a.tiles_x * a.tiles_y * a.n;
-    VSTAB_REQUIRE(blocks > 0 && blocks < 0x7fffffffULL, "warp: grid of %llu blocks is out of range", blocks);
-    const unsigned grid = (unsigned)blocks;
+    unsigned grid = 0;
+    if (int rc = tile_grid("warp", a.n, a.dh, a.dw, tx, 256, &a.tiles_x, &a.tiles_y, &grid)) return rc;
     if (interp == VSTAB_INTERP_BICUBIC) launch_mask<VSTAB_INTERP_BICUBIC, VSTAB_SUBPIX_Q5>(a, with_mask, grid, st, tx);
     else if (subpix == VSTAB_SUBPIX_EXACT) launch_mask<VSTAB_INTERP_BILINEAR, VSTAB_SUBPIX_EXACT>(a, with_mask, grid, st, tx);
     else launch_mask<VSTAB_INTERP_BILINEAR, VSTAB_SUBPIX_Q5>(a, with_mask, grid, st, tx);
@@ -918,8 +1001,6 @@ int launch_warp_blur(const WarpArgs& a, int interp, int subpix, bool with_mask, 
     if (subpix == VSTAB_SUBPIX_EXACT) return launch_blur<VSTAB_INTERP_BILINEAR, VSTAB_SUBPIX_EXACT>(a, with_mask, st);
     return launch_blur<VSTAB_INTERP_BILINEAR, VSTAB_SUBPIX_Q5>(a, with_mask, st);
 }
-
-void fill_xform(const float* m32, WarpXform* xf) { vstab_fill_xform(m32, xf); }
 
 int check_common(const char* who, vstab_ctx* ctx, const void* src, int n, int sh, int sw, const void* mats,
                  int dh, int dw, int interp, const float* border, int subpix, const void* dst)
@@ -935,18 +1016,35 @@ int check_common(const char* who, vstab_ctx* ctx, const void* src, int n, int sh
     return 0;
 }
 
-void fill_geometry(WarpArgs& a, int n, int sh, int sw, int dh, int dw, const float* border, const float* dst, const float* mask)
+// OpenCV's column block width for a dw x dh output and whether it is a power of two (block_origin's cheap form).
+void set_block_width(int dh, int dw, int* bw0, int* bw0_pow2)
 {
+    *bw0 = vstab_warp_block_width(dh, dw);
+    *bw0_pow2 = (*bw0 & (*bw0 - 1)) == 0;
+}
+
+// What every warp launch shares: pointers, sizes, OpenCV's column block width, the border colour.
+void fill_geometry(WarpArgs& a, const float* src, const WarpXform* xf, int n, int sh, int sw, int dh, int dw, const float* border,
+                   float* dst, float* mask, unsigned* pad_count)
+{
+    a.src = src; a.dst = dst; a.mask = mask; a.pad_count = pad_count; a.xf = xf;
+    a.samples = 1; a.nxf_per_frame = 1;
     a.n = n; a.sh = sh; a.sw = sw; a.dh = dh; a.dw = dw;
-    const int BLOCK_SZ = 32;
-    int bh0 = BLOCK_SZ / 2 < dh ? BLOCK_SZ / 2 : dh;
-    int bw0 = BLOCK_SZ * BLOCK_SZ / bh0 < dw ? BLOCK_SZ * BLOCK_SZ / bh0 : dw;
-    a.bw0 = bw0;
-    a.bw0_pow2 = (bw0 & (bw0 - 1)) == 0;
+    set_block_width(dh, dw, &a.bw0, &a.bw0_pow2);
     a.b0 = border[0]; a.b1 = border[1]; a.b2 = border[2];
 }
 
 }  // namespace
+
+int vstab_stage_xforms(vstab_ctx* ctx, const float* m32, size_t count, const WarpXform** dev_out)
+{
+    std::vector<WarpXform> xf(count);
+    for (size_t i = 0; i < count; i++) vstab_fill_xform(m32 + i * 9, &xf[i]);
+    void* d_xf = nullptr;
+    if (vstab_stage_params(ctx, xf.data(), xf.size() * sizeof(WarpXform), &d_xf)) return 1;
+    *dev_out = static_cast<const WarpXform*>(d_xf);
+    return 0;
+}
 
 // ---- the counts' way to the host (see vstab_internal.h) ----
 namespace {
@@ -1005,16 +1103,10 @@ extern "C" int vstab_warp_batch(vstab_ctx* ctx, const float* src, int n, int src
 {
     if (int rc = check_common("vstab_warp_batch", ctx, src, n, src_h, src_w, matrices, out_h, out_w, interp, border_rgb, subpix, dst)) return rc;
     VSTAB_HIP(hipSetDevice(ctx->device));
-    std::vector<WarpXform> xf((size_t)n);
-    for (int i = 0; i < n; i++) fill_xform(matrices + (size_t)i * 9, &xf[i]);
-    void* d_xf = nullptr;
-    if (vstab_stage_params(ctx, xf.data(), xf.size() * sizeof(WarpXform), &d_xf)) return 1;
-
+    const WarpXform* xf = nullptr;
+    if (vstab_stage_xforms(ctx, matrices, (size_t)n, &xf)) return 1;
     WarpArgs a{};
-    a.src = src; a.dst = dst; a.mask = mask; a.pad_count = pad_count;
-    a.xf = static_cast<const WarpXform*>(d_xf);
-    a.samples = 1; a.nxf_per_frame = 1;
-    fill_geometry(a, n, src_h, src_w, out_h, out_w, border_rgb, dst, mask);
+    fill_geometry(a, src, xf, n, src_h, src_w, out_h, out_w, border_rgb, dst, mask, pad_count);
     if (pad_count) VSTAB_HIP(hipMemsetAsync(pad_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
     {
         KernelTimer timer(ctx, "warp");
@@ -1036,10 +1128,7 @@ extern "C" int vstab_warp_batch_planned(vstab_ctx* ctx, const float* src, int fi
     VSTAB_REQUIRE(xf != nullptr, "vstab_warp_batch_planned: frames [%d, %d) are outside the pending device plan", first, first + n);
     VSTAB_HIP(hipSetDevice(ctx->device));
     WarpArgs a{};
-    a.src = src; a.dst = dst; a.mask = mask; a.pad_count = pad_count;
-    a.xf = xf;
-    a.samples = 1; a.nxf_per_frame = 1;
-    fill_geometry(a, n, src_h, src_w, out_h, out_w, border_rgb, dst, mask);
+    fill_geometry(a, src, xf, n, src_h, src_w, out_h, out_w, border_rgb, dst, mask, pad_count);
     if (pad_count && pad_count != ctx->plan_zeroed_ptr) VSTAB_HIP(hipMemsetAsync(pad_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
     ctx->plan_zeroed_ptr = nullptr;   // (the plan kernel zeroed a registered array once: a second warp into it fills it itself)
     {
@@ -1090,16 +1179,11 @@ extern "C" int vstab_warp_blur_clip_batch(vstab_ctx* ctx, const float* src, int 
     const int per_frame = (clip_total <= 1) ? 1 : samples;
     std::vector<float> m32((size_t)n * per_frame * 9);
     if (int rc = vstab_blur_sample_matrices(clip_matrices, clip_total, clip_first, n, ts, samples, m32.data())) return rc;
-    std::vector<WarpXform> xf((size_t)n * per_frame);
-    for (size_t i = 0; i < xf.size(); i++) fill_xform(m32.data() + i * 9, &xf[i]);
-    void* d_xf = nullptr;
-    if (vstab_stage_params(ctx, xf.data(), xf.size() * sizeof(WarpXform), &d_xf)) return 1;
-
+    const WarpXform* xf = nullptr;
+    if (vstab_stage_xforms(ctx, m32.data(), (size_t)n * per_frame, &xf)) return 1;
     WarpArgs a{};
-    a.src = src; a.dst = dst; a.mask = mask; a.pad_count = nullptr;
-    a.xf = static_cast<const WarpXform*>(d_xf);
+    fill_geometry(a, src, xf, n, src_h, src_w, out_h, out_w, border_rgb, dst, mask, nullptr);
     a.samples = samples; a.nxf_per_frame = per_frame;
-    fill_geometry(a, n, src_h, src_w, out_h, out_w, border_rgb, dst, mask);
     KernelTimer timer(ctx, "warp_blur");
     return launch_warp_blur(a, interp, subpix, mask != nullptr, ctx->stream);
 }
@@ -1110,6 +1194,38 @@ extern "C" int vstab_warp_blur_batch(vstab_ctx* ctx, const float* src, int n, in
 {
     return vstab_warp_blur_clip_batch(ctx, src, n, src_h, src_w, matrices, n, 0, ts, samples, out_h, out_w, interp, border_rgb,
                                       subpix, dst, mask);
+}
+
+extern "C" int vstab_mesh_warp_batch(vstab_ctx* ctx, const float* src, int n, int src_h, int src_w, const float* matrices,
+                                     int out_h, int out_w, const float* border_rgb, int subpix, const float* offsets, int mw, int mh,
+                                     float* dst, float* mask, uint32_t* pad_count)
+{
+    const char* who = "vstab_mesh_warp_batch";
+    if (int rc = check_common(who, ctx, src, n, src_h, src_w, matrices, out_h, out_w, VSTAB_INTERP_BILINEAR, border_rgb, subpix, dst)) return rc;
+    VSTAB_REQUIRE(offsets != nullptr, "%s: NULL pointer argument", who);
+    VSTAB_REQUIRE(src_h >= 2 && src_w >= 2, "%s: bad size (n=%d src=%dx%d out=%dx%d; the source must be at least 2x2)", who, n, src_w, src_h, out_w, out_h);
+    VSTAB_REQUIRE(mw >= 2 && mh >= 2 && mw <= MESH_MAX_VERTS && mh <= MESH_MAX_VERTS, "%s: %dx%d vertices outside 2..%d", who, mw, mh, MESH_MAX_VERTS);
+    VSTAB_HIP(hipSetDevice(ctx->device));
+    const WarpXform* xf = nullptr;
+    if (vstab_stage_xforms(ctx, matrices, (size_t)n, &xf)) return 1;
+    MeshWarpArgs a{};
+    fill_geometry(a, src, xf, n, src_h, src_w, out_h, out_w, border_rgb, dst, mask, pad_count);
+    a.offsets = offsets; a.mw = mw; a.mh = mh;
+    unsigned blocks = 0;
+    if (int rc = tile_grid(who, n, out_h, out_w, 32, 256, &a.tiles_x, &a.tiles_y, &blocks)) return rc;
+    if (pad_count) VSTAB_HIP(hipMemsetAsync(pad_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
+    const size_t lds = (size_t)mw * mh * 2 * sizeof(float);    // <= 33.8 KB
+    const dim3 grid(blocks), block(256);
+    KernelTimer timer(ctx, "mesh_warp");
+    if (subpix == VSTAB_SUBPIX_EXACT) {
+        if (mask) hipLaunchKernelGGL((mesh_warp_kernel<VSTAB_SUBPIX_EXACT, true>), grid, block, lds, ctx->stream, a);
+        else hipLaunchKernelGGL((mesh_warp_kernel<VSTAB_SUBPIX_EXACT, false>), grid, block, lds, ctx->stream, a);
+    } else {
+        if (mask) hipLaunchKernelGGL((mesh_warp_kernel<VSTAB_SUBPIX_Q5, true>), grid, block, lds, ctx->stream, a);
+        else hipLaunchKernelGGL((mesh_warp_kernel<VSTAB_SUBPIX_Q5, false>), grid, block, lds, ctx->stream, a);
+    }
+    VSTAB_HIP(hipGetLastError());
+    return 0;
 }
 
 // ---- temporal fill: padding pixels taken from neighbouring frames ----------------------------------------------------
@@ -1147,19 +1263,10 @@ struct FillArgs {
 template <int INTERP, int SUBPIX>
 __global__ __launch_bounds__(256) void temporal_fill_kernel(FillArgs a, const FillCand* __restrict__ cands)
 {
-    constexpr int TILE_TX = 32, TILE_W = TILE_TX * TILE_PX, TILE_H = 256 / TILE_TX;
-    __shared__ unsigned s_cnt[2][4];
+    constexpr int TILE_TX = 32;
     __shared__ __attribute__((aligned(16))) float s_cub[32 * 4];
-    const unsigned t = xcd_remap(blockIdx.x, gridDim.x);
-    const unsigned tiles_per_frame = (unsigned)a.tiles_x * a.tiles_y;
-    const int frame = t / tiles_per_frame;
-    const unsigned tr = t - frame * tiles_per_frame;
-    const int tile_y = tr / a.tiles_x, tile_x = tr - tile_y * a.tiles_x;
-    const int tx = threadIdx.x % TILE_TX, ty = threadIdx.x / TILE_TX;
-    const int x0 = tile_x * TILE_W + tx;
-    const int y = tile_y * TILE_H + ty;
-    const bool active = (y < a.dh) && (x0 < a.dw);
-    const int npx = active ? (a.dw - x0 + TILE_TX - 1) / TILE_TX : 0;
+    const TileShell<TILE_TX> t(a.tiles_x, a.tiles_y, a.dh, a.dw);
+    const int frame = t.frame, x0 = t.x0, y = t.y, npx = t.npx;
 
     float* __restrict__ Mk = a.mask + (size_t)frame * a.dh * a.dw;
     const unsigned row = (unsigned)y * (unsigned)a.dw;
@@ -1220,7 +1327,7 @@ __global__ __launch_bounds__(256) void temporal_fill_kernel(FillArgs a, const Fi
                     valid = flx >= 0.f && flx < (float)(a.sw - 1) && fly >= 0.f && fly < (float)(a.sh - 1);
                     return valid ? sample_exact(S, a.sh, a.sw, fsx, fsy, 0.f, 0.f, 0.f) : Px{0.f, 0.f, 0.f};
                 },
-                c_unused);
+                NoDisplacement{}, c_unused);
             if (valid) {
                 const unsigned pix = row + (unsigned)x;
                 f3 rgb = {v.r, v.g, v.b};
@@ -1235,19 +1342,10 @@ __global__ __launch_bounds__(256) void temporal_fill_kernel(FillArgs a, const Fi
     }
 
     if (a.fill_count != nullptr || a.pad_count != nullptr) {
-        unsigned left = 0;
+        unsigned cnt[2] = {filled, 0};   // filled, left
 #pragma unroll
-        for (int p = 0; p < TILE_PX; p++) left += need[p] ? 1u : 0u;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) { filled += __shfl_down(filled, off); left += __shfl_down(left, off); }
-        if ((threadIdx.x & 63) == 0) { s_cnt[0][threadIdx.x >> 6] = filled; s_cnt[1][threadIdx.x >> 6] = left; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned f = s_cnt[0][0] + s_cnt[0][1] + s_cnt[0][2] + s_cnt[0][3];
-            const unsigned l = s_cnt[1][0] + s_cnt[1][1] + s_cnt[1][2] + s_cnt[1][3];
-            if (f && a.fill_count) atomicAdd(a.fill_count + frame, f);
-            if (l && a.pad_count) atomicAdd(a.pad_count + frame, l);
-        }
+        for (int p = 0; p < TILE_PX; p++) cnt[1] += need[p] ? 1u : 0u;
+        block_count_add<2>(cnt, {a.fill_count, a.pad_count}, frame);
     }
 }
 
@@ -1271,7 +1369,7 @@ extern "C" int vstab_temporal_fill_batch(vstab_ctx* ctx, const float* src, int c
         const int f = cand_frame[i];
         VSTAB_REQUIRE(f >= -1 && f < clip_frames, "%s: cand_frame[%zu]=%d outside [-1, %d)", who, i, f, clip_frames);
         const float* m32 = matrices + i * 9;
-        fill_xform(m32, &cd[i].xf);
+        vstab_fill_xform(m32, &cd[i].xf);
         // a matrix that cv::invert would refuse (zero or non-finite determinant) has no source position: no candidate
         double M[9], inv[9];
         bool finite = true;
@@ -1285,24 +1383,20 @@ extern "C" int vstab_temporal_fill_batch(vstab_ctx* ctx, const float* src, int c
     void* d_cd = nullptr;
     if (vstab_stage_params(ctx, cd.data(), cd.size() * sizeof(FillCand), &d_cd)) return 1;
 
-    WarpArgs g{};
-    fill_geometry(g, n, src_h, src_w, out_h, out_w, no_border, dst, mask);
     FillArgs a{};
     a.src = src; a.dst = dst; a.mask = mask; a.filled_from = reinterpret_cast<signed char*>(filled_from);
     a.fill_count = fill_count; a.pad_count = pad_count;
     a.n = n; a.K = K; a.sh = src_h; a.sw = src_w; a.dh = out_h; a.dw = out_w;
-    a.bw0 = g.bw0; a.bw0_pow2 = g.bw0_pow2;
-    a.tiles_x = (out_w + 32 * TILE_PX - 1) / (32 * TILE_PX);
-    a.tiles_y = (out_h + 7) / 8;
-    const unsigned long long blocks = (unsigned long long)a.tiles_x * a.tiles_y * n;
-    VSTAB_REQUIRE(blocks > 0 && blocks < 0x7fffffffULL, "%s: grid of %llu blocks is out of range", who, blocks);
+    set_block_width(out_h, out_w, &a.bw0, &a.bw0_pow2);
+    unsigned blocks = 0;
+    if (int rc = tile_grid(who, n, out_h, out_w, 32, 256, &a.tiles_x, &a.tiles_y, &blocks)) return rc;
     const size_t px = (size_t)n * out_h * out_w;
     if (filled_from) VSTAB_HIP(hipMemsetAsync(filled_from, 0xff, px, ctx->stream));   // -1: not filled
     if (fill_count) VSTAB_HIP(hipMemsetAsync(fill_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
     if (pad_count) VSTAB_HIP(hipMemsetAsync(pad_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
     const FillCand* cands = static_cast<const FillCand*>(d_cd);
     KernelTimer timer(ctx, "fill");
-    const dim3 grid((unsigned)blocks), block(256);
+    const dim3 grid(blocks), block(256);
     if (interp == VSTAB_INTERP_BICUBIC) hipLaunchKernelGGL((temporal_fill_kernel<VSTAB_INTERP_BICUBIC, VSTAB_SUBPIX_Q5>), grid, block, 0, ctx->stream, a, cands);
     else if (subpix == VSTAB_SUBPIX_EXACT) hipLaunchKernelGGL((temporal_fill_kernel<VSTAB_INTERP_BILINEAR, VSTAB_SUBPIX_EXACT>), grid, block, 0, ctx->stream, a, cands);
     else hipLaunchKernelGGL((temporal_fill_kernel<VSTAB_INTERP_BILINEAR, VSTAB_SUBPIX_Q5>), grid, block, 0, ctx->stream, a, cands);

@@ -1,10 +1,11 @@
 """Mesh warp: take out the residual motion that one global fit per frame pair leaves (parallax, rolling-shutter skew, lens
 breathing), after MeshFlow (Liu et al., ECCV 2016: per-vertex motion profiles).
 
-The device side is csrc/vstab_mesh.hip: `native.Context.mesh_residual_batch` reduces the stride-8 flow grid a Flow run
-already has to one residual per mesh vertex and pair, `native.Context.mesh_warp_batch` is the plain warp with a per-vertex
-displacement of the source frame (include/vstab.h states both rules).  This module is the host side between the two: the
-checks of a request and the vertex paths.  Nothing here needs a GPU.
+The device side: `native.Context.mesh_residual_batch` (csrc/vstab_mesh.hip) reduces the stride-8 flow grid a Flow run
+already has to one residual per mesh vertex and pair, `native.Context.mesh_warp_batch` (csrc/vstab_warp.hip:
+mesh_warp_kernel) is the plain warp with a per-vertex displacement of the source frame (include/vstab.h states both
+rules). This module is the host side between the two: the checks of a request and the vertex paths. Nothing here needs
+a GPU.
 
 A vertex path is treated exactly as the global parameters are: P_0 = 0, P_{i+1} = P_i + r_i, sent through the same
 trajectory routine with the plan's own smooth / fps / strength / camera_lock, so local and global smoothing agree by

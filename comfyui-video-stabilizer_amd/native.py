@@ -478,22 +478,33 @@ class Context:
         return dst
 
     # ------------------------------------------------------------------ warp
-    def warp_batch(self, frames, matrices, out_size, interp="bilinear", border=(0.0, 0.0, 0.0),
-                   subpix=None, want_mask=True, want_count=False, out=None, out_mask=None):
-        """frames [N,H,W,3] f32 (device or host) -> (dst [N,h,w,3], mask [N,h,w] | None, counts [N] | None)."""
+    def _warp_io(self, who, frames, out_size, border, want_mask, want_count, out=None, out_mask=None, counts=None):
+        """What warp_batch, warp_batch_planned and mesh_warp_batch prepare alike: the source on the device, the sizes, the border colour and the
+        dst / mask / counts tensors (`out` / `out_mask` / `counts` are taken instead of fresh ones where given and fitting).
+        -> (src, (n, sh, sw), (out_h, out_w), border f32 [3], dst, mask | None, counts | None)"""
         torch = self.torch
         src = self._as_device_frames(frames)
         n, sh, sw, ch = src.shape
         if ch != 3:
-            raise VstabError(f"warp_batch expects 3-channel frames, got {ch}")
+            raise VstabError(f"{who} expects 3-channel frames, got {ch}")
         out_w, out_h = int(out_size[0]), int(out_size[1])
-        m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(n, 9)
         b = np.ascontiguousarray(border, dtype=np.float32).reshape(3)
         dst = out if out is not None else torch.empty((n, out_h, out_w, 3), dtype=torch.float32, device=self.device)
         mask = None
         if want_mask:
             mask = out_mask if out_mask is not None else torch.empty((n, out_h, out_w), dtype=torch.float32, device=self.device)
-        counts = torch.empty((n,), dtype=torch.int32, device=self.device) if (want_count and want_mask) else None
+        if not (want_count and want_mask):
+            counts = None
+        elif counts is None or counts.shape[0] != n:
+            counts = torch.empty((n,), dtype=torch.int32, device=self.device)
+        return src, (n, sh, sw), (out_h, out_w), b, dst, mask, counts
+
+    def warp_batch(self, frames, matrices, out_size, interp="bilinear", border=(0.0, 0.0, 0.0),
+                   subpix=None, want_mask=True, want_count=False, out=None, out_mask=None):
+        """frames [N,H,W,3] f32 (device or host) -> (dst [N,h,w,3], mask [N,h,w] | None, counts [N] | None)."""
+        src, (n, sh, sw), (out_h, out_w), b, dst, mask, counts = self._warp_io(
+            "warp_batch", frames, out_size, border, want_mask, want_count, out, out_mask)
+        m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(n, 9)
         self.use_torch_stream()
         _check(
             self.lib.vstab_warp_batch(
@@ -739,22 +750,15 @@ class Context:
         include/vstab.h).  offsets f32 [N,mh,mw,2] in full-resolution px (host or device) ->
         (dst [N,h,w,3], mask [N,h,w] | None, counts [N] | None).  All-zero offsets give warp_batch's bits."""
         torch = self.torch
-        src = self._as_device_frames(frames)
-        n, sh, sw, ch = src.shape
-        if ch != 3:
-            raise VstabError(f"mesh_warp_batch expects 3-channel frames, got {ch}")
+        src, (n, sh, sw), (out_h, out_w), b, dst, mask, counts = self._warp_io(
+            "mesh_warp_batch", frames, out_size, border, want_mask, want_count)
         if not isinstance(offsets, torch.Tensor):
             offsets = torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.float32))
         if offsets.dim() != 4 or offsets.shape[0] != n or offsets.shape[3] != 2 or offsets.dtype != torch.float32:
             raise ValueError(f"mesh_warp_batch: offsets {tuple(offsets.shape)} {offsets.dtype} are not float32 [{n},mh,mw,2]")
         mw, mh = self._check_mesh("mesh_warp_batch", offsets.shape[2], offsets.shape[1])
         offsets = offsets.to(self.device).contiguous()
-        out_w, out_h = int(out_size[0]), int(out_size[1])
         m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(n, 9)
-        b = np.ascontiguousarray(border, dtype=np.float32).reshape(3)
-        dst = torch.empty((n, out_h, out_w, 3), dtype=torch.float32, device=self.device)
-        mask = torch.empty((n, out_h, out_w), dtype=torch.float32, device=self.device) if want_mask else None
-        counts = torch.empty((n,), dtype=torch.int32, device=self.device) if (want_count and want_mask) else None
         self.use_torch_stream()
         _check(self.lib.vstab_mesh_warp_batch(
             self.handle, _dev_ptr(src), n, sh, sw, m.ctypes.data, out_h, out_w, b.ctypes.data, SUBPIX[subpix or DEFAULT_SUBPIX],
@@ -885,21 +889,12 @@ class Context:
 
     def warp_batch_planned(self, frames, first, out_size, border=(0.0, 0.0, 0.0), subpix=None, want_mask=True, want_count=False):
         """warp_batch (bilinear) for frames [first, first + n) of the clip whose plan is pending on the device."""
-        torch = self.torch
-        src = self._as_device_frames(frames)
-        n, sh, sw, ch = src.shape
-        if ch != 3:
-            raise VstabError(f"warp_batch_planned expects 3-channel frames, got {ch}")
-        out_w, out_h = int(out_size[0]), int(out_size[1])
-        b = np.ascontiguousarray(border, dtype=np.float32).reshape(3)
-        dst = torch.empty((n, out_h, out_w, 3), dtype=torch.float32, device=self.device)
-        mask = torch.empty((n, out_h, out_w), dtype=torch.float32, device=self.device) if want_mask else None
-        counts = None
+        handed = None
         if want_count and want_mask:
-            counts = getattr(self, "_planned_counts", None)      # zeroed by the plan kernel, if the plan call was told of this warp
+            handed = getattr(self, "_planned_counts", None)      # zeroed by the plan kernel, if the plan call was told of this warp
             self._planned_counts = None
-            if counts is None or counts.shape[0] != n:
-                counts = torch.empty((n,), dtype=torch.int32, device=self.device)
+        src, (n, sh, sw), (out_h, out_w), b, dst, mask, counts = self._warp_io(
+            "warp_batch_planned", frames, out_size, border, want_mask, want_count, counts=handed)
         self.use_torch_stream()
         _check(self.lib.vstab_warp_batch_planned(
             self.handle, _dev_ptr(src), int(first), n, sh, sw, out_h, out_w, INTERP["bilinear"], b.ctypes.data,

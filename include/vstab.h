@@ -510,7 +510,9 @@ int vstab_mesh_residual_batch(vstab_ctx* ctx, const float* grid_flow, int pairs,
  *     pad_count.
  * Invariant: all-zero offsets give dst, mask and pad_count bit-identical to vstab_warp_batch (c = +0.0, and v - 0.0 == v).
  *   offsets dev [n, mh, mw, 2] f32 (x, y), full-resolution px;  2 <= mw, mh <= 65;  src_w, src_h >= 2.
- * The other arguments are vstab_warp_batch's, interp fixed to bilinear.  Each workgroup stages its frame's vertex table in
+ * The other arguments are vstab_warp_batch's, interp fixed to bilinear, and are checked as vstab_warp_batch checks them
+ * (same error texts under this function's name); a 1-px source and a vertex count out of range are refused in front of the
+ * launch with texts of their own.  Each workgroup stages its frame's vertex table in
  * LDS; apart from that it is the same HBM stream as the plain warp (same tile, same XCD remap).  Timing kind "mesh_warp". */
 int vstab_mesh_warp_batch(vstab_ctx* ctx, const float* src, int n, int src_h, int src_w, const float* matrices,
                           int out_h, int out_w, const float* border_rgb, int subpix, const float* offsets, int mw, int mh,

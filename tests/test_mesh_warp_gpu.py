@@ -119,7 +119,8 @@ def test_residual_kernel_argument_checks(pkg, ctx):
 @pytest.mark.parametrize("kind,size,out_size", [
     ("similarity", (1920, 1080), (1920, 1080)), ("perspective", (1920, 1080), (1920, 1080)),
     ("similarity", (480, 270), (523, 301)), ("perspective", (333, 187), (333, 187)), ("perspective", (960, 540), (1011, 577)),
-    ("horizon", (160, 90), (160, 90)), ("far", (160, 90), (177, 95)), ("similarity", (61, 45), (1100, 20))])
+    ("horizon", (160, 90), (160, 90)), ("far", (160, 90), (177, 95)), ("similarity", (61, 45), (1100, 20)),
+    ("similarity", (61, 45), (333, 11))])   # 11 rows: column blocks of 1024 // 11 = 93 px, neither a power of two nor the whole row
 def test_zero_offsets_are_the_plain_warp(pkg, ctx, subpix, kind, size, out_size):
     import torch
 
@@ -146,7 +147,8 @@ def test_zero_offsets_are_the_plain_warp(pkg, ctx, subpix, kind, size, out_size)
 @pytest.mark.parametrize("kind,size,out_size,verts", [("similarity", (320, 180), (320, 180), (17, 10)),
                                                       ("perspective", (213, 121), (240, 140), (9, 6)),
                                                       ("translation", (96, 64), (1100, 24), (2, 2)),
-                                                      ("horizon", (120, 80), (120, 80), (5, 4))])
+                                                      ("horizon", (120, 80), (120, 80), (5, 4)),
+                                                      ("perspective", (96, 64), (333, 11), (3, 3))])   # 93-px column blocks
 def test_mesh_warp_equals_the_restatement(pkg, ctx, subpix, kind, size, out_size, verts):
     import torch
 
