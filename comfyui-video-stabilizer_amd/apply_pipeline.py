@@ -13,6 +13,7 @@ from typing import Any, Callable, Dict, List, Optional, Tuple
 import numpy as np
 
 from . import host_math as hm
+from . import mesh_warp as mesh_warp_mod
 from . import native
 from .comfy_compat import check_interrupt
 from .meta_v2 import MotionMeta, motion_meta_from_stabilization_warp, resolve_motion_meta
@@ -47,16 +48,17 @@ def _validate_context(context: hm.VideoContext, motion: MotionMeta) -> None:
         )
 
 
-def _resolve_motion_for_context(meta: Dict[str, Any], context: hm.VideoContext) -> MotionMeta:
-    """Pick the block whose input_size matches the connected frames (motion_apply.py:45-67)."""
+def _resolve_motion_and_origin(meta: Dict[str, Any], context: hm.VideoContext) -> Tuple[MotionMeta, bool]:
+    """Pick the block whose input_size matches the connected frames (motion_apply.py:45-67) -> (the motion, whether it is
+    the inverse derived from stabilization_warp rather than the motion_meta block itself)."""
     if not isinstance(meta, dict):
-        return resolve_motion_meta(meta)
+        return resolve_motion_meta(meta), False
     size = (context.width, context.height)
     block = meta.get("motion_meta")
     if isinstance(block, dict):
         direct = resolve_motion_meta({"motion_meta": block})
         if size == direct.input_size:
-            return direct
+            return direct, False
     warp = meta.get("stabilization_warp")
     if isinstance(warp, dict):
         fps = float(block.get("fps", 16.0)) if isinstance(block, dict) else 16.0
@@ -64,8 +66,64 @@ def _resolve_motion_for_context(meta: Dict[str, Any], context: hm.VideoContext) 
         if inverse_block is not None:
             inverse = resolve_motion_meta({"motion_meta": inverse_block})
             if size == inverse.input_size:
-                return inverse
-    return resolve_motion_meta(meta)
+                return inverse, True
+    return resolve_motion_meta(meta), not isinstance(block, dict)
+
+
+def _resolve_motion_for_context(meta: Dict[str, Any], context: hm.VideoContext) -> MotionMeta:
+    return _resolve_motion_and_origin(meta, context)[0]
+
+
+@dataclass
+class MeshReplay:
+    """What apply_motion(mesh=True) hands to the warp: the recorded vertex offsets and the direction they are applied in."""
+
+    direction: str          # "forward": the mesh warp itself; "inverse": its per-pixel inverse (mesh_unwarp_batch)
+    offsets: np.ndarray     # f32 [N,mh,mw,2]
+
+
+def _check_mesh_request(framing_mode: str, interpolation: str, motion_blur: float) -> None:
+    """What mesh=True cannot be combined with, each with its reason; needs neither the meta nor a GPU."""
+    if interpolation == "bicubic":
+        raise ValueError("mesh=True is not supported with bicubic interpolation: the mesh warp and its inverse exist for the "
+                         "bilinear sampler only.")
+    if float(motion_blur) > 0.0:
+        raise ValueError(f"mesh=True is not supported with motion_blur={motion_blur}: the blur samples are global matrices, "
+                         "which do not describe a mesh-warped frame.")
+    if framing_mode == "crop":
+        raise ValueError("mesh=True is not supported with framing_mode 'crop': the common coverage is computed from matrices "
+                         "only, so it cannot keep a per-vertex displacement free of padding.")
+
+
+def _mesh_replay(meta, motion: MotionMeta, derived: bool, framing_mode: str) -> MeshReplay:
+    """The direction follows the block the call resolved: motion_meta itself replays the mesh warp (its domain is the block's
+    input canvas), the inverse derived from stabilization_warp undoes it (its domain is the block's output canvas)."""
+    if derived:
+        if framing_mode == "expand":
+            raise ValueError("mesh=True restores with framing_mode 'crop_and_pad' only: the mesh lies over the original canvas, "
+                             "which 'expand' would replace by another.")
+        parsed = mesh_warp_mod.parse_motion_block(meta, motion.frame_count, motion.output_size)
+        return MeshReplay("inverse", parsed.offsets)
+    parsed = mesh_warp_mod.parse_motion_block(meta, motion.frame_count, motion.input_size)
+    return MeshReplay("forward", parsed.offsets)
+
+
+def _mesh_warp(ctx, device_frames, matrices, output_size, padding_rgb, replay: MeshReplay, progress_callback, first: int = 0):
+    """_warp's plain branch with the recorded mesh: -> (frames, masks [n,h,w], unconverged_max)."""
+    n = device_frames.shape[0]
+    check_interrupt()
+    m32 = np.stack([np.asarray(m, dtype=np.float32) for m in matrices[first:first + n]])
+    offsets = replay.offsets[first:first + n]
+    border = hm.border_value(padding_rgb)
+    unconverged_max = 0
+    if replay.direction == "forward":
+        dst, mask, _ = ctx.mesh_warp_batch(device_frames, m32, output_size, offsets, border=border, want_mask=True)
+    else:
+        dst, mask, _, unconverged = ctx.mesh_unwarp_batch(device_frames, m32, output_size, offsets, border=border, want_mask=True,
+                                                          want_unconverged=True)
+        unconverged_max = int(unconverged.max().item()) if n else 0
+    _tick(progress_callback, n)
+    return dst, mask, unconverged_max
 
 
 def _tick(cb: Optional[ProgressCallback], times: int) -> None:
@@ -170,11 +228,12 @@ def _expand_matrices(matrices: List[np.ndarray], input_size: Tuple[int, int]):
 
 def apply_motion_on_device(ctx, device_frames, first: int, motion: MotionMeta, meta: Dict[str, Any], padding_rgb, *,
                            framing_mode: str, interpolation: str, motion_blur: float, motion_blur_samples: int,
-                           progress_callback: Optional[ProgressCallback] = None):
+                           progress_callback: Optional[ProgressCallback] = None, mesh_replay: Optional[MeshReplay] = None):
     """motion_apply.py:311-428 for frames [first, first + n) of the clip described by `motion` (already resolved and
     validated).  Everything that spans the clip -- the common coverage of `crop`, the bounding box of `expand`, the
     neighbour matrix of a blurred frame -- is a function of the replicated matrices alone, so a shard needs no
-    exchange with other ranks.  Returns device tensors (frames [n,h,w,3], masks [n,h,w]) and the meta."""
+    exchange with other ranks.  Returns device tensors (frames [n,h,w,3], masks [n,h,w]) and the meta.
+    mesh_replay (apply_motion's mesh=True, already checked): the plain warp is replaced by the mesh warp or its inverse."""
     matrices = [t.matrix for t in motion.per_frame]
     output_size = motion.output_size
     interpolation = _check_interpolation(interpolation)
@@ -187,7 +246,15 @@ def apply_motion_on_device(ctx, device_frames, first: int, motion: MotionMeta, m
         raise ValueError(f"Unsupported framing_mode {framing_mode!r}; expected 'crop_and_pad', 'crop', or 'expand'.")
 
     kw = dict(progress_callback=progress_callback, first=first)
-    if requested == "crop_and_pad":
+    unconverged_max = 0
+    if mesh_replay is not None:
+        _check_mesh_request(requested, interpolation, motion_blur)
+        if requested == "expand":
+            if mesh_replay.direction != "forward":
+                raise ValueError("mesh=True restores with framing_mode 'crop_and_pad' only.")
+            matrices, output_size = _expand_matrices(matrices, motion.input_size)
+        frames, masks, unconverged_max = _mesh_warp(ctx, device_frames, matrices, output_size, padding_rgb, mesh_replay, **kw)
+    elif requested == "crop_and_pad":
         frames, masks = _warp(ctx, device_frames, matrices, output_size, interpolation, padding_rgb, motion_blur,
                               motion_blur_samples, masks_zero=False, **kw)
     elif requested == "crop":
@@ -216,6 +283,8 @@ def apply_motion_on_device(ctx, device_frames, first: int, motion: MotionMeta, m
         "motion_blur_samples": motion_blur_samples,
         "source": motion.source,
     }
+    if mesh_replay is not None:
+        result_meta["motion_apply"]["mesh"] = {"direction": mesh_replay.direction, "unconverged_max": unconverged_max}
     return frames, masks, result_meta
 
 
@@ -231,21 +300,37 @@ def apply_motion(
     progress_callback: Optional[ProgressCallback] = None,
     ctx: Optional[native.Context] = None,
     keep_on_device: bool = False,
+    mesh: bool = False,
 ) -> MotionApplyResult:
-    """Signature of the reference's apply_motion (motion_apply.py:297-307) plus GPU-context extras."""
+    """Signature of the reference's apply_motion (motion_apply.py:297-307) plus GPU-context extras.
+    mesh (beyond the reference, False by default): True replays the per-vertex offsets a mesh-warped Flow run recorded
+    (meta["mesh_warp"]["motion"], Flow's mesh_motion=True) next to the matrices.  On the run's source frames the resolved
+    block is motion_meta and the mesh warp is applied again (crop_and_pad or expand); on its stabilized frames the block is
+    the inverse of stabilization_warp and the displacement is undone per pixel (mesh_unwarp_batch, crop_and_pad only).
+    Bilinear, no motion blur, no crop framing; meta["motion_apply"]["mesh"] reports the direction and the largest per-frame
+    count of unconverged pixels."""
+    requested_framing = "crop_and_pad" if framing_mode == "pad" else framing_mode
+    mesh_replay = None
+
     def checked_motion():
-        motion = _resolve_motion_for_context(meta, context)
+        nonlocal mesh_replay
+        motion, derived = _resolve_motion_and_origin(meta, context)
         _validate_context(context, motion)
         _check_interpolation(interpolation)
-        if ("crop_and_pad" if framing_mode == "pad" else framing_mode) not in ("crop_and_pad", "crop", "expand"):
+        if requested_framing not in ("crop_and_pad", "crop", "expand"):
             raise ValueError(f"Unsupported framing_mode {framing_mode!r}; expected 'crop_and_pad', 'crop', or 'expand'.")
+        if mesh:
+            mesh_replay = _mesh_replay(meta, motion, derived, requested_framing)
         return motion
+
+    if mesh:   # the refusals come before any GPU use, resident frames or not
+        _check_mesh_request(requested_framing, interpolation, float(np.clip(motion_blur, 0.0, 1.0)))
 
     # Frames that are already on the device (a Flow -> Motion Apply chain with device-resident sockets): the range pass below is
     # launched BEFORE the meta is parsed and validated (0.4 ms of host work for 256 frames, during which the GPU had nothing to
     # do: tools/chain_timeline.py).  Host frames: validation first -- a bad meta must not cost an upload.
     resident = context.batch is not None and getattr(context.batch, "device", None) is not None and context.batch.device.type == "cuda"
-    motion = None if resident else checked_motion()
+    motion = None if (resident and not mesh) else checked_motion()
     ctx = ctx or native.default_context()
     device_frames = context.device_batch(ctx)
     kw = dict(framing_mode=framing_mode, interpolation=interpolation, motion_blur=motion_blur, motion_blur_samples=motion_blur_samples)
@@ -265,7 +350,7 @@ def apply_motion(
             if motion is None:
                 motion = checked_motion()
             frames, masks, result_meta = apply_motion_on_device(ctx, device_frames, 0, motion, meta, padding_rgb,
-                                                                progress_callback=progress_callback, **kw)
+                                                                progress_callback=progress_callback, mesh_replay=mesh_replay, **kw)
         finally:
             # also when the validation or the warp raised (a bad meta, VstabError, a cancel delivered by a progress tick): the
             # maxima pass still reads the frames, and the caller is free to drop them as soon as this frame unwinds
@@ -274,12 +359,12 @@ def apply_motion(
             check_interrupt()
             device_frames = context.device_batch(ctx)
             frames, masks, result_meta = apply_motion_on_device(ctx, device_frames, 0, motion, meta, padding_rgb,
-                                                                progress_callback=None, **kw)
+                                                                progress_callback=None, mesh_replay=mesh_replay, **kw)
     else:
         if motion is None:
             motion = checked_motion()
         frames, masks, result_meta = apply_motion_on_device(ctx, device_frames, 0, motion, meta, padding_rgb,
-                                                            progress_callback=progress_callback, **kw)
+                                                            progress_callback=progress_callback, mesh_replay=mesh_replay, **kw)
     check_interrupt()
     if keep_on_device:
         return MotionApplyResult(frames, masks.unsqueeze(-1), result_meta)

@@ -1,5 +1,6 @@
-// vstab_warp.hip -- perspective/similarity warp with padding mask, its mesh-displaced form (mesh_warp_kernel), the
-// multi-sample motion blur and the temporal fill.  All of them take their coordinates from ONE definition, warp_pixel, and
+// vstab_warp.hip -- perspective/similarity warp with padding mask, its mesh-displaced forms (mesh_warp_kernel and its
+// inverse, mesh_unwarp_kernel), the multi-sample motion blur and the temporal fill.
+// All of them take their coordinates from ONE definition, warp_pixel, and
 // share one tile shell (TileShell, warp_kernel's body, block_count_add); the scalar pieces that vstab_crop / vstab_dis / vstab_tvl1
 // use too are in vstab_internal.h.  profiles/warp_traffic.json is tied to the hash of these two files: the warp's arithmetic
 // stays in them.
@@ -264,10 +265,13 @@ __device__ __forceinline__ void block_count_add(unsigned (&v)[NC], unsigned* con
     }
 }
 
-// warp_pixel's displacement hook: a functor evaluated at the source position q = (Xn * Wn, Yn * Wn) that gives the
-// offset (cx, cy) taken off it before the roundings.  NoDisplacement is the plain warp: nothing of the hook is compiled.
+// warp_pixel's displacement hook, of two kinds.  OUTPUT == false: a functor evaluated at the source position
+// q = (Xn * Wn, Yn * Wn) that gives the offset (cx, cy) taken off it before the roundings.  OUTPUT == true: `solve`, evaluated
+// on the output pixel in front of the matrix (MeshInverseDisplacement).  NoDisplacement is the plain warp: nothing of the
+// hook is compiled.
 struct NoDisplacement {
     static constexpr bool ACTIVE = false;
+    static constexpr bool OUTPUT = false;
 };
 
 // one axis of the mesh lookup: clamped coordinate -> cell index and fraction (the rule's operation order, include/vstab.h)
@@ -286,6 +290,7 @@ __device__ __forceinline__ void mesh_cell(double q, int size, int verts, int* ce
 // The mesh warp's displacement: bilinear in the frame's mw x mh vertex table (staged in LDS, [mh][mw][2]).
 struct MeshDisplacement {
     static constexpr bool ACTIVE = true;
+    static constexpr bool OUTPUT = false;
     const float* off;
     int sh, sw, mw, mh;
     __device__ __forceinline__ void operator()(double qx, double qy, double& cx, double& cy) const
@@ -299,6 +304,29 @@ struct MeshDisplacement {
         const double ga = 1.0 - fa, gb = 1.0 - fb;
         cx = ((double)c0[0] * ga + (double)c0[2] * fa) * gb + ((double)c1[0] * ga + (double)c1[2] * fa) * fb;
         cy = ((double)c0[1] * ga + (double)c0[3] * fa) * gb + ((double)c1[1] * ga + (double)c1[3] * fa) * fb;
+    }
+};
+
+// The mesh unwarp's displacement: the inverse of q -> q - c(q) at the output pixel, by the bounded fixed-point iteration of
+// vstab_mesh_unwarp_batch's rule (include/vstab.h); `mesh` is the lookup over the OUTPUT canvas.  The trip count differs per
+// lane: a plain loop, the wavefront runs as long as its slowest pixel (3 steps on a smooth field).
+struct MeshInverseDisplacement {
+    static constexpr bool ACTIVE = true;
+    static constexpr bool OUTPUT = true;
+    MeshDisplacement mesh;
+    // -> converged; (ex, ey) = c of the last step taken
+    __device__ __forceinline__ bool solve(int x, int y, double& ex, double& ey) const
+    {
+        const double px = (double)x, py = (double)y;
+        double qx = px, qy = py;
+        bool done = false;
+        for (int k = 0; k < VSTAB_MESH_UNWARP_MAX_STEPS && !done; k++) {
+            mesh(qx, qy, ex, ey);
+            const double nx = px + ex, ny = py + ey;
+            done = __builtin_fabs(nx - qx) <= VSTAB_MESH_UNWARP_TOL && __builtin_fabs(ny - qy) <= VSTAB_MESH_UNWARP_TOL;   // NaN: not met
+            qx = nx; qy = ny;
+        }
+        return done;
     }
 };
 
@@ -325,11 +353,14 @@ struct XformRegs {
 // coordinate arithmetic (f64 row-start terms per OpenCV column block, Q5 rounding or the float32 `exact` chain), shared by
 // warp_kernel, mesh_warp_kernel and temporal_fill_kernel.  `q5(X, Y)` samples at the 1/32-px coordinates, `exact(fsx, fsy)`
 // at the float32 ones; `c` receives the nearest-neighbour coverage (WITH_MASK only).  `disp` (see NoDisplacement) moves
-// the source position: s = q - disp(q), applied to the unrounded value in front of each of the three roundings.
+// the source position: s = q - disp(q), applied to the unrounded value in front of each of the three roundings.  A `disp` of
+// the OUTPUT kind moves the output pixel by e = disp.solve(x, y) in front of the matrix instead: m * e is added to the
+// unrounded terms Xn, Yn, W (and, float32-rounded, to the `exact` chain's), and *unconverged counts the pixels whose solve
+// hit its step limit.  e == 0 adds nothing at all (not even a signed zero): the plain warp's bits.
 template <int INTERP, int SUBPIX, bool WITH_MASK, class SampleQ5, class SampleExact, class Disp>
 __device__ __forceinline__ Px warp_pixel(const WarpXform* __restrict__ xf, const XformRegs<INTERP, SUBPIX>& r, int sh, int sw,
                                          int dw, int bw0, int bw0_pow2, int x, int y, double dy, SampleQ5&& q5,
-                                         SampleExact&& exact, const Disp& disp, float& c)
+                                         SampleExact&& exact, const Disp& disp, float& c, unsigned* unconverged = nullptr)
 {
     // OpenCV evaluates the row-start terms X0, Y0, W0 once per 64-wide column block (xb) and adds m * (x - xb)
     // per pixel; a thread's pixels lie in up to TILE_PX different blocks, so the terms are formed per pixel.
@@ -353,31 +384,52 @@ __device__ __forceinline__ Px warp_pixel(const WarpXform* __restrict__ xf, const
             c = ((unsigned)nx < (unsigned)sw && (unsigned)ny < (unsigned)sh) ? 1.f : 0.f;
         }
     } else {
+        // OUTPUT kind: the displaced terms (Xd, Yd) and what m * e adds to W and to the float32 chain
+        double Xd = Xn, Yd = Yn, dX = 0.0, dY = 0.0, dW = 0.0;
+        bool moved = false;
+        if constexpr (Disp::OUTPUT) {
+            double ex, ey;
+            if (!disp.solve(x, y, ex, ey)) *unconverged += 1u;
+            moved = !(ex == 0.0 && ey == 0.0);
+            if (moved) {
+                dX = r.m0 * ex + r.m1 * ey; dY = r.m3 * ex + r.m4 * ey; dW = r.m6 * ex + r.m7 * ey;
+                Xd = Xn + dX; Yd = Yn + dY;
+            }
+        }
         double Wq, Wn;
         if (r.affine) { Wq = xf->wq; Wn = xf->wn; }
         else {
             // one fp64 division serves both: 32/W == 32 * (1/W) bit for bit (scaling a correctly rounded
             // quotient by a power of two is exact)
-            const double W = W0 + r.m6 * dx1;
+            double W = W0 + r.m6 * dx1;
+            if constexpr (Disp::OUTPUT) { if (moved) W = W + dW; }
             Wn = (W != 0.0) ? 1.0 / W : 0.0;
             Wq = 32.0 * Wn;
         }
         double cx = 0.0, cy = 0.0;
-        if constexpr (Disp::ACTIVE) disp(Xn * Wn, Yn * Wn, cx, cy);
+        if constexpr (Disp::ACTIVE && !Disp::OUTPUT) disp(Xn * Wn, Yn * Wn, cx, cy);
         if (XformRegs<INTERP, SUBPIX>::EXACT) {
-            const float w = x * r.mf[6] + y * r.mf[7] + r.mf[8];
-            float fsx = (x * r.mf[0] + y * r.mf[1] + r.mf[2]) / w;
-            float fsy = (x * r.mf[3] + y * r.mf[4] + r.mf[5]) / w;
-            if constexpr (Disp::ACTIVE) { fsx = (float)((double)fsx - cx); fsy = (float)((double)fsy - cy); }
+            float fsx, fsy;
+            if constexpr (Disp::OUTPUT) {
+                float w = x * r.mf[6] + y * r.mf[7] + r.mf[8];
+                float numx = x * r.mf[0] + y * r.mf[1] + r.mf[2], numy = x * r.mf[3] + y * r.mf[4] + r.mf[5];
+                if (moved) { numx = numx + (float)dX; numy = numy + (float)dY; w = w + (float)dW; }
+                fsx = numx / w; fsy = numy / w;
+            } else {
+                const float w = x * r.mf[6] + y * r.mf[7] + r.mf[8];
+                fsx = (x * r.mf[0] + y * r.mf[1] + r.mf[2]) / w;
+                fsy = (x * r.mf[3] + y * r.mf[4] + r.mf[5]) / w;
+                if constexpr (Disp::ACTIVE) { fsx = (float)((double)fsx - cx); fsy = (float)((double)fsy - cy); }
+            }
             v = exact(fsx, fsy);
         } else {
-            double Xq = Xn * Wq, Yq = Yn * Wq;
-            if constexpr (Disp::ACTIVE) { Xq = Xq - 32.0 * cx; Yq = Yq - 32.0 * cy; }
+            double Xq = Xd * Wq, Yq = Yd * Wq;
+            if constexpr (Disp::ACTIVE && !Disp::OUTPUT) { Xq = Xq - 32.0 * cx; Yq = Yq - 32.0 * cy; }
             v = q5(clamp_round_i32(Xq), clamp_round_i32(Yq));
         }
         if (WITH_MASK) {
-            double qx = Xn * Wn, qy = Yn * Wn;
-            if constexpr (Disp::ACTIVE) { qx = qx - cx; qy = qy - cy; }
+            double qx = Xd * Wn, qy = Yd * Wn;
+            if constexpr (Disp::ACTIVE && !Disp::OUTPUT) { qx = qx - cx; qy = qy - cy; }
             c = vstab_nn_covered(qx, qy, sh, sw) ? 1.f : 0.f;
         }
     }
@@ -390,22 +442,37 @@ struct MeshWarpArgs : WarpArgs {
     int mw, mh;
 };
 
+// The mesh unwarp's: the mesh warp's plus the count of pixels whose fixed point hit the step limit.
+struct MeshUnwarpArgs : MeshWarpArgs {
+    unsigned* unconverged;  // [n] or nullptr
+};
+
 // The displacement a kernel's arguments ask for.  Plain warp: none.  Mesh warp: the frame's vertex table (mw * mh * 8 bytes:
 // 1.4 KB by default) is staged in LDS once per workgroup.
 __device__ __forceinline__ NoDisplacement make_displacement(const WarpArgs&, int) { return {}; }
-__device__ __forceinline__ MeshDisplacement make_displacement(const MeshWarpArgs& a, int frame)
+__device__ __forceinline__ const float* stage_vertex_table(const MeshWarpArgs& a, int frame)
 {
     extern __shared__ float s_off[];      // this frame's vertex table [mh][mw][2]
     const int table = a.mw * a.mh * 2;
     const float* __restrict__ O = a.offsets + (size_t)frame * table;
     for (int i = threadIdx.x; i < table; i += 256) s_off[i] = O[i];
     __syncthreads();
-    return MeshDisplacement{s_off, a.sh, a.sw, a.mw, a.mh};
+    return s_off;
+}
+__device__ __forceinline__ MeshDisplacement make_displacement(const MeshWarpArgs& a, int frame)
+{
+    return MeshDisplacement{stage_vertex_table(a, frame), a.sh, a.sw, a.mw, a.mh};
+}
+// (the unwarp's mesh lies over the OUTPUT canvas: the source canvas of the forward mesh warp being undone)
+__device__ __forceinline__ MeshInverseDisplacement make_displacement(const MeshUnwarpArgs& a, int frame)
+{
+    return MeshInverseDisplacement{MeshDisplacement{stage_vertex_table(a, frame), a.dh, a.dw, a.mw, a.mh}};
 }
 
 // One 64 x 8 (TILE_TX = 32) tile of the warp: every pixel through warp_pixel, RGB + mask stored, padded pixels counted.
-// Args = WarpArgs is the plain warp, Args = MeshWarpArgs the mesh warp (the rule is in include/vstab.h): the same body with
-// the displacement its arguments ask for.  The body stays in the kernel: inlined from a device function that receives the
+// Args = WarpArgs is the plain warp, Args = MeshWarpArgs the mesh warp, Args = MeshUnwarpArgs its inverse (the rules are in
+// include/vstab.h): the same body with the displacement its arguments ask for.
+// The body stays in the kernel: inlined from a device function that receives the
 // arguments by reference, the compiler issued the two epilogue stores in another order and the plain warp ran 0.3-1 %
 // slower (profiles/r11_one_warp_arithmetic.md).
 template <int INTERP, int SUBPIX, bool WITH_MASK, int TILE_TX, class Args>
@@ -421,12 +488,14 @@ __global__ __launch_bounds__(256) void warp_kernel(Args a)
     const TileShell<TILE_TX> t(a.tiles_x, a.tiles_y, a.dh, a.dw);
     const int frame = t.frame, x0 = t.x0, y = t.y, npx = t.npx;
     const auto disp = make_displacement(a, frame);
+    using Disp = std::remove_const_t<decltype(disp)>;
     const float* __restrict__ S = a.src + (size_t)frame * a.sh * a.sw * 3;
 
     float acc[TILE_PX][3];
     float cov[TILE_PX];
 #pragma unroll
     for (int p = 0; p < TILE_PX; p++) { acc[p][0] = acc[p][1] = acc[p][2] = 0.f; cov[p] = 0.f; }
+    unsigned unconv = 0;      // mesh unwarp only: this thread's pixels whose fixed point hit the step limit
 
     if (t.active) {
         const double dy = (double)y;
@@ -440,7 +509,7 @@ __global__ __launch_bounds__(256) void warp_kernel(Args a)
             const Px v = warp_pixel<INTERP, SUBPIX, WITH_MASK>(
                 xf, r, a.sh, a.sw, a.dw, a.bw0, a.bw0_pow2, x, y, dy,
                 [&](int X, int Y) { return sample_q5<INTERP>(S, a.sh, a.sw, X, Y, a.b0, a.b1, a.b2, cub_tab); },
-                [&](float fsx, float fsy) { return sample_exact(S, a.sh, a.sw, fsx, fsy, a.b0, a.b1, a.b2); }, disp, c);
+                [&](float fsx, float fsy) { return sample_exact(S, a.sh, a.sw, fsx, fsy, a.b0, a.b1, a.b2); }, disp, c, &unconv);
             acc[p][0] = v.r; acc[p][1] = v.g; acc[p][2] = v.b;
             if (WITH_MASK) cov[p] = c;
         }
@@ -474,11 +543,21 @@ __global__ __launch_bounds__(256) void warp_kernel(Args a)
         }
     }
 
-    if (WITH_MASK && a.pad_count != nullptr) block_count_add<1>(padded, {a.pad_count}, frame);
+    if constexpr (Disp::OUTPUT) {
+        // two counters through one reduction (the conditions are kernel arguments: uniform)
+        if ((WITH_MASK && a.pad_count != nullptr) || a.unconverged != nullptr) {
+            unsigned counts[2] = {padded[0], unconv};
+            block_count_add<2>(counts, {WITH_MASK ? a.pad_count : nullptr, a.unconverged}, frame);
+        }
+    } else {
+        if (WITH_MASK && a.pad_count != nullptr) block_count_add<1>(padded, {a.pad_count}, frame);
+    }
 }
 
 template <int SUBPIX, bool WITH_MASK>
 constexpr auto mesh_warp_kernel = warp_kernel<VSTAB_INTERP_BILINEAR, SUBPIX, WITH_MASK, 32, MeshWarpArgs>;
+template <int SUBPIX, bool WITH_MASK>
+constexpr auto mesh_unwarp_kernel = warp_kernel<VSTAB_INTERP_BILINEAR, SUBPIX, WITH_MASK, 32, MeshUnwarpArgs>;
 
 // ---- motion blur: S samples per output pixel (motion_apply.py:137-202) ---------------------------------------------
 //
@@ -1196,36 +1275,63 @@ extern "C" int vstab_warp_blur_batch(vstab_ctx* ctx, const float* src, int n, in
                                       subpix, dst, mask);
 }
 
-extern "C" int vstab_mesh_warp_batch(vstab_ctx* ctx, const float* src, int n, int src_h, int src_w, const float* matrices,
-                                     int out_h, int out_w, const float* border_rgb, int subpix, const float* offsets, int mw, int mh,
-                                     float* dst, float* mask, uint32_t* pad_count)
+namespace {
+// vstab_mesh_warp_batch and vstab_mesh_unwarp_batch: the same checks, staging, grid and LDS; the kernel differs.
+// domain_h x domain_w is the canvas the mesh lies over: the source (warp) or the output (unwarp).
+int mesh_launch(const char* who, const char* kind, bool inverse, vstab_ctx* ctx, const float* src, int n, int src_h, int src_w,
+                const float* matrices, int out_h, int out_w, const float* border_rgb, int subpix, const float* offsets, int mw,
+                int mh, float* dst, float* mask, uint32_t* pad_count, uint32_t* unconverged)
 {
-    const char* who = "vstab_mesh_warp_batch";
     if (int rc = check_common(who, ctx, src, n, src_h, src_w, matrices, out_h, out_w, VSTAB_INTERP_BILINEAR, border_rgb, subpix, dst)) return rc;
     VSTAB_REQUIRE(offsets != nullptr, "%s: NULL pointer argument", who);
-    VSTAB_REQUIRE(src_h >= 2 && src_w >= 2, "%s: bad size (n=%d src=%dx%d out=%dx%d; the source must be at least 2x2)", who, n, src_w, src_h, out_w, out_h);
+    const int domain_h = inverse ? out_h : src_h, domain_w = inverse ? out_w : src_w;
+    VSTAB_REQUIRE(domain_h >= 2 && domain_w >= 2, "%s: bad size (n=%d src=%dx%d out=%dx%d; the %s must be at least 2x2)", who, n, src_w, src_h, out_w, out_h, inverse ? "output" : "source");
     VSTAB_REQUIRE(mw >= 2 && mh >= 2 && mw <= MESH_MAX_VERTS && mh <= MESH_MAX_VERTS, "%s: %dx%d vertices outside 2..%d", who, mw, mh, MESH_MAX_VERTS);
     VSTAB_HIP(hipSetDevice(ctx->device));
     const WarpXform* xf = nullptr;
     if (vstab_stage_xforms(ctx, matrices, (size_t)n, &xf)) return 1;
-    MeshWarpArgs a{};
+    MeshUnwarpArgs a{};
     fill_geometry(a, src, xf, n, src_h, src_w, out_h, out_w, border_rgb, dst, mask, pad_count);
-    a.offsets = offsets; a.mw = mw; a.mh = mh;
+    a.offsets = offsets; a.mw = mw; a.mh = mh; a.unconverged = unconverged;
     unsigned blocks = 0;
     if (int rc = tile_grid(who, n, out_h, out_w, 32, 256, &a.tiles_x, &a.tiles_y, &blocks)) return rc;
     if (pad_count) VSTAB_HIP(hipMemsetAsync(pad_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
+    if (unconverged) VSTAB_HIP(hipMemsetAsync(unconverged, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
     const size_t lds = (size_t)mw * mh * 2 * sizeof(float);    // <= 33.8 KB
     const dim3 grid(blocks), block(256);
-    KernelTimer timer(ctx, "mesh_warp");
-    if (subpix == VSTAB_SUBPIX_EXACT) {
-        if (mask) hipLaunchKernelGGL((mesh_warp_kernel<VSTAB_SUBPIX_EXACT, true>), grid, block, lds, ctx->stream, a);
-        else hipLaunchKernelGGL((mesh_warp_kernel<VSTAB_SUBPIX_EXACT, false>), grid, block, lds, ctx->stream, a);
-    } else {
-        if (mask) hipLaunchKernelGGL((mesh_warp_kernel<VSTAB_SUBPIX_Q5, true>), grid, block, lds, ctx->stream, a);
-        else hipLaunchKernelGGL((mesh_warp_kernel<VSTAB_SUBPIX_Q5, false>), grid, block, lds, ctx->stream, a);
-    }
+    KernelTimer timer(ctx, kind);
+#define LAUNCH_MESH(KERNEL, ARGS)                                                                                          \
+    do {                                                                                                                   \
+        if (subpix == VSTAB_SUBPIX_EXACT) {                                                                                \
+            if (mask) hipLaunchKernelGGL((KERNEL<VSTAB_SUBPIX_EXACT, true>), grid, block, lds, ctx->stream, ARGS);         \
+            else hipLaunchKernelGGL((KERNEL<VSTAB_SUBPIX_EXACT, false>), grid, block, lds, ctx->stream, ARGS);             \
+        } else {                                                                                                           \
+            if (mask) hipLaunchKernelGGL((KERNEL<VSTAB_SUBPIX_Q5, true>), grid, block, lds, ctx->stream, ARGS);            \
+            else hipLaunchKernelGGL((KERNEL<VSTAB_SUBPIX_Q5, false>), grid, block, lds, ctx->stream, ARGS);                \
+        }                                                                                                                  \
+    } while (0)
+    if (inverse) LAUNCH_MESH(mesh_unwarp_kernel, a);
+    else LAUNCH_MESH(mesh_warp_kernel, static_cast<const MeshWarpArgs&>(a));
+#undef LAUNCH_MESH
     VSTAB_HIP(hipGetLastError());
     return 0;
+}
+}  // namespace
+
+extern "C" int vstab_mesh_warp_batch(vstab_ctx* ctx, const float* src, int n, int src_h, int src_w, const float* matrices,
+                                     int out_h, int out_w, const float* border_rgb, int subpix, const float* offsets, int mw, int mh,
+                                     float* dst, float* mask, uint32_t* pad_count)
+{
+    return mesh_launch("vstab_mesh_warp_batch", "mesh_warp", false, ctx, src, n, src_h, src_w, matrices, out_h, out_w, border_rgb,
+                       subpix, offsets, mw, mh, dst, mask, pad_count, nullptr);
+}
+
+extern "C" int vstab_mesh_unwarp_batch(vstab_ctx* ctx, const float* src, int n, int src_h, int src_w, const float* matrices,
+                                       int out_h, int out_w, const float* border_rgb, int subpix, const float* offsets, int mw, int mh,
+                                       float* dst, float* mask, uint32_t* pad_count, uint32_t* unconverged)
+{
+    return mesh_launch("vstab_mesh_unwarp_batch", "mesh_unwarp", true, ctx, src, n, src_h, src_w, matrices, out_h, out_w, border_rgb,
+                       subpix, offsets, mw, mh, dst, mask, pad_count, unconverged);
 }
 
 // ---- temporal fill: padding pixels taken from neighbouring frames ----------------------------------------------------

@@ -722,6 +722,7 @@ def _stabilize_frames(
     cut_threshold=None,
     mesh_warp=None,
     mesh_max_shift=None,
+    mesh_motion: bool = False,
 ) -> hm.StabilizationResult:
     """Positional signature of the reference (flow.py:213-223); keyword-only extras select the GPU
     context, keep outputs resident in HBM (multi-GPU sharding lives in distributed.py) or switch the
@@ -744,9 +745,14 @@ def _stabilize_frames(
     per-vertex correction, clamped to mesh_max_shift full-resolution px per axis (None: 1/64 of the width).  For the DIS and
     TV-L1 estimators under crop_and_pad / expand framing, without temporal_fill; meta["mesh_warp"] reports residuals and
     corrections, motion_meta keeps describing the global part.  None: the reference's behaviour and meta.  Bypass paths
-    ignore it."""
+    ignore it.
+    mesh_motion (with mesh_warp only, False by default): True adds the per-vertex offsets themselves as
+    meta["mesh_warp"]["motion"] (mesh_warp.motion_block), which is what Motion Apply's mesh=True replays or undoes.  False:
+    the meta without it, byte for byte."""
     scene = scene_cuts_mod.check_request(scene_cuts, cut_threshold)
     mesh = mesh_warp_mod.check_request(mesh_warp, mesh_max_shift)
+    if mesh_motion and mesh is None:
+        raise ValueError("mesh_motion=True needs mesh_warp: without a mesh warp there are no per-vertex offsets to record.")
     if estimator not in _META_SOURCE:
         raise ValueError(f"Unknown estimator {estimator!r}; expected 'flow' or 'classic'.")
     temporal_fill = int(temporal_fill)
@@ -873,6 +879,8 @@ def _stabilize_frames(
         dst, mask, counts = ctx.mesh_warp_batch(
             device_frames, plan.final_matrices, plan.output_size, offsets, border=hm.border_value(padding_rgb),
             want_mask=True, want_count=True)
+        if mesh_motion:
+            mesh_block["motion"] = mesh_warp_mod.motion_block(offsets, size)
     else:
         dst, mask, counts = ctx.warp_batch(
             device_frames, plan.final_matrices, plan.output_size, interp="bilinear",

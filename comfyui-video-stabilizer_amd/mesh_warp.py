@@ -9,8 +9,13 @@ a GPU.
 
 A vertex path is treated exactly as the global parameters are: P_0 = 0, P_{i+1} = P_i + r_i, sent through the same
 trajectory routine with the plan's own smooth / fps / strength / camera_lock, so local and global smoothing agree by
-construction.  Out of scope: bicubic and motion-blur warps, Motion Apply / Inverse (motion_meta carries the global part
-only), the device plan, the sharded path, per-vertex adaptive smoothing.
+construction.
+
+The round trip: `motion_block` puts the per-vertex offsets of a run into meta["mesh_warp"]["motion"] (Flow's
+`mesh_motion=True`), `parse_motion_block` reads and checks them, and Motion Apply's `mesh=True` replays them -- forward
+through `mesh_warp_batch`, or restoring through `native.Context.mesh_unwarp_batch`, the per-pixel inverse of the
+displacement (include/vstab.h states that rule too).  Out of scope of the round trip: bicubic interpolation, motion blur,
+`crop` framing and the sharded path; of the mesh warp as a whole also the device plan and per-vertex adaptive smoothing.
 """
 
 from __future__ import annotations
@@ -25,6 +30,8 @@ CELLS_MIN, CELLS_MAX = 2, 64
 # max_shift default: 1/64 of the frame's width, full-resolution px (30 px at 1920).  Tried on synthetic material only --
 # procedural texture under a smooth differential shake, no footage -- which is why it is a parameter of every entry point.
 DEFAULT_MAX_SHIFT_FRACTION = 1.0 / 64.0
+MOTION_VERSION = 1               # meta["mesh_warp"]["motion"]["version"]
+VERTS_MIN, VERTS_MAX = 2, 65     # vertices per axis (native.MESH_MAX_VERTS)
 
 _ESTIMATOR_LIMITS = {
     "classic": "the Classic estimator tracks sparse corners: it has no dense grid of flow samples to take the residual from.",
@@ -126,3 +133,71 @@ def meta_block(request: Request, max_shift: float, residual, count, offsets, min
             "residual_px_mean": float(res.mean()), "residual_px_max": float(res.max()),
             "correction_px_mean": float(off.mean()), "correction_px_max": float(off.max()),
             "vertices_without_samples": int((np.asarray(count) < int(min_samples)).sum())}
+
+
+# ---- the round trip: the offsets in the meta -----------------------------------------------------------------------------
+@dataclass
+class Motion:
+    """A parsed meta["mesh_warp"]["motion"] block."""
+
+    domain_size: Tuple[int, int]    # (w, h) of the canvas the mesh lies over: the source frames of the mesh-warped run
+    vertices: Tuple[int, int]       # (mw, mh)
+    offsets: np.ndarray             # f32 [N,mh,mw,2], px of the domain
+
+
+def motion_block(offsets, domain_size) -> Dict[str, Any]:
+    """meta["mesh_warp"]["motion"]: the warp's per-frame vertex offsets, f32 [N,mh,mw,2] in px of domain_size = (w, h), as JSON
+    numbers.  A float32 widened to a Python float survives json.dumps / loads exactly (repr round-trips a double)."""
+    off = np.asarray(offsets, dtype=np.float32)
+    if off.ndim != 4 or off.shape[3] != 2:
+        raise ValueError(f"mesh motion: offsets {off.shape} are not [N,mh,mw,2]")
+    n, mh, mw, _ = off.shape
+    return {"version": MOTION_VERSION, "domain_size": [int(domain_size[0]), int(domain_size[1])], "vertices": [int(mw), int(mh)],
+            "frame_count": int(n), "offsets": off.astype(np.float64).tolist()}
+
+
+def _int_pair(block, key) -> Tuple[int, int]:
+    raw = block.get(key)
+    ok = (isinstance(raw, (list, tuple)) and len(raw) == 2
+          and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in raw))
+    if not ok:
+        raise ValueError(f"mesh_warp.motion.{key} must be a pair of integers, got {raw!r}.")
+    return int(raw[0]), int(raw[1])
+
+
+def parse_motion_block(meta, frame_count: Optional[int] = None, domain_size: Optional[Tuple[int, int]] = None) -> Motion:
+    """meta["mesh_warp"]["motion"] -> Motion, or a ValueError that names the key or shape that is wrong.  frame_count /
+    domain_size: what the motion the caller resolved expects (None: not checked)."""
+    mesh = meta.get("mesh_warp") if isinstance(meta, dict) else None
+    block = mesh.get("motion") if isinstance(mesh, dict) else None
+    if not isinstance(block, dict):
+        raise ValueError("meta has no mesh_warp.motion block: run Flow with mesh_warp and mesh_motion=True "
+                         "(the Video Stabilizer Flow (Mesh Motion) node) to record the per-vertex offsets.")
+    if block.get("version") != MOTION_VERSION:
+        raise ValueError(f"mesh_warp.motion.version must be {MOTION_VERSION}, got {block.get('version')!r}.")
+    domain = _int_pair(block, "domain_size")
+    if domain[0] < 2 or domain[1] < 2:
+        raise ValueError(f"mesh_warp.motion.domain_size {list(domain)} must be at least 2x2.")
+    mw, mh = _int_pair(block, "vertices")
+    if not (VERTS_MIN <= mw <= VERTS_MAX and VERTS_MIN <= mh <= VERTS_MAX):
+        raise ValueError(f"mesh_warp.motion.vertices {[mw, mh]} outside {VERTS_MIN}..{VERTS_MAX} per axis.")
+    count = block.get("frame_count")
+    if not isinstance(count, (int, np.integer)) or isinstance(count, bool) or count < 0:
+        raise ValueError(f"mesh_warp.motion.frame_count must be a non-negative integer, got {count!r}.")
+    try:
+        wide = np.asarray(block.get("offsets"), dtype=np.float64)
+    except (TypeError, ValueError) as exc:
+        raise ValueError("mesh_warp.motion.offsets must be a [frame_count][mh][mw][2] list of numbers.") from exc
+    if wide.shape != (int(count), mh, mw, 2):
+        raise ValueError(f"mesh_warp.motion.offsets has shape {list(wide.shape)}, expected {[int(count), mh, mw, 2]} "
+                         "([frame_count][mh][mw][2]).")
+    with np.errstate(over="ignore"):
+        off = wide.astype(np.float32)
+    if not np.isfinite(off).all():
+        raise ValueError("mesh_warp.motion.offsets must contain finite float32 numbers.")
+    if frame_count is not None and int(count) != int(frame_count):
+        raise ValueError(f"mesh_warp.motion.frame_count is {int(count)}, the motion describes {int(frame_count)} frame(s).")
+    if domain_size is not None and tuple(domain) != (int(domain_size[0]), int(domain_size[1])):
+        raise ValueError(f"mesh_warp.motion.domain_size {list(domain)} does not match the motion's canvas "
+                         f"{[int(domain_size[0]), int(domain_size[1])]}.")
+    return Motion(domain, (mw, mh), np.ascontiguousarray(off))

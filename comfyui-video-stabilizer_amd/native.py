@@ -180,6 +180,9 @@ _SIGNATURES = {
     "vstab_mesh_warp_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                   C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vstab_mesh_unwarp_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                  C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vstab_fit_records_device": (C.c_void_p, [C.c_void_p]),
     "vstab_sample_fit_batch_end": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "vstab_flow_plan_device": (
@@ -744,20 +747,24 @@ class Context:
             "vstab_mesh_residual_batch")
         return residual, count
 
+    def _mesh_offsets(self, who, offsets, n):
+        """offsets f32 [n,mh,mw,2] (host or device) -> (contiguous device tensor, mw, mh)."""
+        torch = self.torch
+        if not isinstance(offsets, torch.Tensor):
+            offsets = torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.float32))
+        if offsets.dim() != 4 or offsets.shape[0] != n or offsets.shape[3] != 2 or offsets.dtype != torch.float32:
+            raise ValueError(f"{who}: offsets {tuple(offsets.shape)} {offsets.dtype} are not float32 [{n},mh,mw,2]")
+        mw, mh = self._check_mesh(who, offsets.shape[2], offsets.shape[1])
+        return offsets.to(self.device).contiguous(), mw, mh
+
     def mesh_warp_batch(self, frames, matrices, out_size, offsets, border=(0.0, 0.0, 0.0), subpix=None, want_mask=True,
                         want_count=False):
         """warp_batch (bilinear) with a per-vertex displacement of the source frame (vstab_mesh_warp_batch; the rule is in
         include/vstab.h).  offsets f32 [N,mh,mw,2] in full-resolution px (host or device) ->
         (dst [N,h,w,3], mask [N,h,w] | None, counts [N] | None).  All-zero offsets give warp_batch's bits."""
-        torch = self.torch
         src, (n, sh, sw), (out_h, out_w), b, dst, mask, counts = self._warp_io(
             "mesh_warp_batch", frames, out_size, border, want_mask, want_count)
-        if not isinstance(offsets, torch.Tensor):
-            offsets = torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.float32))
-        if offsets.dim() != 4 or offsets.shape[0] != n or offsets.shape[3] != 2 or offsets.dtype != torch.float32:
-            raise ValueError(f"mesh_warp_batch: offsets {tuple(offsets.shape)} {offsets.dtype} are not float32 [{n},mh,mw,2]")
-        mw, mh = self._check_mesh("mesh_warp_batch", offsets.shape[2], offsets.shape[1])
-        offsets = offsets.to(self.device).contiguous()
+        offsets, mw, mh = self._mesh_offsets("mesh_warp_batch", offsets, n)
         m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(n, 9)
         self.use_torch_stream()
         _check(self.lib.vstab_mesh_warp_batch(
@@ -765,6 +772,26 @@ class Context:
             _dev_ptr(offsets), mw, mh, _dev_ptr(dst), _dev_ptr(mask) if mask is not None else None,
             _dev_ptr(counts) if counts is not None else None), "vstab_mesh_warp_batch")
         return dst, mask, counts
+
+    def mesh_unwarp_batch(self, frames, matrices, out_size, offsets, border=(0.0, 0.0, 0.0), subpix=None, want_mask=True,
+                          want_count=False, want_unconverged=False):
+        """The inverse of mesh_warp_batch's displacement (vstab_mesh_unwarp_batch; the rule is in include/vstab.h): warp_batch
+        (bilinear) whose output pixel is moved by the inverse of the mesh displacement in front of the matrix.  offsets f32
+        [N,mh,mw,2] in px of the OUTPUT canvas (host or device) -> (dst [N,h,w,3], mask [N,h,w] | None, counts [N] | None,
+        unconverged [N] i32 | None: pixels per frame whose fixed point hit the step limit).  All-zero offsets give
+        warp_batch's bits."""
+        src, (n, sh, sw), (out_h, out_w), b, dst, mask, counts = self._warp_io(
+            "mesh_unwarp_batch", frames, out_size, border, want_mask, want_count)
+        offsets, mw, mh = self._mesh_offsets("mesh_unwarp_batch", offsets, n)
+        unconverged = self.torch.empty((n,), dtype=self.torch.int32, device=self.device) if want_unconverged else None
+        m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(n, 9)
+        self.use_torch_stream()
+        _check(self.lib.vstab_mesh_unwarp_batch(
+            self.handle, _dev_ptr(src), n, sh, sw, m.ctypes.data, out_h, out_w, b.ctypes.data, SUBPIX[subpix or DEFAULT_SUBPIX],
+            _dev_ptr(offsets), mw, mh, _dev_ptr(dst), _dev_ptr(mask) if mask is not None else None,
+            _dev_ptr(counts) if counts is not None else None,
+            _dev_ptr(unconverged) if unconverged is not None else None), "vstab_mesh_unwarp_batch")
+        return dst, mask, counts, unconverged
 
     def _fit_inputs(self, grid_flow, blocked):
         if grid_flow.device != self.device:

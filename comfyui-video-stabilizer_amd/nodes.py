@@ -540,6 +540,76 @@ class VideoStabilizerFlowMesh(io.ComfyNode):
         return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
 
 
+class VideoStabilizerFlowMeshMotion(io.ComfyNode):
+    """The Flow (Mesh) node that also records its per-vertex offsets in the meta (mesh_motion=True), so that Motion Apply
+    (Mesh) can apply the same warp to a companion clip or undo it.  Not one of the reference's nodes: it is listed by an
+    extension but kept out of NODE_CLASSES."""
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        base = VideoStabilizerFlowMesh.define_schema()
+        schema = io.Schema(
+            node_id="video_stabilizer_flow_mesh_motion",
+            display_name="Video Stabilizer Flow (Mesh Motion)",
+            category="Video/Stabilization",
+            description=("Video Stabilizer Flow (Mesh) whose meta also carries the mesh's per-vertex offsets, which Video "
+                         "Stabilizer Motion Apply (Mesh) needs to repeat or undo the warp."),
+        )
+        schema.inputs = list(base.inputs)
+        schema.outputs = _estimator_outputs()
+        return schema
+
+    @classmethod
+    def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
+                strength: float, smooth: float, keep_fov: float, padding_color: str, mesh_cols: int, mesh_rows: int,
+                max_shift: float) -> io.NodeOutput:
+        context = hm._normalize_video_input(frames)
+        result = _stabilize_frames(
+            context, framing_mode, transform_mode, camera_lock, strength, smooth, keep_fov,
+            hm._parse_padding_color(padding_color), frame_rate, keep_on_device=True, estimator="flow",
+            mesh_warp=(int(mesh_cols), int(mesh_rows)), mesh_max_shift=float(max_shift) if max_shift else None,
+            mesh_motion=True,
+        )
+        return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
+
+
+class VideoStabilizerMotionApplyMesh(io.ComfyNode):
+    """Motion Apply for a mesh-warped run (apply_motion's mesh=True): on the run's source frames (or a companion clip of
+    their size) it applies the recorded matrices and mesh again, on its stabilized frames it restores the original camera
+    motion through the mesh warp's per-pixel inverse.  Bilinear, no motion blur.  Not one of the reference's nodes."""
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        schema = io.Schema(
+            node_id="video_stabilizer_motion_apply_mesh",
+            display_name="Video Stabilizer Motion Apply (Mesh)",
+            category="Video/Stabilization",
+            description=("Applies or undoes the motion of a Video Stabilizer Flow (Mesh Motion) run, per-vertex mesh "
+                         "corrections included, and emits a padding mask."),
+        )
+        schema.inputs = [
+            io.Image.Input("frames", display_name="Frames"),
+            JSONType.Input("meta", display_name="Meta"),
+            io.Combo.Input("framing_mode", options=["crop_and_pad", "expand"], default="crop_and_pad",
+                           display_name="Framing Mode"),
+            io.Color.Input("padding_color", default="#7F7F7F", display_name="Padding Color",
+                           tooltip="HEX padding color used where warping exposes empty pixels."),
+        ]
+        schema.outputs = [
+            io.Image.Output("frames", display_name="Frames"),
+            io.Mask.Output("padding_mask", display_name="Padding Mask"),
+            JSONType.Output("meta", display_name="Meta"),
+        ]
+        return schema
+
+    @classmethod
+    def execute(cls, frames: Any, meta: dict, framing_mode: str, padding_color: str) -> io.NodeOutput:
+        context = hm._normalize_video_input(frames)
+        result = apply_motion(context, meta, hm._parse_padding_color(padding_color), framing_mode=framing_mode,
+                              interpolation="bilinear", keep_on_device=True, mesh=True)
+        return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
+
+
 NODE_CLASSES = [VideoStabilizerClassic, VideoStabilizerFlow, VideoStabilizerMotionApply, VideoStabilizerShakeGenerator,
                 VideoStabilizerShakeGeneratorManual, VideoStabilizerInverse]
 
@@ -595,3 +665,11 @@ class VideoStabilizerAmdMeshExtension(VideoStabilizerAmdScenesExtension):
 
     async def get_node_list(self) -> list:
         return await super().get_node_list() + [VideoStabilizerFlowMesh]
+
+
+class VideoStabilizerAmdMeshApplyExtension(VideoStabilizerAmdMeshExtension):
+    """The mesh extension's ten nodes plus the two of the mesh round trip: Video Stabilizer Flow (Mesh Motion) and Video
+    Stabilizer Motion Apply (Mesh).  A class of its own for the reason the three before it are."""
+
+    async def get_node_list(self) -> list:
+        return await super().get_node_list() + [VideoStabilizerFlowMeshMotion, VideoStabilizerMotionApplyMesh]

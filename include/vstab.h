@@ -517,6 +517,44 @@ int vstab_mesh_residual_batch(vstab_ctx* ctx, const float* grid_flow, int pairs,
 int vstab_mesh_warp_batch(vstab_ctx* ctx, const float* src, int n, int src_h, int src_w, const float* matrices,
                           int out_h, int out_w, const float* border_rgb, int subpix, const float* offsets, int mw, int mh,
                           float* dst, float* mask, uint32_t* pad_count);
+/* vstab_mesh_unwarp_batch -- the inverse of vstab_mesh_warp_batch's displacement: vstab_warp_batch (bilinear) whose OUTPUT
+ * pixel is moved by the inverse of the mesh displacement before the frame's matrix is applied.  The mesh lies over the output
+ * canvas, out_w x out_h: the source canvas of the forward mesh warp being undone.  That warp sampled its source at
+ * s = g(q) = q - c(q); restoring needs q = g^-1(p) = p + c(q), which has no closed form on a bilinear vertex table.  The rule,
+ * per output pixel (x, y):
+ *   - fixed point: q_0 = (x, y) as fp64 integers.  Step k = 0, 1, ...: c_k = c(q_k), vstab_mesh_warp_batch's lookup unchanged
+ *     (clamp, cell, fraction, bilinear association) with S = out_w / out_h; q_{k+1} = (x + c_k.x, y + c_k.y).  The step is the
+ *     last one if |q_{k+1}.x - q_k.x| <= VSTAB_MESH_UNWARP_TOL and |q_{k+1}.y - q_k.y| <= VSTAB_MESH_UNWARP_TOL (two fp64
+ *     subtractions; a NaN does not meet the test), or if it is step number VSTAB_MESH_UNWARP_MAX_STEPS.  e = c of the last
+ *     step taken.  A pixel whose last step did not meet the test is UNCONVERGED; it uses e all the same.
+ *     2^-7 is a quarter of the 1/32-px coordinate step: for a field with Lipschitz constant L <= 1/2 the remaining error is
+ *     L/(1-L) * 2^-7 <= 2^-7, below half a Q5 step.  A smooth field stops within 3 steps; independent vertex offsets of
+ *     full amplitude are not a contraction everywhere, which is why the limit and the count exist.
+ *   - Xn, Yn, W are formed exactly as vstab_warp_batch forms them (float32 forward matrix inverted in fp64 to m, OpenCV
+ *     column-block terms).  If e.x == 0 and e.y == 0 (zeros of either sign) NOTHING is added: Xd = Xn, Yd = Yn, Wd = W and the
+ *     float32 chain is the plain warp's, which settles every sign-of-zero corner in favour of the invariant below.
+ *     Otherwise Xd = Xn + (m0*e.x + m1*e.y), Yd = Yn + (m3*e.x + m4*e.y), Wd = W + (m6*e.x + m7*e.y) -- separate IEEE fp64
+ *     operations in this association, nothing fused.  For an affine m (m6 == m7 == 0) the frame's constants Wn / Wq are
+ *     used as they are and Wd is not formed; otherwise Wn = (Wd != 0) ? 1/Wd : 0, Wq = 32 * Wn.
+ *   - Xd, Yd, Wd enter the three roundings in place of Xn, Yn, W:
+ *       1/32-px coordinate:  cvRound(Xd*Wq), cvRound(Yd*Wq)                          (VSTAB_SUBPIX_Q5)
+ *       float32 coordinate:  with the plain warp's float32 numerators nx, ny and denominator w (a moved pixel only):
+ *                            nx += (float)(m0*e.x + m1*e.y), ny += (float)(m3*e.x + m4*e.y), w += (float)(m6*e.x + m7*e.y)
+ *                            (the fp64 sums above, rounded to float32; w also for an affine m), then fsx = nx / w,
+ *                            fsy = ny / w                                             (VSTAB_SUBPIX_EXACT)
+ *       nearest (mask):      cvRound(Xd*Wn), cvRound(Yd*Wn)
+ *     and everything behind them is vstab_warp_batch's.
+ * Invariant: all-zero offsets give dst, mask and pad_count bit-identical to vstab_warp_batch, and unconverged == 0.
+ *   offsets dev [n, mh, mw, 2] f32 (x, y), px of the output canvas;  2 <= mw, mh <= 65;  out_w, out_h >= 2.
+ *   unconverged dev [n] u32 or NULL: unconverged pixels per frame.
+ * The other arguments are vstab_mesh_warp_batch's and are checked as it checks them (same error texts under this function's
+ * name; the 2x2 minimum applies to the output, where the mesh lies).  Same tile, XCD remap and LDS staging of the vertex
+ * table as the forward kernel; the iteration is a bounded per-lane loop.  Timing kind "mesh_unwarp". */
+#define VSTAB_MESH_UNWARP_TOL 0.0078125      /* 2^-7 px */
+#define VSTAB_MESH_UNWARP_MAX_STEPS 8
+int vstab_mesh_unwarp_batch(vstab_ctx* ctx, const float* src, int n, int src_h, int src_w, const float* matrices,
+                            int out_h, int out_w, const float* border_rgb, int subpix, const float* offsets, int mw, int mh,
+                            float* dst, float* mask, uint32_t* pad_count, uint32_t* unconverged);
 
 /* ---- F6 / F9 host helper: element-wise libm over fp64 arrays (host pointers, no GPU involved) ----
  * nodes/stabilizer_utils.py:300-358 (_matrix_to_params / _params_to_matrix) call math.sqrt/atan2/log and
