@@ -14,6 +14,7 @@ import numpy as np
 
 from . import host_math as hm
 from . import mesh_warp as mesh_warp_mod
+from . import spatial_fill as spatial_fill_mod
 from . import native
 from .comfy_compat import check_interrupt
 from .meta_v2 import MotionMeta, motion_meta_from_stabilization_warp, resolve_motion_meta
@@ -301,6 +302,7 @@ def apply_motion(
     ctx: Optional[native.Context] = None,
     keep_on_device: bool = False,
     mesh: bool = False,
+    spatial_fill: bool = False,
 ) -> MotionApplyResult:
     """Signature of the reference's apply_motion (motion_apply.py:297-307) plus GPU-context extras.
     mesh (beyond the reference, False by default): True replays the per-vertex offsets a mesh-warped Flow run recorded
@@ -308,7 +310,16 @@ def apply_motion(
     block is motion_meta and the mesh warp is applied again (crop_and_pad or expand); on its stabilized frames the block is
     the inverse of stabilization_warp and the displacement is undone per pixel (mesh_unwarp_batch, crop_and_pad only).
     Bilinear, no motion blur, no crop framing; meta["motion_apply"]["mesh"] reports the direction and the largest per-frame
-    count of unconverged pixels."""
+    count of unconverged pixels.
+    spatial_fill (beyond the reference, False by default): True fills what the warp left as padding from each frame's own
+    valid pixels (spatial_fill.py; include/vstab.h states the rule) as the last pass, mesh=True in either direction included;
+    the masks are unchanged and meta["motion_apply"]["spatial_fill"] describes the fill.  Not with motion_blur > 0, whose
+    masks are fractions; `crop` framing has no padding: nothing is launched and no block is added."""
+    spatial_fill = spatial_fill_mod.check_request(spatial_fill)
+    if spatial_fill and float(np.clip(motion_blur, 0.0, 1.0)) > 0.0:   # before any GPU use
+        raise ValueError(f"spatial_fill=True is not supported with motion_blur={motion_blur}: the blur's masks are the fraction "
+                         "of samples that missed the frame, so a marked pixel is partly padding colour already, which a 0/1 "
+                         "hole test cannot undo.")
     requested_framing = "crop_and_pad" if framing_mode == "pad" else framing_mode
     mesh_replay = None
 
@@ -365,6 +376,8 @@ def apply_motion(
             motion = checked_motion()
         frames, masks, result_meta = apply_motion_on_device(ctx, device_frames, 0, motion, meta, padding_rgb,
                                                             progress_callback=progress_callback, mesh_replay=mesh_replay, **kw)
+    if spatial_fill and result_meta["motion_apply"]["framing_mode"] != "crop":
+        result_meta["motion_apply"]["spatial_fill"] = spatial_fill_mod.fill_on_device(ctx, frames, masks)
     check_interrupt()
     if keep_on_device:
         return MotionApplyResult(frames, masks.unsqueeze(-1), result_meta)

@@ -157,6 +157,7 @@ int vstab_destroy(vstab_ctx* ctx)
     ctx->d_gray_tmp.release();
     ctx->d_range.release();
     ctx->d_mask_rows.release();
+    ctx->d_sfill.release();
     ctx->d_plan.release();
     ctx->h_plan.release();
     if (ctx->h_peaks) (void)hipHostFree(ctx->h_peaks);

@@ -61,6 +61,7 @@ struct vstab_ctx {
     // DIS / fit workspaces (grow-only)
     ScratchBuf d_dis, d_fit, h_fit, d_gray_tmp, d_range;
     ScratchBuf d_mask_rows;   // estimation mask: the dilated rows between the two kernels of vstab_mask_block_grid
+    ScratchBuf d_sfill;       // spatial fill: the pyramid records of one chunk of frames and their per-frame words (vstab_fill.hip)
     // Device-side failure reports: one host-resident word (coherent, device-mapped).  A kernel ORs a VSTAB_STATUS_*
     // bit into it through d_status; the host reads h_status after any stream synchronisation at no cost.
     volatile int* h_status = nullptr;

@@ -25,6 +25,7 @@ from . import host_math as hm
 from . import mesh_warp as mesh_warp_mod
 from . import native
 from . import scene_cuts as scene_cuts_mod
+from . import spatial_fill as spatial_fill_mod
 from . import temporal_fill as temporal_fill_mod
 from .comfy_compat import ProgressBar, check_interrupt
 from .meta_v2 import applied_motion_meta_from_arrays, applied_motion_meta_from_stabilization_warp
@@ -571,6 +572,15 @@ def _temporal_fill(ctx, device_frames, dst, mask, plan, meta, radius: int) -> No
         ctx, device_frames, dst, mask, plan.final_matrices, np.asarray(em["matrices"], dtype=np.float32), em["confidences"], radius)
 
 
+def _spatial_fill(ctx, dst, mask, plan, meta, enabled: bool) -> None:
+    """Fills what is still padding from each frame's own valid pixels in place (spatial_fill.py), as the very last pass on
+    the outputs, and adds meta["spatial_fill"]; the mask and the other meta keys are unchanged.  `crop` framing has no
+    padding: nothing to do."""
+    if not enabled or plan.framing_mode == "crop":
+        return
+    meta["spatial_fill"] = spatial_fill_mod.fill_on_device(ctx, dst, mask)
+
+
 # ---- estimation mask (beyond the reference; the rule is in include/vstab.h) --------------------------------------------
 MASK_MARGIN_MAX = 64
 _MASK_LIMITS = {
@@ -649,7 +659,7 @@ def _mesh_offsets(ctx, mesh, plan, grid, blocked, working_size, size, segments, 
 
 def _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode, camera_lock,
                                 strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested, pbar, progress_total,
-                                keep_on_device, temporal_fill=0, blocked=None, mask_info=None):
+                                keep_on_device, temporal_fill=0, blocked=None, mask_info=None, spatial_fill=False):
     """F2-F14 with the plan formed on the device (see above).  Returns None when F0 found 0..255 float data: the
     speculative run used the unscaled frames and is discarded; the caller takes the regular path on the rescaled clip."""
     size = (context.width, context.height)
@@ -695,6 +705,7 @@ def _stabilize_with_device_plan(ctx, context, device_frames, working_size, total
     if mask_info is not None:
         meta["estimation_mask"] = estimation_mask_meta(fit_records, *mask_info)
     _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill)   # on the host plan's verified matrices
+    _spatial_fill(ctx, dst, mask, plan, meta, spatial_fill)
     check_interrupt()
     if keep_on_device:
         return hm.StabilizationResult(dst, mask.unsqueeze(-1), meta, verdict)
@@ -723,6 +734,7 @@ def _stabilize_frames(
     mesh_warp=None,
     mesh_max_shift=None,
     mesh_motion: bool = False,
+    spatial_fill: bool = False,
 ) -> hm.StabilizationResult:
     """Positional signature of the reference (flow.py:213-223); keyword-only extras select the GPU
     context, keep outputs resident in HBM (multi-GPU sharding lives in distributed.py) or switch the
@@ -748,7 +760,13 @@ def _stabilize_frames(
     ignore it.
     mesh_motion (with mesh_warp only, False by default): True adds the per-vertex offsets themselves as
     meta["mesh_warp"]["motion"] (mesh_warp.motion_block), which is what Motion Apply's mesh=True replays or undoes.  False:
-    the meta without it, byte for byte."""
+    the meta without it, byte for byte.
+    spatial_fill (beyond the reference, False by default): True fills the pixels that are still padding after the warp (plain
+    or mesh) and after temporal_fill from each frame's own valid pixels by pyramid push-pull (spatial_fill.py; include/vstab.h
+    states the rule), as the very last pass.  `padding_mask` and `padding_fraction_*` keep describing the warp -- the pixels
+    are invented, not seen -- and meta["spatial_fill"] describes the fill.  False: the behaviour and meta without it, byte
+    for byte, and nothing is launched.  `crop` framing has no padding; bypass paths ignore it."""
+    spatial_fill = spatial_fill_mod.check_request(spatial_fill)
     scene = scene_cuts_mod.check_request(scene_cuts, cut_threshold)
     mesh = mesh_warp_mod.check_request(mesh_warp, mesh_max_shift)
     if mesh_motion and mesh is None:
@@ -833,7 +851,7 @@ def _stabilize_frames(
     if scene is None and mesh is None and device_plan_applies(estimator, framing_mode, transform_mode, total_frames):
         done = _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode,
                                            camera_lock, strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested,
-                                           pbar, progress_total, keep_on_device, temporal_fill, blocked, mask_info)
+                                           pbar, progress_total, keep_on_device, temporal_fill, blocked, mask_info, spatial_fill)
         if done is not None:
             return done
         device_frames = context.device_batch(ctx)   # F0 rescaled the clip: everything is redone on the rescaled frames below
@@ -895,6 +913,7 @@ def _stabilize_frames(
     if mesh_block is not None:
         meta["mesh_warp"] = mesh_block
     _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill)
+    _spatial_fill(ctx, dst, mask, plan, meta, spatial_fill)
     check_interrupt()
     verdict = {"used": False, "mismatched_frames": 0}
     if keep_on_device:

@@ -196,6 +196,8 @@ _SIGNATURES = {
     "vstab_temporal_fill_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                   C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vstab_spatial_fill_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vstab_gftt_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p,
                   C.c_void_p]),
@@ -967,6 +969,34 @@ class Context:
             _dev_ptr(fill_count) if fill_count is not None else None,
             _dev_ptr(pad_count) if pad_count is not None else None), "vstab_temporal_fill_batch")
         return filled_from, fill_count, pad_count
+
+    # ------------------------------------------------------------------ spatial fill
+    def spatial_fill_batch(self, dst, mask, chunk_frames=0, want_counts=True):
+        """Fills the hole pixels (!(mask <= 0.5)) of dst [n,h,w,3] from the frame's own valid pixels by pyramid push-pull, in
+        place; mask [n,h,w] (or [n,h,w,1]) is read only.  Both f32, device, contiguous (see include/vstab.h for the rule).
+        chunk_frames: frames per pass over the workspace, 0 = automatic; the result does not depend on it.
+        -> (hole_count i32 [n] | None, fill_count i32 [n] | None), device tensors."""
+        torch = self.torch
+        for name, t in (("dst", dst), ("mask", mask)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()):
+                raise VstabError(f"spatial_fill_batch: {name} must be a contiguous float32 tensor on {self.device}")
+        if dst.dim() != 4 or dst.shape[3] != 3 or mask.dim() not in (3, 4) or mask.numel() * 3 != dst.numel() \
+                or tuple(mask.shape[:3]) != tuple(dst.shape[:3]):
+            raise VstabError(f"spatial_fill_batch: dst {tuple(dst.shape)} / mask {tuple(mask.shape)} do not match")
+        chunk_frames = int(chunk_frames)
+        if chunk_frames < 0:
+            raise VstabError(f"spatial_fill_batch: chunk_frames={chunk_frames} is negative")
+        n, h, w = int(dst.shape[0]), int(dst.shape[1]), int(dst.shape[2])
+        hole_count = torch.empty((n,), dtype=torch.int32, device=self.device) if want_counts else None
+        fill_count = torch.empty((n,), dtype=torch.int32, device=self.device) if want_counts else None
+        if n == 0 or h == 0 or w == 0:
+            return hole_count, fill_count
+        self.use_torch_stream()
+        _check(self.lib.vstab_spatial_fill_batch(
+            self.handle, _dev_ptr(dst), _dev_ptr(mask), n, h, w, chunk_frames,
+            _dev_ptr(hole_count) if hole_count is not None else None,
+            _dev_ptr(fill_count) if fill_count is not None else None), "vstab_spatial_fill_batch")
+        return hole_count, fill_count
 
     # ------------------------------------------------------------------ Classic estimator (sparse features + LK)
     def gftt_batch(self, gray, max_corners=400, quality=0.01, min_distance=7.0, block_size=21):

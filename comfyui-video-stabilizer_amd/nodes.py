@@ -610,6 +610,67 @@ class VideoStabilizerMotionApplyMesh(io.ComfyNode):
         return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
 
 
+class VideoStabilizerPaddingFill(io.ComfyNode):
+    """Fills the padded pixels of any frames / padding mask pair from each frame's own valid pixels by pyramid push-pull
+    (spatial_fill.py): the outputs of any node of this package, or of the unchanged reference nodes.  The mask is not an
+    output: it stays what it was, for a downstream in-painter.  Not one of the reference's nodes: it is listed by an
+    extension but kept out of NODE_CLASSES."""
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        schema = io.Schema(
+            node_id="video_stabilizer_padding_fill",
+            display_name="Video Stabilizer Padding Fill",
+            category="Video/Stabilization",
+            description=("Fills the padding a stabilizer left with a smooth continuation of each frame's own content "
+                         "(push-pull), a far better start for an in-painter than a flat colour; the padding mask still "
+                         "marks the invented pixels."),
+        )
+        schema.inputs = [
+            io.Image.Input("frames", display_name="Frames", tooltip="Stabilized frames with padding."),
+            io.Mask.Input("padding_mask", display_name="Padding Mask", tooltip="[N,H,W], or [1,H,W] for every frame."),
+        ]
+        schema.outputs = [
+            io.Image.Output("frames", display_name="Frames"),
+            io.String.Output("meta", display_name="Meta"),
+        ]
+        return schema
+
+    @classmethod
+    def execute(cls, frames: Any, padding_mask: Any) -> io.NodeOutput:
+        import json
+
+        from . import native, spatial_fill
+
+        context = hm._normalize_video_input(frames)
+        n, h, w = len(context.frames), context.height, context.width
+        # every check comes before any GPU work
+        if n == 0:
+            raise ValueError("padding fill: socket 'frames' holds no frame")
+        if not (hasattr(padding_mask, "dtype") and hasattr(padding_mask, "shape")):
+            raise ValueError(f"padding fill: socket 'padding_mask' must be a floating-point MASK tensor, got {type(padding_mask).__name__}")
+        if "float" not in str(padding_mask.dtype):
+            raise ValueError(f"padding fill: socket 'padding_mask' must be a floating-point MASK, got {padding_mask.dtype}")
+        shape = tuple(int(v) for v in padding_mask.shape)
+        if len(shape) == 4 and shape[3] == 1:
+            shape = shape[:3]
+        if len(shape) != 3 or shape[1:] != (h, w) or shape[0] not in (1, n):
+            raise ValueError(f"padding fill: socket 'padding_mask' of shape {tuple(padding_mask.shape)} does not match socket "
+                             f"'frames' [{n},{h},{w},3]: expected [{n},{h},{w}] or [1,{h},{w}]")
+        ctx = native.default_context()
+        torch = ctx.torch
+        src = context.device_batch(ctx)
+        if context.range_pending:   # F0's value-range rule, as every node of the package applies it to its frames
+            if hm.resolve_value_range(context, hm.prefetch_peaks(ctx.frame_range(src)), ctx):
+                src = context.device_batch(ctx)
+        # the fill works in place: on a copy, so the caller's tensor (another node's cached output) stays as it is
+        dst = src.clone()
+        mask = padding_mask if isinstance(padding_mask, torch.Tensor) else torch.from_numpy(np.asarray(padding_mask))
+        mask = mask.to(device=ctx.device, dtype=torch.float32).reshape((shape[0], h, w)).expand(n, h, w).contiguous()
+        block = spatial_fill.fill_on_device(ctx, dst, mask)
+        return io.NodeOutput(_image_out(dst, context), json.dumps({"spatial_fill": block}))
+
+
 NODE_CLASSES = [VideoStabilizerClassic, VideoStabilizerFlow, VideoStabilizerMotionApply, VideoStabilizerShakeGenerator,
                 VideoStabilizerShakeGeneratorManual, VideoStabilizerInverse]
 
@@ -673,3 +734,11 @@ class VideoStabilizerAmdMeshApplyExtension(VideoStabilizerAmdMeshExtension):
 
     async def get_node_list(self) -> list:
         return await super().get_node_list() + [VideoStabilizerFlowMeshMotion, VideoStabilizerMotionApplyMesh]
+
+
+class VideoStabilizerAmdFillExtension(VideoStabilizerAmdMeshApplyExtension):
+    """The mesh round trip extension's twelve nodes plus Video Stabilizer Padding Fill.  A class of its own for the reason
+    the four before it are."""
+
+    async def get_node_list(self) -> list:
+        return await super().get_node_list() + [VideoStabilizerPaddingFill]

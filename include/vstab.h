@@ -556,6 +556,34 @@ int vstab_mesh_unwarp_batch(vstab_ctx* ctx, const float* src, int n, int src_h, 
                             int out_h, int out_w, const float* border_rgb, int subpix, const float* offsets, int mw, int mh,
                             float* dst, float* mask, uint32_t* pad_count, uint32_t* unconverged);
 
+/* ---- spatial fill: push-pull inpainting of the pixels that stay padding (beyond the reference, off by default) ----
+ * What the warp (and temporal fill) leave as padding is filled per frame from the frame's own valid pixels by pyramid
+ * push-pull (Gortler et al., "The Lumigraph", 1996).  The rule -- float32, per frame and per channel, separate IEEE
+ * operations in the association written here, nothing fused:
+ *   - Holes.  A pixel is a hole iff !(mask <= 0.5f): > 0.5 or not finite (the estimation mask's convention).  Level 0 is the
+ *     frame itself with V_0 = !hole.
+ *   - Pull.  Level l+1 is h' = (h_l + 1) >> 1 by w' = (w_l + 1) >> 1.  Cell (Y, X) has the taps t00 = (2Y, 2X),
+ *     t01 = (2Y, 2X+1), t10 = (2Y+1, 2X), t11 = (2Y+1, 2X+1) of level l; a tap outside the level or with V_l == 0 enters as
+ *     +0.0f; n = the number of valid taps.  n == 0: V = 0, C = +0.0f.  Otherwise V = 1 and
+ *     C = ((t00 + t01) + (t10 + t11)) / (float)n.  Levels go on until 1 x 1.
+ *   - Push, from the top level down.  F_top = C_top if V_top.  V_top == 0: the whole frame is hole, it is left untouched
+ *     and fill_count = 0.  Otherwise F_l(y, x) = V_l ? C_l : up(F_{l+1})(y, x), the centre-aligned x2 bilinear upsample:
+ *     along an axis with index i the near coarse index is i >> 1, the far one near - 1 (even i) or near + 1 (odd i),
+ *     clamped to the coarse level; horizontally first r(row) = F[row][x_near] * 0.75f + F[row][x_far] * 0.25f, then
+ *     up = r(y_near) * 0.75f + r(y_far) * 0.25f.  F_0 at the hole pixels is the result.
+ *   - Valid pixels of dst are not stored to.  mask is not written at all: these pixels are invented, not seen, and a
+ *     downstream in-painter still needs to know where they are (temporal fill, whose pixels are real, clears it).
+ * dst   dev [n, h, w, 3] f32, in and out;  mask dev [n, h, w] f32, read only.
+ * chunk_frames  frames per pass over the workspace, 0 = as many as keep it at or below 1 GiB; the result does not depend on it.
+ * hole_count / fill_count  dev [n] u32 or NULL: holes found / pixels written (== hole_count, or 0 for an all-hole frame).
+ * The pyramid lives in the context's grow-only workspace, one float4 {r, g, b, valid} record per cell of levels >= 1 (a
+ * third of a frame's pixels).  Kernels (vstab_fill.hip): one pass over dst and mask forms levels 1..3 in LDS and counts the
+ * holes; one workgroup per frame takes the levels that fit its LDS to 1 x 1 and back; push kernels go down the rest and
+ * store only invalid cells, at level 0 only hole pixels.  Workgroups of a frame without holes (or without a valid pixel)
+ * return on a per-frame flag.  Asynchronous on the context's stream; timing kind "sfill". */
+int vstab_spatial_fill_batch(vstab_ctx* ctx, float* dst, const float* mask, int n, int h, int w, int chunk_frames,
+                             uint32_t* hole_count, uint32_t* fill_count);
+
 /* ---- F6 / F9 host helper: element-wise libm over fp64 arrays (host pointers, no GPU involved) ----
  * nodes/stabilizer_utils.py:300-358 (_matrix_to_params / _params_to_matrix) call math.sqrt/atan2/log and
  * math.exp/cos/sin per frame; this runs the same libm functions over a whole clip in one call.
