@@ -95,9 +95,12 @@ __global__ __launch_bounds__(256) void erode_bbox_kernel(const uint8_t* __restri
     }
 }
 
+// The pixel loops below count in 64 bits: npx may be anything below 2^31 - 1, and an int counter would wrap when the
+// grid's stride (up to 2^21, grid_for) is added to a pixel index within that distance of INT_MAX.
 __global__ __launch_bounds__(256) void common_kernel(const uint8_t* __restrict__ cov, uint8_t* __restrict__ common, int n, int npx)
 {
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < npx; p += gridDim.x * blockDim.x) {
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < npx; q += (long long)gridDim.x * blockDim.x) {
+        const int p = (int)q;
         int all = 1;
         for (int f = 0; f < n; f++) all &= cov[(size_t)f * npx + p];
         common[p] = (uint8_t)all;
@@ -107,7 +110,8 @@ __global__ __launch_bounds__(256) void common_kernel(const uint8_t* __restrict__
 __global__ __launch_bounds__(256) void erode3_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int dh, int dw)
 {
     const int npx = dh * dw;
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < npx; p += gridDim.x * blockDim.x) {
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < npx; q += (long long)gridDim.x * blockDim.x) {
+        const int p = (int)q;
         const int y = p / dw, x = p - y * dw;
         int v = 1;
         for (int ey = -1; ey <= 1; ey++)
@@ -125,7 +129,8 @@ __global__ __launch_bounds__(256) void common_coverage_kernel(const WarpXform* _
                                                               int sw, int dh, int dw, int bw0)
 {
     const int npx = dh * dw;
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < npx; p += gridDim.x * blockDim.x) {
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < npx; q += (long long)gridDim.x * blockDim.x) {
+        const int p = (int)q;
         const int y = p / dw, x = p - y * dw;
         const int xb = (bw0 >= dw) ? 0 : (x / bw0) * bw0;
         const double dxb = (double)xb, dy = (double)y, dx1 = (double)(x - xb);
@@ -187,6 +192,9 @@ extern "C" int vstab_crop_analysis(vstab_ctx* ctx, const float* matrices, int n,
     VSTAB_REQUIRE(matrices && bbox && common, "vstab_crop_analysis: NULL pointer argument");
     VSTAB_REQUIRE(n > 0 && src_h > 0 && src_w > 0 && out_h > 0 && out_w > 0, "vstab_crop_analysis: non-positive size");
     VSTAB_REQUIRE(src_h <= 32767 && src_w <= 32767, "vstab_crop_analysis: source larger than 32767 px");
+    // the pixel index is an int in common_kernel / erode3_kernel ((int)npx), the band kernels count BAND * out_w items in an int
+    VSTAB_REQUIRE((long long)out_h * out_w < 0x7fffffffLL, "vstab_crop_analysis: output too large");
+    VSTAB_REQUIRE((long long)BAND * out_w + 256 <= 0x7fffffffLL, "vstab_crop_analysis: output too wide");
     VSTAB_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const WarpXform* d_xf = nullptr;

@@ -415,6 +415,20 @@ def crop_analysis(matrices, src_size, out_size):
     return bbox, common
 
 
+def coverage_planes(matrices, src_size, out_size):
+    """The per-frame nearest coverage vo_crop_analysis starts from (vo_warp_frame without a source, > 0.5) -> bool [n,oh,ow]."""
+    m = _f32(matrices).reshape(-1, 9)
+    n = m.shape[0]
+    sw, sh = int(src_size[0]), int(src_size[1])
+    ow, oh = int(out_size[0]), int(out_size[1])
+    b = np.zeros(3, np.float32)
+    cov = np.empty((n, oh, ow), np.float32)
+    for f in range(n):
+        lib().vo_warp_frame(None, sh, sw, _ptr(m[f], C.c_float), oh, ow, INTERP["bilinear"], _ptr(b, C.c_float), SUBPIX["q5"],
+                            None, _ptr(cov[f], C.c_float))
+    return cov > 0.5
+
+
 # ---------------------------------------------------------------- Classic estimator (GFTT + pyramidal LK)
 GFTT = dict(max_corners=400, quality=0.01, min_distance=7.0, block=21)   # classic.py:76-83
 LK = dict(win=31, max_level=3, max_count=50, epsilon=0.01)               # classic.py:88-96
