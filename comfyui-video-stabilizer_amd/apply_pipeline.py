@@ -15,6 +15,7 @@ import numpy as np
 from . import host_math as hm
 from . import mesh_warp as mesh_warp_mod
 from . import spatial_fill as spatial_fill_mod
+from . import stability as stability_mod
 from . import native
 from .comfy_compat import check_interrupt
 from .meta_v2 import MotionMeta, motion_meta_from_stabilization_warp, resolve_motion_meta
@@ -303,6 +304,7 @@ def apply_motion(
     keep_on_device: bool = False,
     mesh: bool = False,
     spatial_fill: bool = False,
+    stability_report: bool = False,
 ) -> MotionApplyResult:
     """Signature of the reference's apply_motion (motion_apply.py:297-307) plus GPU-context extras.
     mesh (beyond the reference, False by default): True replays the per-vertex offsets a mesh-warped Flow run recorded
@@ -314,8 +316,16 @@ def apply_motion(
     spatial_fill (beyond the reference, False by default): True fills what the warp left as padding from each frame's own
     valid pixels (spatial_fill.py; include/vstab.h states the rule) as the last pass, mesh=True in either direction included;
     the masks are unchanged and meta["motion_apply"]["spatial_fill"] describes the fill.  Not with motion_blur > 0, whose
-    masks are fractions; `crop` framing has no padding: nothing is launched and no block is added."""
+    masks are fractions; `crop` framing has no padding: nothing is launched and no block is added.
+    stability_report (beyond the reference, False by default): True adds meta["motion_apply"]["stability"], the inter-frame
+    transformation fidelity (stability.py; include/vstab.h states the rule) of the frames as given and of the returned frames
+    under the returned mask (none under `crop` framing), behind the spatial fill, and their difference.  Frames, masks and
+    the rest of the meta are unchanged.  Not with motion_blur > 0, whose masks are fractions."""
     spatial_fill = spatial_fill_mod.check_request(spatial_fill)
+    stability_report = stability_mod.check_request(stability_report)
+    if stability_report and float(np.clip(motion_blur, 0.0, 1.0)) > 0.0:   # before any GPU use
+        raise ValueError(f"stability_report=True is not supported with motion_blur={motion_blur}: the blur's masks are the "
+                         "fraction of samples that missed the frame, and the report's rule takes a pixel as shown or not shown.")
     if spatial_fill and float(np.clip(motion_blur, 0.0, 1.0)) > 0.0:   # before any GPU use
         raise ValueError(f"spatial_fill=True is not supported with motion_blur={motion_blur}: the blur's masks are the fraction "
                          "of samples that missed the frame, so a marked pixel is partly padding colour already, which a 0/1 "
@@ -378,6 +388,9 @@ def apply_motion(
                                                             progress_callback=progress_callback, mesh_replay=mesh_replay, **kw)
     if spatial_fill and result_meta["motion_apply"]["framing_mode"] != "crop":
         result_meta["motion_apply"]["spatial_fill"] = spatial_fill_mod.fill_on_device(ctx, frames, masks)
+    if stability_report:
+        result_meta["motion_apply"]["stability"] = stability_mod.report_on_device(
+            ctx, device_frames, frames, None if result_meta["motion_apply"]["framing_mode"] == "crop" else masks)
     check_interrupt()
     if keep_on_device:
         return MotionApplyResult(frames, masks.unsqueeze(-1), result_meta)

@@ -26,6 +26,7 @@ from . import mesh_warp as mesh_warp_mod
 from . import native
 from . import scene_cuts as scene_cuts_mod
 from . import spatial_fill as spatial_fill_mod
+from . import stability as stability_mod
 from . import temporal_fill as temporal_fill_mod
 from .comfy_compat import ProgressBar, check_interrupt
 from .meta_v2 import applied_motion_meta_from_arrays, applied_motion_meta_from_stabilization_warp
@@ -581,6 +582,16 @@ def _spatial_fill(ctx, dst, mask, plan, meta, enabled: bool) -> None:
     meta["spatial_fill"] = spatial_fill_mod.fill_on_device(ctx, dst, mask)
 
 
+def _stability_report(ctx, device_frames, dst, mask, plan, meta, enabled: bool, segments=None) -> None:
+    """Adds meta["stability"] (stability.py): the ITF of the source frames, without a mask, and of the outputs under their
+    padding mask, measured behind every fill -- spatial fill leaves the mask as it is, so its invented pixels stay out.
+    `crop` framing has no mask.  Pairs across a scene cut are in neither mean.  Reads only; the other meta keys are unchanged."""
+    if not enabled:
+        return
+    cuts = None if segments is None else [s for s, _ in segments[1:]]
+    meta["stability"] = stability_mod.report_on_device(ctx, device_frames, dst, None if plan.framing_mode == "crop" else mask, cuts)
+
+
 # ---- estimation mask (beyond the reference; the rule is in include/vstab.h) --------------------------------------------
 MASK_MARGIN_MAX = 64
 _MASK_LIMITS = {
@@ -659,7 +670,8 @@ def _mesh_offsets(ctx, mesh, plan, grid, blocked, working_size, size, segments, 
 
 def _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode, camera_lock,
                                 strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested, pbar, progress_total,
-                                keep_on_device, temporal_fill=0, blocked=None, mask_info=None, spatial_fill=False):
+                                keep_on_device, temporal_fill=0, blocked=None, mask_info=None, spatial_fill=False,
+                                stability_report=False):
     """F2-F14 with the plan formed on the device (see above).  Returns None when F0 found 0..255 float data: the
     speculative run used the unscaled frames and is discarded; the caller takes the regular path on the rescaled clip."""
     size = (context.width, context.height)
@@ -706,6 +718,7 @@ def _stabilize_with_device_plan(ctx, context, device_frames, working_size, total
         meta["estimation_mask"] = estimation_mask_meta(fit_records, *mask_info)
     _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill)   # on the host plan's verified matrices
     _spatial_fill(ctx, dst, mask, plan, meta, spatial_fill)
+    _stability_report(ctx, device_frames, dst, mask, plan, meta, stability_report)
     check_interrupt()
     if keep_on_device:
         return hm.StabilizationResult(dst, mask.unsqueeze(-1), meta, verdict)
@@ -735,6 +748,7 @@ def _stabilize_frames(
     mesh_max_shift=None,
     mesh_motion: bool = False,
     spatial_fill: bool = False,
+    stability_report: bool = False,
 ) -> hm.StabilizationResult:
     """Positional signature of the reference (flow.py:213-223); keyword-only extras select the GPU
     context, keep outputs resident in HBM (multi-GPU sharding lives in distributed.py) or switch the
@@ -765,8 +779,14 @@ def _stabilize_frames(
     or mesh) and after temporal_fill from each frame's own valid pixels by pyramid push-pull (spatial_fill.py; include/vstab.h
     states the rule), as the very last pass.  `padding_mask` and `padding_fraction_*` keep describing the warp -- the pixels
     are invented, not seen -- and meta["spatial_fill"] describes the fill.  False: the behaviour and meta without it, byte
-    for byte, and nothing is launched.  `crop` framing has no padding; bypass paths ignore it."""
+    for byte, and nothing is launched.  `crop` framing has no padding; bypass paths ignore it.
+    stability_report (beyond the reference, False by default): True adds meta["stability"], the inter-frame transformation
+    fidelity (mean PSNR between consecutive frames over the pixels both show; stability.py, include/vstab.h states the rule)
+    of the source frames and of the returned frames under the returned mask, behind every fill, and their difference
+    gain_db; pairs across a scene cut are left out and counted.  Frames, mask and every other meta key are unchanged.
+    False: the meta without it, byte for byte, and nothing is launched.  Bypass paths ignore it."""
     spatial_fill = spatial_fill_mod.check_request(spatial_fill)
+    stability_report = stability_mod.check_request(stability_report)
     scene = scene_cuts_mod.check_request(scene_cuts, cut_threshold)
     mesh = mesh_warp_mod.check_request(mesh_warp, mesh_max_shift)
     if mesh_motion and mesh is None:
@@ -851,7 +871,8 @@ def _stabilize_frames(
     if scene is None and mesh is None and device_plan_applies(estimator, framing_mode, transform_mode, total_frames):
         done = _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode,
                                            camera_lock, strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested,
-                                           pbar, progress_total, keep_on_device, temporal_fill, blocked, mask_info, spatial_fill)
+                                           pbar, progress_total, keep_on_device, temporal_fill, blocked, mask_info, spatial_fill,
+                                           stability_report)
         if done is not None:
             return done
         device_frames = context.device_batch(ctx)   # F0 rescaled the clip: everything is redone on the rescaled frames below
@@ -914,6 +935,7 @@ def _stabilize_frames(
         meta["mesh_warp"] = mesh_block
     _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill)
     _spatial_fill(ctx, dst, mask, plan, meta, spatial_fill)
+    _stability_report(ctx, device_frames, dst, mask, plan, meta, stability_report, segments)
     check_interrupt()
     verdict = {"used": False, "mismatched_frames": 0}
     if keep_on_device:

@@ -198,6 +198,8 @@ _SIGNATURES = {
                   C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vstab_spatial_fill_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vstab_frame_sse_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vstab_gftt_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p,
                   C.c_void_p]),
@@ -997,6 +999,35 @@ class Context:
             _dev_ptr(hole_count) if hole_count is not None else None,
             _dev_ptr(fill_count) if fill_count is not None else None), "vstab_spatial_fill_batch")
         return hole_count, fill_count
+
+    # ------------------------------------------------------------------ stability report
+    def frame_sse_batch(self, a, b, mask_a=None, mask_b=None):
+        """Masked squared error of frame a[k] against frame b[k] as exact integers (include/vstab.h states the rule): a, b
+        [n,h,w,3], mask_a / mask_b [n,h,w] or None (every pixel valid), all f32, device, contiguous.  a and b may be views of
+        one tensor (b = clip[1:], a = clip[:-1] is the consecutive-frame form); nothing is written to them.
+        -> (sse i64 [n], count i32 [n]), device tensors."""
+        torch = self.torch
+        for name, t in (("a", a), ("b", b), ("mask_a", mask_a), ("mask_b", mask_b)):
+            if t is None and name.startswith("mask"):
+                continue
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()):
+                raise ValueError(f"frame_sse_batch: {name} must be a contiguous float32 tensor on {self.device}")
+        if a.dim() != 4 or a.shape[3] != 3:
+            raise ValueError(f"frame_sse_batch: a of shape {tuple(a.shape)} is not [n,h,w,3]")
+        if tuple(b.shape) != tuple(a.shape):
+            raise ValueError(f"frame_sse_batch: b of shape {tuple(b.shape)} does not match a {tuple(a.shape)}")
+        for name, t in (("mask_a", mask_a), ("mask_b", mask_b)):
+            if t is not None and tuple(t.shape) != tuple(a.shape[:3]):
+                raise ValueError(f"frame_sse_batch: {name} of shape {tuple(t.shape)} does not match the frames: expected "
+                                 f"{tuple(a.shape[:3])}")
+        n, h, w = int(a.shape[0]), int(a.shape[1]), int(a.shape[2])
+        sse = torch.empty((n,), dtype=torch.int64, device=self.device)
+        count = torch.empty((n,), dtype=torch.int32, device=self.device)
+        self.use_torch_stream()
+        _check(self.lib.vstab_frame_sse_batch(
+            self.handle, _dev_ptr(a), _dev_ptr(mask_a) if mask_a is not None else None, _dev_ptr(b),
+            _dev_ptr(mask_b) if mask_b is not None else None, n, h, w, _dev_ptr(sse), _dev_ptr(count)), "vstab_frame_sse_batch")
+        return sse, count
 
     # ------------------------------------------------------------------ Classic estimator (sparse features + LK)
     def gftt_batch(self, gray, max_corners=400, quality=0.01, min_distance=7.0, block_size=21):

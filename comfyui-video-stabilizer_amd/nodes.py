@@ -671,6 +671,74 @@ class VideoStabilizerPaddingFill(io.ComfyNode):
         return io.NodeOutput(_image_out(dst, context), json.dumps({"spatial_fill": block}))
 
 
+class VideoStabilizerStabilityReport(io.ComfyNode):
+    """How steady a clip is, as a number: the inter-frame transformation fidelity (stability.py) of any frames, under their
+    padding mask if one is given, and next to the unstabilized clip's if that is given.  Reads its inputs and returns the
+    block as JSON.  Not one of the reference's nodes: it is listed by an extension but kept out of NODE_CLASSES."""
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        schema = io.Schema(
+            node_id="video_stabilizer_stability_report",
+            display_name="Video Stabilizer Stability Report",
+            category="Video/Stabilization",
+            description=("Mean PSNR between consecutive frames (ITF) over the pixels both frames really show; with the "
+                         "unstabilized clip connected, also its ITF and the gain in dB."),
+        )
+        schema.inputs = [
+            io.Image.Input("frames", display_name="Frames", tooltip="The clip to measure, e.g. stabilized frames."),
+            io.Mask.Input("padding_mask", display_name="Padding Mask", optional=True,
+                          tooltip="[N,H,W], or [1,H,W] for every frame; padded pixels stay out of the measure."),
+            io.Image.Input("reference_frames", display_name="Reference Frames", optional=True,
+                           tooltip="The unstabilized clip, for `before` and `gain_db`."),
+        ]
+        schema.outputs = [io.String.Output("meta", display_name="Meta")]
+        return schema
+
+    @classmethod
+    def execute(cls, frames: Any, padding_mask: Any = None, reference_frames: Any = None) -> io.NodeOutput:
+        import json
+
+        from . import native, stability
+
+        context = hm._normalize_video_input(frames)
+        n, h, w = len(context.frames), context.height, context.width
+        # every check comes before any GPU work
+        if n == 0:
+            raise ValueError("stability report: socket 'frames' holds no frame")
+        shape = None
+        if padding_mask is not None:
+            if not (hasattr(padding_mask, "dtype") and hasattr(padding_mask, "shape")):
+                raise ValueError(f"stability report: socket 'padding_mask' must be a floating-point MASK tensor, got {type(padding_mask).__name__}")
+            if "float" not in str(padding_mask.dtype):
+                raise ValueError(f"stability report: socket 'padding_mask' must be a floating-point MASK, got {padding_mask.dtype}")
+            shape = tuple(int(v) for v in padding_mask.shape)
+            if len(shape) == 4 and shape[3] == 1:
+                shape = shape[:3]
+            if len(shape) != 3 or shape[1:] != (h, w) or shape[0] not in (1, n):
+                raise ValueError(f"stability report: socket 'padding_mask' of shape {tuple(padding_mask.shape)} does not match "
+                                 f"socket 'frames' [{n},{h},{w},3]: expected [{n},{h},{w}] or [1,{h},{w}]")
+        reference = None if reference_frames is None else hm._normalize_video_input(reference_frames)
+        if reference is not None and len(reference.frames) == 0:
+            raise ValueError("stability report: socket 'reference_frames' holds no frame")
+        ctx = native.default_context()
+        torch = ctx.torch
+
+        def on_device(video):   # F0's value-range rule, as every node of the package applies it to its frames
+            batch = video.device_batch(ctx)
+            if video.range_pending and hm.resolve_value_range(video, hm.prefetch_peaks(ctx.frame_range(batch)), ctx):
+                batch = video.device_batch(ctx)
+            return batch
+
+        mask = None
+        if padding_mask is not None:
+            mask = padding_mask if isinstance(padding_mask, torch.Tensor) else torch.from_numpy(np.asarray(padding_mask))
+            mask = mask.to(device=ctx.device, dtype=torch.float32).reshape((shape[0], h, w)).expand(n, h, w).contiguous()
+        after = stability.itf(on_device(context), mask, ctx=ctx)
+        before = None if reference is None else stability.itf(on_device(reference), None, ctx=ctx)
+        return io.NodeOutput(json.dumps({"stability": stability.report_block(before, after)}))
+
+
 NODE_CLASSES = [VideoStabilizerClassic, VideoStabilizerFlow, VideoStabilizerMotionApply, VideoStabilizerShakeGenerator,
                 VideoStabilizerShakeGeneratorManual, VideoStabilizerInverse]
 
@@ -742,3 +810,11 @@ class VideoStabilizerAmdFillExtension(VideoStabilizerAmdMeshApplyExtension):
 
     async def get_node_list(self) -> list:
         return await super().get_node_list() + [VideoStabilizerPaddingFill]
+
+
+class VideoStabilizerAmdReportExtension(VideoStabilizerAmdFillExtension):
+    """The fill extension's thirteen nodes plus Video Stabilizer Stability Report.  A class of its own for the reason the
+    five before it are."""
+
+    async def get_node_list(self) -> list:
+        return await super().get_node_list() + [VideoStabilizerStabilityReport]

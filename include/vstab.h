@@ -584,6 +584,31 @@ int vstab_mesh_unwarp_batch(vstab_ctx* ctx, const float* src, int n, int src_h, 
 int vstab_spatial_fill_batch(vstab_ctx* ctx, float* dst, const float* mask, int n, int h, int w, int chunk_frames,
                              uint32_t* hole_count, uint32_t* fill_count);
 
+/* ---- stability report: masked squared error between frames, as exact integers (beyond the reference, off by default) ----
+ * The inter-frame transformation fidelity (ITF) of the stabilization literature is the mean PSNR between consecutive frames,
+ * here over the pixels both frames really show.  This entry point forms its sums on the device; the logarithm is host
+ * arithmetic on the downloaded integers (stability.py).  It compares frame a[k] with frame b[k] for k in 0..n-1.  The rule:
+ *   - A pixel is VALID in a frame iff mask <= 0.5f (spatial fill's convention: a NaN, an inf and anything above 0.5 are not
+ *     valid); a NULL mask makes every pixel of its frames valid.  A pixel COUNTS for pair k iff it is valid in a[k] and in
+ *     b[k]; count[k] is the number of such pixels.
+ *   - For every counting pixel and every channel: d = a - b, one IEEE float32 subtraction; e = (double)d * (double)d, exact
+ *     in fp64; e = (e < 4.0) ? e : 4.0, so that a NaN or inf difference contributes the cap; q = (uint64_t)(e * 4294967296.0),
+ *     the multiply by 2^32 exact and the conversion truncating.
+ *   - sse[k] is the sum of q over the counting pixels and the three channels as a 64-bit integer: it does not depend on the
+ *     order of the additions, so the result equals a NumPy restatement exactly.  One pixel contributes at most 3 * 2^34, a
+ *     frame of 8.3 Mpixel stays below 2^59: no wrap.  A pair without a counting pixel has count = 0 and sse = 0.
+ * a, b            dev [n, h, w, 3] f32.  They may overlap in any way: b = a + h*w*3 with n = N - 1 is the consecutive-frame
+ *                 form.  Nothing is written to a, b or the masks.
+ * mask_a, mask_b  dev [n, h, w] f32 or NULL, each independently of the other.
+ * sse             dev [n] u64;  count  dev [n] u32.  The call zeroes both itself.
+ * n >= 1, h, w >= 1, h * w < 2^31.  Kernel (vstab_stability.hip): one launch over all pairs reads the frames as flat float
+ * arrays, float4 per lane where a[k] and b[k] sit at the same offset from a 16-byte boundary (a scalar head and tail of up
+ * to 3 floats each), one float per lane where they do not; the reduction runs per thread, by wavefront shuffle, in LDS, and
+ * ends in one 64-bit and one 32-bit atomic add per workgroup and pair, skipped when the workgroup counted nothing.
+ * Asynchronous on the context's stream; timing kind "stability". */
+int vstab_frame_sse_batch(vstab_ctx* ctx, const float* a, const float* mask_a, const float* b, const float* mask_b,
+                          int n, int h, int w, uint64_t* sse, uint32_t* count);
+
 /* ---- F6 / F9 host helper: element-wise libm over fp64 arrays (host pointers, no GPU involved) ----
  * nodes/stabilizer_utils.py:300-358 (_matrix_to_params / _params_to_matrix) call math.sqrt/atan2/log and
  * math.exp/cos/sin per frame; this runs the same libm functions over a whole clip in one call.
