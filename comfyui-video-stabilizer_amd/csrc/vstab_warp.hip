@@ -1,5 +1,6 @@
 // vstab_warp.hip -- perspective/similarity warp with padding mask, its mesh-displaced forms (mesh_warp_kernel and its
-// inverse, mesh_unwarp_kernel), the multi-sample motion blur and the temporal fill.
+// inverse, mesh_unwarp_kernel), the multi-sample motion blur, the temporal fill and the coverage extent of the dynamic zoom
+// (cover_extent_kernel: warp_pixel's coverage bit alone, nothing sampled).
 // All of them take their coordinates from ONE definition, warp_pixel, and
 // share one tile shell (TileShell, warp_kernel's body, block_count_add); the scalar pieces that vstab_crop / vstab_dis / vstab_tvl1
 // use too are in vstab_internal.h.  profiles/warp_traffic.json is tied to the hash of these two files: the warp's arithmetic
@@ -559,6 +560,67 @@ constexpr auto mesh_warp_kernel = warp_kernel<VSTAB_INTERP_BILINEAR, SUBPIX, WIT
 template <int SUBPIX, bool WITH_MASK>
 constexpr auto mesh_unwarp_kernel = warp_kernel<VSTAB_INTERP_BILINEAR, SUBPIX, WITH_MASK, 32, MeshUnwarpArgs>;
 
+// ---- coverage extent (dynamic zoom; the rule: vstab_cover_extent_batch in include/vstab.h) ------------------------------
+// How far the warp's own nearest-neighbour coverage reaches around the canvas centre: the minimum over a frame's uncovered
+// pixels of their scaled Chebyshev distance e from the centre.  The coverage bit is warp_pixel's `c`, taken with samplers
+// that load nothing: the compiler drops the Q5 / float32 sampling chains, what stays is the fp64 coordinate arithmetic and,
+// under a mesh, the LDS vertex lookups.  No image memory is read or written, so the pass is bound by fp64 VALU.
+// Args = WarpArgs: the plain warp's coverage; Args = MeshWarpArgs: the mesh warp's (src, dst, mask, pad_count unused).
+__global__ void extent_preset_kernel(unsigned* __restrict__ extent, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) extent[i] = 0xFFFFFFFFu;
+}
+
+template <int SUBPIX, class Args>
+__global__ __launch_bounds__(256) void cover_extent_kernel(Args a, unsigned* __restrict__ extent)
+{
+    constexpr int TILE_TX = 32;
+    __shared__ unsigned s_min[256 / 64];
+    const TileShell<TILE_TX> t(a.tiles_x, a.tiles_y, a.dh, a.dw);
+    const int frame = t.frame, x0 = t.x0, y = t.y, npx = t.npx;
+    const auto disp = make_displacement(a, frame);
+
+    unsigned best = 0xFFFFFFFFu;
+    if (t.active) {
+        const double dy = (double)y;
+        const WarpXform* __restrict__ xf = a.xf + frame;
+        const XformRegs<VSTAB_INTERP_BILINEAR, SUBPIX> r(xf);
+        // |2y - (dh-1)| * (dw-1) and |2x - (dw-1)| * (dh-1): below 2^31 each (the host checks (dw-1) * (dh-1) < 2^31)
+        const unsigned wm = (unsigned)(a.dw - 1), hm = (unsigned)(a.dh - 1);
+        const unsigned y2 = 2u * (unsigned)y;
+        const unsigned ey = (y2 > hm ? y2 - hm : hm - y2) * wm;
+#pragma unroll
+        for (int p = 0; p < TILE_PX; p++) {
+            if (p >= npx) continue;
+            const int x = x0 + p * TILE_TX;
+            float c = 0.f;
+            (void)warp_pixel<VSTAB_INTERP_BILINEAR, SUBPIX, true>(
+                xf, r, a.sh, a.sw, a.dw, a.bw0, a.bw0_pow2, x, y, dy,
+                [](int, int) { return Px{0.f, 0.f, 0.f}; }, [](float, float) { return Px{0.f, 0.f, 0.f}; }, disp, c);
+            const unsigned x2 = 2u * (unsigned)x;
+            const unsigned ex = (x2 > wm ? x2 - wm : wm - x2) * hm;
+            const unsigned e = ex > ey ? ex : ey;
+            if (c == 0.f) best = e < best ? e : best;     // mask = 1 - c == 1.0f: uncovered
+        }
+    }
+
+    // per thread -> wave shuffle -> LDS -> one atomic minimum per workgroup, none if it saw no uncovered pixel
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned o = __shfl_down(best, off);
+        best = o < best ? o : best;
+    }
+    if ((threadIdx.x & 63) == 0) s_min[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned total = s_min[0];
+#pragma unroll
+        for (int w = 1; w < 256 / 64; w++) total = s_min[w] < total ? s_min[w] : total;
+        if (total != 0xFFFFFFFFu) atomicMin(extent + frame, total);
+    }
+}
+
 // ---- motion blur: S samples per output pixel (motion_apply.py:137-202) ---------------------------------------------
 //
 // What bounds the S-sample loop (profiles/r03_blur_kernel.md): a bicubic sample reads 16 taps x 12 B = 192 B per output
@@ -1081,16 +1143,38 @@ int launch_warp_blur(const WarpArgs& a, int interp, int subpix, bool with_mask, 
     return launch_blur<VSTAB_INTERP_BILINEAR, VSTAB_SUBPIX_Q5>(a, with_mask, st);
 }
 
+// The limits every entry point of this file puts on frame count and sizes, and on the sub-pixel mode: one definition each, so
+// that an entry point "checked as vstab_warp_batch checks it" (the mesh forms, the coverage extent) stays so.
+int check_sizes(const char* who, int n, int sh, int sw, int dh, int dw)
+{
+    VSTAB_REQUIRE(n > 0 && sh > 0 && sw > 0 && dh > 0 && dw > 0, "%s: non-positive size (n=%d src=%dx%d out=%dx%d)", who, n, sw, sh, dw, dh);
+    VSTAB_REQUIRE(sh <= 32767 && sw <= 32767, "%s: source larger than 32767 px is not representable in OpenCV's short maps", who);
+    VSTAB_REQUIRE((long long)sh * sw < (1LL << 30) && (long long)dh * dw < (1LL << 30), "%s: frames of 2^30 pixels or more are not supported (32-bit in-frame offsets)", who);
+    return 0;
+}
+
+int check_subpix(const char* who, int subpix)
+{
+    VSTAB_REQUIRE(subpix == VSTAB_SUBPIX_Q5 || subpix == VSTAB_SUBPIX_EXACT, "%s: unknown subpix mode %d", who, subpix);
+    return 0;
+}
+
+// A mesh of mw x mh vertices over a domain_w x domain_h canvas (`domain`: which canvas that is, for the message).
+int check_mesh(const char* who, int n, int sh, int sw, int dh, int dw, int domain_h, int domain_w, const char* domain, int mw, int mh)
+{
+    VSTAB_REQUIRE(domain_h >= 2 && domain_w >= 2, "%s: bad size (n=%d src=%dx%d out=%dx%d; the %s must be at least 2x2)", who, n, sw, sh, dw, dh, domain);
+    VSTAB_REQUIRE(mw >= 2 && mh >= 2 && mw <= MESH_MAX_VERTS && mh <= MESH_MAX_VERTS, "%s: %dx%d vertices outside 2..%d", who, mw, mh, MESH_MAX_VERTS);
+    return 0;
+}
+
 int check_common(const char* who, vstab_ctx* ctx, const void* src, int n, int sh, int sw, const void* mats,
                  int dh, int dw, int interp, const float* border, int subpix, const void* dst)
 {
     VSTAB_REQUIRE(ctx != nullptr, "%s: ctx is NULL", who);
     VSTAB_REQUIRE(src && mats && border && dst, "%s: NULL pointer argument", who);
-    VSTAB_REQUIRE(n > 0 && sh > 0 && sw > 0 && dh > 0 && dw > 0, "%s: non-positive size (n=%d src=%dx%d out=%dx%d)", who, n, sw, sh, dw, dh);
-    VSTAB_REQUIRE(sh <= 32767 && sw <= 32767, "%s: source larger than 32767 px is not representable in OpenCV's short maps", who);
-    VSTAB_REQUIRE((long long)sh * sw < (1LL << 30) && (long long)dh * dw < (1LL << 30), "%s: frames of 2^30 pixels or more are not supported (32-bit in-frame offsets)", who);
+    if (int rc = check_sizes(who, n, sh, sw, dh, dw)) return rc;
     VSTAB_REQUIRE(interp == VSTAB_INTERP_BILINEAR || interp == VSTAB_INTERP_BICUBIC, "%s: unknown interpolation %d", who, interp);
-    VSTAB_REQUIRE(subpix == VSTAB_SUBPIX_Q5 || subpix == VSTAB_SUBPIX_EXACT, "%s: unknown subpix mode %d", who, subpix);
+    if (int rc = check_subpix(who, subpix)) return rc;
     VSTAB_REQUIRE(!(subpix == VSTAB_SUBPIX_EXACT && interp == VSTAB_INTERP_BICUBIC), "%s: exact sub-pixel mode exists for bilinear only", who);
     return 0;
 }
@@ -1285,8 +1369,7 @@ int mesh_launch(const char* who, const char* kind, bool inverse, vstab_ctx* ctx,
     if (int rc = check_common(who, ctx, src, n, src_h, src_w, matrices, out_h, out_w, VSTAB_INTERP_BILINEAR, border_rgb, subpix, dst)) return rc;
     VSTAB_REQUIRE(offsets != nullptr, "%s: NULL pointer argument", who);
     const int domain_h = inverse ? out_h : src_h, domain_w = inverse ? out_w : src_w;
-    VSTAB_REQUIRE(domain_h >= 2 && domain_w >= 2, "%s: bad size (n=%d src=%dx%d out=%dx%d; the %s must be at least 2x2)", who, n, src_w, src_h, out_w, out_h, inverse ? "output" : "source");
-    VSTAB_REQUIRE(mw >= 2 && mh >= 2 && mw <= MESH_MAX_VERTS && mh <= MESH_MAX_VERTS, "%s: %dx%d vertices outside 2..%d", who, mw, mh, MESH_MAX_VERTS);
+    if (int rc = check_mesh(who, n, src_h, src_w, out_h, out_w, domain_h, domain_w, inverse ? "output" : "source", mw, mh)) return rc;
     VSTAB_HIP(hipSetDevice(ctx->device));
     const WarpXform* xf = nullptr;
     if (vstab_stage_xforms(ctx, matrices, (size_t)n, &xf)) return 1;
@@ -1332,6 +1415,46 @@ extern "C" int vstab_mesh_unwarp_batch(vstab_ctx* ctx, const float* src, int n, 
 {
     return mesh_launch("vstab_mesh_unwarp_batch", "mesh_unwarp", true, ctx, src, n, src_h, src_w, matrices, out_h, out_w, border_rgb,
                        subpix, offsets, mw, mh, dst, mask, pad_count, unconverged);
+}
+
+extern "C" int vstab_cover_extent_batch(vstab_ctx* ctx, const float* matrices, int n, int src_h, int src_w, int out_h, int out_w,
+                                        int subpix, const float* offsets, int mw, int mh, uint32_t* extent)
+{
+    const char* who = "vstab_cover_extent_batch";
+    VSTAB_REQUIRE(ctx != nullptr, "%s: ctx is NULL", who);
+    VSTAB_REQUIRE(matrices != nullptr && extent != nullptr, "%s: NULL pointer argument", who);
+    VSTAB_REQUIRE(out_w >= 2 && out_h >= 2, "%s: a %dx%d canvas has no centred extent (both sides must be at least 2 px)", who, out_w, out_h);
+    VSTAB_REQUIRE((long long)(out_w - 1) * (out_h - 1) < (1LL << 31), "%s: (out_w-1)*(out_h-1) of a %dx%d canvas does not fit the 32-bit extent", who, out_w, out_h);
+    // the rest as vstab_warp_batch / vstab_mesh_warp_batch check it: the same routines
+    if (int rc = check_sizes(who, n, src_h, src_w, out_h, out_w)) return rc;
+    if (int rc = check_subpix(who, subpix)) return rc;
+    VSTAB_REQUIRE(((uintptr_t)extent & 3) == 0, "%s: extent is not aligned to its element size", who);
+    if (offsets != nullptr) {
+        if (int rc = check_mesh(who, n, src_h, src_w, out_h, out_w, src_h, src_w, "source", mw, mh)) return rc;
+    }
+    VSTAB_HIP(hipSetDevice(ctx->device));
+    const WarpXform* xf = nullptr;
+    if (vstab_stage_xforms(ctx, matrices, (size_t)n, &xf)) return 1;
+    const float no_border[3] = {0.f, 0.f, 0.f};
+    MeshWarpArgs a{};
+    fill_geometry(a, nullptr, xf, n, src_h, src_w, out_h, out_w, no_border, nullptr, nullptr, nullptr);
+    a.offsets = offsets; a.mw = mw; a.mh = mh;
+    unsigned blocks = 0;
+    if (int rc = tile_grid(who, n, out_h, out_w, 32, 256, &a.tiles_x, &a.tiles_y, &blocks)) return rc;
+    const dim3 grid(blocks), block(256);
+    KernelTimer timer(ctx, "cover_extent");
+    hipLaunchKernelGGL(extent_preset_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, extent, n);
+    if (offsets != nullptr) {
+        const size_t lds = (size_t)mw * mh * 2 * sizeof(float);    // <= 33.8 KB
+        if (subpix == VSTAB_SUBPIX_EXACT) hipLaunchKernelGGL((cover_extent_kernel<VSTAB_SUBPIX_EXACT, MeshWarpArgs>), grid, block, lds, ctx->stream, a, extent);
+        else hipLaunchKernelGGL((cover_extent_kernel<VSTAB_SUBPIX_Q5, MeshWarpArgs>), grid, block, lds, ctx->stream, a, extent);
+    } else {
+        const WarpArgs& plain = a;
+        if (subpix == VSTAB_SUBPIX_EXACT) hipLaunchKernelGGL((cover_extent_kernel<VSTAB_SUBPIX_EXACT, WarpArgs>), grid, block, 0, ctx->stream, plain, extent);
+        else hipLaunchKernelGGL((cover_extent_kernel<VSTAB_SUBPIX_Q5, WarpArgs>), grid, block, 0, ctx->stream, plain, extent);
+    }
+    VSTAB_HIP(hipGetLastError());
+    return 0;
 }
 
 // ---- temporal fill: padding pixels taken from neighbouring frames ----------------------------------------------------

@@ -216,7 +216,7 @@ def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, t
                       strength: float, smooth: float, keep_fov: float, padding_rgb, frame_rate: float, group=None,
                       estimator: str = "flow", stats: Optional[Dict[str, float]] = None, want_meta: bool = True,
                       check_value_range: bool = True, temporal_fill: int = 0, estimation_mask=None, scene_cuts=None,
-                      mesh_warp=None):
+                      mesh_warp=None, dynamic_zoom=None):
     """Sharded equivalent of `_stabilize_frames` (flow.py:213-640).
 
     local_frames: device tensor [n_local (+1 halo for rank > 0 that owns frames), H, W, 3] float32 -- this rank's frames
@@ -243,6 +243,11 @@ def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, t
         # before the warp, which the sharded path does not do; every rank raises alike, before any collective
         raise ValueError("stabilize_sharded does not support mesh_warp: the mesh warp is not sharded (vertex paths need every "
                          "rank's flow grid); run the single-GPU pipeline for a mesh-warped stabilization")
+    if dynamic_zoom is not None:
+        # the envelope runs over the whole clip: every rank's coverage extents would have to be gathered before the warp,
+        # which the sharded path does not do; every rank raises alike, before any collective
+        raise ValueError("stabilize_sharded does not support dynamic_zoom: dynamic zoom is not sharded (the envelope needs "
+                         "every rank's extents); run the single-GPU pipeline for a dynamically zoomed stabilization")
     import torch.distributed as dist
 
     from . import native

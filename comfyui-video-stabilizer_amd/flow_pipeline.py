@@ -16,11 +16,12 @@ from __future__ import annotations
 
 import gc
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Any, Dict, Optional, Tuple
 
 import numpy as np
 
+from . import dynamic_zoom as dynamic_zoom_mod
 from . import host_math as hm
 from . import mesh_warp as mesh_warp_mod
 from . import native
@@ -668,6 +669,16 @@ def _mesh_offsets(ctx, mesh, plan, grid, blocked, working_size, size, segments, 
     return offsets, mesh_warp_mod.meta_block(mesh, max_shift, residual, count, offsets, native.MESH_MIN_SAMPLES)
 
 
+# ---- dynamic zoom (beyond the reference; dynamic_zoom.py, the rule is in include/vstab.h) -------------------------------
+def _dynamic_zoom(ctx, zoom, plan, offsets, segments):
+    """-> (the plan with its final matrices zoomed, meta["dynamic_zoom"] still without the warp's counts).  One launch of the
+    coverage-extent kernel over the plan's final matrices -- and the mesh warp's vertex offsets, where there are any -- then
+    the envelope on the host, per shot under scene cuts; Z @ final in float32, like the other framing shifts."""
+    extent = ctx.cover_extent_batch(plan.final_matrices, plan.source_size, plan.output_size, offsets)
+    Z, block = dynamic_zoom_mod.plan_zoom(zoom, extent, plan.output_size, plan.fps_effective, segments)
+    return replace(plan, final_matrices=np.matmul(Z, np.asarray(plan.final_matrices, dtype=np.float32))), block
+
+
 def _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode, camera_lock,
                                 strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested, pbar, progress_total,
                                 keep_on_device, temporal_fill=0, blocked=None, mask_info=None, spatial_fill=False,
@@ -749,6 +760,8 @@ def _stabilize_frames(
     mesh_motion: bool = False,
     spatial_fill: bool = False,
     stability_report: bool = False,
+    dynamic_zoom=None,
+    zoom_limit=None,
 ) -> hm.StabilizationResult:
     """Positional signature of the reference (flow.py:213-223); keyword-only extras select the GPU
     context, keep outputs resident in HBM (multi-GPU sharding lives in distributed.py) or switch the
@@ -784,7 +797,18 @@ def _stabilize_frames(
     fidelity (mean PSNR between consecutive frames over the pixels both show; stability.py, include/vstab.h states the rule)
     of the source frames and of the returned frames under the returned mask, behind every fill, and their difference
     gain_db; pairs across a scene cut are left out and counted.  Frames, mask and every other meta key are unchanged.
-    False: the meta without it, byte for byte, and nothing is launched.  Bypass paths ignore it."""
+    False: the meta without it, byte for byte, and nothing is launched.  Bypass paths ignore it.
+    dynamic_zoom (beyond the reference, None by default): True (a window of 2 s) or a window in seconds in (0, 60].  Every
+    frame is zoomed about the canvas centre just enough to hide its own border: the coverage extent of the plan's final
+    matrices (and of the mesh offsets, under mesh_warp) is measured per output pixel with the warp's own arithmetic
+    (dynamic_zoom.py; include/vstab.h states the rule), the zoom each frame needs goes through a sliding maximum and a box
+    mean over the window -- per shot under scene_cuts -- and is capped at zoom_limit (None: 2.0, else in [1, 16]); the
+    plan's final matrices are replaced by the zoomed ones and the warp runs unchanged.  For crop_and_pad framing only;
+    meta["dynamic_zoom"] reports the zoom per frame, stabilization_warp / motion_meta hold the zoomed matrices.  None: the
+    behaviour and meta without it, byte for byte, and nothing is launched.  Bypass paths ignore it."""
+    zoom = dynamic_zoom_mod.check_request(dynamic_zoom, zoom_limit)
+    if zoom is not None:
+        dynamic_zoom_mod.check_pipeline(framing_mode)
     spatial_fill = spatial_fill_mod.check_request(spatial_fill)
     stability_report = stability_mod.check_request(stability_report)
     scene = scene_cuts_mod.check_request(scene_cuts, cut_threshold)
@@ -867,8 +891,9 @@ def _stabilize_frames(
         masked = {"blocked": blocked}
 
     # (scene-aware calls form the plan on the host: plan_kernel knows one continuous camera move; so do mesh-warp calls: the
-    # vertex paths need the plan's own transitions before the warp can be queued)
-    if scene is None and mesh is None and device_plan_applies(estimator, framing_mode, transform_mode, total_frames):
+    # vertex paths need the plan's own transitions before the warp can be queued; and dynamic-zoom calls: the zoom is formed
+    # from the plan's final matrices before the warp can be queued)
+    if scene is None and mesh is None and zoom is None and device_plan_applies(estimator, framing_mode, transform_mode, total_frames):
         done = _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode,
                                            camera_lock, strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested,
                                            pbar, progress_total, keep_on_device, temporal_fill, blocked, mask_info, spatial_fill,
@@ -911,10 +936,13 @@ def _stabilize_frames(
         return hm.StabilizationResult(frames_out, masks_out, _attach_motion_meta(plan.bypass_meta, fps_effective, estimator))
 
     # ---- warp (F13) ------------------------------------------------------------
-    mesh_block = None
+    mesh_block = zoom_block = offsets = None
     if mesh is not None:
         offsets, mesh_block = _mesh_offsets(ctx, mesh, plan, masked["grid_out"][0], blocked, working_size, size, segments,
                                             strength, smooth, camera_lock, fps_effective)
+    if zoom is not None:
+        plan, zoom_block = _dynamic_zoom(ctx, zoom, plan, offsets, segments)
+    if mesh is not None:
         dst, mask, counts = ctx.mesh_warp_batch(
             device_frames, plan.final_matrices, plan.output_size, offsets, border=hm.border_value(padding_rgb),
             want_mask=True, want_count=True)
@@ -926,7 +954,10 @@ def _stabilize_frames(
             border=hm.border_value(padding_rgb), want_mask=True, want_count=True)
     meta = prepare_meta(plan)  # host JSON work overlaps the warp kernel
     progress_done = _replay_progress(pbar, progress_done, total_frames, progress_total)
-    meta = complete_meta(meta, plan, _counts_to_host(counts))
+    pad_counts = _counts_to_host(counts)
+    meta = complete_meta(meta, plan, pad_counts)
+    if zoom_block is not None:
+        meta["dynamic_zoom"] = dynamic_zoom_mod.finish_meta(zoom_block, pad_counts)
     if mask_info is not None:
         meta["estimation_mask"] = estimation_mask_meta(fit_records, *mask_info)
     if scene_block is not None:

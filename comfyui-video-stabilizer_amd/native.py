@@ -183,6 +183,9 @@ _SIGNATURES = {
     "vstab_mesh_unwarp_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                   C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vstab_cover_extent_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                  C.c_void_p]),
     "vstab_fit_records_device": (C.c_void_p, [C.c_void_p]),
     "vstab_sample_fit_batch_end": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "vstab_flow_plan_device": (
@@ -796,6 +799,26 @@ class Context:
             _dev_ptr(counts) if counts is not None else None,
             _dev_ptr(unconverged) if unconverged is not None else None), "vstab_mesh_unwarp_batch")
         return dst, mask, counts, unconverged
+
+    def cover_extent_batch(self, matrices, src_size, out_size, offsets=None, subpix=None):
+        """How far the warp's own coverage reaches around the canvas centre (vstab_cover_extent_batch; the rule is in
+        include/vstab.h): matrices f32 [N,3,3] forward, src_size / out_size (w, h), offsets f32 [N,mh,mw,2] (host or device) for
+        the mesh warp's coverage or None for the plain warp's -> uint32 [N] on the host: per frame the minimum of
+        e = max(|2x-(w-1)|*(h-1), |2y-(h-1)|*(w-1)) over the pixels the warp would leave uncovered, 0xFFFFFFFF if there is none."""
+        torch = self.torch
+        m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(-1, 9)
+        n = m.shape[0]
+        sw, sh = int(src_size[0]), int(src_size[1])
+        ow, oh = int(out_size[0]), int(out_size[1])
+        mw = mh = 0
+        if offsets is not None:
+            offsets, mw, mh = self._mesh_offsets("cover_extent_batch", offsets, n)
+        extent = torch.empty((max(n, 1),), dtype=torch.int32, device=self.device)
+        self.use_torch_stream()
+        _check(self.lib.vstab_cover_extent_batch(
+            self.handle, m.ctypes.data, n, sh, sw, oh, ow, SUBPIX[subpix or DEFAULT_SUBPIX],
+            _dev_ptr(offsets) if offsets is not None else None, mw, mh, _dev_ptr(extent)), "vstab_cover_extent_batch")
+        return extent[:n].cpu().numpy().view(np.uint32)
 
     def _fit_inputs(self, grid_flow, blocked):
         if grid_flow.device != self.device:

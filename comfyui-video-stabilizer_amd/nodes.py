@@ -739,6 +739,47 @@ class VideoStabilizerStabilityReport(io.ComfyNode):
         return io.NodeOutput(json.dumps({"stability": stability.report_block(before, after)}))
 
 
+class VideoStabilizerFlowZoom(io.ComfyNode):
+    """The Flow node with a dynamic zoom instead of padding: every frame is zoomed about the centre just enough to hide
+    its own border, and the zoom is smoothed over a window so that it never pumps (dynamic_zoom.py).  Framing is fixed to
+    crop_and_pad.  Not one of the reference's nodes: it is listed by an extension but kept out of NODE_CLASSES."""
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        from .dynamic_zoom import DEFAULT_WINDOW_S, DEFAULT_ZOOM_LIMIT, WINDOW_MAX_S, ZOOM_LIMIT_MAX, ZOOM_LIMIT_MIN
+
+        schema = io.Schema(
+            node_id="video_stabilizer_flow_zoom",
+            display_name="Video Stabilizer Flow (Dynamic Zoom)",
+            category="Video/Stabilization",
+            description=("Video Stabilizer Flow whose borders are hidden by a per-frame zoom that follows the shake: calm "
+                         "stretches keep their field of view, only the shaky ones are zoomed in."),
+        )
+        base = VideoStabilizerFlow.define_schema()
+        schema.inputs = [s for s in base.inputs if s.id != "framing_mode"] + [
+            io.Float.Input("zoom_window", default=DEFAULT_WINDOW_S, min=0.05, max=WINDOW_MAX_S, step=0.05, display_name="Zoom Window",
+                           tooltip=("Seconds over which the zoom is smoothed: it starts rising this long before a shake and "
+                                    "settles this long after it.  The default has been tried on synthetic clips only.")),
+            io.Float.Input("zoom_limit", default=DEFAULT_ZOOM_LIMIT, min=ZOOM_LIMIT_MIN, max=ZOOM_LIMIT_MAX, step=0.05,
+                           display_name="Zoom Limit",
+                           tooltip=("Largest zoom factor.  Frames that would need more keep some padding, which the padding "
+                                    "mask and the meta report.  The default has been tried on synthetic clips only.")),
+        ]
+        schema.outputs = _estimator_outputs()
+        return schema
+
+    @classmethod
+    def execute(cls, frames: Any, frame_rate: float, transform_mode: str, camera_lock: bool, strength: float, smooth: float,
+                keep_fov: float, padding_color: str, zoom_window: float, zoom_limit: float) -> io.NodeOutput:
+        context = hm._normalize_video_input(frames)
+        result = _stabilize_frames(
+            context, "crop_and_pad", transform_mode, camera_lock, strength, smooth, keep_fov,
+            hm._parse_padding_color(padding_color), frame_rate, keep_on_device=True, estimator="flow",
+            dynamic_zoom=float(zoom_window), zoom_limit=float(zoom_limit),
+        )
+        return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
+
+
 NODE_CLASSES = [VideoStabilizerClassic, VideoStabilizerFlow, VideoStabilizerMotionApply, VideoStabilizerShakeGenerator,
                 VideoStabilizerShakeGeneratorManual, VideoStabilizerInverse]
 
@@ -818,3 +859,11 @@ class VideoStabilizerAmdReportExtension(VideoStabilizerAmdFillExtension):
 
     async def get_node_list(self) -> list:
         return await super().get_node_list() + [VideoStabilizerStabilityReport]
+
+
+class VideoStabilizerAmdZoomExtension(VideoStabilizerAmdReportExtension):
+    """The report extension's fourteen nodes plus Video Stabilizer Flow (Dynamic Zoom).  A class of its own for the reason
+    the six before it are."""
+
+    async def get_node_list(self) -> list:
+        return await super().get_node_list() + [VideoStabilizerFlowZoom]

@@ -556,6 +556,33 @@ int vstab_mesh_unwarp_batch(vstab_ctx* ctx, const float* src, int n, int src_h, 
                             int out_h, int out_w, const float* border_rgb, int subpix, const float* offsets, int mw, int mh,
                             float* dst, float* mask, uint32_t* pad_count, uint32_t* unconverged);
 
+/* ---- dynamic zoom (not a reference feature, off by default): how far a warp's own coverage reaches around the centre ----
+ * A per-frame zoom that hides the frame's own border needs to know the largest centred rectangle of the canvas the warp
+ * covers.  Closed-form geometry would drift from the warp at the nearest-rounding boundary and does not exist for a mesh,
+ * so the measure is taken per output pixel with the warp's own coordinate arithmetic.  The rule, for frame f:
+ *   - pixel (x, y) of the out_h x out_w canvas is UNCOVERED iff vstab_warp_batch (offsets == NULL) or
+ *     vstab_mesh_warp_batch (offsets given) would write mask == 1.0f there for the same matrix, sizes and subpix: the
+ *     nearest-neighbour coverage of those rules (vstab_nn_covered, same column-block terms, displacement and roundings).
+ *   - e(x, y) = max(|2x - (out_w-1)| * (out_h-1), |2y - (out_h-1)| * (out_w-1)) as unsigned 32-bit integers: the Chebyshev
+ *     distance from the canvas centre in units in which the canvas edge is at E = (out_w-1) * (out_h-1) on both axes.
+ *   - extent[f] = the minimum of e over the uncovered pixels, 0xFFFFFFFF if every pixel is covered.
+ * An integer minimum does not depend on the order of its reduction, so the result equals a NumPy restatement exactly.
+ * Every pixel with e < extent[f] is covered, and those pixels form a full centred integer rectangle; for a matrix warp the
+ * covered set is convex, so the continuous rectangle they span is covered too (under a mesh it need not be).
+ * What is decided from the number is host arithmetic (dynamic_zoom.py): the zoom about the canvas centre that brings the
+ * covered rectangle, less VSTAB_ZOOM_MARGIN_PX pixels on every side, out to the canvas edge.
+ *   matrices host [n, 9] f32 forward (source -> output), inverted as vstab_warp_batch inverts them
+ *   offsets  dev  [n, mh, mw, 2] f32 as for vstab_mesh_warp_batch (2 <= mw, mh <= 65; src_w, src_h >= 2), or NULL (mw, mh unused)
+ *   extent   dev  [n] u32; preset by the call itself (a small kernel in front of the pass)
+ * out_w < 2, out_h < 2 or (out_w-1) * (out_h-1) >= 2^31 is refused in front of any launch; the other sizes are checked as
+ * vstab_warp_batch checks them.  Kernel (vstab_warp.hip, beside warp_pixel, which it calls with samplers that load nothing):
+ * the warp's 64 x 8 tile and XCD remap, no image memory read or written; per thread -> wave shuffle -> LDS -> one atomic
+ * minimum per workgroup and frame, skipped when the workgroup saw no uncovered pixel.  Asynchronous on the context's stream;
+ * timing kind "cover_extent". */
+#define VSTAB_ZOOM_MARGIN_PX 2
+int vstab_cover_extent_batch(vstab_ctx* ctx, const float* matrices, int n, int src_h, int src_w, int out_h, int out_w,
+                             int subpix, const float* offsets, int mw, int mh, uint32_t* extent);
+
 /* ---- spatial fill: push-pull inpainting of the pixels that stay padding (beyond the reference, off by default) ----
  * What the warp (and temporal fill) leave as padding is filled per frame from the frame's own valid pixels by pyramid
  * push-pull (Gortler et al., "The Lumigraph", 1996).  The rule -- float32, per frame and per channel, separate IEEE
