@@ -3,13 +3,22 @@
 
 Tolerance: bit-exact against the NumPy restatement tests/tvl1_restatement.py (dense flow and inner-iteration counts),
 which is unpinned against a real OpenCV (see its docstring).  Accuracy against known motion is checked independently of
-any restatement."""
+any restatement.
+
+The cases of tests/tvl1_cases.py take the inner kernel through every rows-per-workgroup choice (8, 4, 2, 1), the row tree
+and the row-sum tree across a power of two, last workgroups with fewer rows, the largest level the size guard admits,
+every parameter off its default and the content that drives the data-dependent branches; tests/test_tvl1_cases_cpu.py
+shows on the CPU that they do.  The scheme itself is refereed on the CPU (tests/test_tvl1_referee_cpu.py: the restatement
+against a float64 statement of the published iteration, within 5.4e-5 px after 300 iterations, and against the true
+motion of a sub-pixel similarity); since the kernels equal the restatement bit for bit, what the referee shows holds for
+them."""
 
 import json
 
 import numpy as np
 import pytest
 
+from tests import tvl1_cases as C
 from tests import tvl1_restatement as R
 
 pytestmark = pytest.mark.gpu
@@ -32,7 +41,7 @@ def textured_clip(n, h, w, seed):
 def _run(ctx, gray, params=None, **kw):
     import torch
 
-    flow, grid, iters = ctx.tvl1_flow_batch(torch.from_numpy(gray), params=params, want_full=True, want_grid=True,
+    flow, grid, iters = ctx.tvl1_flow_batch(torch.from_numpy(np.array(gray)), params=params, want_full=True, want_grid=True,
                                             want_iterations=True, **kw)
     return flow.cpu().numpy(), grid.cpu().numpy(), iters.cpu().numpy()
 
@@ -59,6 +68,44 @@ def test_tvl1_matches_restatement_at_960x540(ctx):
     ref, counts = R.tvl1_clip(gray, R.params(**prm))
     assert np.array_equal(iters, counts)
     assert np.array_equal(flow, ref), f"max abs diff {np.abs(flow - ref).max()}"
+
+
+@pytest.mark.parametrize("case_id", C.CASE_IDS)
+def test_tvl1_case_matches_restatement(ctx, case_id):
+    """Every case of tests/tvl1_cases.py: flow, stride-8 grid and iteration counters bit-equal to the restatement.
+    largest-1025x2048 pins the launch that asks for 65 536 B of dynamic LDS beside the kernel's 16 B of static LDS."""
+    gray = C.clip(case_id)
+    ref, counts = C.restated(case_id)
+    flow, grid, iters = _run(ctx, gray, params=C.library_params(case_id) or None)
+    assert iters.shape == counts.shape
+    assert np.array_equal(iters, counts), (iters, counts)
+    assert np.array_equal(flow, ref), f"max abs diff {np.abs(flow - ref).max()}"
+    assert np.array_equal(grid, ref[:, ::8, ::8])
+
+
+def test_tvl1_grid_sampling(ctx):
+    """sample_step = 1: the grid is the full flow; a step that divides neither side: ceil(h / step) x ceil(w / step)."""
+    ref, _ = C.restated("sum-tree-65x47")
+    flow, grid, _ = _run(ctx, C.clip("sum-tree-65x47"), sample_step=1)
+    assert np.array_equal(flow, ref) and np.array_equal(grid, ref)
+    ref, _ = C.wide_restated()
+    _, grid, _ = _run(ctx, C.wide_clip(), sample_step=9)
+    assert ref.shape[1] % 9 and ref.shape[2] % 9
+    assert grid.shape == (3, 3, 156, 2) and np.array_equal(grid, ref[:, ::9, ::9])
+
+
+def test_tvl1_batch_invariance_on_the_one_row_path(ctx):
+    """Three pairs at 24x1400 (R = 1 at the finest level, R = 2 at the second): one call, one pair per chunk and one
+    call per pair give the restatement's bits -- the per-pair buffer index and ticket of the one-row workgroups."""
+    gray = C.wide_clip()
+    ref, counts = C.wide_restated()
+    flow, grid, iters = _run(ctx, gray)
+    assert np.array_equal(flow, ref) and np.array_equal(iters, counts) and np.array_equal(grid, ref[:, ::8, ::8])
+    f2, g2, i2 = _run(ctx, gray, params={"chunk_pairs": 1})
+    assert np.array_equal(f2, flow) and np.array_equal(g2, grid) and np.array_equal(i2, iters)
+    for p in range(len(gray) - 1):
+        f1, g1, i1 = _run(ctx, gray[p:p + 2])
+        assert np.array_equal(f1[0], flow[p]) and np.array_equal(g1[0], grid[p]) and np.array_equal(i1[0], iters[p])
 
 
 def test_tvl1_batch_and_chunk_invariance(ctx):
@@ -94,6 +141,16 @@ def test_tvl1_rejects_what_it_does_not_restate(ctx):
         ctx.tvl1_flow_batch(torch.zeros((3, 40, 12), dtype=torch.uint8))
     with pytest.raises(ValueError, match="unknown TV-L1 parameter"):
         ctx.tvl1_flow_batch(gray, params={"lambda": 0.1})
+    with pytest.raises(native.VstabError, match="2049x16: at most 2048x2048"):
+        ctx.tvl1_flow_batch(torch.zeros((2, 16, 2049), dtype=torch.uint8))
+    with pytest.raises(native.VstabError, match="16x2049: at most 2048x2048"):
+        ctx.tvl1_flow_batch(torch.zeros((2, 2049, 16), dtype=torch.uint8))
+    with pytest.raises(native.VstabError, match="medianFiltering must be 1 .off. or 5, got 3"):
+        ctx.tvl1_flow_batch(gray, params={"median_filtering": 3})
+    with pytest.raises(native.VstabError, match="nscales must be in .1, 10., got 0"):
+        ctx.tvl1_flow_batch(gray, params={"nscales": 0})
+    with pytest.raises(native.VstabError, match="scaleStep must be in .0, 1., got 1"):
+        ctx.tvl1_flow_batch(gray, params={"scale_step": 1.0})
 
 
 def _similarity(tx, ty, deg, cx, cy):
