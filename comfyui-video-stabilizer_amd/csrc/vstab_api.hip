@@ -43,6 +43,27 @@ void ScratchBuf::release()
     bytes = 0;
 }
 
+MappedBuf::~MappedBuf()
+{
+    if (h) (void)hipHostFree(h);
+}
+
+int MappedBuf::reserve(size_t need, hipStream_t stream)
+{
+    if (need <= bytes) return 0;
+    if (h) {
+        VSTAB_HIP(hipStreamSynchronize(stream));
+        VSTAB_HIP(hipHostFree(h));
+        h = d = nullptr;
+        bytes = 0;
+    }
+    VSTAB_HIP(hipHostMalloc(&h, need, hipHostMallocMapped | hipHostMallocCoherent));
+    memset(h, 0, need);
+    VSTAB_HIP(hipHostGetDevicePointer(&d, h, 0));
+    bytes = need;
+    return 0;
+}
+
 bool vstab_invert3x3(const double* S, double* D) { return vstab_invert3x3_hd(S, D); }
 
 int vstab_stage_params(vstab_ctx* ctx, const void* host, size_t bytes, void** dev_out)
@@ -60,13 +81,12 @@ int vstab_stage_params(vstab_ctx* ctx, const void* host, size_t bytes, void** de
 
 EventPair* vstab_timer_slot(vstab_ctx* ctx, const char* kind)
 {
-    auto it = ctx->timers.find(kind);
-    if (it == ctx->timers.end()) {
-        EventPair ep;
-        if (hipEventCreate(&ep.start) != hipSuccess || hipEventCreate(&ep.stop) != hipSuccess) return nullptr;
-        it = ctx->timers.emplace(kind, ep).first;
+    EventPair& ep = ctx->timers[kind];
+    if (ep.start.ensure(hipEventDefault) != hipSuccess || ep.stop.ensure(hipEventDefault) != hipSuccess) {
+        ctx->timers.erase(kind);
+        return nullptr;
     }
-    return &it->second;
+    return &ep;
 }
 
 int vstab_timer_fold(EventPair* ev)
@@ -83,10 +103,11 @@ int vstab_timer_fold(EventPair* ev)
 
 int vstab_check_device_status(vstab_ctx* ctx, const char* who)
 {
-    if (!ctx || !ctx->h_status) return 0;
-    const int word = *ctx->h_status;
+    volatile int* status = ctx ? ctx->status.host<volatile int>() : nullptr;
+    if (!status) return 0;
+    const int word = *status;
     if (word == 0) return 0;
-    *ctx->h_status = 0;
+    *status = 0;
     if (word & VSTAB_STATUS_PIS_TIMEOUT)
         vstab_set_error("%s: the DIS patch inverse search reported an expired dependency wait (status 0x%x): a wave did not see "
                         "its neighbour row's progress counter advance within the spin bound, the flow of this call is invalid",
@@ -96,8 +117,16 @@ int vstab_check_device_status(vstab_ctx* ctx, const char* who)
     return 3;
 }
 
-// vstab_tvl1.hip: frees the TV-L1 workspace and host mirror of a context
-void vstab_tvl1_release(vstab_ctx* ctx);
+// vstab_create behind its argument checks, the device set: on failure the caller deletes the context
+static int ctx_init(vstab_ctx* ctx)
+{
+    ctx->h_params.pinned_host = true;
+    ctx->h_fit.pinned_host = true;
+    ctx->h_xfer.pinned_host = true;
+    VSTAB_HIP(ctx->ev_params_free.ensure());
+    VSTAB_HIP(hipEventRecord(ctx->ev_params_free, nullptr));
+    return ctx->status.reserve(64, nullptr);
+}
 
 extern "C" {
 
@@ -125,19 +154,9 @@ int vstab_create(vstab_ctx** out, int device)
     VSTAB_HIP(hipSetDevice(device));
     vstab_ctx* ctx = new vstab_ctx();
     ctx->device = device;
-    ctx->h_params.pinned_host = true;
-    ctx->h_fit.pinned_host = true;
-    ctx->h_xfer.pinned_host = true;
-    VSTAB_HIP(hipEventCreateWithFlags(&ctx->ev_params_free, hipEventDisableTiming));
-    VSTAB_HIP(hipEventRecord(ctx->ev_params_free, nullptr));
-    {
-        void* h = nullptr;
-        VSTAB_HIP(hipHostMalloc(&h, 64, hipHostMallocMapped | hipHostMallocCoherent));
-        memset(h, 0, 64);
-        void* d = nullptr;
-        VSTAB_HIP(hipHostGetDevicePointer(&d, h, 0));
-        ctx->h_status = static_cast<volatile int*>(h);
-        ctx->d_status = static_cast<int*>(d);
+    if (int rc = ctx_init(ctx)) {
+        delete ctx;
+        return rc;
     }
     *out = ctx;
     return 0;
@@ -148,37 +167,9 @@ int vstab_destroy(vstab_ctx* ctx)
     if (!ctx) return 0;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    ctx->h_params.release();
-    ctx->d_params.release();
-    ctx->d_dis.release();
-    vstab_tvl1_release(ctx);
-    ctx->d_fit.release();
-    ctx->h_fit.release();
-    ctx->d_gray_tmp.release();
-    ctx->d_range.release();
-    ctx->d_mask_rows.release();
-    ctx->d_sfill.release();
-    ctx->d_plan.release();
-    ctx->h_plan.release();
-    if (ctx->h_peaks) (void)hipHostFree(ctx->h_peaks);
-    if (ctx->d_peaks_count) (void)hipFree(ctx->d_peaks_count);
-    if (ctx->h_counts) (void)hipHostFree(ctx->h_counts);
-    if (ctx->ev_fit_done) (void)hipEventDestroy(ctx->ev_fit_done);
-    if (ctx->ev_plan_done) (void)hipEventDestroy(ctx->ev_plan_done);
-    if (ctx->side_stream) { (void)hipStreamSynchronize(ctx->side_stream); (void)hipStreamDestroy(ctx->side_stream); }
-    if (ctx->ev_side) (void)hipEventDestroy(ctx->ev_side);
-    for (auto& kv : ctx->timers) { (void)hipEventDestroy(kv.second.start); (void)hipEventDestroy(kv.second.stop); }
-    (void)hipEventDestroy(ctx->ev_params_free);
-    if (ctx->h_status) (void)hipHostFree(const_cast<int*>(ctx->h_status));
-    if (ctx->xfer_stream) { (void)hipStreamSynchronize(ctx->xfer_stream); (void)hipStreamDestroy(ctx->xfer_stream); }
-    for (auto& ev : ctx->ev_xfer) if (ev) (void)hipEventDestroy(ev);
-    if (ctx->ev_xfer_sync) (void)hipEventDestroy(ctx->ev_xfer_sync);
-    ctx->h_xfer.release();
-    ctx->d_xfer.release();
-    if (ctx->prep_stream) { (void)hipStreamSynchronize(ctx->prep_stream); (void)hipStreamDestroy(ctx->prep_stream); }
-    for (auto& ev : ctx->ev_prep) if (ev) (void)hipEventDestroy(ev);
-    if (ctx->ev_pyramid) (void)hipEventDestroy(ctx->ev_pyramid);
-    delete ctx;
+    for (hipStream_t st : {ctx->side_stream.st, ctx->xfer_stream.st, ctx->prep_stream.st})
+        if (st) (void)hipStreamSynchronize(st);
+    delete ctx;   // every member releases what it holds
     return 0;
 }
 

@@ -1634,15 +1634,13 @@ static int dis_run(vstab_ctx* ctx, const uint8_t* gray, int n, int h, int w, int
     static_assert(sizeof(ctx->ev_prep) / sizeof(ctx->ev_prep[0]) >= MAX_LEVELS, "one event per pyramid level");
     hipStream_t ps = st;
     if (two_streams) {
-        if (!ctx->prep_stream) {
-            VSTAB_HIP(hipStreamCreateWithFlags(&ctx->prep_stream, hipStreamNonBlocking));
-            VSTAB_HIP(hipEventCreateWithFlags(&ctx->ev_pyramid, hipEventDisableTiming));
-            for (auto& ev : ctx->ev_prep) VSTAB_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        }
+        VSTAB_HIP(ctx->prep_stream.ensure());
+        VSTAB_HIP(ctx->ev_pyramid.ensure());
+        for (auto& ev : ctx->ev_prep) VSTAB_HIP(ev.ensure());
         ps = ctx->prep_stream;
     }
     // (set_timing level 2 only: events around the stages of this call, vstab_internal.h)
-    auto prep_timer = std::make_unique<DetailTimer>(ctx, "dis_prep");
+    auto prep_timer = std::make_unique<KernelTimer>(ctx, "dis_prep", KernelTimer::DETAIL);
     bool coarsest_prepared = false;   // pyramid_tail_kernel also formed the coarsest level's padded copy, gradients and tensor
     {
         if (launch_area(st, gray, I[FINEST], n, h, w, G[FINEST].h, G[FINEST].w)) return 1;
@@ -1735,14 +1733,14 @@ static int dis_run(vstab_ctx* ctx, const uint8_t* gray, int n, int h, int w, int
 #ifdef VSTAB_TEST_HOOKS   // fault injector of the test build (lib/libvstab_hooks.so): 0 forces the timeout report
         if (const char* e = getenv("VSTAB_DEBUG_PIS_SPIN_LIMIT")) pa.spin_limit = atoi(e);
 #endif
-        pa.status = ctx->d_status;
+        pa.status = ctx->status.dev<int>();
         if (two_streams && i != coarsest) VSTAB_HIP(hipStreamWaitEvent(st, ctx->ev_prep[i], 0));   // this level's padded image, gradients, tensor
         const size_t lds_bytes = (((size_t)(g.w + 32) * (g.h + 32) + 15) & ~size_t(15)) + sizeof(float) * 2 * (size_t)g.hs * g.ws + sizeof(int) * 2 * (size_t)g.hs;
         VSTAB_REQUIRE(lds_bytes <= 160 * 1024, "vstab_dis_flow_batch: level %dx%d needs %zu B of LDS (> 160 KB)", g.w, g.h, lds_bytes);
         char kind_pis[24], kind_level[24];
         snprintf(kind_pis, sizeof(kind_pis), "dis_pis4_L%d", i);
         snprintf(kind_level, sizeof(kind_level), "dis_level_L%d", i);
-        auto stage_timer = std::make_unique<DetailTimer>(ctx, kind_pis);
+        auto stage_timer = std::make_unique<KernelTimer>(ctx, kind_pis, KernelTimer::DETAIL);
         // one wavefront per stripe walks its rows in groups of four; two share the groups where a stripe has more rows
         if (pa.stripe_sz > 4) {
             if (lds_bytes > 64 * 1024)
@@ -1754,7 +1752,7 @@ static int dis_run(vstab_ctx* ctx, const uint8_t* gray, int n, int h, int w, int
             hipLaunchKernelGGL(pis4_kernel<1>, dim3((unsigned)P * 2), dim3(64 * PIS_STRIPES_PER_BLOCK), lds_bytes, st, pa);
         }
         stage_timer.reset();
-        stage_timer = std::make_unique<DetailTimer>(ctx, kind_level);
+        stage_timer = std::make_unique<KernelTimer>(ctx, kind_level, KernelTimer::DETAIL);
         LevelArgs la{};
 #ifdef VSTAB_FUSED_TRACE
         la.dbg = g_dis_dbg ? g_dis_dbg + 16 * i : nullptr;
@@ -1827,7 +1825,7 @@ static int dis_run(vstab_ctx* ctx, const uint8_t* gray, int n, int h, int w, int
         VSTAB_HIP(hipGetLastError());
         stage_timer.reset();
     }
-    DetailTimer final_timer(ctx, "dis_final");
+    KernelTimer final_timer(ctx, "dis_final", KernelTimer::DETAIL);
     const double fsx = 1. / ((double)w / F.w), fsy = 1. / ((double)h / F.h);
     const float mul = (float)(1 << FINEST);
     if (grid_flow && !grid_fused) {

@@ -465,7 +465,7 @@ static int run_fit(vstab_ctx* ctx, const float* data, const int* counts, int pai
         // the records' download is NOT queued here: a copy on this stream would sit between the fit kernel and whatever the
         // caller queues next (the plan kernel, the warp).  vstab_flow_plan_device issues it on the side stream behind the plan
         // kernel; vstab_sample_fit_batch_end issues it itself if nobody has by then.
-        if (!ctx->ev_fit_done) VSTAB_HIP(hipEventCreateWithFlags(&ctx->ev_fit_done, hipEventDisableTiming));
+        VSTAB_HIP(ctx->ev_fit_done.ensure());
         ctx->fit_pairs_pending = pairs;
         ctx->fit_copy_bytes = rec_bytes;
         return 0;

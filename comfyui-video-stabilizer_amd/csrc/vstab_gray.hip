@@ -9,6 +9,7 @@
 // fma(b, 0.114, fma(g, 0.587, r*0.299)) and an unfused scalar tail for the last (w % 8) pixels
 // of a row; then v = gray*255 (f32), clip to [0,255], truncate.
 #include "vstab_internal.h"
+#include "vstab_wait.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -396,23 +397,15 @@ static int gray_run(vstab_ctx* ctx, const float* frames, int n, int src_h, int s
 #undef LAUNCH_GRAY
     if (frame_max) {
         // the host's copy of the maxima: written by the kernel itself into coherent host memory (no copy, no event on the stream)
-        if (ctx->h_peaks_cap < n) {
-            if (ctx->h_peaks) { VSTAB_HIP(hipStreamSynchronize(st)); VSTAB_HIP(hipHostFree(ctx->h_peaks)); ctx->h_peaks = nullptr; ctx->h_peaks_cap = 0; }
-            const int cap = std::max(1024, n);
-            void* hp = nullptr;
-            VSTAB_HIP(hipHostMalloc(&hp, sizeof(float) * (size_t)cap, hipHostMallocMapped | hipHostMallocCoherent));
-            void* dp = nullptr;
-            VSTAB_HIP(hipHostGetDevicePointer(&dp, hp, 0));
-            ctx->h_peaks = static_cast<float*>(hp); ctx->d_peaks_mirror = static_cast<float*>(dp); ctx->h_peaks_cap = cap;
-        }
-        if (!ctx->d_peaks_count) {   // the device-side count of finished frames (never reset: passes are told their target)
-            VSTAB_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_peaks_count), 256));
-            VSTAB_HIP(hipMemsetAsync(ctx->d_peaks_count, 0, 256, st));
+        if (ctx->peaks.reserve(sizeof(float) * (size_t)std::max(1024, n), st)) return 1;
+        if (!ctx->d_peaks_count.ptr) {   // the device-side count of finished frames (never reset: passes are told their target)
+            if (ctx->d_peaks_count.reserve(256)) return 1;
+            VSTAB_HIP(hipMemsetAsync(ctx->d_peaks_count.ptr, 0, ctx->d_peaks_count.bytes, st));
         }
         ctx->peaks_target += (unsigned)n;
         ctx->peaks_frames = n;
-        hipLaunchKernelGGL(frame_max_kernel, dim3((unsigned)n), dim3(256), 0, st, row_max, frame_max, range_rows, ctx->d_peaks_mirror,
-                           reinterpret_cast<unsigned*>(ctx->d_status) + VSTAB_PEAKS_DONE_WORD, ctx->d_peaks_count, ctx->peaks_target);
+        hipLaunchKernelGGL(frame_max_kernel, dim3((unsigned)n), dim3(256), 0, st, row_max, frame_max, range_rows, ctx->peaks.dev<float>(),
+                           ctx->status.dev<unsigned>() + VSTAB_PEAKS_DONE_WORD, static_cast<unsigned*>(ctx->d_peaks_count.ptr), ctx->peaks_target);
         VSTAB_HIP(hipGetLastError());
     }
     return 0;
@@ -448,21 +441,17 @@ extern "C" int vstab_gray_downscale_range(vstab_ctx* ctx, const float* frames, i
 extern "C" int vstab_last_frame_peaks(vstab_ctx* ctx, int n, float* out)
 {
     VSTAB_REQUIRE(ctx != nullptr && out != nullptr, "vstab_last_frame_peaks: NULL argument");
-    VSTAB_REQUIRE(ctx->h_peaks != nullptr && n == ctx->peaks_frames, "vstab_last_frame_peaks: no range pass over %d frames is pending", n);
-    volatile unsigned* done = reinterpret_cast<volatile unsigned*>(ctx->h_status) + VSTAB_PEAKS_DONE_WORD;
+    VSTAB_REQUIRE(ctx->peaks.bytes != 0 && n == ctx->peaks_frames, "vstab_last_frame_peaks: no range pass over %d frames is pending", n);
+    volatile unsigned* done = ctx->status.host<volatile unsigned>() + VSTAB_PEAKS_DONE_WORD;
     const unsigned target = ctx->peaks_target;
+    auto reached = [=] { return vstab_seq_reached(*done, target); };
     // the gray pass of a 256 x 1080p clip takes ~1 ms; should the count never arrive (a lost launch), a stream
-    // synchronisation after ~2 s turns the wait into the runtime's own error report
-    for (long spins = 0; (int)(*done - target) < 0; spins++) {
-        if (spins > 20000000L) {
-            VSTAB_HIP(hipStreamSynchronize(ctx->stream));
-            VSTAB_REQUIRE((int)(*done - target) >= 0, "vstab_last_frame_peaks: the range pass finished without reporting its %d frames", n);
-            break;
-        }
-        __builtin_ia32_pause();
+    // synchronisation after 2 s turns the wait into the runtime's own error report
+    if (!vstab_spin_until(reached, std::chrono::seconds(2))) {
+        VSTAB_HIP(hipStreamSynchronize(ctx->stream));
+        VSTAB_REQUIRE(reached(), "vstab_last_frame_peaks: the range pass finished without reporting its %d frames", n);
     }
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    memcpy(out, ctx->h_peaks, sizeof(float) * (size_t)n);
+    memcpy(out, ctx->peaks.host<float>(), sizeof(float) * (size_t)n);
     return 0;
 }
 

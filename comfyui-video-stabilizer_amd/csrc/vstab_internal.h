@@ -29,20 +29,63 @@ void vstab_set_error(const char* fmt, ...);
         }                                                                                \
     } while (0)
 
+// What the context holds releases itself with it; none of these is copied.
+struct NoCopy {
+    NoCopy() = default;
+    NoCopy(const NoCopy&) = delete;
+    NoCopy& operator=(const NoCopy&) = delete;
+};
+
 // A grow-only device/pinned-host scratch buffer.
-struct ScratchBuf {
+struct ScratchBuf : NoCopy {
     void* ptr = nullptr;
     size_t bytes = 0;
     bool pinned_host = false;
+    ~ScratchBuf() { release(); }
     int reserve(size_t need);
     void release();
 };
 
+// Coherent, device-mapped host memory, zero-filled: a kernel writes through dev<T>() what the host reads through
+// host<T>(), with no copy on the stream.
+struct MappedBuf : NoCopy {
+    size_t bytes = 0;
+    ~MappedBuf();
+    // No-op if `need` bytes are there; else drains `stream` (a queued kernel may still write into the old block) and reallocates.
+    int reserve(size_t need, hipStream_t stream);
+    template <class T> T* host() const { return static_cast<T*>(h); }
+    template <class T> T* dev() const { return static_cast<T*>(d); }
+private:
+    void *h = nullptr, *d = nullptr;
+};
+
+// An event (timing disabled unless asked otherwise) / a non-blocking stream, created by the first ensure().
+struct LazyEvent : NoCopy {
+    hipEvent_t ev = nullptr;
+    ~LazyEvent() { if (ev) (void)hipEventDestroy(ev); }
+    hipError_t ensure(unsigned flags = hipEventDisableTiming) { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, flags); }
+    operator hipEvent_t() const { return ev; }
+};
+struct LazyStream : NoCopy {
+    hipStream_t st = nullptr;
+    ~LazyStream() { if (st) (void)hipStreamDestroy(st); }
+    hipError_t ensure() { return st ? hipSuccess : hipStreamCreateWithFlags(&st, hipStreamNonBlocking); }
+    operator hipStream_t() const { return st; }
+};
+
 struct EventPair {
-    hipEvent_t start = nullptr, stop = nullptr;
+    LazyEvent start, stop;
     bool pending = false;        // a start/stop pair has been recorded and not yet folded into the totals
     double total_ms = 0.0;       // folded launches since vstab_set_timing(ctx, 1)
     int launches = 0;
+};
+
+// TV-L1 (vstab_tvl1.hip): the grow-only workspace, and one 64-bit word of coherent host memory that the inner kernel's
+// last workgroup writes, (launch number << 32) | active pairs; gen numbers the inner launches.
+struct TvState {
+    ScratchBuf work;
+    MappedBuf word;
+    unsigned gen = 0;
 };
 // Folds a finished, still pending measurement into the totals (blocks until the stop event has passed).
 int vstab_timer_fold(EventPair* ev);
@@ -57,42 +100,41 @@ struct vstab_ctx {
     std::map<std::string, EventPair> timers;
     // staging for small per-call parameter tables (pinned host + device mirror)
     ScratchBuf h_params, d_params;
-    hipEvent_t ev_params_free = nullptr;  // recorded after the H2D copy of h_params
+    LazyEvent ev_params_free;  // recorded after the H2D copy of h_params
     // DIS / fit workspaces (grow-only)
     ScratchBuf d_dis, d_fit, h_fit, d_gray_tmp, d_range;
     ScratchBuf d_mask_rows;   // estimation mask: the dilated rows between the two kernels of vstab_mask_block_grid
     ScratchBuf d_sfill;       // spatial fill: the pyramid records of one chunk of frames and their per-frame words (vstab_fill.hip)
+    TvState tvl1;
     // Device-side failure reports: one host-resident word (coherent, device-mapped).  A kernel ORs a VSTAB_STATUS_*
-    // bit into it through d_status; the host reads h_status after any stream synchronisation at no cost.
-    volatile int* h_status = nullptr;
-    int* d_status = nullptr;
+    // bit into word [0] through its device pointer; the host reads it after any stream synchronisation at no cost.
+    // (The words behind it: VSTAB_PEAKS_DONE_WORD and the others below.)
+    MappedBuf status;
     // F0's per-frame maxima as the gray pass reports them, mirrored into coherent host memory by the kernel that forms them
     // (frame_max_kernel) -- no copy and no event on the stream (those cost the stream ~25 us between the gray pass and the
     // pyramid, profiles/r05_dis_small_steps.md).  peaks_target counts the frames of all range passes since the context was created; the pass
-    // that completes it writes that number into h_status[VSTAB_PEAKS_DONE_WORD] behind the values (vstab_last_frame_peaks polls it).
-    float* h_peaks = nullptr;       // host pointer
-    float* d_peaks_mirror = nullptr;   // the same memory as the device sees it
-    int h_peaks_cap = 0, peaks_frames = 0;
+    // that completes it writes that number into status[VSTAB_PEAKS_DONE_WORD] behind the values (vstab_last_frame_peaks polls it).
+    MappedBuf peaks;
+    int peaks_frames = 0;
     unsigned peaks_target = 0;
-    unsigned* d_peaks_count = nullptr;   // device memory: frames finished since the context was created
+    ScratchBuf d_peaks_count;   // device memory: frames finished since the context was created
     // The plain warp's per-frame padded-pixel counts reach the host the same way: a one-workgroup kernel behind the warp
-    // copies them into coherent host memory and sets h_status[VSTAB_COUNTS_DONE_WORD] to the call's generation number, which
+    // copies them into coherent host memory and sets status[VSTAB_COUNTS_DONE_WORD] to the call's generation number, which
     // vstab_last_pad_counts polls -- the step's last host wait costs the flag's round trip instead of a copy + a stream
     // synchronisation (~30 us of GPU idle between two steps).
-    unsigned* h_counts = nullptr;
-    unsigned* d_counts_mirror = nullptr;
-    int h_counts_cap = 0, counts_n = 0;
+    MappedBuf counts;
+    int counts_n = 0;
     unsigned counts_gen = 0;
     // bulk host <-> device transfers (vstab_xfer.hip): pinned ring, its events, a copy stream
     ScratchBuf h_xfer;
     ScratchBuf d_xfer;   // device side of the coded forms: landing slots of byte-coded upload chunks / the packed mask
-    hipEvent_t ev_xfer[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_xfer_sync = nullptr;
-    hipStream_t xfer_stream = nullptr;
+    LazyEvent ev_xfer[4];
+    LazyEvent ev_xfer_sync;
+    LazyStream xfer_stream;
     // speculative device-side plan (vstab_plan.hip): the plan's outputs on the device (final float32 matrices, warp
     // table, path / target) and their pinned host copy, an event behind each asynchronous download
     ScratchBuf d_plan, h_plan;
-    hipEvent_t ev_fit_done = nullptr, ev_plan_done = nullptr;
+    LazyEvent ev_fit_done, ev_plan_done;
     int fit_pairs_pending = 0, plan_frames = 0, plan_params = 0;
     // The downloads behind the speculative plan (fit records, plan results) run on a stream of their own, behind ONE event
     // recorded after plan_kernel: a copy queued on the call's stream sat between fit -> plan -> warp as two engine hand-overs
@@ -102,17 +144,17 @@ struct vstab_ctx {
     unsigned* plan_zero_ptr = nullptr;     // registered for the next plan kernel to zero (vstab_flow_plan_zero_counts)
     int plan_zero_n = 0;
     unsigned* plan_zeroed_ptr = nullptr;   // what the last plan kernel zeroed: the planned warp skips its own fill for it
-    hipStream_t side_stream = nullptr;
-    hipEvent_t ev_side = nullptr;
+    LazyStream side_stream;
+    LazyEvent ev_side;
     size_t fit_copy_bytes = 0;
     // DIS: the per-level image preparation (pad, gradients, structure tensor) runs on its own stream beside the
     // coarse-to-fine chain, one event per pyramid level (vstab_dis.hip)
-    hipStream_t prep_stream = nullptr;
-    hipEvent_t ev_prep[16] = {};   // MAX_LEVELS of vstab_dis.hip
-    hipEvent_t ev_pyramid = nullptr;
+    LazyStream prep_stream;
+    LazyEvent ev_prep[16];   // MAX_LEVELS of vstab_dis.hip
+    LazyEvent ev_pyramid;
 };
 
-enum { VSTAB_PEAKS_DONE_WORD = 4, VSTAB_COUNTS_DONE_WORD = 5, VSTAB_XFER_OTHER_WORD = 6 };      // index into h_status / d_status (the status word itself is [0])
+enum { VSTAB_PEAKS_DONE_WORD = 4, VSTAB_COUNTS_DONE_WORD = 5, VSTAB_XFER_OTHER_WORD = 6 };      // index into ctx->status (the status word itself is [0])
 enum { VSTAB_STATUS_PIS_TIMEOUT = 1 };   // DIS patch search: a bounded intra-workgroup dependency wait expired
 
 // Call after a host synchronisation of ctx->stream: turns a device-side failure report into a non-zero return
@@ -126,13 +168,17 @@ int vstab_stage_params(vstab_ctx* ctx, const void* host, size_t bytes, void** de
 // sync here: vstab_last_kernel_ms waits for the stop event when the number is asked for).
 EventPair* vstab_timer_slot(vstab_ctx* ctx, const char* kind);
 
+// DETAIL: the same around one stage inside a call, only under vstab_set_timing(ctx, 2): the events sit between dependent
+// kernels, where they lengthen the chain a little, and a kind used twice in one call folds (waits for) its previous
+// measurement -- for a measurement pass of its own, never inside a timed loop.
 struct KernelTimer {
+    enum Scope { CALL, DETAIL };
     vstab_ctx* ctx;
     EventPair* ev = nullptr;
-    KernelTimer(vstab_ctx* c, const char* k) : ctx(c) {
+    KernelTimer(vstab_ctx* c, const char* k, Scope scope = CALL) : ctx(c) {
         // (level 3: an event pair costs the stream ~10 us -- 0.05-0.1 ms over the four stages of a C2 step, measured -- so a
         // timed loop keeps them around the one kernel whose per-launch time it reports, profiles/r05_dis_small_steps.md)
-        if (ctx->timing && (!ctx->timing_warp_only || strncmp(k, "warp", 4) == 0)) {
+        if (ctx->timing && (scope == DETAIL ? ctx->timing_detail : (!ctx->timing_warp_only || strncmp(k, "warp", 4) == 0))) {
             ev = vstab_timer_slot(ctx, k);
             // the previous launch of this kind finished long ago (every pipeline pass synchronises with the host
             // between two launches of the same kind), so folding it costs no wait
@@ -141,27 +187,6 @@ struct KernelTimer {
         }
     }
     ~KernelTimer() {
-        if (ev) {
-            (void)hipEventRecord(ev->stop, ctx->stream);
-            ev->pending = true;
-        }
-    }
-};
-
-// The same around one stage inside a call, only under vstab_set_timing(ctx, 2): the events sit between dependent kernels,
-// where they lengthen the chain a little, and a kind used twice in one call folds (waits for) its previous measurement --
-// for a measurement pass of its own, never inside a timed loop.
-struct DetailTimer {
-    vstab_ctx* ctx;
-    EventPair* ev = nullptr;
-    DetailTimer(vstab_ctx* c, const char* k) : ctx(c) {
-        if (ctx->timing && ctx->timing_detail) {
-            ev = vstab_timer_slot(ctx, k);
-            if (ev && ev->pending) (void)vstab_timer_fold(ev);
-            if (ev) (void)hipEventRecord(ev->start, ctx->stream);
-        }
-    }
-    ~DetailTimer() {
         if (ev) {
             (void)hipEventRecord(ev->stop, ctx->stream);
             ev->pending = true;

@@ -23,26 +23,13 @@
 // Algorithmic traffic of one inner iteration: read u1 u2 (8 B), p11 p12 p21 p22 (16 B), I1wx I1wy grad rho_c (16 B),
 // write u1 u2 p11 p12 p21 p22 (24 B): 64 B per pixel.
 #include "vstab_internal.h"
+#include "vstab_wait.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <map>
 #include <memory>
-#include <mutex>
 
 namespace {
-
-// Per-context TV-L1 state, kept beside vstab_ctx: the grow-only workspace, and one 64-bit word of coherent host memory
-// that the inner kernel's last workgroup writes, (launch number << 32) | active pairs; gen numbers the inner launches.
-struct TvState {
-    ScratchBuf work;
-    unsigned long long* h_mirror = nullptr;
-    unsigned long long* d_mirror = nullptr;
-    unsigned gen = 0;
-};
-std::mutex g_tv_mu;
-std::map<const vstab_ctx*, TvState> g_tv;
 
 // initInterTab1D(INTER_CUBIC): A = -0.75, x = i/32, same operation order as OpenCV's interpolateCubic (the same
 // table as cubic_coeffs of vstab_warp.hip)
@@ -500,25 +487,17 @@ void tvl1_layout(TCarver& c, TvWork& k, const TLevel* L, int ns, int P)
 // Waits (bounded) until the inner launch numbered `target` has mirrored its count; returns the count it reports.
 int tvl1_poll(vstab_ctx* ctx, TvState& tv, unsigned target, unsigned* n_active)
 {
-    volatile unsigned long long* word = tv.h_mirror;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (long spins = 0;; spins++) {
-        const unsigned long long v = *word;
-        if ((int)((unsigned)(v >> 32) - target) >= 0) {
-            *n_active = (unsigned)(v & 0xffffffffu);
-            return 0;
-        }
-        // an inner launch of a 960x540 chunk takes a few ms; should the word never arrive (a lost launch), a stream
-        // synchronisation after ~2 s turns the wait into the runtime's own error report
-        if ((spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-            VSTAB_HIP(hipStreamSynchronize(ctx->stream));
-            const unsigned long long v2 = *word;
-            VSTAB_REQUIRE((int)((unsigned)(v2 >> 32) - target) >= 0, "vstab_tvl1_flow_batch: inner launch %u never reported", target);
-            *n_active = (unsigned)(v2 & 0xffffffffu);
-            return 0;
-        }
-        __builtin_ia32_pause();
+    volatile unsigned long long* word = tv.word.host<volatile unsigned long long>();
+    unsigned long long v = 0;
+    auto reached = [&] { v = *word; return vstab_seq_reached((unsigned)(v >> 32), target); };
+    // an inner launch of a 960x540 chunk takes a few ms; should the word never arrive (a lost launch), a stream
+    // synchronisation after 2 s turns the wait into the runtime's own error report
+    if (!vstab_spin_until(reached, std::chrono::seconds(2))) {
+        VSTAB_HIP(hipStreamSynchronize(ctx->stream));
+        VSTAB_REQUIRE(reached(), "vstab_tvl1_flow_batch: inner launch %u never reported", target);
     }
+    *n_active = (unsigned)(v & 0xffffffffu);
+    return 0;
 }
 
 int tvl1_chunk(vstab_ctx* ctx, TvState& tv, const uint8_t* gray, int P, const TLevel* L, int ns, const vstab_tvl1_params& prm, float* flow,
@@ -561,7 +540,7 @@ int tvl1_chunk(vstab_ctx* ctx, TvState& tv, const uint8_t* gray, int P, const TL
         InnerArgs ia{};
         ia.U = k.U[s]; ia.Pd = k.Pd; ia.W = k.W; ia.M = k.M; ia.rowsum = k.rowsum; ia.active = k.active; ia.cur = k.cur;
         ia.ticket = k.ticket;
-        ia.mirror = tv.d_mirror;
+        ia.mirror = tv.word.dev<unsigned long long>();
         ia.P = P; ia.h = h; ia.w = w; ia.L = pow2_at_least(w); ia.HL = pow2_at_least(h);
         ia.l_t = l_t; ia.taut = taut; ia.theta = theta;
         ia.eps = (float)(prm.epsilon * prm.epsilon * (double)((long long)h * w));
@@ -620,16 +599,6 @@ int tvl1_chunk(vstab_ctx* ctx, TvState& tv, const uint8_t* gray, int P, const TL
 
 }  // namespace
 
-void vstab_tvl1_release(vstab_ctx* ctx)
-{
-    std::lock_guard<std::mutex> lock(g_tv_mu);
-    auto it = g_tv.find(ctx);
-    if (it == g_tv.end()) return;
-    it->second.work.release();
-    if (it->second.h_mirror) (void)hipHostFree(it->second.h_mirror);
-    g_tv.erase(it);
-}
-
 extern "C" void vstab_tvl1_default_params(vstab_tvl1_params* p)
 {
     if (!p) return;
@@ -683,22 +652,8 @@ extern "C" int vstab_tvl1_flow_batch(vstab_ctx* ctx, const uint8_t* gray, int n,
         L[ns++] = {nh, nw};
     }
     VSTAB_HIP(hipSetDevice(ctx->device));
-    TvState* tvp;
-    {
-        std::lock_guard<std::mutex> lock(g_tv_mu);
-        tvp = &g_tv[ctx];   // std::map: the element stays where it is while others are added
-    }
-    TvState& tv = *tvp;
-    if (!tv.h_mirror) {
-        void* hp = nullptr;
-        void* dp = nullptr;
-        VSTAB_HIP(hipHostMalloc(&hp, 64, hipHostMallocMapped | hipHostMallocCoherent));
-        memset(hp, 0, 64);
-        VSTAB_HIP(hipHostGetDevicePointer(&dp, hp, 0));
-        tv.h_mirror = static_cast<unsigned long long*>(hp);
-        tv.d_mirror = static_cast<unsigned long long*>(dp);
-        tv.gen = 0;
-    }
+    TvState& tv = ctx->tvl1;
+    if (tv.word.reserve(64, ctx->stream)) return 1;
     KernelTimer timer(ctx, "tvl1");
     const int pairs = n - 1;
     if (iterations) VSTAB_HIP(hipMemsetAsync(iterations, 0, sizeof(int32_t) * (size_t)pairs * prm.nscales * prm.warps, ctx->stream));

@@ -19,6 +19,7 @@
 //   * blockIdx is remapped so that the 8 XCDs (private L2 each) own contiguous runs of tiles
 //   * padding-pixel count: wave shuffle reduction -> LDS -> one atomic per block, only if non-zero
 #include "vstab_internal.h"
+#include "vstab_wait.h"
 #include <type_traits>
 #include <cstdlib>
 #include <cmath>
@@ -1221,19 +1222,11 @@ __global__ __launch_bounds__(256) void mirror_counts_kernel(const uint32_t* __re
 
 int mirror_counts(vstab_ctx* ctx, const uint32_t* pad_count, int n)
 {
-    if (ctx->h_counts_cap < n) {
-        if (ctx->h_counts) { VSTAB_HIP(hipStreamSynchronize(ctx->stream)); VSTAB_HIP(hipHostFree(ctx->h_counts)); ctx->h_counts = nullptr; ctx->h_counts_cap = 0; }
-        const int cap = n > 4096 ? n : 4096;
-        void* hp = nullptr;
-        VSTAB_HIP(hipHostMalloc(&hp, sizeof(unsigned) * (size_t)cap, hipHostMallocMapped | hipHostMallocCoherent));
-        void* dp = nullptr;
-        VSTAB_HIP(hipHostGetDevicePointer(&dp, hp, 0));
-        ctx->h_counts = static_cast<unsigned*>(hp); ctx->d_counts_mirror = static_cast<unsigned*>(dp); ctx->h_counts_cap = cap;
-    }
+    if (ctx->counts.reserve(sizeof(unsigned) * (size_t)(n > 4096 ? n : 4096), ctx->stream)) return 1;
     ctx->counts_gen += 1;
     ctx->counts_n = n;
-    hipLaunchKernelGGL(mirror_counts_kernel, dim3(1), dim3(256), 0, ctx->stream, pad_count, ctx->d_counts_mirror, n,
-                       reinterpret_cast<unsigned*>(ctx->d_status) + VSTAB_COUNTS_DONE_WORD, ctx->counts_gen);
+    hipLaunchKernelGGL(mirror_counts_kernel, dim3(1), dim3(256), 0, ctx->stream, pad_count, ctx->counts.dev<unsigned>(), n,
+                       ctx->status.dev<unsigned>() + VSTAB_COUNTS_DONE_WORD, ctx->counts_gen);
     VSTAB_HIP(hipGetLastError());
     return 0;
 }
@@ -1244,19 +1237,16 @@ int mirror_counts(vstab_ctx* ctx, const uint32_t* pad_count, int n)
 extern "C" int vstab_last_pad_counts(vstab_ctx* ctx, int n, uint32_t* out)
 {
     VSTAB_REQUIRE(ctx != nullptr && out != nullptr, "vstab_last_pad_counts: NULL argument");
-    VSTAB_REQUIRE(ctx->h_counts != nullptr && n == ctx->counts_n, "vstab_last_pad_counts: no warp with counts over %d frames is pending", n);
-    volatile unsigned* done = reinterpret_cast<volatile unsigned*>(ctx->h_status) + VSTAB_COUNTS_DONE_WORD;
+    VSTAB_REQUIRE(ctx->counts.bytes != 0 && n == ctx->counts_n, "vstab_last_pad_counts: no warp with counts over %d frames is pending", n);
+    volatile unsigned* done = ctx->status.host<volatile unsigned>() + VSTAB_COUNTS_DONE_WORD;
     const unsigned gen = ctx->counts_gen;
-    for (long spins = 0; *done != gen; spins++) {
-        if (spins > 200000000L) {   // ~10 s: a warp of a long 4K clip takes tens of milliseconds; then the runtime's own report
-            VSTAB_HIP(hipStreamSynchronize(ctx->stream));
-            VSTAB_REQUIRE(*done == gen, "vstab_last_pad_counts: the warp finished without reporting its counts");
-            break;
-        }
-        __builtin_ia32_pause();
+    auto reached = [=] { return *done == gen; };
+    // 10 s: a warp of a long 4K clip takes tens of milliseconds; then the runtime's own report
+    if (!vstab_spin_until(reached, std::chrono::seconds(10))) {
+        VSTAB_HIP(hipStreamSynchronize(ctx->stream));
+        VSTAB_REQUIRE(reached(), "vstab_last_pad_counts: the warp finished without reporting its counts");
     }
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    memcpy(out, ctx->h_counts, sizeof(uint32_t) * (size_t)n);
+    memcpy(out, ctx->counts.host<uint32_t>(), sizeof(uint32_t) * (size_t)n);
     return 0;
 }
 

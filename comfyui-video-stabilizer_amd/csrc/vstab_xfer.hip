@@ -130,10 +130,10 @@ int ring_get(vstab_ctx* ctx, Ring& r)
     if (ctx->h_xfer.reserve(CHUNK * SLOTS)) return 1;
     for (int i = 0; i < SLOTS; i++) {
         r.slot[i] = static_cast<char*>(ctx->h_xfer.ptr) + CHUNK * i;
-        if (!ctx->ev_xfer[i]) VSTAB_HIP(hipEventCreateWithFlags(&ctx->ev_xfer[i], hipEventDisableTiming));
+        VSTAB_HIP(ctx->ev_xfer[i].ensure());
         r.done[i] = ctx->ev_xfer[i];
     }
-    if (!ctx->xfer_stream) VSTAB_HIP(hipStreamCreateWithFlags(&ctx->xfer_stream, hipStreamNonBlocking));
+    VSTAB_HIP(ctx->xfer_stream.ensure());
     return 0;
 }
 
@@ -150,7 +150,7 @@ extern "C" int vstab_upload(vstab_ctx* ctx, const void* host_src, void* dev_dst,
     // dev_dst may be a block the caller's allocator handed back while its previous user is still queued on the
     // context's stream (e.g. the frames of an earlier clip that a running blur warp still reads): order the copy
     // stream behind everything launched so far, as vstab_download does
-    if (!ctx->ev_xfer_sync) VSTAB_HIP(hipEventCreateWithFlags(&ctx->ev_xfer_sync, hipEventDisableTiming));
+    VSTAB_HIP(ctx->ev_xfer_sync.ensure());
     VSTAB_HIP(hipEventRecord(ctx->ev_xfer_sync, ctx->stream));
     VSTAB_HIP(hipStreamWaitEvent(ctx->xfer_stream, ctx->ev_xfer_sync, 0));
     const char* src = static_cast<const char*>(host_src);
@@ -191,7 +191,7 @@ extern "C" int vstab_download(vstab_ctx* ctx, const void* dev_src, void* host_ds
     Ring r;
     if (ring_get(ctx, r)) return 1;
     // the producer of dev_src ran on the context's stream: order the copy stream behind it
-    if (!ctx->ev_xfer_sync) VSTAB_HIP(hipEventCreateWithFlags(&ctx->ev_xfer_sync, hipEventDisableTiming));
+    VSTAB_HIP(ctx->ev_xfer_sync.ensure());
     VSTAB_HIP(hipEventRecord(ctx->ev_xfer_sync, ctx->stream));
     VSTAB_HIP(hipStreamWaitEvent(ctx->xfer_stream, ctx->ev_xfer_sync, 0));
     const char* src = static_cast<const char*>(dev_src);
@@ -353,7 +353,7 @@ static int upload_as_bytes(vstab_ctx* ctx, const void* host_src, float* dev_dst,
     if (ring_get(ctx, r)) return 1;
     if (ctx->d_xfer.reserve(QCHUNK * SLOTS)) return 1;        // the byte chunks' landing slots on the device
     unsigned char* dslot = static_cast<unsigned char*>(ctx->d_xfer.ptr);
-    if (!ctx->ev_xfer_sync) VSTAB_HIP(hipEventCreateWithFlags(&ctx->ev_xfer_sync, hipEventDisableTiming));
+    VSTAB_HIP(ctx->ev_xfer_sync.ensure());
     VSTAB_HIP(hipEventRecord(ctx->ev_xfer_sync, ctx->stream));                 // as vstab_upload: dev_dst may still be in use on the stream
     VSTAB_HIP(hipStreamWaitEvent(ctx->xfer_stream, ctx->ev_xfer_sync, 0));
     const size_t chunks = (count + QCHUNK - 1) / QCHUNK;
@@ -462,10 +462,10 @@ static int download_mask_levels(vstab_ctx* ctx, const float* dev_src, float* hos
     const size_t packed_bytes = (count + 15) & ~size_t(15);
     if (ctx->d_xfer.reserve(packed_bytes + 16)) return 1;
     unsigned char* packed = static_cast<unsigned char*>(ctx->d_xfer.ptr);
-    volatile int* other = ctx->h_status + VSTAB_XFER_OTHER_WORD;   // coherent host word, device-visible
-    int* d_other = ctx->d_status + VSTAB_XFER_OTHER_WORD;
+    volatile int* other = ctx->status.host<volatile int>() + VSTAB_XFER_OTHER_WORD;   // coherent host word, device-visible
+    int* d_other = ctx->status.dev<int>() + VSTAB_XFER_OTHER_WORD;
     // d_xfer may still be the source of an upload's expansion on the copy stream: the pack kernel runs behind it
-    if (!ctx->ev_xfer_sync) VSTAB_HIP(hipEventCreateWithFlags(&ctx->ev_xfer_sync, hipEventDisableTiming));
+    VSTAB_HIP(ctx->ev_xfer_sync.ensure());
     VSTAB_HIP(hipEventRecord(ctx->ev_xfer_sync, ctx->xfer_stream));
     VSTAB_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_xfer_sync, 0));
     *other = 0;

@@ -130,13 +130,14 @@ def test_range_sniff_with_both_infinities(ctx, oracle):
 def test_frame_maxima_reach_the_host_without_a_copy(ctx):
     """The kernel that forms the per-frame maxima mirrors them into coherent host memory (its last workgroup: one store of
     all values, then a flag); `last_frame_peaks` waits for that kernel alone.  The host values are the device tensor's,
-    NaN and infinities included, across passes of different frame counts (the pass's target count is cumulative), and
+    NaN and infinities included, across passes of different frame counts (the pass's target count is cumulative) -- one
+    of them a frame past the host block's first 1024 values, so that it is regrown and then used by a small pass -- and
     `host_math.apply_value_range` takes them from there (`_vstab_fetch`) instead of a transfer of its own."""
     import torch
     from vstab_amd import host_math as hm
 
-    for n, seed in ((3, 1), (1, 2), (40, 3), (3, 4)):
-        frames = synth_frames(n, 90, 160, seed=seed)
+    for n, h, w, seed in ((3, 90, 160, 1), (1, 90, 160, 2), (40, 90, 160, 3), (1025, 16, 16, 5), (3, 90, 160, 4)):
+        frames = synth_frames(n, h, w, seed=seed)
         frames[0, 3, 4, 1] = 7.5
         if n > 2:
             frames[1, 5, 6, 2] = np.nan

@@ -122,6 +122,24 @@ def test_tvl1_batch_and_chunk_invariance(ctx):
     assert len({tuple(x) for x in iters.reshape(len(iters), -1).tolist()}) > 1
 
 
+def test_tvl1_state_belongs_to_its_context(ctx):
+    """The workspace, the progress word and the launch numbering live in the context: a second context on the same device
+    gives the first one's bits, and closing it leaves the first one's state as it was."""
+    from vstab_amd import native
+
+    prm = dict(nscales=1, warps=1, outer_iterations=1, inner_iterations=5)
+    gray = textured_clip(2, 32, 32, seed=11)
+    first = _run(ctx, gray, params=prm)
+    other = native.Context()
+    try:
+        second = _run(other, gray, params=prm)
+        assert all(np.array_equal(a, b) for a, b in zip(second, first))
+    finally:
+        other.close()
+    again = _run(ctx, gray, params=prm)
+    assert all(np.array_equal(a, b) for a, b in zip(again, first))
+
+
 def test_tvl1_rejects_what_it_does_not_restate(ctx):
     import torch
     from vstab_amd import native
