@@ -229,6 +229,11 @@ def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, t
     a driver that needs the dict once asks rank 0 only.  check_value_range: F0's per-frame `max > 1.5 -> /255` rule
     (stabilizer_utils.py:127-131) is applied to this rank's frames from the maxima the gray pass reports; it is a
     per-frame rule, so no rank needs to know another rank's verdict."""
+    if estimator == "subject":
+        # the subject's mask would have to be sharded with the frames and its gaps interpolated across ranks; every rank
+        # raises alike, before any collective
+        raise ValueError("stabilize_sharded does not support estimator 'subject': the subject lock is not sharded (its mask "
+                         "is not distributed with each rank's frames); run the single-GPU pipeline for a subject lock")
     if estimation_mask is not None:
         # the mask would have to be sharded with the frames, halo frame included; every rank raises alike, before any collective
         raise ValueError("stabilize_sharded does not support estimation_mask: the sharded path does not distribute a mask "

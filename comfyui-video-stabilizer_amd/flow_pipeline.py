@@ -28,6 +28,7 @@ from . import native
 from . import scene_cuts as scene_cuts_mod
 from . import spatial_fill as spatial_fill_mod
 from . import stability as stability_mod
+from . import subject_lock as subject_lock_mod
 from . import temporal_fill as temporal_fill_mod
 from .comfy_compat import ProgressBar, check_interrupt
 from .meta_v2 import applied_motion_meta_from_arrays, applied_motion_meta_from_stabilization_warp
@@ -59,8 +60,11 @@ class _gc_paused:
 #
 # "flow_tvl1" is the Flow node on its second dense backend, cv2.optflow.DualTVL1OpticalFlow (flow.py:76-80), which the
 # reference picks when DIS cannot be created; here it is chosen by the caller (_stabilize_frames(estimator="flow_tvl1")).
+#
+# "subject" (subject_lock.py, beyond the reference) measures no camera at all: its transitions are those of a masked
+# subject's centroid and area, so that everything behind the fit table holds the subject still instead of the background.
 _META_SOURCE = {"flow": "estimated_flow", "flow_phase_correlate": "estimated_flow", "flow_tvl1": "estimated_flow",
-                "classic": "estimated_classic"}
+                "classic": "estimated_classic", "subject": "estimated_subject"}
 _PHASE_REASON = "DIS unavailable (disabled by VSTAB_FLOW_BACKEND); cv2.optflow missing; using phase correlation."
 _TVL1_REASON = "DIS unavailable (disabled by the caller); using TV-L1."
 
@@ -85,6 +89,8 @@ def _backend_fields(estimator: str) -> Dict[str, Any]:
         return {"flow_backend": "phase_correlate", "flow_fallback_reason": _PHASE_REASON}
     if estimator == "flow_tvl1":
         return {"flow_backend": "TVL1", "flow_fallback_reason": _TVL1_REASON}
+    if estimator == "subject":
+        return {"flow_backend": "subject_mask", "flow_fallback_reason": None}
     return {}
 
 
@@ -224,8 +230,22 @@ def estimate_transitions_classic(ctx, device_frames, working_size, transform_mod
     return ctx.points_fit_batch(pairs, counts, transform_mode)
 
 
+def estimate_transitions_subject(ctx, device_frames, working_size, transform_mode: str, clip_start: bool = True, peaks_out=None,
+                                 subject=None):
+    """Subject lock (subject_lock.py): one reduction over the mask clip (HIP), 28 bytes per frame to the host, the candidate
+    fits from the subject's centroid and area.  subject: {"mask": device f32 [N,H,W]}; receives "block", meta["subject_lock"].
+    The frames are never read, so where the caller still owes the value-range sniff (F0) their per-frame maxima come from a
+    pass of their own, as in Motion Apply."""
+    if peaks_out is not None:
+        peaks_out.append(hm.prefetch_peaks(ctx.frame_range(device_frames)))
+    size = (int(device_frames.shape[2]), int(device_frames.shape[1]))
+    table, subject["block"] = subject_lock_mod.estimate_on_device(ctx, subject["mask"], size, working_size)
+    return table
+
+
 _ESTIMATORS.update({"flow": estimate_transitions, "flow_phase_correlate": estimate_transitions_phase,
-                    "flow_tvl1": estimate_transitions_tvl1, "classic": estimate_transitions_classic})
+                    "flow_tvl1": estimate_transitions_tvl1, "classic": estimate_transitions_classic,
+                    "subject": estimate_transitions_subject})
 
 
 def _fps_fields(context: hm.VideoContext, frame_rate) -> Tuple[float, Optional[float]]:
@@ -598,6 +618,7 @@ MASK_MARGIN_MAX = 64
 _MASK_LIMITS = {
     "classic": "the Classic estimator fits tracked corners, not grid samples: it needs a masked corner detector, which does not exist yet.",
     "flow_phase_correlate": "phase correlation yields one global transform per pair: it has no samples to drop.",
+    "subject": "the subject lock follows a mask's centroid: it has no camera-motion fit to keep a subject out of.",
 }
 
 
@@ -762,6 +783,7 @@ def _stabilize_frames(
     stability_report: bool = False,
     dynamic_zoom=None,
     zoom_limit=None,
+    subject_mask=None,
 ) -> hm.StabilizationResult:
     """Positional signature of the reference (flow.py:213-223); keyword-only extras select the GPU
     context, keep outputs resident in HBM (multi-GPU sharding lives in distributed.py) or switch the
@@ -805,7 +827,15 @@ def _stabilize_frames(
     mean over the window -- per shot under scene_cuts -- and is capped at zoom_limit (None: 2.0, else in [1, 16]); the
     plan's final matrices are replaced by the zoomed ones and the warp runs unchanged.  For crop_and_pad framing only;
     meta["dynamic_zoom"] reports the zoom per frame, stabilization_warp / motion_meta hold the zoomed matrices.  None: the
-    behaviour and meta without it, byte for byte, and nothing is launched.  Bypass paths ignore it."""
+    behaviour and meta without it, byte for byte, and nothing is launched.  Bypass paths ignore it.
+    subject_mask (beyond the reference, None by default; with estimator="subject" only, and required by it): [N,H,W] float
+    at the frames' resolution, > 0.5 where the subject is (a NaN is not subject).  The transitions are then the subject's, not
+    the camera's: count, coordinate sums and bounding box of every mask come from one reduction (subject_lock.py;
+    include/vstab.h states the rule), translation follows the centroid, similarity also the square root of the area ratio,
+    frames without a subject are interpolated and reported with confidence 0.  Everything behind the fit table is unchanged:
+    camera_lock=True pins the subject where frame 0 shows it.  For translation / similarity, without temporal_fill,
+    estimation_mask, mesh_warp or scene_cuts="auto"; meta["subject_lock"] reports centroids and gaps.  None: the behaviour and
+    meta without it, byte for byte, and nothing is launched.  Bypass paths ignore it."""
     zoom = dynamic_zoom_mod.check_request(dynamic_zoom, zoom_limit)
     if zoom is not None:
         dynamic_zoom_mod.check_pipeline(framing_mode)
@@ -817,6 +847,7 @@ def _stabilize_frames(
         raise ValueError("mesh_motion=True needs mesh_warp: without a mesh warp there are no per-vertex offsets to record.")
     if estimator not in _META_SOURCE:
         raise ValueError(f"Unknown estimator {estimator!r}; expected 'flow' or 'classic'.")
+    subject = subject_lock_mod.check_request(subject_mask, transform_mode, estimator)
     temporal_fill = int(temporal_fill)
     if not 0 <= temporal_fill <= temporal_fill_mod.MAX_RADIUS:
         raise ValueError(f"temporal_fill={temporal_fill} outside [0, {temporal_fill_mod.MAX_RADIUS}]")
@@ -825,6 +856,8 @@ def _stabilize_frames(
         mask_margin = check_estimation_mask_request(estimator, mask_margin)
     if mesh is not None:
         mesh_warp_mod.check_pipeline(estimator, framing_mode, temporal_fill)
+    if subject:
+        subject_lock_mod.check_pipeline(temporal_fill, scene, estimation_mask)
     total_frames = len(context.frames)
     fps_effective, fps_requested = _fps_fields(context, frame_rate)
     size = (context.width, context.height)
@@ -880,6 +913,8 @@ def _stabilize_frames(
         check_estimation_mask_shape(estimation_mask, total_frames, size)
     if scene is not None and scene.mode == "given":
         scene_cuts_mod.check_given_cuts(scene.cuts, total_frames)
+    if subject:
+        subject_lock_mod.check_request(subject_mask, transform_mode, estimator, total_frames, size)
     ctx = ctx or native.default_context()
     device_frames = context.device_batch(ctx)
     working_size = hm._working_estimation_size(context.width, context.height)
@@ -909,6 +944,8 @@ def _stabilize_frames(
         masked = dict(masked, gray_out=[])     # the estimation images stay alive for the score below
     if mesh is not None:
         masked = dict(masked, grid_out=[])     # so does the grid of flow samples, for the vertex residuals
+    if subject:
+        masked = {"subject": {"mask": subject_lock_mod.mask_on_device(ctx, subject_mask)}}
     fit_records = estimate(ctx, device_frames, working_size, transform_mode, peaks_out=peaks, **masked)
     if peaks and hm.resolve_value_range(context, peaks[0], ctx):
         # F0 (stabilizer_utils.py:127-131): some frame turned out to be 0..255 float data.  The estimation above ran
@@ -964,6 +1001,8 @@ def _stabilize_frames(
         meta["scene_cuts"] = scene_block
     if mesh_block is not None:
         meta["mesh_warp"] = mesh_block
+    if subject:
+        meta["subject_lock"] = masked["subject"]["block"]
     _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill)
     _spatial_fill(ctx, dst, mask, plan, meta, spatial_fill)
     _stability_report(ctx, device_frames, dst, mask, plan, meta, stability_report, segments)

@@ -36,6 +36,7 @@ VERTS_MIN, VERTS_MAX = 2, 65     # vertices per axis (native.MESH_MAX_VERTS)
 _ESTIMATOR_LIMITS = {
     "classic": "the Classic estimator tracks sparse corners: it has no dense grid of flow samples to take the residual from.",
     "flow_phase_correlate": "phase correlation yields one global shift per pair: it has no dense grid of flow samples.",
+    "subject": "the subject lock reduces a mask to a centroid and an area: it has no dense grid of flow samples.",
 }
 
 

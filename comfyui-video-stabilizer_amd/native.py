@@ -203,6 +203,7 @@ _SIGNATURES = {
         C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vstab_frame_sse_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vstab_mask_moments_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vstab_gftt_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p,
                   C.c_void_p]),
@@ -1051,6 +1052,25 @@ class Context:
             self.handle, _dev_ptr(a), _dev_ptr(mask_a) if mask_a is not None else None, _dev_ptr(b),
             _dev_ptr(mask_b) if mask_b is not None else None, n, h, w, _dev_ptr(sse), _dev_ptr(count)), "vstab_frame_sse_batch")
         return sse, count
+
+    # ------------------------------------------------------------------ subject lock
+    def mask_moments_batch(self, mask):
+        """Count, coordinate sums and bounding box of the subject pixels (mask > 0.5; a NaN is not subject, +inf is) of every
+        frame of mask [n,h,w], f32, device, contiguous, as exact integers (include/vstab.h states the rule); nothing is
+        written to it.  -> (sums i64 [n,3] = count, sum_x, sum_y;  bbox i32 [n,4] = x0, y0, x1, y1 inclusive, four -1 for a
+        frame without a subject pixel), device tensors."""
+        torch = self.torch
+        if not (isinstance(mask, torch.Tensor) and mask.dtype == torch.float32 and mask.device == self.device and mask.is_contiguous()):
+            raise ValueError(f"mask_moments_batch: mask must be a contiguous float32 tensor on {self.device}")
+        if mask.dim() != 3:
+            raise ValueError(f"mask_moments_batch: mask of shape {tuple(mask.shape)} is not [n,h,w]")
+        n, h, w = int(mask.shape[0]), int(mask.shape[1]), int(mask.shape[2])
+        sums = torch.empty((n, 3), dtype=torch.int64, device=self.device)
+        bbox = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+        self.use_torch_stream()
+        _check(self.lib.vstab_mask_moments_batch(self.handle, _dev_ptr(mask), n, h, w, _dev_ptr(sums), _dev_ptr(bbox)),
+               "vstab_mask_moments_batch")
+        return sums, bbox
 
     # ------------------------------------------------------------------ Classic estimator (sparse features + LK)
     def gftt_batch(self, gray, max_corners=400, quality=0.01, min_distance=7.0, block_size=21):

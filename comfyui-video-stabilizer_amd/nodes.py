@@ -780,6 +780,47 @@ class VideoStabilizerFlowZoom(io.ComfyNode):
         return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
 
 
+class VideoStabilizerFlowSubject(io.ComfyNode):
+    """The Flow node locked on a subject: `subject_mask` (a per-frame segmentation of a person, face, product or vehicle) is
+    reduced to the subject's centroid and area in every frame (subject_lock.py), and those -- not the camera's motion -- are
+    what the trajectory steadies: with Camera Lock the subject stays where frame 0 shows it.  Not one of the reference's
+    nodes: it is listed by an extension but kept out of NODE_CLASSES."""
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        schema = io.Schema(
+            node_id="video_stabilizer_subject",
+            display_name="Video Stabilizer Flow (Subject Lock)",
+            category="Video/Stabilization",
+            description=("Video Stabilizer Flow that stabilizes on a masked subject instead of the background: the subject is "
+                         "held still (Camera Lock) or followed smoothly, without the drift of integrated optical flow."),
+        )
+        base = VideoStabilizerFlow.define_schema()
+        schema.inputs = [
+            io.Combo.Input("transform_mode", options=["translation", "similarity"], default="translation",
+                           display_name="Transform Mode",
+                           tooltip=("translation follows the subject's centroid; similarity also its size (the square root "
+                                    "of the mask's area ratio), without rotation."))
+            if s.id == "transform_mode" else s for s in base.inputs] + [
+            io.Mask.Input("subject_mask", display_name="Subject Mask",
+                          tooltip=("Per-frame mask of the subject at the frames' resolution; values above 0.5 are the subject. "
+                                   "Frames without a subject are interpolated from their neighbours.")),
+        ]
+        schema.outputs = _estimator_outputs()
+        return schema
+
+    @classmethod
+    def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
+                strength: float, smooth: float, keep_fov: float, padding_color: str, subject_mask: Any) -> io.NodeOutput:
+        context = hm._normalize_video_input(frames)
+        result = _stabilize_frames(
+            context, framing_mode, transform_mode, camera_lock, strength, smooth, keep_fov,
+            hm._parse_padding_color(padding_color), frame_rate, keep_on_device=True, estimator="subject",
+            subject_mask=subject_mask,
+        )
+        return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
+
+
 NODE_CLASSES = [VideoStabilizerClassic, VideoStabilizerFlow, VideoStabilizerMotionApply, VideoStabilizerShakeGenerator,
                 VideoStabilizerShakeGeneratorManual, VideoStabilizerInverse]
 
@@ -867,3 +908,11 @@ class VideoStabilizerAmdZoomExtension(VideoStabilizerAmdReportExtension):
 
     async def get_node_list(self) -> list:
         return await super().get_node_list() + [VideoStabilizerFlowZoom]
+
+
+class VideoStabilizerAmdSubjectExtension(VideoStabilizerAmdZoomExtension):
+    """The zoom extension's fifteen nodes plus Video Stabilizer Flow (Subject Lock).  A class of its own for the reason
+    the seven before it are."""
+
+    async def get_node_list(self) -> list:
+        return await super().get_node_list() + [VideoStabilizerFlowSubject]

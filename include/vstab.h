@@ -636,6 +636,29 @@ int vstab_spatial_fill_batch(vstab_ctx* ctx, float* dst, const float* mask, int 
 int vstab_frame_sse_batch(vstab_ctx* ctx, const float* a, const float* mask_a, const float* b, const float* mask_b,
                           int n, int h, int w, uint64_t* sse, uint32_t* count);
 
+/* ---- subject lock: where a mask's subject is, per frame, as exact integers (beyond the reference, off by default) ----
+ * Stabilizing ON a subject (subject_lock.py) needs the subject's absolute position in every frame; a per-frame segmentation
+ * mask gives it without drift.  This entry point reduces a clip of masks to seven integers per frame; everything formed
+ * from them (centroid, area ratio, transitions) is host arithmetic on the downloaded 28 bytes.  The rule:
+ *   - Pixel (x, y) of frame k is SUBJECT iff mask[k, y, x] > 0.5f: a NaN is not subject, +inf is.  This deliberately
+ *     differs from the estimation mask, where a non-finite value means subject -- the conservative choice for exclusion;
+ *     here a NaN must not attract the track.
+ *   - sums[k] = {count, sum_x, sum_y}: the number of subject pixels and the sums of their x and of their y, 64-bit.
+ *   - bbox[k] = {x0, y0, x1, y1}: the inclusive bounding box of the subject pixels; a frame without one reports
+ *     {-1, -1, -1, -1} and sums of 0.
+ * Integer sums, minima and maxima do not depend on the order of their reduction, so the result equals a NumPy restatement
+ * exactly.  sum_x < 2^31 * 2^15: no wrap.
+ *   mask dev [n, h, w] f32, read only;  sums dev [n, 3] u64;  bbox dev [n, 4] i32.  The call presets both outputs itself.
+ * n >= 1;  1 <= w, h <= 32768 (32-bit coordinates per thread);  h * w < 2^31.  Kernel (vstab_subject.hip, shaped as
+ * frame_sse_kernel is): one launch reads every frame as the flat float array it is, float4 per lane behind a scalar head of
+ * up to 3 floats where a frame does not start on a 16-byte boundary (frame k of a clip whose h * w is no multiple of 4 starts
+ * (k * h * w) mod 4 floats past one), and a tail of up to 3; (x, y) of a float4's first pixel from one division, the others
+ * by stepping with wrap; per thread -> wavefront shuffle -> LDS -> three 64-bit atomic adds, two unsigned atomic minima
+ * (x0, y0 preset to 0xFFFFFFFF) and two signed atomic maxima (x1, y1 preset to -1) per workgroup and frame, skipped when the
+ * workgroup counted nothing -- so an empty frame reads as four -1 without a finishing pass.  Asynchronous on the context's
+ * stream; timing kind "mask_moments". */
+int vstab_mask_moments_batch(vstab_ctx* ctx, const float* mask, int n, int h, int w, uint64_t* sums, int32_t* bbox);
+
 /* ---- F6 / F9 host helper: element-wise libm over fp64 arrays (host pointers, no GPU involved) ----
  * nodes/stabilizer_utils.py:300-358 (_matrix_to_params / _params_to_matrix) call math.sqrt/atan2/log and
  * math.exp/cos/sin per frame; this runs the same libm functions over a whole clip in one call.
