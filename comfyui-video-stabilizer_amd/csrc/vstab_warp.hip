@@ -1,5 +1,6 @@
 // vstab_warp.hip -- perspective/similarity warp with padding mask, its mesh-displaced forms (mesh_warp_kernel and its
-// inverse, mesh_unwarp_kernel), the multi-sample motion blur, the temporal fill and the coverage extent of the dynamic zoom
+// inverse, mesh_unwarp_kernel), the multi-sample motion blur, the temporal fill (plain, and blended: fill_gain_sums_kernel,
+// temporal_fill_blend_kernel) and the coverage extent of the dynamic zoom
 // (cover_extent_kernel: warp_pixel's coverage bit alone, nothing sampled).
 // All of them take their coordinates from ONE definition, warp_pixel, and
 // share one tile shell (TileShell, warp_kernel's body, block_count_add); the scalar pieces that vstab_crop / vstab_dis / vstab_tvl1
@@ -1568,6 +1569,289 @@ __global__ __launch_bounds__(256) void temporal_fill_kernel(FillArgs a, const Fi
     }
 }
 
+
+// The candidate records of a call: the transform of every float32 forward matrix and the frame it samples, -1 where the
+// fill skips it.  cand_frame == nullptr: the records of a frame's OWN matrices (frame 0 where usable, -1 where not).
+int fill_cand_records(const char* who, const float* matrices, const int32_t* cand_frame, size_t count, int clip_frames, FillCand* cd)
+{
+    for (size_t i = 0; i < count; i++) {
+        const int f = cand_frame ? cand_frame[i] : 0;
+        VSTAB_REQUIRE(f >= -1 && f < clip_frames, "%s: cand_frame[%zu]=%d outside [-1, %d)", who, i, f, clip_frames);
+        const float* m32 = matrices + i * 9;
+        vstab_fill_xform(m32, &cd[i].xf);
+        // a matrix that cv::invert would refuse (zero or non-finite determinant) has no source position: no candidate
+        double M[9], inv[9];
+        bool finite = true;
+        for (int j = 0; j < 9; j++) { M[j] = (double)m32[j]; finite = finite && std::isfinite(M[j]); }
+        bool ok = f >= 0 && finite && vstab_invert3x3_hd(M, inv);
+        for (int j = 0; ok && j < 9; j++) ok = std::isfinite(inv[j]);
+        cd[i].frame = ok ? f : -1;
+        cd[i].pad_ = 0;
+    }
+    return 0;
+}
+
+// ---- blended temporal fill: exposure-matched candidates, feathered seam (include/vstab.h states both rules) -------------
+//
+// Two kernels beside temporal_fill_kernel, which stays as it is (its instances, its FillCand records, its cost):
+//   fill_gain_sums_kernel       integer sums of own and candidate values over the lattice x % 8 == 4 && y % 8 == 4 where
+//                               both see source content by the interior rule; the host turns them into one gain per
+//                               (frame, candidate, channel).  A workgroup = 256 lattice pixels of one (frame, candidate) pair, so
+//                               both records are block-uniform (scalar loads); per-thread values -> wave shuffle -> LDS -> one
+//                               64-bit atomic per sum, skipped where the workgroup counted nothing.  Nothing waits for
+//                               another workgroup, and integer sums do not depend on the order of the atomics.
+//   temporal_fill_blend_kernel  the fill's tile, shell and candidate walk, with (a) the sample scaled by the candidate's gain
+//                               and (b) the own pixels within feather_px of the frame's tap-interior border cross-faded
+//                               towards the first valid candidate.  Whether an own pixel takes part costs its mask and its
+//                               own coordinate (warp_pixel with a sampler that only records X, Y: ALU, no loads); a tile
+//                               without padded or feathered pixels returns before anything else is read or stored.
+
+// All taps of the Q5 coordinate (X, Y) inside an sw x sh frame: the interior tests of sample_q5, as temporal_fill_kernel
+// states them in its sampler.
+template <int INTERP>
+__device__ __forceinline__ bool fill_taps_inside(int sh, int sw, int X, int Y)
+{
+    const int sx = sat_short(X >> 5), sy = sat_short(Y >> 5);
+    if (INTERP == VSTAB_INTERP_BILINEAR) return (unsigned)sx < (unsigned)(sw - 1) && (unsigned)sy < (unsigned)(sh - 1);
+    const unsigned width1 = (unsigned)(sw - 3 > 0 ? sw - 3 : 0);
+    const unsigned height1 = (unsigned)(sh - 3 > 0 ? sh - 3 : 0);
+    return (unsigned)(sx - 1) < width1 && (unsigned)(sy - 1) < height1;
+}
+
+// The Q5 coordinate of output pixel (x, y) under one record: warp_pixel with samplers that read nothing.
+template <int INTERP>
+__device__ __forceinline__ void fill_coordinate(const WarpXform* __restrict__ xf, const XformRegs<INTERP, VSTAB_SUBPIX_Q5>& r, int sh,
+                                                int sw, int dw, int bw0, int bw0_pow2, int x, int y, double dy, int& X, int& Y)
+{
+    float c_unused = 0.f;
+    int ox = 0, oy = 0;
+    (void)warp_pixel<INTERP, VSTAB_SUBPIX_Q5, false>(
+        xf, r, sh, sw, dw, bw0, bw0_pow2, x, y, dy, [&](int qx, int qy) { ox = qx; oy = qy; return Px{0.f, 0.f, 0.f}; },
+        [&](float, float) { return Px{0.f, 0.f, 0.f}; }, NoDisplacement{}, c_unused);
+    X = ox; Y = oy;
+}
+
+// The fill's sample of one candidate at (x, y), taken only where every tap is inside (`valid`).
+template <int INTERP>
+__device__ __forceinline__ Px fill_candidate_sample(const float* __restrict__ S, const WarpXform* __restrict__ xf,
+                                                    const XformRegs<INTERP, VSTAB_SUBPIX_Q5>& r, int sh, int sw, int dw, int bw0,
+                                                    int bw0_pow2, int x, int y, double dy, const float* cub_tab, bool& valid)
+{
+    float c_unused = 0.f;
+    bool ok = false;
+    const Px v = warp_pixel<INTERP, VSTAB_SUBPIX_Q5, false>(
+        xf, r, sh, sw, dw, bw0, bw0_pow2, x, y, dy,
+        [&](int X, int Y) {
+            ok = fill_taps_inside<INTERP>(sh, sw, X, Y);
+            return ok ? sample_q5<INTERP>(S, sh, sw, X, Y, 0.f, 0.f, 0.f, cub_tab) : Px{0.f, 0.f, 0.f};
+        },
+        [&](float, float) { return Px{0.f, 0.f, 0.f}; }, NoDisplacement{}, c_unused);
+    valid = ok;
+    return v;
+}
+
+// q of the gain sums: a value in 16 fractional bits, truncated; below 0 and NaN give 0, 1 and above give 65536.
+__device__ __forceinline__ unsigned gain_q(float v)
+{
+    return v > 0.f ? (v < 1.f ? (unsigned)(v * 65536.0f) : 65536u) : 0u;
+}
+
+struct GainArgs {
+    const float* src;
+    const float* dst;
+    unsigned long long* sums;   // [n, K, 7]
+    int K, sh, sw, dh, dw;
+    int bw0, bw0_pow2;
+    int lw;                     // lattice columns: x = 8 * lx + 4 < dw
+    unsigned lattice;           // lattice pixels per frame
+    unsigned blocks_per_pair;   // workgroups per (frame, candidate) pair
+};
+
+template <int INTERP>
+__global__ __launch_bounds__(256) void fill_gain_sums_kernel(GainArgs a, const FillCand* __restrict__ cands, const FillCand* __restrict__ own)
+{
+    constexpr int NS = 7, WAVES = 4;
+    __shared__ __attribute__((aligned(16))) float s_cub[32 * 4];
+    __shared__ unsigned s_sum[NS][WAVES];
+    const unsigned pair = blockIdx.x / a.blocks_per_pair;          // frame * K + k
+    const unsigned chunk = blockIdx.x - pair * a.blocks_per_pair;
+    const unsigned frame = pair / (unsigned)a.K;
+    const FillCand* __restrict__ cd = cands + pair;
+    const FillCand* __restrict__ ow = own + frame;
+    if (ow->frame < 0 || cd->frame < 0) return;                    // block-uniform: this pair counts nothing
+
+    const float* cub_tab = nullptr;
+    if (INTERP == VSTAB_INTERP_BICUBIC) {
+        if (threadIdx.x < 32) cubic_coeffs((int)threadIdx.x, s_cub + threadIdx.x * 4);
+        __syncthreads();
+        cub_tab = s_cub;
+    }
+
+    // a workgroup's sums fit 32 bits: 256 values of at most 65536
+    unsigned v[NS];
+#pragma unroll
+    for (int c = 0; c < NS; c++) v[c] = 0u;
+    const unsigned l = chunk * 256u + threadIdx.x;
+    if (l < a.lattice) {
+        const unsigned ly = l / (unsigned)a.lw;
+        const int x = (int)(l - ly * (unsigned)a.lw) * VSTAB_FILL_GAIN_STRIDE + VSTAB_FILL_GAIN_STRIDE / 2;   // x < dw, y < dh by the
+        const int y = (int)ly * VSTAB_FILL_GAIN_STRIDE + VSTAB_FILL_GAIN_STRIDE / 2;                            // lattice's size
+        const double dy = (double)y;
+        int X, Y;
+        {
+            const WarpXform* __restrict__ xo = &ow->xf;
+            const XformRegs<INTERP, VSTAB_SUBPIX_Q5> ro(xo);
+            fill_coordinate<INTERP>(xo, ro, a.sh, a.sw, a.dw, a.bw0, a.bw0_pow2, x, y, dy, X, Y);
+        }
+        if (fill_taps_inside<INTERP>(a.sh, a.sw, X, Y)) {
+            const float* __restrict__ S = a.src + (size_t)cd->frame * ((size_t)a.sh * a.sw * 3);
+            const WarpXform* __restrict__ xf = &cd->xf;
+            const XformRegs<INTERP, VSTAB_SUBPIX_Q5> r(xf);
+            bool valid = false;
+            const Px s = fill_candidate_sample<INTERP>(S, xf, r, a.sh, a.sw, a.dw, a.bw0, a.bw0_pow2, x, y, dy, cub_tab, valid);
+            if (valid) {
+                const float* __restrict__ D = a.dst + (size_t)frame * a.dh * a.dw * 3;
+                const Px o = load_px(D + ((unsigned)y * (unsigned)a.dw + (unsigned)x) * 3u);
+                v[0] = 1u;
+                v[1] = gain_q(o.r); v[2] = gain_q(o.g); v[3] = gain_q(o.b);
+                v[4] = gain_q(s.r); v[5] = gain_q(s.g); v[6] = gain_q(s.b);
+            }
+        }
+    }
+
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int c = 0; c < NS; c++) v[c] += __shfl_down(v[c], off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < NS; c++) s_sum[c][threadIdx.x >> 6] = v[c];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned total[NS];
+#pragma unroll
+        for (int c = 0; c < NS; c++) total[c] = s_sum[c][0] + s_sum[c][1] + s_sum[c][2] + s_sum[c][3];
+        if (total[0] != 0u) {       // nothing counted: every sum is zero, no atomic
+            unsigned long long* out = a.sums + (size_t)pair * NS;
+#pragma unroll
+            for (int c = 0; c < NS; c++) atomicAdd(out + c, (unsigned long long)total[c]);
+        }
+    }
+}
+
+struct BlendArgs : FillArgs {
+    unsigned* blend_count;
+    int Fe;             // 32 * feather_px
+    int lo, hi_x, hi_y; // the tap-interior border in 1/32 px: lo <= X <= hi_x, lo <= Y <= hi_y
+};
+
+template <int INTERP>
+__global__ __launch_bounds__(256) void temporal_fill_blend_kernel(BlendArgs a, const FillCand* __restrict__ cands,
+                                                                  const FillCand* __restrict__ own, const float* __restrict__ gains)
+{
+    constexpr int TILE_TX = 32;
+    __shared__ __attribute__((aligned(16))) float s_cub[32 * 4];
+    const TileShell<TILE_TX> t(a.tiles_x, a.tiles_y, a.dh, a.dw);
+    const int frame = t.frame, x0 = t.x0, y = t.y, npx = t.npx;
+
+    float* __restrict__ Mk = a.mask + (size_t)frame * a.dh * a.dw;
+    const unsigned row = (unsigned)y * (unsigned)a.dw;
+    const double dy = (double)y;
+    const FillCand* __restrict__ ow = own + frame;
+    const bool feather = a.Fe > 0 && ow->frame >= 0;      // block-uniform
+    bool need[TILE_PX], padded[TILE_PX];
+    float wgt[TILE_PX];                                   // own pixels: the weight of the own value
+    bool any = false;
+#pragma unroll
+    for (int p = 0; p < TILE_PX; p++) {
+        need[p] = padded[p] = false;
+        wgt[p] = 1.0f;
+        if (p < npx) {
+            const int x = x0 + p * TILE_TX;
+            if (Mk[row + (unsigned)x] == 1.0f) need[p] = padded[p] = true;
+            else if (feather) {
+                const WarpXform* __restrict__ xo = &ow->xf;
+                const XformRegs<INTERP, VSTAB_SUBPIX_Q5> ro(xo);
+                int X, Y;
+                fill_coordinate<INTERP>(xo, ro, a.sh, a.sw, a.dw, a.bw0, a.bw0_pow2, x, y, dy, X, Y);
+                // d32 = min(X - lo, Y - lo, hi_x - X, hi_y - Y), clamped to [0, Fe].  X and Y may be anywhere in int: one
+                // step outside the border already gives a negative term, so they are clamped to that first and no
+                // difference can overflow.
+                const int Xc = min(max(X, a.lo - 1), a.hi_x + 1), Yc = min(max(Y, a.lo - 1), a.hi_y + 1);
+                const int d32 = min(min(Xc - a.lo, Yc - a.lo), min(a.hi_x - Xc, a.hi_y - Yc));
+                const int d = min(max(d32, 0), a.Fe);
+                wgt[p] = (float)d / (float)a.Fe;
+                need[p] = d < a.Fe;                       // w < 1 (d == Fe divides to exactly 1.0f)
+            }
+        }
+        any = any || need[p];
+    }
+    if (!__syncthreads_or(any)) return;   // nothing padded, nothing within the feather: nothing to read, store or count
+
+    const float* cub_tab = nullptr;
+    if (INTERP == VSTAB_INTERP_BICUBIC) {
+        if (threadIdx.x < 32) cubic_coeffs((int)threadIdx.x, s_cub + threadIdx.x * 4);
+        __syncthreads();
+        cub_tab = s_cub;
+    }
+
+    float* __restrict__ D = a.dst + (size_t)frame * a.dh * a.dw * 3;
+    signed char* __restrict__ From = a.filled_from ? a.filled_from + (size_t)frame * a.dh * a.dw : nullptr;
+    const size_t src_frame = (size_t)a.sh * a.sw * 3;
+    unsigned filled = 0, blended = 0;
+    typedef float f3 __attribute__((ext_vector_type(3)));
+
+    for (int k = 0; k < a.K; k++) {
+        if (!__any(any)) break;                       // wave-uniform: no pixel of this wavefront is waiting
+        const FillCand* __restrict__ cd = cands + (size_t)frame * a.K + k;
+        if (cd->frame < 0) continue;                  // block-uniform
+        const float* __restrict__ S = a.src + (size_t)cd->frame * src_frame;
+        const float* __restrict__ g = gains + ((size_t)frame * a.K + k) * 3;
+        const float g0 = g[0], g1 = g[1], g2 = g[2];
+        const WarpXform* __restrict__ xf = &cd->xf;
+        const XformRegs<INTERP, VSTAB_SUBPIX_Q5> r(xf);
+        any = false;
+#pragma unroll
+        for (int p = 0; p < TILE_PX; p++) {
+            if (!need[p]) continue;
+            const int x = x0 + p * TILE_TX;
+            bool valid = false;
+            const Px s = fill_candidate_sample<INTERP>(S, xf, r, a.sh, a.sw, a.dw, a.bw0, a.bw0_pow2, x, y, dy, cub_tab, valid);
+            if (valid) {
+                const unsigned pix = row + (unsigned)x;
+                f3 rgb = {g0 * s.r, g1 * s.g, g2 * s.b};      // one float32 multiply; nothing of the old pixel enters
+                if (padded[p]) {
+                    Mk[pix] = 0.f;
+                    filled += 1u;
+                } else {
+                    const float w = wgt[p];
+                    if (w != 0.f) {                           // w == 0 (the fringe ring and beyond): the candidate alone
+                        const Px o = load_px(D + pix * 3u);
+                        const float u = 1.0f - w;
+                        rgb.x = o.r * w + rgb.x * u;
+                        rgb.y = o.g * w + rgb.y * u;
+                        rgb.z = o.b * w + rgb.z * u;
+                    }
+                    blended += 1u;
+                }
+                __builtin_memcpy(D + pix * 3u, &rgb, 12);
+                if (From) From[pix] = (signed char)k;
+                need[p] = false;
+            }
+            any = any || need[p];
+        }
+    }
+
+    if (a.fill_count != nullptr || a.pad_count != nullptr || a.blend_count != nullptr) {
+        unsigned cnt[3] = {filled, 0, blended};   // filled, left, blended
+#pragma unroll
+        for (int p = 0; p < TILE_PX; p++) cnt[1] += (need[p] && padded[p]) ? 1u : 0u;
+        block_count_add<3>(cnt, {a.fill_count, a.pad_count, a.blend_count}, frame);
+    }
+}
+
 }  // namespace
 
 extern "C" int vstab_temporal_fill_batch(vstab_ctx* ctx, const float* src, int clip_frames, int src_h, int src_w, int first,
@@ -1584,20 +1868,7 @@ extern "C" int vstab_temporal_fill_batch(vstab_ctx* ctx, const float* src, int c
                   first, first + n, clip_frames);
     VSTAB_REQUIRE((const void*)src != (const void*)dst, "%s: dst must not alias src (candidates read src while dst is written)", who);
     std::vector<FillCand> cd((size_t)n * K);
-    for (size_t i = 0; i < cd.size(); i++) {
-        const int f = cand_frame[i];
-        VSTAB_REQUIRE(f >= -1 && f < clip_frames, "%s: cand_frame[%zu]=%d outside [-1, %d)", who, i, f, clip_frames);
-        const float* m32 = matrices + i * 9;
-        vstab_fill_xform(m32, &cd[i].xf);
-        // a matrix that cv::invert would refuse (zero or non-finite determinant) has no source position: no candidate
-        double M[9], inv[9];
-        bool finite = true;
-        for (int j = 0; j < 9; j++) { M[j] = (double)m32[j]; finite = finite && std::isfinite(M[j]); }
-        bool ok = f >= 0 && finite && vstab_invert3x3_hd(M, inv);
-        for (int j = 0; ok && j < 9; j++) ok = std::isfinite(inv[j]);
-        cd[i].frame = ok ? f : -1;
-        cd[i].pad_ = 0;
-    }
+    if (int rc = fill_cand_records(who, matrices, cand_frame, cd.size(), clip_frames, cd.data())) return rc;
     VSTAB_HIP(hipSetDevice(ctx->device));
     void* d_cd = nullptr;
     if (vstab_stage_params(ctx, cd.data(), cd.size() * sizeof(FillCand), &d_cd)) return 1;
@@ -1619,6 +1890,117 @@ extern "C" int vstab_temporal_fill_batch(vstab_ctx* ctx, const float* src, int c
     if (interp == VSTAB_INTERP_BICUBIC) hipLaunchKernelGGL((temporal_fill_kernel<VSTAB_INTERP_BICUBIC, VSTAB_SUBPIX_Q5>), grid, block, 0, ctx->stream, a, cands);
     else if (subpix == VSTAB_SUBPIX_EXACT) hipLaunchKernelGGL((temporal_fill_kernel<VSTAB_INTERP_BILINEAR, VSTAB_SUBPIX_EXACT>), grid, block, 0, ctx->stream, a, cands);
     else hipLaunchKernelGGL((temporal_fill_kernel<VSTAB_INTERP_BILINEAR, VSTAB_SUBPIX_Q5>), grid, block, 0, ctx->stream, a, cands);
+    VSTAB_HIP(hipGetLastError());
+    return 0;
+}
+
+namespace {
+// What the two blended entries share with vstab_temporal_fill_batch: its checks, plus Q5 and the own matrices.
+int check_fill_blend(const char* who, vstab_ctx* ctx, const float* src, int clip_frames, int src_h, int src_w, int first, int n,
+                     const float* matrices, const int32_t* cand_frame, int K, const float* own_matrices, int out_h, int out_w,
+                     int interp, int subpix, const float* dst)
+{
+    const float no_border[3] = {0.f, 0.f, 0.f};
+    if (int rc = check_common(who, ctx, src, n, src_h, src_w, matrices, out_h, out_w, interp, no_border, subpix, dst)) return rc;
+    VSTAB_REQUIRE(subpix == VSTAB_SUBPIX_Q5, "%s: VSTAB_SUBPIX_EXACT is not supported (the feather distance and the gain lattice "
+                  "are stated on the 1/32-px coordinates of VSTAB_SUBPIX_Q5)", who);
+    VSTAB_REQUIRE(cand_frame != nullptr && own_matrices != nullptr, "%s: NULL pointer argument", who);
+    VSTAB_REQUIRE(K >= 1 && K <= 64, "%s: K=%d outside [1,64]", who, K);
+    VSTAB_REQUIRE(clip_frames > 0 && first >= 0 && first + n <= clip_frames, "%s: frames [%d, %d) outside a clip of %d frames", who,
+                  first, first + n, clip_frames);
+    VSTAB_REQUIRE((const void*)src != (const void*)dst, "%s: dst must not alias src (candidates read src while dst is written)", who);
+    return 0;
+}
+
+// Candidate records [n * K] followed by the own records [n], staged as one block.
+int stage_fill_blend_records(const char* who, vstab_ctx* ctx, const float* matrices, const int32_t* cand_frame, int n, int K,
+                             int clip_frames, const float* own_matrices, const float* gains, const FillCand** cands,
+                             const FillCand** own, const float** gains_dev)
+{
+    const size_t pairs = (size_t)n * K;
+    const size_t rec_bytes = (pairs + (size_t)n) * sizeof(FillCand);
+    std::vector<unsigned char> blob(rec_bytes + (gains ? pairs * 3 * sizeof(float) : 0));
+    FillCand* cd = reinterpret_cast<FillCand*>(blob.data());
+    if (int rc = fill_cand_records(who, matrices, cand_frame, pairs, clip_frames, cd)) return rc;
+    if (int rc = fill_cand_records(who, own_matrices, nullptr, (size_t)n, clip_frames, cd + pairs)) return rc;
+    if (gains) memcpy(blob.data() + rec_bytes, gains, pairs * 3 * sizeof(float));
+    void* dev = nullptr;
+    if (vstab_stage_params(ctx, blob.data(), blob.size(), &dev)) return 1;
+    *cands = static_cast<const FillCand*>(dev);
+    *own = *cands + pairs;
+    if (gains_dev) *gains_dev = reinterpret_cast<const float*>(static_cast<const unsigned char*>(dev) + rec_bytes);
+    return 0;
+}
+}  // namespace
+
+extern "C" int vstab_fill_gain_sums(vstab_ctx* ctx, const float* src, int clip_frames, int src_h, int src_w, int first, int n,
+                                    const float* matrices, const int32_t* cand_frame, int K, const float* own_matrices, int out_h,
+                                    int out_w, int interp, int subpix, const float* dst, uint64_t* sums)
+{
+    const char* who = "vstab_fill_gain_sums";
+    if (int rc = check_fill_blend(who, ctx, src, clip_frames, src_h, src_w, first, n, matrices, cand_frame, K, own_matrices, out_h,
+                                  out_w, interp, subpix, dst)) return rc;
+    VSTAB_REQUIRE(sums != nullptr, "%s: NULL pointer argument", who);
+    VSTAB_REQUIRE(((uintptr_t)sums & 7) == 0, "%s: sums is not aligned to its element size", who);
+    GainArgs a{};
+    a.src = src; a.dst = dst; a.sums = reinterpret_cast<unsigned long long*>(sums);
+    a.K = K; a.sh = src_h; a.sw = src_w; a.dh = out_h; a.dw = out_w;
+    set_block_width(out_h, out_w, &a.bw0, &a.bw0_pow2);
+    constexpr int STRIDE = VSTAB_FILL_GAIN_STRIDE, REST = STRIDE - STRIDE / 2 - 1;
+    a.lw = (out_w + REST) / STRIDE;                                    // x = STRIDE * lx + STRIDE / 2 < out_w
+    a.lattice = (unsigned)a.lw * (unsigned)((out_h + REST) / STRIDE);
+    a.blocks_per_pair = (a.lattice + 255u) / 256u;
+    const unsigned long long blocks = (unsigned long long)a.blocks_per_pair * (unsigned long long)n * (unsigned long long)K;
+    VSTAB_REQUIRE(blocks < 0x7fffffffULL, "%s: grid of %llu blocks is out of range", who, blocks);
+    VSTAB_HIP(hipSetDevice(ctx->device));
+    const FillCand *cands = nullptr, *own = nullptr;
+    if (int rc = stage_fill_blend_records(who, ctx, matrices, cand_frame, n, K, clip_frames, own_matrices, nullptr, &cands, &own, nullptr)) return rc;
+    KernelTimer timer(ctx, "fill_gain");
+    VSTAB_HIP(hipMemsetAsync(sums, 0, sizeof(uint64_t) * 7 * (size_t)n * K, ctx->stream));
+    if (blocks == 0) return 0;                                         // a canvas without a lattice pixel: every sum is zero
+    const dim3 grid((unsigned)blocks), block(256);
+    if (interp == VSTAB_INTERP_BICUBIC) hipLaunchKernelGGL((fill_gain_sums_kernel<VSTAB_INTERP_BICUBIC>), grid, block, 0, ctx->stream, a, cands, own);
+    else hipLaunchKernelGGL((fill_gain_sums_kernel<VSTAB_INTERP_BILINEAR>), grid, block, 0, ctx->stream, a, cands, own);
+    VSTAB_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int vstab_temporal_fill_blend_batch(vstab_ctx* ctx, const float* src, int clip_frames, int src_h, int src_w, int first,
+                                               int n, const float* matrices, const int32_t* cand_frame, int K,
+                                               const float* own_matrices, const float* gains, int feather_px, int out_h, int out_w,
+                                               int interp, int subpix, float* dst, float* mask, int8_t* filled_from,
+                                               uint32_t* fill_count, uint32_t* pad_count, uint32_t* blend_count)
+{
+    const char* who = "vstab_temporal_fill_blend_batch";
+    if (int rc = check_fill_blend(who, ctx, src, clip_frames, src_h, src_w, first, n, matrices, cand_frame, K, own_matrices, out_h,
+                                  out_w, interp, subpix, dst)) return rc;
+    VSTAB_REQUIRE(mask != nullptr && gains != nullptr, "%s: NULL pointer argument", who);
+    VSTAB_REQUIRE(feather_px >= 0 && feather_px <= VSTAB_FILL_FEATHER_MAX, "%s: feather_px=%d outside [0,%d]", who, feather_px,
+                  VSTAB_FILL_FEATHER_MAX);
+    VSTAB_HIP(hipSetDevice(ctx->device));
+    const FillCand *cands = nullptr, *own = nullptr;
+    const float* gains_dev = nullptr;
+    if (int rc = stage_fill_blend_records(who, ctx, matrices, cand_frame, n, K, clip_frames, own_matrices, gains, &cands, &own, &gains_dev)) return rc;
+
+    BlendArgs a{};
+    a.src = src; a.dst = dst; a.mask = mask; a.filled_from = reinterpret_cast<signed char*>(filled_from);
+    a.fill_count = fill_count; a.pad_count = pad_count; a.blend_count = blend_count;
+    a.n = n; a.K = K; a.sh = src_h; a.sw = src_w; a.dh = out_h; a.dw = out_w;
+    a.Fe = 32 * feather_px;
+    const int inset = interp == VSTAB_INTERP_BICUBIC ? 1 : 0;          // bicubic: X - 32 and 32 (sw - 2) - X
+    a.lo = 32 * inset; a.hi_x = 32 * (src_w - 1 - inset); a.hi_y = 32 * (src_h - 1 - inset);
+    set_block_width(out_h, out_w, &a.bw0, &a.bw0_pow2);
+    unsigned blocks = 0;
+    if (int rc = tile_grid(who, n, out_h, out_w, 32, 256, &a.tiles_x, &a.tiles_y, &blocks)) return rc;
+    const size_t px = (size_t)n * out_h * out_w;
+    if (filled_from) VSTAB_HIP(hipMemsetAsync(filled_from, 0xff, px, ctx->stream));   // -1: neither filled nor blended
+    if (fill_count) VSTAB_HIP(hipMemsetAsync(fill_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
+    if (pad_count) VSTAB_HIP(hipMemsetAsync(pad_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
+    if (blend_count) VSTAB_HIP(hipMemsetAsync(blend_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
+    KernelTimer timer(ctx, "fill_blend");
+    const dim3 grid(blocks), block(256);
+    if (interp == VSTAB_INTERP_BICUBIC) hipLaunchKernelGGL((temporal_fill_blend_kernel<VSTAB_INTERP_BICUBIC>), grid, block, 0, ctx->stream, a, cands, own, gains_dev);
+    else hipLaunchKernelGGL((temporal_fill_blend_kernel<VSTAB_INTERP_BILINEAR>), grid, block, 0, ctx->stream, a, cands, own, gains_dev);
     VSTAB_HIP(hipGetLastError());
     return 0;
 }

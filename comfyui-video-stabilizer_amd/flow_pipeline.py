@@ -584,14 +584,16 @@ def _rewarp_mismatched(ctx, device_frames, plan, final_dev, dst, mask, counts, p
     return int(bad.size)
 
 
-def _temporal_fill(ctx, device_frames, dst, mask, plan, meta, radius: int) -> None:
+def _temporal_fill(ctx, device_frames, dst, mask, plan, meta, radius: int, blend=(None, False)) -> None:
     """Fills the warp's padding from neighbouring frames in place (temporal_fill.py) and adds meta["temporal_fill"]; the
-    other meta keys keep describing the warp.  `crop` framing has no padding: nothing to do."""
+    other meta keys keep describing the warp.  `crop` framing has no padding: nothing to do.  blend = (feather px | None,
+    exposure): temporal_fill.check_blend_request's answer; (None, False) is the plain fill."""
     if radius <= 0 or plan.framing_mode == "crop":
         return
     em = plan.estimated_motion
     meta["temporal_fill"] = temporal_fill_mod.fill_on_device(
-        ctx, device_frames, dst, mask, plan.final_matrices, np.asarray(em["matrices"], dtype=np.float32), em["confidences"], radius)
+        ctx, device_frames, dst, mask, plan.final_matrices, np.asarray(em["matrices"], dtype=np.float32), em["confidences"], radius,
+        feather=blend[0], exposure=blend[1])
 
 
 def _spatial_fill(ctx, dst, mask, plan, meta, enabled: bool) -> None:
@@ -703,7 +705,7 @@ def _dynamic_zoom(ctx, zoom, plan, offsets, segments):
 def _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode, camera_lock,
                                 strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested, pbar, progress_total,
                                 keep_on_device, temporal_fill=0, blocked=None, mask_info=None, spatial_fill=False,
-                                stability_report=False):
+                                stability_report=False, fill_blend=(None, False)):
     """F2-F14 with the plan formed on the device (see above).  Returns None when F0 found 0..255 float data: the
     speculative run used the unscaled frames and is discarded; the caller takes the regular path on the rescaled clip."""
     size = (context.width, context.height)
@@ -748,7 +750,7 @@ def _stabilize_with_device_plan(ctx, context, device_frames, working_size, total
     meta = complete_meta(meta, plan, _counts_to_host(counts, mirrored=mirror_ok))
     if mask_info is not None:
         meta["estimation_mask"] = estimation_mask_meta(fit_records, *mask_info)
-    _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill)   # on the host plan's verified matrices
+    _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill, fill_blend)   # on the host plan's verified matrices
     _spatial_fill(ctx, dst, mask, plan, meta, spatial_fill)
     _stability_report(ctx, device_frames, dst, mask, plan, meta, stability_report)
     check_interrupt()
@@ -784,6 +786,8 @@ def _stabilize_frames(
     dynamic_zoom=None,
     zoom_limit=None,
     subject_mask=None,
+    fill_feather=None,
+    fill_exposure: bool = False,
 ) -> hm.StabilizationResult:
     """Positional signature of the reference (flow.py:213-223); keyword-only extras select the GPU
     context, keep outputs resident in HBM (multi-GPU sharding lives in distributed.py) or switch the
@@ -835,7 +839,16 @@ def _stabilize_frames(
     frames without a subject are interpolated and reported with confidence 0.  Everything behind the fit table is unchanged:
     camera_lock=True pins the subject where frame 0 shows it.  For translation / similarity, without temporal_fill,
     estimation_mask, mesh_warp or scene_cuts="auto"; meta["subject_lock"] reports centroids and gaps.  None: the behaviour and
-    meta without it, byte for byte, and nothing is launched.  Bypass paths ignore it."""
+    meta without it, byte for byte, and nothing is launched.  Bypass paths ignore it.
+    fill_feather, fill_exposure (beyond the reference, None / False by default; with temporal_fill > 0 only): how the temporal
+    fill writes its pixels (temporal_fill.py; include/vstab.h states both rules).  fill_exposure=True scales what a neighbour
+    supplies by one gain per channel, the ratio of the two frames' sums over the lattice of pixels both see, so a clip shot
+    with auto exposure leaves no brightness step at the filled border.  fill_feather = True (16 px) or an int in 0..64
+    cross-fades the frame's own pixels within that many source pixels of its border into the neighbour's, which also
+    replaces the ring of own pixels the padding colour was interpolated into.  Each works without the other;
+    meta["temporal_fill"] gains feather_px, blended_fraction_* and exposure.  Not in sub-pixel mode 'exact'.  None / False:
+    the behaviour and meta without them, byte for byte, and nothing new is launched.  `crop` framing and bypass paths
+    ignore them."""
     zoom = dynamic_zoom_mod.check_request(dynamic_zoom, zoom_limit)
     if zoom is not None:
         dynamic_zoom_mod.check_pipeline(framing_mode)
@@ -851,6 +864,7 @@ def _stabilize_frames(
     temporal_fill = int(temporal_fill)
     if not 0 <= temporal_fill <= temporal_fill_mod.MAX_RADIUS:
         raise ValueError(f"temporal_fill={temporal_fill} outside [0, {temporal_fill_mod.MAX_RADIUS}]")
+    fill_blend = temporal_fill_mod.check_blend_request(temporal_fill, fill_feather, fill_exposure)
     estimator = resolve_flow_backend(estimator)
     if estimation_mask is not None:
         mask_margin = check_estimation_mask_request(estimator, mask_margin)
@@ -932,7 +946,7 @@ def _stabilize_frames(
         done = _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode,
                                            camera_lock, strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested,
                                            pbar, progress_total, keep_on_device, temporal_fill, blocked, mask_info, spatial_fill,
-                                           stability_report)
+                                           stability_report, fill_blend)
         if done is not None:
             return done
         device_frames = context.device_batch(ctx)   # F0 rescaled the clip: everything is redone on the rescaled frames below
@@ -1003,7 +1017,7 @@ def _stabilize_frames(
         meta["mesh_warp"] = mesh_block
     if subject:
         meta["subject_lock"] = masked["subject"]["block"]
-    _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill)
+    _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill, fill_blend)
     _spatial_fill(ctx, dst, mask, plan, meta, spatial_fill)
     _stability_report(ctx, device_frames, dst, mask, plan, meta, stability_report, segments)
     check_interrupt()

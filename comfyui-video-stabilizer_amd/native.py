@@ -199,6 +199,13 @@ _SIGNATURES = {
     "vstab_temporal_fill_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                   C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vstab_fill_gain_sums": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vstab_temporal_fill_blend_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                  C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                  C.c_void_p, C.c_void_p]),
     "vstab_spatial_fill_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vstab_frame_sse_batch": (
@@ -995,6 +1002,75 @@ class Context:
             _dev_ptr(fill_count) if fill_count is not None else None,
             _dev_ptr(pad_count) if pad_count is not None else None), "vstab_temporal_fill_batch")
         return filled_from, fill_count, pad_count
+
+    def _fill_blend_io(self, who, clip_frames, matrices, cand_frame, own_matrices, dst, mask, subpix):
+        """The arguments the two blended-fill entries share, checked as temporal_fill_batch checks its own."""
+        torch = self.torch
+        src = self._as_device_frames(clip_frames)
+        total, sh, sw, ch = src.shape
+        if ch != 3:
+            raise VstabError(f"{who} expects 3-channel frames, got {ch}")
+        if (subpix or DEFAULT_SUBPIX) != "q5":
+            raise VstabError(f"{who}: sub-pixel mode {(subpix or DEFAULT_SUBPIX)!r} is not supported; the blended fill is 'q5' only")
+        for name, t in (("dst", dst), ("mask", mask)):
+            if t is None and name == "mask":
+                continue
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()):
+                raise VstabError(f"{who}: {name} must be a contiguous float32 tensor on {self.device}")
+        if dst.dim() != 4 or dst.shape[3] != 3 or (mask is not None and mask.numel() * 3 != dst.numel()):
+            raise VstabError(f"{who}: dst {tuple(dst.shape)} / mask {tuple(mask.shape) if mask is not None else None} do not match")
+        n, out_h, out_w = int(dst.shape[0]), int(dst.shape[1]), int(dst.shape[2])
+        cf = np.ascontiguousarray(cand_frame, dtype=np.int32)
+        if cf.ndim != 2 or cf.shape[0] != n:
+            raise VstabError(f"{who}: cand_frame {cf.shape} is not [n={n}, K]")
+        k = int(cf.shape[1])
+        m = np.ascontiguousarray(matrices, dtype=np.float32)
+        if m.size != n * k * 9:
+            raise VstabError(f"{who}: matrices {m.shape} are not [n={n}, K={k}, 3, 3]")
+        own = np.ascontiguousarray(own_matrices, dtype=np.float32)
+        if own.size != n * 9:
+            raise VstabError(f"{who}: own_matrices {own.shape} are not [n={n}, 3, 3]")
+        return src, (total, sh, sw), (n, out_h, out_w, k), m, cf, own
+
+    def fill_gain_sums(self, clip_frames, matrices, cand_frame, own_matrices, dst, first=0, interp="bilinear", subpix=None):
+        """The integer sums behind the blended fill's exposure gains (include/vstab.h: vstab_fill_gain_sums), for output frames
+        [first, first + n): clip_frames / matrices / cand_frame as temporal_fill_batch takes them, own_matrices [n,3,3] f32 (the
+        frames' own forward matrices), dst [n,h,w,3] f32 device as the warp left it (read only).
+        -> sums i64 [n,K,7] device tensor: count, own r g b, candidate r g b (see temporal_fill.gains_from_sums)."""
+        src, (total, sh, sw), (n, out_h, out_w, k), m, cf, own = self._fill_blend_io(
+            "fill_gain_sums", clip_frames, matrices, cand_frame, own_matrices, dst, None, subpix)
+        sums = self.torch.empty((n, k, 7), dtype=self.torch.int64, device=self.device)
+        self.use_torch_stream()
+        _check(self.lib.vstab_fill_gain_sums(
+            self.handle, _dev_ptr(src), total, sh, sw, int(first), n, m.ctypes.data, cf.ctypes.data, k, own.ctypes.data, out_h,
+            out_w, INTERP[interp], SUBPIX["q5"], _dev_ptr(dst), _dev_ptr(sums)), "vstab_fill_gain_sums")
+        return sums
+
+    def temporal_fill_blend_batch(self, clip_frames, matrices, cand_frame, own_matrices, gains, dst, mask, feather_px=0, first=0,
+                                  interp="bilinear", subpix=None, want_filled_from=False, want_counts=True):
+        """temporal_fill_batch with a gain per (frame, candidate, channel) on what a candidate supplies and a feather of
+        feather_px (0..64) source pixels in which the frame's own border pixels fade into the first valid candidate, in
+        place (include/vstab.h: vstab_temporal_fill_blend_batch).  own_matrices [n,3,3] f32, gains [n,K,3] f32; the rest as
+        temporal_fill_batch.  'q5' only.
+        -> (filled_from i8 [n,h,w] | None, fill_count, pad_count, blend_count i32 [n] | None), device tensors."""
+        torch = self.torch
+        src, (total, sh, sw), (n, out_h, out_w, k), m, cf, own = self._fill_blend_io(
+            "temporal_fill_blend_batch", clip_frames, matrices, cand_frame, own_matrices, dst, mask, subpix)
+        if mask is None:
+            raise VstabError("temporal_fill_blend_batch: mask must be a contiguous float32 tensor")
+        g = np.ascontiguousarray(gains, dtype=np.float32)
+        if g.size != n * k * 3:
+            raise VstabError(f"temporal_fill_blend_batch: gains {g.shape} are not [n={n}, K={k}, 3]")
+        feather_px = int(feather_px)
+        filled_from = torch.empty((n, out_h, out_w), dtype=torch.int8, device=self.device) if want_filled_from else None
+        counts = [torch.empty((n,), dtype=torch.int32, device=self.device) if want_counts else None for _ in range(3)]
+        self.use_torch_stream()
+        _check(self.lib.vstab_temporal_fill_blend_batch(
+            self.handle, _dev_ptr(src), total, sh, sw, int(first), n, m.ctypes.data, cf.ctypes.data, k, own.ctypes.data,
+            g.ctypes.data, feather_px, out_h, out_w, INTERP[interp], SUBPIX["q5"], _dev_ptr(dst), _dev_ptr(mask),
+            _dev_ptr(filled_from) if filled_from is not None else None,
+            *[_dev_ptr(c) if c is not None else None for c in counts]), "vstab_temporal_fill_blend_batch")
+        return filled_from, counts[0], counts[1], counts[2]
 
     # ------------------------------------------------------------------ spatial fill
     def spatial_fill_batch(self, dst, mask, chunk_frames=0, want_counts=True):

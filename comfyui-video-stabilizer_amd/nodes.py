@@ -384,9 +384,16 @@ class VideoStabilizerTemporalFill(io.ComfyNode):
     @classmethod
     def execute(cls, frames: Any, frames_stabilized: Any, padding_mask: Any, meta: dict, radius: int,
                 interpolation: str) -> io.NodeOutput:
+        return cls._fill(frames, frames_stabilized, padding_mask, meta, radius, interpolation)
+
+    @classmethod
+    def _fill(cls, frames: Any, frames_stabilized: Any, padding_mask: Any, meta: dict, radius: int, interpolation: str,
+              feather=None, exposure: bool = False) -> io.NodeOutput:
+        """The node's work; feather / exposure are the blended node's two sockets (None / False: the plain fill)."""
         from . import native, temporal_fill
 
         plan = temporal_fill.plan_from_meta(meta)   # ValueError naming the missing key, before any GPU work
+        feather, exposure = temporal_fill.check_blend_request(int(radius), feather, exposure)
         if interpolation not in native.INTERP:
             raise ValueError(f"Unknown interpolation {interpolation!r}; expected 'bilinear' or 'bicubic'.")
         context = hm._normalize_video_input(frames)
@@ -415,11 +422,45 @@ class VideoStabilizerTemporalFill(io.ComfyNode):
             raise ValueError(f"temporal fill: padding_mask {tuple(mask.shape)} does not match the stabilized frames {tuple(dst.shape[:3])}")
         mask = mask.contiguous().clone()
         block = temporal_fill.fill_on_device(ctx, src, dst, mask, plan["final_matrices"], plan["transitions"],
-                                             plan["confidences"], int(radius), interp=interpolation)
+                                             plan["confidences"], int(radius), interp=interpolation, feather=feather,
+                                             exposure=exposure)
         block["interpolation"] = interpolation
         out_meta = dict(meta)
         out_meta["temporal_fill"] = block
         return io.NodeOutput(_image_out(dst, out_context), _mask_out(mask), out_meta)
+
+
+class VideoStabilizerTemporalFillBlend(VideoStabilizerTemporalFill):
+    """The Temporal Fill node with an exposure-matched, feathered seam (temporal_fill.py: `feather`, `exposure`).  Not one of
+    the reference's nodes: it is listed by VideoStabilizerAmdFillBlendExtension and kept out of NODE_CLASSES."""
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        schema = io.Schema(
+            node_id="video_stabilizer_temporal_fill_blend",
+            display_name="Video Stabilizer Temporal Fill (Blended)",
+            category="Video/Stabilization",
+            description=("Video Stabilizer Temporal Fill whose filled pixels are matched to the frame's exposure and fade into "
+                         "the frame's own content over a feather, instead of meeting it at a hard cut."),
+        )
+        base = VideoStabilizerTemporalFill.define_schema()
+        schema.inputs = list(base.inputs) + [
+            io.Int.Input("feather", default=16, min=0, max=64, display_name="Feather",
+                         tooltip=("Width in source pixels over which the frame's own border fades into the neighbour's content; "
+                                  "0 keeps the hard seam.")),
+            io.Boolean.Input("match_exposure", default=True, display_name="Match Exposure",
+                             tooltip="Scale what a neighbouring frame supplies to this frame's brightness, per channel."),
+        ]
+        schema.outputs = list(base.outputs)
+        return schema
+
+    @classmethod
+    def execute(cls, frames: Any, frames_stabilized: Any, padding_mask: Any, meta: dict, radius: int, interpolation: str,
+                feather: int, match_exposure: bool) -> io.NodeOutput:
+        if isinstance(feather, bool):
+            raise ValueError(f"feather={feather!r} is not an integer in 0..64")
+        return cls._fill(frames, frames_stabilized, padding_mask, meta, radius, interpolation, feather=feather,
+                         exposure=match_exposure)
 
 
 class VideoStabilizerFlowMasked(io.ComfyNode):
@@ -916,3 +957,11 @@ class VideoStabilizerAmdSubjectExtension(VideoStabilizerAmdZoomExtension):
 
     async def get_node_list(self) -> list:
         return await super().get_node_list() + [VideoStabilizerFlowSubject]
+
+
+class VideoStabilizerAmdFillBlendExtension(VideoStabilizerAmdSubjectExtension):
+    """The subject extension's sixteen nodes plus Video Stabilizer Temporal Fill (Blended).  A class of its own for the
+    reason the eight before it are: comfy_entrypoint() keeps handing out its own."""
+
+    async def get_node_list(self) -> list:
+        return await super().get_node_list() + [VideoStabilizerTemporalFillBlend]

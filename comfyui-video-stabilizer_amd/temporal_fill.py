@@ -12,6 +12,13 @@ i.e. source frame j reaches the canvas of frame i through the FORWARD matrix
 `fill_candidates` forms these on the host (NumPy float64, one cast to float32); the kernel behind
 `native.Context.temporal_fill_batch` (csrc/vstab_warp.hip: temporal_fill_kernel) warps the first candidate whose every
 interpolation tap lies inside its frame into the pixel -- see include/vstab.h for the exact rule.  Off by default.
+
+That fill is a hard cut: a neighbour's raw value next to the frame's own content.  Two options, each off by default and each
+working without the other, go through `native.Context.temporal_fill_blend_batch` instead (temporal_fill_blend_kernel):
+`exposure` scales what candidate j supplies to frame i by one gain per channel, the ratio of the two frames' sums over the
+lattice of pixels both see (`native.Context.fill_gain_sums`, then `gains_from_sums`), and `feather` cross-fades the frame's own
+pixels within that many source pixels of its border into the candidate, which also replaces the ring of own pixels the
+padding colour was interpolated into.  include/vstab.h states both rules.
 """
 
 from __future__ import annotations
@@ -21,6 +28,12 @@ from typing import Any, Dict, Optional, Tuple
 import numpy as np
 
 MAX_RADIUS = 32   # K = 2 * radius candidates per frame; the kernel takes K <= 64
+MAX_FEATHER = 64          # VSTAB_FILL_FEATHER_MAX
+DEFAULT_FEATHER = 16      # fill_feather=True
+# Choices, not calibrations (like the lattice stride of 8, VSTAB_FILL_GAIN_STRIDE): a gain needs an overlap of at least
+# GAIN_MIN_COUNT lattice pixels (a 45 x 45 px patch) and stays within one photographic stop either way.
+GAIN_MIN_COUNT = 32
+GAIN_CLAMP = (0.5, 2.0)
 
 
 def _finite(m: np.ndarray) -> bool:
@@ -143,10 +156,85 @@ def fill_meta(radius: int, fill_counts, pad_counts, output_size) -> Dict[str, An
             "padding_fraction_mean_after": float(np.mean(left)), "padding_fraction_max_after": float(np.max(left))}
 
 
+def gains_from_sums(sums) -> np.ndarray:
+    """sums [n,K,7] (count, own r g b, candidate r g b: vstab_fill_gain_sums) -> gains float32 [n,K,3], formed in float64:
+    g_c = own_c / cand_c, clamped to GAIN_CLAMP, where count >= GAIN_MIN_COUNT and cand_c >= 1; 1.0 otherwise.  The gain
+    relates candidate j to frame i directly, over their own overlap: nothing accumulates along a chain."""
+    s = np.asarray(sums).astype(np.float64)
+    if s.ndim != 3 or s.shape[2] != 7:
+        raise ValueError(f"temporal fill: gain sums {s.shape} are not [n, K, 7]")
+    own, cand = s[..., 1:4], s[..., 4:7]
+    ok = (s[..., 0:1] >= GAIN_MIN_COUNT) & (cand >= 1.0)
+    ratio = np.clip(own / np.where(ok, cand, 1.0), GAIN_CLAMP[0], GAIN_CLAMP[1])
+    return np.where(ok, ratio, 1.0).astype(np.float32)
+
+
+def check_blend_request(temporal_fill: int, fill_feather=None, fill_exposure=False, subpix=None):
+    """-> (feather px | None, exposure bool) of a `fill_feather` / `fill_exposure` request; None, False = neither.
+    fill_feather: None (or False) is off, True is DEFAULT_FEATHER px, an int in 0..MAX_FEATHER is that width.  Everything is
+    checked here, before any GPU work: either option needs temporal_fill > 0 and the 'q5' sub-pixel mode."""
+    if fill_feather is None or fill_feather is False:
+        feather = None
+    elif fill_feather is True:
+        feather = DEFAULT_FEATHER
+    elif isinstance(fill_feather, (int, np.integer)) and 0 <= int(fill_feather) <= MAX_FEATHER:
+        feather = int(fill_feather)
+    else:
+        raise ValueError(f"fill_feather={fill_feather!r} is not None, True or an integer in 0..{MAX_FEATHER}")
+    if not isinstance(fill_exposure, (bool, np.bool_)):
+        raise ValueError(f"fill_exposure={fill_exposure!r} is not a bool")
+    exposure = bool(fill_exposure)
+    if feather is None and not exposure:
+        return None, False
+    if int(temporal_fill) <= 0:
+        raise ValueError(f"fill_feather={fill_feather!r} / fill_exposure={fill_exposure!r} need temporal_fill > 0: they change how the "
+                         "temporal fill writes its pixels")
+    if subpix is None:
+        from . import native
+        subpix = native.DEFAULT_SUBPIX
+    if subpix != "q5":
+        raise ValueError(f"fill_feather / fill_exposure are not supported in sub-pixel mode {subpix!r}: the blended fill is stated on "
+                         "the 1/32-px coordinates of 'q5'")
+    return feather, exposure
+
+
+def blend_meta(feather_px: int, blend_counts, output_size, matched: bool, gains, counted, cand_frame) -> Dict[str, Any]:
+    """The keys the blended fill adds to the `temporal_fill` block.  gains [n,K,3]; counted [n,K] bool: the candidate's overlap
+    reached GAIN_MIN_COUNT (None without exposure matching); gain_min / gain_max run over those candidates."""
+    pixels = np.float32(int(output_size[0]) * int(output_size[1]))
+    blended = (np.asarray(blend_counts, dtype=np.int64).astype(np.float32) / pixels).astype(np.float64)
+    exposure = {"matched": bool(matched), "gain_min": 1.0, "gain_max": 1.0, "candidates_without_overlap": 0}
+    if matched:
+        present = np.asarray(cand_frame) >= 0
+        used = present & np.asarray(counted, dtype=bool)
+        if used.any():
+            g = np.asarray(gains, dtype=np.float32)[used]
+            exposure["gain_min"], exposure["gain_max"] = float(g.min()), float(g.max())
+        exposure["candidates_without_overlap"] = int((present & ~used).sum())
+    return {"feather_px": int(feather_px), "blended_fraction_mean": float(np.mean(blended)),
+            "blended_fraction_max": float(np.max(blended)), "exposure": exposure}
+
+
 def fill_on_device(ctx, device_frames, dst, mask, final_matrices, transitions, confidences, radius: int,
-                   interp: str = "bilinear", subpix=None) -> Dict[str, Any]:
-    """Runs the fill over a whole clip in place (dst [N,h,w,3], mask [N,h,w], device) and returns the meta block."""
+                   interp: str = "bilinear", subpix=None, feather=None, exposure=False) -> Dict[str, Any]:
+    """Runs the fill over a whole clip in place (dst [N,h,w,3], mask [N,h,w], device) and returns the meta block.
+    feather (px, None = off) or exposure=True switch to the blended entry; exposure off means gains of 1, exposure on the
+    sums launch in front of the fill, one small download and `gains_from_sums`."""
     mats, cand = fill_candidates(final_matrices, transitions, confidences, radius)
-    _, fill_count, pad_count = ctx.temporal_fill_batch(device_frames, mats, cand, dst, mask, first=0, interp=interp, subpix=subpix)
-    counts = ctx.torch.stack([fill_count, pad_count]).cpu().numpy()
-    return fill_meta(radius, counts[0], counts[1], (dst.shape[2], dst.shape[1]))
+    if feather is None and not exposure:
+        _, fill_count, pad_count = ctx.temporal_fill_batch(device_frames, mats, cand, dst, mask, first=0, interp=interp, subpix=subpix)
+        counts = ctx.torch.stack([fill_count, pad_count]).cpu().numpy()
+        return fill_meta(radius, counts[0], counts[1], (dst.shape[2], dst.shape[1]))
+    feather_px = 0 if feather is None else int(feather)
+    own = np.asarray(final_matrices, dtype=np.float32).reshape(-1, 3, 3)
+    gains, counted = np.ones(cand.shape + (3,), np.float32), None
+    if exposure:
+        sums = ctx.fill_gain_sums(device_frames, mats, cand, own, dst, first=0, interp=interp, subpix=subpix).cpu().numpy()
+        gains, counted = gains_from_sums(sums), sums[..., 0] >= GAIN_MIN_COUNT
+    _, fill_count, pad_count, blend_count = ctx.temporal_fill_blend_batch(
+        device_frames, mats, cand, own, gains, dst, mask, feather_px=feather_px, first=0, interp=interp, subpix=subpix)
+    counts = ctx.torch.stack([fill_count, pad_count, blend_count]).cpu().numpy()
+    size = (dst.shape[2], dst.shape[1])
+    block = fill_meta(radius, counts[0], counts[1], size)
+    block.update(blend_meta(feather_px, counts[2], size, bool(exposure), gains, counted, cand))
+    return block

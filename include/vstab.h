@@ -459,6 +459,56 @@ int vstab_temporal_fill_batch(vstab_ctx* ctx, const float* src, int clip_frames,
                               int subpix, float* dst, float* mask, int8_t* filled_from, uint32_t* fill_count,
                               uint32_t* pad_count);
 
+/* ---- blended temporal fill: exposure-matched candidates and a feathered seam (beyond the reference, off by default) ----
+ * vstab_temporal_fill_batch writes a hard cut: the raw value of a neighbour frame next to the frame's own content.  The two
+ * entries below take the same candidates (matrices, cand_frame: as above, and skipped as above) plus the frame's OWN forward
+ * matrix (own_matrices host [n, 9] f32, source frame first + f -> its output canvas; "usable" = a candidate's matrix test).
+ * Both are VSTAB_SUBPIX_Q5 only (VSTAB_SUBPIX_EXACT is refused), bilinear and bicubic.  "Q5 coordinate" = the integers X, Y
+ * (1/32 px) that vstab_warp_batch forms for a matrix at an output pixel; "inside" = the interior rule above on X >> 5, Y >> 5.
+ *
+ * vstab_fill_gain_sums -- per output frame f and candidate k, over the lattice of output pixels with
+ * x % VSTAB_FILL_GAIN_STRIDE == VSTAB_FILL_GAIN_STRIDE / 2 && y % VSTAB_FILL_GAIN_STRIDE == VSTAB_FILL_GAIN_STRIDE / 2:
+ *   - a lattice pixel COUNTS for (f, k) iff its Q5 coordinate under the own matrix is inside AND its Q5 coordinate under
+ *     candidate k is inside.  A skipped candidate counts nothing; a non-usable own matrix counts nothing for the frame.
+ *   - own value = dst[f, y, x, c] as the warp left it; candidate value = the sample vstab_temporal_fill_batch would write
+ *     for that candidate.  q(v) = v > 0 ? (v < 1 ? (uint32)(v * 65536.0f) : 65536) : 0 (a NaN gives 0).
+ *   - sums[f, k] = { count, sum q(own r), q(own g), q(own b), sum q(cand r), q(cand g), q(cand b) }: integer sums, the same
+ *     whatever the order of addition.  The call zeroes them itself.  It only reads dst: queue it in front of the fill.
+ * dst   dev [n, out_h, out_w, 3] f32 (read only);  sums dev [n, K, 7] u64.  Timing kind "fill_gain".
+ * The gain the host forms from them (temporal_fill.gains_from_sums) relates candidate and frame over their own overlap, so
+ * nothing accumulates along a chain.  The stride of 8 is a choice (1/64 of the pixels: thousands of samples at 1080p), not a
+ * calibration. */
+#define VSTAB_FILL_GAIN_STRIDE 8
+int vstab_fill_gain_sums(vstab_ctx* ctx, const float* src, int clip_frames, int src_h, int src_w, int first, int n,
+                         const float* matrices, const int32_t* cand_frame, int K, const float* own_matrices, int out_h,
+                         int out_w, int interp, int subpix, const float* dst, uint64_t* sums);
+
+/* vstab_temporal_fill_blend_batch -- per output pixel, with Fe = 32 * feather_px:
+ *   - mask == 1.0f (padded): the candidates are walked exactly as vstab_temporal_fill_batch walks them.  The first valid
+ *     candidate k with sample s writes dst_c = gains[f, k, c] * s_c (one float32 multiply; nothing of the old pixel is read,
+ *     so a NaN in the padding cannot leak), mask = 0, filled_from = k, and counts in fill_count.  None valid: untouched.
+ *   - mask != 1.0f (own), only with feather_px > 0 and a usable own matrix: with X, Y the Q5 coordinate under the own matrix,
+ *     d32 = the distance to the tap-interior border, formed without 32-bit overflow:
+ *       bilinear  d32 = min(X, Y, 32 * (src_w - 1) - X, 32 * (src_h - 1) - Y)
+ *       bicubic   d32 = min(X - 32, Y - 32, 32 * (src_w - 2) - X, 32 * (src_h - 2) - Y)
+ *     and w = (float)min(max(d32, 0), Fe) / (float)Fe.  w == 1.0f: untouched, nothing is stored.  Otherwise the candidates
+ *     are walked as for a padded pixel; the first valid one gives c_c = gains[f, k, c] * s_c and
+ *       dst_c = (w == 0) ? c_c : own_c * w + c_c * (1.0f - w)     (float32, separate roundings, nothing fused)
+ *     with own_c the pixel's value before the call; the mask stays as it is, filled_from = k, and the pixel counts in
+ *     blend_count.  None valid: untouched.  So the ring of own pixels the padding colour was interpolated into (d32 <= 0,
+ *     mask 0) is replaced by neighbour content, and the seam fades over feather_px source pixels.
+ *   - feather_px == 0 and every gain == 1.0f: dst, mask, filled_from, fill_count and pad_count are those of
+ *     vstab_temporal_fill_batch, bit for bit, and blend_count is 0.
+ * gains       host [n, K, 3] f32;  feather_px in 0..VSTAB_FILL_FEATHER_MAX
+ * blend_count dev  [n] u32 or NULL;  pad_count: the pixels whose mask is still 1.0f afterwards, as above.
+ * filled_from is -1 where a pixel was neither filled nor blended.  Timing kind "fill_blend". */
+#define VSTAB_FILL_FEATHER_MAX 64
+int vstab_temporal_fill_blend_batch(vstab_ctx* ctx, const float* src, int clip_frames, int src_h, int src_w, int first, int n,
+                                    const float* matrices, const int32_t* cand_frame, int K, const float* own_matrices,
+                                    const float* gains, int feather_px, int out_h, int out_w, int interp, int subpix,
+                                    float* dst, float* mask, int8_t* filled_from, uint32_t* fill_count, uint32_t* pad_count,
+                                    uint32_t* blend_count);
+
 /* ---- mesh warp (not a reference feature, off by default): the residual motion one global fit leaves ------------
  * One matrix per frame cannot express parallax, rolling-shutter skew or lens breathing.  What it leaves is measured on a
  * coarse mesh of mw x mh vertices (MeshFlow, Liu et al., ECCV 2016: per-vertex motion profiles) and taken out by a second,
