@@ -1,6 +1,6 @@
 // vstab_warp.hip -- perspective/similarity warp with padding mask, its mesh-displaced forms (mesh_warp_kernel and its
 // inverse, mesh_unwarp_kernel), the multi-sample motion blur, the temporal fill (plain, and blended: fill_gain_sums_kernel,
-// temporal_fill_blend_kernel) and the coverage extent of the dynamic zoom
+// temporal_fill_blend_kernel), the sharpness transfer (sharp_transfer_kernel) and the coverage extent of the dynamic zoom
 // (cover_extent_kernel: warp_pixel's coverage bit alone, nothing sampled).
 // All of them take their coordinates from ONE definition, warp_pixel, and
 // share one tile shell (TileShell, warp_kernel's body, block_count_add); the scalar pieces that vstab_crop / vstab_dis / vstab_tvl1
@@ -2001,6 +2001,171 @@ extern "C" int vstab_temporal_fill_blend_batch(vstab_ctx* ctx, const float* src,
     const dim3 grid(blocks), block(256);
     if (interp == VSTAB_INTERP_BICUBIC) hipLaunchKernelGGL((temporal_fill_blend_kernel<VSTAB_INTERP_BICUBIC>), grid, block, 0, ctx->stream, a, cands, own, gains_dev);
     else hipLaunchKernelGGL((temporal_fill_blend_kernel<VSTAB_INTERP_BILINEAR>), grid, block, 0, ctx->stream, a, cands, own, gains_dev);
+    VSTAB_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- sharpness transfer: own pixels of a blurred frame pulled towards what sharper neighbours show there -------------------
+//
+// The rule is stated in include/vstab.h (vstab_sharp_transfer_batch; Matsushita et al., PAMI 2006, section 5).  The fill's
+// tile, shell, XCD remap, candidate records and sampler (fill_candidate_sample: warp_pixel with the interior test), but the
+// other way round: the fill writes PADDED pixels from the FIRST valid candidate, this writes OWN pixels from EVERY valid
+// candidate with a positive ratio, weighted by how well the sample agrees with the pixel.
+//
+// Shape: only frames with a live candidate (ratio > 0, not skipped) get workgroups at all -- the host lists them
+// (`live`), so a clip without a blurred frame launches nothing and a frame that borrows nothing costs nothing: the
+// "all ratios zero" exit is taken before the launch instead of per block.  A tile reads its mask and returns if it has
+// no own pixel.  Candidates whose ratio is 0 or that are skipped are passed over block-uniformly (scalar loads of the
+// record and the ratio); there is no "first wins" exit, so every other candidate is sampled for every own pixel.  Per
+// pixel the kernel keeps o (3), num (3) and den (1) in registers, two pixels per thread.
+// Resource usage (-Rpass-analysis=kernel-resource-usage, gfx950): bilinear 52 VGPRs, 8 waves per SIMD; bicubic 100 VGPRs, 4
+// waves per SIMD; no scratch in either.
+// The two divisions are IEEE-correct (-fhip-fp32-correctly-rounded-divide-sqrt, csrc/Makefile) and nothing is fused
+// (-ffp-contract=off), so NumPy float32 gives the same bits.
+namespace {
+
+struct SharpArgs {
+    const float* src;
+    float* dst;
+    const float* mask;          // nullptr: every pixel is own
+    unsigned* transfer_count;
+    float alpha;
+    int K, sh, sw, dh, dw;
+    int bw0, bw0_pow2;
+    int tiles_x, tiles_y;
+};
+
+template <int INTERP>
+__global__ __launch_bounds__(256) void sharp_transfer_kernel(SharpArgs a, const FillCand* __restrict__ cands,
+                                                             const float* __restrict__ ratios, const int* __restrict__ live)
+{
+    constexpr int TILE_TX = 32;
+    __shared__ __attribute__((aligned(16))) float s_cub[32 * 4];
+    const TileShell<TILE_TX> t(a.tiles_x, a.tiles_y, a.dh, a.dw);
+    const int frame = live[t.frame], x0 = t.x0, y = t.y, npx = t.npx;      // t.frame counts the live frames
+
+    const unsigned row = (unsigned)y * (unsigned)a.dw;
+    bool own[TILE_PX];
+    bool any = false;
+#pragma unroll
+    for (int p = 0; p < TILE_PX; p++) {
+        own[p] = p < npx;
+        if (own[p] && a.mask != nullptr) own[p] = !(a.mask[(size_t)frame * a.dh * a.dw + row + (unsigned)(x0 + p * TILE_TX)] == 1.0f);
+        any = any || own[p];
+    }
+    if (!__syncthreads_or(any)) return;   // a tile of padding: nothing to read, store or count
+
+    const float* cub_tab = nullptr;
+    if (INTERP == VSTAB_INTERP_BICUBIC) {
+        if (threadIdx.x < 32) cubic_coeffs((int)threadIdx.x, s_cub + threadIdx.x * 4);
+        __syncthreads();
+        cub_tab = s_cub;
+    }
+
+    float* __restrict__ D = a.dst + (size_t)frame * a.dh * a.dw * 3;
+    const size_t src_frame = (size_t)a.sh * a.sw * 3;
+    const double dy = (double)y;
+    Px o[TILE_PX], num[TILE_PX];
+    float den[TILE_PX];
+#pragma unroll
+    for (int p = 0; p < TILE_PX; p++) {
+        num[p] = Px{0.f, 0.f, 0.f};
+        den[p] = 0.f;
+        o[p] = own[p] ? load_px(D + (row + (unsigned)(x0 + p * TILE_TX)) * 3u) : Px{0.f, 0.f, 0.f};
+    }
+
+    for (int k = 0; k < a.K; k++) {
+        const FillCand* __restrict__ cd = cands + (size_t)frame * a.K + k;
+        const float ratio = ratios[(size_t)frame * a.K + k];
+        if (cd->frame < 0 || !(ratio > 0.f)) continue;             // block-uniform
+        const float* __restrict__ S = a.src + (size_t)cd->frame * src_frame;
+        const WarpXform* __restrict__ xf = &cd->xf;
+        const XformRegs<INTERP, VSTAB_SUBPIX_Q5> r(xf);
+#pragma unroll
+        for (int p = 0; p < TILE_PX; p++) {
+            if (!own[p]) continue;
+            bool valid = false;
+            const Px s = fill_candidate_sample<INTERP>(S, xf, r, a.sh, a.sw, a.dw, a.bw0, a.bw0_pow2, x0 + p * TILE_TX, y, dy, cub_tab, valid);
+            if (!valid) continue;
+            const float Dd = (__builtin_fabsf(s.r - o[p].r) + __builtin_fabsf(s.g - o[p].g)) + __builtin_fabsf(s.b - o[p].b);
+            if (Dd < __builtin_inff()) {                           // false for a NaN in the sample or in the pixel
+                const float w = ratio / (ratio + a.alpha * Dd);
+                num[p].r = num[p].r + w * s.r;
+                num[p].g = num[p].g + w * s.g;
+                num[p].b = num[p].b + w * s.b;
+                den[p] = den[p] + w;
+            }
+        }
+    }
+
+    unsigned cnt[1] = {0u};
+    typedef float f3 __attribute__((ext_vector_type(3)));
+#pragma unroll
+    for (int p = 0; p < TILE_PX; p++) {
+        if (own[p] && den[p] > 0.f) {
+            const float d1 = 1.0f + den[p];
+            const f3 rgb = {(o[p].r + num[p].r) / d1, (o[p].g + num[p].g) / d1, (o[p].b + num[p].b) / d1};
+            __builtin_memcpy(D + (row + (unsigned)(x0 + p * TILE_TX)) * 3u, &rgb, 12);
+            cnt[0] += 1u;
+        }
+    }
+    if (a.transfer_count != nullptr) block_count_add<1>(cnt, {a.transfer_count}, frame);
+}
+
+}  // namespace
+
+extern "C" int vstab_sharp_transfer_batch(vstab_ctx* ctx, const float* src, int clip_frames, int src_h, int src_w, int first, int n,
+                                          const float* matrices, const int32_t* cand_frame, int K, const float* ratio, float alpha,
+                                          int out_h, int out_w, int interp, int subpix, float* dst, const float* mask,
+                                          uint32_t* transfer_count)
+{
+    const char* who = "vstab_sharp_transfer_batch";
+    const float no_border[3] = {0.f, 0.f, 0.f};
+    if (int rc = check_common(who, ctx, src, n, src_h, src_w, matrices, out_h, out_w, interp, no_border, subpix, dst)) return rc;
+    VSTAB_REQUIRE(subpix == VSTAB_SUBPIX_Q5, "%s: VSTAB_SUBPIX_EXACT is not supported (the transfer samples as the blended fill "
+                  "does, on the 1/32-px coordinates of VSTAB_SUBPIX_Q5)", who);
+    VSTAB_REQUIRE(cand_frame != nullptr && ratio != nullptr, "%s: NULL pointer argument", who);
+    VSTAB_REQUIRE(K >= 1 && K <= 64, "%s: K=%d outside [1,64]", who, K);
+    VSTAB_REQUIRE(clip_frames > 0 && first >= 0 && first + n <= clip_frames, "%s: frames [%d, %d) outside a clip of %d frames", who,
+                  first, first + n, clip_frames);
+    VSTAB_REQUIRE((const void*)src != (const void*)dst, "%s: dst must not alias src (candidates read src while dst is written)", who);
+    VSTAB_REQUIRE(alpha >= 0.f && std::isfinite(alpha), "%s: alpha=%g is not a finite number >= 0", who, (double)alpha);
+    const size_t pairs = (size_t)n * K;
+    for (size_t i = 0; i < pairs; i++)
+        VSTAB_REQUIRE(ratio[i] >= 0.f && std::isfinite(ratio[i]), "%s: ratio[%zu]=%g is not a finite number >= 0", who, i, (double)ratio[i]);
+
+    // one staged block: candidate records [n * K], ratios [n * K], the list of live frames [n_live]
+    const size_t rec_bytes = pairs * sizeof(FillCand), ratio_bytes = pairs * sizeof(float);
+    std::vector<unsigned char> blob(rec_bytes + ratio_bytes + (size_t)n * sizeof(int));
+    FillCand* cd = reinterpret_cast<FillCand*>(blob.data());
+    if (int rc = fill_cand_records(who, matrices, cand_frame, pairs, clip_frames, cd)) return rc;
+    memcpy(blob.data() + rec_bytes, ratio, ratio_bytes);
+    int* live = reinterpret_cast<int*>(blob.data() + rec_bytes + ratio_bytes);
+    int n_live = 0;
+    for (int f = 0; f < n; f++) {
+        bool any = false;
+        for (int k = 0; k < K && !any; k++) any = cd[(size_t)f * K + k].frame >= 0 && ratio[(size_t)f * K + k] > 0.f;
+        if (any) live[n_live++] = f;
+    }
+
+    VSTAB_HIP(hipSetDevice(ctx->device));
+    KernelTimer timer(ctx, "sharp_transfer");
+    if (transfer_count) VSTAB_HIP(hipMemsetAsync(transfer_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
+    if (n_live == 0) return 0;                                     // no frame borrows anything: dst keeps every byte
+    SharpArgs a{};
+    a.src = src; a.dst = dst; a.mask = mask; a.transfer_count = transfer_count; a.alpha = alpha;
+    a.K = K; a.sh = src_h; a.sw = src_w; a.dh = out_h; a.dw = out_w;
+    set_block_width(out_h, out_w, &a.bw0, &a.bw0_pow2);
+    unsigned blocks = 0;
+    if (int rc = tile_grid(who, n_live, out_h, out_w, 32, 256, &a.tiles_x, &a.tiles_y, &blocks)) return rc;
+    void* dev = nullptr;
+    if (vstab_stage_params(ctx, blob.data(), rec_bytes + ratio_bytes + (size_t)n_live * sizeof(int), &dev)) return 1;
+    const FillCand* cands = static_cast<const FillCand*>(dev);
+    const float* ratios_dev = reinterpret_cast<const float*>(static_cast<const unsigned char*>(dev) + rec_bytes);
+    const int* live_dev = reinterpret_cast<const int*>(static_cast<const unsigned char*>(dev) + rec_bytes + ratio_bytes);
+    const dim3 grid(blocks), block(256);
+    if (interp == VSTAB_INTERP_BICUBIC) hipLaunchKernelGGL((sharp_transfer_kernel<VSTAB_INTERP_BICUBIC>), grid, block, 0, ctx->stream, a, cands, ratios_dev, live_dev);
+    else hipLaunchKernelGGL((sharp_transfer_kernel<VSTAB_INTERP_BILINEAR>), grid, block, 0, ctx->stream, a, cands, ratios_dev, live_dev);
     VSTAB_HIP(hipGetLastError());
     return 0;
 }

@@ -26,6 +26,7 @@ from . import host_math as hm
 from . import mesh_warp as mesh_warp_mod
 from . import native
 from . import scene_cuts as scene_cuts_mod
+from . import sharpness_transfer as sharpness_transfer_mod
 from . import spatial_fill as spatial_fill_mod
 from . import stability as stability_mod
 from . import subject_lock as subject_lock_mod
@@ -596,6 +597,19 @@ def _temporal_fill(ctx, device_frames, dst, mask, plan, meta, radius: int, blend
         feather=blend[0], exposure=blend[1])
 
 
+def _sharpness_transfer(ctx, device_frames, dst, mask, plan, meta, sharp) -> None:
+    """Pulls the own pixels of blurred frames towards what sharper neighbours show there, in place (sharpness_transfer.py), and
+    adds meta["sharpness_transfer"]; mask and the other meta keys are unchanged.  sharp = (radius, alpha) or None:
+    sharpness_transfer.check_request's answer.  It runs BEFORE the fills: a filled pixel gets mask 0 and would be taken for
+    an own one.  `crop` framing has no padding: every pixel is own."""
+    if sharp is None:
+        return
+    em = plan.estimated_motion
+    meta["sharpness_transfer"] = sharpness_transfer_mod.transfer_on_device(
+        ctx, device_frames, dst, None if plan.framing_mode == "crop" else mask, plan.final_matrices,
+        np.asarray(em["matrices"], dtype=np.float32), em["confidences"], sharp[0], sharp[1])
+
+
 def _spatial_fill(ctx, dst, mask, plan, meta, enabled: bool) -> None:
     """Fills what is still padding from each frame's own valid pixels in place (spatial_fill.py), as the very last pass on
     the outputs, and adds meta["spatial_fill"]; the mask and the other meta keys are unchanged.  `crop` framing has no
@@ -705,7 +719,7 @@ def _dynamic_zoom(ctx, zoom, plan, offsets, segments):
 def _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode, camera_lock,
                                 strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested, pbar, progress_total,
                                 keep_on_device, temporal_fill=0, blocked=None, mask_info=None, spatial_fill=False,
-                                stability_report=False, fill_blend=(None, False)):
+                                stability_report=False, fill_blend=(None, False), sharpness=None):
     """F2-F14 with the plan formed on the device (see above).  Returns None when F0 found 0..255 float data: the
     speculative run used the unscaled frames and is discarded; the caller takes the regular path on the rescaled clip."""
     size = (context.width, context.height)
@@ -750,7 +764,8 @@ def _stabilize_with_device_plan(ctx, context, device_frames, working_size, total
     meta = complete_meta(meta, plan, _counts_to_host(counts, mirrored=mirror_ok))
     if mask_info is not None:
         meta["estimation_mask"] = estimation_mask_meta(fit_records, *mask_info)
-    _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill, fill_blend)   # on the host plan's verified matrices
+    _sharpness_transfer(ctx, device_frames, dst, mask, plan, meta, sharpness)               # on the host plan's verified matrices,
+    _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill, fill_blend)   # and so is the fill
     _spatial_fill(ctx, dst, mask, plan, meta, spatial_fill)
     _stability_report(ctx, device_frames, dst, mask, plan, meta, stability_report)
     check_interrupt()
@@ -788,6 +803,8 @@ def _stabilize_frames(
     subject_mask=None,
     fill_feather=None,
     fill_exposure: bool = False,
+    sharpness_transfer=None,
+    sharpness_alpha=None,
 ) -> hm.StabilizationResult:
     """Positional signature of the reference (flow.py:213-223); keyword-only extras select the GPU
     context, keep outputs resident in HBM (multi-GPU sharding lives in distributed.py) or switch the
@@ -848,7 +865,16 @@ def _stabilize_frames(
     replaces the ring of own pixels the padding colour was interpolated into.  Each works without the other;
     meta["temporal_fill"] gains feather_px, blended_fraction_* and exposure.  Not in sub-pixel mode 'exact'.  None / False:
     the behaviour and meta without them, byte for byte, and nothing new is launched.  `crop` framing and bypass paths
-    ignore them."""
+    ignore them.
+    sharpness_transfer = R in 1..16, sharpness_alpha (beyond the reference, None by default): after the final warp and before
+    any fill, the own pixels of a frame that a camera jolt blurred are pulled towards what the up to R frames before and
+    after show there (sharpness_transfer.py; include/vstab.h states both rules).  Every source frame's gradient energy is
+    measured as one exact integer; frame i borrows from neighbour j only where E_j / E_i >= 1.1, each sample weighted by
+    ratio / (ratio + alpha * D), D the L1 colour distance to the pixel (sharpness_alpha None: 16.0, else in [0, 1024]), the
+    pixel itself with weight 1.  Frames with no sharper neighbour, the mask and every other meta key are unchanged, bit for
+    bit; meta["sharpness_transfer"] lists every frame's sharpness and what was transferred.  Not with mesh_warp, estimator
+    "subject" or sub-pixel mode 'exact'.  0 / None / False: the behaviour and meta without it, byte for byte, and nothing new
+    is launched.  Bypass paths ignore it."""
     zoom = dynamic_zoom_mod.check_request(dynamic_zoom, zoom_limit)
     if zoom is not None:
         dynamic_zoom_mod.check_pipeline(framing_mode)
@@ -865,6 +891,9 @@ def _stabilize_frames(
     if not 0 <= temporal_fill <= temporal_fill_mod.MAX_RADIUS:
         raise ValueError(f"temporal_fill={temporal_fill} outside [0, {temporal_fill_mod.MAX_RADIUS}]")
     fill_blend = temporal_fill_mod.check_blend_request(temporal_fill, fill_feather, fill_exposure)
+    sharpness = sharpness_transfer_mod.check_request(sharpness_transfer, sharpness_alpha)
+    if sharpness is not None:
+        sharpness_transfer_mod.check_pipeline(estimator, mesh)
     estimator = resolve_flow_backend(estimator)
     if estimation_mask is not None:
         mask_margin = check_estimation_mask_request(estimator, mask_margin)
@@ -946,7 +975,7 @@ def _stabilize_frames(
         done = _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode,
                                            camera_lock, strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested,
                                            pbar, progress_total, keep_on_device, temporal_fill, blocked, mask_info, spatial_fill,
-                                           stability_report, fill_blend)
+                                           stability_report, fill_blend, sharpness)
         if done is not None:
             return done
         device_frames = context.device_batch(ctx)   # F0 rescaled the clip: everything is redone on the rescaled frames below
@@ -1017,6 +1046,7 @@ def _stabilize_frames(
         meta["mesh_warp"] = mesh_block
     if subject:
         meta["subject_lock"] = masked["subject"]["block"]
+    _sharpness_transfer(ctx, device_frames, dst, mask, plan, meta, sharpness)
     _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill, fill_blend)
     _spatial_fill(ctx, dst, mask, plan, meta, spatial_fill)
     _stability_report(ctx, device_frames, dst, mask, plan, meta, stability_report, segments)

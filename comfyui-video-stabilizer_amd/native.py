@@ -211,6 +211,10 @@ _SIGNATURES = {
     "vstab_frame_sse_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vstab_mask_moments_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vstab_frame_sharpness_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vstab_sharp_transfer_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                  C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vstab_gftt_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p,
                   C.c_void_p]),
@@ -1004,14 +1008,15 @@ class Context:
         return filled_from, fill_count, pad_count
 
     def _fill_blend_io(self, who, clip_frames, matrices, cand_frame, own_matrices, dst, mask, subpix):
-        """The arguments the two blended-fill entries share, checked as temporal_fill_batch checks its own."""
+        """The arguments the two blended-fill entries and the sharpness transfer share, checked as temporal_fill_batch checks its
+        own (own_matrices None: the entry takes none)."""
         torch = self.torch
         src = self._as_device_frames(clip_frames)
         total, sh, sw, ch = src.shape
         if ch != 3:
             raise VstabError(f"{who} expects 3-channel frames, got {ch}")
         if (subpix or DEFAULT_SUBPIX) != "q5":
-            raise VstabError(f"{who}: sub-pixel mode {(subpix or DEFAULT_SUBPIX)!r} is not supported; the blended fill is 'q5' only")
+            raise VstabError(f"{who}: sub-pixel mode {(subpix or DEFAULT_SUBPIX)!r} is not supported; the entry is 'q5' only")
         for name, t in (("dst", dst), ("mask", mask)):
             if t is None and name == "mask":
                 continue
@@ -1027,9 +1032,11 @@ class Context:
         m = np.ascontiguousarray(matrices, dtype=np.float32)
         if m.size != n * k * 9:
             raise VstabError(f"{who}: matrices {m.shape} are not [n={n}, K={k}, 3, 3]")
-        own = np.ascontiguousarray(own_matrices, dtype=np.float32)
-        if own.size != n * 9:
-            raise VstabError(f"{who}: own_matrices {own.shape} are not [n={n}, 3, 3]")
+        own = None
+        if own_matrices is not None:
+            own = np.ascontiguousarray(own_matrices, dtype=np.float32)
+            if own.size != n * 9:
+                raise VstabError(f"{who}: own_matrices {own.shape} are not [n={n}, 3, 3]")
         return src, (total, sh, sw), (n, out_h, out_w, k), m, cf, own
 
     def fill_gain_sums(self, clip_frames, matrices, cand_frame, own_matrices, dst, first=0, interp="bilinear", subpix=None):
@@ -1147,6 +1154,43 @@ class Context:
         _check(self.lib.vstab_mask_moments_batch(self.handle, _dev_ptr(mask), n, h, w, _dev_ptr(sums), _dev_ptr(bbox)),
                "vstab_mask_moments_batch")
         return sums, bbox
+
+    # ------------------------------------------------------------------ sharpness transfer
+    def frame_sharpness_batch(self, frames):
+        """The gradient energy of every frame of frames [n,h,w,3], f32, device, contiguous, as one exact integer per frame
+        (include/vstab.h states the rule: 16-bit fixed-point luma, forward differences, sum of squares); nothing is written
+        to the frames.  -> energy i64 [n], device tensor."""
+        torch = self.torch
+        if not (isinstance(frames, torch.Tensor) and frames.dtype == torch.float32 and frames.device == self.device and frames.is_contiguous()):
+            raise ValueError(f"frame_sharpness_batch: frames must be a contiguous float32 tensor on {self.device}")
+        if frames.dim() != 4 or frames.shape[3] != 3:
+            raise ValueError(f"frame_sharpness_batch: frames of shape {tuple(frames.shape)} are not [n,h,w,3]")
+        n, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+        energy = torch.empty((n,), dtype=torch.int64, device=self.device)
+        self.use_torch_stream()
+        _check(self.lib.vstab_frame_sharpness_batch(self.handle, _dev_ptr(frames), n, h, w, _dev_ptr(energy)),
+               "vstab_frame_sharpness_batch")
+        return energy
+
+    def sharp_transfer_batch(self, clip_frames, matrices, cand_frame, ratio, alpha, dst, mask=None, first=0, interp="bilinear",
+                             subpix=None, want_counts=True):
+        """Pulls the own pixels (mask != 1; every pixel where mask is None) of output frames [first, first + n) towards what the
+        candidates with a positive ratio show there, in place (include/vstab.h: vstab_sharp_transfer_batch).  clip_frames /
+        matrices / cand_frame as temporal_fill_batch takes them, ratio [n,K] f32 (finite, >= 0), alpha a finite float >= 0,
+        dst [n,h,w,3] f32 device and contiguous, mask [n,h,w] f32 device (read only) or None.  'q5' only.
+        -> transfer_count i32 [n] device tensor | None."""
+        src, (total, sh, sw), (n, out_h, out_w, k), m, cf, _ = self._fill_blend_io(
+            "sharp_transfer_batch", clip_frames, matrices, cand_frame, None, dst, mask, subpix)
+        r = np.ascontiguousarray(ratio, dtype=np.float32)
+        if r.shape != (n, k):
+            raise VstabError(f"sharp_transfer_batch: ratio {r.shape} is not [n={n}, K={k}]")
+        counts = self.torch.empty((n,), dtype=self.torch.int32, device=self.device) if want_counts else None
+        self.use_torch_stream()
+        _check(self.lib.vstab_sharp_transfer_batch(
+            self.handle, _dev_ptr(src), total, sh, sw, int(first), n, m.ctypes.data, cf.ctypes.data, k, r.ctypes.data, float(alpha),
+            out_h, out_w, INTERP[interp], SUBPIX["q5"], _dev_ptr(dst), _dev_ptr(mask) if mask is not None else None,
+            _dev_ptr(counts) if counts is not None else None), "vstab_sharp_transfer_batch")
+        return counts
 
     # ------------------------------------------------------------------ Classic estimator (sparse features + LK)
     def gftt_batch(self, gray, max_corners=400, quality=0.01, min_distance=7.0, block_size=21):

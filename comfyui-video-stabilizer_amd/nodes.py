@@ -463,6 +463,81 @@ class VideoStabilizerTemporalFillBlend(VideoStabilizerTemporalFill):
                          exposure=match_exposure)
 
 
+class VideoStabilizerSharpnessTransfer(io.ComfyNode):
+    """Repairs the shake-blurred frames of a Flow / Classic result from sharper neighbouring frames (sharpness_transfer.py),
+    from the meta JSON alone, like the Temporal Fill node -- in front of which it belongs, since a filled pixel is no longer
+    marked as padding.  Not one of the reference's nodes: it is listed by VideoStabilizerAmdSharpnessExtension and kept out
+    of NODE_CLASSES."""
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        schema = io.Schema(
+            node_id="video_stabilizer_sharpness_transfer",
+            display_name="Video Stabilizer Sharpness Transfer",
+            category="Video/Stabilization",
+            description=("Pulls the pixels of frames a camera jolt blurred towards what sharper neighbouring frames show there, "
+                         "using the stabilizer's own motion metadata; frames with no sharper neighbour pass through unchanged."),
+        )
+        schema.inputs = [
+            io.Image.Input("frames", display_name="Frames", tooltip="The original (unstabilized) frames."),
+            io.Image.Input("frames_stabilized", display_name="Stabilized Frames"),
+            JSONType.Input("meta", display_name="Motion Meta"),
+            io.Int.Input("radius", default=2, min=1, max=16, display_name="Radius",
+                         tooltip="Frames before and after each frame that may lend it their sharpness."),
+            io.Float.Input("alpha", default=16.0, min=0.0, max=1024.0, step=0.5, display_name="Alpha",
+                           tooltip="How fast a neighbour's sample that disagrees with the pixel loses its weight; 0 averages."),
+            io.Mask.Input("padding_mask", display_name="Padding Mask", optional=True,
+                          tooltip="The stabilizer's padding mask; padded pixels are left alone.  Without it every pixel is own."),
+        ]
+        schema.outputs = [
+            io.Image.Output("frames", display_name="Frames"),
+            io.String.Output("meta", display_name="Meta"),
+        ]
+        return schema
+
+    @classmethod
+    def execute(cls, frames: Any, frames_stabilized: Any, meta: dict, radius: int, alpha: float, padding_mask: Any = None) -> io.NodeOutput:
+        import json
+
+        from . import native, sharpness_transfer, temporal_fill
+
+        plan = temporal_fill.plan_from_meta(meta)   # ValueError naming the missing key, before any GPU work
+        radius, alpha = sharpness_transfer.check_request(radius, alpha) or (0, 0.0)
+        if radius == 0:
+            raise ValueError("sharpness transfer: radius=0 transfers nothing; the node needs a radius in 1..16")
+        context = hm._normalize_video_input(frames)
+        out_context = hm._normalize_video_input(frames_stabilized)
+        n = len(plan["final_matrices"])
+        if len(context.frames) != n or len(out_context.frames) != n:
+            raise ValueError(f"sharpness transfer: meta describes {n} frames, got {len(context.frames)} original and "
+                             f"{len(out_context.frames)} stabilized frames")
+        if (context.width, context.height) != plan["source_size"] or (out_context.width, out_context.height) != plan["output_size"]:
+            raise ValueError(f"sharpness transfer: frame sizes {(context.width, context.height)} -> "
+                             f"{(out_context.width, out_context.height)} do not match the meta's "
+                             f"{plan['source_size']} -> {plan['output_size']}")
+        ctx = native.default_context()
+        torch = ctx.torch
+        src = context.device_batch(ctx)
+        if context.range_pending:   # F0's value-range rule, as the stabilizer applied it to these frames
+            if hm.resolve_value_range(context, hm.prefetch_peaks(ctx.frame_range(src)), ctx):
+                src = context.device_batch(ctx)
+        # the transfer works in place: on a copy, so the caller's tensor (another node's cached output) stays as it is
+        dst = out_context.device_batch(ctx).clone()
+        mask = None
+        if padding_mask is not None:
+            mask = padding_mask if isinstance(padding_mask, torch.Tensor) else torch.from_numpy(np.asarray(padding_mask, dtype=np.float32))
+            mask = mask.to(device=ctx.device, dtype=torch.float32)
+            if mask.ndim == 4:
+                mask = mask[..., 0]
+            if tuple(mask.shape) != tuple(dst.shape[:3]):
+                raise ValueError(f"sharpness transfer: padding_mask {tuple(mask.shape)} does not match the stabilized frames "
+                                 f"{tuple(dst.shape[:3])}")
+            mask = mask.contiguous()
+        block = sharpness_transfer.transfer_on_device(ctx, src, dst, mask, plan["final_matrices"], plan["transitions"],
+                                                      plan["confidences"], radius, alpha)
+        return io.NodeOutput(_image_out(dst, out_context), json.dumps({"sharpness_transfer": block}))
+
+
 class VideoStabilizerFlowMasked(io.ComfyNode):
     """The Flow node with an estimation mask: the pixels of `exclude_mask` (a segmentation of the moving subject, or one mask
     for a burnt-in logo) take no part in the camera-motion fit.  Not one of the reference's nodes: it is registered by the
@@ -965,3 +1040,11 @@ class VideoStabilizerAmdFillBlendExtension(VideoStabilizerAmdSubjectExtension):
 
     async def get_node_list(self) -> list:
         return await super().get_node_list() + [VideoStabilizerTemporalFillBlend]
+
+
+class VideoStabilizerAmdSharpnessExtension(VideoStabilizerAmdFillBlendExtension):
+    """The blended-fill extension's seventeen nodes plus Video Stabilizer Sharpness Transfer.  A class of its own for the
+    reason the nine before it are: comfy_entrypoint() keeps handing out its own."""
+
+    async def get_node_list(self) -> list:
+        return await super().get_node_list() + [VideoStabilizerSharpnessTransfer]

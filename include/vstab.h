@@ -709,6 +709,51 @@ int vstab_frame_sse_batch(vstab_ctx* ctx, const float* a, const float* mask_a, c
  * stream; timing kind "mask_moments". */
 int vstab_mask_moments_batch(vstab_ctx* ctx, const float* mask, int n, int h, int w, uint64_t* sums, int32_t* bbox);
 
+/* ---- sharpness transfer: shake-blurred frames repaired from sharper neighbours (beyond the reference, off by default) ----
+ * A camera jolt blurs the frames it hits; once the picture stands still those frames read as a sharpness pulse.  Matsushita
+ * et al. ("Full-frame video stabilization with motion inpainting", PAMI 2006, section 5) transfer pixels from sharper
+ * neighbouring frames, registered by the transitions the stabilizer already has.  Two entries: a per-frame sharpness measure
+ * and the weighted transfer (sharpness_transfer.py forms the ratios between them on the host).
+ *
+ * vstab_frame_sharpness_batch -- the gradient energy of every frame as one exact integer:
+ *   - q(v) = v > 0 ? (v < 1 ? (uint32)(v * 65536.0f) : 65536) : 0, the blended fill's q (a NaN gives 0).
+ *   - Y(x, y) = (q(r) + 2 * q(g) + q(b)) >> 2, an integer in 0..65536.
+ *   - over 0 <= x < w - 1, 0 <= y < h - 1:  gx = Y(x + 1, y) - Y(x, y),  gy = Y(x, y + 1) - Y(x, y).
+ *   - energy[k] = the 64-bit integer sum of gx * gx + gy * gy over those pixels of frame k.
+ * One pixel contributes at most 2^33 and h * w <= 2^30 is required, so nothing wraps; w == 1 or h == 1 gives 0.  An integer
+ * sum does not depend on the order of addition, so the result equals a NumPy restatement exactly.
+ *   frames dev [n, h, w, 3] f32, read only;  energy dev [n] u64, zeroed by the call.  n >= 1.
+ * Kernel (vstab_sharp.hip): a workgroup per 64 x 32 tile, Y once per pixel into LDS with a one-column, one-row halo, the
+ * differences from LDS, per thread -> wavefront shuffle -> LDS -> one 64-bit atomic add per workgroup and frame, skipped where
+ * the tile is flat.  Asynchronous on the context's stream; timing kind "sharpness". */
+int vstab_frame_sharpness_batch(vstab_ctx* ctx, const float* frames, int n, int h, int w, uint64_t* energy);
+
+/* vstab_sharp_transfer_batch -- src, clip_frames, first, n, matrices, cand_frame, K: the candidates of
+ * vstab_temporal_fill_batch, skipped as there (cand_frame -1, a matrix cv::invert would refuse); "sample" and "valid" are the
+ * blended fill's: the value vstab_temporal_fill_batch would write for that candidate, taken where every interpolation tap
+ * of the Q5 coordinate lies inside the candidate's frame (the interior rule above).  Per output pixel of frame first + f:
+ *   - mask == 1.0f (padded): untouched, nothing is stored.  mask == NULL: every pixel is own (`crop` framing).
+ *   - otherwise o = the pixel's value before the call, num = (0, 0, 0), den = 0, and the candidates k = 0 .. K-1 are walked
+ *     in order.  Candidate k CONTRIBUTES iff ratio[f, k] > 0, it is not skipped, it is valid at the pixel, and
+ *     D < INFINITY with D = (|s_r - o_r| + |s_g - o_g|) + |s_b - o_b| for its sample s (a NaN in either value makes the
+ *     comparison false).  A contributing candidate adds, in float32, every operation rounded on its own, nothing fused:
+ *         w = ratio / (ratio + alpha * D);    num_c = num_c + w * s_c;    den = den + w
+ *   - after the walk, den > 0: dst_c = (o_c + num_c) / (1.0f + den), and the pixel counts in transfer_count.  Otherwise
+ *     nothing is stored.  Both divisions are the correctly rounded ones.
+ *   - the mask is never written.  dst is read only at the pixel itself and the candidates sample src, so working in place
+ *     is free of races (dst must not alias src).
+ * The own value has weight 1, a neighbour at most 1 (D == 0) and less the more it disagrees: a misregistered or occluded
+ * sample fades out instead of ghosting.  There is no "first wins": every contributing candidate is sampled.
+ *   ratio  host [n, K] f32, finite and >= 0 (sharpness_transfer.ratios_from_energy: E_j / E_i, 0 below 1.1)
+ *   alpha  finite and >= 0;  dst dev [n, out_h, out_w, 3] f32, in and out;  mask dev [n, out_h, out_w] f32 or NULL
+ *   transfer_count dev [n] u32 or NULL, zeroed by the call.  K in 1..64.
+ * VSTAB_SUBPIX_Q5 only (VSTAB_SUBPIX_EXACT is refused), bilinear and bicubic.  Only frames with a contributing candidate get
+ * workgroups: a call whose ratios are all 0 launches no kernel.  Timing kind "sharp_transfer". */
+int vstab_sharp_transfer_batch(vstab_ctx* ctx, const float* src, int clip_frames, int src_h, int src_w, int first, int n,
+                               const float* matrices, const int32_t* cand_frame, int K, const float* ratio, float alpha,
+                               int out_h, int out_w, int interp, int subpix, float* dst, const float* mask,
+                               uint32_t* transfer_count);
+
 /* ---- F6 / F9 host helper: element-wise libm over fp64 arrays (host pointers, no GPU involved) ----
  * nodes/stabilizer_utils.py:300-358 (_matrix_to_params / _params_to_matrix) call math.sqrt/atan2/log and
  * math.exp/cos/sin per frame; this runs the same libm functions over a whole clip in one call.
