@@ -244,10 +244,18 @@ __host__ __device__ inline void vstab_fill_xform(const float* m32, WarpXform* xf
 // float32 matrices [count, 9] -> WarpXform table -> the call's staged parameters on the device (vstab_warp.hip).
 int vstab_stage_xforms(vstab_ctx* ctx, const float* m32, size_t count, const WarpXform** dev_out);
 
+// Host-side checks and launch geometry of every warp-shaped entry point (vstab_warp.hip; vstab_neighbour.hip uses them too).
+int vstab_check_sizes(const char* who, int n, int sh, int sw, int dh, int dw);
+int vstab_check_subpix(const char* who, int subpix);
+int vstab_check_common(const char* who, vstab_ctx* ctx, const void* src, int n, int sh, int sw, const void* mats,
+                       int dh, int dw, int interp, const float* border, int subpix, const void* dst);
+void vstab_set_block_width(int dh, int dw, int* bw0, int* bw0_pow2);
+int vstab_tile_grid(const char* who, int n, int dh, int dw, int tx, int nt, int* tiles_x, int* tiles_y, unsigned* grid);
+
 // ---- mesh warp ----
 constexpr int MESH_MAX_VERTS = 65;   // vertices per axis (64 cells): the residual (vstab_mesh.hip) and the warp (vstab_warp.hip)
 
-// ---- the scalar pieces of the warp's arithmetic that other translation units use too (the rest: vstab_warp.hip) ----
+// ---- the scalar pieces of the warp's arithmetic that other translation units use too (the rest: the guarded section below) ----
 
 // std::max((double)INT_MIN, std::min((double)INT_MAX, v)) followed by cvRound
 __device__ __forceinline__ int clamp_round_i32(double v)
@@ -280,3 +288,343 @@ __device__ __forceinline__ bool vstab_nn_covered(double qx, double qy, int sh, i
     const int ny = sat_short(clamp_round_i32(qy));
     return (unsigned)nx < (unsigned)sw && (unsigned)ny < (unsigned)sh;
 }
+
+// ---- the warp's arithmetic proper: samplers, tile shell, warp_pixel ----
+// Compiled only where a translation unit defines VSTAB_WARP_ARITHMETIC in front of this include (vstab_warp.hip and
+// vstab_neighbour.hip).  It lives here because profiles/warp_traffic.json is tied to the hash of vstab_warp.hip + this
+// file: whatever decides the plain warp's instructions stays inside the two.
+#ifdef VSTAB_WARP_ARITHMETIC
+constexpr int TILE_PX = 2;       // pixels per thread along x, strided by the tile width (profiles/r01_warp_tile_sweep.md)
+// Round-half-even of an fp64 value known to satisfy |v| < 2^31: adding 1.5*2^52 leaves the integer in the
+// low 32 bits of the sum's bit pattern (one fp64 add instead of clamp + rint + convert).  Exactly what
+// cvRound gives for such values.
+__device__ __forceinline__ int round_small(double v)
+{
+    return (int)(unsigned)__double_as_longlong(v + 6755399441055744.0);
+}
+
+// initInterTab1D(INTER_CUBIC): A = -0.75, x = i/32, same operation order as OpenCV's interpolateCubic
+__device__ __forceinline__ void cubic_coeffs(int i, float* c)
+{
+    const float A = -0.75f;
+    const float x = i * (1.f / 32);
+    c[0] = ((A * (x + 1) - 5 * A) * (x + 1) + 8 * A) * (x + 1) - 4 * A;
+    c[1] = ((A + 2) * x - (A + 3)) * x * x + 1;
+    c[2] = ((A + 2) * (1 - x) - (A + 3)) * (1 - x) * (1 - x) + 1;
+    c[3] = 1.f - c[0] - c[1] - c[2];
+}
+
+struct Px { float r, g, b; };
+
+__device__ __forceinline__ Px load_px(const float* p)
+{
+    Px v;
+    __builtin_memcpy(&v, p, 12);
+    return v;
+}
+
+template <int INTERP>
+__device__ __forceinline__ Px sample_q5(const float* __restrict__ S, int sh, int sw, int X, int Y,
+                                        float b0, float b1, float b2, const float* cub_tab /* LDS [32][4] or nullptr */)
+{
+    const int sx = sat_short(X >> 5), sy = sat_short(Y >> 5);
+    const int fx = X & 31, fy = Y & 31;
+    Px o;
+    if (INTERP == VSTAB_INTERP_BILINEAR) {
+        const float wx1 = fx * (1.f / 32), wx0 = 1.f - wx1;
+        const float wy1 = fy * (1.f / 32), wy0 = 1.f - wy1;
+        const float w0 = wy0 * wx0, w1 = wy0 * wx1, w2 = wy1 * wx0, w3 = wy1 * wx1;
+        if ((unsigned)sx < (unsigned)(sw - 1) && (unsigned)sy < (unsigned)(sh - 1)) {
+            const float* p = S + ((unsigned)sy * (unsigned)sw + (unsigned)sx) * 3u;
+            float r0[6], r1[6];
+            __builtin_memcpy(r0, p, 24);
+            __builtin_memcpy(r1, p + (unsigned)sw * 3u, 24);
+            o.r = r0[0] * w0 + r0[3] * w1 + r1[0] * w2 + r1[3] * w3;
+            o.g = r0[1] * w0 + r0[4] * w1 + r1[1] * w2 + r1[4] * w3;
+            o.b = r0[2] * w0 + r0[5] * w1 + r1[2] * w2 + r1[5] * w3;
+            return o;
+        }
+        if (sx >= sw || sx + 1 < 0 || sy >= sh || sy + 1 < 0) {
+            o.r = b0; o.g = b1; o.b = b2;
+            return o;
+        }
+        const bool x0ok = sx >= 0 && sx < sw, x1ok = sx + 1 >= 0 && sx + 1 < sw;
+        const bool y0ok = sy >= 0 && sy < sh, y1ok = sy + 1 >= 0 && sy + 1 < sh;
+        const Px bd = {b0, b1, b2};
+        const Px v0 = (x0ok && y0ok) ? load_px(S + ((unsigned)sy * (unsigned)sw + (unsigned)sx) * 3u) : bd;
+        const Px v1 = (x1ok && y0ok) ? load_px(S + ((unsigned)sy * (unsigned)sw + (unsigned)(sx + 1)) * 3u) : bd;
+        const Px v2 = (x0ok && y1ok) ? load_px(S + ((unsigned)(sy + 1) * (unsigned)sw + (unsigned)sx) * 3u) : bd;
+        const Px v3 = (x1ok && y1ok) ? load_px(S + ((unsigned)(sy + 1) * (unsigned)sw + (unsigned)(sx + 1)) * 3u) : bd;
+        o.r = v0.r * w0 + v1.r * w1 + v2.r * w2 + v3.r * w3;
+        o.g = v0.g * w0 + v1.g * w1 + v2.g * w2 + v3.g * w3;
+        o.b = v0.b * w0 + v1.b * w1 + v2.b * w2 + v3.b * w3;
+        return o;
+    } else {
+        float cx[4], cy[4];
+        if (cub_tab != nullptr) {   // OpenCV reads these from its own 32-entry table too (initInterTab1D): same values
+            typedef float f4_t __attribute__((ext_vector_type(4)));
+            const f4_t tx = reinterpret_cast<const f4_t*>(cub_tab)[fx], ty = reinterpret_cast<const f4_t*>(cub_tab)[fy];
+            cx[0] = tx.x; cx[1] = tx.y; cx[2] = tx.z; cx[3] = tx.w;
+            cy[0] = ty.x; cy[1] = ty.y; cy[2] = ty.z; cy[3] = ty.w;
+        } else {
+            cubic_coeffs(fx, cx);
+            cubic_coeffs(fy, cy);
+        }
+        const int x0 = sx - 1, y0 = sy - 1;
+        const unsigned width1 = (unsigned)(sw - 3 > 0 ? sw - 3 : 0);
+        const unsigned height1 = (unsigned)(sh - 3 > 0 ? sh - 3 : 0);
+        if ((unsigned)x0 < width1 && (unsigned)y0 < height1) {
+            const float* p = S + ((unsigned)y0 * (unsigned)sw + (unsigned)x0) * 3u;
+            float sr = 0.f, sg = 0.f, sb = 0.f;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                float row[12];
+                __builtin_memcpy(row, p + (unsigned)i * (unsigned)sw * 3u, 48);
+                const float w0 = cy[i] * cx[0], w1 = cy[i] * cx[1], w2 = cy[i] * cx[2], w3 = cy[i] * cx[3];
+                const float tr = row[0] * w0 + row[3] * w1 + row[6] * w2 + row[9] * w3;
+                const float tg = row[1] * w0 + row[4] * w1 + row[7] * w2 + row[10] * w3;
+                const float tb = row[2] * w0 + row[5] * w1 + row[8] * w2 + row[11] * w3;
+                if (i == 0) { sr = tr; sg = tg; sb = tb; }
+                else { sr += tr; sg += tg; sb += tb; }
+            }
+            o.r = sr; o.g = sg; o.b = sb;
+            return o;
+        }
+        if (x0 >= sw || x0 + 4 <= 0 || y0 >= sh || y0 + 4 <= 0) {
+            o.r = b0; o.g = b1; o.b = b2;
+            return o;
+        }
+        float sr = b0, sg = b1, sb = b2;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int yy = y0 + i;
+            if (yy < 0 || yy >= sh) continue;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int xx = x0 + j;
+                if (xx < 0 || xx >= sw) continue;
+                const Px v = load_px(S + ((unsigned)yy * (unsigned)sw + (unsigned)xx) * 3u);
+                const float w = cy[i] * cx[j];
+                sr += (v.r - b0) * w;
+                sg += (v.g - b1) * w;
+                sb += (v.b - b2) * w;
+            }
+        }
+        o.r = sr; o.g = sg; o.b = sb;
+        return o;
+    }
+}
+
+__device__ __forceinline__ Px sample_exact(const float* __restrict__ S, int sh, int sw, float fsx, float fsy,
+                                           float b0, float b1, float b2)
+{
+    Px o;
+    const float flx = __builtin_floorf(fsx), fly = __builtin_floorf(fsy);
+    const bool bad = !(fsx == fsx) || !(fsy == fsy) || flx >= 2.0e9f || flx <= -2.0e9f || fly >= 2.0e9f || fly <= -2.0e9f;
+    const int ix = bad ? 0 : (int)flx, iy = bad ? 0 : (int)fly;
+    const float ax = fsx - ix, ay = fsy - iy;
+    if (bad || ix >= sw || ix + 1 < 0 || iy >= sh || iy + 1 < 0) {
+        o.r = b0; o.g = b1; o.b = b2;
+        return o;
+    }
+    const bool x0ok = ix >= 0 && ix < sw, x1ok = ix + 1 >= 0 && ix + 1 < sw;
+    const bool y0ok = iy >= 0 && iy < sh, y1ok = iy + 1 >= 0 && iy + 1 < sh;
+    const Px bd = {b0, b1, b2};
+    const Px p00 = (x0ok && y0ok) ? load_px(S + ((unsigned)iy * (unsigned)sw + (unsigned)ix) * 3u) : bd;
+    const Px p01 = (x1ok && y0ok) ? load_px(S + ((unsigned)iy * (unsigned)sw + (unsigned)(ix + 1)) * 3u) : bd;
+    const Px p10 = (x0ok && y1ok) ? load_px(S + ((unsigned)(iy + 1) * (unsigned)sw + (unsigned)ix) * 3u) : bd;
+    const Px p11 = (x1ok && y1ok) ? load_px(S + ((unsigned)(iy + 1) * (unsigned)sw + (unsigned)(ix + 1)) * 3u) : bd;
+    float v0, v1;
+    v0 = p00.r + ax * (p01.r - p00.r); v1 = p10.r + ax * (p11.r - p10.r); o.r = v0 + ay * (v1 - v0);
+    v0 = p00.g + ax * (p01.g - p00.g); v1 = p10.g + ax * (p11.g - p10.g); o.g = v0 + ay * (v1 - v0);
+    v0 = p00.b + ax * (p01.b - p00.b); v1 = p10.b + ax * (p11.b - p10.b); o.b = v0 + ay * (v1 - v0);
+    return o;
+}
+
+// XCD-aware bijective remap of the linear block id (8 XCDs, round-robin dispatch):
+// blocks that share an XCD get a contiguous run of logical tile ids.
+__device__ __forceinline__ unsigned xcd_remap(unsigned b, unsigned nblk)
+{
+    const unsigned q = nblk >> 3, r = nblk & 7, x = b & 7, i = b >> 3;
+    const unsigned base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
+    return base + i;
+}
+
+// Column-block origin of output column x (OpenCV evaluates the row-start terms once per block of bw0 columns).
+__device__ __forceinline__ int block_origin(int x, int dw, int bw0, int bw0_pow2)
+{
+    if (bw0 >= dw) return 0;
+    if (bw0_pow2) return x & ~(bw0 - 1);
+    return (x / bw0) * bw0;
+}
+
+// The tile shell of every warp kernel: block -> (frame, tile) through the XCD remap, thread -> row y and first pixel x0 of
+// its npx pixels.  Pixel p of a thread is x0 + p * TILE_TX: the lanes of a wavefront cover CONSECUTIVE output pixels, so
+// one load instruction of the bilinear taps touches ~13 cache lines (24 B per lane at a 12-B lane stride) instead of 48 (at
+// the 48-B stride of 4 consecutive pixels per thread) -- the texture addresser was 83 % busy that way (PMC TA_BUSY) and
+// limited the read side to 2.8 TB/s -- and the stores are whole lines (12 B per lane, contiguous).
+template <int TILE_TX, int NT = 256>
+struct TileShell {
+    static constexpr int TILE_W = TILE_TX * TILE_PX, TILE_H = NT / TILE_TX;
+    int frame, tile_x, tile_y, x0, y, npx;
+    bool active;
+    __device__ __forceinline__ TileShell(int tiles_x, int tiles_y, int dh, int dw)
+    {
+        const unsigned t = xcd_remap(blockIdx.x, gridDim.x);
+        const unsigned tiles_per_frame = (unsigned)tiles_x * tiles_y;
+        frame = t / tiles_per_frame;
+        const unsigned tr = t - frame * tiles_per_frame;
+        tile_y = tr / tiles_x;
+        tile_x = tr - tile_y * tiles_x;
+        const int tx = threadIdx.x % TILE_TX, ty = threadIdx.x / TILE_TX;
+        x0 = tile_x * TILE_W + tx;
+        y = tile_y * TILE_H + ty;
+        active = (y < dh) && (x0 < dw);
+        npx = active ? (int)((unsigned)(dw - x0 + TILE_TX - 1) / TILE_TX) : 0;   // pixels x0 + p*TILE_TX < dw (callers cap it at TILE_PX); active: dw > x0
+    }
+};
+
+// Per-thread counts of an NT-thread block -> wave shuffle -> LDS -> one atomic per counter and block, only if non-zero
+// and asked for (out[c] != nullptr); out[c] is a per-frame array.
+template <int NC, int NT = 256>
+__device__ __forceinline__ void block_count_add(unsigned (&v)[NC], unsigned* const (&out)[NC], int frame)
+{
+    static_assert(NT % 64 == 0, "whole wavefronts");
+    constexpr int WAVES = NT / 64;
+    __shared__ unsigned s_cnt[NC][WAVES];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int c = 0; c < NC; c++) v[c] += __shfl_down(v[c], off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < NC; c++) s_cnt[c][threadIdx.x >> 6] = v[c];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            unsigned total = s_cnt[c][0];
+#pragma unroll
+            for (int w = 1; w < WAVES; w++) total += s_cnt[c][w];
+            if (total && out[c]) atomicAdd(out[c] + frame, total);
+        }
+    }
+}
+
+// warp_pixel's displacement hook, of two kinds.  OUTPUT == false: a functor evaluated at the source position
+// q = (Xn * Wn, Yn * Wn) that gives the offset (cx, cy) taken off it before the roundings.  OUTPUT == true: `solve`, evaluated
+// on the output pixel in front of the matrix (MeshInverseDisplacement).  NoDisplacement is the plain warp: nothing of the
+// hook is compiled.
+struct NoDisplacement {
+    static constexpr bool ACTIVE = false;
+    static constexpr bool OUTPUT = false;
+};
+
+// One transform record in registers, as warp_kernel and temporal_fill_kernel use it for all pixels of a thread.
+template <int INTERP, int SUBPIX>
+struct XformRegs {
+    static constexpr bool EXACT = SUBPIX == VSTAB_SUBPIX_EXACT && INTERP == VSTAB_INTERP_BILINEAR;
+    double m0, m1, m2, m3, m4, m5, m6, m7, m8;
+    float mf[9];      // EXACT only
+    bool affine, fast_ok;
+    __device__ __forceinline__ explicit XformRegs(const WarpXform* __restrict__ xf)
+        : m0(xf->m[0]), m1(xf->m[1]), m2(xf->m[2]), m3(xf->m[3]), m4(xf->m[4]), m5(xf->m[5]), m6(xf->m[6]), m7(xf->m[7]),
+          m8(xf->m[8]), affine(xf->affine != 0)
+    {
+        if (EXACT) {
+#pragma unroll
+            for (int i = 0; i < 9; i++) mf[i] = (float)xf->m[i];
+        }
+        fast_ok = affine && !EXACT;
+    }
+};
+
+// The warp's source position of output pixel (x, y) under one transform, and what is sampled there: THE definition of the
+// coordinate arithmetic (f64 row-start terms per OpenCV column block, Q5 rounding or the float32 `exact` chain), shared by
+// warp_kernel, mesh_warp_kernel and temporal_fill_kernel.  `q5(X, Y)` samples at the 1/32-px coordinates, `exact(fsx, fsy)`
+// at the float32 ones; `c` receives the nearest-neighbour coverage (WITH_MASK only).  `disp` (see NoDisplacement) moves
+// the source position: s = q - disp(q), applied to the unrounded value in front of each of the three roundings.  A `disp` of
+// the OUTPUT kind moves the output pixel by e = disp.solve(x, y) in front of the matrix instead: m * e is added to the
+// unrounded terms Xn, Yn, W (and, float32-rounded, to the `exact` chain's), and *unconverged counts the pixels whose solve
+// hit its step limit.  e == 0 adds nothing at all (not even a signed zero): the plain warp's bits.
+template <int INTERP, int SUBPIX, bool WITH_MASK, class SampleQ5, class SampleExact, class Disp>
+__device__ __forceinline__ Px warp_pixel(const WarpXform* __restrict__ xf, const XformRegs<INTERP, SUBPIX>& r, int sh, int sw,
+                                         int dw, int bw0, int bw0_pow2, int x, int y, double dy, SampleQ5&& q5,
+                                         SampleExact&& exact, const Disp& disp, float& c, unsigned* unconverged = nullptr)
+{
+    // OpenCV evaluates the row-start terms X0, Y0, W0 once per 64-wide column block (xb) and adds m * (x - xb)
+    // per pixel; a thread's pixels lie in up to TILE_PX different blocks, so the terms are formed per pixel.
+    const int xb = block_origin(x, dw, bw0, bw0_pow2);
+    const double dxb = (double)xb;
+    const double X0 = r.m0 * dxb + r.m1 * dy + r.m2;
+    const double Y0 = r.m3 * dxb + r.m4 * dy + r.m5;
+    const double W0 = r.m6 * dxb + r.m7 * dy + r.m8;
+    const double dx1 = (double)(x - xb);
+    const double Xn = X0 + r.m0 * dx1, Yn = Y0 + r.m3 * dx1;
+    Px v;
+    // Fast path (the common case): affine map whose 1/32-px coordinates stay far inside the range where
+    // OpenCV's INT clamp and short saturation are no-ops.  A displaced pixel takes the general branch.
+    bool small = false;
+    if constexpr (!Disp::ACTIVE) small = r.fast_ok && __builtin_fabs(Xn * xf->wq) < 1.0e6 && __builtin_fabs(Yn * xf->wq) < 1.0e6;
+    if (small) {
+        const int X = round_small(Xn * xf->wq), Y = round_small(Yn * xf->wq);
+        v = q5(X, Y);
+        if (WITH_MASK) {
+            const int nx = round_small(Xn * xf->wn), ny = round_small(Yn * xf->wn);
+            c = ((unsigned)nx < (unsigned)sw && (unsigned)ny < (unsigned)sh) ? 1.f : 0.f;
+        }
+    } else {
+        // OUTPUT kind: the displaced terms (Xd, Yd) and what m * e adds to W and to the float32 chain
+        double Xd = Xn, Yd = Yn, dX = 0.0, dY = 0.0, dW = 0.0;
+        bool moved = false;
+        if constexpr (Disp::OUTPUT) {
+            double ex, ey;
+            if (!disp.solve(x, y, ex, ey)) *unconverged += 1u;
+            moved = !(ex == 0.0 && ey == 0.0);
+            if (moved) {
+                dX = r.m0 * ex + r.m1 * ey; dY = r.m3 * ex + r.m4 * ey; dW = r.m6 * ex + r.m7 * ey;
+                Xd = Xn + dX; Yd = Yn + dY;
+            }
+        }
+        double Wq, Wn;
+        if (r.affine) { Wq = xf->wq; Wn = xf->wn; }
+        else {
+            // one fp64 division serves both: 32/W == 32 * (1/W) bit for bit (scaling a correctly rounded
+            // quotient by a power of two is exact)
+            double W = W0 + r.m6 * dx1;
+            if constexpr (Disp::OUTPUT) { if (moved) W = W + dW; }
+            Wn = (W != 0.0) ? 1.0 / W : 0.0;
+            Wq = 32.0 * Wn;
+        }
+        double cx = 0.0, cy = 0.0;
+        if constexpr (Disp::ACTIVE && !Disp::OUTPUT) disp(Xn * Wn, Yn * Wn, cx, cy);
+        if (XformRegs<INTERP, SUBPIX>::EXACT) {
+            float fsx, fsy;
+            if constexpr (Disp::OUTPUT) {
+                float w = x * r.mf[6] + y * r.mf[7] + r.mf[8];
+                float numx = x * r.mf[0] + y * r.mf[1] + r.mf[2], numy = x * r.mf[3] + y * r.mf[4] + r.mf[5];
+                if (moved) { numx = numx + (float)dX; numy = numy + (float)dY; w = w + (float)dW; }
+                fsx = numx / w; fsy = numy / w;
+            } else {
+                const float w = x * r.mf[6] + y * r.mf[7] + r.mf[8];
+                fsx = (x * r.mf[0] + y * r.mf[1] + r.mf[2]) / w;
+                fsy = (x * r.mf[3] + y * r.mf[4] + r.mf[5]) / w;
+                if constexpr (Disp::ACTIVE) { fsx = (float)((double)fsx - cx); fsy = (float)((double)fsy - cy); }
+            }
+            v = exact(fsx, fsy);
+        } else {
+            double Xq = Xd * Wq, Yq = Yd * Wq;
+            if constexpr (Disp::ACTIVE && !Disp::OUTPUT) { Xq = Xq - 32.0 * cx; Yq = Yq - 32.0 * cy; }
+            v = q5(clamp_round_i32(Xq), clamp_round_i32(Yq));
+        }
+        if (WITH_MASK) {
+            double qx = Xd * Wn, qy = Yd * Wn;
+            if constexpr (Disp::ACTIVE && !Disp::OUTPUT) { qx = qx - cx; qy = qy - cy; }
+            c = vstab_nn_covered(qx, qy, sh, sw) ? 1.f : 0.f;
+        }
+    }
+    return v;
+}
+#endif  // VSTAB_WARP_ARITHMETIC

@@ -1,5 +1,5 @@
 // vstab_mesh.hip -- mesh warp: the per-vertex residual of a global fit (vstab_mesh_residual_batch).  The warp that takes it
-// out (vstab_mesh_warp_batch) is vstab_warp.hip's warp_pixel with a displacement hook and lives there.  Not a reference
+// out (vstab_mesh_warp_batch) is warp_pixel (vstab_internal.h) with a displacement hook and lives in vstab_warp.hip.  Not a reference
 // feature; both rules are stated in include/vstab.h.
 //
 // mesh_residual_kernel: one workgroup per (pair, vertex).  The grid samples of the four cells around the vertex are

@@ -1,5 +1,5 @@
 // vstab_sharp.hip -- sharpness transfer: the gradient energy of every frame of a clip as one exact 64-bit integer (the rule:
-// include/vstab.h, vstab_frame_sharpness_batch).  The transfer itself is a warp kernel and lives in vstab_warp.hip.
+// include/vstab.h, vstab_frame_sharpness_batch).  The transfer itself is a warp kernel and lives in vstab_neighbour.hip.
 //
 //   frame_sharpness_kernel  one workgroup = one 64 x 32 tile of one frame.  Y = (q(r) + 2 q(g) + q(b)) >> 2 of the tile's pixels
 //                           and of one more column and row (the halo the forward differences reach into) is computed once per
@@ -31,7 +31,7 @@ __device__ __forceinline__ float sh_load(const float* p)
 #endif
 }
 
-// q of the blended fill's gain sums (vstab_warp.hip: gain_q): 16 fractional bits, truncated; below 0 and NaN give 0, 1 and
+// q of the blended fill's gain sums (vstab_neighbour.hip: gain_q): 16 fractional bits, truncated; below 0 and NaN give 0, 1 and
 // above give 65536.
 __device__ __forceinline__ unsigned sh_q(float v)
 {

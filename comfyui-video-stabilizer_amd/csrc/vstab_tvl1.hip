@@ -32,7 +32,7 @@
 namespace {
 
 // initInterTab1D(INTER_CUBIC): A = -0.75, x = i/32, same operation order as OpenCV's interpolateCubic (the same
-// table as cubic_coeffs of vstab_warp.hip)
+// table as cubic_coeffs of vstab_internal.h)
 __device__ __forceinline__ void tvl1_cubic_coeffs(int i, float* c)
 {
     const float A = -0.75f;

@@ -1,11 +1,11 @@
 // vstab_warp.hip -- perspective/similarity warp with padding mask, its mesh-displaced forms (mesh_warp_kernel and its
-// inverse, mesh_unwarp_kernel), the multi-sample motion blur, the temporal fill (plain, and blended: fill_gain_sums_kernel,
-// temporal_fill_blend_kernel), the sharpness transfer (sharp_transfer_kernel) and the coverage extent of the dynamic zoom
+// inverse, mesh_unwarp_kernel), the multi-sample motion blur and the coverage extent of the dynamic zoom
 // (cover_extent_kernel: warp_pixel's coverage bit alone, nothing sampled).
-// All of them take their coordinates from ONE definition, warp_pixel, and
-// share one tile shell (TileShell, warp_kernel's body, block_count_add); the scalar pieces that vstab_crop / vstab_dis / vstab_tvl1
-// use too are in vstab_internal.h.  profiles/warp_traffic.json is tied to the hash of these two files: the warp's arithmetic
-// stays in them.
+// All of them take their coordinates from ONE definition, warp_pixel, and share one tile shell (TileShell, warp_kernel's
+// body, block_count_add).  Those, the samplers and the scalar pieces that vstab_crop / vstab_dis / vstab_tvl1 use too are in
+// vstab_internal.h (VSTAB_WARP_ARITHMETIC); the mesh displacements are here; the passes that sample OTHER frames of the clip
+// through the same arithmetic are in vstab_neighbour.hip.  profiles/warp_traffic.json is tied to the hash of this file and
+// vstab_internal.h: the warp's arithmetic stays in them.
 //
 // Replaces the OpenCV calls of nodes/video_stabilizer_flow.py:560-588 (F13) and
 // nodes/motion_apply.py:75-202 (A3, A5) of the reference.  Arithmetic follows OpenCV's
@@ -19,18 +19,18 @@
 //     source footprint of the tile stays in the CU's L1, vertically adjacent tiles share a source row through L2
 //   * blockIdx is remapped so that the 8 XCDs (private L2 each) own contiguous runs of tiles
 //   * padding-pixel count: wave shuffle reduction -> LDS -> one atomic per block, only if non-zero
+#define VSTAB_WARP_ARITHMETIC
 #include "vstab_internal.h"
 #include "vstab_wait.h"
 #include <type_traits>
 #include <cstdlib>
-#include <cmath>
 
 namespace {
 
-constexpr int TILE_PX = 2;        // pixels per thread along x, strided by the tile width (profiles/r01_warp_tile_sweep.md)
 constexpr int MAX_BLUR_SAMPLES = 33;
 
-// WarpXform (per frame / sample transform record): vstab_internal.h
+// WarpXform (per frame / sample transform record), TILE_PX, the samplers, TileShell, XformRegs, warp_pixel and the scalar
+// pieces other translation units use too (clamp_round_i32, sat_short, vstab_nn_covered): vstab_internal.h
 
 struct WarpArgs {
     const float* src;
@@ -46,235 +46,6 @@ struct WarpArgs {
     int nxf_per_frame;  // sample matrices stored per frame (1 for a single-frame blur clip)
     int blur_fast;      // blur: the interior fast path may be used (host-checked preconditions, see warp_blur_kernel)
     float b0, b1, b2;   // border colour
-};
-
-// clamp_round_i32, sat_short, vstab_nn_covered (used by other translation units too): vstab_internal.h
-
-// Round-half-even of an fp64 value known to satisfy |v| < 2^31: adding 1.5*2^52 leaves the integer in the
-// low 32 bits of the sum's bit pattern (one fp64 add instead of clamp + rint + convert).  Exactly what
-// cvRound gives for such values.
-__device__ __forceinline__ int round_small(double v)
-{
-    return (int)(unsigned)__double_as_longlong(v + 6755399441055744.0);
-}
-
-// initInterTab1D(INTER_CUBIC): A = -0.75, x = i/32, same operation order as OpenCV's interpolateCubic
-__device__ __forceinline__ void cubic_coeffs(int i, float* c)
-{
-    const float A = -0.75f;
-    const float x = i * (1.f / 32);
-    c[0] = ((A * (x + 1) - 5 * A) * (x + 1) + 8 * A) * (x + 1) - 4 * A;
-    c[1] = ((A + 2) * x - (A + 3)) * x * x + 1;
-    c[2] = ((A + 2) * (1 - x) - (A + 3)) * (1 - x) * (1 - x) + 1;
-    c[3] = 1.f - c[0] - c[1] - c[2];
-}
-
-struct Px { float r, g, b; };
-
-__device__ __forceinline__ Px load_px(const float* p)
-{
-    Px v;
-    __builtin_memcpy(&v, p, 12);
-    return v;
-}
-
-template <int INTERP>
-__device__ __forceinline__ Px sample_q5(const float* __restrict__ S, int sh, int sw, int X, int Y,
-                                        float b0, float b1, float b2, const float* cub_tab /* LDS [32][4] or nullptr */)
-{
-    const int sx = sat_short(X >> 5), sy = sat_short(Y >> 5);
-    const int fx = X & 31, fy = Y & 31;
-    Px o;
-    if (INTERP == VSTAB_INTERP_BILINEAR) {
-        const float wx1 = fx * (1.f / 32), wx0 = 1.f - wx1;
-        const float wy1 = fy * (1.f / 32), wy0 = 1.f - wy1;
-        const float w0 = wy0 * wx0, w1 = wy0 * wx1, w2 = wy1 * wx0, w3 = wy1 * wx1;
-        if ((unsigned)sx < (unsigned)(sw - 1) && (unsigned)sy < (unsigned)(sh - 1)) {
-            const float* p = S + ((unsigned)sy * (unsigned)sw + (unsigned)sx) * 3u;
-            float r0[6], r1[6];
-            __builtin_memcpy(r0, p, 24);
-            __builtin_memcpy(r1, p + (unsigned)sw * 3u, 24);
-            o.r = r0[0] * w0 + r0[3] * w1 + r1[0] * w2 + r1[3] * w3;
-            o.g = r0[1] * w0 + r0[4] * w1 + r1[1] * w2 + r1[4] * w3;
-            o.b = r0[2] * w0 + r0[5] * w1 + r1[2] * w2 + r1[5] * w3;
-            return o;
-        }
-        if (sx >= sw || sx + 1 < 0 || sy >= sh || sy + 1 < 0) {
-            o.r = b0; o.g = b1; o.b = b2;
-            return o;
-        }
-        const bool x0ok = sx >= 0 && sx < sw, x1ok = sx + 1 >= 0 && sx + 1 < sw;
-        const bool y0ok = sy >= 0 && sy < sh, y1ok = sy + 1 >= 0 && sy + 1 < sh;
-        const Px bd = {b0, b1, b2};
-        const Px v0 = (x0ok && y0ok) ? load_px(S + ((unsigned)sy * (unsigned)sw + (unsigned)sx) * 3u) : bd;
-        const Px v1 = (x1ok && y0ok) ? load_px(S + ((unsigned)sy * (unsigned)sw + (unsigned)(sx + 1)) * 3u) : bd;
-        const Px v2 = (x0ok && y1ok) ? load_px(S + ((unsigned)(sy + 1) * (unsigned)sw + (unsigned)sx) * 3u) : bd;
-        const Px v3 = (x1ok && y1ok) ? load_px(S + ((unsigned)(sy + 1) * (unsigned)sw + (unsigned)(sx + 1)) * 3u) : bd;
-        o.r = v0.r * w0 + v1.r * w1 + v2.r * w2 + v3.r * w3;
-        o.g = v0.g * w0 + v1.g * w1 + v2.g * w2 + v3.g * w3;
-        o.b = v0.b * w0 + v1.b * w1 + v2.b * w2 + v3.b * w3;
-        return o;
-    } else {
-        float cx[4], cy[4];
-        if (cub_tab != nullptr) {   // OpenCV reads these from its own 32-entry table too (initInterTab1D): same values
-            typedef float f4_t __attribute__((ext_vector_type(4)));
-            const f4_t tx = reinterpret_cast<const f4_t*>(cub_tab)[fx], ty = reinterpret_cast<const f4_t*>(cub_tab)[fy];
-            cx[0] = tx.x; cx[1] = tx.y; cx[2] = tx.z; cx[3] = tx.w;
-            cy[0] = ty.x; cy[1] = ty.y; cy[2] = ty.z; cy[3] = ty.w;
-        } else {
-            cubic_coeffs(fx, cx);
-            cubic_coeffs(fy, cy);
-        }
-        const int x0 = sx - 1, y0 = sy - 1;
-        const unsigned width1 = (unsigned)(sw - 3 > 0 ? sw - 3 : 0);
-        const unsigned height1 = (unsigned)(sh - 3 > 0 ? sh - 3 : 0);
-        if ((unsigned)x0 < width1 && (unsigned)y0 < height1) {
-            const float* p = S + ((unsigned)y0 * (unsigned)sw + (unsigned)x0) * 3u;
-            float sr = 0.f, sg = 0.f, sb = 0.f;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                float row[12];
-                __builtin_memcpy(row, p + (unsigned)i * (unsigned)sw * 3u, 48);
-                const float w0 = cy[i] * cx[0], w1 = cy[i] * cx[1], w2 = cy[i] * cx[2], w3 = cy[i] * cx[3];
-                const float tr = row[0] * w0 + row[3] * w1 + row[6] * w2 + row[9] * w3;
-                const float tg = row[1] * w0 + row[4] * w1 + row[7] * w2 + row[10] * w3;
-                const float tb = row[2] * w0 + row[5] * w1 + row[8] * w2 + row[11] * w3;
-                if (i == 0) { sr = tr; sg = tg; sb = tb; }
-                else { sr += tr; sg += tg; sb += tb; }
-            }
-            o.r = sr; o.g = sg; o.b = sb;
-            return o;
-        }
-        if (x0 >= sw || x0 + 4 <= 0 || y0 >= sh || y0 + 4 <= 0) {
-            o.r = b0; o.g = b1; o.b = b2;
-            return o;
-        }
-        float sr = b0, sg = b1, sb = b2;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int yy = y0 + i;
-            if (yy < 0 || yy >= sh) continue;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int xx = x0 + j;
-                if (xx < 0 || xx >= sw) continue;
-                const Px v = load_px(S + ((unsigned)yy * (unsigned)sw + (unsigned)xx) * 3u);
-                const float w = cy[i] * cx[j];
-                sr += (v.r - b0) * w;
-                sg += (v.g - b1) * w;
-                sb += (v.b - b2) * w;
-            }
-        }
-        o.r = sr; o.g = sg; o.b = sb;
-        return o;
-    }
-}
-
-__device__ __forceinline__ Px sample_exact(const float* __restrict__ S, int sh, int sw, float fsx, float fsy,
-                                           float b0, float b1, float b2)
-{
-    Px o;
-    const float flx = __builtin_floorf(fsx), fly = __builtin_floorf(fsy);
-    const bool bad = !(fsx == fsx) || !(fsy == fsy) || flx >= 2.0e9f || flx <= -2.0e9f || fly >= 2.0e9f || fly <= -2.0e9f;
-    const int ix = bad ? 0 : (int)flx, iy = bad ? 0 : (int)fly;
-    const float ax = fsx - ix, ay = fsy - iy;
-    if (bad || ix >= sw || ix + 1 < 0 || iy >= sh || iy + 1 < 0) {
-        o.r = b0; o.g = b1; o.b = b2;
-        return o;
-    }
-    const bool x0ok = ix >= 0 && ix < sw, x1ok = ix + 1 >= 0 && ix + 1 < sw;
-    const bool y0ok = iy >= 0 && iy < sh, y1ok = iy + 1 >= 0 && iy + 1 < sh;
-    const Px bd = {b0, b1, b2};
-    const Px p00 = (x0ok && y0ok) ? load_px(S + ((unsigned)iy * (unsigned)sw + (unsigned)ix) * 3u) : bd;
-    const Px p01 = (x1ok && y0ok) ? load_px(S + ((unsigned)iy * (unsigned)sw + (unsigned)(ix + 1)) * 3u) : bd;
-    const Px p10 = (x0ok && y1ok) ? load_px(S + ((unsigned)(iy + 1) * (unsigned)sw + (unsigned)ix) * 3u) : bd;
-    const Px p11 = (x1ok && y1ok) ? load_px(S + ((unsigned)(iy + 1) * (unsigned)sw + (unsigned)(ix + 1)) * 3u) : bd;
-    float v0, v1;
-    v0 = p00.r + ax * (p01.r - p00.r); v1 = p10.r + ax * (p11.r - p10.r); o.r = v0 + ay * (v1 - v0);
-    v0 = p00.g + ax * (p01.g - p00.g); v1 = p10.g + ax * (p11.g - p10.g); o.g = v0 + ay * (v1 - v0);
-    v0 = p00.b + ax * (p01.b - p00.b); v1 = p10.b + ax * (p11.b - p10.b); o.b = v0 + ay * (v1 - v0);
-    return o;
-}
-
-// XCD-aware bijective remap of the linear block id (8 XCDs, round-robin dispatch):
-// blocks that share an XCD get a contiguous run of logical tile ids.
-__device__ __forceinline__ unsigned xcd_remap(unsigned b, unsigned nblk)
-{
-    const unsigned q = nblk >> 3, r = nblk & 7, x = b & 7, i = b >> 3;
-    const unsigned base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-    return base + i;
-}
-
-// Column-block origin of output column x (OpenCV evaluates the row-start terms once per block of bw0 columns).
-__device__ __forceinline__ int block_origin(int x, int dw, int bw0, int bw0_pow2)
-{
-    if (bw0 >= dw) return 0;
-    if (bw0_pow2) return x & ~(bw0 - 1);
-    return (x / bw0) * bw0;
-}
-
-// The tile shell of every warp kernel: block -> (frame, tile) through the XCD remap, thread -> row y and first pixel x0 of
-// its npx pixels.  Pixel p of a thread is x0 + p * TILE_TX: the lanes of a wavefront cover CONSECUTIVE output pixels, so
-// one load instruction of the bilinear taps touches ~13 cache lines (24 B per lane at a 12-B lane stride) instead of 48 (at
-// the 48-B stride of 4 consecutive pixels per thread) -- the texture addresser was 83 % busy that way (PMC TA_BUSY) and
-// limited the read side to 2.8 TB/s -- and the stores are whole lines (12 B per lane, contiguous).
-template <int TILE_TX, int NT = 256>
-struct TileShell {
-    static constexpr int TILE_W = TILE_TX * TILE_PX, TILE_H = NT / TILE_TX;
-    int frame, tile_x, tile_y, x0, y, npx;
-    bool active;
-    __device__ __forceinline__ TileShell(int tiles_x, int tiles_y, int dh, int dw)
-    {
-        const unsigned t = xcd_remap(blockIdx.x, gridDim.x);
-        const unsigned tiles_per_frame = (unsigned)tiles_x * tiles_y;
-        frame = t / tiles_per_frame;
-        const unsigned tr = t - frame * tiles_per_frame;
-        tile_y = tr / tiles_x;
-        tile_x = tr - tile_y * tiles_x;
-        const int tx = threadIdx.x % TILE_TX, ty = threadIdx.x / TILE_TX;
-        x0 = tile_x * TILE_W + tx;
-        y = tile_y * TILE_H + ty;
-        active = (y < dh) && (x0 < dw);
-        npx = active ? (int)((unsigned)(dw - x0 + TILE_TX - 1) / TILE_TX) : 0;   // pixels x0 + p*TILE_TX < dw (callers cap it at TILE_PX); active: dw > x0
-    }
-};
-
-// Per-thread counts of an NT-thread block -> wave shuffle -> LDS -> one atomic per counter and block, only if non-zero
-// and asked for (out[c] != nullptr); out[c] is a per-frame array.
-template <int NC, int NT = 256>
-__device__ __forceinline__ void block_count_add(unsigned (&v)[NC], unsigned* const (&out)[NC], int frame)
-{
-    static_assert(NT % 64 == 0, "whole wavefronts");
-    constexpr int WAVES = NT / 64;
-    __shared__ unsigned s_cnt[NC][WAVES];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int c = 0; c < NC; c++) v[c] += __shfl_down(v[c], off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < NC; c++) s_cnt[c][threadIdx.x >> 6] = v[c];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int c = 0; c < NC; c++) {
-            unsigned total = s_cnt[c][0];
-#pragma unroll
-            for (int w = 1; w < WAVES; w++) total += s_cnt[c][w];
-            if (total && out[c]) atomicAdd(out[c] + frame, total);
-        }
-    }
-}
-
-// warp_pixel's displacement hook, of two kinds.  OUTPUT == false: a functor evaluated at the source position
-// q = (Xn * Wn, Yn * Wn) that gives the offset (cx, cy) taken off it before the roundings.  OUTPUT == true: `solve`, evaluated
-// on the output pixel in front of the matrix (MeshInverseDisplacement).  NoDisplacement is the plain warp: nothing of the
-// hook is compiled.
-struct NoDisplacement {
-    static constexpr bool ACTIVE = false;
-    static constexpr bool OUTPUT = false;
 };
 
 // one axis of the mesh lookup: clamped coordinate -> cell index and fraction (the rule's operation order, include/vstab.h)
@@ -332,112 +103,6 @@ struct MeshInverseDisplacement {
         return done;
     }
 };
-
-// One transform record in registers, as warp_kernel and temporal_fill_kernel use it for all pixels of a thread.
-template <int INTERP, int SUBPIX>
-struct XformRegs {
-    static constexpr bool EXACT = SUBPIX == VSTAB_SUBPIX_EXACT && INTERP == VSTAB_INTERP_BILINEAR;
-    double m0, m1, m2, m3, m4, m5, m6, m7, m8;
-    float mf[9];      // EXACT only
-    bool affine, fast_ok;
-    __device__ __forceinline__ explicit XformRegs(const WarpXform* __restrict__ xf)
-        : m0(xf->m[0]), m1(xf->m[1]), m2(xf->m[2]), m3(xf->m[3]), m4(xf->m[4]), m5(xf->m[5]), m6(xf->m[6]), m7(xf->m[7]),
-          m8(xf->m[8]), affine(xf->affine != 0)
-    {
-        if (EXACT) {
-#pragma unroll
-            for (int i = 0; i < 9; i++) mf[i] = (float)xf->m[i];
-        }
-        fast_ok = affine && !EXACT;
-    }
-};
-
-// The warp's source position of output pixel (x, y) under one transform, and what is sampled there: THE definition of the
-// coordinate arithmetic (f64 row-start terms per OpenCV column block, Q5 rounding or the float32 `exact` chain), shared by
-// warp_kernel, mesh_warp_kernel and temporal_fill_kernel.  `q5(X, Y)` samples at the 1/32-px coordinates, `exact(fsx, fsy)`
-// at the float32 ones; `c` receives the nearest-neighbour coverage (WITH_MASK only).  `disp` (see NoDisplacement) moves
-// the source position: s = q - disp(q), applied to the unrounded value in front of each of the three roundings.  A `disp` of
-// the OUTPUT kind moves the output pixel by e = disp.solve(x, y) in front of the matrix instead: m * e is added to the
-// unrounded terms Xn, Yn, W (and, float32-rounded, to the `exact` chain's), and *unconverged counts the pixels whose solve
-// hit its step limit.  e == 0 adds nothing at all (not even a signed zero): the plain warp's bits.
-template <int INTERP, int SUBPIX, bool WITH_MASK, class SampleQ5, class SampleExact, class Disp>
-__device__ __forceinline__ Px warp_pixel(const WarpXform* __restrict__ xf, const XformRegs<INTERP, SUBPIX>& r, int sh, int sw,
-                                         int dw, int bw0, int bw0_pow2, int x, int y, double dy, SampleQ5&& q5,
-                                         SampleExact&& exact, const Disp& disp, float& c, unsigned* unconverged = nullptr)
-{
-    // OpenCV evaluates the row-start terms X0, Y0, W0 once per 64-wide column block (xb) and adds m * (x - xb)
-    // per pixel; a thread's pixels lie in up to TILE_PX different blocks, so the terms are formed per pixel.
-    const int xb = block_origin(x, dw, bw0, bw0_pow2);
-    const double dxb = (double)xb;
-    const double X0 = r.m0 * dxb + r.m1 * dy + r.m2;
-    const double Y0 = r.m3 * dxb + r.m4 * dy + r.m5;
-    const double W0 = r.m6 * dxb + r.m7 * dy + r.m8;
-    const double dx1 = (double)(x - xb);
-    const double Xn = X0 + r.m0 * dx1, Yn = Y0 + r.m3 * dx1;
-    Px v;
-    // Fast path (the common case): affine map whose 1/32-px coordinates stay far inside the range where
-    // OpenCV's INT clamp and short saturation are no-ops.  A displaced pixel takes the general branch.
-    bool small = false;
-    if constexpr (!Disp::ACTIVE) small = r.fast_ok && __builtin_fabs(Xn * xf->wq) < 1.0e6 && __builtin_fabs(Yn * xf->wq) < 1.0e6;
-    if (small) {
-        const int X = round_small(Xn * xf->wq), Y = round_small(Yn * xf->wq);
-        v = q5(X, Y);
-        if (WITH_MASK) {
-            const int nx = round_small(Xn * xf->wn), ny = round_small(Yn * xf->wn);
-            c = ((unsigned)nx < (unsigned)sw && (unsigned)ny < (unsigned)sh) ? 1.f : 0.f;
-        }
-    } else {
-        // OUTPUT kind: the displaced terms (Xd, Yd) and what m * e adds to W and to the float32 chain
-        double Xd = Xn, Yd = Yn, dX = 0.0, dY = 0.0, dW = 0.0;
-        bool moved = false;
-        if constexpr (Disp::OUTPUT) {
-            double ex, ey;
-            if (!disp.solve(x, y, ex, ey)) *unconverged += 1u;
-            moved = !(ex == 0.0 && ey == 0.0);
-            if (moved) {
-                dX = r.m0 * ex + r.m1 * ey; dY = r.m3 * ex + r.m4 * ey; dW = r.m6 * ex + r.m7 * ey;
-                Xd = Xn + dX; Yd = Yn + dY;
-            }
-        }
-        double Wq, Wn;
-        if (r.affine) { Wq = xf->wq; Wn = xf->wn; }
-        else {
-            // one fp64 division serves both: 32/W == 32 * (1/W) bit for bit (scaling a correctly rounded
-            // quotient by a power of two is exact)
-            double W = W0 + r.m6 * dx1;
-            if constexpr (Disp::OUTPUT) { if (moved) W = W + dW; }
-            Wn = (W != 0.0) ? 1.0 / W : 0.0;
-            Wq = 32.0 * Wn;
-        }
-        double cx = 0.0, cy = 0.0;
-        if constexpr (Disp::ACTIVE && !Disp::OUTPUT) disp(Xn * Wn, Yn * Wn, cx, cy);
-        if (XformRegs<INTERP, SUBPIX>::EXACT) {
-            float fsx, fsy;
-            if constexpr (Disp::OUTPUT) {
-                float w = x * r.mf[6] + y * r.mf[7] + r.mf[8];
-                float numx = x * r.mf[0] + y * r.mf[1] + r.mf[2], numy = x * r.mf[3] + y * r.mf[4] + r.mf[5];
-                if (moved) { numx = numx + (float)dX; numy = numy + (float)dY; w = w + (float)dW; }
-                fsx = numx / w; fsy = numy / w;
-            } else {
-                const float w = x * r.mf[6] + y * r.mf[7] + r.mf[8];
-                fsx = (x * r.mf[0] + y * r.mf[1] + r.mf[2]) / w;
-                fsy = (x * r.mf[3] + y * r.mf[4] + r.mf[5]) / w;
-                if constexpr (Disp::ACTIVE) { fsx = (float)((double)fsx - cx); fsy = (float)((double)fsy - cy); }
-            }
-            v = exact(fsx, fsy);
-        } else {
-            double Xq = Xd * Wq, Yq = Yd * Wq;
-            if constexpr (Disp::ACTIVE && !Disp::OUTPUT) { Xq = Xq - 32.0 * cx; Yq = Yq - 32.0 * cy; }
-            v = q5(clamp_round_i32(Xq), clamp_round_i32(Yq));
-        }
-        if (WITH_MASK) {
-            double qx = Xd * Wn, qy = Yd * Wn;
-            if constexpr (Disp::ACTIVE && !Disp::OUTPUT) { qx = qx - cx; qy = qy - cy; }
-            c = vstab_nn_covered(qx, qy, sh, sw) ? 1.f : 0.f;
-        }
-    }
-    return v;
-}
 
 // The mesh warp's arguments: the plain warp's plus the per-frame vertex tables.
 struct MeshWarpArgs : WarpArgs {
@@ -1049,26 +714,15 @@ __global__ __launch_bounds__((BlurGeom<INTERP, SUBPIX>::NT)) __attribute__((amdg
     }
 }
 
-// Tiles of tx * TILE_PX x nt / tx output pixels over n frames of dw x dh: the tile counts and the launch grid.
-int tile_grid(const char* who, int n, int dh, int dw, int tx, int nt, int* tiles_x, int* tiles_y, unsigned* grid)
-{
-    *tiles_x = (dw + tx * TILE_PX - 1) / (tx * TILE_PX);
-    *tiles_y = (dh + nt / tx - 1) / (nt / tx);
-    const unsigned long long blocks = (unsigned long long)*tiles_x * *tiles_y * n;
-    VSTAB_REQUIRE(blocks > 0 && blocks < 0x7fffffffULL, "%s: grid of %llu blocks is out of range", who, blocks);
-    *grid = (unsigned)blocks;
-    return 0;
-}
-
 template <int INTERP, int SUBPIX>
 int launch_blur(WarpArgs a, bool with_mask, hipStream_t st)
 {
     using G = BlurGeom<INTERP, SUBPIX>;
     constexpr int TILE_W = 32 * TILE_PX;
     unsigned blocks = 0;
-    if (int rc = tile_grid("warp", a.n, a.dh, a.dw, 32, G::NT, &a.tiles_x, &a.tiles_y, &blocks)) return rc;
+    if (int rc = vstab_tile_grid("warp", a.n, a.dh, a.dw, 32, G::NT, &a.tiles_x, &a.tiles_y, &blocks)) return rc;
     // staged-path precondition that does not depend on the block: a thread's two pixels share OpenCV's column block (the
-    // u24 multiply of the window index is exact: check_common has sh, sw <= 32767 and the window is at most 4864 texels)
+    // u24 multiply of the window index is exact: vstab_check_common has sh, sw <= 32767 and the window is at most 4864 texels)
     a.blur_fast = ((a.bw0 >= a.dw) || (a.bw0 % TILE_W == 0)) ? 1 : 0;
     // the prologue (corner classification, staging, two barriers) is amortised over the samples: measured break-even
     // S = 4 for bilinear (S = 3: 2.00 vs 1.86 ms per 64 x 1080p; S = 5: 2.38 vs 2.50), below 3 for bicubic
@@ -1130,7 +784,7 @@ int launch_warp(WarpArgs a, int interp, int subpix, bool with_mask, hipStream_t 
     int tx = 32;
     if (const char* e = getenv("VSTAB_WARP_TX")) { const int v = atoi(e); if (v == 8 || v == 16 || v == 64) tx = v; }
     unsigned grid = 0;
-    if (int rc = tile_grid("warp", a.n, a.dh, a.dw, tx, 256, &a.tiles_x, &a.tiles_y, &grid)) return rc;
+    if (int rc = vstab_tile_grid("warp", a.n, a.dh, a.dw, tx, 256, &a.tiles_x, &a.tiles_y, &grid)) return rc;
     if (interp == VSTAB_INTERP_BICUBIC) launch_mask<VSTAB_INTERP_BICUBIC, VSTAB_SUBPIX_Q5>(a, with_mask, grid, st, tx);
     else if (subpix == VSTAB_SUBPIX_EXACT) launch_mask<VSTAB_INTERP_BILINEAR, VSTAB_SUBPIX_EXACT>(a, with_mask, grid, st, tx);
     else launch_mask<VSTAB_INTERP_BILINEAR, VSTAB_SUBPIX_Q5>(a, with_mask, grid, st, tx);
@@ -1145,47 +799,12 @@ int launch_warp_blur(const WarpArgs& a, int interp, int subpix, bool with_mask, 
     return launch_blur<VSTAB_INTERP_BILINEAR, VSTAB_SUBPIX_Q5>(a, with_mask, st);
 }
 
-// The limits every entry point of this file puts on frame count and sizes, and on the sub-pixel mode: one definition each, so
-// that an entry point "checked as vstab_warp_batch checks it" (the mesh forms, the coverage extent) stays so.
-int check_sizes(const char* who, int n, int sh, int sw, int dh, int dw)
-{
-    VSTAB_REQUIRE(n > 0 && sh > 0 && sw > 0 && dh > 0 && dw > 0, "%s: non-positive size (n=%d src=%dx%d out=%dx%d)", who, n, sw, sh, dw, dh);
-    VSTAB_REQUIRE(sh <= 32767 && sw <= 32767, "%s: source larger than 32767 px is not representable in OpenCV's short maps", who);
-    VSTAB_REQUIRE((long long)sh * sw < (1LL << 30) && (long long)dh * dw < (1LL << 30), "%s: frames of 2^30 pixels or more are not supported (32-bit in-frame offsets)", who);
-    return 0;
-}
-
-int check_subpix(const char* who, int subpix)
-{
-    VSTAB_REQUIRE(subpix == VSTAB_SUBPIX_Q5 || subpix == VSTAB_SUBPIX_EXACT, "%s: unknown subpix mode %d", who, subpix);
-    return 0;
-}
-
 // A mesh of mw x mh vertices over a domain_w x domain_h canvas (`domain`: which canvas that is, for the message).
 int check_mesh(const char* who, int n, int sh, int sw, int dh, int dw, int domain_h, int domain_w, const char* domain, int mw, int mh)
 {
     VSTAB_REQUIRE(domain_h >= 2 && domain_w >= 2, "%s: bad size (n=%d src=%dx%d out=%dx%d; the %s must be at least 2x2)", who, n, sw, sh, dw, dh, domain);
     VSTAB_REQUIRE(mw >= 2 && mh >= 2 && mw <= MESH_MAX_VERTS && mh <= MESH_MAX_VERTS, "%s: %dx%d vertices outside 2..%d", who, mw, mh, MESH_MAX_VERTS);
     return 0;
-}
-
-int check_common(const char* who, vstab_ctx* ctx, const void* src, int n, int sh, int sw, const void* mats,
-                 int dh, int dw, int interp, const float* border, int subpix, const void* dst)
-{
-    VSTAB_REQUIRE(ctx != nullptr, "%s: ctx is NULL", who);
-    VSTAB_REQUIRE(src && mats && border && dst, "%s: NULL pointer argument", who);
-    if (int rc = check_sizes(who, n, sh, sw, dh, dw)) return rc;
-    VSTAB_REQUIRE(interp == VSTAB_INTERP_BILINEAR || interp == VSTAB_INTERP_BICUBIC, "%s: unknown interpolation %d", who, interp);
-    if (int rc = check_subpix(who, subpix)) return rc;
-    VSTAB_REQUIRE(!(subpix == VSTAB_SUBPIX_EXACT && interp == VSTAB_INTERP_BICUBIC), "%s: exact sub-pixel mode exists for bilinear only", who);
-    return 0;
-}
-
-// OpenCV's column block width for a dw x dh output and whether it is a power of two (block_origin's cheap form).
-void set_block_width(int dh, int dw, int* bw0, int* bw0_pow2)
-{
-    *bw0 = vstab_warp_block_width(dh, dw);
-    *bw0_pow2 = (*bw0 & (*bw0 - 1)) == 0;
 }
 
 // What every warp launch shares: pointers, sizes, OpenCV's column block width, the border colour.
@@ -1195,11 +814,58 @@ void fill_geometry(WarpArgs& a, const float* src, const WarpXform* xf, int n, in
     a.src = src; a.dst = dst; a.mask = mask; a.pad_count = pad_count; a.xf = xf;
     a.samples = 1; a.nxf_per_frame = 1;
     a.n = n; a.sh = sh; a.sw = sw; a.dh = dh; a.dw = dw;
-    set_block_width(dh, dw, &a.bw0, &a.bw0_pow2);
+    vstab_set_block_width(dh, dw, &a.bw0, &a.bw0_pow2);
     a.b0 = border[0]; a.b1 = border[1]; a.b2 = border[2];
 }
 
 }  // namespace
+
+// Host helpers shared with vstab_neighbour.hip (vstab_internal.h).  Tiles of tx * TILE_PX x nt / tx output pixels over n
+// frames of dw x dh: the tile counts and the launch grid.
+int vstab_tile_grid(const char* who, int n, int dh, int dw, int tx, int nt, int* tiles_x, int* tiles_y, unsigned* grid)
+{
+    *tiles_x = (dw + tx * TILE_PX - 1) / (tx * TILE_PX);
+    *tiles_y = (dh + nt / tx - 1) / (nt / tx);
+    const unsigned long long blocks = (unsigned long long)*tiles_x * *tiles_y * n;
+    VSTAB_REQUIRE(blocks > 0 && blocks < 0x7fffffffULL, "%s: grid of %llu blocks is out of range", who, blocks);
+    *grid = (unsigned)blocks;
+    return 0;
+}
+
+// The limits every entry point of this file puts on frame count and sizes, and on the sub-pixel mode: one definition each, so
+// that an entry point "checked as vstab_warp_batch checks it" (the mesh forms, the coverage extent) stays so.
+int vstab_check_sizes(const char* who, int n, int sh, int sw, int dh, int dw)
+{
+    VSTAB_REQUIRE(n > 0 && sh > 0 && sw > 0 && dh > 0 && dw > 0, "%s: non-positive size (n=%d src=%dx%d out=%dx%d)", who, n, sw, sh, dw, dh);
+    VSTAB_REQUIRE(sh <= 32767 && sw <= 32767, "%s: source larger than 32767 px is not representable in OpenCV's short maps", who);
+    VSTAB_REQUIRE((long long)sh * sw < (1LL << 30) && (long long)dh * dw < (1LL << 30), "%s: frames of 2^30 pixels or more are not supported (32-bit in-frame offsets)", who);
+    return 0;
+}
+
+int vstab_check_subpix(const char* who, int subpix)
+{
+    VSTAB_REQUIRE(subpix == VSTAB_SUBPIX_Q5 || subpix == VSTAB_SUBPIX_EXACT, "%s: unknown subpix mode %d", who, subpix);
+    return 0;
+}
+
+int vstab_check_common(const char* who, vstab_ctx* ctx, const void* src, int n, int sh, int sw, const void* mats,
+                       int dh, int dw, int interp, const float* border, int subpix, const void* dst)
+{
+    VSTAB_REQUIRE(ctx != nullptr, "%s: ctx is NULL", who);
+    VSTAB_REQUIRE(src && mats && border && dst, "%s: NULL pointer argument", who);
+    if (int rc = vstab_check_sizes(who, n, sh, sw, dh, dw)) return rc;
+    VSTAB_REQUIRE(interp == VSTAB_INTERP_BILINEAR || interp == VSTAB_INTERP_BICUBIC, "%s: unknown interpolation %d", who, interp);
+    if (int rc = vstab_check_subpix(who, subpix)) return rc;
+    VSTAB_REQUIRE(!(subpix == VSTAB_SUBPIX_EXACT && interp == VSTAB_INTERP_BICUBIC), "%s: exact sub-pixel mode exists for bilinear only", who);
+    return 0;
+}
+
+// OpenCV's column block width for a dw x dh output and whether it is a power of two (block_origin's cheap form).
+void vstab_set_block_width(int dh, int dw, int* bw0, int* bw0_pow2)
+{
+    *bw0 = vstab_warp_block_width(dh, dw);
+    *bw0_pow2 = (*bw0 & (*bw0 - 1)) == 0;
+}
 
 int vstab_stage_xforms(vstab_ctx* ctx, const float* m32, size_t count, const WarpXform** dev_out)
 {
@@ -1255,7 +921,7 @@ extern "C" int vstab_warp_batch(vstab_ctx* ctx, const float* src, int n, int src
                                 int out_h, int out_w, int interp, const float* border_rgb, int subpix, float* dst,
                                 float* mask, uint32_t* pad_count)
 {
-    if (int rc = check_common("vstab_warp_batch", ctx, src, n, src_h, src_w, matrices, out_h, out_w, interp, border_rgb, subpix, dst)) return rc;
+    if (int rc = vstab_check_common("vstab_warp_batch", ctx, src, n, src_h, src_w, matrices, out_h, out_w, interp, border_rgb, subpix, dst)) return rc;
     VSTAB_HIP(hipSetDevice(ctx->device));
     const WarpXform* xf = nullptr;
     if (vstab_stage_xforms(ctx, matrices, (size_t)n, &xf)) return 1;
@@ -1277,7 +943,7 @@ extern "C" int vstab_warp_batch_planned(vstab_ctx* ctx, const float* src, int fi
                                         int out_w, int interp, const float* border_rgb, int subpix, float* dst, float* mask,
                                         uint32_t* pad_count)
 {
-    if (int rc = check_common("vstab_warp_batch_planned", ctx, src, n, src_h, src_w, border_rgb, out_h, out_w, interp, border_rgb, subpix, dst)) return rc;
+    if (int rc = vstab_check_common("vstab_warp_batch_planned", ctx, src, n, src_h, src_w, border_rgb, out_h, out_w, interp, border_rgb, subpix, dst)) return rc;
     const WarpXform* xf = vstab_plan_xforms(ctx, first, n);
     VSTAB_REQUIRE(xf != nullptr, "vstab_warp_batch_planned: frames [%d, %d) are outside the pending device plan", first, first + n);
     VSTAB_HIP(hipSetDevice(ctx->device));
@@ -1324,7 +990,7 @@ extern "C" int vstab_warp_blur_clip_batch(vstab_ctx* ctx, const float* src, int 
                                           int samples, int out_h, int out_w, int interp, const float* border_rgb, int subpix,
                                           float* dst, float* mask)
 {
-    if (int rc = check_common("vstab_warp_blur_clip_batch", ctx, src, n, src_h, src_w, clip_matrices, out_h, out_w, interp, border_rgb, subpix, dst)) return rc;
+    if (int rc = vstab_check_common("vstab_warp_blur_clip_batch", ctx, src, n, src_h, src_w, clip_matrices, out_h, out_w, interp, border_rgb, subpix, dst)) return rc;
     VSTAB_REQUIRE(ts != nullptr, "vstab_warp_blur_clip_batch: ts is NULL");
     VSTAB_REQUIRE(samples >= 1 && samples <= MAX_BLUR_SAMPLES, "vstab_warp_blur_clip_batch: samples=%d outside [1,%d]", samples, MAX_BLUR_SAMPLES);
     VSTAB_REQUIRE(clip_first >= 0 && clip_first + n <= clip_total,
@@ -1357,7 +1023,7 @@ int mesh_launch(const char* who, const char* kind, bool inverse, vstab_ctx* ctx,
                 const float* matrices, int out_h, int out_w, const float* border_rgb, int subpix, const float* offsets, int mw,
                 int mh, float* dst, float* mask, uint32_t* pad_count, uint32_t* unconverged)
 {
-    if (int rc = check_common(who, ctx, src, n, src_h, src_w, matrices, out_h, out_w, VSTAB_INTERP_BILINEAR, border_rgb, subpix, dst)) return rc;
+    if (int rc = vstab_check_common(who, ctx, src, n, src_h, src_w, matrices, out_h, out_w, VSTAB_INTERP_BILINEAR, border_rgb, subpix, dst)) return rc;
     VSTAB_REQUIRE(offsets != nullptr, "%s: NULL pointer argument", who);
     const int domain_h = inverse ? out_h : src_h, domain_w = inverse ? out_w : src_w;
     if (int rc = check_mesh(who, n, src_h, src_w, out_h, out_w, domain_h, domain_w, inverse ? "output" : "source", mw, mh)) return rc;
@@ -1368,7 +1034,7 @@ int mesh_launch(const char* who, const char* kind, bool inverse, vstab_ctx* ctx,
     fill_geometry(a, src, xf, n, src_h, src_w, out_h, out_w, border_rgb, dst, mask, pad_count);
     a.offsets = offsets; a.mw = mw; a.mh = mh; a.unconverged = unconverged;
     unsigned blocks = 0;
-    if (int rc = tile_grid(who, n, out_h, out_w, 32, 256, &a.tiles_x, &a.tiles_y, &blocks)) return rc;
+    if (int rc = vstab_tile_grid(who, n, out_h, out_w, 32, 256, &a.tiles_x, &a.tiles_y, &blocks)) return rc;
     if (pad_count) VSTAB_HIP(hipMemsetAsync(pad_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
     if (unconverged) VSTAB_HIP(hipMemsetAsync(unconverged, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
     const size_t lds = (size_t)mw * mh * 2 * sizeof(float);    // <= 33.8 KB
@@ -1417,8 +1083,8 @@ extern "C" int vstab_cover_extent_batch(vstab_ctx* ctx, const float* matrices, i
     VSTAB_REQUIRE(out_w >= 2 && out_h >= 2, "%s: a %dx%d canvas has no centred extent (both sides must be at least 2 px)", who, out_w, out_h);
     VSTAB_REQUIRE((long long)(out_w - 1) * (out_h - 1) < (1LL << 31), "%s: (out_w-1)*(out_h-1) of a %dx%d canvas does not fit the 32-bit extent", who, out_w, out_h);
     // the rest as vstab_warp_batch / vstab_mesh_warp_batch check it: the same routines
-    if (int rc = check_sizes(who, n, src_h, src_w, out_h, out_w)) return rc;
-    if (int rc = check_subpix(who, subpix)) return rc;
+    if (int rc = vstab_check_sizes(who, n, src_h, src_w, out_h, out_w)) return rc;
+    if (int rc = vstab_check_subpix(who, subpix)) return rc;
     VSTAB_REQUIRE(((uintptr_t)extent & 3) == 0, "%s: extent is not aligned to its element size", who);
     if (offsets != nullptr) {
         if (int rc = check_mesh(who, n, src_h, src_w, out_h, out_w, src_h, src_w, "source", mw, mh)) return rc;
@@ -1431,7 +1097,7 @@ extern "C" int vstab_cover_extent_batch(vstab_ctx* ctx, const float* matrices, i
     fill_geometry(a, nullptr, xf, n, src_h, src_w, out_h, out_w, no_border, nullptr, nullptr, nullptr);
     a.offsets = offsets; a.mw = mw; a.mh = mh;
     unsigned blocks = 0;
-    if (int rc = tile_grid(who, n, out_h, out_w, 32, 256, &a.tiles_x, &a.tiles_y, &blocks)) return rc;
+    if (int rc = vstab_tile_grid(who, n, out_h, out_w, 32, 256, &a.tiles_x, &a.tiles_y, &blocks)) return rc;
     const dim3 grid(blocks), block(256);
     KernelTimer timer(ctx, "cover_extent");
     hipLaunchKernelGGL(extent_preset_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, extent, n);
@@ -1444,728 +1110,6 @@ extern "C" int vstab_cover_extent_batch(vstab_ctx* ctx, const float* matrices, i
         if (subpix == VSTAB_SUBPIX_EXACT) hipLaunchKernelGGL((cover_extent_kernel<VSTAB_SUBPIX_EXACT, WarpArgs>), grid, block, 0, ctx->stream, plain, extent);
         else hipLaunchKernelGGL((cover_extent_kernel<VSTAB_SUBPIX_Q5, WarpArgs>), grid, block, 0, ctx->stream, plain, extent);
     }
-    VSTAB_HIP(hipGetLastError());
-    return 0;
-}
-
-// ---- temporal fill: padding pixels taken from neighbouring frames ----------------------------------------------------
-//
-// After a warp, an output pixel whose mask is 1 saw no source content in its own frame.  For each such pixel the kernel
-// walks up to K candidate (frame, matrix) pairs in order and takes the first one whose source position -- warp_pixel's,
-// the plain warp's own arithmetic -- has EVERY interpolation tap inside that frame: the value written is then the one
-// vstab_warp_batch would have written for that frame and matrix, and no border colour can enter it.
-//
-// Shape: the warp's 64 x 8 tile and XCD remap.  A tile reads its mask (4 B per pixel); if none of its pixels is padded the
-// block returns -- the common case, so the pass over a mostly covered clip is close to a plain read of the mask.  The
-// candidate records are block-uniform (a `const T* __restrict__` kernel parameter: scalar loads).  A wavefront leaves the
-// candidate loop as soon as none of its pixels is waiting.  Only filled pixels are stored.  dst is read by nobody
-// (candidates sample src), so working in place is free of races.
-namespace {
-
-struct FillCand {
-    WarpXform xf;
-    int frame;     // clip frame the candidate samples, -1: none (out of the clip, cut chain, singular matrix)
-    int pad_;
-};
-
-struct FillArgs {
-    const float* src;
-    float* dst;
-    float* mask;
-    signed char* filled_from;
-    unsigned* fill_count;
-    unsigned* pad_count;
-    int n, K, sh, sw, dh, dw;
-    int bw0, bw0_pow2;
-    int tiles_x, tiles_y;
-};
-
-template <int INTERP, int SUBPIX>
-__global__ __launch_bounds__(256) void temporal_fill_kernel(FillArgs a, const FillCand* __restrict__ cands)
-{
-    constexpr int TILE_TX = 32;
-    __shared__ __attribute__((aligned(16))) float s_cub[32 * 4];
-    const TileShell<TILE_TX> t(a.tiles_x, a.tiles_y, a.dh, a.dw);
-    const int frame = t.frame, x0 = t.x0, y = t.y, npx = t.npx;
-
-    float* __restrict__ Mk = a.mask + (size_t)frame * a.dh * a.dw;
-    const unsigned row = (unsigned)y * (unsigned)a.dw;
-    bool need[TILE_PX];
-    bool any = false;
-#pragma unroll
-    for (int p = 0; p < TILE_PX; p++) {
-        need[p] = (p < npx) && Mk[row + (unsigned)(x0 + p * TILE_TX)] == 1.0f;
-        any = any || need[p];
-    }
-    if (!__syncthreads_or(any)) return;   // nothing padded in this tile: nothing to fill, nothing to count
-
-    const float* cub_tab = nullptr;
-    if (INTERP == VSTAB_INTERP_BICUBIC) {
-        if (threadIdx.x < 32) cubic_coeffs((int)threadIdx.x, s_cub + threadIdx.x * 4);
-        __syncthreads();
-        cub_tab = s_cub;
-    }
-
-    float* __restrict__ D = a.dst + (size_t)frame * a.dh * a.dw * 3;
-    signed char* __restrict__ From = a.filled_from ? a.filled_from + (size_t)frame * a.dh * a.dw : nullptr;
-    const size_t src_frame = (size_t)a.sh * a.sw * 3;
-    const double dy = (double)y;
-    unsigned filled = 0;
-    typedef float f3 __attribute__((ext_vector_type(3)));
-
-    for (int k = 0; k < a.K; k++) {
-        if (!__any(any)) break;                       // wave-uniform: no pixel of this wavefront is waiting
-        const FillCand* __restrict__ cd = cands + (size_t)frame * a.K + k;
-        if (cd->frame < 0) continue;                  // block-uniform
-        const float* __restrict__ S = a.src + (size_t)cd->frame * src_frame;
-        const WarpXform* __restrict__ xf = &cd->xf;
-        const XformRegs<INTERP, SUBPIX> r(xf);
-        any = false;
-#pragma unroll
-        for (int p = 0; p < TILE_PX; p++) {
-            if (!need[p]) continue;
-            const int x = x0 + p * TILE_TX;
-            bool valid = false;
-            float c_unused = 0.f;
-            // validity = the samplers' own "all taps inside" branches (sample_q5's interior tests, sample_exact's four
-            // in-range flags): the sample is taken only then, so the border arguments are never read
-            const Px v = warp_pixel<INTERP, SUBPIX, false>(
-                xf, r, a.sh, a.sw, a.dw, a.bw0, a.bw0_pow2, x, y, dy,
-                [&](int X, int Y) {
-                    const int sx = sat_short(X >> 5), sy = sat_short(Y >> 5);
-                    if (INTERP == VSTAB_INTERP_BILINEAR) {
-                        valid = (unsigned)sx < (unsigned)(a.sw - 1) && (unsigned)sy < (unsigned)(a.sh - 1);
-                    } else {
-                        const unsigned width1 = (unsigned)(a.sw - 3 > 0 ? a.sw - 3 : 0);
-                        const unsigned height1 = (unsigned)(a.sh - 3 > 0 ? a.sh - 3 : 0);
-                        valid = (unsigned)(sx - 1) < width1 && (unsigned)(sy - 1) < height1;
-                    }
-                    return valid ? sample_q5<INTERP>(S, a.sh, a.sw, X, Y, 0.f, 0.f, 0.f, cub_tab) : Px{0.f, 0.f, 0.f};
-                },
-                [&](float fsx, float fsy) {
-                    const float flx = __builtin_floorf(fsx), fly = __builtin_floorf(fsy);   // NaN / inf compare false
-                    valid = flx >= 0.f && flx < (float)(a.sw - 1) && fly >= 0.f && fly < (float)(a.sh - 1);
-                    return valid ? sample_exact(S, a.sh, a.sw, fsx, fsy, 0.f, 0.f, 0.f) : Px{0.f, 0.f, 0.f};
-                },
-                NoDisplacement{}, c_unused);
-            if (valid) {
-                const unsigned pix = row + (unsigned)x;
-                f3 rgb = {v.r, v.g, v.b};
-                __builtin_memcpy(D + pix * 3u, &rgb, 12);
-                Mk[pix] = 0.f;
-                if (From) From[pix] = (signed char)k;
-                need[p] = false;
-                filled += 1u;
-            }
-            any = any || need[p];
-        }
-    }
-
-    if (a.fill_count != nullptr || a.pad_count != nullptr) {
-        unsigned cnt[2] = {filled, 0};   // filled, left
-#pragma unroll
-        for (int p = 0; p < TILE_PX; p++) cnt[1] += need[p] ? 1u : 0u;
-        block_count_add<2>(cnt, {a.fill_count, a.pad_count}, frame);
-    }
-}
-
-
-// The candidate records of a call: the transform of every float32 forward matrix and the frame it samples, -1 where the
-// fill skips it.  cand_frame == nullptr: the records of a frame's OWN matrices (frame 0 where usable, -1 where not).
-int fill_cand_records(const char* who, const float* matrices, const int32_t* cand_frame, size_t count, int clip_frames, FillCand* cd)
-{
-    for (size_t i = 0; i < count; i++) {
-        const int f = cand_frame ? cand_frame[i] : 0;
-        VSTAB_REQUIRE(f >= -1 && f < clip_frames, "%s: cand_frame[%zu]=%d outside [-1, %d)", who, i, f, clip_frames);
-        const float* m32 = matrices + i * 9;
-        vstab_fill_xform(m32, &cd[i].xf);
-        // a matrix that cv::invert would refuse (zero or non-finite determinant) has no source position: no candidate
-        double M[9], inv[9];
-        bool finite = true;
-        for (int j = 0; j < 9; j++) { M[j] = (double)m32[j]; finite = finite && std::isfinite(M[j]); }
-        bool ok = f >= 0 && finite && vstab_invert3x3_hd(M, inv);
-        for (int j = 0; ok && j < 9; j++) ok = std::isfinite(inv[j]);
-        cd[i].frame = ok ? f : -1;
-        cd[i].pad_ = 0;
-    }
-    return 0;
-}
-
-// ---- blended temporal fill: exposure-matched candidates, feathered seam (include/vstab.h states both rules) -------------
-//
-// Two kernels beside temporal_fill_kernel, which stays as it is (its instances, its FillCand records, its cost):
-//   fill_gain_sums_kernel       integer sums of own and candidate values over the lattice x % 8 == 4 && y % 8 == 4 where
-//                               both see source content by the interior rule; the host turns them into one gain per
-//                               (frame, candidate, channel).  A workgroup = 256 lattice pixels of one (frame, candidate) pair, so
-//                               both records are block-uniform (scalar loads); per-thread values -> wave shuffle -> LDS -> one
-//                               64-bit atomic per sum, skipped where the workgroup counted nothing.  Nothing waits for
-//                               another workgroup, and integer sums do not depend on the order of the atomics.
-//   temporal_fill_blend_kernel  the fill's tile, shell and candidate walk, with (a) the sample scaled by the candidate's gain
-//                               and (b) the own pixels within feather_px of the frame's tap-interior border cross-faded
-//                               towards the first valid candidate.  Whether an own pixel takes part costs its mask and its
-//                               own coordinate (warp_pixel with a sampler that only records X, Y: ALU, no loads); a tile
-//                               without padded or feathered pixels returns before anything else is read or stored.
-
-// All taps of the Q5 coordinate (X, Y) inside an sw x sh frame: the interior tests of sample_q5, as temporal_fill_kernel
-// states them in its sampler.
-template <int INTERP>
-__device__ __forceinline__ bool fill_taps_inside(int sh, int sw, int X, int Y)
-{
-    const int sx = sat_short(X >> 5), sy = sat_short(Y >> 5);
-    if (INTERP == VSTAB_INTERP_BILINEAR) return (unsigned)sx < (unsigned)(sw - 1) && (unsigned)sy < (unsigned)(sh - 1);
-    const unsigned width1 = (unsigned)(sw - 3 > 0 ? sw - 3 : 0);
-    const unsigned height1 = (unsigned)(sh - 3 > 0 ? sh - 3 : 0);
-    return (unsigned)(sx - 1) < width1 && (unsigned)(sy - 1) < height1;
-}
-
-// The Q5 coordinate of output pixel (x, y) under one record: warp_pixel with samplers that read nothing.
-template <int INTERP>
-__device__ __forceinline__ void fill_coordinate(const WarpXform* __restrict__ xf, const XformRegs<INTERP, VSTAB_SUBPIX_Q5>& r, int sh,
-                                                int sw, int dw, int bw0, int bw0_pow2, int x, int y, double dy, int& X, int& Y)
-{
-    float c_unused = 0.f;
-    int ox = 0, oy = 0;
-    (void)warp_pixel<INTERP, VSTAB_SUBPIX_Q5, false>(
-        xf, r, sh, sw, dw, bw0, bw0_pow2, x, y, dy, [&](int qx, int qy) { ox = qx; oy = qy; return Px{0.f, 0.f, 0.f}; },
-        [&](float, float) { return Px{0.f, 0.f, 0.f}; }, NoDisplacement{}, c_unused);
-    X = ox; Y = oy;
-}
-
-// The fill's sample of one candidate at (x, y), taken only where every tap is inside (`valid`).
-template <int INTERP>
-__device__ __forceinline__ Px fill_candidate_sample(const float* __restrict__ S, const WarpXform* __restrict__ xf,
-                                                    const XformRegs<INTERP, VSTAB_SUBPIX_Q5>& r, int sh, int sw, int dw, int bw0,
-                                                    int bw0_pow2, int x, int y, double dy, const float* cub_tab, bool& valid)
-{
-    float c_unused = 0.f;
-    bool ok = false;
-    const Px v = warp_pixel<INTERP, VSTAB_SUBPIX_Q5, false>(
-        xf, r, sh, sw, dw, bw0, bw0_pow2, x, y, dy,
-        [&](int X, int Y) {
-            ok = fill_taps_inside<INTERP>(sh, sw, X, Y);
-            return ok ? sample_q5<INTERP>(S, sh, sw, X, Y, 0.f, 0.f, 0.f, cub_tab) : Px{0.f, 0.f, 0.f};
-        },
-        [&](float, float) { return Px{0.f, 0.f, 0.f}; }, NoDisplacement{}, c_unused);
-    valid = ok;
-    return v;
-}
-
-// q of the gain sums: a value in 16 fractional bits, truncated; below 0 and NaN give 0, 1 and above give 65536.
-__device__ __forceinline__ unsigned gain_q(float v)
-{
-    return v > 0.f ? (v < 1.f ? (unsigned)(v * 65536.0f) : 65536u) : 0u;
-}
-
-struct GainArgs {
-    const float* src;
-    const float* dst;
-    unsigned long long* sums;   // [n, K, 7]
-    int K, sh, sw, dh, dw;
-    int bw0, bw0_pow2;
-    int lw;                     // lattice columns: x = 8 * lx + 4 < dw
-    unsigned lattice;           // lattice pixels per frame
-    unsigned blocks_per_pair;   // workgroups per (frame, candidate) pair
-};
-
-template <int INTERP>
-__global__ __launch_bounds__(256) void fill_gain_sums_kernel(GainArgs a, const FillCand* __restrict__ cands, const FillCand* __restrict__ own)
-{
-    constexpr int NS = 7, WAVES = 4;
-    __shared__ __attribute__((aligned(16))) float s_cub[32 * 4];
-    __shared__ unsigned s_sum[NS][WAVES];
-    const unsigned pair = blockIdx.x / a.blocks_per_pair;          // frame * K + k
-    const unsigned chunk = blockIdx.x - pair * a.blocks_per_pair;
-    const unsigned frame = pair / (unsigned)a.K;
-    const FillCand* __restrict__ cd = cands + pair;
-    const FillCand* __restrict__ ow = own + frame;
-    if (ow->frame < 0 || cd->frame < 0) return;                    // block-uniform: this pair counts nothing
-
-    const float* cub_tab = nullptr;
-    if (INTERP == VSTAB_INTERP_BICUBIC) {
-        if (threadIdx.x < 32) cubic_coeffs((int)threadIdx.x, s_cub + threadIdx.x * 4);
-        __syncthreads();
-        cub_tab = s_cub;
-    }
-
-    // a workgroup's sums fit 32 bits: 256 values of at most 65536
-    unsigned v[NS];
-#pragma unroll
-    for (int c = 0; c < NS; c++) v[c] = 0u;
-    const unsigned l = chunk * 256u + threadIdx.x;
-    if (l < a.lattice) {
-        const unsigned ly = l / (unsigned)a.lw;
-        const int x = (int)(l - ly * (unsigned)a.lw) * VSTAB_FILL_GAIN_STRIDE + VSTAB_FILL_GAIN_STRIDE / 2;   // x < dw, y < dh by the
-        const int y = (int)ly * VSTAB_FILL_GAIN_STRIDE + VSTAB_FILL_GAIN_STRIDE / 2;                            // lattice's size
-        const double dy = (double)y;
-        int X, Y;
-        {
-            const WarpXform* __restrict__ xo = &ow->xf;
-            const XformRegs<INTERP, VSTAB_SUBPIX_Q5> ro(xo);
-            fill_coordinate<INTERP>(xo, ro, a.sh, a.sw, a.dw, a.bw0, a.bw0_pow2, x, y, dy, X, Y);
-        }
-        if (fill_taps_inside<INTERP>(a.sh, a.sw, X, Y)) {
-            const float* __restrict__ S = a.src + (size_t)cd->frame * ((size_t)a.sh * a.sw * 3);
-            const WarpXform* __restrict__ xf = &cd->xf;
-            const XformRegs<INTERP, VSTAB_SUBPIX_Q5> r(xf);
-            bool valid = false;
-            const Px s = fill_candidate_sample<INTERP>(S, xf, r, a.sh, a.sw, a.dw, a.bw0, a.bw0_pow2, x, y, dy, cub_tab, valid);
-            if (valid) {
-                const float* __restrict__ D = a.dst + (size_t)frame * a.dh * a.dw * 3;
-                const Px o = load_px(D + ((unsigned)y * (unsigned)a.dw + (unsigned)x) * 3u);
-                v[0] = 1u;
-                v[1] = gain_q(o.r); v[2] = gain_q(o.g); v[3] = gain_q(o.b);
-                v[4] = gain_q(s.r); v[5] = gain_q(s.g); v[6] = gain_q(s.b);
-            }
-        }
-    }
-
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int c = 0; c < NS; c++) v[c] += __shfl_down(v[c], off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < NS; c++) s_sum[c][threadIdx.x >> 6] = v[c];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned total[NS];
-#pragma unroll
-        for (int c = 0; c < NS; c++) total[c] = s_sum[c][0] + s_sum[c][1] + s_sum[c][2] + s_sum[c][3];
-        if (total[0] != 0u) {       // nothing counted: every sum is zero, no atomic
-            unsigned long long* out = a.sums + (size_t)pair * NS;
-#pragma unroll
-            for (int c = 0; c < NS; c++) atomicAdd(out + c, (unsigned long long)total[c]);
-        }
-    }
-}
-
-struct BlendArgs : FillArgs {
-    unsigned* blend_count;
-    int Fe;             // 32 * feather_px
-    int lo, hi_x, hi_y; // the tap-interior border in 1/32 px: lo <= X <= hi_x, lo <= Y <= hi_y
-};
-
-template <int INTERP>
-__global__ __launch_bounds__(256) void temporal_fill_blend_kernel(BlendArgs a, const FillCand* __restrict__ cands,
-                                                                  const FillCand* __restrict__ own, const float* __restrict__ gains)
-{
-    constexpr int TILE_TX = 32;
-    __shared__ __attribute__((aligned(16))) float s_cub[32 * 4];
-    const TileShell<TILE_TX> t(a.tiles_x, a.tiles_y, a.dh, a.dw);
-    const int frame = t.frame, x0 = t.x0, y = t.y, npx = t.npx;
-
-    float* __restrict__ Mk = a.mask + (size_t)frame * a.dh * a.dw;
-    const unsigned row = (unsigned)y * (unsigned)a.dw;
-    const double dy = (double)y;
-    const FillCand* __restrict__ ow = own + frame;
-    const bool feather = a.Fe > 0 && ow->frame >= 0;      // block-uniform
-    bool need[TILE_PX], padded[TILE_PX];
-    float wgt[TILE_PX];                                   // own pixels: the weight of the own value
-    bool any = false;
-#pragma unroll
-    for (int p = 0; p < TILE_PX; p++) {
-        need[p] = padded[p] = false;
-        wgt[p] = 1.0f;
-        if (p < npx) {
-            const int x = x0 + p * TILE_TX;
-            if (Mk[row + (unsigned)x] == 1.0f) need[p] = padded[p] = true;
-            else if (feather) {
-                const WarpXform* __restrict__ xo = &ow->xf;
-                const XformRegs<INTERP, VSTAB_SUBPIX_Q5> ro(xo);
-                int X, Y;
-                fill_coordinate<INTERP>(xo, ro, a.sh, a.sw, a.dw, a.bw0, a.bw0_pow2, x, y, dy, X, Y);
-                // d32 = min(X - lo, Y - lo, hi_x - X, hi_y - Y), clamped to [0, Fe].  X and Y may be anywhere in int: one
-                // step outside the border already gives a negative term, so they are clamped to that first and no
-                // difference can overflow.
-                const int Xc = min(max(X, a.lo - 1), a.hi_x + 1), Yc = min(max(Y, a.lo - 1), a.hi_y + 1);
-                const int d32 = min(min(Xc - a.lo, Yc - a.lo), min(a.hi_x - Xc, a.hi_y - Yc));
-                const int d = min(max(d32, 0), a.Fe);
-                wgt[p] = (float)d / (float)a.Fe;
-                need[p] = d < a.Fe;                       // w < 1 (d == Fe divides to exactly 1.0f)
-            }
-        }
-        any = any || need[p];
-    }
-    if (!__syncthreads_or(any)) return;   // nothing padded, nothing within the feather: nothing to read, store or count
-
-    const float* cub_tab = nullptr;
-    if (INTERP == VSTAB_INTERP_BICUBIC) {
-        if (threadIdx.x < 32) cubic_coeffs((int)threadIdx.x, s_cub + threadIdx.x * 4);
-        __syncthreads();
-        cub_tab = s_cub;
-    }
-
-    float* __restrict__ D = a.dst + (size_t)frame * a.dh * a.dw * 3;
-    signed char* __restrict__ From = a.filled_from ? a.filled_from + (size_t)frame * a.dh * a.dw : nullptr;
-    const size_t src_frame = (size_t)a.sh * a.sw * 3;
-    unsigned filled = 0, blended = 0;
-    typedef float f3 __attribute__((ext_vector_type(3)));
-
-    for (int k = 0; k < a.K; k++) {
-        if (!__any(any)) break;                       // wave-uniform: no pixel of this wavefront is waiting
-        const FillCand* __restrict__ cd = cands + (size_t)frame * a.K + k;
-        if (cd->frame < 0) continue;                  // block-uniform
-        const float* __restrict__ S = a.src + (size_t)cd->frame * src_frame;
-        const float* __restrict__ g = gains + ((size_t)frame * a.K + k) * 3;
-        const float g0 = g[0], g1 = g[1], g2 = g[2];
-        const WarpXform* __restrict__ xf = &cd->xf;
-        const XformRegs<INTERP, VSTAB_SUBPIX_Q5> r(xf);
-        any = false;
-#pragma unroll
-        for (int p = 0; p < TILE_PX; p++) {
-            if (!need[p]) continue;
-            const int x = x0 + p * TILE_TX;
-            bool valid = false;
-            const Px s = fill_candidate_sample<INTERP>(S, xf, r, a.sh, a.sw, a.dw, a.bw0, a.bw0_pow2, x, y, dy, cub_tab, valid);
-            if (valid) {
-                const unsigned pix = row + (unsigned)x;
-                f3 rgb = {g0 * s.r, g1 * s.g, g2 * s.b};      // one float32 multiply; nothing of the old pixel enters
-                if (padded[p]) {
-                    Mk[pix] = 0.f;
-                    filled += 1u;
-                } else {
-                    const float w = wgt[p];
-                    if (w != 0.f) {                           // w == 0 (the fringe ring and beyond): the candidate alone
-                        const Px o = load_px(D + pix * 3u);
-                        const float u = 1.0f - w;
-                        rgb.x = o.r * w + rgb.x * u;
-                        rgb.y = o.g * w + rgb.y * u;
-                        rgb.z = o.b * w + rgb.z * u;
-                    }
-                    blended += 1u;
-                }
-                __builtin_memcpy(D + pix * 3u, &rgb, 12);
-                if (From) From[pix] = (signed char)k;
-                need[p] = false;
-            }
-            any = any || need[p];
-        }
-    }
-
-    if (a.fill_count != nullptr || a.pad_count != nullptr || a.blend_count != nullptr) {
-        unsigned cnt[3] = {filled, 0, blended};   // filled, left, blended
-#pragma unroll
-        for (int p = 0; p < TILE_PX; p++) cnt[1] += (need[p] && padded[p]) ? 1u : 0u;
-        block_count_add<3>(cnt, {a.fill_count, a.pad_count, a.blend_count}, frame);
-    }
-}
-
-}  // namespace
-
-extern "C" int vstab_temporal_fill_batch(vstab_ctx* ctx, const float* src, int clip_frames, int src_h, int src_w, int first,
-                                         int n, const float* matrices, const int32_t* cand_frame, int K, int out_h, int out_w,
-                                         int interp, int subpix, float* dst, float* mask, int8_t* filled_from,
-                                         uint32_t* fill_count, uint32_t* pad_count)
-{
-    const char* who = "vstab_temporal_fill_batch";
-    const float no_border[3] = {0.f, 0.f, 0.f};
-    if (int rc = check_common(who, ctx, src, n, src_h, src_w, matrices, out_h, out_w, interp, no_border, subpix, dst)) return rc;
-    VSTAB_REQUIRE(mask != nullptr && cand_frame != nullptr, "%s: NULL pointer argument", who);
-    VSTAB_REQUIRE(K >= 1 && K <= 64, "%s: K=%d outside [1,64]", who, K);
-    VSTAB_REQUIRE(clip_frames > 0 && first >= 0 && first + n <= clip_frames, "%s: frames [%d, %d) outside a clip of %d frames", who,
-                  first, first + n, clip_frames);
-    VSTAB_REQUIRE((const void*)src != (const void*)dst, "%s: dst must not alias src (candidates read src while dst is written)", who);
-    std::vector<FillCand> cd((size_t)n * K);
-    if (int rc = fill_cand_records(who, matrices, cand_frame, cd.size(), clip_frames, cd.data())) return rc;
-    VSTAB_HIP(hipSetDevice(ctx->device));
-    void* d_cd = nullptr;
-    if (vstab_stage_params(ctx, cd.data(), cd.size() * sizeof(FillCand), &d_cd)) return 1;
-
-    FillArgs a{};
-    a.src = src; a.dst = dst; a.mask = mask; a.filled_from = reinterpret_cast<signed char*>(filled_from);
-    a.fill_count = fill_count; a.pad_count = pad_count;
-    a.n = n; a.K = K; a.sh = src_h; a.sw = src_w; a.dh = out_h; a.dw = out_w;
-    set_block_width(out_h, out_w, &a.bw0, &a.bw0_pow2);
-    unsigned blocks = 0;
-    if (int rc = tile_grid(who, n, out_h, out_w, 32, 256, &a.tiles_x, &a.tiles_y, &blocks)) return rc;
-    const size_t px = (size_t)n * out_h * out_w;
-    if (filled_from) VSTAB_HIP(hipMemsetAsync(filled_from, 0xff, px, ctx->stream));   // -1: not filled
-    if (fill_count) VSTAB_HIP(hipMemsetAsync(fill_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
-    if (pad_count) VSTAB_HIP(hipMemsetAsync(pad_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
-    const FillCand* cands = static_cast<const FillCand*>(d_cd);
-    KernelTimer timer(ctx, "fill");
-    const dim3 grid(blocks), block(256);
-    if (interp == VSTAB_INTERP_BICUBIC) hipLaunchKernelGGL((temporal_fill_kernel<VSTAB_INTERP_BICUBIC, VSTAB_SUBPIX_Q5>), grid, block, 0, ctx->stream, a, cands);
-    else if (subpix == VSTAB_SUBPIX_EXACT) hipLaunchKernelGGL((temporal_fill_kernel<VSTAB_INTERP_BILINEAR, VSTAB_SUBPIX_EXACT>), grid, block, 0, ctx->stream, a, cands);
-    else hipLaunchKernelGGL((temporal_fill_kernel<VSTAB_INTERP_BILINEAR, VSTAB_SUBPIX_Q5>), grid, block, 0, ctx->stream, a, cands);
-    VSTAB_HIP(hipGetLastError());
-    return 0;
-}
-
-namespace {
-// What the two blended entries share with vstab_temporal_fill_batch: its checks, plus Q5 and the own matrices.
-int check_fill_blend(const char* who, vstab_ctx* ctx, const float* src, int clip_frames, int src_h, int src_w, int first, int n,
-                     const float* matrices, const int32_t* cand_frame, int K, const float* own_matrices, int out_h, int out_w,
-                     int interp, int subpix, const float* dst)
-{
-    const float no_border[3] = {0.f, 0.f, 0.f};
-    if (int rc = check_common(who, ctx, src, n, src_h, src_w, matrices, out_h, out_w, interp, no_border, subpix, dst)) return rc;
-    VSTAB_REQUIRE(subpix == VSTAB_SUBPIX_Q5, "%s: VSTAB_SUBPIX_EXACT is not supported (the feather distance and the gain lattice "
-                  "are stated on the 1/32-px coordinates of VSTAB_SUBPIX_Q5)", who);
-    VSTAB_REQUIRE(cand_frame != nullptr && own_matrices != nullptr, "%s: NULL pointer argument", who);
-    VSTAB_REQUIRE(K >= 1 && K <= 64, "%s: K=%d outside [1,64]", who, K);
-    VSTAB_REQUIRE(clip_frames > 0 && first >= 0 && first + n <= clip_frames, "%s: frames [%d, %d) outside a clip of %d frames", who,
-                  first, first + n, clip_frames);
-    VSTAB_REQUIRE((const void*)src != (const void*)dst, "%s: dst must not alias src (candidates read src while dst is written)", who);
-    return 0;
-}
-
-// Candidate records [n * K] followed by the own records [n], staged as one block.
-int stage_fill_blend_records(const char* who, vstab_ctx* ctx, const float* matrices, const int32_t* cand_frame, int n, int K,
-                             int clip_frames, const float* own_matrices, const float* gains, const FillCand** cands,
-                             const FillCand** own, const float** gains_dev)
-{
-    const size_t pairs = (size_t)n * K;
-    const size_t rec_bytes = (pairs + (size_t)n) * sizeof(FillCand);
-    std::vector<unsigned char> blob(rec_bytes + (gains ? pairs * 3 * sizeof(float) : 0));
-    FillCand* cd = reinterpret_cast<FillCand*>(blob.data());
-    if (int rc = fill_cand_records(who, matrices, cand_frame, pairs, clip_frames, cd)) return rc;
-    if (int rc = fill_cand_records(who, own_matrices, nullptr, (size_t)n, clip_frames, cd + pairs)) return rc;
-    if (gains) memcpy(blob.data() + rec_bytes, gains, pairs * 3 * sizeof(float));
-    void* dev = nullptr;
-    if (vstab_stage_params(ctx, blob.data(), blob.size(), &dev)) return 1;
-    *cands = static_cast<const FillCand*>(dev);
-    *own = *cands + pairs;
-    if (gains_dev) *gains_dev = reinterpret_cast<const float*>(static_cast<const unsigned char*>(dev) + rec_bytes);
-    return 0;
-}
-}  // namespace
-
-extern "C" int vstab_fill_gain_sums(vstab_ctx* ctx, const float* src, int clip_frames, int src_h, int src_w, int first, int n,
-                                    const float* matrices, const int32_t* cand_frame, int K, const float* own_matrices, int out_h,
-                                    int out_w, int interp, int subpix, const float* dst, uint64_t* sums)
-{
-    const char* who = "vstab_fill_gain_sums";
-    if (int rc = check_fill_blend(who, ctx, src, clip_frames, src_h, src_w, first, n, matrices, cand_frame, K, own_matrices, out_h,
-                                  out_w, interp, subpix, dst)) return rc;
-    VSTAB_REQUIRE(sums != nullptr, "%s: NULL pointer argument", who);
-    VSTAB_REQUIRE(((uintptr_t)sums & 7) == 0, "%s: sums is not aligned to its element size", who);
-    GainArgs a{};
-    a.src = src; a.dst = dst; a.sums = reinterpret_cast<unsigned long long*>(sums);
-    a.K = K; a.sh = src_h; a.sw = src_w; a.dh = out_h; a.dw = out_w;
-    set_block_width(out_h, out_w, &a.bw0, &a.bw0_pow2);
-    constexpr int STRIDE = VSTAB_FILL_GAIN_STRIDE, REST = STRIDE - STRIDE / 2 - 1;
-    a.lw = (out_w + REST) / STRIDE;                                    // x = STRIDE * lx + STRIDE / 2 < out_w
-    a.lattice = (unsigned)a.lw * (unsigned)((out_h + REST) / STRIDE);
-    a.blocks_per_pair = (a.lattice + 255u) / 256u;
-    const unsigned long long blocks = (unsigned long long)a.blocks_per_pair * (unsigned long long)n * (unsigned long long)K;
-    VSTAB_REQUIRE(blocks < 0x7fffffffULL, "%s: grid of %llu blocks is out of range", who, blocks);
-    VSTAB_HIP(hipSetDevice(ctx->device));
-    const FillCand *cands = nullptr, *own = nullptr;
-    if (int rc = stage_fill_blend_records(who, ctx, matrices, cand_frame, n, K, clip_frames, own_matrices, nullptr, &cands, &own, nullptr)) return rc;
-    KernelTimer timer(ctx, "fill_gain");
-    VSTAB_HIP(hipMemsetAsync(sums, 0, sizeof(uint64_t) * 7 * (size_t)n * K, ctx->stream));
-    if (blocks == 0) return 0;                                         // a canvas without a lattice pixel: every sum is zero
-    const dim3 grid((unsigned)blocks), block(256);
-    if (interp == VSTAB_INTERP_BICUBIC) hipLaunchKernelGGL((fill_gain_sums_kernel<VSTAB_INTERP_BICUBIC>), grid, block, 0, ctx->stream, a, cands, own);
-    else hipLaunchKernelGGL((fill_gain_sums_kernel<VSTAB_INTERP_BILINEAR>), grid, block, 0, ctx->stream, a, cands, own);
-    VSTAB_HIP(hipGetLastError());
-    return 0;
-}
-
-extern "C" int vstab_temporal_fill_blend_batch(vstab_ctx* ctx, const float* src, int clip_frames, int src_h, int src_w, int first,
-                                               int n, const float* matrices, const int32_t* cand_frame, int K,
-                                               const float* own_matrices, const float* gains, int feather_px, int out_h, int out_w,
-                                               int interp, int subpix, float* dst, float* mask, int8_t* filled_from,
-                                               uint32_t* fill_count, uint32_t* pad_count, uint32_t* blend_count)
-{
-    const char* who = "vstab_temporal_fill_blend_batch";
-    if (int rc = check_fill_blend(who, ctx, src, clip_frames, src_h, src_w, first, n, matrices, cand_frame, K, own_matrices, out_h,
-                                  out_w, interp, subpix, dst)) return rc;
-    VSTAB_REQUIRE(mask != nullptr && gains != nullptr, "%s: NULL pointer argument", who);
-    VSTAB_REQUIRE(feather_px >= 0 && feather_px <= VSTAB_FILL_FEATHER_MAX, "%s: feather_px=%d outside [0,%d]", who, feather_px,
-                  VSTAB_FILL_FEATHER_MAX);
-    VSTAB_HIP(hipSetDevice(ctx->device));
-    const FillCand *cands = nullptr, *own = nullptr;
-    const float* gains_dev = nullptr;
-    if (int rc = stage_fill_blend_records(who, ctx, matrices, cand_frame, n, K, clip_frames, own_matrices, gains, &cands, &own, &gains_dev)) return rc;
-
-    BlendArgs a{};
-    a.src = src; a.dst = dst; a.mask = mask; a.filled_from = reinterpret_cast<signed char*>(filled_from);
-    a.fill_count = fill_count; a.pad_count = pad_count; a.blend_count = blend_count;
-    a.n = n; a.K = K; a.sh = src_h; a.sw = src_w; a.dh = out_h; a.dw = out_w;
-    a.Fe = 32 * feather_px;
-    const int inset = interp == VSTAB_INTERP_BICUBIC ? 1 : 0;          // bicubic: X - 32 and 32 (sw - 2) - X
-    a.lo = 32 * inset; a.hi_x = 32 * (src_w - 1 - inset); a.hi_y = 32 * (src_h - 1 - inset);
-    set_block_width(out_h, out_w, &a.bw0, &a.bw0_pow2);
-    unsigned blocks = 0;
-    if (int rc = tile_grid(who, n, out_h, out_w, 32, 256, &a.tiles_x, &a.tiles_y, &blocks)) return rc;
-    const size_t px = (size_t)n * out_h * out_w;
-    if (filled_from) VSTAB_HIP(hipMemsetAsync(filled_from, 0xff, px, ctx->stream));   // -1: neither filled nor blended
-    if (fill_count) VSTAB_HIP(hipMemsetAsync(fill_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
-    if (pad_count) VSTAB_HIP(hipMemsetAsync(pad_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
-    if (blend_count) VSTAB_HIP(hipMemsetAsync(blend_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
-    KernelTimer timer(ctx, "fill_blend");
-    const dim3 grid(blocks), block(256);
-    if (interp == VSTAB_INTERP_BICUBIC) hipLaunchKernelGGL((temporal_fill_blend_kernel<VSTAB_INTERP_BICUBIC>), grid, block, 0, ctx->stream, a, cands, own, gains_dev);
-    else hipLaunchKernelGGL((temporal_fill_blend_kernel<VSTAB_INTERP_BILINEAR>), grid, block, 0, ctx->stream, a, cands, own, gains_dev);
-    VSTAB_HIP(hipGetLastError());
-    return 0;
-}
-
-// ---- sharpness transfer: own pixels of a blurred frame pulled towards what sharper neighbours show there -------------------
-//
-// The rule is stated in include/vstab.h (vstab_sharp_transfer_batch; Matsushita et al., PAMI 2006, section 5).  The fill's
-// tile, shell, XCD remap, candidate records and sampler (fill_candidate_sample: warp_pixel with the interior test), but the
-// other way round: the fill writes PADDED pixels from the FIRST valid candidate, this writes OWN pixels from EVERY valid
-// candidate with a positive ratio, weighted by how well the sample agrees with the pixel.
-//
-// Shape: only frames with a live candidate (ratio > 0, not skipped) get workgroups at all -- the host lists them
-// (`live`), so a clip without a blurred frame launches nothing and a frame that borrows nothing costs nothing: the
-// "all ratios zero" exit is taken before the launch instead of per block.  A tile reads its mask and returns if it has
-// no own pixel.  Candidates whose ratio is 0 or that are skipped are passed over block-uniformly (scalar loads of the
-// record and the ratio); there is no "first wins" exit, so every other candidate is sampled for every own pixel.  Per
-// pixel the kernel keeps o (3), num (3) and den (1) in registers, two pixels per thread.
-// Resource usage (-Rpass-analysis=kernel-resource-usage, gfx950): bilinear 52 VGPRs, 8 waves per SIMD; bicubic 100 VGPRs, 4
-// waves per SIMD; no scratch in either.
-// The two divisions are IEEE-correct (-fhip-fp32-correctly-rounded-divide-sqrt, csrc/Makefile) and nothing is fused
-// (-ffp-contract=off), so NumPy float32 gives the same bits.
-namespace {
-
-struct SharpArgs {
-    const float* src;
-    float* dst;
-    const float* mask;          // nullptr: every pixel is own
-    unsigned* transfer_count;
-    float alpha;
-    int K, sh, sw, dh, dw;
-    int bw0, bw0_pow2;
-    int tiles_x, tiles_y;
-};
-
-template <int INTERP>
-__global__ __launch_bounds__(256) void sharp_transfer_kernel(SharpArgs a, const FillCand* __restrict__ cands,
-                                                             const float* __restrict__ ratios, const int* __restrict__ live)
-{
-    constexpr int TILE_TX = 32;
-    __shared__ __attribute__((aligned(16))) float s_cub[32 * 4];
-    const TileShell<TILE_TX> t(a.tiles_x, a.tiles_y, a.dh, a.dw);
-    const int frame = live[t.frame], x0 = t.x0, y = t.y, npx = t.npx;      // t.frame counts the live frames
-
-    const unsigned row = (unsigned)y * (unsigned)a.dw;
-    bool own[TILE_PX];
-    bool any = false;
-#pragma unroll
-    for (int p = 0; p < TILE_PX; p++) {
-        own[p] = p < npx;
-        if (own[p] && a.mask != nullptr) own[p] = !(a.mask[(size_t)frame * a.dh * a.dw + row + (unsigned)(x0 + p * TILE_TX)] == 1.0f);
-        any = any || own[p];
-    }
-    if (!__syncthreads_or(any)) return;   // a tile of padding: nothing to read, store or count
-
-    const float* cub_tab = nullptr;
-    if (INTERP == VSTAB_INTERP_BICUBIC) {
-        if (threadIdx.x < 32) cubic_coeffs((int)threadIdx.x, s_cub + threadIdx.x * 4);
-        __syncthreads();
-        cub_tab = s_cub;
-    }
-
-    float* __restrict__ D = a.dst + (size_t)frame * a.dh * a.dw * 3;
-    const size_t src_frame = (size_t)a.sh * a.sw * 3;
-    const double dy = (double)y;
-    Px o[TILE_PX], num[TILE_PX];
-    float den[TILE_PX];
-#pragma unroll
-    for (int p = 0; p < TILE_PX; p++) {
-        num[p] = Px{0.f, 0.f, 0.f};
-        den[p] = 0.f;
-        o[p] = own[p] ? load_px(D + (row + (unsigned)(x0 + p * TILE_TX)) * 3u) : Px{0.f, 0.f, 0.f};
-    }
-
-    for (int k = 0; k < a.K; k++) {
-        const FillCand* __restrict__ cd = cands + (size_t)frame * a.K + k;
-        const float ratio = ratios[(size_t)frame * a.K + k];
-        if (cd->frame < 0 || !(ratio > 0.f)) continue;             // block-uniform
-        const float* __restrict__ S = a.src + (size_t)cd->frame * src_frame;
-        const WarpXform* __restrict__ xf = &cd->xf;
-        const XformRegs<INTERP, VSTAB_SUBPIX_Q5> r(xf);
-#pragma unroll
-        for (int p = 0; p < TILE_PX; p++) {
-            if (!own[p]) continue;
-            bool valid = false;
-            const Px s = fill_candidate_sample<INTERP>(S, xf, r, a.sh, a.sw, a.dw, a.bw0, a.bw0_pow2, x0 + p * TILE_TX, y, dy, cub_tab, valid);
-            if (!valid) continue;
-            const float Dd = (__builtin_fabsf(s.r - o[p].r) + __builtin_fabsf(s.g - o[p].g)) + __builtin_fabsf(s.b - o[p].b);
-            if (Dd < __builtin_inff()) {                           // false for a NaN in the sample or in the pixel
-                const float w = ratio / (ratio + a.alpha * Dd);
-                num[p].r = num[p].r + w * s.r;
-                num[p].g = num[p].g + w * s.g;
-                num[p].b = num[p].b + w * s.b;
-                den[p] = den[p] + w;
-            }
-        }
-    }
-
-    unsigned cnt[1] = {0u};
-    typedef float f3 __attribute__((ext_vector_type(3)));
-#pragma unroll
-    for (int p = 0; p < TILE_PX; p++) {
-        if (own[p] && den[p] > 0.f) {
-            const float d1 = 1.0f + den[p];
-            const f3 rgb = {(o[p].r + num[p].r) / d1, (o[p].g + num[p].g) / d1, (o[p].b + num[p].b) / d1};
-            __builtin_memcpy(D + (row + (unsigned)(x0 + p * TILE_TX)) * 3u, &rgb, 12);
-            cnt[0] += 1u;
-        }
-    }
-    if (a.transfer_count != nullptr) block_count_add<1>(cnt, {a.transfer_count}, frame);
-}
-
-}  // namespace
-
-extern "C" int vstab_sharp_transfer_batch(vstab_ctx* ctx, const float* src, int clip_frames, int src_h, int src_w, int first, int n,
-                                          const float* matrices, const int32_t* cand_frame, int K, const float* ratio, float alpha,
-                                          int out_h, int out_w, int interp, int subpix, float* dst, const float* mask,
-                                          uint32_t* transfer_count)
-{
-    const char* who = "vstab_sharp_transfer_batch";
-    const float no_border[3] = {0.f, 0.f, 0.f};
-    if (int rc = check_common(who, ctx, src, n, src_h, src_w, matrices, out_h, out_w, interp, no_border, subpix, dst)) return rc;
-    VSTAB_REQUIRE(subpix == VSTAB_SUBPIX_Q5, "%s: VSTAB_SUBPIX_EXACT is not supported (the transfer samples as the blended fill "
-                  "does, on the 1/32-px coordinates of VSTAB_SUBPIX_Q5)", who);
-    VSTAB_REQUIRE(cand_frame != nullptr && ratio != nullptr, "%s: NULL pointer argument", who);
-    VSTAB_REQUIRE(K >= 1 && K <= 64, "%s: K=%d outside [1,64]", who, K);
-    VSTAB_REQUIRE(clip_frames > 0 && first >= 0 && first + n <= clip_frames, "%s: frames [%d, %d) outside a clip of %d frames", who,
-                  first, first + n, clip_frames);
-    VSTAB_REQUIRE((const void*)src != (const void*)dst, "%s: dst must not alias src (candidates read src while dst is written)", who);
-    VSTAB_REQUIRE(alpha >= 0.f && std::isfinite(alpha), "%s: alpha=%g is not a finite number >= 0", who, (double)alpha);
-    const size_t pairs = (size_t)n * K;
-    for (size_t i = 0; i < pairs; i++)
-        VSTAB_REQUIRE(ratio[i] >= 0.f && std::isfinite(ratio[i]), "%s: ratio[%zu]=%g is not a finite number >= 0", who, i, (double)ratio[i]);
-
-    // one staged block: candidate records [n * K], ratios [n * K], the list of live frames [n_live]
-    const size_t rec_bytes = pairs * sizeof(FillCand), ratio_bytes = pairs * sizeof(float);
-    std::vector<unsigned char> blob(rec_bytes + ratio_bytes + (size_t)n * sizeof(int));
-    FillCand* cd = reinterpret_cast<FillCand*>(blob.data());
-    if (int rc = fill_cand_records(who, matrices, cand_frame, pairs, clip_frames, cd)) return rc;
-    memcpy(blob.data() + rec_bytes, ratio, ratio_bytes);
-    int* live = reinterpret_cast<int*>(blob.data() + rec_bytes + ratio_bytes);
-    int n_live = 0;
-    for (int f = 0; f < n; f++) {
-        bool any = false;
-        for (int k = 0; k < K && !any; k++) any = cd[(size_t)f * K + k].frame >= 0 && ratio[(size_t)f * K + k] > 0.f;
-        if (any) live[n_live++] = f;
-    }
-
-    VSTAB_HIP(hipSetDevice(ctx->device));
-    KernelTimer timer(ctx, "sharp_transfer");
-    if (transfer_count) VSTAB_HIP(hipMemsetAsync(transfer_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
-    if (n_live == 0) return 0;                                     // no frame borrows anything: dst keeps every byte
-    SharpArgs a{};
-    a.src = src; a.dst = dst; a.mask = mask; a.transfer_count = transfer_count; a.alpha = alpha;
-    a.K = K; a.sh = src_h; a.sw = src_w; a.dh = out_h; a.dw = out_w;
-    set_block_width(out_h, out_w, &a.bw0, &a.bw0_pow2);
-    unsigned blocks = 0;
-    if (int rc = tile_grid(who, n_live, out_h, out_w, 32, 256, &a.tiles_x, &a.tiles_y, &blocks)) return rc;
-    void* dev = nullptr;
-    if (vstab_stage_params(ctx, blob.data(), rec_bytes + ratio_bytes + (size_t)n_live * sizeof(int), &dev)) return 1;
-    const FillCand* cands = static_cast<const FillCand*>(dev);
-    const float* ratios_dev = reinterpret_cast<const float*>(static_cast<const unsigned char*>(dev) + rec_bytes);
-    const int* live_dev = reinterpret_cast<const int*>(static_cast<const unsigned char*>(dev) + rec_bytes + ratio_bytes);
-    const dim3 grid(blocks), block(256);
-    if (interp == VSTAB_INTERP_BICUBIC) hipLaunchKernelGGL((sharp_transfer_kernel<VSTAB_INTERP_BICUBIC>), grid, block, 0, ctx->stream, a, cands, ratios_dev, live_dev);
-    else hipLaunchKernelGGL((sharp_transfer_kernel<VSTAB_INTERP_BILINEAR>), grid, block, 0, ctx->stream, a, cands, ratios_dev, live_dev);
     VSTAB_HIP(hipGetLastError());
     return 0;
 }

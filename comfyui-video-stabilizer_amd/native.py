@@ -978,23 +978,10 @@ class Context:
         cand_frame [n,K] i32 (-1: none), dst [n,h,w,3] / mask [n,h,w] f32 device and contiguous (see include/vstab.h for the
         rule).  -> (filled_from i8 [n,h,w] | None, fill_count i32 [n] | None, pad_count i32 [n] | None), device tensors."""
         torch = self.torch
-        src = self._as_device_frames(clip_frames)
-        total, sh, sw, ch = src.shape
-        if ch != 3:
-            raise VstabError(f"temporal_fill_batch expects 3-channel frames, got {ch}")
-        for name, t in (("dst", dst), ("mask", mask)):
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()):
-                raise VstabError(f"temporal_fill_batch: {name} must be a contiguous float32 tensor on {self.device}")
-        if dst.dim() != 4 or dst.shape[3] != 3 or mask.numel() * 3 != dst.numel():
-            raise VstabError(f"temporal_fill_batch: dst {tuple(dst.shape)} / mask {tuple(mask.shape)} do not match")
-        n, out_h, out_w = int(dst.shape[0]), int(dst.shape[1]), int(dst.shape[2])
-        cf = np.ascontiguousarray(cand_frame, dtype=np.int32)
-        if cf.ndim != 2 or cf.shape[0] != n:
-            raise VstabError(f"temporal_fill_batch: cand_frame {cf.shape} is not [n={n}, K]")
-        k = int(cf.shape[1])
-        m = np.ascontiguousarray(matrices, dtype=np.float32)
-        if m.size != n * k * 9:
-            raise VstabError(f"temporal_fill_batch: matrices {m.shape} are not [n={n}, K={k}, 3, 3]")
+        if mask is None:
+            raise VstabError(f"temporal_fill_batch: mask must be a contiguous float32 tensor on {self.device}")
+        src, (total, sh, sw), (n, out_h, out_w, k), m, cf, _ = self._neighbour_io(
+            "temporal_fill_batch", clip_frames, matrices, cand_frame, None, dst, mask, subpix, accepts_exact=True)
         filled_from = torch.empty((n, out_h, out_w), dtype=torch.int8, device=self.device) if want_filled_from else None
         fill_count = torch.empty((n,), dtype=torch.int32, device=self.device) if want_counts else None
         pad_count = torch.empty((n,), dtype=torch.int32, device=self.device) if want_counts else None
@@ -1007,15 +994,16 @@ class Context:
             _dev_ptr(pad_count) if pad_count is not None else None), "vstab_temporal_fill_batch")
         return filled_from, fill_count, pad_count
 
-    def _fill_blend_io(self, who, clip_frames, matrices, cand_frame, own_matrices, dst, mask, subpix):
-        """The arguments the two blended-fill entries and the sharpness transfer share, checked as temporal_fill_batch checks its
-        own (own_matrices None: the entry takes none)."""
+    def _neighbour_io(self, who, clip_frames, matrices, cand_frame, own_matrices, dst, mask, subpix, accepts_exact=False):
+        """The arguments the temporal fill, the two blended-fill entries and the sharpness transfer share (csrc/vstab_neighbour.hip),
+        checked in one place.  own_matrices None: the entry takes none; mask None: the entry's own affair; accepts_exact: the
+        entry (the plain fill) has the 'exact' sub-pixel mode besides 'q5'."""
         torch = self.torch
         src = self._as_device_frames(clip_frames)
         total, sh, sw, ch = src.shape
         if ch != 3:
             raise VstabError(f"{who} expects 3-channel frames, got {ch}")
-        if (subpix or DEFAULT_SUBPIX) != "q5":
+        if not accepts_exact and (subpix or DEFAULT_SUBPIX) != "q5":
             raise VstabError(f"{who}: sub-pixel mode {(subpix or DEFAULT_SUBPIX)!r} is not supported; the entry is 'q5' only")
         for name, t in (("dst", dst), ("mask", mask)):
             if t is None and name == "mask":
@@ -1044,7 +1032,7 @@ class Context:
         [first, first + n): clip_frames / matrices / cand_frame as temporal_fill_batch takes them, own_matrices [n,3,3] f32 (the
         frames' own forward matrices), dst [n,h,w,3] f32 device as the warp left it (read only).
         -> sums i64 [n,K,7] device tensor: count, own r g b, candidate r g b (see temporal_fill.gains_from_sums)."""
-        src, (total, sh, sw), (n, out_h, out_w, k), m, cf, own = self._fill_blend_io(
+        src, (total, sh, sw), (n, out_h, out_w, k), m, cf, own = self._neighbour_io(
             "fill_gain_sums", clip_frames, matrices, cand_frame, own_matrices, dst, None, subpix)
         sums = self.torch.empty((n, k, 7), dtype=self.torch.int64, device=self.device)
         self.use_torch_stream()
@@ -1061,7 +1049,7 @@ class Context:
         temporal_fill_batch.  'q5' only.
         -> (filled_from i8 [n,h,w] | None, fill_count, pad_count, blend_count i32 [n] | None), device tensors."""
         torch = self.torch
-        src, (total, sh, sw), (n, out_h, out_w, k), m, cf, own = self._fill_blend_io(
+        src, (total, sh, sw), (n, out_h, out_w, k), m, cf, own = self._neighbour_io(
             "temporal_fill_blend_batch", clip_frames, matrices, cand_frame, own_matrices, dst, mask, subpix)
         if mask is None:
             raise VstabError("temporal_fill_blend_batch: mask must be a contiguous float32 tensor")
@@ -1179,7 +1167,7 @@ class Context:
         matrices / cand_frame as temporal_fill_batch takes them, ratio [n,K] f32 (finite, >= 0), alpha a finite float >= 0,
         dst [n,h,w,3] f32 device and contiguous, mask [n,h,w] f32 device (read only) or None.  'q5' only.
         -> transfer_count i32 [n] device tensor | None."""
-        src, (total, sh, sw), (n, out_h, out_w, k), m, cf, _ = self._fill_blend_io(
+        src, (total, sh, sw), (n, out_h, out_w, k), m, cf, _ = self._neighbour_io(
             "sharp_transfer_batch", clip_frames, matrices, cand_frame, None, dst, mask, subpix)
         r = np.ascontiguousarray(ratio, dtype=np.float32)
         if r.shape != (n, k):

@@ -11,7 +11,7 @@ Two device passes (include/vstab.h states both rules):
   * `native.Context.frame_sharpness_batch` (csrc/vstab_sharp.hip) gives every SOURCE frame's gradient energy E as one exact
     integer; `ratios_from_energy` turns it into the relative sharpness E_j / E_i of candidate j against frame i, 0 where the
     neighbour is not clearly sharper;
-  * `native.Context.sharp_transfer_batch` (csrc/vstab_warp.hip: sharp_transfer_kernel) pulls every own pixel of frame i's
+  * `native.Context.sharp_transfer_batch` (csrc/vstab_neighbour.hip: sharp_transfer_kernel) pulls every own pixel of frame i's
     OUTPUT towards the candidates' samples, each weighted by ratio / (ratio + alpha * D) with D the L1 colour distance to
     the pixel, the pixel itself with weight 1.  Padded pixels are left to the fills, which run afterwards.
 

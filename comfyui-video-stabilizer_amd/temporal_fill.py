@@ -10,7 +10,7 @@ i.e. source frame j reaches the canvas of frame i through the FORWARD matrix
     H_{i,j} = F_i (A_{j-1} ... A_i)^-1   (j > i),    H_{i,j} = F_i A_{i-1} ... A_j   (j < i).
 
 `fill_candidates` forms these on the host (NumPy float64, one cast to float32); the kernel behind
-`native.Context.temporal_fill_batch` (csrc/vstab_warp.hip: temporal_fill_kernel) warps the first candidate whose every
+`native.Context.temporal_fill_batch` (csrc/vstab_neighbour.hip: temporal_fill_kernel) warps the first candidate whose every
 interpolation tap lies inside its frame into the pixel -- see include/vstab.h for the exact rule.  Off by default.
 
 That fill is a hard cut: a neighbour's raw value next to the frame's own content.  Two options, each off by default and each

@@ -625,7 +625,7 @@ int vstab_mesh_unwarp_batch(vstab_ctx* ctx, const float* src, int n, int src_h, 
  *   offsets  dev  [n, mh, mw, 2] f32 as for vstab_mesh_warp_batch (2 <= mw, mh <= 65; src_w, src_h >= 2), or NULL (mw, mh unused)
  *   extent   dev  [n] u32; preset by the call itself (a small kernel in front of the pass)
  * out_w < 2, out_h < 2 or (out_w-1) * (out_h-1) >= 2^31 is refused in front of any launch; the other sizes are checked as
- * vstab_warp_batch checks them.  Kernel (vstab_warp.hip, beside warp_pixel, which it calls with samplers that load nothing):
+ * vstab_warp_batch checks them.  Kernel (vstab_warp.hip; it calls warp_pixel of vstab_internal.h with samplers that load nothing):
  * the warp's 64 x 8 tile and XCD remap, no image memory read or written; per thread -> wave shuffle -> LDS -> one atomic
  * minimum per workgroup and frame, skipped when the workgroup saw no uncovered pixel.  Asynchronous on the context's stream;
  * timing kind "cover_extent". */

@@ -1,4 +1,4 @@
-"""GPU: vstab_fill_gain_sums and vstab_temporal_fill_blend_batch (csrc/vstab_warp.hip: fill_gain_sums_kernel,
+"""GPU: vstab_fill_gain_sums and vstab_temporal_fill_blend_batch (csrc/vstab_neighbour.hip: fill_gain_sums_kernel,
 temporal_fill_blend_kernel) and the `fill_feather` / `fill_exposure` keywords / the blended node.
 
 Every comparison of pixels, masks, indices, counts and sums is exact and over all pixels: against the NumPy restatement

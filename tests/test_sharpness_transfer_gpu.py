@@ -1,4 +1,4 @@
-"""GPU: vstab_frame_sharpness_batch (csrc/vstab_sharp.hip), vstab_sharp_transfer_batch (csrc/vstab_warp.hip:
+"""GPU: vstab_frame_sharpness_batch (csrc/vstab_sharp.hip), vstab_sharp_transfer_batch (csrc/vstab_neighbour.hip:
 sharp_transfer_kernel) and the `sharpness_transfer` keyword / the Sharpness Transfer node.
 
 Every comparison of energies, pixels and counts is exact and over all pixels, against the NumPy restatement

@@ -1,4 +1,4 @@
-"""GPU: vstab_temporal_fill_batch (csrc/vstab_warp.hip: temporal_fill_kernel) and the `temporal_fill` keyword / node.
+"""GPU: vstab_temporal_fill_batch (csrc/vstab_neighbour.hip: temporal_fill_kernel) and the `temporal_fill` keyword / node.
 
 Every comparison of pixels, masks, indices and counts is bit-exact and over all pixels: against the NumPy restatement
 (tests/temporal_fill_restatement.py, whose validity rule is refereed on the CPU in tests/test_temporal_fill_cpu.py),

@@ -27,7 +27,7 @@ ap.add_argument("--frames", type=int, default=256)
 ap.add_argument("--radius", type=int, default=8)
 ap.add_argument("--parent", default=None, help="a built checkout of the parent commit, for the bench alternation")
 ap.add_argument("--bench-rounds", type=int, default=3)
-ap.add_argument("--resources", default=None, help="JSON written by --resources-only (default: compile csrc/vstab_warp.hip now)")
+ap.add_argument("--resources", default=None, help="JSON written by --resources-only (default: compile csrc/vstab_neighbour.hip now)")
 ap.add_argument("--resources-only", action="store_true")
 ap.add_argument("--out", default=None, help="where to write the profile (default: the next free profiles/rNN_fill_blend.md)")
 args = ap.parse_args()
@@ -35,13 +35,13 @@ args = ap.parse_args()
 
 def resource_report():
     """{kernel instance: {vgprs, sgprs, scratch, occupancy, lds}} of the fill kernels, from hipcc's kernel-resource-usage
-    remarks on csrc/vstab_warp.hip with the Makefile's flags."""
+    remarks on csrc/vstab_neighbour.hip with the Makefile's flags."""
     csrc = ROOT / "comfyui-video-stabilizer_amd" / "csrc"
     flags = re.search(r"^CXXFLAGS = (.*?)\n(?!\s)", (csrc / "Makefile").read_text(), flags=re.S | re.M).group(1)
     flags = flags.replace("\\\n", " ").replace("$(ARCH)", "gfx950").replace("$(EXTRA)", "").split()
     with tempfile.TemporaryDirectory() as tmp:
         out = subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), *flags, "-Rpass-analysis=kernel-resource-usage", "-c",
-                              "vstab_warp.hip", "-o", str(Path(tmp) / "warp.o")], cwd=str(csrc), capture_output=True, text=True)
+                              "vstab_neighbour.hip", "-o", str(Path(tmp) / "neighbour.o")], cwd=str(csrc), capture_output=True, text=True)
     if out.returncode != 0:
         raise SystemExit(f"hipcc failed:\n{out.stderr[-3000:]}")
     table, name = {}, None

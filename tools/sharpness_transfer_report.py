@@ -49,7 +49,7 @@ def resource_report():
     table = {}
     keys = {"VGPRs": "vgprs", "TotalSGPRs": "sgprs", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy",
             "LDS Size [bytes/block]": "lds"}
-    for source in ("vstab_sharp.hip", "vstab_warp.hip"):
+    for source in ("vstab_sharp.hip", "vstab_neighbour.hip"):
         with tempfile.TemporaryDirectory() as tmp:
             out = subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), *flags, "-Rpass-analysis=kernel-resource-usage", "-c",
                                   source, "-o", str(Path(tmp) / "out.o")], cwd=str(csrc), capture_output=True, text=True)
