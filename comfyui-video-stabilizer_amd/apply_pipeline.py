@@ -13,6 +13,7 @@ from typing import Any, Callable, Dict, List, Optional, Tuple
 import numpy as np
 
 from . import host_math as hm
+from . import mask_handoff as mask_handoff_mod
 from . import mesh_warp as mesh_warp_mod
 from . import spatial_fill as spatial_fill_mod
 from . import stability as stability_mod
@@ -305,6 +306,10 @@ def apply_motion(
     mesh: bool = False,
     spatial_fill: bool = False,
     stability_report: bool = False,
+    mask_grow=None,
+    mask_feather=None,
+    mask_hold=None,
+    mask_tapered=None,
 ) -> MotionApplyResult:
     """Signature of the reference's apply_motion (motion_apply.py:297-307) plus GPU-context extras.
     mesh (beyond the reference, False by default): True replays the per-vertex offsets a mesh-warped Flow run recorded
@@ -320,7 +325,14 @@ def apply_motion(
     stability_report (beyond the reference, False by default): True adds meta["motion_apply"]["stability"], the inter-frame
     transformation fidelity (stability.py; include/vstab.h states the rule) of the frames as given and of the returned frames
     under the returned mask (none under `crop` framing), behind the spatial fill, and their difference.  Frames, masks and
-    the rest of the meta are unchanged.  Not with motion_blur > 0, whose masks are fractions."""
+    the rest of the meta are unchanged.  Not with motion_blur > 0, whose masks are fractions.
+    mask_grow, mask_feather, mask_hold, mask_tapered (beyond the reference, None by default): the hand-off of the returned mask
+    to a generative outpainter, as Flow's keywords of the same names (mask_handoff.py; include/vstab.h states the rules): hold
+    over neighbouring frames, GrowMask's dilation, an outward feather, as the last pass, behind the spatial fill and the
+    stability report.  Only the returned mask changes; meta["motion_apply"]["mask_handoff"] describes it.  Allowed with
+    motion_blur > 0: fractional masks are what a grey dilation is for.  `crop` framing has no mask: nothing is launched and
+    no block is added.  All None: the behaviour and meta without it, byte for byte."""
+    handoff = mask_handoff_mod.check_request(mask_grow, mask_feather, mask_hold, mask_tapered)
     spatial_fill = spatial_fill_mod.check_request(spatial_fill)
     stability_report = stability_mod.check_request(stability_report)
     if stability_report and float(np.clip(motion_blur, 0.0, 1.0)) > 0.0:   # before any GPU use
@@ -391,6 +403,8 @@ def apply_motion(
     if stability_report:
         result_meta["motion_apply"]["stability"] = stability_mod.report_on_device(
             ctx, device_frames, frames, None if result_meta["motion_apply"]["framing_mode"] == "crop" else masks)
+    if handoff is not None and result_meta["motion_apply"]["framing_mode"] != "crop":
+        masks, result_meta["motion_apply"]["mask_handoff"] = mask_handoff_mod.handoff_on_device(ctx, masks.contiguous(), handoff)
     check_interrupt()
     if keep_on_device:
         return MotionApplyResult(frames, masks.unsqueeze(-1), result_meta)

@@ -26,6 +26,7 @@ from . import host_math as hm
 from . import mesh_warp as mesh_warp_mod
 from . import native
 from . import scene_cuts as scene_cuts_mod
+from . import mask_handoff as mask_handoff_mod
 from . import sharpness_transfer as sharpness_transfer_mod
 from . import spatial_fill as spatial_fill_mod
 from . import stability as stability_mod
@@ -629,6 +630,17 @@ def _stability_report(ctx, device_frames, dst, mask, plan, meta, enabled: bool, 
     meta["stability"] = stability_mod.report_on_device(ctx, device_frames, dst, None if plan.framing_mode == "crop" else mask, cuts)
 
 
+def _mask_handoff(ctx, mask, plan, meta, request, segments=None):
+    """-> the mask to return: held, grown and feathered for an outpainter (mask_handoff.py), with meta["mask_handoff"] added --
+    or `mask` itself where nothing was asked for.  request: mask_handoff.check_request's answer.  It runs LAST, behind the
+    sharpness transfer, the fills and the stability report, which all see the true mask; `padding_fraction_*` and every other
+    block keep describing the warp.  `crop` framing has no mask: nothing to do."""
+    if request is None or plan.framing_mode == "crop":
+        return mask
+    mask, meta["mask_handoff"] = mask_handoff_mod.handoff_on_device(ctx, mask, request, segments)
+    return mask
+
+
 # ---- estimation mask (beyond the reference; the rule is in include/vstab.h) --------------------------------------------
 MASK_MARGIN_MAX = 64
 _MASK_LIMITS = {
@@ -719,7 +731,7 @@ def _dynamic_zoom(ctx, zoom, plan, offsets, segments):
 def _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode, camera_lock,
                                 strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested, pbar, progress_total,
                                 keep_on_device, temporal_fill=0, blocked=None, mask_info=None, spatial_fill=False,
-                                stability_report=False, fill_blend=(None, False), sharpness=None):
+                                stability_report=False, fill_blend=(None, False), sharpness=None, handoff=None):
     """F2-F14 with the plan formed on the device (see above).  Returns None when F0 found 0..255 float data: the
     speculative run used the unscaled frames and is discarded; the caller takes the regular path on the rescaled clip."""
     size = (context.width, context.height)
@@ -768,6 +780,7 @@ def _stabilize_with_device_plan(ctx, context, device_frames, working_size, total
     _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill, fill_blend)   # and so is the fill
     _spatial_fill(ctx, dst, mask, plan, meta, spatial_fill)
     _stability_report(ctx, device_frames, dst, mask, plan, meta, stability_report)
+    mask = _mask_handoff(ctx, mask, plan, meta, handoff)
     check_interrupt()
     if keep_on_device:
         return hm.StabilizationResult(dst, mask.unsqueeze(-1), meta, verdict)
@@ -805,6 +818,10 @@ def _stabilize_frames(
     fill_exposure: bool = False,
     sharpness_transfer=None,
     sharpness_alpha=None,
+    mask_grow=None,
+    mask_feather=None,
+    mask_hold=None,
+    mask_tapered=None,
 ) -> hm.StabilizationResult:
     """Positional signature of the reference (flow.py:213-223); keyword-only extras select the GPU
     context, keep outputs resident in HBM (multi-GPU sharding lives in distributed.py) or switch the
@@ -874,7 +891,17 @@ def _stabilize_frames(
     pixel itself with weight 1.  Frames with no sharper neighbour, the mask and every other meta key are unchanged, bit for
     bit; meta["sharpness_transfer"] lists every frame's sharpness and what was transferred.  Not with mesh_warp, estimator
     "subject" or sub-pixel mode 'exact'.  0 / None / False: the behaviour and meta without it, byte for byte, and nothing new
-    is launched.  Bypass paths ignore it."""
+    is launched.  Bypass paths ignore it.
+    mask_grow, mask_feather, mask_hold, mask_tapered (beyond the reference, None by default): the hand-off of `padding_mask` to
+    a generative outpainter (mask_handoff.py; include/vstab.h states the rules).  mask_hold = T in 0..16 takes the maximum of
+    the mask over the frames within T of each frame, inside its shot under scene_cuts, so the repaint region stands still;
+    mask_grow = g in -64..64 is ComfyUI's GrowMask (negative erodes), over the L1 ball (mask_tapered None / True: GrowMask's
+    tapered corners) or the square one (False); mask_feather = f in 0..64 adds an outward linear ramp of f pixels.  Any of the
+    first three switches the pass on, the others read as 0.  It runs last and replaces only the returned mask: the fills,
+    the sharpness transfer and the stability report see the true mask, frames and every other meta key are unchanged, and
+    meta["mask_handoff"] reports the request and the fraction of pixels above 0.5.  All None: the behaviour and meta without
+    it, byte for byte, and nothing new is launched.  `crop` framing has no mask; bypass paths ignore them."""
+    handoff = mask_handoff_mod.check_request(mask_grow, mask_feather, mask_hold, mask_tapered)
     zoom = dynamic_zoom_mod.check_request(dynamic_zoom, zoom_limit)
     if zoom is not None:
         dynamic_zoom_mod.check_pipeline(framing_mode)
@@ -975,7 +1002,7 @@ def _stabilize_frames(
         done = _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode,
                                            camera_lock, strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested,
                                            pbar, progress_total, keep_on_device, temporal_fill, blocked, mask_info, spatial_fill,
-                                           stability_report, fill_blend, sharpness)
+                                           stability_report, fill_blend, sharpness, handoff)
         if done is not None:
             return done
         device_frames = context.device_batch(ctx)   # F0 rescaled the clip: everything is redone on the rescaled frames below
@@ -1050,6 +1077,7 @@ def _stabilize_frames(
     _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill, fill_blend)
     _spatial_fill(ctx, dst, mask, plan, meta, spatial_fill)
     _stability_report(ctx, device_frames, dst, mask, plan, meta, stability_report, segments)
+    mask = _mask_handoff(ctx, mask, plan, meta, handoff, segments)
     check_interrupt()
     verdict = {"used": False, "mismatched_frames": 0}
     if keep_on_device:

@@ -20,6 +20,8 @@ LIB_PATH = Path(os.environ["VSTAB_LIB"]).resolve() if os.environ.get("VSTAB_LIB"
 INTERP = {"bilinear": 0, "bicubic": 1}
 SUBPIX = {"q5": 0, "exact": 1}
 MODES = {"translation": 0, "similarity": 1, "perspective": 2}
+GROW_TAPERED, GROW_SQUARE = 0, 1                               # VSTAB_GROW_* of include/vstab.h
+MASK_HOLD_MAX, MASK_GROW_MAX, MASK_FEATHER_MAX = 16, 64, 64    # VSTAB_MASK_*_MAX
 MODE_NAMES = ("translation", "similarity", "perspective")
 MESH_MAX_VERTS = 65      # vertices per axis of a mesh warp (64 cells; include/vstab.h)
 MESH_MIN_SAMPLES = 4     # VSTAB_MESH_MIN_SAMPLES
@@ -215,6 +217,9 @@ _SIGNATURES = {
     "vstab_sharp_transfer_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                   C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vstab_mask_hold_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vstab_mask_grow_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vstab_gftt_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p,
                   C.c_void_p]),
@@ -1179,6 +1184,60 @@ class Context:
             out_h, out_w, INTERP[interp], SUBPIX["q5"], _dev_ptr(dst), _dev_ptr(mask) if mask is not None else None,
             _dev_ptr(counts) if counts is not None else None), "vstab_sharp_transfer_batch")
         return counts
+
+    # ------------------------------------------------------------------ mask hand-off
+    def _handoff_mask(self, who, mask):
+        torch = self.torch
+        if not (isinstance(mask, torch.Tensor) and mask.dtype == torch.float32 and mask.device == self.device and mask.is_contiguous()):
+            raise ValueError(f"{who}: mask must be a contiguous float32 tensor on {self.device}")
+        if mask.dim() != 3 or min(mask.shape) < 1:
+            raise ValueError(f"{who}: mask of shape {tuple(mask.shape)} is not [n,h,w] with n, h, w >= 1")
+        return int(mask.shape[0]), int(mask.shape[1]), int(mask.shape[2])
+
+    def mask_hold_batch(self, mask, hold, shots=None):
+        """The maximum of every pixel of mask [n,h,w] (f32, device, contiguous) over the frames within `hold` (an int in 0..16)
+        of its own that belong to the same shot (include/vstab.h states the rule; a NaN reads as 1.0, hold = 0 returns the
+        input's bits).  shots: None (one shot) or a non-decreasing integer sequence [n].  -> a new device tensor [n,h,w]."""
+        n, h, w = self._handoff_mask("mask_hold_batch", mask)
+        if isinstance(hold, (bool, np.bool_)) or not isinstance(hold, (int, np.integer)) or not 0 <= int(hold) <= MASK_HOLD_MAX:
+            raise ValueError(f"mask_hold_batch: hold={hold!r} is not an integer in 0..{MASK_HOLD_MAX}")
+        shot = None
+        if shots is not None:
+            shot = np.ascontiguousarray(shots, dtype=np.int32).reshape(-1)
+            if shot.shape[0] != n or (np.diff(shot.astype(np.int64)) < 0).any():
+                raise ValueError(f"mask_hold_batch: shots of shape {np.shape(shots)} is not a non-decreasing sequence of n={n} integers")
+        out = self.torch.empty_like(mask)
+        self.use_torch_stream()
+        _check(self.lib.vstab_mask_hold_batch(self.handle, _dev_ptr(mask), n, h, w, int(hold), shot.ctypes.data if shot is not None else None,
+                                              _dev_ptr(out)), "vstab_mask_hold_batch")
+        return out
+
+    def mask_grow_batch(self, mask, grow, tapered=True, feather=0, want_count=False, out=None):
+        """ComfyUI's GrowMask on mask [n,h,w] (f32, device, contiguous) and an outward feather behind it (include/vstab.h states
+        both rules): grow an int in -64..64 (negative erodes), tapered True = the L1 ball (GrowMask's tapered_corners), False
+        = the square one, feather an int in 0..64.  `out`: a tensor like mask to write into (it must not share memory with
+        mask), None for a new one.  -> out, or (out, count i32 [n] of pixels > 0.5, a device tensor) with want_count."""
+        n, h, w = self._handoff_mask("mask_grow_batch", mask)
+        if isinstance(grow, (bool, np.bool_)) or not isinstance(grow, (int, np.integer)) or not -MASK_GROW_MAX <= int(grow) <= MASK_GROW_MAX:
+            raise ValueError(f"mask_grow_batch: grow={grow!r} is not an integer in -{MASK_GROW_MAX}..{MASK_GROW_MAX}")
+        if isinstance(feather, (bool, np.bool_)) or not isinstance(feather, (int, np.integer)) or not 0 <= int(feather) <= MASK_FEATHER_MAX:
+            raise ValueError(f"mask_grow_batch: feather={feather!r} is not an integer in 0..{MASK_FEATHER_MAX}")
+        if not isinstance(tapered, (bool, np.bool_)):
+            raise ValueError(f"mask_grow_batch: tapered={tapered!r} is not a bool")
+        torch = self.torch
+        if out is None:
+            out = torch.empty_like(mask)
+        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == self.device and out.is_contiguous()
+                  and tuple(out.shape) == tuple(mask.shape)):
+            raise ValueError(f"mask_grow_batch: out must be a contiguous float32 tensor of shape {tuple(mask.shape)} on {self.device}")
+        elif out.data_ptr() < mask.data_ptr() + mask.numel() * 4 and mask.data_ptr() < out.data_ptr() + out.numel() * 4:
+            raise ValueError("mask_grow_batch: out shares memory with mask: a tile's halo would read pixels already written")
+        count = torch.empty((n,), dtype=torch.int32, device=self.device) if want_count else None
+        self.use_torch_stream()
+        _check(self.lib.vstab_mask_grow_batch(self.handle, _dev_ptr(mask), n, h, w, int(grow), GROW_TAPERED if tapered else GROW_SQUARE,
+                                              int(feather), _dev_ptr(out), _dev_ptr(count) if count is not None else None),
+               "vstab_mask_grow_batch")
+        return (out, count) if want_count else out
 
     # ------------------------------------------------------------------ Classic estimator (sparse features + LK)
     def gftt_batch(self, gray, max_corners=400, quality=0.01, min_distance=7.0, block_size=21):

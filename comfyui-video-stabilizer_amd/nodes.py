@@ -941,6 +941,59 @@ NODE_CLASSES = [VideoStabilizerClassic, VideoStabilizerFlow, VideoStabilizerMoti
                 VideoStabilizerShakeGeneratorManual, VideoStabilizerInverse]
 
 
+class VideoStabilizerMaskGrow(io.ComfyNode):
+    """ComfyUI's GrowMask on the GPU, with an outward feather and a temporal hold (mask_handoff.py): the node between a
+    stabilizer's padding mask and an outpainter.  `mask`, `expand` and `tapered_corners` carry GrowMask's socket names and
+    defaults, so it takes GrowMask's place in the reference's two workflows.  Not one of the reference's nodes: it is listed
+    by an extension but kept out of NODE_CLASSES."""
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        schema = io.Schema(
+            node_id="video_stabilizer_mask_grow",
+            display_name="Video Stabilizer Mask Grow",
+            category="Video/Stabilization",
+            description=("Grows (or shrinks) a padding mask as GrowMask does, on the GPU, optionally holds it over neighbouring "
+                         "frames so the repaint region stands still, and feathers its edge outwards."),
+        )
+        schema.inputs = [
+            io.Mask.Input("mask", display_name="Mask", tooltip="[N,H,W] or [H,W]."),
+            io.Int.Input("expand", default=5, min=-64, max=64, step=1, display_name="Expand",
+                         tooltip="Pixels of growth; negative shrinks."),
+            io.Boolean.Input("tapered_corners", default=True, display_name="Tapered Corners",
+                             tooltip="True grows over a diamond (GrowMask's cross footprint), False over a square."),
+            io.Int.Input("feather", default=0, min=0, max=64, step=1, display_name="Feather",
+                         tooltip="Pixels of linear ramp added outside the grown mask."),
+            io.Int.Input("hold", default=0, min=0, max=16, step=1, display_name="Hold",
+                         tooltip="Frames before and after over which the mask is held (maximum), before it is grown."),
+        ]
+        schema.outputs = [io.Mask.Output("mask", display_name="Mask")]
+        return schema
+
+    @classmethod
+    def execute(cls, mask: Any, expand: int = 5, tapered_corners: bool = True, feather: int = 0, hold: int = 0) -> io.NodeOutput:
+        from . import mask_handoff, native
+
+        # every check comes before any GPU work
+        request = mask_handoff.check_request(expand, feather, hold, tapered_corners)
+        if not (hasattr(mask, "dtype") and hasattr(mask, "shape")):
+            raise ValueError(f"mask grow: socket 'mask' must be a floating-point MASK tensor, got {type(mask).__name__}")
+        if "float" not in str(mask.dtype):
+            raise ValueError(f"mask grow: socket 'mask' must be a floating-point MASK, got {mask.dtype}")
+        shape = tuple(int(v) for v in mask.shape)
+        if len(shape) not in (2, 3) or min(shape) < 1:
+            raise ValueError(f"mask grow: socket 'mask' of shape {tuple(mask.shape)} is not [N,H,W] or [H,W]")
+        ctx = native.default_context()
+        torch = ctx.torch
+        m = mask if isinstance(mask, torch.Tensor) else torch.from_numpy(np.asarray(mask))
+        m = m.to(device=ctx.device, dtype=torch.float32).reshape(shape[-3:] if len(shape) == 3 else (1,) + shape).contiguous()
+        out, _ = mask_handoff.handoff_on_device(ctx, m, request)
+        out = out.reshape(shape)
+        # a feathered mask is neither 0 / 1 nor a motion-blur level: levels = 1 lets a 0 / 1 result cross as bytes, and the
+        # download itself takes the float path for a mask with any other value -- the bits arrive either way
+        return io.NodeOutput(_mask_out(out, 1))
+
+
 class VideoStabilizerAmdExtension(ComfyExtension):
     async def get_node_list(self) -> list:
         return list(NODE_CLASSES) + [VideoStabilizerTemporalFill]   # the six reference nodes + the temporal fill
@@ -1048,3 +1101,11 @@ class VideoStabilizerAmdSharpnessExtension(VideoStabilizerAmdFillBlendExtension)
 
     async def get_node_list(self) -> list:
         return await super().get_node_list() + [VideoStabilizerSharpnessTransfer]
+
+
+class VideoStabilizerAmdHandoffExtension(VideoStabilizerAmdSharpnessExtension):
+    """The sharpness extension's eighteen nodes plus Video Stabilizer Mask Grow.  A class of its own for the reason the ten
+    before it are: comfy_entrypoint() keeps handing out its own."""
+
+    async def get_node_list(self) -> list:
+        return await super().get_node_list() + [VideoStabilizerMaskGrow]

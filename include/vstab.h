@@ -754,6 +754,57 @@ int vstab_sharp_transfer_batch(vstab_ctx* ctx, const float* src, int clip_frames
                                int out_h, int out_w, int interp, int subpix, float* dst, const float* mask,
                                uint32_t* transfer_count);
 
+/* ---- mask hand-off: hold, grow and feather the padding mask for a generative outpainter (beyond the reference, off by default) ----
+ * The reference's workflows put ComfyUI's GrowMask (scipy grey_dilation, 3 x 3, once per pixel of growth, on one CPU thread)
+ * between the stabilizer and the outpainter, and users chain a feather behind it by hand.  Both, and a temporal hold that
+ * keeps the repaint region from jittering, are maxima; a maximum is the same in any order, so what these two entries return
+ * equals a NumPy restatement (tests/mask_handoff_restatement.py) in bits whatever decomposition the kernels use.
+ *
+ * m is a float32 mask [n, h, w].  A NaN reads as 1.0f: an unknown pixel is to be repainted (the spatial fill's convention).
+ * Every other value, infinities included, reads as itself.  Values are ordered as IEEE 754 orders them, -0.0f below +0.0f
+ * (the total order of the sign-magnitude bits), so that a maximum never has to choose between equals with different bits.
+ * Nothing crosses from one frame into another except in the hold.
+ *
+ * vstab_mask_hold_batch -- 1. Hold, T = hold in 0..VSTAB_MASK_HOLD_MAX:
+ *   - held_i(p) = max of m_j(p) over |j - i| <= T, 0 <= j < n, and shot[j] == shot[i].
+ *   - shot  host [n] i32, non-decreasing (refused otherwise), or NULL: one shot.
+ *   - T = 0 returns the input's bits, its NaNs included; T > 0 reads a NaN as 1.0f like every other maximum here.
+ *   mask dev [n, h, w] f32, read only;  out dev [n, h, w] f32, must not overlap mask.
+ * Kernel (vstab_handoff.hip): streaming, one 16-byte load per lane and window frame where h * w is a multiple of 4 and both
+ * pointers are 16-byte aligned, one float per lane otherwise; the windows come down as a host-formed table.  A pixel's
+ * 2T + 1 reads are whole-frame re-reads.  T = 0 is one device copy.  Timing kind "mask_hold".
+ *
+ * vstab_mask_grow_batch -- 2. Grow, g = grow in -VSTAB_MASK_GROW_MAX..VSTAB_MASK_GROW_MAX, footprint VSTAB_GROW_TAPERED (the
+ * L1 ball |dx| + |dy| <= |g|) or VSTAB_GROW_SQUARE (the L-infinity ball max(|dx|, |dy|) <= |g|):
+ *   - G(p) = max (g > 0) or min (g < 0) of the mask over the ball around p, clipped to the frame.  g = 0 is the identity
+ *     (G holds the input's bits, a NaN included).
+ *   - This is ComfyUI's GrowMask: |g| iterations of scipy's 3 x 3 grey_dilation / grey_erosion (cross or full footprint,
+ *     mode="reflect") equal the clipped-ball extremum, because a reflected neighbour is an in-frame pixel no farther away.
+ * 3. Feather, f = feather in 0..VSTAB_MASK_FEATHER_MAX, outward, in the norm of the chosen footprint.  f = 0: out = G, float
+ * for float.  f > 0, with dist the L1 or L-infinity distance:
+ *   - Q(p) = max(0, max over q in the clipped ball of radius f of [ q16(G(q)) - dist(p, q) * step ])
+ *   - step = 65536 / (f + 1) in integer division;  q16(v) = v > 0 ? (v < 1 ? (uint32)(v * 65536.0f) : 65536) : 0, the blended
+ *     fill's quantiser, with a NaN of G read as 1.0f first (so q16 = 65536);  out = (float)Q / 65536, which is exact.
+ *   For a 0 / 1 mask this is the ramp 1 - d * step / 65536 over the chamfer distance d <= f, and 0 beyond.
+ * 4. Count.  count_out[k] = the number of pixels of out frame k that are > 0.5f.
+ *   mask dev [n, h, w] f32, read only;  out dev [n, h, w] f32, must not overlap mask;  count_out dev [n] u32 or NULL, zeroed
+ *   by the call.  h * w < 2^31.
+ * Kernel (vstab_handoff.hip): balls and cones of one norm compose, so the |g| + f one-pixel steps are cut into passes of at
+ * most 16.  In a pass a workgroup of 256 threads stages a 64 x 32 core tile and a halo of the pass's steps in LDS as integer
+ * order keys, rows packed densely, relaxes it step by step over a shrinking region between two LDS buffers (flat steps
+ * first, then the quantised integer ones with the decrement; a thread keeps, per cell, the number of steps the cell takes
+ * part in), keeps the cells outside the frame at the identity, and stores the core once; the last pass counts (one atomic
+ * add per workgroup and frame).  Passes alternate between out and a workspace of the context, a chunk of frames (at most
+ * 1 GiB) at a time.  Asynchronous on the context's stream; timing kind "mask_grow". */
+#define VSTAB_GROW_TAPERED 0
+#define VSTAB_GROW_SQUARE 1
+#define VSTAB_MASK_HOLD_MAX 16
+#define VSTAB_MASK_GROW_MAX 64
+#define VSTAB_MASK_FEATHER_MAX 64
+int vstab_mask_hold_batch(vstab_ctx* ctx, const float* mask, int n, int h, int w, int hold, const int32_t* shot, float* out);
+int vstab_mask_grow_batch(vstab_ctx* ctx, const float* mask, int n, int h, int w, int grow, int footprint, int feather,
+                          float* out, uint32_t* count_out);
+
 /* ---- F6 / F9 host helper: element-wise libm over fp64 arrays (host pointers, no GPU involved) ----
  * nodes/stabilizer_utils.py:300-358 (_matrix_to_params / _params_to_matrix) call math.sqrt/atan2/log and
  * math.exp/cos/sin per frame; this runs the same libm functions over a whole clip in one call.
