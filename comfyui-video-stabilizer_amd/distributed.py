@@ -216,7 +216,7 @@ def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, t
                       strength: float, smooth: float, keep_fov: float, padding_rgb, frame_rate: float, group=None,
                       estimator: str = "flow", stats: Optional[Dict[str, float]] = None, want_meta: bool = True,
                       check_value_range: bool = True, temporal_fill: int = 0, estimation_mask=None, scene_cuts=None,
-                      mesh_warp=None, dynamic_zoom=None, sharpness_transfer=None):
+                      mesh_warp=None, dynamic_zoom=None, sharpness_transfer=None, rolling_shutter=None):
     """Sharded equivalent of `_stabilize_frames` (flow.py:213-640).
 
     local_frames: device tensor [n_local (+1 halo for rank > 0 that owns frames), H, W, 3] float32 -- this rank's frames
@@ -253,6 +253,12 @@ def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, t
         # which the sharded path does not do; every rank raises alike, before any collective
         raise ValueError("stabilize_sharded does not support dynamic_zoom: dynamic zoom is not sharded (the envelope needs "
                          "every rank's extents); run the single-GPU pipeline for a dynamically zoomed stabilization")
+    if rolling_shutter is not None:
+        # a frame's velocity needs the transitions on both of its sides and the readout estimate every rank's row residuals,
+        # neither of which the sharded path gathers before the warp; every rank raises alike, before any collective
+        raise ValueError(f"stabilize_sharded does not support rolling_shutter={rolling_shutter!r}: the rolling-shutter correction "
+                         "is not sharded (velocities and the readout estimate need every rank's transitions); run the "
+                         "single-GPU pipeline for it")
     if sharpness_transfer is not None and sharpness_transfer is not False and sharpness_transfer != 0:
         # a rank would need the sharpness of, and the source frames, up to `sharpness_transfer` frames before and after its
         # shard (a halo it does not hold); every rank raises alike, before any collective

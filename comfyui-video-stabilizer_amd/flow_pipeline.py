@@ -27,6 +27,7 @@ from . import mesh_warp as mesh_warp_mod
 from . import native
 from . import scene_cuts as scene_cuts_mod
 from . import mask_handoff as mask_handoff_mod
+from . import rolling_shutter as rolling_shutter_mod
 from . import sharpness_transfer as sharpness_transfer_mod
 from . import spatial_fill as spatial_fill_mod
 from . import stability as stability_mod
@@ -718,6 +719,25 @@ def _mesh_offsets(ctx, mesh, plan, grid, blocked, working_size, size, segments, 
     return offsets, mesh_warp_mod.meta_block(mesh, max_shift, residual, count, offsets, native.MESH_MIN_SAMPLES)
 
 
+# ---- rolling shutter (beyond the reference; rolling_shutter.py, the rules are in include/vstab.h) -----------------------
+def _rolling_shutter(ctx, rolling, plan, grid_out, blocked, working_size, size, segments):
+    """-> (the warp's per-frame velocities f64 [N,6] in full-resolution px per frame, the readout, meta["rolling_shutter"]).
+    A given readout launches nothing here.  "auto": one launch of the row-residual kernel over the grid the estimator made,
+    against the working-resolution transitions the plan itself used, then the least-squares readout on the host."""
+    em = plan.estimated_motion
+    velocity = rolling_shutter_mod.velocities(em["matrices"], em["confidences"], segments)
+    estimate = None
+    if rolling == rolling_shutter_mod.AUTO:
+        work = working_size if working_size is not None else size
+        residual, count = ctx.row_residual_batch(grid_out[0], SAMPLE_STEP, work, em["work_matrices"], blocked=blocked)
+        estimate = rolling_shutter_mod.estimate_readout(residual.cpu().numpy(), count.cpu().numpy(), em["work_matrices"],
+                                                        em["confidences"], em["modes"], segments, work, SAMPLE_STEP)
+        readout, source = estimate["readout"], estimate["source"]
+    else:
+        readout, source = float(rolling), "given"
+    return velocity, readout, rolling_shutter_mod.meta_block(readout, source, estimate, velocity, size)
+
+
 # ---- dynamic zoom (beyond the reference; dynamic_zoom.py, the rule is in include/vstab.h) -------------------------------
 def _dynamic_zoom(ctx, zoom, plan, offsets, segments):
     """-> (the plan with its final matrices zoomed, meta["dynamic_zoom"] still without the warp's counts).  One launch of the
@@ -822,6 +842,7 @@ def _stabilize_frames(
     mask_feather=None,
     mask_hold=None,
     mask_tapered=None,
+    rolling_shutter=None,
 ) -> hm.StabilizationResult:
     """Positional signature of the reference (flow.py:213-223); keyword-only extras select the GPU
     context, keep outputs resident in HBM (multi-GPU sharding lives in distributed.py) or switch the
@@ -900,7 +921,17 @@ def _stabilize_frames(
     first three switches the pass on, the others read as 0.  It runs last and replaces only the returned mask: the fills,
     the sharpness transfer and the stability report see the true mask, frames and every other meta key are unchanged, and
     meta["mask_handoff"] reports the request and the fraction of pixels above 0.5.  All None: the behaviour and meta without
-    it, byte for byte, and nothing new is launched.  `crop` framing has no mask; bypass paths ignore them."""
+    it, byte for byte, and nothing new is launched.  `crop` framing has no mask; bypass paths ignore them.
+    rolling_shutter (beyond the reference, None by default): the readout time of the sensor as a fraction of the frame interval,
+    a finite number in [-1, 1] (negative: read out bottom to top), or "auto" to estimate it.  A sensor read out row by row
+    shears and bends every frame with the camera's velocity; the final warp then samples every source row where that readout
+    showed it (rolling_shutter.py; include/vstab.h states both rules): the per-frame image velocity comes from the plan's own
+    full-resolution transitions, and "auto" fits the one number to the per-row medians of the global fits' residuals over the
+    flow grid (DIS / TV-L1 only), reporting "not_observable" and correcting nothing on a clip without acceleration.  For
+    translation / similarity under crop_and_pad / expand, without mesh_warp, temporal_fill, sharpness_transfer, dynamic_zoom or
+    estimator "subject"; everything behind the final warp follows unchanged.  meta["rolling_shutter"] reports the readout, the
+    skew it amounts to and every frame's velocity.  None / 0: the behaviour and meta without it, byte for byte, and nothing new
+    is launched.  Bypass paths ignore it."""
     handoff = mask_handoff_mod.check_request(mask_grow, mask_feather, mask_hold, mask_tapered)
     zoom = dynamic_zoom_mod.check_request(dynamic_zoom, zoom_limit)
     if zoom is not None:
@@ -928,6 +959,9 @@ def _stabilize_frames(
         mesh_warp_mod.check_pipeline(estimator, framing_mode, temporal_fill)
     if subject:
         subject_lock_mod.check_pipeline(temporal_fill, scene, estimation_mask)
+    rolling = rolling_shutter_mod.check_request(rolling_shutter)
+    if rolling is not None:
+        rolling_shutter_mod.check_pipeline(rolling, transform_mode, framing_mode, estimator, mesh, temporal_fill, sharpness, zoom)
     total_frames = len(context.frames)
     fps_effective, fps_requested = _fps_fields(context, frame_rate)
     size = (context.width, context.height)
@@ -997,8 +1031,9 @@ def _stabilize_frames(
 
     # (scene-aware calls form the plan on the host: plan_kernel knows one continuous camera move; so do mesh-warp calls: the
     # vertex paths need the plan's own transitions before the warp can be queued; and dynamic-zoom calls: the zoom is formed
-    # from the plan's final matrices before the warp can be queued)
-    if scene is None and mesh is None and zoom is None and device_plan_applies(estimator, framing_mode, transform_mode, total_frames):
+    # from the plan's final matrices before the warp can be queued; and rolling-shutter calls: the velocities come from the
+    # plan's transitions before the warp can be queued)
+    if scene is None and mesh is None and zoom is None and rolling is None and device_plan_applies(estimator, framing_mode, transform_mode, total_frames):
         done = _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode,
                                            camera_lock, strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested,
                                            pbar, progress_total, keep_on_device, temporal_fill, blocked, mask_info, spatial_fill,
@@ -1012,8 +1047,8 @@ def _stabilize_frames(
     peaks = [] if context.range_pending else None
     if scene is not None and scene.mode == "auto":
         masked = dict(masked, gray_out=[])     # the estimation images stay alive for the score below
-    if mesh is not None:
-        masked = dict(masked, grid_out=[])     # so does the grid of flow samples, for the vertex residuals
+    if mesh is not None or rolling == rolling_shutter_mod.AUTO:
+        masked = dict(masked, grid_out=[])     # so does the grid of flow samples, for the vertex / row residuals
     if subject:
         masked = {"subject": {"mask": subject_lock_mod.mask_on_device(ctx, subject_mask)}}
     fit_records = estimate(ctx, device_frames, working_size, transform_mode, peaks_out=peaks, **masked)
@@ -1049,12 +1084,20 @@ def _stabilize_frames(
                                             strength, smooth, camera_lock, fps_effective)
     if zoom is not None:
         plan, zoom_block = _dynamic_zoom(ctx, zoom, plan, offsets, segments)
+    rolling_block = None
+    if rolling is not None:
+        velocity, readout, rolling_block = _rolling_shutter(ctx, rolling, plan, masked.get("grid_out"), blocked, working_size, size,
+                                                            segments)
     if mesh is not None:
         dst, mask, counts = ctx.mesh_warp_batch(
             device_frames, plan.final_matrices, plan.output_size, offsets, border=hm.border_value(padding_rgb),
             want_mask=True, want_count=True)
         if mesh_motion:
             mesh_block["motion"] = mesh_warp_mod.motion_block(offsets, size)
+    elif rolling is not None:
+        dst, mask, counts = ctx.rolling_warp_batch(
+            device_frames, plan.final_matrices, plan.output_size, velocity, readout, border=hm.border_value(padding_rgb),
+            want_mask=True, want_count=True)
     else:
         dst, mask, counts = ctx.warp_batch(
             device_frames, plan.final_matrices, plan.output_size, interp="bilinear",
@@ -1073,6 +1116,8 @@ def _stabilize_frames(
         meta["mesh_warp"] = mesh_block
     if subject:
         meta["subject_lock"] = masked["subject"]["block"]
+    if rolling_block is not None:
+        meta["rolling_shutter"] = rolling_block
     _sharpness_transfer(ctx, device_frames, dst, mask, plan, meta, sharpness)
     _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill, fill_blend)
     _spatial_fill(ctx, dst, mask, plan, meta, spatial_fill)

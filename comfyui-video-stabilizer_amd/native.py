@@ -185,6 +185,12 @@ _SIGNATURES = {
     "vstab_mesh_unwarp_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                   C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vstab_rolling_warp_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                  C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vstab_row_residual_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                  C.c_void_p, C.c_void_p]),
     "vstab_cover_extent_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                   C.c_void_p]),
@@ -816,6 +822,52 @@ class Context:
             _dev_ptr(counts) if counts is not None else None,
             _dev_ptr(unconverged) if unconverged is not None else None), "vstab_mesh_unwarp_batch")
         return dst, mask, counts, unconverged
+
+    # ------------------------------------------------------------------ rolling shutter
+    def rolling_warp_batch(self, frames, matrices, out_size, velocity, readout, border=(0.0, 0.0, 0.0), subpix=None,
+                           want_mask=True, want_count=True):
+        """warp_batch (bilinear) that samples every source row where a sensor read out over `readout` of the frame interval
+        showed it (vstab_rolling_warp_batch; the rule is in include/vstab.h).  velocity f64 [N,6] (host), full-resolution px per
+        frame interval; readout in [-1, 1] -> (dst [N,h,w,3], mask [N,h,w] | None, counts [N] | None).  All-zero velocity or
+        readout == 0 give warp_batch's bits."""
+        src, (n, sh, sw), (out_h, out_w), b, dst, mask, counts = self._warp_io(
+            "rolling_warp_batch", frames, out_size, border, want_mask, want_count)
+        v = np.ascontiguousarray(velocity, dtype=np.float64)
+        if v.size != n * 6:
+            raise ValueError(f"rolling_warp_batch: velocity {v.shape} is not [{n},6]")
+        readout = float(readout)
+        if not -1.0 <= readout <= 1.0:       # (a NaN fails it too)
+            raise ValueError(f"rolling_warp_batch: readout={readout!r} outside [-1, 1]")
+        m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(n, 9)
+        self.use_torch_stream()
+        _check(self.lib.vstab_rolling_warp_batch(
+            self.handle, _dev_ptr(src), n, sh, sw, m.ctypes.data, out_h, out_w, b.ctypes.data, SUBPIX[subpix or DEFAULT_SUBPIX],
+            v.ctypes.data, readout, _dev_ptr(dst), _dev_ptr(mask) if mask is not None else None,
+            _dev_ptr(counts) if counts is not None else None), "vstab_rolling_warp_batch")
+        return dst, mask, counts
+
+    def row_residual_batch(self, grid_flow, step, work_size, transitions, blocked=None):
+        """Per-row median of the global fit's residual (vstab_row_residual_batch; the rule is in include/vstab.h).
+        grid_flow f32 [P,gh,gw,2] (device), work_size = (w, h) of the estimation images, transitions f32 [P,3,3] at working
+        resolution, blocked u8 [P+1,gh,gw] or None -> (residual f32 [P,gh,2], count i32 [P,gh]), device tensors."""
+        torch = self.torch
+        if grid_flow.dtype != torch.float32 or grid_flow.dim() != 4 or grid_flow.shape[3] != 2:
+            raise ValueError("row_residual_batch expects a float32 [P,gh,gw,2] tensor")
+        grid_flow, blocked, pairs, gh, gw = self._fit_inputs(grid_flow, blocked)
+        ww, wh, step = int(work_size[0]), int(work_size[1]), int(step)
+        if step < 1 or (gh, gw) != ((wh + step - 1) // step, (ww + step - 1) // step):
+            raise ValueError(f"row_residual_batch: a grid of {gw}x{gh} samples is not a {ww}x{wh} image at step {step}")
+        m = np.ascontiguousarray(transitions, dtype=np.float32)
+        if m.size != pairs * 9:
+            raise ValueError(f"row_residual_batch: transitions {m.shape} are not [{pairs},3,3]")
+        residual = torch.empty((pairs, gh, 2), dtype=torch.float32, device=self.device)
+        count = torch.empty((pairs, gh), dtype=torch.int32, device=self.device)
+        self.use_torch_stream()
+        _check(self.lib.vstab_row_residual_batch(
+            self.handle, _dev_ptr(grid_flow), pairs, gh, gw, step, wh, ww, m.ctypes.data,
+            _dev_ptr(blocked) if blocked is not None else None, _dev_ptr(residual), _dev_ptr(count)),
+            "vstab_row_residual_batch")
+        return residual, count
 
     def cover_extent_batch(self, matrices, src_size, out_size, offsets=None, subpix=None):
         """How far the warp's own coverage reaches around the canvas centre (vstab_cover_extent_batch; the rule is in

@@ -937,6 +937,48 @@ class VideoStabilizerFlowSubject(io.ComfyNode):
         return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
 
 
+class VideoStabilizerFlowRolling(io.ComfyNode):
+    """The Flow node with the rolling-shutter correction: the final warp samples every source row where a sensor read out
+    row by row showed it, so the lean and wobble that remain once the shake is gone ("jello") are taken out with it
+    (rolling_shutter.py).  Readout 0 estimates the sensor's readout time from the clip.  Not one of the reference's nodes: it
+    is listed by an extension but kept out of NODE_CLASSES."""
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        schema = io.Schema(
+            node_id="video_stabilizer_flow_rolling",
+            display_name="Video Stabilizer Flow (Rolling Shutter)",
+            category="Video/Stabilization",
+            description=("Video Stabilizer Flow that also removes the skew and wobble of a rolling shutter: each row is "
+                         "corrected for the time at which the sensor read it."),
+        )
+        base = VideoStabilizerFlow.define_schema()
+        schema.inputs = [
+            io.Combo.Input("transform_mode", options=["translation", "similarity"], default="similarity",
+                           display_name="Transform Mode",
+                           tooltip=("Select the geometric model fitted to the optical flow.  The row correction is a closed "
+                                    "form of an affine image velocity, so perspective is not offered."))
+            if s.id == "transform_mode" else s for s in base.inputs] + [
+            io.Float.Input("readout", default=0.0, min=-1.0, max=1.0, step=0.01, display_name="Readout",
+                           tooltip=("Readout time of the sensor as a fraction of the frame interval; negative for a sensor "
+                                    "read from the bottom up.  0 estimates it from the clip, which needs a clip whose "
+                                    "camera accelerates; the meta reports what was found.")),
+        ]
+        schema.outputs = _estimator_outputs()
+        return schema
+
+    @classmethod
+    def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
+                strength: float, smooth: float, keep_fov: float, padding_color: str, readout: float = 0.0) -> io.NodeOutput:
+        context = hm._normalize_video_input(frames)
+        result = _stabilize_frames(
+            context, framing_mode, transform_mode, camera_lock, strength, smooth, keep_fov,
+            hm._parse_padding_color(padding_color), frame_rate, keep_on_device=True, estimator="flow",
+            rolling_shutter="auto" if float(readout) == 0.0 else float(readout),
+        )
+        return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
+
+
 NODE_CLASSES = [VideoStabilizerClassic, VideoStabilizerFlow, VideoStabilizerMotionApply, VideoStabilizerShakeGenerator,
                 VideoStabilizerShakeGeneratorManual, VideoStabilizerInverse]
 
@@ -1109,3 +1151,11 @@ class VideoStabilizerAmdHandoffExtension(VideoStabilizerAmdSharpnessExtension):
 
     async def get_node_list(self) -> list:
         return await super().get_node_list() + [VideoStabilizerMaskGrow]
+
+
+class VideoStabilizerAmdRollingExtension(VideoStabilizerAmdHandoffExtension):
+    """The hand-off extension's nineteen nodes plus Video Stabilizer Flow (Rolling Shutter).  A class of its own for the reason
+    the eleven before it are: comfy_entrypoint() keeps handing out its own."""
+
+    async def get_node_list(self) -> list:
+        return await super().get_node_list() + [VideoStabilizerFlowRolling]

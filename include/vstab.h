@@ -606,6 +606,51 @@ int vstab_mesh_unwarp_batch(vstab_ctx* ctx, const float* src, int n, int src_h, 
                             int out_h, int out_w, const float* border_rgb, int subpix, const float* offsets, int mw, int mh,
                             float* dst, float* mask, uint32_t* pad_count, uint32_t* unconverged);
 
+/* ---- rolling shutter (not a reference feature, off by default): the per-row readout correction of the final warp ----
+ * A sensor read out row by row over the fraction rho of the frame interval (the READOUT; negative: bottom to top) shows a
+ * point that a global shutter would show at q at s = q + tau(s_y) * v(q) instead, tau(y) = rho * (y/(H-1) - 1/2) in frame
+ * intervals and v(q) = V * (q_x, q_y, 1) the image velocity in px per frame interval, a 2x3 V per frame (rolling_shutter.py
+ * forms it from the transitions).  The equation is linear in s_y: tau = rho*(q_y/(H-1) - 1/2) / (1 - rho*v_y/(H-1)).
+ *
+ * vstab_rolling_warp_batch -- vstab_warp_batch (bilinear) that samples the source at s instead of q: vstab_mesh_warp_batch's
+ * rule with another displacement c = -tau * v in s = q - c(q).  Xn, Yn, W, Wn, Wq, q = (qx, qy) = (Xn*Wn, Yn*Wn), the three
+ * roundings c enters and everything behind them are stated there.  c, with H = src_h, V = the frame's six coefficients and
+ * rho = readout -- every operation IEEE fp64 and rounded on its own, nothing fused:
+ *   - yc = (qy > 0) ? qy : 0 (a NaN becomes 0), yc = (yc < H-1) ? yc : H-1
+ *   - vx = (V0*qx + V1*qy) + V2, vy = (V3*qx + V4*qy) + V5
+ *   - D = 1 - (rho*vy) / (H-1); if D >= 0.5 does not hold (a NaN included), D = 0.5: a row velocity that would fold the
+ *     readout over itself is not believed
+ *   - tau = (rho * (yc/(H-1) - 0.5)) / D
+ *   - cx = -(tau*vx), cy = -(tau*vy); if either is not finite, both are 0.
+ * Invariant: all-zero velocity or readout == 0 give dst, mask and pad_count bit-identical to vstab_warp_batch (c is a zero,
+ * and v - c == v for every v that is not a zero of c's sign, which rounds and samples as its counterpart does).
+ *   velocity host [n, 6] f64 (V0..V5), full-resolution px per frame interval, staged with the transform records
+ *   readout  in [-1, 1]; src_h >= 2
+ * The other arguments are vstab_warp_batch's, interp fixed to bilinear, and are checked as vstab_warp_batch checks them (same
+ * error texts under this function's name).  Kernel (vstab_rolling.hip): the plain warp's 64 x 8 tile and XCD remap; the
+ * frame's coefficients and the readout are uniform, there is no table in LDS.  Timing kind "rolling_warp".
+ *
+ * vstab_row_residual_batch -- what the readout is estimated from: per pair i and grid row gy, the per-axis median of the
+ * global fit's residual over the row's admitted samples.  A rolling shutter leaves a residual that is linear in the row.
+ *   - the residual r of grid sample (gx, gy) at (x, y) = (gx*step, gy*step) is vstab_mesh_residual_batch's, unchanged:
+ *     r = ( (float)((x + (double)u) - X / W), (float)((y + (double)v) - Y / W) ) with X, Y, W as stated there.
+ *   - the sample is ADMITTED iff u, v and both components of r are finite and it is blocked neither in frame i nor in
+ *     frame i+1 (blocked == NULL: nothing is).
+ *   - count = the number of admitted samples of the row.  count >= VSTAB_ROW_MIN_SAMPLES: per axis the median as
+ *     numpy.median gives it on float32 (an even count: (lo + hi) / 2.0f).  Fewer: residual (0, 0), true count.
+ * A median does not depend on the order of its inputs, so the result equals the NumPy restatement exactly.
+ *   grid_flow, transitions, blocked: as for vstab_mesh_residual_batch
+ *   residual dev [pairs, gh, 2] f32;  count dev [pairs, gh] i32
+ * work_w, work_h >= 2; a row of more than 4096 grid positions is refused.  One workgroup per (pair, row), rank counting in
+ * LDS.  Asynchronous on the context's stream; timing kind "row_residual".  VSTAB_ROW_MIN_SAMPLES is a choice, not a
+ * calibration: a median of fewer values is hardly one. */
+#define VSTAB_ROW_MIN_SAMPLES 8
+int vstab_rolling_warp_batch(vstab_ctx* ctx, const float* src, int n, int src_h, int src_w, const float* matrices,
+                             int out_h, int out_w, const float* border_rgb, int subpix, const double* velocity,
+                             double readout, float* dst, float* mask, uint32_t* pad_count);
+int vstab_row_residual_batch(vstab_ctx* ctx, const float* grid_flow, int pairs, int gh, int gw, int step, int work_h,
+                             int work_w, const float* transitions, const uint8_t* blocked, float* residual, int32_t* count);
+
 /* ---- dynamic zoom (not a reference feature, off by default): how far a warp's own coverage reaches around the centre ----
  * A per-frame zoom that hides the frame's own border needs to know the largest centred rectangle of the canvas the warp
  * covers.  Closed-form geometry would drift from the warp at the nearest-rounding boundary and does not exist for a mesh,
