@@ -229,42 +229,48 @@ def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, t
     a driver that needs the dict once asks rank 0 only.  check_value_range: F0's per-frame `max > 1.5 -> /255` rule
     (stabilizer_utils.py:127-131) is applied to this rank's frames from the maxima the gray pass reports; it is a
     per-frame rule, so no rank needs to know another rank's verdict."""
-    if estimator == "subject":
-        # the subject's mask would have to be sharded with the frames and its gaps interpolated across ranks; every rank
-        # raises alike, before any collective
-        raise ValueError("stabilize_sharded does not support estimator 'subject': the subject lock is not sharded (its mask "
-                         "is not distributed with each rank's frames); run the single-GPU pipeline for a subject lock")
-    if estimation_mask is not None:
-        # the mask would have to be sharded with the frames, halo frame included; every rank raises alike, before any collective
-        raise ValueError("stabilize_sharded does not support estimation_mask: the sharded path does not distribute a mask "
-                         "with each rank's frames and halo; run the single-GPU pipeline for a masked estimation")
-    if scene_cuts is not None:
+    # What the sharded path does not do: (keyword, is it requested, message), refused in this order.  Every rank raises alike,
+    # before any collective (and before torch.distributed is imported).
+    refusals = (
+        # the subject's mask would have to be sharded with the frames and its gaps interpolated across ranks
+        ("estimator", estimator == "subject",
+         "stabilize_sharded does not support estimator 'subject': the subject lock is not sharded (its mask "
+         "is not distributed with each rank's frames); run the single-GPU pipeline for a subject lock"),
+        # the mask would have to be sharded with the frames, halo frame included
+        ("estimation_mask", estimation_mask is not None,
+         "stabilize_sharded does not support estimation_mask: the sharded path does not distribute a mask "
+         "with each rank's frames and halo; run the single-GPU pipeline for a masked estimation"),
         # a shot may span ranks: the per-shot mode walk and trajectory would need every rank's records before the plan, which
-        # the sharded plan (one continuous camera move) does not form; every rank raises alike, before any collective
-        raise ValueError("stabilize_sharded does not support scene_cuts: scene cuts are not sharded (the sharded plan treats the "
-                         "clip as one continuous camera move); run the single-GPU pipeline for a scene-aware stabilization")
-    if mesh_warp is not None:
+        # the sharded plan (one continuous camera move) does not form
+        ("scene_cuts", scene_cuts is not None,
+         "stabilize_sharded does not support scene_cuts: scene cuts are not sharded (the sharded plan treats the "
+         "clip as one continuous camera move); run the single-GPU pipeline for a scene-aware stabilization"),
         # every vertex path runs through the whole clip: the residuals of every rank's flow grid would have to be gathered
-        # before the warp, which the sharded path does not do; every rank raises alike, before any collective
-        raise ValueError("stabilize_sharded does not support mesh_warp: the mesh warp is not sharded (vertex paths need every "
-                         "rank's flow grid); run the single-GPU pipeline for a mesh-warped stabilization")
-    if dynamic_zoom is not None:
+        # before the warp, which the sharded path does not do
+        ("mesh_warp", mesh_warp is not None,
+         "stabilize_sharded does not support mesh_warp: the mesh warp is not sharded (vertex paths need every "
+         "rank's flow grid); run the single-GPU pipeline for a mesh-warped stabilization"),
         # the envelope runs over the whole clip: every rank's coverage extents would have to be gathered before the warp,
-        # which the sharded path does not do; every rank raises alike, before any collective
-        raise ValueError("stabilize_sharded does not support dynamic_zoom: dynamic zoom is not sharded (the envelope needs "
-                         "every rank's extents); run the single-GPU pipeline for a dynamically zoomed stabilization")
-    if rolling_shutter is not None:
+        # which the sharded path does not do
+        ("dynamic_zoom", dynamic_zoom is not None,
+         "stabilize_sharded does not support dynamic_zoom: dynamic zoom is not sharded (the envelope needs "
+         "every rank's extents); run the single-GPU pipeline for a dynamically zoomed stabilization"),
         # a frame's velocity needs the transitions on both of its sides and the readout estimate every rank's row residuals,
-        # neither of which the sharded path gathers before the warp; every rank raises alike, before any collective
-        raise ValueError(f"stabilize_sharded does not support rolling_shutter={rolling_shutter!r}: the rolling-shutter correction "
-                         "is not sharded (velocities and the readout estimate need every rank's transitions); run the "
-                         "single-GPU pipeline for it")
-    if sharpness_transfer is not None and sharpness_transfer is not False and sharpness_transfer != 0:
+        # neither of which the sharded path gathers before the warp
+        ("rolling_shutter", rolling_shutter is not None,
+         f"stabilize_sharded does not support rolling_shutter={rolling_shutter!r}: the rolling-shutter correction "
+         "is not sharded (velocities and the readout estimate need every rank's transitions); run the "
+         "single-GPU pipeline for it"),
         # a rank would need the sharpness of, and the source frames, up to `sharpness_transfer` frames before and after its
-        # shard (a halo it does not hold); every rank raises alike, before any collective
-        raise ValueError(f"stabilize_sharded does not support sharpness_transfer={sharpness_transfer!r}: the sharpness transfer is "
-                         "not sharded (the sharded path holds no halo of neighbouring source frames); run the single-GPU "
-                         "pipeline for it")
+        # shard (a halo it does not hold)
+        ("sharpness_transfer", sharpness_transfer is not None and sharpness_transfer is not False and sharpness_transfer != 0,
+         f"stabilize_sharded does not support sharpness_transfer={sharpness_transfer!r}: the sharpness transfer is "
+         "not sharded (the sharded path holds no halo of neighbouring source frames); run the single-GPU "
+         "pipeline for it"),
+    )
+    for _keyword, requested, message in refusals:
+        if requested:
+            raise ValueError(message)
     import torch.distributed as dist
 
     from . import native

@@ -17,7 +17,7 @@ from __future__ import annotations
 import gc
 import os
 from dataclasses import dataclass, replace
-from typing import Any, Dict, Optional, Tuple
+from typing import Any, Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -702,10 +702,10 @@ def _scene_segments(ctx, scene, fit_records, gray_out, transform_mode: str, tota
 
 
 # ---- mesh warp (beyond the reference; mesh_warp.py, the rules are in include/vstab.h) -----------------------------------
-def _mesh_offsets(ctx, mesh, plan, grid, blocked, working_size, size, segments, strength, smooth, camera_lock, fps_effective):
+def _mesh_offsets(ctx, mesh, plan, grid, blocked, working_size, size, segments, args):
     """-> (the warp's vertex offsets f32 [N,mh,mw,2] in full-resolution px, meta["mesh_warp"]).  One launch of the residual
     kernel over the grid the estimator made, against the working-resolution transitions the plan itself used; the vertex
-    paths go through the trajectory routine with the plan's own (clipped) smooth / strength."""
+    paths go through the trajectory routine with the plan's own (clipped) smooth / strength.  args: the call's FlowArgs."""
     width, height = size
     work = working_size if working_size is not None else size
     mw, mh = mesh.vertices
@@ -714,8 +714,8 @@ def _mesh_offsets(ctx, mesh, plan, grid, blocked, working_size, size, segments, 
     residual, count = residual.cpu().numpy(), count.cpu().numpy()
     max_shift = mesh.max_shift_px(width)
     offsets, _ = mesh_warp_mod.plan_offsets(
-        ctx.trajectory, residual, em["confidences"], segments, float(np.clip(smooth, 0.0, 1.0)), fps_effective,
-        float(np.clip(strength, 0.0, 1.0)), bool(camera_lock), (1.0 / (work[0] / float(width)), 1.0 / (work[1] / float(height))), max_shift)   # the plan's own up-scale factors
+        ctx.trajectory, residual, em["confidences"], segments, float(np.clip(args.smooth, 0.0, 1.0)), args.fps_effective,
+        float(np.clip(args.strength, 0.0, 1.0)), bool(args.camera_lock), (1.0 / (work[0] / float(width)), 1.0 / (work[1] / float(height))), max_shift)   # the plan's own up-scale factors
     return offsets, mesh_warp_mod.meta_block(mesh, max_shift, residual, count, offsets, native.MESH_MIN_SAMPLES)
 
 
@@ -748,19 +748,142 @@ def _dynamic_zoom(ctx, zoom, plan, offsets, segments):
     return replace(plan, final_matrices=np.matmul(Z, np.asarray(plan.final_matrices, dtype=np.float32))), block
 
 
-def _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode, camera_lock,
-                                strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested, pbar, progress_total,
-                                keep_on_device, temporal_fill=0, blocked=None, mask_info=None, spatial_fill=False,
-                                stability_report=False, fill_blend=(None, False), sharpness=None, handoff=None):
+# ---- the driver: one validated request, one record of the reference's arguments, one post-warp tail ----------------------
+@dataclass(frozen=True)
+class FlowRequest:
+    """The keyword extras of one `_stabilize_frames` call, checked: every field is what its feature's check returned, and
+    the object existing means the requests are valid and compatible with each other, with the framing and with the
+    transform mode.  It carries no tensor and no per-call state (masks, clip, context travel beside it).  What each keyword
+    means is in `_stabilize_frames`' docstring."""
+
+    estimator: str                     # resolved (resolve_flow_backend)
+    temporal_fill: int                 # radius, 0 = off
+    fill_blend: Tuple[Optional[int], bool]   # temporal_fill.check_blend_request: (feather px | None, exposure)
+    sharpness: Optional[Tuple[int, float]]   # sharpness_transfer.check_request: (radius, alpha) | None
+    handoff: Any                       # mask_handoff.check_request: Request | None
+    zoom: Any                          # dynamic_zoom.check_request | None
+    scene: Any                         # scene_cuts.check_request | None
+    mesh: Any                          # mesh_warp.check_request | None
+    mesh_motion: bool
+    subject: bool                      # the estimator is the subject lock (its mask travels beside the request)
+    rolling: Any                       # rolling_shutter.check_request: readout | AUTO | None
+    spatial_fill: bool
+    stability_report: bool
+    mask_margin: Optional[int]         # the estimation mask's margin; None: no estimation mask was given
+
+    @property
+    def needs_host_plan(self) -> bool:
+        """Scene-aware calls form the plan on the host: plan_kernel knows one continuous camera move; so do mesh-warp calls:
+        the vertex paths need the plan's own transitions before the warp can be queued; and dynamic-zoom calls: the zoom is
+        formed from the plan's final matrices before the warp can be queued; and rolling-shutter calls: the velocities come
+        from the plan's transitions before the warp can be queued."""
+        return not (self.scene is None and self.mesh is None and self.zoom is None and self.rolling is None)
+
+    @property
+    def kept_by_products(self) -> Tuple[str, ...]:
+        """The estimator's by-products that stay alive behind the fits (its `*_out` keywords): the estimation images for the
+        scene-cut score, the grid of flow samples for the vertex / row residuals."""
+        keep = ("gray_out",) if self.scene is not None and self.scene.mode == "auto" else ()
+        return keep + (("grid_out",) if self.mesh is not None or self.rolling == rolling_shutter_mod.AUTO else ())
+
+
+def check_flow_request(framing_mode: str, transform_mode: str, estimator: str, kw: Dict[str, Any]) -> FlowRequest:
+    """Every check of `_stabilize_frames`' keyword extras `kw` (by name) that needs neither the clip nor a GPU, in one fixed
+    order: a call that is wrong in several ways always raises the same message (tests/test_flow_request_cpu.py)."""
+    handoff = mask_handoff_mod.check_request(kw["mask_grow"], kw["mask_feather"], kw["mask_hold"], kw["mask_tapered"])
+    zoom = dynamic_zoom_mod.check_request(kw["dynamic_zoom"], kw["zoom_limit"])
+    if zoom is not None:
+        dynamic_zoom_mod.check_pipeline(framing_mode)
+    spatial_fill = spatial_fill_mod.check_request(kw["spatial_fill"])
+    stability_report = stability_mod.check_request(kw["stability_report"])
+    scene = scene_cuts_mod.check_request(kw["scene_cuts"], kw["cut_threshold"])
+    mesh = mesh_warp_mod.check_request(kw["mesh_warp"], kw["mesh_max_shift"])
+    if kw["mesh_motion"] and mesh is None:
+        raise ValueError("mesh_motion=True needs mesh_warp: without a mesh warp there are no per-vertex offsets to record.")
+    if estimator not in _META_SOURCE:
+        raise ValueError(f"Unknown estimator {estimator!r}; expected 'flow' or 'classic'.")
+    subject = subject_lock_mod.check_request(kw["subject_mask"], transform_mode, estimator)
+    temporal_fill = int(kw["temporal_fill"])
+    if not 0 <= temporal_fill <= temporal_fill_mod.MAX_RADIUS:
+        raise ValueError(f"temporal_fill={temporal_fill} outside [0, {temporal_fill_mod.MAX_RADIUS}]")
+    fill_blend = temporal_fill_mod.check_blend_request(temporal_fill, kw["fill_feather"], kw["fill_exposure"])
+    sharpness = sharpness_transfer_mod.check_request(kw["sharpness_transfer"], kw["sharpness_alpha"])
+    if sharpness is not None:
+        sharpness_transfer_mod.check_pipeline(estimator, mesh)
+    estimator = resolve_flow_backend(estimator)
+    mask_margin = None
+    if kw["estimation_mask"] is not None:
+        mask_margin = check_estimation_mask_request(estimator, kw["mask_margin"])
+    if mesh is not None:
+        mesh_warp_mod.check_pipeline(estimator, framing_mode, temporal_fill)
+    if subject:
+        subject_lock_mod.check_pipeline(temporal_fill, scene, kw["estimation_mask"])
+    rolling = rolling_shutter_mod.check_request(kw["rolling_shutter"])
+    if rolling is not None:
+        rolling_shutter_mod.check_pipeline(rolling, transform_mode, framing_mode, estimator, mesh, temporal_fill, sharpness, zoom)
+    return FlowRequest(estimator, temporal_fill, fill_blend, sharpness, handoff, zoom, scene, mesh, bool(kw["mesh_motion"]),
+                       bool(subject), rolling, spatial_fill, stability_report, mask_margin)
+
+
+def _check_request_against_clip(request: FlowRequest, kw: Dict[str, Any], transform_mode: str, total_frames: int, size) -> None:
+    """The three checks that need the clip's length and size, run as soon as they are known."""
+    if kw["estimation_mask"] is not None:
+        check_estimation_mask_shape(kw["estimation_mask"], total_frames, size)
+    if request.scene is not None and request.scene.mode == "given":
+        scene_cuts_mod.check_given_cuts(request.scene.cuts, total_frames)
+    if request.subject:
+        subject_lock_mod.check_request(kw["subject_mask"], transform_mode, request.estimator, total_frames, size)
+
+
+class FlowArgs(NamedTuple):
+    """The reference's arguments of one call behind the clip, in the order plan_stabilization takes them (`*args`)."""
+
+    framing_mode: str
+    transform_mode: str
+    camera_lock: bool
+    strength: float
+    smooth: float
+    keep_fov: float
+    padding_rgb: Tuple[int, int, int]
+    fps_effective: float
+    fps_requested: Optional[float]
+
+
+def _finish(ctx, request: FlowRequest, plan, device_frames, dst, mask, meta, segments, keep_on_device: bool, verdict):
+    """Everything behind the warp, for either plan path: the five post-warp passes, then the result on the device or the host.
+    The ORDER is a correctness rule.  The sharpness transfer runs before the fills: a filled pixel gets mask 0 and would be
+    taken for an own one.  Temporal fill comes before spatial fill: seen pixels before invented ones.  The stability report
+    measures behind every fill; the spatial fill leaves the mask as it is, so its invented pixels stay out of it.  The mask
+    hand-off runs last, so that every other pass has seen the true mask; it replaces only the mask that is returned.  Each
+    pass adds its own meta block, in this order, and nothing else in the meta changes.
+    segments: the shots under scene cuts, None for one continuous camera move (always on the device-plan path)."""
+    _sharpness_transfer(ctx, device_frames, dst, mask, plan, meta, request.sharpness)
+    _temporal_fill(ctx, device_frames, dst, mask, plan, meta, request.temporal_fill, request.fill_blend)
+    _spatial_fill(ctx, dst, mask, plan, meta, request.spatial_fill)
+    _stability_report(ctx, device_frames, dst, mask, plan, meta, request.stability_report, segments)
+    mask = _mask_handoff(ctx, mask, plan, meta, request.handoff, segments)
+    check_interrupt()
+    if keep_on_device:
+        return hm.StabilizationResult(dst, mask.unsqueeze(-1), meta, verdict)
+    return hm.StabilizationResult(dst.cpu().numpy(), mask.cpu().numpy()[..., np.newaxis], meta, verdict)
+
+
+def _stabilize_with_device_plan(ctx, context, device_frames, request: FlowRequest, args: FlowArgs, pbar, keep_on_device: bool,
+                                blocked=None, mask_info=None):
     """F2-F14 with the plan formed on the device (see above).  Returns None when F0 found 0..255 float data: the
-    speculative run used the unscaled frames and is discarded; the caller takes the regular path on the rescaled clip."""
+    speculative run used the unscaled frames and is discarded; the caller takes the regular path on the rescaled clip.
+    Only for requests that do not need the host plan: there are no shots here, one continuous camera move."""
     size = (context.width, context.height)
+    total_frames = len(context.frames)
+    progress_total = (total_frames - 1) + total_frames
+    working_size = hm._working_estimation_size(context.width, context.height)
+    framing_mode, transform_mode, padding_rgb = args.framing_mode, args.transform_mode, args.padding_rgb
     peaks = [] if context.range_pending else None
     gray = _gray(ctx, device_frames, working_size, peaks)
     _, grid = ctx.dis_flow_batch(gray, sample_step=SAMPLE_STEP, want_full=False, want_grid=True)
     pairs = ctx.sample_fit_batch_begin(grid, SAMPLE_STEP, transform_mode, blocked=blocked)
-    ctx.flow_plan_device(ctx.fit_records_device(), pairs, transform_mode, size, working_size, smooth, fps_effective, strength,
-                         bool(camera_lock), warp_frames=total_frames, framing=framing_mode)
+    ctx.flow_plan_device(ctx.fit_records_device(), pairs, transform_mode, size, working_size, args.smooth, args.fps_effective,
+                         args.strength, bool(args.camera_lock), warp_frames=total_frames, framing=framing_mode)
     out_size = size
     if framing_mode == "expand":
         # the canvas has to exist before the warp is queued: wait for the plan kernel's region (the plan's download, ~30 us
@@ -776,8 +899,7 @@ def _stabilize_with_device_plan(ctx, context, device_frames, working_size, total
         return None
     progress_done = _replay_progress(pbar, 0, total_frames - 1, progress_total)
     check_interrupt()
-    plan = plan_stabilization(ctx, fit_records, size, total_frames, framing_mode, transform_mode, camera_lock, strength, smooth,
-                              keep_fov, padding_rgb, fps_effective, fps_requested, estimator="flow")
+    plan = plan_stabilization(ctx, fit_records, size, total_frames, *args, estimator="flow")
     meta = prepare_meta(plan)                               # host JSON work overlaps the warp kernel
     final_dev = ctx.flow_plan_result(total_frames, PLAN_PARAMS[transform_mode])[0]
     if tuple(plan.output_size) != tuple(out_size):
@@ -796,15 +918,8 @@ def _stabilize_with_device_plan(ctx, context, device_frames, working_size, total
     meta = complete_meta(meta, plan, _counts_to_host(counts, mirrored=mirror_ok))
     if mask_info is not None:
         meta["estimation_mask"] = estimation_mask_meta(fit_records, *mask_info)
-    _sharpness_transfer(ctx, device_frames, dst, mask, plan, meta, sharpness)               # on the host plan's verified matrices,
-    _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill, fill_blend)   # and so is the fill
-    _spatial_fill(ctx, dst, mask, plan, meta, spatial_fill)
-    _stability_report(ctx, device_frames, dst, mask, plan, meta, stability_report)
-    mask = _mask_handoff(ctx, mask, plan, meta, handoff)
-    check_interrupt()
-    if keep_on_device:
-        return hm.StabilizationResult(dst, mask.unsqueeze(-1), meta, verdict)
-    return hm.StabilizationResult(dst.cpu().numpy(), mask.cpu().numpy()[..., np.newaxis], meta, verdict)
+    # the passes run on the host plan's verified matrices
+    return _finish(ctx, request, plan, device_frames, dst, mask, meta, None, keep_on_device, verdict)
 
 
 def _stabilize_frames(
@@ -932,38 +1047,12 @@ def _stabilize_frames(
     estimator "subject"; everything behind the final warp follows unchanged.  meta["rolling_shutter"] reports the readout, the
     skew it amounts to and every frame's velocity.  None / 0: the behaviour and meta without it, byte for byte, and nothing new
     is launched.  Bypass paths ignore it."""
-    handoff = mask_handoff_mod.check_request(mask_grow, mask_feather, mask_hold, mask_tapered)
-    zoom = dynamic_zoom_mod.check_request(dynamic_zoom, zoom_limit)
-    if zoom is not None:
-        dynamic_zoom_mod.check_pipeline(framing_mode)
-    spatial_fill = spatial_fill_mod.check_request(spatial_fill)
-    stability_report = stability_mod.check_request(stability_report)
-    scene = scene_cuts_mod.check_request(scene_cuts, cut_threshold)
-    mesh = mesh_warp_mod.check_request(mesh_warp, mesh_max_shift)
-    if mesh_motion and mesh is None:
-        raise ValueError("mesh_motion=True needs mesh_warp: without a mesh warp there are no per-vertex offsets to record.")
-    if estimator not in _META_SOURCE:
-        raise ValueError(f"Unknown estimator {estimator!r}; expected 'flow' or 'classic'.")
-    subject = subject_lock_mod.check_request(subject_mask, transform_mode, estimator)
-    temporal_fill = int(temporal_fill)
-    if not 0 <= temporal_fill <= temporal_fill_mod.MAX_RADIUS:
-        raise ValueError(f"temporal_fill={temporal_fill} outside [0, {temporal_fill_mod.MAX_RADIUS}]")
-    fill_blend = temporal_fill_mod.check_blend_request(temporal_fill, fill_feather, fill_exposure)
-    sharpness = sharpness_transfer_mod.check_request(sharpness_transfer, sharpness_alpha)
-    if sharpness is not None:
-        sharpness_transfer_mod.check_pipeline(estimator, mesh)
-    estimator = resolve_flow_backend(estimator)
-    if estimation_mask is not None:
-        mask_margin = check_estimation_mask_request(estimator, mask_margin)
-    if mesh is not None:
-        mesh_warp_mod.check_pipeline(estimator, framing_mode, temporal_fill)
-    if subject:
-        subject_lock_mod.check_pipeline(temporal_fill, scene, estimation_mask)
-    rolling = rolling_shutter_mod.check_request(rolling_shutter)
-    if rolling is not None:
-        rolling_shutter_mod.check_pipeline(rolling, transform_mode, framing_mode, estimator, mesh, temporal_fill, sharpness, zoom)
+    kw = dict(locals())     # every argument by name (nothing else is local yet): the keyword extras are read from here
+    request = check_flow_request(framing_mode, transform_mode, estimator, kw)
+    estimator = request.estimator
     total_frames = len(context.frames)
     fps_effective, fps_requested = _fps_fields(context, frame_rate)
+    args = FlowArgs(framing_mode, transform_mode, camera_lock, strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested)
     size = (context.width, context.height)
     rgb_list = [int(c) for c in padding_rgb]
 
@@ -1013,63 +1102,49 @@ def _stabilize_frames(
         masks_out = np.zeros((1, context.height, context.width, 1), np.float32)
         return hm.StabilizationResult(frames_out, masks_out, _attach_motion_meta(meta, fps_effective, estimator))
 
-    if estimation_mask is not None:
-        check_estimation_mask_shape(estimation_mask, total_frames, size)
-    if scene is not None and scene.mode == "given":
-        scene_cuts_mod.check_given_cuts(scene.cuts, total_frames)
-    if subject:
-        subject_lock_mod.check_request(subject_mask, transform_mode, estimator, total_frames, size)
+    _check_request_against_clip(request, kw, transform_mode, total_frames, size)
     ctx = ctx or native.default_context()
     device_frames = context.device_batch(ctx)
     working_size = hm._working_estimation_size(context.width, context.height)
     blocked = mask_info = None
-    masked = {}
     if estimation_mask is not None:   # reduced once per call: the block grid serves every estimation pass below
-        blocked, mask_frames = _block_grid(ctx, estimation_mask, total_frames, working_size, mask_margin)
-        mask_info = (mask_margin, mask_frames, int(blocked.shape[1] * blocked.shape[2]))
-        masked = {"blocked": blocked}
+        blocked, mask_frames = _block_grid(ctx, estimation_mask, total_frames, working_size, request.mask_margin)
+        mask_info = (request.mask_margin, mask_frames, int(blocked.shape[1] * blocked.shape[2]))
 
-    # (scene-aware calls form the plan on the host: plan_kernel knows one continuous camera move; so do mesh-warp calls: the
-    # vertex paths need the plan's own transitions before the warp can be queued; and dynamic-zoom calls: the zoom is formed
-    # from the plan's final matrices before the warp can be queued; and rolling-shutter calls: the velocities come from the
-    # plan's transitions before the warp can be queued)
-    if scene is None and mesh is None and zoom is None and rolling is None and device_plan_applies(estimator, framing_mode, transform_mode, total_frames):
-        done = _stabilize_with_device_plan(ctx, context, device_frames, working_size, total_frames, framing_mode, transform_mode,
-                                           camera_lock, strength, smooth, keep_fov, padding_rgb, fps_effective, fps_requested,
-                                           pbar, progress_total, keep_on_device, temporal_fill, blocked, mask_info, spatial_fill,
-                                           stability_report, fill_blend, sharpness, handoff)
+    if not request.needs_host_plan and device_plan_applies(estimator, framing_mode, transform_mode, total_frames):
+        done = _stabilize_with_device_plan(ctx, context, device_frames, request, args, pbar, keep_on_device, blocked, mask_info)
         if done is not None:
             return done
         device_frames = context.device_batch(ctx)   # F0 rescaled the clip: everything is redone on the rescaled frames below
 
     # ---- estimation (F2-F5) -------------------------------------------------
-    estimate = _ESTIMATORS[estimator]
+    # the estimator's keyword arguments, built here and nowhere else: the block grid or the subject's mask (never both: the
+    # checks refuse it), and a fresh list for every by-product that has to stay alive behind the fits
+    extras = {"subject": {"mask": subject_lock_mod.mask_on_device(ctx, subject_mask)}} if request.subject else {}
+    if blocked is not None:
+        extras["blocked"] = blocked
+
+    def estimate(frames, peaks_out=None):
+        extras.update({name: [] for name in request.kept_by_products})
+        return _ESTIMATORS[estimator](ctx, frames, working_size, transform_mode, peaks_out=peaks_out, **extras)
+
     peaks = [] if context.range_pending else None
-    if scene is not None and scene.mode == "auto":
-        masked = dict(masked, gray_out=[])     # the estimation images stay alive for the score below
-    if mesh is not None or rolling == rolling_shutter_mod.AUTO:
-        masked = dict(masked, grid_out=[])     # so does the grid of flow samples, for the vertex / row residuals
-    if subject:
-        masked = {"subject": {"mask": subject_lock_mod.mask_on_device(ctx, subject_mask)}}
-    fit_records = estimate(ctx, device_frames, working_size, transform_mode, peaks_out=peaks, **masked)
+    fit_records = estimate(device_frames, peaks)
     if peaks and hm.resolve_value_range(context, peaks[0], ctx):
         # F0 (stabilizer_utils.py:127-131): some frame turned out to be 0..255 float data.  The estimation above ran
         # optimistically on the tensor as given (the gray pass reported the per-frame maxima for free); the frames
         # have been rescaled now, so it is repeated on the rescaled clip.  0..1 input -- the ComfyUI IMAGE contract --
         # never takes this branch.
         device_frames = context.device_batch(ctx)
-        for kept in ("gray_out", "grid_out"):
-            if kept in masked:
-                masked[kept] = []
-        fit_records = estimate(ctx, device_frames, working_size, transform_mode, **masked)
+        fit_records = estimate(device_frames)
     progress_done = _replay_progress(pbar, 0, total_frames - 1, progress_total)
     check_interrupt()
 
+    scene, mesh, zoom, rolling = request.scene, request.mesh, request.zoom, request.rolling
     segments = scene_block = None
     if scene is not None:
-        segments, scene_block = _scene_segments(ctx, scene, fit_records, masked.get("gray_out"), transform_mode, total_frames)
-    plan = plan_stabilization(ctx, fit_records, size, total_frames, framing_mode, transform_mode, camera_lock, strength,
-                              smooth, keep_fov, padding_rgb, fps_effective, fps_requested, estimator=estimator, segments=segments)
+        segments, scene_block = _scene_segments(ctx, scene, fit_records, extras.get("gray_out"), transform_mode, total_frames)
+    plan = plan_stabilization(ctx, fit_records, size, total_frames, *args, estimator=estimator, segments=segments)
     if plan.bypass_meta is not None:  # crop + keep_fov ~ 1 (flow.py:387-429): original frames
         pbar.update_absolute(progress_total, progress_total)
         frames_out = device_frames if keep_on_device else _host_frames(context)
@@ -1078,53 +1153,34 @@ def _stabilize_frames(
         return hm.StabilizationResult(frames_out, masks_out, _attach_motion_meta(plan.bypass_meta, fps_effective, estimator))
 
     # ---- warp (F13) ------------------------------------------------------------
-    mesh_block = zoom_block = offsets = None
+    mesh_block = zoom_block = rolling_block = offsets = None
     if mesh is not None:
-        offsets, mesh_block = _mesh_offsets(ctx, mesh, plan, masked["grid_out"][0], blocked, working_size, size, segments,
-                                            strength, smooth, camera_lock, fps_effective)
+        offsets, mesh_block = _mesh_offsets(ctx, mesh, plan, extras["grid_out"][0], blocked, working_size, size, segments, args)
     if zoom is not None:
         plan, zoom_block = _dynamic_zoom(ctx, zoom, plan, offsets, segments)
-    rolling_block = None
     if rolling is not None:
-        velocity, readout, rolling_block = _rolling_shutter(ctx, rolling, plan, masked.get("grid_out"), blocked, working_size, size,
+        velocity, readout, rolling_block = _rolling_shutter(ctx, rolling, plan, extras.get("grid_out"), blocked, working_size, size,
                                                             segments)
+    warp_args = dict(border=hm.border_value(padding_rgb), want_mask=True, want_count=True)
     if mesh is not None:
-        dst, mask, counts = ctx.mesh_warp_batch(
-            device_frames, plan.final_matrices, plan.output_size, offsets, border=hm.border_value(padding_rgb),
-            want_mask=True, want_count=True)
-        if mesh_motion:
+        dst, mask, counts = ctx.mesh_warp_batch(device_frames, plan.final_matrices, plan.output_size, offsets, **warp_args)
+        if request.mesh_motion:
             mesh_block["motion"] = mesh_warp_mod.motion_block(offsets, size)
     elif rolling is not None:
-        dst, mask, counts = ctx.rolling_warp_batch(
-            device_frames, plan.final_matrices, plan.output_size, velocity, readout, border=hm.border_value(padding_rgb),
-            want_mask=True, want_count=True)
+        dst, mask, counts = ctx.rolling_warp_batch(device_frames, plan.final_matrices, plan.output_size, velocity, readout, **warp_args)
     else:
-        dst, mask, counts = ctx.warp_batch(
-            device_frames, plan.final_matrices, plan.output_size, interp="bilinear",
-            border=hm.border_value(padding_rgb), want_mask=True, want_count=True)
+        dst, mask, counts = ctx.warp_batch(device_frames, plan.final_matrices, plan.output_size, interp="bilinear", **warp_args)
     meta = prepare_meta(plan)  # host JSON work overlaps the warp kernel
     progress_done = _replay_progress(pbar, progress_done, total_frames, progress_total)
     pad_counts = _counts_to_host(counts)
     meta = complete_meta(meta, plan, pad_counts)
-    if zoom_block is not None:
-        meta["dynamic_zoom"] = dynamic_zoom_mod.finish_meta(zoom_block, pad_counts)
-    if mask_info is not None:
-        meta["estimation_mask"] = estimation_mask_meta(fit_records, *mask_info)
-    if scene_block is not None:
-        meta["scene_cuts"] = scene_block
-    if mesh_block is not None:
-        meta["mesh_warp"] = mesh_block
-    if subject:
-        meta["subject_lock"] = masked["subject"]["block"]
-    if rolling_block is not None:
-        meta["rolling_shutter"] = rolling_block
-    _sharpness_transfer(ctx, device_frames, dst, mask, plan, meta, sharpness)
-    _temporal_fill(ctx, device_frames, dst, mask, plan, meta, temporal_fill, fill_blend)
-    _spatial_fill(ctx, dst, mask, plan, meta, spatial_fill)
-    _stability_report(ctx, device_frames, dst, mask, plan, meta, stability_report, segments)
-    mask = _mask_handoff(ctx, mask, plan, meta, handoff, segments)
-    check_interrupt()
-    verdict = {"used": False, "mismatched_frames": 0}
-    if keep_on_device:
-        return hm.StabilizationResult(dst, mask.unsqueeze(-1), meta, verdict)
-    return hm.StabilizationResult(dst.cpu().numpy(), mask.cpu().numpy()[..., np.newaxis], meta, verdict)
+    blocks = {   # in the order the meta lists them
+        "dynamic_zoom": None if zoom_block is None else dynamic_zoom_mod.finish_meta(zoom_block, pad_counts),
+        "estimation_mask": None if mask_info is None else estimation_mask_meta(fit_records, *mask_info),
+        "scene_cuts": scene_block,
+        "mesh_warp": mesh_block,
+        "subject_lock": extras["subject"]["block"] if request.subject else None,
+        "rolling_shutter": rolling_block,
+    }
+    meta.update({key: block for key, block in blocks.items() if block is not None})
+    return _finish(ctx, request, plan, device_frames, dst, mask, meta, segments, keep_on_device, {"used": False, "mismatched_frames": 0})

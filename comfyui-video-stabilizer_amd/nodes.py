@@ -80,11 +80,12 @@ def _estimator_outputs() -> list:
 
 
 def _run_estimator_node(estimator: str, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str,
-                        camera_lock: bool, strength: float, smooth: float, keep_fov: float, padding_color: str):
+                        camera_lock: bool, strength: float, smooth: float, keep_fov: float, padding_color: str, **extras):
+    """What every estimator node's `execute` does; extras: the keyword extras of _stabilize_frames a Flow variant adds."""
     context = hm._normalize_video_input(frames)
     result = _stabilize_frames(
         context, framing_mode, transform_mode, camera_lock, strength, smooth, keep_fov,
-        hm._parse_padding_color(padding_color), frame_rate, keep_on_device=True, estimator=estimator,
+        hm._parse_padding_color(padding_color), frame_rate, keep_on_device=True, estimator=estimator, **extras,
     )
     return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
 
@@ -567,13 +568,8 @@ class VideoStabilizerFlowMasked(io.ComfyNode):
     def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
                 strength: float, smooth: float, keep_fov: float, padding_color: str, exclude_mask: Any,
                 mask_margin: int) -> io.NodeOutput:
-        context = hm._normalize_video_input(frames)
-        result = _stabilize_frames(
-            context, framing_mode, transform_mode, camera_lock, strength, smooth, keep_fov,
-            hm._parse_padding_color(padding_color), frame_rate, keep_on_device=True, estimator="flow",
-            estimation_mask=exclude_mask, mask_margin=int(mask_margin),
-        )
-        return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
+        return _run_estimator_node("flow", frames, frame_rate, framing_mode, transform_mode, camera_lock, strength, smooth,
+                                   keep_fov, padding_color, estimation_mask=exclude_mask, mask_margin=int(mask_margin))
 
 
 class VideoStabilizerFlowScenes(io.ComfyNode):
@@ -605,13 +601,9 @@ class VideoStabilizerFlowScenes(io.ComfyNode):
     @classmethod
     def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
                 strength: float, smooth: float, keep_fov: float, padding_color: str, cut_threshold: float) -> io.NodeOutput:
-        context = hm._normalize_video_input(frames)
-        result = _stabilize_frames(
-            context, framing_mode, transform_mode, camera_lock, strength, smooth, keep_fov,
-            hm._parse_padding_color(padding_color), frame_rate, keep_on_device=True, estimator="flow",
-            scene_cuts="auto", cut_threshold=float(cut_threshold) if cut_threshold else None,
-        )
-        return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
+        return _run_estimator_node("flow", frames, frame_rate, framing_mode, transform_mode, camera_lock, strength, smooth,
+                                   keep_fov, padding_color, scene_cuts="auto",
+                                   cut_threshold=float(cut_threshold) if cut_threshold else None)
 
 
 class VideoStabilizerFlowMesh(io.ComfyNode):
@@ -647,13 +639,9 @@ class VideoStabilizerFlowMesh(io.ComfyNode):
     def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
                 strength: float, smooth: float, keep_fov: float, padding_color: str, mesh_cols: int, mesh_rows: int,
                 max_shift: float) -> io.NodeOutput:
-        context = hm._normalize_video_input(frames)
-        result = _stabilize_frames(
-            context, framing_mode, transform_mode, camera_lock, strength, smooth, keep_fov,
-            hm._parse_padding_color(padding_color), frame_rate, keep_on_device=True, estimator="flow",
-            mesh_warp=(int(mesh_cols), int(mesh_rows)), mesh_max_shift=float(max_shift) if max_shift else None,
-        )
-        return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
+        return _run_estimator_node("flow", frames, frame_rate, framing_mode, transform_mode, camera_lock, strength, smooth,
+                                   keep_fov, padding_color, mesh_warp=(int(mesh_cols), int(mesh_rows)),
+                                   mesh_max_shift=float(max_shift) if max_shift else None)
 
 
 class VideoStabilizerFlowMeshMotion(io.ComfyNode):
@@ -679,14 +667,9 @@ class VideoStabilizerFlowMeshMotion(io.ComfyNode):
     def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
                 strength: float, smooth: float, keep_fov: float, padding_color: str, mesh_cols: int, mesh_rows: int,
                 max_shift: float) -> io.NodeOutput:
-        context = hm._normalize_video_input(frames)
-        result = _stabilize_frames(
-            context, framing_mode, transform_mode, camera_lock, strength, smooth, keep_fov,
-            hm._parse_padding_color(padding_color), frame_rate, keep_on_device=True, estimator="flow",
-            mesh_warp=(int(mesh_cols), int(mesh_rows)), mesh_max_shift=float(max_shift) if max_shift else None,
-            mesh_motion=True,
-        )
-        return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
+        return _run_estimator_node("flow", frames, frame_rate, framing_mode, transform_mode, camera_lock, strength, smooth,
+                                   keep_fov, padding_color, mesh_warp=(int(mesh_cols), int(mesh_rows)),
+                                   mesh_max_shift=float(max_shift) if max_shift else None, mesh_motion=True)
 
 
 class VideoStabilizerMotionApplyMesh(io.ComfyNode):
@@ -887,13 +870,8 @@ class VideoStabilizerFlowZoom(io.ComfyNode):
     @classmethod
     def execute(cls, frames: Any, frame_rate: float, transform_mode: str, camera_lock: bool, strength: float, smooth: float,
                 keep_fov: float, padding_color: str, zoom_window: float, zoom_limit: float) -> io.NodeOutput:
-        context = hm._normalize_video_input(frames)
-        result = _stabilize_frames(
-            context, "crop_and_pad", transform_mode, camera_lock, strength, smooth, keep_fov,
-            hm._parse_padding_color(padding_color), frame_rate, keep_on_device=True, estimator="flow",
-            dynamic_zoom=float(zoom_window), zoom_limit=float(zoom_limit),
-        )
-        return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
+        return _run_estimator_node("flow", frames, frame_rate, "crop_and_pad", transform_mode, camera_lock, strength, smooth,
+                                   keep_fov, padding_color, dynamic_zoom=float(zoom_window), zoom_limit=float(zoom_limit))
 
 
 class VideoStabilizerFlowSubject(io.ComfyNode):
@@ -928,13 +906,8 @@ class VideoStabilizerFlowSubject(io.ComfyNode):
     @classmethod
     def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
                 strength: float, smooth: float, keep_fov: float, padding_color: str, subject_mask: Any) -> io.NodeOutput:
-        context = hm._normalize_video_input(frames)
-        result = _stabilize_frames(
-            context, framing_mode, transform_mode, camera_lock, strength, smooth, keep_fov,
-            hm._parse_padding_color(padding_color), frame_rate, keep_on_device=True, estimator="subject",
-            subject_mask=subject_mask,
-        )
-        return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
+        return _run_estimator_node("subject", frames, frame_rate, framing_mode, transform_mode, camera_lock, strength, smooth,
+                                   keep_fov, padding_color, subject_mask=subject_mask)
 
 
 class VideoStabilizerFlowRolling(io.ComfyNode):
@@ -970,13 +943,8 @@ class VideoStabilizerFlowRolling(io.ComfyNode):
     @classmethod
     def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
                 strength: float, smooth: float, keep_fov: float, padding_color: str, readout: float = 0.0) -> io.NodeOutput:
-        context = hm._normalize_video_input(frames)
-        result = _stabilize_frames(
-            context, framing_mode, transform_mode, camera_lock, strength, smooth, keep_fov,
-            hm._parse_padding_color(padding_color), frame_rate, keep_on_device=True, estimator="flow",
-            rolling_shutter="auto" if float(readout) == 0.0 else float(readout),
-        )
-        return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
+        return _run_estimator_node("flow", frames, frame_rate, framing_mode, transform_mode, camera_lock, strength, smooth,
+                                   keep_fov, padding_color, rolling_shutter="auto" if float(readout) == 0.0 else float(readout))
 
 
 NODE_CLASSES = [VideoStabilizerClassic, VideoStabilizerFlow, VideoStabilizerMotionApply, VideoStabilizerShakeGenerator,
@@ -1065,97 +1033,50 @@ class VideoStabilizerAmdExtension(ComfyExtension):
         )
 
 
-class VideoStabilizerAmdMaskedExtension(VideoStabilizerAmdExtension):
-    """What comfy_entrypoint() hands to ComfyUI: the base extension's seven nodes plus Video Stabilizer Flow (Masked).  The
-    base class keeps its own list, so code that instantiates it sees what it saw before the masked node existed."""
+def _extend(base: type, *added_nodes: type, name: str, doc: str) -> type:
+    """A subclass of the extension `base` whose node list is base's plus `added_nodes`.  Every feature gets a class of its
+    own, so that the extensions before it keep the lists they had and code that instantiates one sees what it saw."""
 
     async def get_node_list(self) -> list:
-        return await super().get_node_list() + [VideoStabilizerFlowMasked]
+        return await base.get_node_list(self) + list(added_nodes)
+
+    return type(name, (base,), {"__doc__": doc, "__module__": __name__, "get_node_list": get_node_list})
 
 
-class VideoStabilizerAmdScenesExtension(VideoStabilizerAmdMaskedExtension):
-    """The masked extension's eight nodes plus Video Stabilizer Flow (Scene-Aware).  A class of its own for the reason the
-    masked one is: the extensions before it keep the lists they had."""
-
-    async def get_node_list(self) -> list:
-        return await super().get_node_list() + [VideoStabilizerFlowScenes]
-
-
-class VideoStabilizerAmdMeshExtension(VideoStabilizerAmdScenesExtension):
-    """The scene-aware extension's nine nodes plus Video Stabilizer Flow (Mesh).  A class of its own for the reason the two
-    before it are: the extensions before it keep the lists they had, and comfy_entrypoint() keeps handing out its own."""
-
-    async def get_node_list(self) -> list:
-        return await super().get_node_list() + [VideoStabilizerFlowMesh]
-
-
-class VideoStabilizerAmdMeshApplyExtension(VideoStabilizerAmdMeshExtension):
-    """The mesh extension's ten nodes plus the two of the mesh round trip: Video Stabilizer Flow (Mesh Motion) and Video
-    Stabilizer Motion Apply (Mesh).  A class of its own for the reason the three before it are."""
-
-    async def get_node_list(self) -> list:
-        return await super().get_node_list() + [VideoStabilizerFlowMeshMotion, VideoStabilizerMotionApplyMesh]
-
-
-class VideoStabilizerAmdFillExtension(VideoStabilizerAmdMeshApplyExtension):
-    """The mesh round trip extension's twelve nodes plus Video Stabilizer Padding Fill.  A class of its own for the reason
-    the four before it are."""
-
-    async def get_node_list(self) -> list:
-        return await super().get_node_list() + [VideoStabilizerPaddingFill]
-
-
-class VideoStabilizerAmdReportExtension(VideoStabilizerAmdFillExtension):
-    """The fill extension's thirteen nodes plus Video Stabilizer Stability Report.  A class of its own for the reason the
-    five before it are."""
-
-    async def get_node_list(self) -> list:
-        return await super().get_node_list() + [VideoStabilizerStabilityReport]
-
-
-class VideoStabilizerAmdZoomExtension(VideoStabilizerAmdReportExtension):
-    """The report extension's fourteen nodes plus Video Stabilizer Flow (Dynamic Zoom).  A class of its own for the reason
-    the six before it are."""
-
-    async def get_node_list(self) -> list:
-        return await super().get_node_list() + [VideoStabilizerFlowZoom]
-
-
-class VideoStabilizerAmdSubjectExtension(VideoStabilizerAmdZoomExtension):
-    """The zoom extension's fifteen nodes plus Video Stabilizer Flow (Subject Lock).  A class of its own for the reason
-    the seven before it are."""
-
-    async def get_node_list(self) -> list:
-        return await super().get_node_list() + [VideoStabilizerFlowSubject]
-
-
-class VideoStabilizerAmdFillBlendExtension(VideoStabilizerAmdSubjectExtension):
-    """The subject extension's sixteen nodes plus Video Stabilizer Temporal Fill (Blended).  A class of its own for the
-    reason the eight before it are: comfy_entrypoint() keeps handing out its own."""
-
-    async def get_node_list(self) -> list:
-        return await super().get_node_list() + [VideoStabilizerTemporalFillBlend]
-
-
-class VideoStabilizerAmdSharpnessExtension(VideoStabilizerAmdFillBlendExtension):
-    """The blended-fill extension's seventeen nodes plus Video Stabilizer Sharpness Transfer.  A class of its own for the
-    reason the nine before it are: comfy_entrypoint() keeps handing out its own."""
-
-    async def get_node_list(self) -> list:
-        return await super().get_node_list() + [VideoStabilizerSharpnessTransfer]
-
-
-class VideoStabilizerAmdHandoffExtension(VideoStabilizerAmdSharpnessExtension):
-    """The sharpness extension's eighteen nodes plus Video Stabilizer Mask Grow.  A class of its own for the reason the ten
-    before it are: comfy_entrypoint() keeps handing out its own."""
-
-    async def get_node_list(self) -> list:
-        return await super().get_node_list() + [VideoStabilizerMaskGrow]
-
-
-class VideoStabilizerAmdRollingExtension(VideoStabilizerAmdHandoffExtension):
-    """The hand-off extension's nineteen nodes plus Video Stabilizer Flow (Rolling Shutter).  A class of its own for the reason
-    the eleven before it are: comfy_entrypoint() keeps handing out its own."""
-
-    async def get_node_list(self) -> list:
-        return await super().get_node_list() + [VideoStabilizerFlowRolling]
+VideoStabilizerAmdMaskedExtension = _extend(
+    VideoStabilizerAmdExtension, VideoStabilizerFlowMasked, name="VideoStabilizerAmdMaskedExtension",
+    doc="What comfy_entrypoint() hands to ComfyUI: the base extension's seven nodes plus Video Stabilizer Flow (Masked).")
+VideoStabilizerAmdScenesExtension = _extend(
+    VideoStabilizerAmdMaskedExtension, VideoStabilizerFlowScenes, name="VideoStabilizerAmdScenesExtension",
+    doc="The masked extension's eight nodes plus Video Stabilizer Flow (Scene-Aware).")
+VideoStabilizerAmdMeshExtension = _extend(
+    VideoStabilizerAmdScenesExtension, VideoStabilizerFlowMesh, name="VideoStabilizerAmdMeshExtension",
+    doc="The scene-aware extension's nine nodes plus Video Stabilizer Flow (Mesh).")
+VideoStabilizerAmdMeshApplyExtension = _extend(
+    VideoStabilizerAmdMeshExtension, VideoStabilizerFlowMeshMotion, VideoStabilizerMotionApplyMesh,
+    name="VideoStabilizerAmdMeshApplyExtension",
+    doc="The mesh extension's ten nodes plus the two of the mesh round trip: Flow (Mesh Motion) and Motion Apply (Mesh).")
+VideoStabilizerAmdFillExtension = _extend(
+    VideoStabilizerAmdMeshApplyExtension, VideoStabilizerPaddingFill, name="VideoStabilizerAmdFillExtension",
+    doc="The mesh round trip extension's twelve nodes plus Video Stabilizer Padding Fill.")
+VideoStabilizerAmdReportExtension = _extend(
+    VideoStabilizerAmdFillExtension, VideoStabilizerStabilityReport, name="VideoStabilizerAmdReportExtension",
+    doc="The fill extension's thirteen nodes plus Video Stabilizer Stability Report.")
+VideoStabilizerAmdZoomExtension = _extend(
+    VideoStabilizerAmdReportExtension, VideoStabilizerFlowZoom, name="VideoStabilizerAmdZoomExtension",
+    doc="The report extension's fourteen nodes plus Video Stabilizer Flow (Dynamic Zoom).")
+VideoStabilizerAmdSubjectExtension = _extend(
+    VideoStabilizerAmdZoomExtension, VideoStabilizerFlowSubject, name="VideoStabilizerAmdSubjectExtension",
+    doc="The zoom extension's fifteen nodes plus Video Stabilizer Flow (Subject Lock).")
+VideoStabilizerAmdFillBlendExtension = _extend(
+    VideoStabilizerAmdSubjectExtension, VideoStabilizerTemporalFillBlend, name="VideoStabilizerAmdFillBlendExtension",
+    doc="The subject extension's sixteen nodes plus Video Stabilizer Temporal Fill (Blended).")
+VideoStabilizerAmdSharpnessExtension = _extend(
+    VideoStabilizerAmdFillBlendExtension, VideoStabilizerSharpnessTransfer, name="VideoStabilizerAmdSharpnessExtension",
+    doc="The blended-fill extension's seventeen nodes plus Video Stabilizer Sharpness Transfer.")
+VideoStabilizerAmdHandoffExtension = _extend(
+    VideoStabilizerAmdSharpnessExtension, VideoStabilizerMaskGrow, name="VideoStabilizerAmdHandoffExtension",
+    doc="The sharpness extension's eighteen nodes plus Video Stabilizer Mask Grow.")
+VideoStabilizerAmdRollingExtension = _extend(
+    VideoStabilizerAmdHandoffExtension, VideoStabilizerFlowRolling, name="VideoStabilizerAmdRollingExtension",
+    doc="The hand-off extension's nineteen nodes plus Video Stabilizer Flow (Rolling Shutter).")

@@ -379,3 +379,62 @@ def test_many_wrong_frames_are_rewarped_in_runs(ctx, pkg, monkeypatch):
     assert n == 6 and bool((dst == want.frames).all()) and bool((mask == want.masks[..., 0]).all())
     untouched = [i for i in range(12) if i not in wrong]
     assert bool((counts[untouched] == 0).all())
+
+
+# ---- the post-warp passes behind either plan path ---------------------------------------------------------------------------
+TAIL_W, TAIL_H, TAIL_N = 160, 96, 12        # the project's small shape (tests/test_spatial_fill_gpu.py)
+TAIL_ARGS = (True, 1.0, 0.5, 0.6, (127, 127, 127), 16.0)      # camera_lock + strength 1: the whole shake becomes padding
+TAIL_BLURRED = 5                            # an interior frame, box-blurred: the one the sharpness transfer has work on
+
+
+def full_tail_clip(device):
+    """12 frames of 160 x 96 under a similarity shake of up to +-4 px per frame, frame 5 blurred by a 5 x 5 box."""
+    import torch
+
+    frames = bench.synth_clip(TAIL_N, 0, TAIL_H, TAIL_W, device, mats=shake_path(TAIL_N, TAIL_W, TAIL_H, "similarity", seed=3, amp=8.0))
+    soft = torch.nn.functional.avg_pool2d(frames[TAIL_BLURRED].permute(2, 0, 1)[None], 5, stride=1, padding=2, count_include_pad=False)
+    frames[TAIL_BLURRED] = soft[0].permute(1, 2, 0)
+    return frames.contiguous()
+
+
+def full_tail_requests(device):
+    """Every post-warp pass at once, and an estimation mask (a small rectangle) so that meta block rides along too."""
+    import torch
+
+    exclude = torch.zeros((TAIL_H, TAIL_W), dtype=torch.float32, device=device)
+    exclude[30:50, 60:90] = 1.0
+    return dict(estimation_mask=exclude, sharpness_transfer=2, temporal_fill=2, fill_feather=4, fill_exposure=True, spatial_fill=True,
+                stability_report=True, mask_hold=1, mask_grow=2, mask_feather=2)
+
+
+@pytest.mark.parametrize("framing", ["crop_and_pad", "expand"])
+def test_post_warp_passes_are_the_same_with_and_without_the_device_plan(ctx, pkg, monkeypatch, framing):
+    """Sharpness transfer, temporal fill (feathered, exposure-matched), spatial fill, stability report and mask hand-off behind
+    the host plan and behind the device plan: same frames and masks in bits, same meta with its keys in the same order -- and
+    every pass had something to do, so the equality is not that of two runs that skipped them."""
+    import torch
+
+    from vstab_amd import flow_pipeline as fp
+    from vstab_amd import host_math as hm
+
+    frames = full_tail_clip(ctx.device)
+    runs = []
+    for device_plan in ("0", "1"):
+        monkeypatch.setenv("VSTAB_DEVICE_PLAN", device_plan)
+        runs.append(fp._stabilize_frames(hm._normalize_video_input(frames), framing, "similarity", *TAIL_ARGS, ctx=ctx,
+                                         keep_on_device=True, **full_tail_requests(ctx.device)))
+    a, b = runs
+    assert a.device_plan == {"used": False, "mismatched_frames": 0} and b.device_plan == {"used": True, "mismatched_frames": 0}
+    assert tuple(a.frames.shape) == tuple(b.frames.shape) and tuple(a.masks.shape) == tuple(b.masks.shape)
+    assert bool((a.frames.view(torch.int32) == b.frames.view(torch.int32)).all())
+    assert bool((a.masks.view(torch.int32) == b.masks.view(torch.int32)).all())
+    assert a.meta == b.meta and list(a.meta) == list(b.meta)
+    assert list(a.meta)[-6:] == ["estimation_mask", "sharpness_transfer", "temporal_fill", "spatial_fill", "stability", "mask_handoff"]
+    m = b.meta
+    print({"padding_fraction_mean": m["padding_fraction_mean"], "sharpness_transfer": {k: v for k, v in m["sharpness_transfer"].items() if k != "sharpness"},
+           "temporal_fill": m["temporal_fill"], "spatial_fill": m["spatial_fill"], "mask_handoff": m["mask_handoff"]})
+    assert m["sharpness_transfer"]["frames_sharpened"] >= 1 and m["sharpness_transfer"]["transferred_fraction_max"] > 0.0
+    assert m["temporal_fill"]["filled_fraction_mean"] > 0.0 and m["temporal_fill"]["blended_fraction_mean"] > 0.0
+    assert m["spatial_fill"]["filled_fraction_mean"] > 0.0
+    assert "gain_db" in m["stability"]
+    assert m["mask_handoff"]["masked_fraction_mean"] > m["padding_fraction_mean"] > 0.0
