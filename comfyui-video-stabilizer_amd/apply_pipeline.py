@@ -15,6 +15,7 @@ import numpy as np
 from . import host_math as hm
 from . import mask_handoff as mask_handoff_mod
 from . import mesh_warp as mesh_warp_mod
+from . import rolling_shutter as rolling_shutter_mod
 from . import spatial_fill as spatial_fill_mod
 from . import stability as stability_mod
 from . import native
@@ -129,6 +130,67 @@ def _mesh_warp(ctx, device_frames, matrices, output_size, padding_rgb, replay: M
     return dst, mask, unconverged_max
 
 
+@dataclass
+class RollingReplay:
+    """What apply_motion(rolling=True) hands to the warp: the recorded readout and per-frame velocities and the direction
+    they are applied in."""
+
+    direction: str          # "forward": the rolling warp itself; "inverse": its closed-form inverse (rolling_unwarp_batch)
+    readout: float          # 0: the run found the readout not observable and warped plainly; so does the replay
+    velocity: np.ndarray    # f64 [N,6]
+
+
+def _check_rolling_request(rolling, mesh: bool, framing_mode: str, interpolation: str, motion_blur: float) -> None:
+    """What rolling=True cannot be combined with, each with its reason; needs neither the meta nor a GPU."""
+    if not isinstance(rolling, bool):
+        raise ValueError(f"rolling={rolling!r}: expected True or False (the readout and the velocities come from "
+                         "meta['rolling_shutter'], not from the keyword)")
+    if not rolling:
+        return
+    if mesh:
+        raise ValueError("rolling=True is not supported with mesh=True: the warp takes one displacement, and a Flow run "
+                         "records either the mesh or the row correction, never both.")
+    if interpolation == "bicubic":
+        raise ValueError("rolling=True is not supported with bicubic interpolation: the rolling warp and its inverse exist for "
+                         "the bilinear sampler only.")
+    if float(np.clip(motion_blur, 0.0, 1.0)) > 0.0:
+        raise ValueError(f"rolling=True is not supported with motion_blur={motion_blur}: the blur samples are global matrices, "
+                         "which do not describe a row-corrected frame.")
+    if framing_mode == "crop":
+        raise ValueError("rolling=True is not supported with framing_mode 'crop': the common coverage is computed from matrices "
+                         "only, so it cannot keep a per-row displacement free of padding.")
+
+
+def _rolling_replay(meta, motion: MotionMeta, derived: bool, framing_mode: str) -> RollingReplay:
+    """The direction follows the block the call resolved, as for the mesh: motion_meta itself replays the rolling warp (the row
+    lever is the height of the block's input canvas), the inverse derived from stabilization_warp undoes it (the lever is the
+    height of the block's output canvas, the run's source)."""
+    if derived and framing_mode == "expand":
+        raise ValueError("rolling=True restores with framing_mode 'crop_and_pad' only: the row times belong to the rows of the "
+                         "original canvas, which 'expand' would replace by another.")
+    readout, velocity = rolling_shutter_mod.parse_block(meta, motion.frame_count)
+    return RollingReplay("inverse" if derived else "forward", readout, velocity)
+
+
+def _rolling_warp(ctx, device_frames, matrices, output_size, padding_rgb, replay: RollingReplay, progress_callback, first: int = 0):
+    """_warp's plain branch with the recorded row correction: -> (frames, masks [n,h,w], unsolved_max)."""
+    n = device_frames.shape[0]
+    check_interrupt()
+    m32 = np.stack([np.asarray(m, dtype=np.float32) for m in matrices[first:first + n]])
+    velocity = replay.velocity[first:first + n]
+    border = hm.border_value(padding_rgb)
+    unsolved_max = 0
+    if replay.direction == "forward":
+        dst, mask, _ = ctx.rolling_warp_batch(device_frames, m32, output_size, velocity, replay.readout, border=border,
+                                              want_mask=True, want_count=False)
+    else:
+        dst, mask, _, unsolved = ctx.rolling_unwarp_batch(device_frames, m32, output_size, velocity, replay.readout, border=border,
+                                                          want_mask=True, want_unsolved=True)
+        unsolved_max = int(unsolved.max().item()) if n else 0
+    _tick(progress_callback, n)
+    return dst, mask, unsolved_max
+
+
 def _tick(cb: Optional[ProgressCallback], times: int) -> None:
     if cb is not None:
         for _ in range(int(times)):
@@ -231,12 +293,15 @@ def _expand_matrices(matrices: List[np.ndarray], input_size: Tuple[int, int]):
 
 def apply_motion_on_device(ctx, device_frames, first: int, motion: MotionMeta, meta: Dict[str, Any], padding_rgb, *,
                            framing_mode: str, interpolation: str, motion_blur: float, motion_blur_samples: int,
-                           progress_callback: Optional[ProgressCallback] = None, mesh_replay: Optional[MeshReplay] = None):
+                           progress_callback: Optional[ProgressCallback] = None, mesh_replay: Optional[MeshReplay] = None,
+                           rolling_replay: Optional[RollingReplay] = None):
     """motion_apply.py:311-428 for frames [first, first + n) of the clip described by `motion` (already resolved and
     validated).  Everything that spans the clip -- the common coverage of `crop`, the bounding box of `expand`, the
     neighbour matrix of a blurred frame -- is a function of the replicated matrices alone, so a shard needs no
     exchange with other ranks.  Returns device tensors (frames [n,h,w,3], masks [n,h,w]) and the meta.
-    mesh_replay (apply_motion's mesh=True, already checked): the plain warp is replaced by the mesh warp or its inverse."""
+    mesh_replay (apply_motion's mesh=True, already checked): the plain warp is replaced by the mesh warp or its inverse.
+    rolling_replay (apply_motion's rolling=True, already checked): by the rolling warp or its inverse; a recorded readout of 0
+    keeps the plain warp."""
     matrices = [t.matrix for t in motion.per_frame]
     output_size = motion.output_size
     interpolation = _check_interpolation(interpolation)
@@ -249,7 +314,7 @@ def apply_motion_on_device(ctx, device_frames, first: int, motion: MotionMeta, m
         raise ValueError(f"Unsupported framing_mode {framing_mode!r}; expected 'crop_and_pad', 'crop', or 'expand'.")
 
     kw = dict(progress_callback=progress_callback, first=first)
-    unconverged_max = 0
+    unconverged_max = unsolved_max = 0
     if mesh_replay is not None:
         _check_mesh_request(requested, interpolation, motion_blur)
         if requested == "expand":
@@ -257,6 +322,17 @@ def apply_motion_on_device(ctx, device_frames, first: int, motion: MotionMeta, m
                 raise ValueError("mesh=True restores with framing_mode 'crop_and_pad' only.")
             matrices, output_size = _expand_matrices(matrices, motion.input_size)
         frames, masks, unconverged_max = _mesh_warp(ctx, device_frames, matrices, output_size, padding_rgb, mesh_replay, **kw)
+    elif rolling_replay is not None:
+        _check_rolling_request(True, False, requested, interpolation, motion_blur)
+        if requested == "expand":
+            if rolling_replay.direction != "forward":
+                raise ValueError("rolling=True restores with framing_mode 'crop_and_pad' only.")
+            matrices, output_size = _expand_matrices(matrices, motion.input_size)
+        if rolling_replay.readout == 0.0:      # "not_observable": the run itself warped plainly
+            frames, masks = _warp(ctx, device_frames, matrices, output_size, interpolation, padding_rgb, 0.0,
+                                  motion_blur_samples, masks_zero=False, **kw)
+        else:
+            frames, masks, unsolved_max = _rolling_warp(ctx, device_frames, matrices, output_size, padding_rgb, rolling_replay, **kw)
     elif requested == "crop_and_pad":
         frames, masks = _warp(ctx, device_frames, matrices, output_size, interpolation, padding_rgb, motion_blur,
                               motion_blur_samples, masks_zero=False, **kw)
@@ -288,6 +364,9 @@ def apply_motion_on_device(ctx, device_frames, first: int, motion: MotionMeta, m
     }
     if mesh_replay is not None:
         result_meta["motion_apply"]["mesh"] = {"direction": mesh_replay.direction, "unconverged_max": unconverged_max}
+    if rolling_replay is not None:
+        result_meta["motion_apply"]["rolling_shutter"] = {"direction": rolling_replay.direction, "readout": rolling_replay.readout,
+                                                          "unsolved_max": unsolved_max}
     return frames, masks, result_meta
 
 
@@ -310,6 +389,7 @@ def apply_motion(
     mask_feather=None,
     mask_hold=None,
     mask_tapered=None,
+    rolling: bool = False,
 ) -> MotionApplyResult:
     """Signature of the reference's apply_motion (motion_apply.py:297-307) plus GPU-context extras.
     mesh (beyond the reference, False by default): True replays the per-vertex offsets a mesh-warped Flow run recorded
@@ -331,7 +411,17 @@ def apply_motion(
     over neighbouring frames, GrowMask's dilation, an outward feather, as the last pass, behind the spatial fill and the
     stability report.  Only the returned mask changes; meta["motion_apply"]["mask_handoff"] describes it.  Allowed with
     motion_blur > 0: fractional masks are what a grey dilation is for.  `crop` framing has no mask: nothing is launched and
-    no block is added.  All None: the behaviour and meta without it, byte for byte."""
+    no block is added.  All None: the behaviour and meta without it, byte for byte.
+    rolling (beyond the reference, False by default): True replays the row correction of a Flow run with rolling_shutter= from
+    the readout and velocities it recorded (meta["rolling_shutter"]; rolling_shutter.parse_block), resolved as mesh=True is.  On
+    the run's source frames, or a companion clip of their size, the block is motion_meta and the rolling warp is applied again
+    (crop_and_pad or expand): Flow's frames and masks, bit for bit.  On its stabilized frames the block is the inverse of
+    stabilization_warp and the displacement is undone in closed form (rolling_unwarp_batch, crop_and_pad only; include/vstab.h
+    states the rule and where the pair is an exact inverse).  A recorded readout of 0 ("not_observable") takes the plain warp.
+    Bilinear, no motion blur, no crop framing, not with mesh=True; meta["motion_apply"]["rolling_shutter"] reports the
+    direction, the readout and the largest per-frame count of unsolved pixels.  False launches nothing new and leaves frames,
+    masks and meta as they were, byte for byte."""
+    _check_rolling_request(rolling, mesh, framing_mode, interpolation, motion_blur)     # before any GPU use, resident frames or not
     handoff = mask_handoff_mod.check_request(mask_grow, mask_feather, mask_hold, mask_tapered)
     spatial_fill = spatial_fill_mod.check_request(spatial_fill)
     stability_report = stability_mod.check_request(stability_report)
@@ -343,10 +433,10 @@ def apply_motion(
                          "of samples that missed the frame, so a marked pixel is partly padding colour already, which a 0/1 "
                          "hole test cannot undo.")
     requested_framing = "crop_and_pad" if framing_mode == "pad" else framing_mode
-    mesh_replay = None
+    mesh_replay = rolling_replay = None
 
     def checked_motion():
-        nonlocal mesh_replay
+        nonlocal mesh_replay, rolling_replay
         motion, derived = _resolve_motion_and_origin(meta, context)
         _validate_context(context, motion)
         _check_interpolation(interpolation)
@@ -354,6 +444,8 @@ def apply_motion(
             raise ValueError(f"Unsupported framing_mode {framing_mode!r}; expected 'crop_and_pad', 'crop', or 'expand'.")
         if mesh:
             mesh_replay = _mesh_replay(meta, motion, derived, requested_framing)
+        if rolling:
+            rolling_replay = _rolling_replay(meta, motion, derived, requested_framing)
         return motion
 
     if mesh:   # the refusals come before any GPU use, resident frames or not
@@ -363,7 +455,7 @@ def apply_motion(
     # launched BEFORE the meta is parsed and validated (0.4 ms of host work for 256 frames, during which the GPU had nothing to
     # do: tools/chain_timeline.py).  Host frames: validation first -- a bad meta must not cost an upload.
     resident = context.batch is not None and getattr(context.batch, "device", None) is not None and context.batch.device.type == "cuda"
-    motion = None if (resident and not mesh) else checked_motion()
+    motion = None if (resident and not mesh and not rolling) else checked_motion()
     ctx = ctx or native.default_context()
     device_frames = context.device_batch(ctx)
     kw = dict(framing_mode=framing_mode, interpolation=interpolation, motion_blur=motion_blur, motion_blur_samples=motion_blur_samples)
@@ -383,7 +475,7 @@ def apply_motion(
             if motion is None:
                 motion = checked_motion()
             frames, masks, result_meta = apply_motion_on_device(ctx, device_frames, 0, motion, meta, padding_rgb,
-                                                                progress_callback=progress_callback, mesh_replay=mesh_replay, **kw)
+                                                                progress_callback=progress_callback, mesh_replay=mesh_replay, rolling_replay=rolling_replay, **kw)
         finally:
             # also when the validation or the warp raised (a bad meta, VstabError, a cancel delivered by a progress tick): the
             # maxima pass still reads the frames, and the caller is free to drop them as soon as this frame unwinds
@@ -392,12 +484,12 @@ def apply_motion(
             check_interrupt()
             device_frames = context.device_batch(ctx)
             frames, masks, result_meta = apply_motion_on_device(ctx, device_frames, 0, motion, meta, padding_rgb,
-                                                                progress_callback=None, mesh_replay=mesh_replay, **kw)
+                                                                progress_callback=None, mesh_replay=mesh_replay, rolling_replay=rolling_replay, **kw)
     else:
         if motion is None:
             motion = checked_motion()
         frames, masks, result_meta = apply_motion_on_device(ctx, device_frames, 0, motion, meta, padding_rgb,
-                                                            progress_callback=progress_callback, mesh_replay=mesh_replay, **kw)
+                                                            progress_callback=progress_callback, mesh_replay=mesh_replay, rolling_replay=rolling_replay, **kw)
     if spatial_fill and result_meta["motion_apply"]["framing_mode"] != "crop":
         result_meta["motion_apply"]["spatial_fill"] = spatial_fill_mod.fill_on_device(ctx, frames, masks)
     if stability_report:

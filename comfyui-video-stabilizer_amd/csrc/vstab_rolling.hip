@@ -1,12 +1,14 @@
-// vstab_rolling.hip -- rolling shutter: the per-row readout correction of the final warp (vstab_rolling_warp_batch) and the
-// per-row median of the global fit's residual that the readout estimate is made from (vstab_row_residual_batch).  Not a
-// reference feature; both rules are stated in include/vstab.h.  profiles/warp_traffic.json is tied to vstab_warp.hip +
-// vstab_internal.h: an edit here leaves it valid.
+// vstab_rolling.hip -- rolling shutter: the per-row readout correction of the final warp (vstab_rolling_warp_batch), its
+// closed-form inverse (vstab_rolling_unwarp_batch) and the per-row median of the global fit's residual that the readout
+// estimate is made from (vstab_row_residual_batch).  Not a reference feature; the rules are stated in include/vstab.h.
+// profiles/warp_traffic.json is tied to vstab_warp.hip + vstab_internal.h: an edit here leaves it valid.
 //
 // rolling_warp_kernel: the plain warp's 64 x 8 tile (TileShell, XCD remap, block_count_add) around warp_pixel with a
 // displacement of the source position that is a closed form of the frame's six velocity coefficients and the readout -- seven
 // uniform doubles, so there is no table and no LDS beyond the count reduction's; what it adds to the plain warp is ~20 fp64
-// operations per pixel (two of them divisions) under the same HBM stream.
+// operations per pixel (two of them divisions) under the same HBM stream.  Its inverse is the same kernel template with
+// RowInverseDisplacement, warp_pixel's OUTPUT kind: a 2x2 solve at the output pixel whose row terms (tau, the matrix, its
+// determinant) are the same for a thread's two pixels: one division per thread for the row, two per pixel by the determinant.
 // row_residual_kernel: one workgroup per (pair, grid row); the row's admitted residuals are compacted into LDS (order does
 // not matter to a median) and ranked by counting, as vstab_mesh.hip does per vertex.  A row of a 960-px estimation image has
 // 120 samples: microseconds per clip.
@@ -46,11 +48,38 @@ struct RowDisplacement {
     }
 };
 
+// The inverse (the rule: vstab_rolling_unwarp_batch in include/vstab.h): the forward warp sampled its source at
+// s = q + tau(s_y) v(q); restoring, the output pixel IS s, so tau is known from the output row and q solves
+// (I + tau L) q = s - tau t.  e = q - s moves the output pixel in front of the matrix (warp_pixel's OUTPUT kind).  tau, a..d
+// and det depend on the row only: a thread's pixels share them.
+struct RowInverseDisplacement {
+    static constexpr bool ACTIVE = true;
+    static constexpr bool OUTPUT = true;
+    double v0, v1, v2, v3, v4, v5;   // the frame's velocity V, px per frame interval
+    double rho, hm1;                 // readout; out_h - 1
+    // -> solved; (ex, ey) = q - s, (0, 0) if not solved
+    __device__ __forceinline__ bool solve(int x, int y, double& ex, double& ey) const
+    {
+        const double xd = (double)x, yd = (double)y;
+        const double tau = rho * (yd / hm1 - 0.5);
+        const double a = 1.0 + tau * v0, b = tau * v1, c = tau * v3, d = 1.0 + tau * v4;
+        const double det = a * d - b * c;
+        const double vx = (v0 * xd + v1 * yd) + v2;
+        const double vy = (v3 * xd + v4 * yd) + v5;
+        const double rx = tau * vx, ry = tau * vy;
+        ex = -((d * rx - b * ry) / det);
+        ey = -((a * ry - c * rx) / det);
+        if (!(det >= VSTAB_ROLLING_UNWARP_MIN_DET) || !(finite_d(ex) && finite_d(ey))) { ex = 0.0; ey = 0.0; return false; }   // also a NaN
+        return true;
+    }
+};
+
 struct RollingWarpArgs {
     const float* src;
     float* dst;
     float* mask;
     unsigned* pad_count;
+    unsigned* unsolved;       // [n] or nullptr; the inverse only
     const WarpXform* xf;
     const double* velocity;   // [n, 6]
     double readout;
@@ -60,21 +89,24 @@ struct RollingWarpArgs {
     float b0, b1, b2;         // border colour
 };
 
-// One 64 x 8 tile: the plain warp's kernel body (vstab_warp.hip: warp_kernel) with RowDisplacement.
-template <int SUBPIX, bool WITH_MASK>
+// One 64 x 8 tile: the plain warp's kernel body (vstab_warp.hip: warp_kernel) with Disp = RowDisplacement (the forward warp;
+// its row lever is the SOURCE's height) or RowInverseDisplacement (the inverse; the OUTPUT's height, which is the forward
+// warp's source).
+template <int SUBPIX, bool WITH_MASK, class Disp>
 __global__ __launch_bounds__(256) void rolling_warp_kernel(RollingWarpArgs a)
 {
     constexpr int INTERP = VSTAB_INTERP_BILINEAR;
     const TileShell<ROLL_TILE_TX> t(a.tiles_x, a.tiles_y, a.dh, a.dw);
     const int frame = t.frame, x0 = t.x0, y = t.y, npx = t.npx;
     const double* __restrict__ V = a.velocity + (size_t)frame * 6;      // block-uniform
-    const RowDisplacement disp{V[0], V[1], V[2], V[3], V[4], V[5], a.readout, (double)(a.sh - 1)};
+    const Disp disp{V[0], V[1], V[2], V[3], V[4], V[5], a.readout, (double)((Disp::OUTPUT ? a.dh : a.sh) - 1)};
     const float* __restrict__ S = a.src + (size_t)frame * a.sh * a.sw * 3;
 
     float acc[TILE_PX][3];
     float cov[TILE_PX];
 #pragma unroll
     for (int p = 0; p < TILE_PX; p++) { acc[p][0] = acc[p][1] = acc[p][2] = 0.f; cov[p] = 0.f; }
+    unsigned unsolved = 0;    // the inverse only: this thread's pixels whose solve was refused
 
     if (t.active) {
         const double dy = (double)y;
@@ -88,7 +120,7 @@ __global__ __launch_bounds__(256) void rolling_warp_kernel(RollingWarpArgs a)
             const Px v = warp_pixel<INTERP, SUBPIX, WITH_MASK>(
                 xf, r, a.sh, a.sw, a.dw, a.bw0, a.bw0_pow2, x, y, dy,
                 [&](int X, int Y) { return sample_q5<INTERP>(S, a.sh, a.sw, X, Y, a.b0, a.b1, a.b2, nullptr); },
-                [&](float fsx, float fsy) { return sample_exact(S, a.sh, a.sw, fsx, fsy, a.b0, a.b1, a.b2); }, disp, c);
+                [&](float fsx, float fsy) { return sample_exact(S, a.sh, a.sw, fsx, fsy, a.b0, a.b1, a.b2); }, disp, c, &unsolved);
             acc[p][0] = v.r; acc[p][1] = v.g; acc[p][2] = v.b;
             if (WITH_MASK) cov[p] = c;
         }
@@ -119,7 +151,15 @@ __global__ __launch_bounds__(256) void rolling_warp_kernel(RollingWarpArgs a)
         }
     }
 
-    if (WITH_MASK && a.pad_count != nullptr) block_count_add<1>(padded, {a.pad_count}, frame);
+    if constexpr (Disp::OUTPUT) {
+        // two counters through one reduction (the conditions are kernel arguments: uniform)
+        if ((WITH_MASK && a.pad_count != nullptr) || a.unsolved != nullptr) {
+            unsigned counts[2] = {padded[0], unsolved};
+            block_count_add<2>(counts, {WITH_MASK ? a.pad_count : nullptr, a.unsolved}, frame);
+        }
+    } else {
+        if (WITH_MASK && a.pad_count != nullptr) block_count_add<1>(padded, {a.pad_count}, frame);
+    }
 }
 
 struct RowResidualArgs {
@@ -196,16 +236,29 @@ __global__ __launch_bounds__(ROW_THREADS) void row_residual_kernel(RowResidualAr
     }
 }
 
-}  // namespace
-
-extern "C" int vstab_rolling_warp_batch(vstab_ctx* ctx, const float* src, int n, int src_h, int src_w, const float* matrices,
-                                        int out_h, int out_w, const float* border_rgb, int subpix, const double* velocity,
-                                        double readout, float* dst, float* mask, uint32_t* pad_count)
+template <class Disp>
+void launch_rolling(const RollingWarpArgs& a, unsigned blocks, int subpix, hipStream_t stream)
 {
-    const char* who = "vstab_rolling_warp_batch";
+    const dim3 grid(blocks), block(256);
+    if (subpix == VSTAB_SUBPIX_EXACT) {
+        if (a.mask) hipLaunchKernelGGL((rolling_warp_kernel<VSTAB_SUBPIX_EXACT, true, Disp>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((rolling_warp_kernel<VSTAB_SUBPIX_EXACT, false, Disp>), grid, block, 0, stream, a);
+    } else {
+        if (a.mask) hipLaunchKernelGGL((rolling_warp_kernel<VSTAB_SUBPIX_Q5, true, Disp>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((rolling_warp_kernel<VSTAB_SUBPIX_Q5, false, Disp>), grid, block, 0, stream, a);
+    }
+}
+
+// Both directions: the checks, the staged table and the launch.  inverse: the row lever is the output's height, `unsolved` is
+// zeroed and counted.
+int rolling_batch(const char* who, bool inverse, vstab_ctx* ctx, const float* src, int n, int src_h, int src_w, const float* matrices,
+                  int out_h, int out_w, const float* border_rgb, int subpix, const double* velocity, double readout, float* dst,
+                  float* mask, uint32_t* pad_count, uint32_t* unsolved)
+{
     if (int rc = vstab_check_common(who, ctx, src, n, src_h, src_w, matrices, out_h, out_w, VSTAB_INTERP_BILINEAR, border_rgb, subpix, dst)) return rc;
     VSTAB_REQUIRE(velocity != nullptr, "%s: NULL pointer argument", who);
-    VSTAB_REQUIRE(src_h >= 2, "%s: bad size (n=%d src=%dx%d out=%dx%d; the source must have at least 2 rows)", who, n, src_w, src_h, out_w, out_h);
+    if (inverse) VSTAB_REQUIRE(out_h >= 2, "%s: bad size (n=%d src=%dx%d out=%dx%d; the output must have at least 2 rows)", who, n, src_w, src_h, out_w, out_h);
+    else VSTAB_REQUIRE(src_h >= 2, "%s: bad size (n=%d src=%dx%d out=%dx%d; the source must have at least 2 rows)", who, n, src_w, src_h, out_w, out_h);
     VSTAB_REQUIRE(readout >= -1.0 && readout <= 1.0, "%s: readout=%g outside [-1, 1] (a fraction of the frame interval)", who, readout);
     VSTAB_HIP(hipSetDevice(ctx->device));
     // one staged table (the staging buffer holds one table per call): n transform records, then n x 6 velocity coefficients
@@ -217,7 +270,7 @@ extern "C" int vstab_rolling_warp_batch(vstab_ctx* ctx, const float* src, int n,
     void* d_table = nullptr;
     if (int rc = vstab_stage_params(ctx, table.data(), table.size(), &d_table)) return rc;
     RollingWarpArgs a{};
-    a.src = src; a.dst = dst; a.mask = mask; a.pad_count = pad_count;
+    a.src = src; a.dst = dst; a.mask = mask; a.pad_count = pad_count; a.unsolved = unsolved;
     a.xf = static_cast<const WarpXform*>(d_table);
     a.velocity = reinterpret_cast<const double*>(static_cast<const unsigned char*>(d_table) + xf_bytes);
     a.readout = readout;
@@ -227,17 +280,30 @@ extern "C" int vstab_rolling_warp_batch(vstab_ctx* ctx, const float* src, int n,
     unsigned blocks = 0;
     if (int rc = vstab_tile_grid(who, n, out_h, out_w, ROLL_TILE_TX, 256, &a.tiles_x, &a.tiles_y, &blocks)) return rc;
     if (pad_count) VSTAB_HIP(hipMemsetAsync(pad_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
-    const dim3 grid(blocks), block(256);
-    KernelTimer timer(ctx, "rolling_warp");
-    if (subpix == VSTAB_SUBPIX_EXACT) {
-        if (mask) hipLaunchKernelGGL((rolling_warp_kernel<VSTAB_SUBPIX_EXACT, true>), grid, block, 0, ctx->stream, a);
-        else hipLaunchKernelGGL((rolling_warp_kernel<VSTAB_SUBPIX_EXACT, false>), grid, block, 0, ctx->stream, a);
-    } else {
-        if (mask) hipLaunchKernelGGL((rolling_warp_kernel<VSTAB_SUBPIX_Q5, true>), grid, block, 0, ctx->stream, a);
-        else hipLaunchKernelGGL((rolling_warp_kernel<VSTAB_SUBPIX_Q5, false>), grid, block, 0, ctx->stream, a);
-    }
+    if (unsolved) VSTAB_HIP(hipMemsetAsync(unsolved, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
+    KernelTimer timer(ctx, inverse ? "rolling_unwarp" : "rolling_warp");
+    if (inverse) launch_rolling<RowInverseDisplacement>(a, blocks, subpix, ctx->stream);
+    else launch_rolling<RowDisplacement>(a, blocks, subpix, ctx->stream);
     VSTAB_HIP(hipGetLastError());
     return 0;
+}
+
+}  // namespace
+
+extern "C" int vstab_rolling_warp_batch(vstab_ctx* ctx, const float* src, int n, int src_h, int src_w, const float* matrices,
+                                        int out_h, int out_w, const float* border_rgb, int subpix, const double* velocity,
+                                        double readout, float* dst, float* mask, uint32_t* pad_count)
+{
+    return rolling_batch("vstab_rolling_warp_batch", false, ctx, src, n, src_h, src_w, matrices, out_h, out_w, border_rgb, subpix,
+                         velocity, readout, dst, mask, pad_count, nullptr);
+}
+
+extern "C" int vstab_rolling_unwarp_batch(vstab_ctx* ctx, const float* src, int n, int src_h, int src_w, const float* matrices,
+                                          int out_h, int out_w, const float* border_rgb, int subpix, const double* velocity,
+                                          double readout, float* dst, float* mask, uint32_t* pad_count, uint32_t* unsolved)
+{
+    return rolling_batch("vstab_rolling_unwarp_batch", true, ctx, src, n, src_h, src_w, matrices, out_h, out_w, border_rgb, subpix,
+                         velocity, readout, dst, mask, pad_count, unsolved);
 }
 
 extern "C" int vstab_row_residual_batch(vstab_ctx* ctx, const float* grid_flow, int pairs, int gh, int gw, int step, int work_h,

@@ -521,15 +521,21 @@ def _stabilize_sharded_device_plan(ctx, local_frames, total_frames, start, n_loc
 
 def apply_motion_sharded(ctx, local_frames, start: int, total_frames: int, meta: Dict[str, Any], padding_rgb, *,
                          framing_mode: str = "crop_and_pad", interpolation: str = "bilinear", motion_blur: float = 0.0,
-                         motion_blur_samples: int = 9, progress_callback=None):
+                         motion_blur_samples: int = 9, progress_callback=None, rolling: bool = False):
     """Sharded `apply_motion` (motion_apply.py:297-429): this rank replays frames [start, start + n_local) of a clip of
     `total_frames` frames whose motion is described by the replicated `meta`.  No collective, no halo frame.
+    rolling: apply_motion's keyword of that name; True is refused here (before any GPU work), False is the call without it.
 
     local_frames: device tensor [n_local, H, W, 3] float32 (may be empty).  Returns (frames [n_local,h,w,3], masks
     [n_local,h,w], result_meta) on this rank's GPU; result_meta is identical on all ranks.  The validation errors of
     the reference (size mismatch, frame-count mismatch against the metadata, bad enums) are raised on every rank alike."""
     from .apply_pipeline import _resolve_motion_for_context, _validate_context, apply_motion_on_device
 
+    if not isinstance(rolling, bool):
+        raise ValueError(f"rolling={rolling!r}: expected True or False")
+    if rolling:
+        raise ValueError("apply_motion_sharded does not support rolling=True: the rolling-shutter replay is not sharded; "
+                         "run apply_motion on one GPU.")
     n_local = int(local_frames.shape[0])
     height, width = int(local_frames.shape[1]), int(local_frames.shape[2])
     if start < 0 or start + n_local > total_frames:

@@ -188,6 +188,9 @@ _SIGNATURES = {
     "vstab_rolling_warp_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                   C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vstab_rolling_unwarp_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                  C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vstab_row_residual_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                   C.c_void_p, C.c_void_p]),
@@ -832,12 +835,7 @@ class Context:
         readout == 0 give warp_batch's bits."""
         src, (n, sh, sw), (out_h, out_w), b, dst, mask, counts = self._warp_io(
             "rolling_warp_batch", frames, out_size, border, want_mask, want_count)
-        v = np.ascontiguousarray(velocity, dtype=np.float64)
-        if v.size != n * 6:
-            raise ValueError(f"rolling_warp_batch: velocity {v.shape} is not [{n},6]")
-        readout = float(readout)
-        if not -1.0 <= readout <= 1.0:       # (a NaN fails it too)
-            raise ValueError(f"rolling_warp_batch: readout={readout!r} outside [-1, 1]")
+        v, readout = self._rolling_inputs("rolling_warp_batch", velocity, readout, n)
         m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(n, 9)
         self.use_torch_stream()
         _check(self.lib.vstab_rolling_warp_batch(
@@ -845,6 +843,38 @@ class Context:
             v.ctypes.data, readout, _dev_ptr(dst), _dev_ptr(mask) if mask is not None else None,
             _dev_ptr(counts) if counts is not None else None), "vstab_rolling_warp_batch")
         return dst, mask, counts
+
+    @staticmethod
+    def _rolling_inputs(who, velocity, readout, n, null_ok=False):
+        """velocity -> contiguous f64 of n * 6 values (None with null_ok: None, a NULL pointer for the library to refuse),
+        readout -> float in [-1, 1]."""
+        v = None if (velocity is None and null_ok) else np.ascontiguousarray(velocity, dtype=np.float64)
+        if v is not None and v.size != n * 6:
+            raise ValueError(f"{who}: velocity {v.shape} is not [{n},6]")
+        readout = float(readout)
+        if not -1.0 <= readout <= 1.0:       # (a NaN fails it too)
+            raise ValueError(f"{who}: readout={readout!r} outside [-1, 1]")
+        return v, readout
+
+    def rolling_unwarp_batch(self, frames, matrices, out_size, velocity, readout, border=(0.0, 0.0, 0.0), subpix=None,
+                             want_mask=True, want_count=False, want_unsolved=False):
+        """The inverse of rolling_warp_batch's displacement (vstab_rolling_unwarp_batch; the rule is in include/vstab.h):
+        warp_batch (bilinear) whose output pixel is moved by the closed-form inverse of the row displacement in front of the
+        matrix.  velocity f64 [N,6] (host) and readout as rolling_warp_batch's; the row lever is the OUTPUT canvas's height ->
+        (dst [N,h,w,3], mask [N,h,w] | None, counts [N] | None, unsolved [N] i32 | None: pixels per frame whose solve was
+        refused and that were warped by the matrix alone).  All-zero velocity or readout == 0 give warp_batch's bits."""
+        src, (n, sh, sw), (out_h, out_w), b, dst, mask, counts = self._warp_io(
+            "rolling_unwarp_batch", frames, out_size, border, want_mask, want_count)
+        v, readout = self._rolling_inputs("rolling_unwarp_batch", velocity, readout, n, null_ok=True)
+        unsolved = self.torch.empty((n,), dtype=self.torch.int32, device=self.device) if want_unsolved else None
+        m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(n, 9)
+        self.use_torch_stream()
+        _check(self.lib.vstab_rolling_unwarp_batch(
+            self.handle, _dev_ptr(src), n, sh, sw, m.ctypes.data, out_h, out_w, b.ctypes.data, SUBPIX[subpix or DEFAULT_SUBPIX],
+            v.ctypes.data if v is not None else None, readout, _dev_ptr(dst), _dev_ptr(mask) if mask is not None else None,
+            _dev_ptr(counts) if counts is not None else None,
+            _dev_ptr(unsolved) if unsolved is not None else None), "vstab_rolling_unwarp_batch")
+        return dst, mask, counts, unsolved
 
     def row_residual_batch(self, grid_flow, step, work_size, transitions, blocked=None):
         """Per-row median of the global fit's residual (vstab_row_residual_batch; the rule is in include/vstab.h).

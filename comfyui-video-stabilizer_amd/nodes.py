@@ -947,6 +947,44 @@ class VideoStabilizerFlowRolling(io.ComfyNode):
                                    keep_fov, padding_color, rolling_shutter="auto" if float(readout) == 0.0 else float(readout))
 
 
+class VideoStabilizerMotionApplyRolling(io.ComfyNode):
+    """Motion Apply for a rolling-shutter run (apply_motion's rolling=True): on the run's source frames (or a companion clip
+    of their size) it applies the recorded matrices and row correction again, on its stabilized frames it restores the
+    original camera motion and skew through the rolling warp's closed-form inverse.  Bilinear, no motion blur.  Not one of the
+    reference's nodes: it is listed by an extension but kept out of NODE_CLASSES."""
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        schema = io.Schema(
+            node_id="video_stabilizer_motion_apply_rolling",
+            display_name="Video Stabilizer Motion Apply (Rolling Shutter)",
+            category="Video/Stabilization",
+            description=("Applies or undoes the motion of a Video Stabilizer Flow (Rolling Shutter) run, per-row readout "
+                         "correction included, and emits a padding mask."),
+        )
+        schema.inputs = [
+            io.Image.Input("frames", display_name="Frames"),
+            JSONType.Input("meta", display_name="Meta"),
+            io.Combo.Input("framing_mode", options=["crop_and_pad", "expand"], default="crop_and_pad",
+                           display_name="Framing Mode"),
+            io.Color.Input("padding_color", default="#7F7F7F", display_name="Padding Color",
+                           tooltip="HEX padding color used where warping exposes empty pixels."),
+        ]
+        schema.outputs = [
+            io.Image.Output("frames", display_name="Frames"),
+            io.Mask.Output("padding_mask", display_name="Padding Mask"),
+            JSONType.Output("meta", display_name="Meta"),
+        ]
+        return schema
+
+    @classmethod
+    def execute(cls, frames: Any, meta: dict, framing_mode: str, padding_color: str) -> io.NodeOutput:
+        context = hm._normalize_video_input(frames)
+        result = apply_motion(context, meta, hm._parse_padding_color(padding_color), framing_mode=framing_mode,
+                              interpolation="bilinear", keep_on_device=True, rolling=True)
+        return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
+
+
 NODE_CLASSES = [VideoStabilizerClassic, VideoStabilizerFlow, VideoStabilizerMotionApply, VideoStabilizerShakeGenerator,
                 VideoStabilizerShakeGeneratorManual, VideoStabilizerInverse]
 
@@ -1080,3 +1118,6 @@ VideoStabilizerAmdHandoffExtension = _extend(
 VideoStabilizerAmdRollingExtension = _extend(
     VideoStabilizerAmdHandoffExtension, VideoStabilizerFlowRolling, name="VideoStabilizerAmdRollingExtension",
     doc="The hand-off extension's nineteen nodes plus Video Stabilizer Flow (Rolling Shutter).")
+VideoStabilizerAmdRollingApplyExtension = _extend(
+    VideoStabilizerAmdRollingExtension, VideoStabilizerMotionApplyRolling, name="VideoStabilizerAmdRollingApplyExtension",
+    doc="The rolling-shutter extension's twenty nodes plus Video Stabilizer Motion Apply (Rolling Shutter).")

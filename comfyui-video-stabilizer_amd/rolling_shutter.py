@@ -16,8 +16,11 @@ grid row and pair (include/vstab.h states both rules).  This module is the host 
 velocities from the transitions, the least-squares estimate of the one physical unknown rho from the row residuals, and the
 meta block.  All float64, pure functions; nothing here needs a GPU.
 
-Out of scope: Motion Apply replay and the inverse (closed-form, because tau is known from the output row; the meta carries
-what it needs), perspective mode, `crop` framing and dynamic zoom, the mesh, temporal-fill, sharpness-transfer, subject and
+The round trip: `parse_block` reads the block back for Motion Apply (`apply_motion(rolling=True)`), which applies the row
+correction again on the run's source frames (`rolling_warp_batch`) or undoes it on the stabilized ones
+(`native.Context.rolling_unwarp_batch`, the closed-form inverse: tau is known from the output row).
+
+Out of scope: perspective mode, `crop` framing and dynamic zoom, the mesh, temporal-fill, sharpness-transfer, subject and
 sharded paths, bicubic and motion-blur warps, a per-row homography mixture, readout tables per camera model.
 """
 
@@ -226,3 +229,28 @@ def meta_block(readout: float, source: str, estimate: Optional[Dict[str, Any]], 
         "skew_px_max": float(skew.max()) if skew.size else 0.0,
         "velocity": V.tolist(),
     }
+
+
+def parse_block(meta, frame_count: int):
+    """meta["rolling_shutter"] as meta_block wrote it (possibly through JSON) -> (readout, velocity f64 [frame_count,6]): what
+    Motion Apply needs to apply the row correction again or to undo it.  A ValueError names the key or shape that is wrong."""
+    block = meta.get("rolling_shutter") if isinstance(meta, dict) else None
+    if not isinstance(block, dict):
+        raise ValueError("rolling=True needs meta['rolling_shutter'], the block a Flow run with rolling_shutter= writes; "
+                         "this meta has none.")
+    if block.get("version") != VERSION or isinstance(block.get("version"), bool):
+        raise ValueError(f"meta['rolling_shutter']['version'] is {block.get('version')!r}, expected {VERSION}")
+    readout = block.get("readout")
+    if not _is_number(readout) or not -1.0 <= float(readout) <= 1.0:        # (a NaN fails it too)
+        raise ValueError(f"meta['rolling_shutter']['readout'] is {readout!r}, expected a number in [-1, 1]")
+    n = int(frame_count)
+    try:
+        V = np.asarray(block.get("velocity"), dtype=np.float64)
+    except (TypeError, ValueError):
+        V = None
+    if V is not None and n == 0 and V.size == 0:
+        V = V.reshape(0, 6)                    # an empty clip's [] has lost its second axis
+    if V is None or V.shape != (n, 6) or not np.isfinite(V).all():
+        shape = "not an array of numbers" if V is None else f"of shape {list(V.shape)}"
+        raise ValueError(f"meta['rolling_shutter']['velocity'] is {shape}; expected [{n}][6] finite numbers, one row per frame")
+    return float(readout), np.ascontiguousarray(V)

@@ -630,6 +630,33 @@ int vstab_mesh_unwarp_batch(vstab_ctx* ctx, const float* src, int n, int src_h, 
  * error texts under this function's name).  Kernel (vstab_rolling.hip): the plain warp's 64 x 8 tile and XCD remap; the
  * frame's coefficients and the readout are uniform, there is no table in LDS.  Timing kind "rolling_warp".
  *
+ * vstab_rolling_unwarp_batch -- the inverse of vstab_rolling_warp_batch's displacement: vstab_warp_batch (bilinear) whose OUTPUT
+ * pixel is moved in front of the frame's matrix, vstab_mesh_unwarp_batch's rule with a closed form in place of the fixed point.
+ * The forward warp sampled its source at s = q + tau(s_y) * v(q).  Restoring, the output pixel is s itself, so tau is known
+ * from the output row, and with v(q) = L q + t the equation (I + tau*L) q = s - tau*t is a 2x2 solve:
+ * e = q - s = -tau * (I + tau*L)^-1 * v(s).  With (x, y) the output pixel as fp64 integers, hm1 = out_h - 1, V = the frame's
+ * six coefficients and rho = readout -- every operation IEEE fp64 and rounded on its own, nothing fused:
+ *   - tau = rho * (y / hm1 - 0.5)
+ *   - a = 1 + tau*V0, b = tau*V1, c = tau*V3, d = 1 + tau*V4;  det = a*d - b*c
+ *   - vx = (V0*x + V1*y) + V2, vy = (V3*x + V4*y) + V5;  rx = tau*vx, ry = tau*vy
+ *   - e.x = -((d*rx - b*ry) / det), e.y = -((a*ry - c*rx) / det)
+ *   - if det >= VSTAB_ROLLING_UNWARP_MIN_DET does not hold (a NaN included) or e.x or e.y is not finite, e = (0, 0) and the
+ *     pixel is UNSOLVED: it is warped by the matrix alone.  0.25 is a choice, not a calibration, the counterpart of the
+ *     forward warp's D >= 0.5: a row whose (I + tau*L) has lost three quarters of its area is one the forward warp folded.
+ *   - e enters Xn, Yn, W and the float32 chain exactly as vstab_mesh_unwarp_batch's e does (e == 0, zeros of either sign: nothing
+ *     is added), and everything behind them is vstab_warp_batch's.
+ * Invariant: all-zero velocity or readout == 0 give dst, mask and pad_count bit-identical to vstab_warp_batch and unsolved == 0
+ * (tau*v is a zero of either sign, and so is e).
+ * Region of validity: the pair is an exact inverse (up to the roundings of two samplings) only where neither of the forward
+ * warp's two clamps binds -- D >= 0.5, and q_y inside [0, H-1].  Where the forward warp clamped, it did not sample at
+ * s = q + tau(s_y) v(q), and this function undoes a displacement that was not applied.  The lever of the forward warp is its
+ * SOURCE's height; here it is the OUTPUT's: the canvas being restored.
+ *   velocity host [n, 6] f64, readout in [-1, 1]: as for vstab_rolling_warp_batch;  out_h >= 2
+ *   unsolved dev [n] u32 or NULL: unsolved pixels per frame, zeroed by the call as pad_count is.
+ * The other arguments are vstab_rolling_warp_batch's and are checked as it checks them (same error texts under this function's
+ * name; the 2-row minimum applies to the output).  The same kernel template as the forward warp with another displacement
+ * functor; tau, a..d and det depend on the row only and are shared by a thread's pixels.  Timing kind "rolling_unwarp".
+ *
  * vstab_row_residual_batch -- what the readout is estimated from: per pair i and grid row gy, the per-axis median of the
  * global fit's residual over the row's admitted samples.  A rolling shutter leaves a residual that is linear in the row.
  *   - the residual r of grid sample (gx, gy) at (x, y) = (gx*step, gy*step) is vstab_mesh_residual_batch's, unchanged:
@@ -648,6 +675,10 @@ int vstab_mesh_unwarp_batch(vstab_ctx* ctx, const float* src, int n, int src_h, 
 int vstab_rolling_warp_batch(vstab_ctx* ctx, const float* src, int n, int src_h, int src_w, const float* matrices,
                              int out_h, int out_w, const float* border_rgb, int subpix, const double* velocity,
                              double readout, float* dst, float* mask, uint32_t* pad_count);
+#define VSTAB_ROLLING_UNWARP_MIN_DET 0.25
+int vstab_rolling_unwarp_batch(vstab_ctx* ctx, const float* src, int n, int src_h, int src_w, const float* matrices,
+                               int out_h, int out_w, const float* border_rgb, int subpix, const double* velocity,
+                               double readout, float* dst, float* mask, uint32_t* pad_count, uint32_t* unsolved);
 int vstab_row_residual_batch(vstab_ctx* ctx, const float* grid_flow, int pairs, int gh, int gw, int step, int work_h,
                              int work_w, const float* transitions, const uint8_t* blocked, float* residual, int32_t* count);
 
