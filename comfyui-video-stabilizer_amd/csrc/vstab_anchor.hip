@@ -1,0 +1,185 @@
+// vstab_anchor.hip -- drift correction: the normal equations of aligning every frame to its keyframe, as exact integer sums
+// (vstab_anchor_sums_batch).  Not a reference feature; the rule is stated in include/vstab.h.
+//
+// One kernel, shaped after pair_residual_kernel (vstab_cut.hip).  A workgroup owns ANCHOR_ROWS template rows of one frame;
+// a lane takes 16 template pixels with one 16-byte load per row (the row itself and its two neighbours for the vertical
+// gradient; the two pixels beside the piece come as byte loads), maps each through the frame's matrix in fp64 (the rule's
+// association, nothing fused: -ffp-contract=off), rounds to Q5 half-to-even and reads the four taps of the frame's image
+// with byte loads.  A shake-sized matrix keeps those taps within a few rows of the pixel, so template and image cross HBM
+// about once: ~2 * h * w bytes per frame.  Everything that is summed is an integer, so lane order, wave order and the order
+// of the atomics do not show in the result: 17 lane sums (i64) -> wave reduction by shuffles -> LDS -> one 64-bit atomic
+// per workgroup and slot, only where the workgroup counted or capped a pixel.
+//
+// Bounds (max(h, w) <= 1024, required by the entry point): |gx|, |gy| <= 255; |u|, |q| <= 1023; so |J2|, |J3| <=
+// 2 * 255 * 1023 = 521730 < 2^19 (int32), |r| <= 261120 < 2^18, a product J_j J_k < 2^38 and J_k r < 2^37 (formed in 64
+// bits), and at most 1022^2 < 2^20 pixels take part: |sum J_j J_k| < 2^58, |sum J_k r| < 2^57, sum |r| < 2^38.  Nothing
+// reaches 2^59, for a lane, a workgroup or a frame.
+#include "vstab_internal.h"
+
+namespace {
+
+constexpr int ANCHOR_ROWS = 16;     // template rows per workgroup (960x540: 34 workgroups per frame)
+constexpr int ANCHOR_THREADS = 256;
+constexpr int ANCHOR_WAVES = ANCHOR_THREADS / 64;
+constexpr int ANCHOR_SLOTS = VSTAB_ANCHOR_SLOTS;
+
+struct AnchorAcc {
+    long long count = 0, capped = 0, sum_abs = 0;
+    long long b0 = 0, b1 = 0, b2 = 0, b3 = 0;
+    long long h00 = 0, h01 = 0, h02 = 0, h03 = 0, h11 = 0, h12 = 0, h13 = 0, h22 = 0, h23 = 0, h33 = 0;
+};
+
+struct AnchorMatrix {
+    double r0, r1, r2, r3, r4, r5;
+};
+
+// one template pixel of the rule: t = T[y,x], l / r / up / dn its four neighbours, img = the frame's image
+__device__ __forceinline__ void anchor_pixel(AnchorAcc& a, const AnchorMatrix& R, const uint8_t* __restrict__ img, int x, int y,
+                                             int h, int w, int cap1024, int t, int l, int r, int up, int dn)
+{
+    const double dx = (double)x, dy = (double)y;
+    const double X = (R.r0 * dx + R.r1 * dy) + R.r2;
+    const double Y = (R.r3 * dx + R.r4 * dy) + R.r5;
+    const double fix = rint(32.0 * X), fiy = rint(32.0 * Y);    // half-to-even; NaN / inf fail the comparisons below
+    if (!(fix >= 0.0 && fix <= (double)(32 * (w - 1)) && fiy >= 0.0 && fiy <= (double)(32 * (h - 1)))) return;
+    const int ix = (int)fix, iy = (int)fiy;
+    const int x0 = ix >> 5, fx = ix & 31, x1 = min(x0 + 1, w - 1);
+    const int y0 = iy >> 5, fy = iy & 31, y1 = min(y0 + 1, h - 1);
+    const uint8_t* __restrict__ r0 = img + (size_t)y0 * w;
+    const uint8_t* __restrict__ r1 = img + (size_t)y1 * w;
+    const int v = (32 - fx) * (32 - fy) * (int)r0[x0] + fx * (32 - fy) * (int)r0[x1] + (32 - fx) * fy * (int)r1[x0] +
+                  fx * fy * (int)r1[x1];
+    const int res = v - 1024 * t;
+    // (both counters are added to without a branch: behind `if (over) capped += 1; else count += 1` the compiler selects
+    // between the addresses of the two and puts them into scratch memory)
+    const int over = abs(res) > cap1024 ? 1 : 0;
+    a.capped += over;
+    a.count += 1 - over;
+    if (over) return;
+    const int gx = r - l, gy = dn - up, u = 2 * x - (w - 1), q = 2 * y - (h - 1);
+    const int j2 = gx * u + gy * q, j3 = gy * u - gx * q;
+    a.sum_abs += abs(res);
+    a.b0 += (long long)gx * res;
+    a.b1 += (long long)gy * res;
+    a.b2 += (long long)j2 * res;
+    a.b3 += (long long)j3 * res;
+    a.h00 += gx * gx;
+    a.h01 += gx * gy;
+    a.h02 += gx * j2;       // < 2^27: the 32-bit products of the first two rows cannot overflow
+    a.h03 += gx * j3;
+    a.h11 += gy * gy;
+    a.h12 += gy * j2;
+    a.h13 += gy * j3;
+    a.h22 += (long long)j2 * j2;
+    a.h23 += (long long)j2 * j3;
+    a.h33 += (long long)j3 * j3;
+}
+
+__device__ __forceinline__ int byte_of(const uint4& v, int k)
+{
+    const unsigned word = (k < 4) ? v.x : (k < 8) ? v.y : (k < 12) ? v.z : v.w;
+    return (int)((word >> ((k & 3) * 8)) & 0xffu);
+}
+
+__device__ __forceinline__ long long wave_sum(long long v)
+{
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+// VEC: w % 16 == 0 and the base 16-byte aligned (every row of every frame then is)
+template <bool VEC>
+__global__ __launch_bounds__(ANCHOR_THREADS) void anchor_sums_kernel(const uint8_t* __restrict__ gray, const double* __restrict__ mats,
+                                                                      const int* __restrict__ anchors, int h, int w, int tiles,
+                                                                      int cap1024, long long* __restrict__ out)
+{
+    __shared__ long long s_part[ANCHOR_WAVES][ANCHOR_SLOTS];
+    const int frame = (int)blockIdx.x / tiles, tile = (int)blockIdx.x - frame * tiles;
+    const int anchor = anchors[frame];
+    if (anchor < 0) return;                             // the whole workgroup: no barrier has been reached
+    const int y_first = 1 + tile * ANCHOR_ROWS, rows = min(ANCHOR_ROWS, (h - 1) - y_first);   // template rows 1..h-2
+    const double* __restrict__ mat = mats + (size_t)frame * 6;
+    const AnchorMatrix R = {mat[0], mat[1], mat[2], mat[3], mat[4], mat[5]};
+    const uint8_t* __restrict__ tmpl = gray + (size_t)anchor * h * w;
+    const uint8_t* __restrict__ img = gray + (size_t)frame * h * w;
+    const int chunks = (w + 15) >> 4;                   // 16-pixel pieces of a row
+    AnchorAcc acc;
+    for (int item = threadIdx.x; item < rows * chunks; item += ANCHOR_THREADS) {
+        const int r = item / chunks, c = item - r * chunks;
+        const int y = y_first + r, xa = c << 4;
+        const uint8_t* __restrict__ row = tmpl + (size_t)y * w;
+        const int xs = max(xa, 1), xe = min(xa + 16, w - 1);   // the piece's pixels with 1 <= x <= w-2
+        if (VEC) {
+            const uint4 mid = *reinterpret_cast<const uint4*>(row + xa);
+            const uint4 upv = *reinterpret_cast<const uint4*>(row - w + xa);
+            const uint4 dnv = *reinterpret_cast<const uint4*>(row + w + xa);
+            const int before = xa > 0 ? (int)row[xa - 1] : 0, after = xa + 16 < w ? (int)row[xa + 16] : 0;
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                const int x = xa + k;
+                if (x >= xs && x < xe)
+                    anchor_pixel(acc, R, img, x, y, h, w, cap1024, byte_of(mid, k), k == 0 ? before : byte_of(mid, k - 1),
+                                 k == 15 ? after : byte_of(mid, k + 1), byte_of(upv, k), byte_of(dnv, k));
+            }
+        } else {
+            for (int x = xs; x < xe; x++)
+                anchor_pixel(acc, R, img, x, y, h, w, cap1024, (int)row[x], (int)row[x - 1], (int)row[x + 1], (int)row[x - w],
+                             (int)row[x + w]);
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int slot = 0;
+    auto put = [&](long long lane_sum) {                // the slots in the order of the rule's step 10
+        const long long total = wave_sum(lane_sum);
+        if (lane == 0) s_part[wave][slot] = total;
+        slot += 1;
+    };
+    put(acc.count), put(acc.capped), put(acc.sum_abs);
+    put(acc.b0), put(acc.b1), put(acc.b2), put(acc.b3);
+    put(acc.h00), put(acc.h01), put(acc.h02), put(acc.h03), put(acc.h11), put(acc.h12), put(acc.h13), put(acc.h22), put(acc.h23), put(acc.h33);
+    __syncthreads();
+    if (threadIdx.x < ANCHOR_SLOTS) {
+        long long touched = 0, total = 0;
+        for (int k = 0; k < ANCHOR_WAVES; k++) {
+            touched += s_part[k][0] + s_part[k][1];
+            total += s_part[k][threadIdx.x];
+        }
+        if (touched) atomicAdd(reinterpret_cast<unsigned long long*>(out + (size_t)frame * ANCHOR_SLOTS + threadIdx.x), (unsigned long long)total);
+    }
+}
+
+}  // namespace
+
+extern "C" int vstab_anchor_sums_batch(vstab_ctx* ctx, const uint8_t* gray, int n, int h, int w, const int32_t* anchor,
+                                       const double* R, int cap, int64_t* out)
+{
+    VSTAB_REQUIRE(ctx != nullptr, "vstab_anchor_sums_batch: ctx is NULL");
+    VSTAB_REQUIRE(gray && anchor && R && out, "vstab_anchor_sums_batch: NULL pointer argument");
+    VSTAB_REQUIRE(n >= 1 && h > 0 && w > 0, "vstab_anchor_sums_batch: needs at least one frame of a positive size (n=%d, %dx%d)", n, w, h);
+    VSTAB_REQUIRE(h <= 1024 && w <= 1024, "vstab_anchor_sums_batch: %dx%d image larger than 1024 on a side (the sums are exact up to there)", w, h);
+    VSTAB_REQUIRE(cap >= 0 && cap <= 255, "vstab_anchor_sums_batch: cap %d outside [0, 255]", cap);
+    for (int i = 0; i < n; i++)
+        VSTAB_REQUIRE(anchor[i] >= -1 && anchor[i] < n, "vstab_anchor_sums_batch: anchor[%d] = %d outside [-1, %d)", i, (int)anchor[i], n);
+    VSTAB_HIP(hipSetDevice(ctx->device));
+    VSTAB_HIP(hipMemsetAsync(out, 0, (size_t)n * ANCHOR_SLOTS * sizeof(int64_t), ctx->stream));
+    if (h < 3 || w < 3) return 0;                       // no template pixel has all four neighbours
+    const int tiles = (h - 2 + ANCHOR_ROWS - 1) / ANCHOR_ROWS;
+    VSTAB_REQUIRE((long long)n * tiles < 0x7fffffffLL, "vstab_anchor_sums_batch: clip too large");
+    // one staged blob: the matrices (fp64, so they come first) and the anchors behind them
+    const size_t mat_bytes = (size_t)n * 6 * sizeof(double);
+    std::vector<unsigned char> blob(mat_bytes + (size_t)n * sizeof(int32_t));
+    memcpy(blob.data(), R, mat_bytes);
+    memcpy(blob.data() + mat_bytes, anchor, (size_t)n * sizeof(int32_t));
+    void* d_blob = nullptr;
+    if (int rc = vstab_stage_params(ctx, blob.data(), blob.size(), &d_blob)) return rc;
+    const double* d_mats = static_cast<const double*>(d_blob);
+    const int* d_anchor = reinterpret_cast<const int*>(static_cast<const unsigned char*>(d_blob) + mat_bytes);
+    KernelTimer timer(ctx, "anchor");
+    const bool vec = (w % 16 == 0) && (reinterpret_cast<uintptr_t>(gray) % 16 == 0);
+    const dim3 grid((unsigned)(n * tiles)), block(ANCHOR_THREADS);
+    long long* sums = reinterpret_cast<long long*>(out);
+    if (vec) hipLaunchKernelGGL(anchor_sums_kernel<true>, grid, block, 0, ctx->stream, gray, d_mats, d_anchor, h, w, tiles, 1024 * cap, sums);
+    else hipLaunchKernelGGL(anchor_sums_kernel<false>, grid, block, 0, ctx->stream, gray, d_mats, d_anchor, h, w, tiles, 1024 * cap, sums);
+    VSTAB_HIP(hipGetLastError());
+    return 0;
+}

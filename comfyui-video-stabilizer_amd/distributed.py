@@ -216,7 +216,8 @@ def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, t
                       strength: float, smooth: float, keep_fov: float, padding_rgb, frame_rate: float, group=None,
                       estimator: str = "flow", stats: Optional[Dict[str, float]] = None, want_meta: bool = True,
                       check_value_range: bool = True, temporal_fill: int = 0, estimation_mask=None, scene_cuts=None,
-                      mesh_warp=None, dynamic_zoom=None, sharpness_transfer=None, rolling_shutter=None):
+                      mesh_warp=None, dynamic_zoom=None, sharpness_transfer=None, rolling_shutter=None,
+                      drift_correction=None):
     """Sharded equivalent of `_stabilize_frames` (flow.py:213-640).
 
     local_frames: device tensor [n_local (+1 halo for rank > 0 that owns frames), H, W, 3] float32 -- this rank's frames
@@ -267,6 +268,10 @@ def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, t
          f"stabilize_sharded does not support sharpness_transfer={sharpness_transfer!r}: the sharpness transfer is "
          "not sharded (the sharded path holds no halo of neighbouring source frames); run the single-GPU "
          "pipeline for it"),
+        # a frame is registered against a keyframe up to a keyframe spacing back, which may lie on another rank
+        ("drift_correction", drift_correction is not None and drift_correction is not False and drift_correction != 0,
+         f"stabilize_sharded does not support drift_correction={drift_correction!r}: the keyframe alignment is not "
+         "sharded (a frame's keyframe may lie on another rank); run the single-GPU pipeline for it"),
     )
     for _keyword, requested, message in refusals:
         if requested:

@@ -28,6 +28,7 @@ from . import native
 from . import scene_cuts as scene_cuts_mod
 from . import mask_handoff as mask_handoff_mod
 from . import rolling_shutter as rolling_shutter_mod
+from . import drift_correction as drift_correction_mod
 from . import sharpness_transfer as sharpness_transfer_mod
 from . import spatial_fill as spatial_fill_mod
 from . import stability as stability_mod
@@ -313,13 +314,23 @@ def _select_per_segment(fit_records, transform_mode: str, segments):
     return work_mats, modes, confs, resids, active
 
 
+def keep_fov_bypasses(framing_mode: str, keep_fov: float) -> bool:
+    """flow.py:387: `crop` framing with keep_fov ~ 1 returns the original frames.  The plan decides it; what would only feed
+    the plan (the drift correction) asks here too, so that the bypass launches nothing."""
+    return framing_mode == "crop" and float(np.clip(keep_fov, 0.0, 1.0)) >= 0.9999
+
+
 def _plan_stabilization(ctx, fit_records, size, total_frames, framing_mode, transform_mode, camera_lock, strength, smooth,
-                       keep_fov, padding_rgb, fps_effective, fps_requested, estimator: str = "flow", segments=None) -> FlowPlan:
+                       keep_fov, padding_rgb, fps_effective, fps_requested, estimator: str = "flow", segments=None,
+                       path_deltas=None) -> FlowPlan:
     """flow.py:324-546 for a whole clip: sticky-mode selection, parameter deltas, trajectory (HIP fp64),
     framing geometry.  `fit_records` covers all N-1 transitions of the clip.
     segments (scene cuts; None: one continuous camera move, the reference's behaviour): frame ranges [s, e) of the shots.
     Selection and trajectory run per shot -- every shot's path starts at 0 -- and are concatenated; the framing below stays
-    global, so there is one output geometry."""
+    global, so there is one output geometry.
+    path_deltas (drift correction; None: the reference's behaviour): float64 [N-1, P], the per-pair steps of a path formed
+    elsewhere.  They replace the parameter deltas of the table's matrices in the trajectory, per shot as those; `matrices`,
+    modes and confidences still come from the table."""
     width, height = size
     rgb_list = [int(c) for c in padding_rgb]
     base_mode = transform_mode
@@ -330,6 +341,11 @@ def _plan_stabilization(ctx, fit_records, size, total_frames, framing_mode, tran
         work_mats, modes_used, confidences, residuals, active_mode = _select_per_segment(fit_records, transform_mode, segments)
     # rescale to full resolution + parameter deltas (flow.py:340-346), one library call over the clip
     matrices, delta_params = native.transitions_to_params(work_mats, base_mode, size, working_size)
+    if path_deltas is not None:
+        path_deltas = np.ascontiguousarray(path_deltas, dtype=np.float64)
+        if path_deltas.shape != delta_params.shape:
+            raise ValueError(f"path_deltas of shape {path_deltas.shape} are not {delta_params.shape}")
+        delta_params = path_deltas
 
     # ---- trajectory (F7-F8) --------------------------------------------------
     strength = float(np.clip(strength, 0.0, 1.0))
@@ -351,7 +367,7 @@ def _plan_stabilization(ctx, fit_records, size, total_frames, framing_mode, tran
     stabilization_scale = 1.0
 
     if framing_mode == "crop":
-        if keep_fov_clamped >= 0.9999:  # flow.py:387-429: return the original frames
+        if keep_fov_bypasses(framing_mode, keep_fov):  # flow.py:387-429: return the original frames
             meta = {
                 "frames": total_frames,
                 "note": "keep_fov~=1.0 in crop mode; returning original frames.",
@@ -738,6 +754,22 @@ def _rolling_shutter(ctx, rolling, plan, grid_out, blocked, working_size, size, 
     return velocity, readout, rolling_shutter_mod.meta_block(readout, source, estimate, velocity, size)
 
 
+# ---- drift correction (beyond the reference; drift_correction.py, the rule is in include/vstab.h) ------------------------
+def _drift_correction(ctx, spacing, fit_records, gray, segments, total_frames, transform_mode, size, working_size):
+    """-> (the fit table with the registered poses' transitions, the path's per-pair steps, meta["drift_correction"]).  Runs
+    on the selection the plan itself will make; every launch covers all frames of the clip that are still iterating."""
+    table = fit_records if isinstance(fit_records, np.ndarray) else native.fit_table_from_dicts(fit_records)
+    if segments is None:
+        selection = select_transitions(table, transform_mode)
+    else:
+        selection = _select_per_segment(table, transform_mode, segments)
+
+    def sums_fn(anchor, R):
+        return ctx.anchor_sums_batch(gray, anchor, R, drift_correction_mod.RESIDUAL_CAP)
+
+    return drift_correction_mod.correct(sums_fn, table, selection, segments, total_frames, transform_mode, size, working_size, spacing)
+
+
 # ---- dynamic zoom (beyond the reference; dynamic_zoom.py, the rule is in include/vstab.h) -------------------------------
 def _dynamic_zoom(ctx, zoom, plan, offsets, segments):
     """-> (the plan with its final matrices zoomed, meta["dynamic_zoom"] still without the warp's counts).  One launch of the
@@ -770,20 +802,22 @@ class FlowRequest:
     spatial_fill: bool
     stability_report: bool
     mask_margin: Optional[int]         # the estimation mask's margin; None: no estimation mask was given
+    drift: Optional[int] = None        # drift_correction.check_request: the keyframe spacing | None
 
     @property
     def needs_host_plan(self) -> bool:
         """Scene-aware calls form the plan on the host: plan_kernel knows one continuous camera move; so do mesh-warp calls:
         the vertex paths need the plan's own transitions before the warp can be queued; and dynamic-zoom calls: the zoom is
         formed from the plan's final matrices before the warp can be queued; and rolling-shutter calls: the velocities come
-        from the plan's transitions before the warp can be queued."""
-        return not (self.scene is None and self.mesh is None and self.zoom is None and self.rolling is None)
+        from the plan's transitions before the warp can be queued; and drift-corrected calls: the keyframe alignment rewrites
+        the transitions before there is a plan."""
+        return not (self.scene is None and self.mesh is None and self.zoom is None and self.rolling is None and self.drift is None)
 
     @property
     def kept_by_products(self) -> Tuple[str, ...]:
         """The estimator's by-products that stay alive behind the fits (its `*_out` keywords): the estimation images for the
-        scene-cut score, the grid of flow samples for the vertex / row residuals."""
-        keep = ("gray_out",) if self.scene is not None and self.scene.mode == "auto" else ()
+        scene-cut score and the keyframe alignment, the grid of flow samples for the vertex / row residuals."""
+        keep = ("gray_out",) if (self.scene is not None and self.scene.mode == "auto") or self.drift is not None else ()
         return keep + (("grid_out",) if self.mesh is not None or self.rolling == rolling_shutter_mod.AUTO else ())
 
 
@@ -821,8 +855,11 @@ def check_flow_request(framing_mode: str, transform_mode: str, estimator: str, k
     rolling = rolling_shutter_mod.check_request(kw["rolling_shutter"])
     if rolling is not None:
         rolling_shutter_mod.check_pipeline(rolling, transform_mode, framing_mode, estimator, mesh, temporal_fill, sharpness, zoom)
+    drift = drift_correction_mod.check_request(kw["drift_correction"])
+    if drift is not None:
+        drift_correction_mod.check_pipeline(transform_mode, bool(subject), kw["estimation_mask"])
     return FlowRequest(estimator, temporal_fill, fill_blend, sharpness, handoff, zoom, scene, mesh, bool(kw["mesh_motion"]),
-                       bool(subject), rolling, spatial_fill, stability_report, mask_margin)
+                       bool(subject), rolling, spatial_fill, stability_report, mask_margin, drift)
 
 
 def _check_request_against_clip(request: FlowRequest, kw: Dict[str, Any], transform_mode: str, total_frames: int, size) -> None:
@@ -958,6 +995,7 @@ def _stabilize_frames(
     mask_hold=None,
     mask_tapered=None,
     rolling_shutter=None,
+    drift_correction=None,
 ) -> hm.StabilizationResult:
     """Positional signature of the reference (flow.py:213-223); keyword-only extras select the GPU
     context, keep outputs resident in HBM (multi-GPU sharding lives in distributed.py) or switch the
@@ -1046,7 +1084,17 @@ def _stabilize_frames(
     translation / similarity under crop_and_pad / expand, without mesh_warp, temporal_fill, sharpness_transfer, dynamic_zoom or
     estimator "subject"; everything behind the final warp follows unchanged.  meta["rolling_shutter"] reports the readout, the
     skew it amounts to and every frame's velocity.  None / 0: the behaviour and meta without it, byte for byte, and nothing new
-    is launched.  Bypass paths ignore it."""
+    is launched.  Bypass paths ignore it.
+    drift_correction (beyond the reference, None by default): True (a keyframe every 32 frames) or the keyframe spacing, an int
+    in 2..4096.  Every estimator measures consecutive pairs, and the bias of a pair adds up along the chain: a locked picture
+    creeps.  With the keyword every frame is registered directly against the latest keyframe before it, and every keyframe
+    against the previous one, by Gauss-Newton on the estimation images (drift_correction.py; include/vstab.h states the rule
+    of its sums), starting from the chained estimate; the transitions the plan reads are those of the registered poses, and
+    the path is the poses' own parameter vector instead of the sum of the pairs', so that camera_lock at strength 1 applies
+    the inverse pose exactly.  A frame whose alignment cannot be trusted keeps its chained estimate, counted by reason in
+    meta["drift_correction"].  For translation / similarity, without estimation_mask or estimator "subject"; everything behind
+    the fit table follows unchanged.  None / 0 / False: the behaviour and meta without it, byte for byte, and nothing new is
+    launched.  Bypass paths ignore it."""
     kw = dict(locals())     # every argument by name (nothing else is local yet): the keyword extras are read from here
     request = check_flow_request(framing_mode, transform_mode, estimator, kw)
     estimator = request.estimator
@@ -1144,7 +1192,12 @@ def _stabilize_frames(
     segments = scene_block = None
     if scene is not None:
         segments, scene_block = _scene_segments(ctx, scene, fit_records, extras.get("gray_out"), transform_mode, total_frames)
-    plan = plan_stabilization(ctx, fit_records, size, total_frames, *args, estimator=estimator, segments=segments)
+    path_deltas = drift_block = None
+    if request.drift is not None and not keep_fov_bypasses(framing_mode, keep_fov):   # (the plan returns the original frames)
+        fit_records, path_deltas, drift_block = _drift_correction(ctx, request.drift, fit_records, extras["gray_out"][0], segments,
+                                                                  total_frames, transform_mode, size, working_size)
+    plan = plan_stabilization(ctx, fit_records, size, total_frames, *args, estimator=estimator, segments=segments,
+                              path_deltas=path_deltas)
     if plan.bypass_meta is not None:  # crop + keep_fov ~ 1 (flow.py:387-429): original frames
         pbar.update_absolute(progress_total, progress_total)
         frames_out = device_frames if keep_on_device else _host_frames(context)
@@ -1181,6 +1234,7 @@ def _stabilize_frames(
         "mesh_warp": mesh_block,
         "subject_lock": extras["subject"]["block"] if request.subject else None,
         "rolling_shutter": rolling_block,
+        "drift_correction": drift_block,
     }
     meta.update({key: block for key, block in blocks.items() if block is not None})
     return _finish(ctx, request, plan, device_frames, dst, mask, meta, segments, keep_on_device, {"used": False, "mismatched_frames": 0})

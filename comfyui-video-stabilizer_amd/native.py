@@ -176,6 +176,8 @@ _SIGNATURES = {
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vstab_pair_residual_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vstab_anchor_sums_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "vstab_mesh_residual_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                   C.c_int, C.c_void_p, C.c_void_p]),
@@ -747,6 +749,35 @@ class Context:
         _check(self.lib.vstab_pair_residual_batch(self.handle, _dev_ptr(gray), n, h, w, m.ctypes.data, _dev_ptr(sums),
                                                   _dev_ptr(inside)), "vstab_pair_residual_batch")
         return sums.cpu().numpy(), inside.cpu().numpy().astype(np.int64)
+
+    def anchor_sums_batch(self, gray, anchor, R, cap):
+        """Drift correction: the normal equations of aligning every frame to its anchor (vstab_anchor_sums_batch; the rule is
+        in include/vstab.h).  gray u8 [N,h,w] (device), anchor int [N] (-1: no anchor), R f64 [N,6] or [N,2,3] (anchor pixel ->
+        frame pixel, working resolution), cap 0..255 -> int64 [N,17] on the host: integers, equal to the NumPy restatement
+        exactly."""
+        torch = self.torch
+        if gray.dtype != torch.uint8 or gray.dim() != 3:
+            raise ValueError("anchor_sums_batch expects a uint8 [N,h,w] tensor")
+        if gray.device != self.device or not gray.is_contiguous():   # (a contiguous view keeps its own, possibly unaligned, base)
+            gray = gray.to(self.device).contiguous()
+        n, h, w = (int(v) for v in gray.shape)
+        if n < 1:
+            raise ValueError("anchor_sums_batch needs at least one frame")
+        a = np.ascontiguousarray(anchor, dtype=np.int32).reshape(-1)
+        m = np.ascontiguousarray(R, dtype=np.float64)
+        if a.size != n or m.size != n * 6:
+            raise ValueError(f"anchor_sums_batch: anchor {a.shape} / R {m.shape} are not [{n}] / [{n},6] for {n} frames")
+        if a.size and (a.min() < -1 or a.max() >= n):
+            raise ValueError(f"anchor_sums_batch: an anchor outside -1..{n - 1}")
+        if max(h, w) > 1024:
+            raise ValueError(f"anchor_sums_batch: {w}x{h} image larger than 1024 on a side")
+        if int(cap) != cap or not 0 <= int(cap) <= 255:
+            raise ValueError(f"anchor_sums_batch: cap {cap!r} is not an integer in 0..255")
+        out = torch.empty((n, 17), dtype=torch.int64, device=self.device)
+        self.use_torch_stream()
+        _check(self.lib.vstab_anchor_sums_batch(self.handle, _dev_ptr(gray), n, h, w, a.ctypes.data, m.ctypes.data, int(cap),
+                                                _dev_ptr(out)), "vstab_anchor_sums_batch")
+        return out.cpu().numpy()
 
     # ------------------------------------------------------------------ mesh warp
     @staticmethod

@@ -947,6 +947,41 @@ class VideoStabilizerFlowRolling(io.ComfyNode):
                                    keep_fov, padding_color, rolling_shutter="auto" if float(readout) == 0.0 else float(readout))
 
 
+class VideoStabilizerFlowAnchored(io.ComfyNode):
+    """The Flow node with drift correction: every frame is registered directly against a keyframe, so the error of the
+    consecutive-pair estimates no longer adds up along the clip and a locked picture stays put (drift_correction.py).  Not
+    one of the reference's nodes: it is listed by an extension but kept out of NODE_CLASSES."""
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        schema = io.Schema(
+            node_id="video_stabilizer_flow_anchored",
+            display_name="Video Stabilizer Flow (Drift-Free)",
+            category="Video/Stabilization",
+            description=("Video Stabilizer Flow that registers every frame against a keyframe, so that the small error of "
+                         "each pair estimate does not accumulate into a creeping picture."),
+        )
+        base = VideoStabilizerFlow.define_schema()
+        schema.inputs = [
+            io.Combo.Input("transform_mode", options=["translation", "similarity"], default="similarity",
+                           display_name="Transform Mode",
+                           tooltip=("Select the geometric model fitted to the optical flow.  The keyframe alignment updates "
+                                    "a shift, a zoom and a rotation, so perspective is not offered."))
+            if s.id == "transform_mode" else s for s in base.inputs] + [
+            io.Int.Input("keyframe_spacing", default=32, min=2, max=4096, step=1, display_name="Keyframe Spacing",
+                         tooltip=("Frames between two keyframes.  Every frame is aligned to the latest keyframe before it and "
+                                  "every keyframe to the previous one; the meta reports how many frames were refined.")),
+        ]
+        schema.outputs = _estimator_outputs()
+        return schema
+
+    @classmethod
+    def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
+                strength: float, smooth: float, keep_fov: float, padding_color: str, keyframe_spacing: int = 32) -> io.NodeOutput:
+        return _run_estimator_node("flow", frames, frame_rate, framing_mode, transform_mode, camera_lock, strength, smooth,
+                                   keep_fov, padding_color, drift_correction=int(keyframe_spacing))
+
+
 class VideoStabilizerMotionApplyRolling(io.ComfyNode):
     """Motion Apply for a rolling-shutter run (apply_motion's rolling=True): on the run's source frames (or a companion clip
     of their size) it applies the recorded matrices and row correction again, on its stabilized frames it restores the
@@ -1121,3 +1156,6 @@ VideoStabilizerAmdRollingExtension = _extend(
 VideoStabilizerAmdRollingApplyExtension = _extend(
     VideoStabilizerAmdRollingExtension, VideoStabilizerMotionApplyRolling, name="VideoStabilizerAmdRollingApplyExtension",
     doc="The rolling-shutter extension's twenty nodes plus Video Stabilizer Motion Apply (Rolling Shutter).")
+VideoStabilizerAmdAnchorExtension = _extend(
+    VideoStabilizerAmdRollingApplyExtension, VideoStabilizerFlowAnchored, name="VideoStabilizerAmdAnchorExtension",
+    doc="The rolling round trip extension's twenty-one nodes plus Video Stabilizer Flow (Drift-Free).")

@@ -284,6 +284,38 @@ int vstab_sample_fit_batch_begin_masked(vstab_ctx* ctx, const float* grid_flow, 
 int vstab_pair_residual_batch(vstab_ctx* ctx, const uint8_t* gray, int n, int h, int w, const float* transitions,
                               uint64_t* sum_abs, uint32_t* inside);
 
+/* ---- Drift correction (not a reference feature): the normal equations of aligning a frame to its keyframe ----------
+ * Consecutive-pair estimates chain their bias; a frame registered directly against a keyframe does not.  One launch forms,
+ * for every frame i with an anchor a = anchor[i], the Gauss-Newton sums of the inverse-compositional alignment of the
+ * template T = gray[a] to the image I = gray[i] under R_i, the row-major affine 2x3 (fp64) that maps an anchor pixel into
+ * frame i.  anchor[i] == -1: the frame's 17 numbers are zero.  For every template pixel (x, y), 1 <= x <= w-2, 1 <= y <= h-2:
+ *   1. X = (R0*x + R1*y) + R2,  Y = (R3*x + R4*y) + R5  -- fp64, separate IEEE multiplies and adds in exactly this
+ *      association, nothing fused;
+ *   2. ix = rint(32 X), iy = rint(32 Y), ties to even;
+ *   3. the pixel takes part iff 0 <= ix <= 32 (w-1) and 0 <= iy <= 32 (h-1), compared in fp64 before any conversion (NaN
+ *      and inf fail);
+ *   4. x0 = ix >> 5, fx = ix & 31, x1 = min(x0 + 1, w-1); y0, fy, y1 likewise;
+ *   5. v = (32-fx)(32-fy) I[y0,x0] + fx (32-fy) I[y0,x1] + (32-fx) fy I[y1,x0] + fx fy I[y1,x1]   (an integer, 0..261120);
+ *   6. r = v - 1024 T[y,x];
+ *   7. |r| > 1024 cap: capped += 1 and nothing else is added (the truncated-L2 guard against moving subjects; cap is an
+ *      integer in 0..255 grey levels, and 255 caps nothing);
+ *   8. gx = T[y,x+1] - T[y,x-1],  gy = T[y+1,x] - T[y-1,x],  u = 2x - (w-1),  q = 2y - (h-1);
+ *   9. J = (gx, gy, gx u + gy q, gy u - gx q)   -- twice the derivative of T along a shift in x, in y, and four times along
+ *      a zoom and a rotation about the image centre ((w-1)/2, (h-1)/2);
+ *  10. out[i] += [1, 0, |r|, J0 r, J1 r, J2 r, J3 r, J0J0, J0J1, J0J2, J0J3, J1J1, J1J2, J1J3, J2J2, J2J3, J3J3], i.e.
+ *      out[i] = [count, capped, sum|r|, b0..b3, H00, H01, H02, H03, H11, H12, H13, H22, H23, H33].
+ * Everything summed is an integer, so the result does not depend on the order of the reduction.  max(h, w) <= 1024 is
+ * required: then |J2|, |J3| <= 2*255*1023 < 2^19, |r| < 2^18, fewer than 2^20 pixels take part, and no sum reaches 2^59.
+ * h < 3 or w < 3: zeros.
+ * vstab_anchor_sums_batch: gray dev [n,h,w] u8 (n >= 1), anchor host [n] i32 (-1 or a frame index in 0..n-1), R host
+ * [n][6] f64, cap 0..255 -> out dev [n][VSTAB_ANCHOR_SLOTS] i64 (zeroed by the call).  One streaming pass of about 2*h*w
+ * bytes per anchored frame; asynchronous on the context's stream; timing kind "anchor".  What is solved from the sums
+ * (drift_correction.py): H d' = b / 1024, d = (2 d'0, 2 d'1, 4 d'2, 4 d'3), R <- R W(d)^-1.
+ */
+#define VSTAB_ANCHOR_SLOTS 17
+int vstab_anchor_sums_batch(vstab_ctx* ctx, const uint8_t* gray, int n, int h, int w, const int32_t* anchor,
+                            const double* R, int cap, int64_t* out);
+
 /* ---- N1 (crop framing): coverage analysis for the keep_fov crop solver ---------
  * Replaces the per-frame cv2 calls of nodes/stabilizer_utils.py:611-643
  * (finalize_with_masks: warpPerspective(ones, NEAREST) > 0.5, dilate 3x3, erode 3x3, bounding box of
