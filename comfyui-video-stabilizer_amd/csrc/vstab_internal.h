@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 #include <map>
+#include <type_traits>
 #include "../../include/vstab.h"
 
 void vstab_set_error(const char* fmt, ...);
@@ -289,9 +290,60 @@ __device__ __forceinline__ bool vstab_nn_covered(double qx, double qy, int sh, i
     return (unsigned)nx < (unsigned)sw && (unsigned)ny < (unsigned)sh;
 }
 
-// ---- the warp's arithmetic proper: samplers, tile shell, warp_pixel ----
-// Compiled only where a translation unit defines VSTAB_WARP_ARITHMETIC in front of this include (vstab_warp.hip and
-// vstab_neighbour.hip).  It lives here because profiles/warp_traffic.json is tied to the hash of vstab_warp.hip + this
+// ---- the residual of the global fit at a grid sample and the median of a workgroup's residuals: the per-vertex form
+// (vstab_mesh.hip) and the per-row form (vstab_rolling.hip) ----
+__device__ __forceinline__ bool finite_f(float v) { return __builtin_fabsf(v) <= 3.4028234663852886e38f; }   // false for NaN
+
+// The grid sample at (x, y) with flow (u, v) against the 3x3 fit A: where the flow takes the point minus where the fit does,
+// every operation fp64 and rounded on its own.  false: a flow or a residual that is not finite (not a sample).
+__device__ __forceinline__ bool vstab_fit_residual(const double (&A)[9], double x, double y, float u, float v, float& rx, float& ry)
+{
+    const double X = (A[0] * x + A[1] * y) + A[2];
+    const double Y = (A[3] * x + A[4] * y) + A[5];
+    const double W = (A[6] * x + A[7] * y) + A[8];
+    rx = (float)((x + (double)u) - X / W);
+    ry = (float)((y + (double)v) - Y / W);
+    return finite_f(u) && finite_f(v) && finite_f(rx) && finite_f(ry);
+}
+
+// The medians of s_rx[0..n) and s_ry[0..n), n >= 1, values in LDS that a barrier has made visible; called by all 256 threads
+// of the workgroup.  Every thread counts the rank of its elements against all others: the element of rank (n-1)/2 and the
+// one of rank n/2 are the middle(s).  Thread 0 writes the two medians to out[0], out[1].
+__device__ __forceinline__ void vstab_median_pair(const float* s_rx, const float* s_ry, int n, float* out)
+{
+    __shared__ float s_mid[2][2];          // [axis][lo, hi]
+    // rank of element i: values below it, and equal values in front of it -- a permutation of 0..n-1
+    const int klo = (n - 1) >> 1, khi = n >> 1;
+    for (int i = threadIdx.x; i < n; i += 256) {
+#pragma unroll
+        for (int axis = 0; axis < 2; axis++) {
+            const float* __restrict__ s = axis ? s_ry : s_rx;
+            const float vi = s[i];
+            int rank = 0;
+            for (int j = 0; j < n; j++) {
+                const float vj = s[j];
+                rank += (vj < vi || (vj == vi && j < i)) ? 1 : 0;
+            }
+            if (rank == klo) s_mid[axis][0] = vi;
+            if (rank == khi) s_mid[axis][1] = vi;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        out[0] = (n & 1) ? s_mid[0][0] : (s_mid[0][0] + s_mid[0][1]) / 2.0f;
+        out[1] = (n & 1) ? s_mid[1][0] : (s_mid[1][0] + s_mid[1][1]) / 2.0f;
+    }
+}
+
+// What the two residual entry points check alike: context, pointers, sizes, grid == ceil(work / step), and the launch grid of
+// per_pair workgroups per pair.
+int vstab_check_residual(const char* who, vstab_ctx* ctx, const void* grid_flow, const void* transitions, const void* residual,
+                         const void* count, int pairs, int gh, int gw, int step, int work_h, int work_w, long long per_pair,
+                         unsigned* blocks);
+
+// ---- the warp's arithmetic proper: samplers, tile shell, warp_pixel, the kernel body ----
+// Compiled only where a translation unit defines VSTAB_WARP_ARITHMETIC in front of this include (vstab_warp.hip,
+// vstab_rolling.hip and vstab_neighbour.hip).  It lives here because profiles/warp_traffic.json is tied to the hash of vstab_warp.hip + this
 // file: whatever decides the plain warp's instructions stays inside the two.
 #ifdef VSTAB_WARP_ARITHMETIC
 constexpr int TILE_PX = 2;       // pixels per thread along x, strided by the tile width (profiles/r01_warp_tile_sweep.md)
@@ -543,7 +595,8 @@ struct XformRegs {
 
 // The warp's source position of output pixel (x, y) under one transform, and what is sampled there: THE definition of the
 // coordinate arithmetic (f64 row-start terms per OpenCV column block, Q5 rounding or the float32 `exact` chain), shared by
-// warp_kernel, mesh_warp_kernel and temporal_fill_kernel.  `q5(X, Y)` samples at the 1/32-px coordinates, `exact(fsx, fsy)`
+// warp_kernel under every Args (plain, mesh and rolling shutter, forward and inverse), cover_extent_kernel and the
+// neighbour passes (vstab_neighbour.hip).  `q5(X, Y)` samples at the 1/32-px coordinates, `exact(fsx, fsy)`
 // at the float32 ones; `c` receives the nearest-neighbour coverage (WITH_MASK only).  `disp` (see NoDisplacement) moves
 // the source position: s = q - disp(q), applied to the unrounded value in front of each of the three roundings.  A `disp` of
 // the OUTPUT kind moves the output pixel by e = disp.solve(x, y) in front of the matrix instead: m * e is added to the
@@ -627,4 +680,138 @@ __device__ __forceinline__ Px warp_pixel(const WarpXform* __restrict__ xf, const
     }
     return v;
 }
+
+struct WarpArgs {
+    const float* src;
+    float* dst;
+    float* mask;
+    unsigned* pad_count;
+    const WarpXform* xf;
+    int n, sh, sw, dh, dw;
+    int bw0;          // column block width of OpenCV's WarpPerspectiveInvoker
+    int bw0_pow2;     // 1 if bw0 is a power of two
+    int tiles_x, tiles_y;
+    int samples;      // 1 for the plain warp
+    int nxf_per_frame;  // sample matrices stored per frame (1 for a single-frame blur clip)
+    int blur_fast;      // blur: the interior fast path may be used (host-checked preconditions, see warp_blur_kernel)
+    float b0, b1, b2;   // border colour
+};
+
+// The displacement a kernel's arguments ask for.  Plain warp: none.  Arguments derived from WarpArgs bring an overload of
+// their own, in their own namespace (the mesh forms: vstab_warp.hip; the rolling-shutter forms: vstab_rolling.hip).
+__device__ __forceinline__ NoDisplacement make_displacement(const WarpArgs&, int) { return {}; }
+
+// One 64 x 8 (TILE_TX = 32) tile of the warp: every pixel through warp_pixel, RGB + mask stored, padded pixels counted.
+// Args = WarpArgs is the plain warp, Args = MeshWarpArgs the mesh warp, Args = MeshUnwarpArgs its inverse, Args =
+// RollingWarpArgs / RollingUnwarpArgs the rolling-shutter warp and its inverse (the rules are in
+// include/vstab.h): the same body with the displacement its arguments ask for.  Arguments of an OUTPUT-kind displacement
+// carry the second counter, `unconverged`.
+// Like every kernel of the library it sits in the translation unit's anonymous namespace: internal linkage, and the
+// profilers' kernel names keep the prefix the tools under tools/ select the library's kernels by.
+// The body stays in the kernel: inlined from a device function that receives the
+// arguments by reference, the compiler issued the two epilogue stores in another order and the plain warp ran 0.3-1 %
+// slower (profiles/r11_one_warp_arithmetic.md).
+namespace {
+template <int INTERP, int SUBPIX, bool WITH_MASK, int TILE_TX, class Args>
+__global__ __launch_bounds__(256) void warp_kernel(Args a)
+{
+    __shared__ __attribute__((aligned(16))) float s_cub[32 * 4];
+    const float* cub_tab = nullptr;
+    if (INTERP == VSTAB_INTERP_BICUBIC) {
+        if (threadIdx.x < 32) cubic_coeffs((int)threadIdx.x, s_cub + threadIdx.x * 4);
+        __syncthreads();
+        cub_tab = s_cub;
+    }
+    const TileShell<TILE_TX> t(a.tiles_x, a.tiles_y, a.dh, a.dw);
+    const int frame = t.frame, x0 = t.x0, y = t.y, npx = t.npx;
+    const auto disp = make_displacement(a, frame);
+    using Disp = std::remove_const_t<decltype(disp)>;
+    const float* __restrict__ S = a.src + (size_t)frame * a.sh * a.sw * 3;
+
+    float acc[TILE_PX][3];
+    float cov[TILE_PX];
+#pragma unroll
+    for (int p = 0; p < TILE_PX; p++) { acc[p][0] = acc[p][1] = acc[p][2] = 0.f; cov[p] = 0.f; }
+    unsigned unconv = 0;      // OUTPUT kind only: this thread's pixels whose solve hit its step limit or was refused
+
+    if (t.active) {
+        const double dy = (double)y;
+        const WarpXform* __restrict__ xf = a.xf + frame;   // one matrix per frame (the S-sample blur is warp_blur_kernel)
+        const XformRegs<INTERP, SUBPIX> r(xf);
+#pragma unroll
+        for (int p = 0; p < TILE_PX; p++) {
+            if (p >= npx) continue;
+            const int x = x0 + p * TILE_TX;
+            float c = 0.f;
+            const Px v = warp_pixel<INTERP, SUBPIX, WITH_MASK>(
+                xf, r, a.sh, a.sw, a.dw, a.bw0, a.bw0_pow2, x, y, dy,
+                [&](int X, int Y) { return sample_q5<INTERP>(S, a.sh, a.sw, X, Y, a.b0, a.b1, a.b2, cub_tab); },
+                [&](float fsx, float fsy) { return sample_exact(S, a.sh, a.sw, fsx, fsy, a.b0, a.b1, a.b2); }, disp, c, &unconv);
+            acc[p][0] = v.r; acc[p][1] = v.g; acc[p][2] = v.b;
+            if (WITH_MASK) cov[p] = c;
+        }
+    }
+
+    // ---- epilogue ----
+    float mk[TILE_PX];
+    unsigned padded[1] = {0};
+#pragma unroll
+    for (int p = 0; p < TILE_PX; p++) {
+        float m = 1.0f - cov[p];
+        mk[p] = (m < 1e-3f) ? 0.f : m;
+        if (WITH_MASK && p < npx) padded[0] += (mk[p] > 0.5f) ? 1u : 0u;
+    }
+
+    if (t.active) {
+        // per-frame bases are uniform (scalar registers); inside a frame 32-bit element offsets suffice (the host checks
+        // that a frame has fewer than 2^30 pixels), which keeps the address arithmetic out of 64-bit VALU multiplies
+        float* __restrict__ D = a.dst + (size_t)frame * a.dh * a.dw * 3;
+        float* __restrict__ Mk = WITH_MASK ? a.mask + (size_t)frame * a.dh * a.dw : nullptr;
+        const unsigned row = (unsigned)y * (unsigned)a.dw;
+        typedef float f3 __attribute__((ext_vector_type(3)));
+#pragma unroll
+        for (int p = 0; p < TILE_PX; p++) {
+            if (p >= npx) continue;
+            const unsigned pix = row + (unsigned)(x0 + p * TILE_TX);
+            // 12 B per lane, consecutive lanes -> consecutive pixels: every store instruction writes whole lines
+            f3 rgb = {acc[p][0], acc[p][1], acc[p][2]};
+            __builtin_memcpy(D + pix * 3u, &rgb, 12);
+            if (WITH_MASK) Mk[pix] = mk[p];
+        }
+    }
+
+    if constexpr (Disp::OUTPUT) {
+        // two counters through one reduction (the conditions are kernel arguments: uniform)
+        if ((WITH_MASK && a.pad_count != nullptr) || a.unconverged != nullptr) {
+            unsigned counts[2] = {padded[0], unconv};
+            block_count_add<2>(counts, {WITH_MASK ? a.pad_count : nullptr, a.unconverged}, frame);
+        }
+    } else {
+        if (WITH_MASK && a.pad_count != nullptr) block_count_add<1>(padded, {a.pad_count}, frame);
+    }
+}
+}  // namespace
+
+// The displaced warps' launch: the SUBPIX x MASK instantiation of the bilinear 64 x 8 tile for these arguments.
+template <class Args>
+void vstab_launch_displaced(const Args& a, unsigned blocks, int subpix, bool with_mask, size_t lds_bytes, hipStream_t stream)
+{
+    constexpr int BILINEAR = VSTAB_INTERP_BILINEAR, Q5 = VSTAB_SUBPIX_Q5, EXACT = VSTAB_SUBPIX_EXACT;
+    const dim3 grid(blocks), block(256);
+    if (subpix == EXACT) {
+        if (with_mask) hipLaunchKernelGGL((warp_kernel<BILINEAR, EXACT, true, 32, Args>), grid, block, lds_bytes, stream, a);
+        else hipLaunchKernelGGL((warp_kernel<BILINEAR, EXACT, false, 32, Args>), grid, block, lds_bytes, stream, a);
+    } else {
+        if (with_mask) hipLaunchKernelGGL((warp_kernel<BILINEAR, Q5, true, 32, Args>), grid, block, lds_bytes, stream, a);
+        else hipLaunchKernelGGL((warp_kernel<BILINEAR, Q5, false, 32, Args>), grid, block, lds_bytes, stream, a);
+    }
+}
+
+// The displaced warps' preparation, behind the caller's checks (vstab_warp.hip): the device, one staged table of the n
+// transform records followed by `tail_bytes` of the caller's own (the staging buffer holds one table per call; *d_tail: where
+// they lie on the device), the geometry, the 32 x 256 tile grid, and zeroed counters (pad_count, second; each may be NULL).
+int vstab_prepare_displaced(const char* who, vstab_ctx* ctx, WarpArgs& a, const float* src, int n, int sh, int sw,
+                            const float* matrices, int dh, int dw, const float* border, float* dst, float* mask,
+                            uint32_t* pad_count, uint32_t* second, const void* tail, size_t tail_bytes, const void** d_tail,
+                            unsigned* blocks);
 #endif  // VSTAB_WARP_ARITHMETIC

@@ -3,9 +3,10 @@
 // feature; both rules are stated in include/vstab.h.
 //
 // mesh_residual_kernel: one workgroup per (pair, vertex).  The grid samples of the four cells around the vertex are
-// tested, their residuals compacted into LDS (order does not matter to a median), and every thread counts the rank of its
-// elements against all others: the element of rank (n-1)/2 and the one of rank n/2 are the middle(s).  8 k samples per
-// pair at 960x540 -- microseconds; it is not where the time goes.
+// tested, their residuals (vstab_fit_residual) compacted into LDS (order does not matter to a median) and ranked by
+// counting (vstab_median_pair); both pieces and the entry point's common checks (vstab_check_residual, defined here) are
+// vstab_internal.h's, shared with the per-row form in vstab_rolling.hip.  8 k samples per pair at 960x540 -- microseconds;
+// it is not where the time goes.
 // Built with -ffp-contract=off like the rest of the library.
 #include "vstab_internal.h"
 #include <cmath>
@@ -24,13 +25,10 @@ struct MeshResidualArgs {
     int gh, gw, step, work_h, work_w, mw, mh, cap;
 };
 
-__device__ __forceinline__ bool finite_f(float v) { return __builtin_fabsf(v) <= 3.4028234663852886e38f; }   // false for NaN
-
 __global__ __launch_bounds__(MESH_THREADS) void mesh_residual_kernel(MeshResidualArgs a)
 {
     extern __shared__ float s_val[];       // [2][cap]: x residuals, y residuals
     __shared__ int s_n;
-    __shared__ float s_mid[2][2];          // [axis][lo, hi]
     float* s_rx = s_val;
     float* s_ry = s_val + a.cap;
     const int verts = a.mw * a.mh;
@@ -62,13 +60,8 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_residual_kernel(MeshResidua
         if (!(fabs(x - vx) < cw && fabs(y - vy) < ch)) continue;
         const size_t g = (size_t)gy * a.gw + gx;
         if (B0 != nullptr && (B0[g] | B1[g])) continue;
-        const float u = G[g * 2], v = G[g * 2 + 1];
-        const double X = (A[0] * x + A[1] * y) + A[2];
-        const double Y = (A[3] * x + A[4] * y) + A[5];
-        const double W = (A[6] * x + A[7] * y) + A[8];
-        const float rx = (float)((x + (double)u) - X / W);
-        const float ry = (float)((y + (double)v) - Y / W);
-        if (!(finite_f(u) && finite_f(v) && finite_f(rx) && finite_f(ry))) continue;
+        float rx, ry;
+        if (!vstab_fit_residual(A, x, y, G[g * 2], G[g * 2 + 1], rx, ry)) continue;
         const int slot = atomicAdd(&s_n, 1);
         if (slot < a.cap) { s_rx[slot] = rx; s_ry[slot] = ry; }     // (slot < cap always: rw * rh <= cap, checked on the host)
     }
@@ -79,40 +72,32 @@ __global__ __launch_bounds__(MESH_THREADS) void mesh_residual_kernel(MeshResidua
         if (threadIdx.x == 0) { out[0] = 0.f; out[1] = 0.f; a.count[(size_t)pair * verts + vert] = n; }
         return;
     }
-    // rank of element i: values below it, and equal values in front of it -- a permutation of 0..n-1
-    const int klo = (n - 1) >> 1, khi = n >> 1;
-    for (int i = threadIdx.x; i < n; i += MESH_THREADS) {
-#pragma unroll
-        for (int axis = 0; axis < 2; axis++) {
-            const float* __restrict__ s = axis ? s_ry : s_rx;
-            const float vi = s[i];
-            int rank = 0;
-            for (int j = 0; j < n; j++) {
-                const float vj = s[j];
-                rank += (vj < vi || (vj == vi && j < i)) ? 1 : 0;
-            }
-            if (rank == klo) s_mid[axis][0] = vi;
-            if (rank == khi) s_mid[axis][1] = vi;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        out[0] = (n & 1) ? s_mid[0][0] : (s_mid[0][0] + s_mid[0][1]) / 2.0f;
-        out[1] = (n & 1) ? s_mid[1][0] : (s_mid[1][0] + s_mid[1][1]) / 2.0f;
-        a.count[(size_t)pair * verts + vert] = n;
-    }
+    vstab_median_pair(s_rx, s_ry, n, out);
+    if (threadIdx.x == 0) a.count[(size_t)pair * verts + vert] = n;
 }
 
 }  // namespace
+
+int vstab_check_residual(const char* who, vstab_ctx* ctx, const void* grid_flow, const void* transitions, const void* residual,
+                         const void* count, int pairs, int gh, int gw, int step, int work_h, int work_w, long long per_pair,
+                         unsigned* blocks)
+{
+    VSTAB_REQUIRE(ctx != nullptr, "%s: ctx is NULL", who);
+    VSTAB_REQUIRE(grid_flow && transitions && residual && count, "%s: NULL pointer argument", who);
+    VSTAB_REQUIRE(pairs > 0 && step > 0 && work_h >= 2 && work_w >= 2, "%s: needs pairs > 0, step > 0 and an image of at least 2x2 (pairs=%d step=%d %dx%d)", who, pairs, step, work_w, work_h);
+    VSTAB_REQUIRE(gh == (work_h + step - 1) / step && gw == (work_w + step - 1) / step, "%s: grid %dx%d is not ceil(%dx%d / %d)", who, gw, gh, work_w, work_h, step);
+    VSTAB_REQUIRE(pairs * per_pair < 0x7fffffffLL, "%s: clip too large", who);
+    *blocks = (unsigned)(pairs * per_pair);
+    return 0;
+}
 
 extern "C" int vstab_mesh_residual_batch(vstab_ctx* ctx, const float* grid_flow, int pairs, int gh, int gw, int step, int work_h,
                                          int work_w, const float* transitions, const uint8_t* blocked, int mw, int mh,
                                          float* residual, int32_t* count)
 {
-    VSTAB_REQUIRE(ctx != nullptr, "vstab_mesh_residual_batch: ctx is NULL");
-    VSTAB_REQUIRE(grid_flow && transitions && residual && count, "vstab_mesh_residual_batch: NULL pointer argument");
-    VSTAB_REQUIRE(pairs > 0 && step > 0 && work_h >= 2 && work_w >= 2, "vstab_mesh_residual_batch: needs pairs > 0, step > 0 and an image of at least 2x2 (pairs=%d step=%d %dx%d)", pairs, step, work_w, work_h);
-    VSTAB_REQUIRE(gh == (work_h + step - 1) / step && gw == (work_w + step - 1) / step, "vstab_mesh_residual_batch: grid %dx%d is not ceil(%dx%d / %d)", gw, gh, work_w, work_h, step);
+    const char* who = "vstab_mesh_residual_batch";
+    unsigned blocks = 0;
+    if (int rc = vstab_check_residual(who, ctx, grid_flow, transitions, residual, count, pairs, gh, gw, step, work_h, work_w, (long long)mw * mh, &blocks)) return rc;
     VSTAB_REQUIRE(mw >= 2 && mh >= 2 && mw <= MESH_MAX_VERTS && mh <= MESH_MAX_VERTS, "vstab_mesh_residual_batch: %dx%d vertices outside 2..%d", mw, mh, MESH_MAX_VERTS);
     // the kernel's rectangle spans floor((v - c) / step) .. ceil((v + c) / step): at most 2c / step + 3 positions per axis
     const double cw = (double)(work_w - 1) / (double)(mw - 1), ch = (double)(work_h - 1) / (double)(mh - 1);
@@ -120,8 +105,6 @@ extern "C" int vstab_mesh_residual_batch(vstab_ctx* ctx, const float* grid_flow,
     const long long span_y = std::min<long long>(gh, (long long)std::floor(2.0 * ch / step) + 3);
     const long long cap = span_x * span_y;
     VSTAB_REQUIRE(cap <= MESH_MAX_NEIGHBOURHOOD, "vstab_mesh_residual_batch: a vertex neighbourhood of %lld grid positions exceeds %d (use a finer mesh)", cap, MESH_MAX_NEIGHBOURHOOD);
-    const long long blocks = (long long)pairs * mw * mh;
-    VSTAB_REQUIRE(blocks < 0x7fffffffLL, "vstab_mesh_residual_batch: clip too large");
     VSTAB_HIP(hipSetDevice(ctx->device));
     void* d_mats = nullptr;
     if (int rc = vstab_stage_params(ctx, transitions, (size_t)pairs * 9 * sizeof(float), &d_mats)) return rc;
@@ -132,7 +115,7 @@ extern "C" int vstab_mesh_residual_batch(vstab_ctx* ctx, const float* grid_flow,
     if (lds > 48 * 1024)
         VSTAB_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mesh_residual_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     KernelTimer timer(ctx, "mesh_residual");
-    hipLaunchKernelGGL(mesh_residual_kernel, dim3((unsigned)blocks), dim3(MESH_THREADS), lds, ctx->stream, a);
+    hipLaunchKernelGGL(mesh_residual_kernel, dim3(blocks), dim3(MESH_THREADS), lds, ctx->stream, a);
     VSTAB_HIP(hipGetLastError());
     return 0;
 }

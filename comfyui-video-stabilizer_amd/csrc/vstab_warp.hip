@@ -1,8 +1,9 @@
-// vstab_warp.hip -- perspective/similarity warp with padding mask, its mesh-displaced forms (mesh_warp_kernel and its
-// inverse, mesh_unwarp_kernel), the multi-sample motion blur and the coverage extent of the dynamic zoom
+// vstab_warp.hip -- perspective/similarity warp with padding mask, its mesh-displaced forms (warp_kernel with MeshWarpArgs and,
+// the inverse, MeshUnwarpArgs), the multi-sample motion blur and the coverage extent of the dynamic zoom
 // (cover_extent_kernel: warp_pixel's coverage bit alone, nothing sampled).
 // All of them take their coordinates from ONE definition, warp_pixel, and share one tile shell (TileShell, warp_kernel's
-// body, block_count_add).  Those, the samplers and the scalar pieces that vstab_crop / vstab_dis / vstab_tvl1 use too are in
+// body, block_count_add).  Those, the launch and preparation of the displaced forms (vstab_launch_displaced,
+// vstab_prepare_displaced: the rolling-shutter warps of vstab_rolling.hip go through them too), the samplers and the scalar pieces that vstab_crop / vstab_dis / vstab_tvl1 use too are in
 // vstab_internal.h (VSTAB_WARP_ARITHMETIC); the mesh displacements are here; the passes that sample OTHER frames of the clip
 // through the same arithmetic are in vstab_neighbour.hip.  profiles/warp_traffic.json is tied to the hash of this file and
 // vstab_internal.h: the warp's arithmetic stays in them.
@@ -22,31 +23,14 @@
 #define VSTAB_WARP_ARITHMETIC
 #include "vstab_internal.h"
 #include "vstab_wait.h"
-#include <type_traits>
 #include <cstdlib>
 
 namespace {
 
 constexpr int MAX_BLUR_SAMPLES = 33;
 
-// WarpXform (per frame / sample transform record), TILE_PX, the samplers, TileShell, XformRegs, warp_pixel and the scalar
-// pieces other translation units use too (clamp_round_i32, sat_short, vstab_nn_covered): vstab_internal.h
-
-struct WarpArgs {
-    const float* src;
-    float* dst;
-    float* mask;
-    unsigned* pad_count;
-    const WarpXform* xf;
-    int n, sh, sw, dh, dw;
-    int bw0;          // column block width of OpenCV's WarpPerspectiveInvoker
-    int bw0_pow2;     // 1 if bw0 is a power of two
-    int tiles_x, tiles_y;
-    int samples;      // 1 for the plain warp
-    int nxf_per_frame;  // sample matrices stored per frame (1 for a single-frame blur clip)
-    int blur_fast;      // blur: the interior fast path may be used (host-checked preconditions, see warp_blur_kernel)
-    float b0, b1, b2;   // border colour
-};
+// WarpXform (per frame / sample transform record), WarpArgs, TILE_PX, the samplers, TileShell, XformRegs, warp_pixel,
+// warp_kernel and the scalar pieces other translation units use too (clamp_round_i32, sat_short, vstab_nn_covered): vstab_internal.h
 
 // one axis of the mesh lookup: clamped coordinate -> cell index and fraction (the rule's operation order, include/vstab.h)
 __device__ __forceinline__ void mesh_cell(double q, int size, int verts, int* cell, double* frac)
@@ -115,9 +99,8 @@ struct MeshUnwarpArgs : MeshWarpArgs {
     unsigned* unconverged;  // [n] or nullptr
 };
 
-// The displacement a kernel's arguments ask for.  Plain warp: none.  Mesh warp: the frame's vertex table (mw * mh * 8 bytes:
-// 1.4 KB by default) is staged in LDS once per workgroup.
-__device__ __forceinline__ NoDisplacement make_displacement(const WarpArgs&, int) { return {}; }
+// The displacement the mesh arguments ask for (make_displacement, vstab_internal.h): the frame's vertex table (mw * mh * 8
+// bytes: 1.4 KB by default) is staged in LDS once per workgroup.
 __device__ __forceinline__ const float* stage_vertex_table(const MeshWarpArgs& a, int frame)
 {
     extern __shared__ float s_off[];      // this frame's vertex table [mh][mw][2]
@@ -136,96 +119,6 @@ __device__ __forceinline__ MeshInverseDisplacement make_displacement(const MeshU
 {
     return MeshInverseDisplacement{MeshDisplacement{stage_vertex_table(a, frame), a.dh, a.dw, a.mw, a.mh}};
 }
-
-// One 64 x 8 (TILE_TX = 32) tile of the warp: every pixel through warp_pixel, RGB + mask stored, padded pixels counted.
-// Args = WarpArgs is the plain warp, Args = MeshWarpArgs the mesh warp, Args = MeshUnwarpArgs its inverse (the rules are in
-// include/vstab.h): the same body with the displacement its arguments ask for.
-// The body stays in the kernel: inlined from a device function that receives the
-// arguments by reference, the compiler issued the two epilogue stores in another order and the plain warp ran 0.3-1 %
-// slower (profiles/r11_one_warp_arithmetic.md).
-template <int INTERP, int SUBPIX, bool WITH_MASK, int TILE_TX, class Args>
-__global__ __launch_bounds__(256) void warp_kernel(Args a)
-{
-    __shared__ __attribute__((aligned(16))) float s_cub[32 * 4];
-    const float* cub_tab = nullptr;
-    if (INTERP == VSTAB_INTERP_BICUBIC) {
-        if (threadIdx.x < 32) cubic_coeffs((int)threadIdx.x, s_cub + threadIdx.x * 4);
-        __syncthreads();
-        cub_tab = s_cub;
-    }
-    const TileShell<TILE_TX> t(a.tiles_x, a.tiles_y, a.dh, a.dw);
-    const int frame = t.frame, x0 = t.x0, y = t.y, npx = t.npx;
-    const auto disp = make_displacement(a, frame);
-    using Disp = std::remove_const_t<decltype(disp)>;
-    const float* __restrict__ S = a.src + (size_t)frame * a.sh * a.sw * 3;
-
-    float acc[TILE_PX][3];
-    float cov[TILE_PX];
-#pragma unroll
-    for (int p = 0; p < TILE_PX; p++) { acc[p][0] = acc[p][1] = acc[p][2] = 0.f; cov[p] = 0.f; }
-    unsigned unconv = 0;      // mesh unwarp only: this thread's pixels whose fixed point hit the step limit
-
-    if (t.active) {
-        const double dy = (double)y;
-        const WarpXform* __restrict__ xf = a.xf + frame;   // one matrix per frame (the S-sample blur is warp_blur_kernel)
-        const XformRegs<INTERP, SUBPIX> r(xf);
-#pragma unroll
-        for (int p = 0; p < TILE_PX; p++) {
-            if (p >= npx) continue;
-            const int x = x0 + p * TILE_TX;
-            float c = 0.f;
-            const Px v = warp_pixel<INTERP, SUBPIX, WITH_MASK>(
-                xf, r, a.sh, a.sw, a.dw, a.bw0, a.bw0_pow2, x, y, dy,
-                [&](int X, int Y) { return sample_q5<INTERP>(S, a.sh, a.sw, X, Y, a.b0, a.b1, a.b2, cub_tab); },
-                [&](float fsx, float fsy) { return sample_exact(S, a.sh, a.sw, fsx, fsy, a.b0, a.b1, a.b2); }, disp, c, &unconv);
-            acc[p][0] = v.r; acc[p][1] = v.g; acc[p][2] = v.b;
-            if (WITH_MASK) cov[p] = c;
-        }
-    }
-
-    // ---- epilogue ----
-    float mk[TILE_PX];
-    unsigned padded[1] = {0};
-#pragma unroll
-    for (int p = 0; p < TILE_PX; p++) {
-        float m = 1.0f - cov[p];
-        mk[p] = (m < 1e-3f) ? 0.f : m;
-        if (WITH_MASK && p < npx) padded[0] += (mk[p] > 0.5f) ? 1u : 0u;
-    }
-
-    if (t.active) {
-        // per-frame bases are uniform (scalar registers); inside a frame 32-bit element offsets suffice (the host checks
-        // that a frame has fewer than 2^30 pixels), which keeps the address arithmetic out of 64-bit VALU multiplies
-        float* __restrict__ D = a.dst + (size_t)frame * a.dh * a.dw * 3;
-        float* __restrict__ Mk = WITH_MASK ? a.mask + (size_t)frame * a.dh * a.dw : nullptr;
-        const unsigned row = (unsigned)y * (unsigned)a.dw;
-        typedef float f3 __attribute__((ext_vector_type(3)));
-#pragma unroll
-        for (int p = 0; p < TILE_PX; p++) {
-            if (p >= npx) continue;
-            const unsigned pix = row + (unsigned)(x0 + p * TILE_TX);
-            // 12 B per lane, consecutive lanes -> consecutive pixels: every store instruction writes whole lines
-            f3 rgb = {acc[p][0], acc[p][1], acc[p][2]};
-            __builtin_memcpy(D + pix * 3u, &rgb, 12);
-            if (WITH_MASK) Mk[pix] = mk[p];
-        }
-    }
-
-    if constexpr (Disp::OUTPUT) {
-        // two counters through one reduction (the conditions are kernel arguments: uniform)
-        if ((WITH_MASK && a.pad_count != nullptr) || a.unconverged != nullptr) {
-            unsigned counts[2] = {padded[0], unconv};
-            block_count_add<2>(counts, {WITH_MASK ? a.pad_count : nullptr, a.unconverged}, frame);
-        }
-    } else {
-        if (WITH_MASK && a.pad_count != nullptr) block_count_add<1>(padded, {a.pad_count}, frame);
-    }
-}
-
-template <int SUBPIX, bool WITH_MASK>
-constexpr auto mesh_warp_kernel = warp_kernel<VSTAB_INTERP_BILINEAR, SUBPIX, WITH_MASK, 32, MeshWarpArgs>;
-template <int SUBPIX, bool WITH_MASK>
-constexpr auto mesh_unwarp_kernel = warp_kernel<VSTAB_INTERP_BILINEAR, SUBPIX, WITH_MASK, 32, MeshUnwarpArgs>;
 
 // ---- coverage extent (dynamic zoom; the rule: vstab_cover_extent_batch in include/vstab.h) ------------------------------
 // How far the warp's own nearest-neighbour coverage reaches around the canvas centre: the minimum over a frame's uncovered
@@ -877,6 +770,27 @@ int vstab_stage_xforms(vstab_ctx* ctx, const float* m32, size_t count, const War
     return 0;
 }
 
+int vstab_prepare_displaced(const char* who, vstab_ctx* ctx, WarpArgs& a, const float* src, int n, int sh, int sw,
+                            const float* matrices, int dh, int dw, const float* border, float* dst, float* mask,
+                            uint32_t* pad_count, uint32_t* second, const void* tail, size_t tail_bytes, const void** d_tail,
+                            unsigned* blocks)
+{
+    VSTAB_HIP(hipSetDevice(ctx->device));
+    static_assert(sizeof(WarpXform) % sizeof(double) == 0, "what lies behind the records stays 8-byte aligned");
+    const size_t xf_bytes = (size_t)n * sizeof(WarpXform);
+    std::vector<unsigned char> table(xf_bytes + tail_bytes);
+    for (int i = 0; i < n; i++) vstab_fill_xform(matrices + (size_t)i * 9, reinterpret_cast<WarpXform*>(table.data()) + i);
+    if (tail_bytes) memcpy(table.data() + xf_bytes, tail, tail_bytes);
+    void* d_table = nullptr;
+    if (int rc = vstab_stage_params(ctx, table.data(), table.size(), &d_table)) return rc;
+    if (d_tail) *d_tail = static_cast<const unsigned char*>(d_table) + xf_bytes;
+    fill_geometry(a, src, static_cast<const WarpXform*>(d_table), n, sh, sw, dh, dw, border, dst, mask, pad_count);
+    if (int rc = vstab_tile_grid(who, n, dh, dw, 32, 256, &a.tiles_x, &a.tiles_y, blocks)) return rc;
+    if (pad_count) VSTAB_HIP(hipMemsetAsync(pad_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
+    if (second) VSTAB_HIP(hipMemsetAsync(second, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
+    return 0;
+}
+
 // ---- the counts' way to the host (see vstab_internal.h) ----
 namespace {
 __global__ __launch_bounds__(256) void mirror_counts_kernel(const uint32_t* __restrict__ counts, unsigned* host, int n, unsigned* flag, unsigned gen)
@@ -1017,7 +931,7 @@ extern "C" int vstab_warp_blur_batch(vstab_ctx* ctx, const float* src, int n, in
 }
 
 namespace {
-// vstab_mesh_warp_batch and vstab_mesh_unwarp_batch: the same checks, staging, grid and LDS; the kernel differs.
+// vstab_mesh_warp_batch and vstab_mesh_unwarp_batch: the same checks, preparation and LDS; the arguments' type differs.
 // domain_h x domain_w is the canvas the mesh lies over: the source (warp) or the output (unwarp).
 int mesh_launch(const char* who, const char* kind, bool inverse, vstab_ctx* ctx, const float* src, int n, int src_h, int src_w,
                 const float* matrices, int out_h, int out_w, const float* border_rgb, int subpix, const float* offsets, int mw,
@@ -1027,32 +941,15 @@ int mesh_launch(const char* who, const char* kind, bool inverse, vstab_ctx* ctx,
     VSTAB_REQUIRE(offsets != nullptr, "%s: NULL pointer argument", who);
     const int domain_h = inverse ? out_h : src_h, domain_w = inverse ? out_w : src_w;
     if (int rc = check_mesh(who, n, src_h, src_w, out_h, out_w, domain_h, domain_w, inverse ? "output" : "source", mw, mh)) return rc;
-    VSTAB_HIP(hipSetDevice(ctx->device));
-    const WarpXform* xf = nullptr;
-    if (vstab_stage_xforms(ctx, matrices, (size_t)n, &xf)) return 1;
     MeshUnwarpArgs a{};
-    fill_geometry(a, src, xf, n, src_h, src_w, out_h, out_w, border_rgb, dst, mask, pad_count);
-    a.offsets = offsets; a.mw = mw; a.mh = mh; a.unconverged = unconverged;
     unsigned blocks = 0;
-    if (int rc = vstab_tile_grid(who, n, out_h, out_w, 32, 256, &a.tiles_x, &a.tiles_y, &blocks)) return rc;
-    if (pad_count) VSTAB_HIP(hipMemsetAsync(pad_count, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
-    if (unconverged) VSTAB_HIP(hipMemsetAsync(unconverged, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));
+    if (int rc = vstab_prepare_displaced(who, ctx, a, src, n, src_h, src_w, matrices, out_h, out_w, border_rgb, dst, mask, pad_count,
+                                         unconverged, nullptr, 0, nullptr, &blocks)) return rc;
+    a.offsets = offsets; a.mw = mw; a.mh = mh; a.unconverged = unconverged;
     const size_t lds = (size_t)mw * mh * 2 * sizeof(float);    // <= 33.8 KB
-    const dim3 grid(blocks), block(256);
     KernelTimer timer(ctx, kind);
-#define LAUNCH_MESH(KERNEL, ARGS)                                                                                          \
-    do {                                                                                                                   \
-        if (subpix == VSTAB_SUBPIX_EXACT) {                                                                                \
-            if (mask) hipLaunchKernelGGL((KERNEL<VSTAB_SUBPIX_EXACT, true>), grid, block, lds, ctx->stream, ARGS);         \
-            else hipLaunchKernelGGL((KERNEL<VSTAB_SUBPIX_EXACT, false>), grid, block, lds, ctx->stream, ARGS);             \
-        } else {                                                                                                           \
-            if (mask) hipLaunchKernelGGL((KERNEL<VSTAB_SUBPIX_Q5, true>), grid, block, lds, ctx->stream, ARGS);            \
-            else hipLaunchKernelGGL((KERNEL<VSTAB_SUBPIX_Q5, false>), grid, block, lds, ctx->stream, ARGS);                \
-        }                                                                                                                  \
-    } while (0)
-    if (inverse) LAUNCH_MESH(mesh_unwarp_kernel, a);
-    else LAUNCH_MESH(mesh_warp_kernel, static_cast<const MeshWarpArgs&>(a));
-#undef LAUNCH_MESH
+    if (inverse) vstab_launch_displaced<MeshUnwarpArgs>(a, blocks, subpix, mask != nullptr, lds, ctx->stream);
+    else vstab_launch_displaced<MeshWarpArgs>(a, blocks, subpix, mask != nullptr, lds, ctx->stream);
     VSTAB_HIP(hipGetLastError());
     return 0;
 }
@@ -1089,15 +986,12 @@ extern "C" int vstab_cover_extent_batch(vstab_ctx* ctx, const float* matrices, i
     if (offsets != nullptr) {
         if (int rc = check_mesh(who, n, src_h, src_w, out_h, out_w, src_h, src_w, "source", mw, mh)) return rc;
     }
-    VSTAB_HIP(hipSetDevice(ctx->device));
-    const WarpXform* xf = nullptr;
-    if (vstab_stage_xforms(ctx, matrices, (size_t)n, &xf)) return 1;
     const float no_border[3] = {0.f, 0.f, 0.f};
     MeshWarpArgs a{};
-    fill_geometry(a, nullptr, xf, n, src_h, src_w, out_h, out_w, no_border, nullptr, nullptr, nullptr);
-    a.offsets = offsets; a.mw = mw; a.mh = mh;
     unsigned blocks = 0;
-    if (int rc = vstab_tile_grid(who, n, out_h, out_w, 32, 256, &a.tiles_x, &a.tiles_y, &blocks)) return rc;
+    if (int rc = vstab_prepare_displaced(who, ctx, a, nullptr, n, src_h, src_w, matrices, out_h, out_w, no_border, nullptr, nullptr,
+                                         nullptr, nullptr, nullptr, 0, nullptr, &blocks)) return rc;
+    a.offsets = offsets; a.mw = mw; a.mh = mh;
     const dim3 grid(blocks), block(256);
     KernelTimer timer(ctx, "cover_extent");
     hipLaunchKernelGGL(extent_preset_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, extent, n);

@@ -3,7 +3,7 @@ breathing), after MeshFlow (Liu et al., ECCV 2016: per-vertex motion profiles).
 
 The device side: `native.Context.mesh_residual_batch` (csrc/vstab_mesh.hip) reduces the stride-8 flow grid a Flow run
 already has to one residual per mesh vertex and pair, `native.Context.mesh_warp_batch` (csrc/vstab_warp.hip:
-mesh_warp_kernel) is the plain warp with a per-vertex displacement of the source frame (include/vstab.h states both
+warp_kernel with MeshWarpArgs) is the plain warp with a per-vertex displacement of the source frame (include/vstab.h states both
 rules). This module is the host side between the two: the checks of a request and the vertex paths. Nothing here needs
 a GPU.
 

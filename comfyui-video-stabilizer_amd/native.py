@@ -793,15 +793,8 @@ class Context:
         device tensors."""
         torch = self.torch
         mw, mh = self._check_mesh("mesh_residual_batch", mw, mh)
-        if grid_flow.dtype != torch.float32 or grid_flow.dim() != 4 or grid_flow.shape[3] != 2:
-            raise ValueError("mesh_residual_batch expects a float32 [P,gh,gw,2] tensor")
-        grid_flow, blocked, pairs, gh, gw = self._fit_inputs(grid_flow, blocked)
-        ww, wh, step = int(work_size[0]), int(work_size[1]), int(step)
-        if step < 1 or (gh, gw) != ((wh + step - 1) // step, (ww + step - 1) // step):
-            raise ValueError(f"mesh_residual_batch: a grid of {gw}x{gh} samples is not a {ww}x{wh} image at step {step}")
-        m = np.ascontiguousarray(transitions, dtype=np.float32)
-        if m.size != pairs * 9:
-            raise ValueError(f"mesh_residual_batch: transitions {m.shape} are not [{pairs},3,3]")
+        grid_flow, blocked, pairs, gh, gw, step, wh, ww, m = self._residual_inputs(
+            "mesh_residual_batch", grid_flow, step, work_size, transitions, blocked)
         residual = torch.empty((pairs, mh, mw, 2), dtype=torch.float32, device=self.device)
         count = torch.empty((pairs, mh, mw), dtype=torch.int32, device=self.device)
         self.use_torch_stream()
@@ -810,6 +803,20 @@ class Context:
             _dev_ptr(blocked) if blocked is not None else None, mw, mh, _dev_ptr(residual), _dev_ptr(count)),
             "vstab_mesh_residual_batch")
         return residual, count
+
+    def _residual_inputs(self, who, grid_flow, step, work_size, transitions, blocked):
+        """What mesh_residual_batch and row_residual_batch check alike: the grid flow, its grid against the working size at
+        `step`, the transitions.  -> (grid_flow, blocked, pairs, gh, gw, step, work_h, work_w, transitions f32)"""
+        if grid_flow.dtype != self.torch.float32 or grid_flow.dim() != 4 or grid_flow.shape[3] != 2:
+            raise ValueError(f"{who} expects a float32 [P,gh,gw,2] tensor")
+        grid_flow, blocked, pairs, gh, gw = self._fit_inputs(grid_flow, blocked)
+        ww, wh, step = int(work_size[0]), int(work_size[1]), int(step)
+        if step < 1 or (gh, gw) != ((wh + step - 1) // step, (ww + step - 1) // step):
+            raise ValueError(f"{who}: a grid of {gw}x{gh} samples is not a {ww}x{wh} image at step {step}")
+        m = np.ascontiguousarray(transitions, dtype=np.float32)
+        if m.size != pairs * 9:
+            raise ValueError(f"{who}: transitions {m.shape} are not [{pairs},3,3]")
+        return grid_flow, blocked, pairs, gh, gw, step, wh, ww, m
 
     def _mesh_offsets(self, who, offsets, n):
         """offsets f32 [n,mh,mw,2] (host or device) -> (contiguous device tensor, mw, mh)."""
@@ -826,16 +833,28 @@ class Context:
         """warp_batch (bilinear) with a per-vertex displacement of the source frame (vstab_mesh_warp_batch; the rule is in
         include/vstab.h).  offsets f32 [N,mh,mw,2] in full-resolution px (host or device) ->
         (dst [N,h,w,3], mask [N,h,w] | None, counts [N] | None).  All-zero offsets give warp_batch's bits."""
-        src, (n, sh, sw), (out_h, out_w), b, dst, mask, counts = self._warp_io(
-            "mesh_warp_batch", frames, out_size, border, want_mask, want_count)
-        offsets, mw, mh = self._mesh_offsets("mesh_warp_batch", offsets, n)
+        return self._displaced_warp("mesh_warp_batch", frames, matrices, out_size, border, subpix, want_mask, want_count,
+                                    lambda n: self._mesh_offsets("mesh_warp_batch", offsets, n))
+
+    def _displaced_warp(self, name, frames, matrices, out_size, border, subpix, want_mask, want_count, own, want_second=()):
+        """The wrapper of the displaced warps (vstab_<name>: the mesh and rolling-shutter forms and their inverses).  own(n) ->
+        the entry point's own arguments, between subpix and dst (a tensor goes as its device pointer, an array as its host
+        pointer); want_second: () for a forward form, (flag,) for an inverse, whose second counter i32 [N] | None is appended
+        to (dst, mask, counts)."""
+        torch = self.torch
+        src, (n, sh, sw), (out_h, out_w), b, dst, mask, counts = self._warp_io(name, frames, out_size, border, want_mask, want_count)
+        own = own(n)
+        second = tuple(torch.empty((n,), dtype=torch.int32, device=self.device) if want else None for want in want_second)
         m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(n, 9)
+
+        def arg(v):
+            return _dev_ptr(v) if isinstance(v, torch.Tensor) else v.ctypes.data if isinstance(v, np.ndarray) else v
+
         self.use_torch_stream()
-        _check(self.lib.vstab_mesh_warp_batch(
+        _check(getattr(self.lib, "vstab_" + name)(
             self.handle, _dev_ptr(src), n, sh, sw, m.ctypes.data, out_h, out_w, b.ctypes.data, SUBPIX[subpix or DEFAULT_SUBPIX],
-            _dev_ptr(offsets), mw, mh, _dev_ptr(dst), _dev_ptr(mask) if mask is not None else None,
-            _dev_ptr(counts) if counts is not None else None), "vstab_mesh_warp_batch")
-        return dst, mask, counts
+            *(arg(v) for v in own), _dev_ptr(dst), *(arg(v) for v in (mask, counts) + second)), "vstab_" + name)
+        return (dst, mask, counts) + second
 
     def mesh_unwarp_batch(self, frames, matrices, out_size, offsets, border=(0.0, 0.0, 0.0), subpix=None, want_mask=True,
                           want_count=False, want_unconverged=False):
@@ -844,18 +863,8 @@ class Context:
         [N,mh,mw,2] in px of the OUTPUT canvas (host or device) -> (dst [N,h,w,3], mask [N,h,w] | None, counts [N] | None,
         unconverged [N] i32 | None: pixels per frame whose fixed point hit the step limit).  All-zero offsets give
         warp_batch's bits."""
-        src, (n, sh, sw), (out_h, out_w), b, dst, mask, counts = self._warp_io(
-            "mesh_unwarp_batch", frames, out_size, border, want_mask, want_count)
-        offsets, mw, mh = self._mesh_offsets("mesh_unwarp_batch", offsets, n)
-        unconverged = self.torch.empty((n,), dtype=self.torch.int32, device=self.device) if want_unconverged else None
-        m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(n, 9)
-        self.use_torch_stream()
-        _check(self.lib.vstab_mesh_unwarp_batch(
-            self.handle, _dev_ptr(src), n, sh, sw, m.ctypes.data, out_h, out_w, b.ctypes.data, SUBPIX[subpix or DEFAULT_SUBPIX],
-            _dev_ptr(offsets), mw, mh, _dev_ptr(dst), _dev_ptr(mask) if mask is not None else None,
-            _dev_ptr(counts) if counts is not None else None,
-            _dev_ptr(unconverged) if unconverged is not None else None), "vstab_mesh_unwarp_batch")
-        return dst, mask, counts, unconverged
+        return self._displaced_warp("mesh_unwarp_batch", frames, matrices, out_size, border, subpix, want_mask, want_count,
+                                    lambda n: self._mesh_offsets("mesh_unwarp_batch", offsets, n), (want_unconverged,))
 
     # ------------------------------------------------------------------ rolling shutter
     def rolling_warp_batch(self, frames, matrices, out_size, velocity, readout, border=(0.0, 0.0, 0.0), subpix=None,
@@ -864,16 +873,8 @@ class Context:
         showed it (vstab_rolling_warp_batch; the rule is in include/vstab.h).  velocity f64 [N,6] (host), full-resolution px per
         frame interval; readout in [-1, 1] -> (dst [N,h,w,3], mask [N,h,w] | None, counts [N] | None).  All-zero velocity or
         readout == 0 give warp_batch's bits."""
-        src, (n, sh, sw), (out_h, out_w), b, dst, mask, counts = self._warp_io(
-            "rolling_warp_batch", frames, out_size, border, want_mask, want_count)
-        v, readout = self._rolling_inputs("rolling_warp_batch", velocity, readout, n)
-        m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(n, 9)
-        self.use_torch_stream()
-        _check(self.lib.vstab_rolling_warp_batch(
-            self.handle, _dev_ptr(src), n, sh, sw, m.ctypes.data, out_h, out_w, b.ctypes.data, SUBPIX[subpix or DEFAULT_SUBPIX],
-            v.ctypes.data, readout, _dev_ptr(dst), _dev_ptr(mask) if mask is not None else None,
-            _dev_ptr(counts) if counts is not None else None), "vstab_rolling_warp_batch")
-        return dst, mask, counts
+        return self._displaced_warp("rolling_warp_batch", frames, matrices, out_size, border, subpix, want_mask, want_count,
+                                    lambda n: self._rolling_inputs("rolling_warp_batch", velocity, readout, n))
 
     @staticmethod
     def _rolling_inputs(who, velocity, readout, n, null_ok=False):
@@ -894,33 +895,17 @@ class Context:
         matrix.  velocity f64 [N,6] (host) and readout as rolling_warp_batch's; the row lever is the OUTPUT canvas's height ->
         (dst [N,h,w,3], mask [N,h,w] | None, counts [N] | None, unsolved [N] i32 | None: pixels per frame whose solve was
         refused and that were warped by the matrix alone).  All-zero velocity or readout == 0 give warp_batch's bits."""
-        src, (n, sh, sw), (out_h, out_w), b, dst, mask, counts = self._warp_io(
-            "rolling_unwarp_batch", frames, out_size, border, want_mask, want_count)
-        v, readout = self._rolling_inputs("rolling_unwarp_batch", velocity, readout, n, null_ok=True)
-        unsolved = self.torch.empty((n,), dtype=self.torch.int32, device=self.device) if want_unsolved else None
-        m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(n, 9)
-        self.use_torch_stream()
-        _check(self.lib.vstab_rolling_unwarp_batch(
-            self.handle, _dev_ptr(src), n, sh, sw, m.ctypes.data, out_h, out_w, b.ctypes.data, SUBPIX[subpix or DEFAULT_SUBPIX],
-            v.ctypes.data if v is not None else None, readout, _dev_ptr(dst), _dev_ptr(mask) if mask is not None else None,
-            _dev_ptr(counts) if counts is not None else None,
-            _dev_ptr(unsolved) if unsolved is not None else None), "vstab_rolling_unwarp_batch")
-        return dst, mask, counts, unsolved
+        return self._displaced_warp(
+            "rolling_unwarp_batch", frames, matrices, out_size, border, subpix, want_mask, want_count,
+            lambda n: self._rolling_inputs("rolling_unwarp_batch", velocity, readout, n, null_ok=True), (want_unsolved,))
 
     def row_residual_batch(self, grid_flow, step, work_size, transitions, blocked=None):
         """Per-row median of the global fit's residual (vstab_row_residual_batch; the rule is in include/vstab.h).
         grid_flow f32 [P,gh,gw,2] (device), work_size = (w, h) of the estimation images, transitions f32 [P,3,3] at working
         resolution, blocked u8 [P+1,gh,gw] or None -> (residual f32 [P,gh,2], count i32 [P,gh]), device tensors."""
         torch = self.torch
-        if grid_flow.dtype != torch.float32 or grid_flow.dim() != 4 or grid_flow.shape[3] != 2:
-            raise ValueError("row_residual_batch expects a float32 [P,gh,gw,2] tensor")
-        grid_flow, blocked, pairs, gh, gw = self._fit_inputs(grid_flow, blocked)
-        ww, wh, step = int(work_size[0]), int(work_size[1]), int(step)
-        if step < 1 or (gh, gw) != ((wh + step - 1) // step, (ww + step - 1) // step):
-            raise ValueError(f"row_residual_batch: a grid of {gw}x{gh} samples is not a {ww}x{wh} image at step {step}")
-        m = np.ascontiguousarray(transitions, dtype=np.float32)
-        if m.size != pairs * 9:
-            raise ValueError(f"row_residual_batch: transitions {m.shape} are not [{pairs},3,3]")
+        grid_flow, blocked, pairs, gh, gw, step, wh, ww, m = self._residual_inputs(
+            "row_residual_batch", grid_flow, step, work_size, transitions, blocked)
         residual = torch.empty((pairs, gh, 2), dtype=torch.float32, device=self.device)
         count = torch.empty((pairs, gh), dtype=torch.int32, device=self.device)
         self.use_torch_stream()

@@ -103,6 +103,10 @@ def test_rolling_warp_equals_the_restatement(pkg, ctx, subpix, size, out_size):
             no_mask = ctx.rolling_warp_batch(dev_frames, mats, out_size, vel, rho, border=border, subpix=subpix, want_mask=False)
             assert no_mask[1] is None and no_mask[2] is None
             assert np.array_equal(_bits(no_mask[0].cpu().numpy()), _bits(want))
+            no_count = ctx.rolling_warp_batch(dev_frames, mats, out_size, vel, rho, border=border, subpix=subpix, want_count=False)
+            assert no_count[2] is None                                         # the mask without the count reduction
+            assert torch.equal(no_count[0].view(torch.int32), got.view(torch.int32))
+            assert torch.equal(no_count[1].view(torch.int32), got_mask.view(torch.int32))
             plain, plain_mask, plain_cnt = ctx.warp_batch(dev_frames, mats, out_size, interp="bilinear", border=border, subpix=subpix,
                                                           want_mask=True, want_count=True)
             for i, kind in enumerate(kinds):
