@@ -1,5 +1,6 @@
 // vstab_anchor.hip -- drift correction: the normal equations of aligning every frame to its keyframe, as exact integer sums
-// (vstab_anchor_sums_batch).  Not a reference feature; the rule is stated in include/vstab.h.
+// (vstab_anchor_sums_batch), and the same with a gain and an offset per frame, two more regression columns and the estimation
+// mask's block grid (vstab_anchor_sums_ex_batch).  Not a reference feature; both rules are stated in include/vstab.h.
 //
 // One kernel, shaped after pair_residual_kernel (vstab_cut.hip).  A workgroup owns ANCHOR_ROWS template rows of one frame;
 // a lane takes 16 template pixels with one 16-byte load per row (the row itself and its two neighbours for the vertical
@@ -14,6 +15,11 @@
 // 2 * 255 * 1023 = 521730 < 2^19 (int32), |r| <= 261120 < 2^18, a product J_j J_k < 2^38 and J_k r < 2^37 (formed in 64
 // bits), and at most 1022^2 < 2^20 pixels take part: |sum J_j J_k| < 2^58, |sum J_k r| < 2^57, sum |r| < 2^38.  Nothing
 // reaches 2^59, for a lane, a workgroup or a frame.
+//
+// The second kernel is the first with 31 lane sums: it walks the template with the same loop (anchor_walk) and takes the sample
+// with the same code (anchor_tap).  Its bounds: |G T + O| <= 4096 * 255 + 2^20 < 2^21 and v < 2^18, so r fits an int; a counted
+// pixel has |r| <= 1024 * 255 < 2^18 by the cap test itself, and the new columns J4 = T <= 255 and J5 = 1 are smaller than the
+// old ones, so every product and every sum stays below the bounds above.
 #include "vstab_internal.h"
 
 namespace {
@@ -22,6 +28,7 @@ constexpr int ANCHOR_ROWS = 16;     // template rows per workgroup (960x540: 34 
 constexpr int ANCHOR_THREADS = 256;
 constexpr int ANCHOR_WAVES = ANCHOR_THREADS / 64;
 constexpr int ANCHOR_SLOTS = VSTAB_ANCHOR_SLOTS;
+constexpr int ANCHOR_EX_SLOTS = VSTAB_ANCHOR_EX_SLOTS;
 
 struct AnchorAcc {
     long long count = 0, capped = 0, sum_abs = 0;
@@ -33,22 +40,31 @@ struct AnchorMatrix {
     double r0, r1, r2, r3, r4, r5;
 };
 
-// one template pixel of the rule: t = T[y,x], l / r / up / dn its four neighbours, img = the frame's image
-__device__ __forceinline__ void anchor_pixel(AnchorAcc& a, const AnchorMatrix& R, const uint8_t* __restrict__ img, int x, int y,
-                                             int h, int w, int cap1024, int t, int l, int r, int up, int dn)
+// steps 1-5 of both rules for one template pixel: the sample position in Q5 and the bilinear integer v of the frame's image;
+// false where the pixel does not take part (outside the frame, or a position that is not finite)
+__device__ __forceinline__ bool anchor_tap(const AnchorMatrix& R, const uint8_t* __restrict__ img, int x, int y, int h, int w, int& ix,
+                                           int& iy, int& v)
 {
     const double dx = (double)x, dy = (double)y;
     const double X = (R.r0 * dx + R.r1 * dy) + R.r2;
     const double Y = (R.r3 * dx + R.r4 * dy) + R.r5;
     const double fix = rint(32.0 * X), fiy = rint(32.0 * Y);    // half-to-even; NaN / inf fail the comparisons below
-    if (!(fix >= 0.0 && fix <= (double)(32 * (w - 1)) && fiy >= 0.0 && fiy <= (double)(32 * (h - 1)))) return;
-    const int ix = (int)fix, iy = (int)fiy;
+    if (!(fix >= 0.0 && fix <= (double)(32 * (w - 1)) && fiy >= 0.0 && fiy <= (double)(32 * (h - 1)))) return false;
+    ix = (int)fix, iy = (int)fiy;
     const int x0 = ix >> 5, fx = ix & 31, x1 = min(x0 + 1, w - 1);
     const int y0 = iy >> 5, fy = iy & 31, y1 = min(y0 + 1, h - 1);
     const uint8_t* __restrict__ r0 = img + (size_t)y0 * w;
     const uint8_t* __restrict__ r1 = img + (size_t)y1 * w;
-    const int v = (32 - fx) * (32 - fy) * (int)r0[x0] + fx * (32 - fy) * (int)r0[x1] + (32 - fx) * fy * (int)r1[x0] +
-                  fx * fy * (int)r1[x1];
+    v = (32 - fx) * (32 - fy) * (int)r0[x0] + fx * (32 - fy) * (int)r0[x1] + (32 - fx) * fy * (int)r1[x0] + fx * fy * (int)r1[x1];
+    return true;
+}
+
+// one template pixel of the rule: t = T[y,x], l / r / up / dn its four neighbours, img = the frame's image
+__device__ __forceinline__ void anchor_pixel(AnchorAcc& a, const AnchorMatrix& R, const uint8_t* __restrict__ img, int x, int y,
+                                             int h, int w, int cap1024, int t, int l, int r, int up, int dn)
+{
+    int ix, iy, v;
+    if (!anchor_tap(R, img, x, y, h, w, ix, iy, v)) return;
     const int res = v - 1024 * t;
     // (both counters are added to without a branch: behind `if (over) capped += 1; else count += 1` the compiler selects
     // between the addresses of the two and puts them into scratch memory)
@@ -75,6 +91,54 @@ __device__ __forceinline__ void anchor_pixel(AnchorAcc& a, const AnchorMatrix& R
     a.h33 += (long long)j3 * j3;
 }
 
+// the exposure-matched, masked rule (vstab_anchor_sums_ex_batch): the frame's gain and offset, and the two frames' block grids
+struct AnchorExFrame {
+    int gain, offset;                       // G in 1/1024, O in 1/1024 grey level
+    const uint8_t* __restrict__ blocked_t;  // the anchor's [gh,gw] grid and the frame's (MASK only)
+    const uint8_t* __restrict__ blocked_i;
+    int step, gh, gw;
+};
+
+struct AnchorExAcc {
+    long long count = 0, capped = 0, masked = 0, sum_abs = 0;
+    long long b[6] = {0, 0, 0, 0, 0, 0};
+    long long hh[21] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // J_j J_k, j <= k, row-major
+};
+
+template <bool MASK>
+__device__ __forceinline__ void anchor_pixel_ex(AnchorExAcc& a, const AnchorMatrix& R, const AnchorExFrame& f,
+                                                const uint8_t* __restrict__ img, int x, int y, int h, int w, int cap1024, int t, int l,
+                                                int r, int up, int dn)
+{
+    int ix, iy, v;
+    if (!anchor_tap(R, img, x, y, h, w, ix, iy, v)) return;
+    int hidden = 0;
+    if (MASK) {
+        const int half = f.step >> 1;
+        const int ty = min((y + half) / f.step, f.gh - 1), tx = min((x + half) / f.step, f.gw - 1);
+        const int xn = min((ix + 16) >> 5, w - 1), yn = min((iy + 16) >> 5, h - 1);
+        const int sy = min((yn + half) / f.step, f.gh - 1), sx = min((xn + half) / f.step, f.gw - 1);
+        hidden = (f.blocked_t[ty * f.gw + tx] | f.blocked_i[sy * f.gw + sx]) != 0 ? 1 : 0;
+    }
+    const int res = v - (f.gain * t + f.offset);        // |G T + O| < 2^21
+    // (the three counters are added to without a branch, as anchor_pixel's two are)
+    const int over = (1 - hidden) & (abs(res) > cap1024 ? 1 : 0);
+    a.masked += hidden;
+    a.capped += over;
+    a.count += 1 - hidden - over;
+    if (hidden | over) return;
+    const int gx = r - l, gy = dn - up, u = 2 * x - (w - 1), q = 2 * y - (h - 1);
+    const int j[6] = {gx, gy, gx * u + gy * q, gy * u - gx * q, t, 1};
+    a.sum_abs += abs(res);
+    int slot = 0;
+#pragma unroll
+    for (int m = 0; m < 6; m++) {
+        a.b[m] += (long long)j[m] * res;
+#pragma unroll
+        for (int k = m; k < 6; k++) a.hh[slot++] += (long long)j[m] * j[k];
+    }
+}
+
 __device__ __forceinline__ int byte_of(const uint4& v, int k)
 {
     const unsigned word = (k < 4) ? v.x : (k < 8) ? v.y : (k < 12) ? v.z : v.w;
@@ -85,6 +149,37 @@ __device__ __forceinline__ long long wave_sum(long long v)
 {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
     return v;
+}
+
+// A workgroup's template pixels: `rows` rows from y_first, in 16-pixel pieces, one piece per lane and step.
+// pixel(x, y, t, l, r, up, dn) gets every pixel with 1 <= x <= w-2 and its four neighbours.
+// VEC: w % 16 == 0 and the base 16-byte aligned (every row of every frame then is)
+template <bool VEC, class Pixel>
+__device__ __forceinline__ void anchor_walk(const uint8_t* __restrict__ tmpl, int y_first, int rows, int w, Pixel pixel)
+{
+    const int chunks = (w + 15) >> 4;                   // 16-pixel pieces of a row
+    for (int item = threadIdx.x; item < rows * chunks; item += ANCHOR_THREADS) {
+        const int r = item / chunks, c = item - r * chunks;
+        const int y = y_first + r, xa = c << 4;
+        const uint8_t* __restrict__ row = tmpl + (size_t)y * w;
+        const int xs = max(xa, 1), xe = min(xa + 16, w - 1);   // the piece's pixels with 1 <= x <= w-2
+        if (VEC) {
+            const uint4 mid = *reinterpret_cast<const uint4*>(row + xa);
+            const uint4 upv = *reinterpret_cast<const uint4*>(row - w + xa);
+            const uint4 dnv = *reinterpret_cast<const uint4*>(row + w + xa);
+            const int before = xa > 0 ? (int)row[xa - 1] : 0, after = xa + 16 < w ? (int)row[xa + 16] : 0;
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                const int x = xa + k;
+                if (x >= xs && x < xe)
+                    pixel(x, y, byte_of(mid, k), k == 0 ? before : byte_of(mid, k - 1), k == 15 ? after : byte_of(mid, k + 1),
+                          byte_of(upv, k), byte_of(dnv, k));
+            }
+        } else {
+            for (int x = xs; x < xe; x++)
+                pixel(x, y, (int)row[x], (int)row[x - 1], (int)row[x + 1], (int)row[x - w], (int)row[x + w]);
+        }
+    }
 }
 
 // VEC: w % 16 == 0 and the base 16-byte aligned (every row of every frame then is)
@@ -102,31 +197,10 @@ __global__ __launch_bounds__(ANCHOR_THREADS) void anchor_sums_kernel(const uint8
     const AnchorMatrix R = {mat[0], mat[1], mat[2], mat[3], mat[4], mat[5]};
     const uint8_t* __restrict__ tmpl = gray + (size_t)anchor * h * w;
     const uint8_t* __restrict__ img = gray + (size_t)frame * h * w;
-    const int chunks = (w + 15) >> 4;                   // 16-pixel pieces of a row
     AnchorAcc acc;
-    for (int item = threadIdx.x; item < rows * chunks; item += ANCHOR_THREADS) {
-        const int r = item / chunks, c = item - r * chunks;
-        const int y = y_first + r, xa = c << 4;
-        const uint8_t* __restrict__ row = tmpl + (size_t)y * w;
-        const int xs = max(xa, 1), xe = min(xa + 16, w - 1);   // the piece's pixels with 1 <= x <= w-2
-        if (VEC) {
-            const uint4 mid = *reinterpret_cast<const uint4*>(row + xa);
-            const uint4 upv = *reinterpret_cast<const uint4*>(row - w + xa);
-            const uint4 dnv = *reinterpret_cast<const uint4*>(row + w + xa);
-            const int before = xa > 0 ? (int)row[xa - 1] : 0, after = xa + 16 < w ? (int)row[xa + 16] : 0;
-#pragma unroll
-            for (int k = 0; k < 16; k++) {
-                const int x = xa + k;
-                if (x >= xs && x < xe)
-                    anchor_pixel(acc, R, img, x, y, h, w, cap1024, byte_of(mid, k), k == 0 ? before : byte_of(mid, k - 1),
-                                 k == 15 ? after : byte_of(mid, k + 1), byte_of(upv, k), byte_of(dnv, k));
-            }
-        } else {
-            for (int x = xs; x < xe; x++)
-                anchor_pixel(acc, R, img, x, y, h, w, cap1024, (int)row[x], (int)row[x - 1], (int)row[x + 1], (int)row[x - w],
-                             (int)row[x + w]);
-        }
-    }
+    anchor_walk<VEC>(tmpl, y_first, rows, w, [&](int x, int y, int t, int l, int r, int up, int dn) {
+        anchor_pixel(acc, R, img, x, y, h, w, cap1024, t, l, r, up, dn);
+    });
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int slot = 0;
     auto put = [&](long long lane_sum) {                // the slots in the order of the rule's step 10
@@ -148,7 +222,102 @@ __global__ __launch_bounds__(ANCHOR_THREADS) void anchor_sums_kernel(const uint8
     }
 }
 
+// The exposure-matched, masked rule: anchor_sums_kernel's shape with 31 lane sums.  `params` holds the anchors, the gains
+// and the offsets of all frames, n each.  MASK: the two block-grid bytes are read (a kernel-uniform choice, made at the launch).
+template <bool VEC, bool MASK>
+__global__ __launch_bounds__(ANCHOR_THREADS) void anchor_sums_ex_kernel(const uint8_t* __restrict__ gray, const double* __restrict__ mats,
+                                                                         const int* __restrict__ params, int n, int h, int w, int tiles,
+                                                                         int cap1024, const uint8_t* __restrict__ blocked, int step,
+                                                                         int gh, int gw, long long* __restrict__ out)
+{
+    __shared__ long long s_part[ANCHOR_WAVES][ANCHOR_EX_SLOTS];
+    const int frame = (int)blockIdx.x / tiles, tile = (int)blockIdx.x - frame * tiles;
+    const int anchor = params[frame];
+    if (anchor < 0) return;                             // the whole workgroup: no barrier has been reached
+    const int y_first = 1 + tile * ANCHOR_ROWS, rows = min(ANCHOR_ROWS, (h - 1) - y_first);   // template rows 1..h-2
+    const double* __restrict__ mat = mats + (size_t)frame * 6;
+    const AnchorMatrix R = {mat[0], mat[1], mat[2], mat[3], mat[4], mat[5]};
+    const uint8_t* __restrict__ tmpl = gray + (size_t)anchor * h * w;
+    const uint8_t* __restrict__ img = gray + (size_t)frame * h * w;
+    const AnchorExFrame f = {params[n + frame], params[2 * n + frame], MASK ? blocked + (size_t)anchor * gh * gw : nullptr,
+                             MASK ? blocked + (size_t)frame * gh * gw : nullptr, step, gh, gw};
+    AnchorExAcc acc;
+    anchor_walk<VEC>(tmpl, y_first, rows, w, [&](int x, int y, int t, int l, int r, int up, int dn) {
+        anchor_pixel_ex<MASK>(acc, R, f, img, x, y, h, w, cap1024, t, l, r, up, dn);
+    });
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int slot = 0;
+    auto put = [&](long long lane_sum) {                // the slots in the order of the rule's output
+        const long long total = wave_sum(lane_sum);
+        if (lane == 0) s_part[wave][slot] = total;
+        slot += 1;
+    };
+    put(acc.count), put(acc.capped), put(acc.masked), put(acc.sum_abs);
+#pragma unroll
+    for (int k = 0; k < 6; k++) put(acc.b[k]);
+#pragma unroll
+    for (int k = 0; k < 21; k++) put(acc.hh[k]);
+    __syncthreads();
+    if (threadIdx.x < ANCHOR_EX_SLOTS) {
+        long long touched = 0, total = 0;
+        for (int k = 0; k < ANCHOR_WAVES; k++) {
+            touched += s_part[k][0] + s_part[k][1] + s_part[k][2];
+            total += s_part[k][threadIdx.x];
+        }
+        if (touched) atomicAdd(reinterpret_cast<unsigned long long*>(out + (size_t)frame * ANCHOR_EX_SLOTS + threadIdx.x), (unsigned long long)total);
+    }
+}
+
 }  // namespace
+
+extern "C" int vstab_anchor_sums_ex_batch(vstab_ctx* ctx, const uint8_t* gray, int n, int h, int w, const int32_t* anchor,
+                                          const double* R, const int32_t* gain, const int32_t* offset, int cap, const uint8_t* blocked,
+                                          int step, int gh, int gw, int64_t* out)
+{
+    VSTAB_REQUIRE(ctx != nullptr, "vstab_anchor_sums_ex_batch: ctx is NULL");
+    VSTAB_REQUIRE(gray && anchor && R && gain && offset && out, "vstab_anchor_sums_ex_batch: NULL pointer argument");
+    VSTAB_REQUIRE(n >= 1 && h > 0 && w > 0, "vstab_anchor_sums_ex_batch: needs at least one frame of a positive size (n=%d, %dx%d)", n, w, h);
+    VSTAB_REQUIRE(h <= 1024 && w <= 1024, "vstab_anchor_sums_ex_batch: %dx%d image larger than 1024 on a side (the sums are exact up to there)", w, h);
+    VSTAB_REQUIRE(cap >= 0 && cap <= 255, "vstab_anchor_sums_ex_batch: cap %d outside [0, 255]", cap);
+    VSTAB_REQUIRE(step >= 1, "vstab_anchor_sums_ex_batch: step %d is not positive", step);
+    if (blocked)
+        VSTAB_REQUIRE(gh == (h + step - 1) / step && gw == (w + step - 1) / step,
+                      "vstab_anchor_sums_ex_batch: a %dx%d block grid for a %dx%d image at step %d (expected %dx%d)", gw, gh, w, h, step,
+                      (w + step - 1) / step, (h + step - 1) / step);
+    for (int i = 0; i < n; i++) {
+        VSTAB_REQUIRE(anchor[i] >= -1 && anchor[i] < n, "vstab_anchor_sums_ex_batch: anchor[%d] = %d outside [-1, %d)", i, (int)anchor[i], n);
+        VSTAB_REQUIRE(gain[i] >= 256 && gain[i] <= 4096, "vstab_anchor_sums_ex_batch: gain[%d] = %d outside [256, 4096]", i, (int)gain[i]);
+        VSTAB_REQUIRE(offset[i] >= -(1 << 20) && offset[i] <= (1 << 20), "vstab_anchor_sums_ex_batch: offset[%d] = %d outside [-2^20, 2^20]", i,
+                      (int)offset[i]);
+    }
+    VSTAB_HIP(hipSetDevice(ctx->device));
+    VSTAB_HIP(hipMemsetAsync(out, 0, (size_t)n * ANCHOR_EX_SLOTS * sizeof(int64_t), ctx->stream));
+    if (h < 3 || w < 3) return 0;                       // no template pixel has all four neighbours
+    const int tiles = (h - 2 + ANCHOR_ROWS - 1) / ANCHOR_ROWS;
+    VSTAB_REQUIRE((long long)n * tiles < 0x7fffffffLL, "vstab_anchor_sums_ex_batch: clip too large");
+    // one staged blob: the matrices (fp64, so they come first), then the anchors, the gains and the offsets
+    const size_t mat_bytes = (size_t)n * 6 * sizeof(double), int_bytes = (size_t)n * sizeof(int32_t);
+    std::vector<unsigned char> blob(mat_bytes + 3 * int_bytes);
+    memcpy(blob.data(), R, mat_bytes);
+    memcpy(blob.data() + mat_bytes, anchor, int_bytes);
+    memcpy(blob.data() + mat_bytes + int_bytes, gain, int_bytes);
+    memcpy(blob.data() + mat_bytes + 2 * int_bytes, offset, int_bytes);
+    void* d_blob = nullptr;
+    if (int rc = vstab_stage_params(ctx, blob.data(), blob.size(), &d_blob)) return rc;
+    const double* d_mats = static_cast<const double*>(d_blob);
+    const int* d_params = reinterpret_cast<const int*>(static_cast<const unsigned char*>(d_blob) + mat_bytes);
+    KernelTimer timer(ctx, "anchor_ex");
+    const bool vec = (w % 16 == 0) && (reinterpret_cast<uintptr_t>(gray) % 16 == 0);
+    const dim3 grid((unsigned)(n * tiles)), block(ANCHOR_THREADS);
+    long long* sums = reinterpret_cast<long long*>(out);
+    const int cap1024 = 1024 * cap;
+    if (vec && blocked) hipLaunchKernelGGL((anchor_sums_ex_kernel<true, true>), grid, block, 0, ctx->stream, gray, d_mats, d_params, n, h, w, tiles, cap1024, blocked, step, gh, gw, sums);
+    else if (vec) hipLaunchKernelGGL((anchor_sums_ex_kernel<true, false>), grid, block, 0, ctx->stream, gray, d_mats, d_params, n, h, w, tiles, cap1024, blocked, step, gh, gw, sums);
+    else if (blocked) hipLaunchKernelGGL((anchor_sums_ex_kernel<false, true>), grid, block, 0, ctx->stream, gray, d_mats, d_params, n, h, w, tiles, cap1024, blocked, step, gh, gw, sums);
+    else hipLaunchKernelGGL((anchor_sums_ex_kernel<false, false>), grid, block, 0, ctx->stream, gray, d_mats, d_params, n, h, w, tiles, cap1024, blocked, step, gh, gw, sums);
+    VSTAB_HIP(hipGetLastError());
+    return 0;
+}
 
 extern "C" int vstab_anchor_sums_batch(vstab_ctx* ctx, const uint8_t* gray, int n, int h, int w, const int32_t* anchor,
                                        const double* R, int cap, int64_t* out)

@@ -217,7 +217,7 @@ def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, t
                       estimator: str = "flow", stats: Optional[Dict[str, float]] = None, want_meta: bool = True,
                       check_value_range: bool = True, temporal_fill: int = 0, estimation_mask=None, scene_cuts=None,
                       mesh_warp=None, dynamic_zoom=None, sharpness_transfer=None, rolling_shutter=None,
-                      drift_correction=None):
+                      drift_correction=None, drift_exposure=None, drift_mask=None):
     """Sharded equivalent of `_stabilize_frames` (flow.py:213-640).
 
     local_frames: device tensor [n_local (+1 halo for rank > 0 that owns frames), H, W, 3] float32 -- this rank's frames
@@ -272,6 +272,13 @@ def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, t
         ("drift_correction", drift_correction is not None and drift_correction is not False and drift_correction != 0,
          f"stabilize_sharded does not support drift_correction={drift_correction!r}: the keyframe alignment is not "
          "sharded (a frame's keyframe may lie on another rank); run the single-GPU pipeline for it"),
+        # both are options of the keyframe alignment, which is not sharded
+        ("drift_exposure", drift_exposure is not None and drift_exposure is not False,
+         f"stabilize_sharded does not support drift_exposure={drift_exposure!r}: the keyframe alignment it belongs to is not "
+         "sharded; run the single-GPU pipeline for it"),
+        ("drift_mask", drift_mask is not None and drift_mask is not False,
+         f"stabilize_sharded does not support drift_mask={drift_mask!r}: the keyframe alignment it belongs to is not "
+         "sharded; run the single-GPU pipeline for it"),
     )
     for _keyword, requested, message in refusals:
         if requested:

@@ -12,7 +12,15 @@ template pixel p = (x, y) about the image centre c = ((w-1)/2, (h-1)/2):
 We look for d with T(W(d) p) = I(R p).  To first order T(W(d) p) = T(p) + grad T . (dW/dd) d, so with the central
 differences grad T = (gx / 2, gy / 2) and xc = u / 2, yc = q / 2 the true Jacobian is D J, D = diag(1/2, 1/2, 1/4, 1/4), of
 the rule's integer J, and the residual is r / 1024.  (D H D) d = D b / 1024 is H d' = b / 1024 with d' = D d, hence
-d = (2 d'0, 2 d'1, 4 d'2, 4 d'3).  Substituting p' = W(d) p gives I(R W(d)^-1 p') = T(p'): the update is R <- R W(d)^-1."""
+d = (2 d'0, 2 d'1, 4 d'2, 4 d'3).  Substituting p' = W(d) p gives I(R W(d)^-1 p') = T(p'): the update is R <- R W(d)^-1.
+
+Exposure matching (`drift_exposure`) and the subject mask (`drift_mask`) use the second form of the rule
+(`native.Context.anchor_sums_ex_batch`, 31 numbers per frame).  The model becomes I(R p) = g T(W(d) p) + o.  The kernel holds
+the integers G = 1024 g and O = 1024 o of the current estimate and forms r = v - G T - O with v = 1024 I(R p).  With the gain
+off by dg and the offset by do, I - g T - o = dg T + do + (g + dg) grad T . (dW/dd) d to first order; times 1024, and with
+the integer Jacobian as above, r = dG T + dO + (G + dG) (J[0..3] . d'), dG = 1024 dg, dO = 1024 do.  That is linear in
+theta = ((G + dG) d'_0..3, dG, dO) with the columns (J0, J1, J2, J3, T, 1): H6 theta = b6, d'_k = theta_k / (G + dG), and d
+and the update of R as above.  At G = 1024, dG = 0 the first four rows are H d' = b / 1024 again."""
 
 from __future__ import annotations
 
@@ -32,6 +40,21 @@ MIN_SPACING, MAX_SPACING = 2, 4096
 MODES = ("translation", "similarity")
 KEEP_REASONS = ("singular", "overlap", "cost", "step", "no_anchor")
 SLOTS = 17
+# The exposure-matched / masked form.  Choices as well: the gain range is the temporal fill's [0.5, 2] clamp, 64 grey levels is a
+# quarter of the range (no auto-exposure step between two frames a spacing apart adds that much), and the first launch of an
+# exposure-matched call runs uncapped because no gain has been estimated yet that the cap could be applied behind.
+SLOTS_EX = 31
+GAIN_UNIT = 1024             # G and O are integers in units of 1/1024 (of 1, of a grey level)
+GAIN_MIN, GAIN_MAX = 512, 2048
+MAX_OFFSET_LEVELS = 64
+BOOTSTRAP_CAP = 255          # caps nothing at G = 1024, O = 0
+KEEP_REASONS_EX = KEEP_REASONS + ("gain",)
+# the 31 slots: count, capped, masked, sum|r|, b0..b5, then J_j J_k for j <= k row-major
+_H_SLOT = {}
+for _j in range(6):
+    for _k in range(_j, 6):
+        _H_SLOT[(_j, _k)] = 10 + len(_H_SLOT)
+PLAIN_SLOTS = [0, 1, 3, 4, 5, 6, 7] + [_H_SLOT[(j, k)] for j in range(4) for k in range(j, 4)]   # the 17 of the plain rule
 
 
 def check_request(value) -> Optional[int]:
@@ -46,15 +69,32 @@ def check_request(value) -> Optional[int]:
                      f"or an int in {MIN_SPACING}..{MAX_SPACING}, the keyframe spacing.")
 
 
-def check_pipeline(transform_mode: str, subject: bool, estimation_mask) -> None:
-    """What drift correction cannot be combined with; each refusal says why."""
+def check_options(drift, drift_exposure, drift_mask, estimation_mask):
+    """The `drift_exposure` / `drift_mask` keywords -> (exposure, masked) as bools.  None / False: off."""
+    for name, value in (("drift_exposure", drift_exposure), ("drift_mask", drift_mask)):
+        if value is not None and not isinstance(value, (bool, np.bool_)):
+            raise ValueError(f"{name}={value!r}: expected None / False (off) or True.")
+    exposure, masked = bool(drift_exposure), bool(drift_mask)
+    for name, on in (("drift_exposure", exposure), ("drift_mask", masked)):
+        if on and drift is None:
+            raise ValueError(f"{name}=True needs drift_correction: it changes how the keyframe alignment is solved, and without "
+                             "drift_correction there is none.")
+    if masked and estimation_mask is None:
+        raise ValueError("drift_mask=True needs estimation_mask: the keyframe alignment leaves out the pixels that mask's block "
+                         "grid names, and without estimation_mask there is no grid.")
+    return exposure, masked
+
+
+def check_pipeline(transform_mode: str, subject: bool, estimation_mask, drift_mask: bool = False) -> None:
+    """What drift correction cannot be combined with; each refusal says why.  drift_mask: the alignment reads the estimation
+    mask's block grid, so the mask is no obstacle."""
     if transform_mode == "perspective":
         raise ValueError("drift_correction does not support transform_mode='perspective': the keyframe alignment updates a "
                          "similarity (shift, zoom, rotation); use 'translation' or 'similarity'.")
     if subject:
         raise ValueError("drift_correction does not support estimator='subject': its transitions follow the subject, while the "
                          "estimation images the keyframe alignment reads show the background.")
-    if estimation_mask is not None:
+    if estimation_mask is not None and not drift_mask:
         raise ValueError("drift_correction does not support estimation_mask: the keyframe alignment has no per-pixel exclusion "
                          "yet (its residual cap is the only guard against moving subjects).")
 
@@ -142,10 +182,21 @@ def solve_update(sums, mode: str):
     H = np.array([[s[7], s[8], s[9], s[10]], [s[8], s[11], s[12], s[13]], [s[9], s[12], s[14], s[15]], [s[10], s[13], s[15], s[16]]])
     b = np.array(s[3:7]) / 1024.0
     k = 2 if mode == "translation" else 4
-    H, b = H[:k, :k], b[:k]
-    # scaled to a unit diagonal first: the zoom / rotation rows are ~1e5 times the shift rows, and the test is on the shape.
-    # Positive definite here means: the Cholesky factor exists and no pivot of the scaled matrix is below 1e-6 (a choice:
-    # below that the solution has no correct digit left in float64 after the two triangular solves' 1e-12 amplification)
+    dp = _solve_scaled(H[:k, :k], b[:k])
+    if dp is None:
+        return None
+    d = np.zeros(4)
+    d[:2] = 2.0 * dp[:2]
+    if k == 4:
+        d[2:] = 4.0 * dp[2:]
+    return d
+
+
+def _solve_scaled(H: np.ndarray, b: np.ndarray):
+    """H x = b for a symmetric H that must be positive definite -> x, or None where it is not.
+    Scaled to a unit diagonal first: the zoom / rotation rows are ~1e5 times the shift rows, and the test is on the shape.
+    Positive definite here means: the Cholesky factor exists and no pivot of the scaled matrix is below 1e-6 (a choice:
+    below that the solution has no correct digit left in float64 after the two triangular solves' 1e-12 amplification)."""
     diag = np.diag(H)
     if not (diag > 0.0).all():
         return None
@@ -157,12 +208,34 @@ def solve_update(sums, mode: str):
         return None
     if not np.isfinite(Lc).all() or np.min(np.diag(Lc)) < 1e-6:
         return None
-    dp = e * np.linalg.solve(Lc.T, np.linalg.solve(Lc, e * b))
+    return e * np.linalg.solve(Lc.T, np.linalg.solve(Lc, e * b))
+
+
+def solve_update_ex(sums, mode: str, gain: int, exposure: bool):
+    """One frame's 31 numbers, taken at the integer gain G -> (d, dG, dO), or None where H is not positive definite.
+    exposure False (the mask alone): today's columns from the new slots; the sums were taken at G = 1024, O = 0, and dG = dO
+    = 0.  exposure True: H6 theta = b6 over the columns (J0..J3, T, 1) -- (J0, J1, T, 1) in translation mode -- with
+    theta = ((G + dG) d', dG, dO)."""
+    if not exposure:
+        d = solve_update([sums[k] for k in PLAIN_SLOTS], mode)
+        return None if d is None else (d, 0.0, 0.0)
+    s = [float(int(v)) for v in sums]
+    cols = (0, 1, 4, 5) if mode == "translation" else (0, 1, 2, 3, 4, 5)
+    H = np.array([[s[_H_SLOT[(min(j, k), max(j, k))]] for k in cols] for j in cols])
+    b = np.array([s[4 + k] for k in cols])
+    theta = _solve_scaled(H, b)
+    if theta is None:
+        return None
+    dG, dO = float(theta[-2]), float(theta[-1])
+    scale = float(gain) + dG
+    if not scale > 0.0:
+        return None
+    dp = theta[:-2] / scale
     d = np.zeros(4)
     d[:2] = 2.0 * dp[:2]
-    if k == 4:
+    if len(cols) == 6:
         d[2:] = 4.0 * dp[2:]
-    return d
+    return d, dG, dO
 
 
 ROUNDING_LATTICE = 8         # the mean rounding displacement is taken over every 8th template pixel per axis
@@ -210,6 +283,11 @@ class Refinement:
     iterations: int
     sums_first: np.ndarray       # int64 [N,17] at the chained matrices
     sums_final: np.ndarray       # int64 [N,17] at the refined ones (zeros where none was evaluated)
+    # the exposure-matched / masked form only (refine_ex); sums_first is then the launch the cost test starts from
+    gain: Optional[np.ndarray] = None        # int64 [N]: G per frame, 1024 where the frame was kept or has no anchor
+    offset: Optional[np.ndarray] = None      # int64 [N]: O per frame
+    masked_first: Optional[np.ndarray] = None    # int64 [N]: the masked pixels of that launch
+    before_launch: int = 1                   # which launch sums_first is, counted from 1
 
 
 def refine(sums_fn, work_mats, sched: Schedule, mode: str, size) -> Refinement:
@@ -262,6 +340,83 @@ def refine(sums_fn, work_mats, sched: Schedule, mode: str, size) -> Refinement:
         if r is not None:
             R[i] = R0[i]
     return Refinement(R, R0, reason, launches, iterations, first, final)
+
+
+def refine_ex(sums_fn, work_mats, sched: Schedule, mode: str, size, exposure: bool) -> Refinement:
+    """`refine` on the 31 numbers of the second form: sums_fn(anchor, R, gain, offset, cap) -> int64 [N,31], with or without
+    a mask behind it.  The kernel always sees the integers held here: G <- rint(G + dG), O <- rint(O + dO) after every solve.
+    exposure: the first launch is the bootstrap.  At G = 1024 an exposure step pushes most pixels over the cap before any gain
+    is known, so that launch runs with BOOTSTRAP_CAP (which caps nothing) and only its gain and offset are taken: uncapped sums
+    hold every moving subject, so the motion they give is not applied, and R stays the chained matrix.  Every later launch and
+    the evaluating one run with RESIDUAL_CAP.  The second launch is therefore the chained matrix under the estimated exposure,
+    and the cost test compares it with the last launch, both under the same cap (`before_launch` = 2), as `refine` compares
+    its first launch with its last.  Without exposure the gain stays 1024 / 0 and the tests are `refine`'s, on the first
+    launch."""
+    if mode not in MODES:
+        raise ValueError(f"drift correction: mode {mode!r} is not one of {MODES}")
+    w, h = size
+    anchor = sched.anchor
+    n = anchor.shape[0]
+    R0 = chained(work_mats, sched)
+    R = R0.copy()
+    G = np.full(n, GAIN_UNIT, np.int64)
+    O = np.zeros(n, np.int64)
+    reason: List[Optional[str]] = [None if a >= 0 else "no_anchor" for a in anchor.tolist()]
+    active = anchor >= 0
+    before_at = 1 if exposure else 0
+    before = np.zeros((n, SLOTS_EX), np.int64)
+    launches = iterations = 0
+
+    def launch(rows, cap):
+        return np.asarray(sums_fn(np.where(rows, anchor, -1), R.reshape(n, 6), G.copy(), O.copy(), cap), dtype=np.int64).reshape(n, SLOTS_EX)
+
+    for it in range(MAX_ITERATIONS):
+        if not active.any():
+            break
+        bootstrap = exposure and it == 0
+        sums = launch(active, BOOTSTRAP_CAP if bootstrap else RESIDUAL_CAP)
+        launches += 1
+        iterations += 1
+        if it == before_at:
+            before = sums.copy()
+        for i in np.nonzero(active)[0].tolist():
+            solved = solve_update_ex(sums[i], mode, int(G[i]), exposure)
+            if solved is None:
+                reason[i], active[i] = "singular", False
+                continue
+            d, dG, dO = solved
+            if exposure:
+                g_new, o_new = float(np.rint(G[i] + dG)), float(np.rint(O[i] + dO))
+                if not (GAIN_MIN <= g_new <= GAIN_MAX and abs(o_new) <= MAX_OFFSET_LEVELS * GAIN_UNIT):
+                    reason[i], active[i] = "gain", False      # (NaN fails the comparisons too); G and O keep their last values
+                    continue
+                G[i], O[i] = int(g_new), int(o_new)
+            if bootstrap:
+                continue
+            new = (_affine3(sampled_at(R[i], size)) @ np.linalg.inv(warp_matrix(d, size)))[:2]
+            moved = corner_distance(new, R[i], size)
+            R[i] = new
+            if moved < CONVERGED_PX:
+                active[i] = False
+    final = np.zeros((n, SLOTS_EX), np.int64)
+    evaluate = np.array([r is None for r in reason])
+    if evaluate.any():
+        final = launch(evaluate, RESIDUAL_CAP)
+        launches += 1
+    need = MIN_OVERLAP * (w - 2) * (h - 2)
+    for i in np.nonzero(evaluate)[0].tolist():
+        count0, sum0, count1, sum1 = int(before[i, 0]), int(before[i, 3]), int(final[i, 0]), int(final[i, 3])
+        if count1 < need:
+            reason[i] = "overlap"
+        elif sum1 * count0 > sum0 * count1:          # the mean |r| went up: integers, no division
+            reason[i] = "cost"
+        elif corner_distance(R[i], R0[i], size) > MAX_CORRECTION_PX:
+            reason[i] = "step"
+    for i, r in enumerate(reason):
+        if r is not None:
+            R[i], G[i], O[i] = R0[i], GAIN_UNIT, 0
+    return Refinement(R, R0, reason, launches, iterations, before[:, PLAIN_SLOTS], final[:, PLAIN_SLOTS], G, O, before[:, 2].copy(),
+                      before_at + 1)
 
 
 # ---------------------------------------------------------------------------------------------------------- poses
@@ -337,14 +492,17 @@ def path_deltas(C_full, mode: str) -> np.ndarray:
 
 
 # ---------------------------------------------------------------------------------------------------------- the whole step
-def correct(sums_fn, fit_records: np.ndarray, selection, segments, total_frames: int, mode: str, size, working_size, spacing: int):
+def correct(sums_fn, fit_records: np.ndarray, selection, segments, total_frames: int, mode: str, size, working_size, spacing: int,
+            exposure: bool = False, masked: bool = False):
     """Everything between the estimator's fit table and the plan: schedule, refinement, poses.
     selection: (work_mats, modes, confidences, ...) as select_transitions returns them.
+    exposure / masked: sums_fn is the second form's, sums_fn(anchor, R, gain, offset, cap) -> int64 [N,31].
     -> (the fit table with the corrected transitions, path_deltas f64 [N-1,P], meta["drift_correction"])."""
     work_mats, modes, confidences = selection[0], selection[1], selection[2]
     work = working_size if working_size is not None else size
     sched = schedule(total_frames, segments, confidences, spacing)
-    result = refine(sums_fn, work_mats, sched, mode, work)
+    extended = exposure or masked
+    result = refine_ex(sums_fn, work_mats, sched, mode, work, exposure) if extended else refine(sums_fn, work_mats, sched, mode, work)
     C = poses(result.R, sched)
     table = write_transitions(fit_records, transitions(C), modes, confidences, sched)
     C_full = rescale_to_full(C, size, working_size)
@@ -353,7 +511,10 @@ def correct(sums_fn, fit_records: np.ndarray, selection, segments, total_frames:
         if sched.shot_start[k + 1]:
             deltas[k] = 0.0
     chained_full = rescale_to_full(poses(result.R_chained, sched), size, working_size)
-    return table, deltas, meta_block(sched, result, C_full, chained_full, size)
+    block = meta_block(sched, result, C_full, chained_full, size)
+    if extended:
+        block.update(meta_block_ex(sched, result, exposure, masked))
+    return table, deltas, block
 
 
 def meta_block(sched: Schedule, result: Refinement, C_full, chained_full, size) -> Dict[str, Any]:
@@ -384,3 +545,21 @@ def meta_block(sched: Schedule, result: Refinement, C_full, chained_full, size) 
         "residual_after": mean_residual(result.sums_final, refined),
         "capped_fraction_mean": float(np.mean(capped)) if capped.size else 0.0,
     }
+
+
+def meta_block_ex(sched: Schedule, result: Refinement, exposure: bool, masked: bool) -> Dict[str, Any]:
+    """What the block gains (and, for frames_kept, replaces) under drift_exposure / drift_mask.  residual_before and
+    capped_fraction_mean then describe launch `residual_before_launch`, the one the cost test starts from."""
+    out: Dict[str, Any] = {"frames_kept": {name: sum(1 for r in result.reason if r == name) for name in KEEP_REASONS_EX}}
+    if exposure:
+        gain = result.gain.astype(np.float64) / GAIN_UNIT
+        out["exposure"] = {"matched": True, "gain": [float(g) for g in gain],
+                           "offset": [float(o) for o in result.offset.astype(np.float64) / GAIN_UNIT],
+                           "gain_min": float(gain.min()), "gain_max": float(gain.max()),
+                           "residual_before_launch": int(result.before_launch)}
+    if masked:
+        anchored = sched.anchor >= 0
+        seen = result.sums_first[anchored, 0] + result.sums_first[anchored, 1] + result.masked_first[anchored]
+        hidden = result.masked_first[anchored][seen > 0] / seen[seen > 0]
+        out["masked_fraction_mean"] = float(np.mean(hidden)) if hidden.size else 0.0
+    return out

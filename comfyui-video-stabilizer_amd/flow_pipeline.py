@@ -755,9 +755,12 @@ def _rolling_shutter(ctx, rolling, plan, grid_out, blocked, working_size, size, 
 
 
 # ---- drift correction (beyond the reference; drift_correction.py, the rule is in include/vstab.h) ------------------------
-def _drift_correction(ctx, spacing, fit_records, gray, segments, total_frames, transform_mode, size, working_size):
+def _drift_correction(ctx, spacing, fit_records, gray, segments, total_frames, transform_mode, size, working_size,
+                      exposure=False, blocked=None):
     """-> (the fit table with the registered poses' transitions, the path's per-pair steps, meta["drift_correction"]).  Runs
-    on the selection the plan itself will make; every launch covers all frames of the clip that are still iterating."""
+    on the selection the plan itself will make; every launch covers all frames of the clip that are still iterating.
+    exposure (drift_exposure) or blocked (drift_mask: the estimation mask's block grid) switch to the second form of the rule;
+    without them the first entry point is the one called."""
     table = fit_records if isinstance(fit_records, np.ndarray) else native.fit_table_from_dicts(fit_records)
     if segments is None:
         selection = select_transitions(table, transform_mode)
@@ -767,6 +770,12 @@ def _drift_correction(ctx, spacing, fit_records, gray, segments, total_frames, t
     def sums_fn(anchor, R):
         return ctx.anchor_sums_batch(gray, anchor, R, drift_correction_mod.RESIDUAL_CAP)
 
+    def sums_ex_fn(anchor, R, gain, offset, cap):
+        return ctx.anchor_sums_ex_batch(gray, anchor, R, cap, gain, offset, blocked, SAMPLE_STEP)
+
+    if exposure or blocked is not None:
+        return drift_correction_mod.correct(sums_ex_fn, table, selection, segments, total_frames, transform_mode, size, working_size,
+                                            spacing, exposure=exposure, masked=blocked is not None)
     return drift_correction_mod.correct(sums_fn, table, selection, segments, total_frames, transform_mode, size, working_size, spacing)
 
 
@@ -803,6 +812,8 @@ class FlowRequest:
     stability_report: bool
     mask_margin: Optional[int]         # the estimation mask's margin; None: no estimation mask was given
     drift: Optional[int] = None        # drift_correction.check_request: the keyframe spacing | None
+    drift_exposure: bool = False       # drift_correction.check_options: the keyframe alignment estimates a gain and an offset
+    drift_mask: bool = False           # ... and leaves out what the estimation mask's block grid names
 
     @property
     def needs_host_plan(self) -> bool:
@@ -816,7 +827,9 @@ class FlowRequest:
     @property
     def kept_by_products(self) -> Tuple[str, ...]:
         """The estimator's by-products that stay alive behind the fits (its `*_out` keywords): the estimation images for the
-        scene-cut score and the keyframe alignment, the grid of flow samples for the vertex / row residuals."""
+        scene-cut score and the keyframe alignment, the grid of flow samples for the vertex / row residuals.  (The estimation
+        mask's block grid, which drift_mask reads behind the fits, is made before the estimator runs and is held by the
+        call itself for all of its length: it is no by-product and needs no entry here.)"""
         keep = ("gray_out",) if (self.scene is not None and self.scene.mode == "auto") or self.drift is not None else ()
         return keep + (("grid_out",) if self.mesh is not None or self.rolling == rolling_shutter_mod.AUTO else ())
 
@@ -856,10 +869,12 @@ def check_flow_request(framing_mode: str, transform_mode: str, estimator: str, k
     if rolling is not None:
         rolling_shutter_mod.check_pipeline(rolling, transform_mode, framing_mode, estimator, mesh, temporal_fill, sharpness, zoom)
     drift = drift_correction_mod.check_request(kw["drift_correction"])
-    if drift is not None:
-        drift_correction_mod.check_pipeline(transform_mode, bool(subject), kw["estimation_mask"])
+    if drift is not None:   # (drift_mask=True lifts the estimation_mask refusal; whether the keyword is well-formed comes next)
+        drift_correction_mod.check_pipeline(transform_mode, bool(subject), kw["estimation_mask"], kw.get("drift_mask") is True)
+    drift_exposure, drift_mask = drift_correction_mod.check_options(drift, kw.get("drift_exposure"), kw.get("drift_mask"),
+                                                                    kw["estimation_mask"])
     return FlowRequest(estimator, temporal_fill, fill_blend, sharpness, handoff, zoom, scene, mesh, bool(kw["mesh_motion"]),
-                       bool(subject), rolling, spatial_fill, stability_report, mask_margin, drift)
+                       bool(subject), rolling, spatial_fill, stability_report, mask_margin, drift, drift_exposure, drift_mask)
 
 
 def _check_request_against_clip(request: FlowRequest, kw: Dict[str, Any], transform_mode: str, total_frames: int, size) -> None:
@@ -996,6 +1011,8 @@ def _stabilize_frames(
     mask_tapered=None,
     rolling_shutter=None,
     drift_correction=None,
+    drift_exposure=None,
+    drift_mask=None,
 ) -> hm.StabilizationResult:
     """Positional signature of the reference (flow.py:213-223); keyword-only extras select the GPU
     context, keep outputs resident in HBM (multi-GPU sharding lives in distributed.py) or switch the
@@ -1094,7 +1111,15 @@ def _stabilize_frames(
     the inverse pose exactly.  A frame whose alignment cannot be trusted keeps its chained estimate, counted by reason in
     meta["drift_correction"].  For translation / similarity, without estimation_mask or estimator "subject"; everything behind
     the fit table follows unchanged.  None / 0 / False: the behaviour and meta without it, byte for byte, and nothing new is
-    launched.  Bypass paths ignore it."""
+    launched.  Bypass paths ignore it.
+    drift_exposure, drift_mask (beyond the reference, None by default; with drift_correction only): what real handheld footage
+    adds to the keyframe alignment.  drift_exposure=True estimates a gain and an offset per frame against its keyframe next to
+    the motion, so that auto-exposure between frames up to a whole spacing apart does not read as a residual; a frame whose
+    gain leaves [0.5, 2] or whose offset exceeds 64 grey levels keeps its chained estimate under the reason "gain".
+    drift_mask=True (needs estimation_mask) leaves the pixels the estimation mask's block grid names, in the keyframe or in the
+    frame, out of the alignment, and with it drift_correction accepts estimation_mask.  Both use the second form of the rule
+    (include/vstab.h); meta["drift_correction"] gains `exposure` (the gains and offsets), `masked_fraction_mean` and
+    frames_kept["gain"].  None / False: the behaviour and meta without them, byte for byte, and nothing new is launched."""
     kw = dict(locals())     # every argument by name (nothing else is local yet): the keyword extras are read from here
     request = check_flow_request(framing_mode, transform_mode, estimator, kw)
     estimator = request.estimator
@@ -1195,7 +1220,8 @@ def _stabilize_frames(
     path_deltas = drift_block = None
     if request.drift is not None and not keep_fov_bypasses(framing_mode, keep_fov):   # (the plan returns the original frames)
         fit_records, path_deltas, drift_block = _drift_correction(ctx, request.drift, fit_records, extras["gray_out"][0], segments,
-                                                                  total_frames, transform_mode, size, working_size)
+                                                                  total_frames, transform_mode, size, working_size,
+                                                                  request.drift_exposure, blocked if request.drift_mask else None)
     plan = plan_stabilization(ctx, fit_records, size, total_frames, *args, estimator=estimator, segments=segments,
                               path_deltas=path_deltas)
     if plan.bypass_meta is not None:  # crop + keep_fov ~ 1 (flow.py:387-429): original frames

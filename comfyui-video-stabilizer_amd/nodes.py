@@ -982,6 +982,43 @@ class VideoStabilizerFlowAnchored(io.ComfyNode):
                                    keep_fov, padding_color, drift_correction=int(keyframe_spacing))
 
 
+class VideoStabilizerFlowAnchoredExposure(io.ComfyNode):
+    """The Drift-Free node for handheld footage: the keyframe alignment also estimates a gain and an offset per frame, so that
+    auto-exposure does not defeat it, and leaves the pixels of an optional `exclude_mask` out (drift_correction.py).  Not one
+    of the reference's nodes: it is listed by an extension but kept out of NODE_CLASSES."""
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        schema = io.Schema(
+            node_id="video_stabilizer_flow_anchored_exposure",
+            display_name="Video Stabilizer Flow (Drift-Free, Exposure-Matched)",
+            category="Video/Stabilization",
+            description=("Video Stabilizer Flow (Drift-Free) whose keyframe alignment follows the camera's auto-exposure and "
+                         "ignores a masked moving subject."),
+        )
+        schema.inputs = list(VideoStabilizerFlowAnchored.define_schema().inputs) + [
+            io.Boolean.Input("match_exposure", default=True, display_name="Match Exposure",
+                             tooltip=("Estimate a brightness gain and offset of every frame against its keyframe next to the "
+                                      "motion; the meta reports them.")),
+            io.Mask.Input("exclude_mask", display_name="Exclude Mask", optional=True,
+                          tooltip=("Per-frame mask (or one mask for the whole clip) at the frames' resolution; values above "
+                                   "0.5 mark pixels neither the motion estimate nor the keyframe alignment may use.")),
+            io.Int.Input("mask_margin", default=16, min=0, max=64, display_name="Mask Margin",
+                         tooltip="Safety margin around the mask, in pixels of the estimation image (long side 960)."),
+        ]
+        schema.outputs = _estimator_outputs()
+        return schema
+
+    @classmethod
+    def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
+                strength: float, smooth: float, keep_fov: float, padding_color: str, keyframe_spacing: int = 32,
+                match_exposure: bool = True, exclude_mask: Any = None, mask_margin: int = 16) -> io.NodeOutput:
+        masked = {} if exclude_mask is None else dict(estimation_mask=exclude_mask, mask_margin=int(mask_margin), drift_mask=True)
+        return _run_estimator_node("flow", frames, frame_rate, framing_mode, transform_mode, camera_lock, strength, smooth,
+                                   keep_fov, padding_color, drift_correction=int(keyframe_spacing),
+                                   drift_exposure=True if match_exposure else None, **masked)
+
+
 class VideoStabilizerMotionApplyRolling(io.ComfyNode):
     """Motion Apply for a rolling-shutter run (apply_motion's rolling=True): on the run's source frames (or a companion clip
     of their size) it applies the recorded matrices and row correction again, on its stabilized frames it restores the
@@ -1159,3 +1196,6 @@ VideoStabilizerAmdRollingApplyExtension = _extend(
 VideoStabilizerAmdAnchorExtension = _extend(
     VideoStabilizerAmdRollingApplyExtension, VideoStabilizerFlowAnchored, name="VideoStabilizerAmdAnchorExtension",
     doc="The rolling round trip extension's twenty-one nodes plus Video Stabilizer Flow (Drift-Free).")
+VideoStabilizerAmdAnchorExposureExtension = _extend(
+    VideoStabilizerAmdAnchorExtension, VideoStabilizerFlowAnchoredExposure, name="VideoStabilizerAmdAnchorExposureExtension",
+    doc="The drift-free extension's twenty-two nodes plus Video Stabilizer Flow (Drift-Free, Exposure-Matched).")

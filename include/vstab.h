@@ -315,6 +315,39 @@ int vstab_pair_residual_batch(vstab_ctx* ctx, const uint8_t* gray, int n, int h,
 #define VSTAB_ANCHOR_SLOTS 17
 int vstab_anchor_sums_batch(vstab_ctx* ctx, const uint8_t* gray, int n, int h, int w, const int32_t* anchor,
                             const double* R, int cap, int64_t* out);
+/* Exposure-matched, masked form (off by default; drift_exposure / drift_mask).  Auto-exposure changes the brightness between a
+ * frame and a keyframe up to a whole spacing away, and a masked subject must not pull the alignment.  The rule is the one
+ * above with three changes; steps 1-5 (mapping, Q5 rounding, the inside test, the bilinear integer v) and 8-9 (gx, gy, u, q,
+ * J0..J3) are unchanged:
+ *   - photometric prediction: every frame carries two host-given i32, G (gain in units of 1/1024, 256..4096) and O (offset
+ *     in units of 1/1024 grey level, |O| <= 2^20), and step 6 becomes r = v - (G T[y,x] + O).  G = 1024, O = 0 is the r above.
+ *   - mask (blocked != NULL only; blocked is vstab_mask_block_grid's [n,gh,gw] u8 grid of the clip at `step`, gh =
+ *     ceil(h/step), gw = ceil(w/step)): tested behind the inside test (step 3) and before the cap (step 7).  With integer
+ *     divisions throughout, the pixel is MASKED iff
+ *       blocked[a][min((y + step/2) / step, gh-1)][min((x + step/2) / step, gw-1)] != 0   -- the template pixel's nearest
+ *       grid sample in the anchor a -- or
+ *       blocked[i][min((yn + step/2) / step, gh-1)][min((xn + step/2) / step, gw-1)] != 0 with xn = min((ix + 16) >> 5, w-1),
+ *       yn = min((iy + 16) >> 5, h-1)   -- the nearest grid sample of the nearest pixel of the sample position in frame i.
+ *     A masked pixel adds 1 to `masked` and nothing else.  A grid sample is blocked iff a covered pixel lies within
+ *     mask_margin of it, and a pixel is up to step/2 from its nearest sample per axis: with mask_margin < step / 2 a subject
+ *     pixel can lie nearer to an unblocked sample than to a blocked one, and the rule then does not cover every subject pixel.
+ *   - cap: |r| > 1024 cap on the compensated r gives capped += 1 and nothing else, as above.
+ *   - two more regression columns: J4 = T[y,x] (the gain's) and J5 = 1 (the offset's).
+ * out[i] = [count, capped, masked, sum|r|, b0..b5, H00, H01, ..., H55]: b_k = sum J_k r, and H the 21 sums J_j J_k for
+ * j <= k, row-major over the upper triangle (H00 H01 H02 H03 H04 H05 H11 H12 ... H45 H55).  Everything summed is an integer,
+ * exact in any order.  Bounds: v <= 261120 and |G T + O| <= 4096*255 + 2^20 < 2^21, so r fits 32 bits; every counted pixel
+ * has |r| <= 1024*255 < 2^18 by the cap test itself; J4 <= 255 and J5 = 1 are smaller than J0..J3; so with max(h, w) <= 1024
+ * the argument above carries over and no sum reaches 2^59.  anchor[i] == -1, h < 3 or w < 3: zeros.
+ * vstab_anchor_sums_ex_batch: gray, anchor, R, cap as above; gain, offset host [n] i32 (both required); blocked dev
+ * [n,gh,gw] u8 or NULL (step >= 1 is checked either way, gh and gw only with blocked) -> out dev [n][VSTAB_ANCHOR_EX_SLOTS]
+ * i64 (zeroed by the call).  Asynchronous on the context's stream; timing kind "anchor_ex".  What is solved from the sums
+ * (drift_correction.py): the model I(R p) = g T(W(d) p) + o gives, to first order, v - G T - O = dG T + dO + (G + dG)
+ * (J[0..3] . d'), so H theta = b with theta = ((G + dG) d'_0..3, dG, dO), d'_k = theta_k / (G + dG), and d, R as above.
+ */
+#define VSTAB_ANCHOR_EX_SLOTS 31
+int vstab_anchor_sums_ex_batch(vstab_ctx* ctx, const uint8_t* gray, int n, int h, int w, const int32_t* anchor,
+                               const double* R, const int32_t* gain, const int32_t* offset, int cap, const uint8_t* blocked,
+                               int step, int gh, int gw, int64_t* out);
 
 /* ---- N1 (crop framing): coverage analysis for the keep_fov crop solver ---------
  * Replaces the per-frame cv2 calls of nodes/stabilizer_utils.py:611-643

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Drift correction: what it costs and what it recovers; writes the next free profiles/rNN_drift_correction.md.
+"""Drift correction: what it costs and what it recovers; writes the next free profiles/rNN_drift_exposure.md.
 
   1. kernel time per launch of anchor_sums_batch for 256 frames at 960x540 (every frame but the first anchored, keyframes
      every 32) next to pair_residual_batch of the same run: HIP events, median of 7 after one warm-up;
@@ -7,7 +7,8 @@
      chain of the reported transitions against the analytic path (worst frame, centre / corner in working px), launches used,
      frames refined / kept -- also with sigma 0.03 noise added to the frames;
   3. camera lock on the similarity clip: PSNR against the static texture without and with;
-  4. a clip whose exposure drifts by 20 % over its length: gain compensation is out of scope, the `cost` test is the only guard;
+  4. a clip whose exposure drifts by 20 % over its length, and one whose exposure flickers from frame to frame: the chain
+     without and with drift_exposure; the same kernel timing for anchor_sums_ex, unmasked and masked, in section 1;
   5. with --parent DIR (a built checkout of the parent commit): `bench.py --gpus 1` alternating between the two trees.
 
     python tools/drift_correction_report.py [--out FILE] [--parent DIR] [--rounds 3] [--steps 20] [--warmup 5]
@@ -31,7 +32,7 @@ import __graft_entry__ as graft  # noqa: E402
 
 def next_profile() -> Path:
     taken = [int(m.group(1)) for p in (ROOT / "profiles").glob("r*") if (m := re.match(r"r(\d+)_", p.name))]
-    return ROOT / "profiles" / f"r{max(taken, default=0) + 1:02d}_drift_correction.md"
+    return ROOT / "profiles" / f"r{max(taken, default=0) + 1:02d}_drift_exposure.md"
 
 
 def bench_once(tree: Path, steps: int, warmup: int) -> float:
@@ -107,14 +108,22 @@ def main() -> int:
     ctx.set_timing(True)
     anchor_ms, anchor_runs = timed("anchor", lambda: ctx.anchor_sums_batch(gray, sched.anchor, Rm, dc.RESIDUAL_CAP))
     cut_ms, cut_runs = timed("cut", lambda: ctx.pair_residual_batch(gray, true.astype(np.float32)))
+    step = 8
+    blocked = (torch.rand((n, -(-h // step), -(-w // step)), device=dev, generator=torch.Generator(device=dev).manual_seed(3)) < 0.3).to(torch.uint8)
+    gains = np.full(n, 900)
+    ex_ms, ex_runs = timed("anchor_ex", lambda: ctx.anchor_sums_ex_batch(gray, sched.anchor, Rm, dc.RESIDUAL_CAP, gains))
+    exm_ms, exm_runs = timed("anchor_ex", lambda: ctx.anchor_sums_ex_batch(gray, sched.anchor, Rm, dc.RESIDUAL_CAP, gains, None, blocked, step))
     ctx.set_timing(False)
     frames_bytes = 2.0 * h * w * (n - 1)
     lines += [f"## Kernel time, {n} frames of {w}x{h} (HIP events, median of {reps})", "",
               "| kernel | ms per launch | TB/s against 2 h w bytes per frame | runs ms |", "|---|---|---|---|",
               f"| anchor_sums ({n - 1} anchored frames) | {anchor_ms:.3f} | {frames_bytes / (anchor_ms * 1e-3) / 1e12:.2f} | {', '.join(f'{v:.3f}' for v in anchor_runs)} |",
+              f"| anchor_sums_ex, unmasked | {ex_ms:.3f} | {frames_bytes / (ex_ms * 1e-3) / 1e12:.2f} | {', '.join(f'{v:.3f}' for v in ex_runs)} |",
+              f"| anchor_sums_ex, 30 % of the grid blocked at random | {exm_ms:.3f} | {frames_bytes / (exm_ms * 1e-3) / 1e12:.2f} | {', '.join(f'{v:.3f}' for v in exm_runs)} |",
               f"| pair_residual ({n - 1} pairs) | {cut_ms:.3f} | {frames_bytes / (cut_ms * 1e-3) / 1e12:.2f} | {', '.join(f'{v:.3f}' for v in cut_runs)} |", "",
-              f"anchor_sums / pair_residual = {anchor_ms / cut_ms:.2f}.  A corrected call launches it `iterations + 1` times.", ""]
-    del gray
+              f"anchor_sums / pair_residual = {anchor_ms / cut_ms:.2f}.  A corrected call launches it `iterations + 1` times.",
+              f"anchor_sums_ex / anchor_sums = {ex_ms / anchor_ms:.2f} unmasked, {exm_ms / anchor_ms:.2f} masked (31 accumulators against 17: {31 / 17:.2f}).", ""]
+    del gray, blocked
     torch.cuda.empty_cache()
 
     # ---- 2. accuracy -------------------------------------------------------------------------------------------------
@@ -147,17 +156,29 @@ def main() -> int:
               f"- without: {json.dumps(without)}", f"- with drift_correction=True: {json.dumps(with_it)}",
               f"- the test's gate is the PSNR with the keyword less 1 dB: {with_it['psnr_db'] - 1.0:.2f} dB", ""]
 
-    # ---- 4. exposure drift -------------------------------------------------------------------------------------------
-    gain = torch.linspace(1.0, 0.8, T.N, device=dev).view(-1, 1, 1, 1)
-    dim = frames * gain
-    c0, k0 = T.chain_error(T.stabilize(ctx, dim, "similarity").meta, cam)
-    meta = T.stabilize(ctx, dim, "similarity", drift_correction=True).meta
-    c1, k1 = T.chain_error(meta, cam)
-    b = meta["drift_correction"]
-    lines += ["## Exposure drifting by 20 % over the clip (gain compensation is out of scope)", "",
-              f"- chain without: centre {c0:.4f}, corner {k0:.4f}; with: centre {c1:.4f}, corner {k1:.4f}",
-              f"- frames refined {b['frames_refined']}, kept {b['frames_kept']}, capped fraction {b['capped_fraction_mean']:.4f}, "
-              f"residual {b['residual_before']:.3f} -> {b['residual_after']:.3f} grey levels", ""]
+    # ---- 4. exposure: a ramp and per-frame flicker ---------------------------------------------------------------------
+    ramp = frames * torch.linspace(1.0, 0.8, T.N, device=dev).view(-1, 1, 1, 1)
+    rng = np.random.default_rng(11)                   # the flicker of tests/test_drift_exposure_gpu.py
+    g, o = rng.uniform(0.75, 0.95, T.N), rng.uniform(0.0, 0.04, T.N)
+    flicker = frames * torch.from_numpy(g).float().to(dev).view(-1, 1, 1, 1) + torch.from_numpy(o).float().to(dev).view(-1, 1, 1, 1)
+    anchor = [-1] + [32 * ((i - 1) // 32) for i in range(1, T.N)]
+    want = np.array([1.0] + [g[i] / g[anchor[i]] for i in range(1, T.N)])
+    lines += ["## Exposure: falling by 20 % over the clip (ramp), and per-frame gains in [0.75, 0.95] with offsets in [0, 0.04] (flicker)", "",
+              "| clip | call | centre | corner | launches | refined | kept | residual before -> after |", "|---|---|---|---|---|---|---|---|"]
+    for name, clip in (("ramp", ramp), ("flicker", flicker)):
+        c0, k0 = T.chain_error(T.stabilize(ctx, clip, "similarity").meta, cam)
+        lines.append(f"| {name} | no drift_correction | {c0:.4f} | {k0:.4f} | | | | |")
+        for label, kw in (("drift_correction=True", {}), ("+ drift_exposure=True", dict(drift_exposure=True))):
+            meta = T.stabilize(ctx, clip, "similarity", drift_correction=True, **kw).meta
+            c1, k1 = T.chain_error(meta, cam)
+            b = meta["drift_correction"]
+            kept = {k: v for k, v in b["frames_kept"].items() if v}
+            lines.append(f"| {name} | {label} | {c1:.4f} | {k1:.4f} | {b['iterations'] + 1} | {b['frames_refined']} | {kept} | "
+                         f"{b['residual_before']:.3f} -> {b['residual_after']:.3f} |")
+            if kw and name == "flicker":
+                worst = float(np.max(np.abs(np.array(b["exposure"]["gain"]) - want)))
+    lines += ["", f"Flicker: the worst |reported gain - g_i / g_anchor(i)| over the clip is {worst:.5f}.  Under drift_exposure "
+                  "`residual_before` is the second launch (the chained matrices under the estimated exposure).", ""]
     out_path.parent.mkdir(parents=True, exist_ok=True)
     out_path.write_text("\n".join(lines))
     print("\n".join(lines))
