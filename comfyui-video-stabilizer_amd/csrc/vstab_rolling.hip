@@ -1,6 +1,7 @@
 // vstab_rolling.hip -- rolling shutter: the per-row readout correction of the final warp (vstab_rolling_warp_batch), its
-// closed-form inverse (vstab_rolling_unwarp_batch) and the per-row median of the global fit's residual that the readout
-// estimate is made from (vstab_row_residual_batch).  Not a reference feature; the rules are stated in include/vstab.h.
+// closed-form inverse (vstab_rolling_unwarp_batch), the per-row median of the global fit's residual that the readout
+// estimate is made from (vstab_row_residual_batch), and the rectifier of the flow samples that the refit of the transitions
+// reads (vstab_rectify_samples_batch).  Not a reference feature; the rules are stated in include/vstab.h.
 // profiles/warp_traffic.json is tied to vstab_warp.hip + vstab_internal.h: an edit here leaves it valid.
 //
 // The warps: the plain warp's kernel body (warp_kernel, vstab_internal.h) with Args = RollingWarpArgs, whose displacement of
@@ -13,6 +14,9 @@
 // row_residual_kernel: one workgroup per (pair, grid row); the row's admitted residuals (vstab_fit_residual) are compacted
 // into LDS (order does not matter to a median) and ranked by counting (vstab_median_pair), as vstab_mesh.hip does per vertex.
 // A row of a 960-px estimation image has 120 samples: microseconds per clip.
+// rectify_kernel (vstab_rectify_samples_batch): the flow grid's samples as point pairs whose two ends are moved by the
+// inverse's e at a point (RowInverseDisplacement::solve_at), for the refit of the pair transitions; one workgroup per pair,
+// an ordered block compaction of the admitted samples, 24 bytes per sample: 0.05 ms for the 255 pairs of a 960 x 540 grid.
 // Built with -ffp-contract=off like the rest of the library.
 #define VSTAB_WARP_ARITHMETIC
 #include "vstab_internal.h"
@@ -22,6 +26,9 @@ namespace {
 
 constexpr int ROW_THREADS = 256;
 constexpr int ROW_MAX_SAMPLES = 4096;       // grid positions of one row: 2 x 16 KB of LDS
+constexpr int RECTIFY_THREADS = 512;        // the fit kernel's block: one workgroup per pair
+constexpr int RECTIFY_WAVES = RECTIFY_THREADS / 64;
+constexpr int RECTIFY_MAX_SAMPLES = 16384;  // what vstab_points_fit_batch takes per pair (MAX_SORT in vstab_fit.hip)
 
 __device__ __forceinline__ bool finite_d(double v) { return __builtin_fabs(v) <= 1.7976931348623157e308; }  // false for NaN
 
@@ -60,7 +67,11 @@ struct RowInverseDisplacement {
     __device__ __forceinline__ bool solve(int x, int y, double& ex, double& ey) const
     {
         const double xd = (double)x, yd = (double)y;
-        const double tau = rho * (yd / hm1 - 0.5);
+        return solve_at(rho * (yd / hm1 - 0.5), xd, yd, ex, ey);
+    }
+    // the same for a point (xd, yd) that is no pixel, at the row time tau (the sample rectifier's: its row is clamped)
+    __device__ __forceinline__ bool solve_at(double tau, double xd, double yd, double& ex, double& ey) const
+    {
         const double a = 1.0 + tau * v0, b = tau * v1, c = tau * v3, d = 1.0 + tau * v4;
         const double det = a * d - b * c;
         const double vx = (v0 * xd + v1 * yd) + v2;
@@ -146,6 +157,91 @@ __global__ __launch_bounds__(ROW_THREADS) void row_residual_kernel(RowResidualAr
     if (threadIdx.x == 0) a.count[cell] = n;
 }
 
+struct RectifyArgs {
+    const float* grid;        // [pairs][gh*gw][2]
+    const double* velocity;   // [pairs + 1][6], working px per frame interval
+    const uint8_t* blocked;   // [pairs + 1][gh*gw] or nullptr
+    float* out;               // [pairs][gh*gw][4]
+    int* counts;              // [pairs]
+    unsigned* unsolved;       // [pairs]
+    int gw, cells, step;
+    double rho, hm1;
+};
+
+// s + e of the rule (vstab_rectify_samples_batch in include/vstab.h), each coordinate rounded once to float32 -> solved
+__device__ __forceinline__ bool rectify_point(const RowInverseDisplacement& f, float sx, float sy, float& qx, float& qy)
+{
+    const double x = (double)sx, y = (double)sy;
+    double yr = (y < 0.0) ? 0.0 : y;            // a NaN stays a NaN
+    yr = (yr > f.hm1) ? f.hm1 : yr;
+    double ex, ey;
+    const bool solved = f.solve_at(f.rho * (yr / f.hm1 - 0.5), x, y, ex, ey);
+    qx = (float)(x + ex);
+    qy = (float)(y + ey);
+    return solved;
+}
+
+// One workgroup per pair.  Thread t owns the grid samples [t*per, (t+1)*per): it counts its admitted ones, the block scans
+// the counts (the fit kernel's wavefront scan) and the thread writes its pairs from its offset on, so the grid order is kept.
+__global__ __launch_bounds__(RECTIFY_THREADS) void rectify_kernel(RectifyArgs a)
+{
+    __shared__ int s_wave[RECTIFY_WAVES];
+    __shared__ unsigned s_bad;
+    const int pair = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const float* __restrict__ G = a.grid + (size_t)pair * a.cells * 2;
+    const uint8_t* __restrict__ B0 = a.blocked ? a.blocked + (size_t)pair * a.cells : nullptr;
+    const uint8_t* __restrict__ B1 = a.blocked ? B0 + a.cells : nullptr;
+    float* __restrict__ out = a.out + (size_t)pair * a.cells * 4;
+    const double* __restrict__ V = a.velocity + (size_t)pair * 6;
+    const RowInverseDisplacement prev{V[0], V[1], V[2], V[3], V[4], V[5], a.rho, a.hm1};
+    const RowInverseDisplacement next{V[6], V[7], V[8], V[9], V[10], V[11], a.rho, a.hm1};
+    if (tid == 0) s_bad = 0u;
+
+    const int per = (a.cells + RECTIFY_THREADS - 1) / RECTIFY_THREADS;
+    const int g0 = min(tid * per, a.cells), g1 = min(g0 + per, a.cells);
+    int local = g1 - g0;
+    if (B0 != nullptr) {
+        local = 0;
+        for (int g = g0; g < g1; g++) local += ((B0[g] | B1[g]) == 0) ? 1 : 0;
+    }
+    int incl = local;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(incl, d);
+        if ((tid & 63) >= d) incl += o;
+    }
+    if ((tid & 63) == 63) s_wave[tid >> 6] = incl;
+    __syncthreads();
+    int before = 0, total = 0;
+    for (int i = 0; i < RECTIFY_WAVES; i++) {
+        if (i < (tid >> 6)) before += s_wave[i];
+        total += s_wave[i];
+    }
+
+    const float nan = __uint_as_float(0x7fc00000u);
+    int o = before + incl - local;               // < total <= cells
+    unsigned bad = 0;
+    for (int g = g0; g < g1; g++) {
+        if (B0 != nullptr && (B0[g] | B1[g])) continue;
+        const int gy = g / a.gw, gx = g - gy * a.gw;
+        const float px = (float)(gx * a.step), py = (float)(gy * a.step);
+        const float cx = px + G[(size_t)g * 2], cy = py + G[(size_t)g * 2 + 1];
+        float4 q;
+        bad += rectify_point(prev, px, py, q.x, q.y) ? 0u : 1u;
+        if (isfinite(cx) && isfinite(cy)) bad += rectify_point(next, cx, cy, q.z, q.w) ? 0u : 1u;
+        else { q.z = nan; q.w = nan; }
+        *reinterpret_cast<float4*>(out + (size_t)o * 4) = q;
+        o++;
+    }
+    for (int k = total + tid; k < a.cells; k += RECTIFY_THREADS)
+        *reinterpret_cast<float4*>(out + (size_t)k * 4) = make_float4(nan, nan, nan, nan);
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) bad += __shfl_down(bad, s);
+    if ((tid & 63) == 0 && bad) atomicAdd(&s_bad, bad);      // an integer sum: the order does not matter
+    __syncthreads();
+    if (tid == 0) { a.counts[pair] = total; a.unsolved[pair] = s_bad; }
+}
+
 // Both directions: the checks, the preparation and the launch.  inverse: the row lever is the output's height, `unsolved` is
 // zeroed and counted.
 int rolling_batch(const char* who, bool inverse, vstab_ctx* ctx, const float* src, int n, int src_h, int src_w, const float* matrices,
@@ -205,6 +301,30 @@ extern "C" int vstab_row_residual_batch(vstab_ctx* ctx, const float* grid_flow, 
     const size_t lds = (size_t)gw * 2 * sizeof(float);     // <= 32 KB
     KernelTimer timer(ctx, "row_residual");
     hipLaunchKernelGGL(row_residual_kernel, dim3(blocks), dim3(ROW_THREADS), lds, ctx->stream, a);
+    VSTAB_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int vstab_rectify_samples_batch(vstab_ctx* ctx, const float* grid_flow, int pairs, int gh, int gw, int step, int work_h,
+                                           const double* velocity, double readout, const uint8_t* blocked, float* point_pairs,
+                                           int32_t* counts, uint32_t* unsolved)
+{
+    const char* who = "vstab_rectify_samples_batch";
+    VSTAB_REQUIRE(ctx != nullptr, "%s: ctx is NULL", who);
+    VSTAB_REQUIRE(grid_flow && velocity && point_pairs && counts && unsolved, "%s: NULL pointer argument", who);
+    VSTAB_REQUIRE(pairs > 0 && gh > 0 && gw > 0 && step > 0 && work_h >= 2, "%s: needs pairs > 0, a grid, step > 0 and an image of at least 2 rows (pairs=%d grid=%dx%d step=%d work_h=%d)", who, pairs, gw, gh, step, work_h);
+    VSTAB_REQUIRE(gh == (work_h + step - 1) / step, "%s: %d grid rows are not ceil(%d / %d)", who, gh, work_h, step);
+    VSTAB_REQUIRE((long long)gh * gw <= RECTIFY_MAX_SAMPLES, "%s: %lld sample points exceed the supported %d", who, (long long)gh * gw, RECTIFY_MAX_SAMPLES);
+    VSTAB_REQUIRE((long long)(gw - 1) * step < (1LL << 24), "%s: a grid of %d columns at step %d leaves the exact float32 range", who, gw, step);
+    VSTAB_REQUIRE(readout >= -1.0 && readout <= 1.0, "%s: readout=%g outside [-1, 1] (a fraction of the frame interval)", who, readout);
+    VSTAB_HIP(hipSetDevice(ctx->device));
+    void* d_velocity = nullptr;
+    if (int rc = vstab_stage_params(ctx, velocity, (size_t)(pairs + 1) * 6 * sizeof(double), &d_velocity)) return rc;
+    RectifyArgs a{};
+    a.grid = grid_flow; a.velocity = static_cast<const double*>(d_velocity); a.blocked = blocked; a.out = point_pairs;
+    a.counts = counts; a.unsolved = unsolved; a.gw = gw; a.cells = gh * gw; a.step = step; a.rho = readout; a.hm1 = (double)(work_h - 1);
+    KernelTimer timer(ctx, "rectify");
+    hipLaunchKernelGGL(rectify_kernel, dim3((unsigned)pairs), dim3(RECTIFY_THREADS), 0, ctx->stream, a);
     VSTAB_HIP(hipGetLastError());
     return 0;
 }

@@ -736,22 +736,40 @@ def _mesh_offsets(ctx, mesh, plan, grid, blocked, working_size, size, segments, 
 
 
 # ---- rolling shutter (beyond the reference; rolling_shutter.py, the rules are in include/vstab.h) -----------------------
-def _rolling_shutter(ctx, rolling, plan, grid_out, blocked, working_size, size, segments):
-    """-> (the warp's per-frame velocities f64 [N,6] in full-resolution px per frame, the readout, meta["rolling_shutter"]).
+def _rolling_shutter(ctx, rolling, plan, grid_out, blocked, working_size, size, segments, refit=None):
+    """-> (the plan, the warp's per-frame velocities f64 [N,6] in full-resolution px per frame, the readout,
+    meta["rolling_shutter"], the fit table of the refit or None).
     A given readout launches nothing here.  "auto": one launch of the row-residual kernel over the grid the estimator made,
-    against the working-resolution transitions the plan itself used, then the least-squares readout on the host."""
+    against the working-resolution transitions the plan itself used, then the least-squares readout on the host.
+    refit (rolling_refit; None: off, and the plan comes back as it went in): plan -> the plan formed again on a fit table.  The
+    readout is the first pass's either way; with a readout other than 0 the flow samples are corrected for it with the first
+    plan's working-resolution velocities (one launch of the rectifier), the pairs are fitted again on them (one launch of the
+    point fit) and the velocities of the warp and of the meta are the second plan's."""
     em = plan.estimated_motion
-    velocity = rolling_shutter_mod.velocities(em["matrices"], em["confidences"], segments)
+    work = working_size if working_size is not None else size
     estimate = None
     if rolling == rolling_shutter_mod.AUTO:
-        work = working_size if working_size is not None else size
         residual, count = ctx.row_residual_batch(grid_out[0], SAMPLE_STEP, work, em["work_matrices"], blocked=blocked)
         estimate = rolling_shutter_mod.estimate_readout(residual.cpu().numpy(), count.cpu().numpy(), em["work_matrices"],
                                                         em["confidences"], em["modes"], segments, work, SAMPLE_STEP)
         readout, source = estimate["readout"], estimate["source"]
     else:
         readout, source = float(rolling), "given"
-    return velocity, readout, rolling_shutter_mod.meta_block(readout, source, estimate, velocity, size)
+    table = refit_block = None
+    if refit is not None and readout == 0.0:          # "not_observable": nothing to correct for, nothing is launched
+        refit_block = rolling_shutter_mod.refit_block(0)
+    elif refit is not None:
+        work_velocity = rolling_shutter_mod.velocities(em["work_matrices"], em["confidences"], segments)
+        point_pairs, counts, unsolved = ctx.rectify_samples_batch(grid_out[0], SAMPLE_STEP, work, work_velocity, readout, blocked=blocked)
+        table = ctx.points_fit_batch(point_pairs, counts, plan.meta_head["transform_mode_requested"])
+        first, plan = em["matrices"], refit(table)
+        em = plan.estimated_motion
+        refit_block = rolling_shutter_mod.refit_block(1, first, em["matrices"], em["confidences"], segments, unsolved.cpu().numpy(), size)
+    velocity = rolling_shutter_mod.velocities(em["matrices"], em["confidences"], segments)
+    block = rolling_shutter_mod.meta_block(readout, source, estimate, velocity, size)
+    if refit_block is not None:
+        block["refit"] = refit_block
+    return plan, velocity, readout, block, table
 
 
 # ---- drift correction (beyond the reference; drift_correction.py, the rule is in include/vstab.h) ------------------------
@@ -814,6 +832,7 @@ class FlowRequest:
     drift: Optional[int] = None        # drift_correction.check_request: the keyframe spacing | None
     drift_exposure: bool = False       # drift_correction.check_options: the keyframe alignment estimates a gain and an offset
     drift_mask: bool = False           # ... and leaves out what the estimation mask's block grid names
+    refit: bool = False                # rolling_shutter.check_refit_request: the transitions are fitted again on rectified samples
 
     @property
     def needs_host_plan(self) -> bool:
@@ -831,7 +850,7 @@ class FlowRequest:
         mask's block grid, which drift_mask reads behind the fits, is made before the estimator runs and is held by the
         call itself for all of its length: it is no by-product and needs no entry here.)"""
         keep = ("gray_out",) if (self.scene is not None and self.scene.mode == "auto") or self.drift is not None else ()
-        return keep + (("grid_out",) if self.mesh is not None or self.rolling == rolling_shutter_mod.AUTO else ())
+        return keep + (("grid_out",) if self.mesh is not None or self.rolling == rolling_shutter_mod.AUTO or self.refit else ())
 
 
 def check_flow_request(framing_mode: str, transform_mode: str, estimator: str, kw: Dict[str, Any]) -> FlowRequest:
@@ -873,8 +892,9 @@ def check_flow_request(framing_mode: str, transform_mode: str, estimator: str, k
         drift_correction_mod.check_pipeline(transform_mode, bool(subject), kw["estimation_mask"], kw.get("drift_mask") is True)
     drift_exposure, drift_mask = drift_correction_mod.check_options(drift, kw.get("drift_exposure"), kw.get("drift_mask"),
                                                                     kw["estimation_mask"])
+    refit = rolling_shutter_mod.check_refit_request(kw.get("rolling_refit"), rolling, estimator, drift)
     return FlowRequest(estimator, temporal_fill, fill_blend, sharpness, handoff, zoom, scene, mesh, bool(kw["mesh_motion"]),
-                       bool(subject), rolling, spatial_fill, stability_report, mask_margin, drift, drift_exposure, drift_mask)
+                       bool(subject), rolling, spatial_fill, stability_report, mask_margin, drift, drift_exposure, drift_mask, refit)
 
 
 def _check_request_against_clip(request: FlowRequest, kw: Dict[str, Any], transform_mode: str, total_frames: int, size) -> None:
@@ -1010,6 +1030,7 @@ def _stabilize_frames(
     mask_hold=None,
     mask_tapered=None,
     rolling_shutter=None,
+    rolling_refit=None,
     drift_correction=None,
     drift_exposure=None,
     drift_mask=None,
@@ -1102,6 +1123,16 @@ def _stabilize_frames(
     estimator "subject"; everything behind the final warp follows unchanged.  meta["rolling_shutter"] reports the readout, the
     skew it amounts to and every frame's velocity.  None / 0: the behaviour and meta without it, byte for byte, and nothing new
     is launched.  Bypass paths ignore it.
+    rolling_refit (beyond the reference, None by default; with rolling_shutter only): True fits the pair transitions again on
+    flow samples that have been corrected for the readout.  The row correction acts on the final warp; the transitions in front
+    of it were fitted on sheared samples, and a similarity fit takes part of the shear for rotation and scale.  Between the
+    first plan and the final one, both ends of every admitted flow sample are rectified with the first pass's per-frame
+    velocities at working resolution (include/vstab.h states the rule), the pairs are fitted again on them by the point fit,
+    and the plan -- sticky modes included -- is formed again on that table; the readout ("auto": estimated on the first
+    pass) is unchanged, the warp's velocities and the meta's are the second plan's, so Motion Apply's rolling=True replays and
+    undoes the run as before.  One pass; a readout of 0 ("not_observable") launches nothing.  For the DIS and TV-L1 estimators,
+    without drift_correction; meta["rolling_shutter"]["refit"] reports passes, pairs_refit, samples_unsolved_max and how far
+    the transitions moved.  None / False: the behaviour and meta without it, byte for byte, and nothing new is launched.
     drift_correction (beyond the reference, None by default): True (a keyframe every 32 frames) or the keyframe spacing, an int
     in 2..4096.  Every estimator measures consecutive pairs, and the bias of a pair adds up along the chain: a locked picture
     creeps.  With the keyword every frame is registered directly against the latest keyframe before it, and every keyframe
@@ -1238,8 +1269,13 @@ def _stabilize_frames(
     if zoom is not None:
         plan, zoom_block = _dynamic_zoom(ctx, zoom, plan, offsets, segments)
     if rolling is not None:
-        velocity, readout, rolling_block = _rolling_shutter(ctx, rolling, plan, extras.get("grid_out"), blocked, working_size, size,
-                                                            segments)
+        def plan_again(table):
+            return plan_stabilization(ctx, table, size, total_frames, *args, estimator=estimator, segments=segments)
+
+        plan, velocity, readout, rolling_block, refit_table = _rolling_shutter(
+            ctx, rolling, plan, extras.get("grid_out"), blocked, working_size, size, segments, plan_again if request.refit else None)
+        if refit_table is not None:
+            fit_records = refit_table          # what the meta's counts describe from here on
     warp_args = dict(border=hm.border_value(padding_rgb), want_mask=True, want_count=True)
     if mesh is not None:
         dst, mask, counts = ctx.mesh_warp_batch(device_frames, plan.final_matrices, plan.output_size, offsets, **warp_args)

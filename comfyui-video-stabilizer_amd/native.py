@@ -199,6 +199,9 @@ _SIGNATURES = {
     "vstab_row_residual_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                   C.c_void_p, C.c_void_p]),
+    "vstab_rectify_samples_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_void_p,
+                  C.c_void_p, C.c_void_p, C.c_void_p]),
     "vstab_cover_extent_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                   C.c_void_p]),
@@ -964,6 +967,31 @@ class Context:
             _dev_ptr(blocked) if blocked is not None else None, _dev_ptr(residual), _dev_ptr(count)),
             "vstab_row_residual_batch")
         return residual, count
+
+    def rectify_samples_batch(self, grid_flow, step, work_size, velocity, readout, blocked=None):
+        """The flow grid's samples as point pairs corrected for the readout (vstab_rectify_samples_batch; the rule is in
+        include/vstab.h).  grid_flow f32 [P,gh,gw,2] (device), work_size = (w, h) of the estimation images, velocity f64 [P+1,6]
+        (host) in working px per frame interval, readout in [-1, 1], blocked u8 [P+1,gh,gw] or None ->
+        (point_pairs f32 [P,gh*gw,4]: the admitted samples in grid order, NaN rows behind them; counts i32 [P]; unsolved i32 [P]),
+        device tensors: what points_fit_batch takes."""
+        torch = self.torch
+        who = "rectify_samples_batch"
+        if grid_flow.dtype != torch.float32 or grid_flow.dim() != 4 or grid_flow.shape[3] != 2:
+            raise ValueError(f"{who} expects a float32 [P,gh,gw,2] tensor")
+        grid_flow, blocked, pairs, gh, gw = self._fit_inputs(grid_flow, blocked)
+        ww, wh, step = int(work_size[0]), int(work_size[1]), int(step)
+        if step < 1 or (gh, gw) != ((wh + step - 1) // step, (ww + step - 1) // step):
+            raise ValueError(f"{who}: a grid of {gw}x{gh} samples is not a {ww}x{wh} image at step {step}")
+        v, readout = self._rolling_inputs(who, velocity, readout, pairs + 1, null_ok=True)
+        point_pairs = torch.empty((pairs, gh * gw, 4), dtype=torch.float32, device=self.device)
+        counts = torch.empty((pairs,), dtype=torch.int32, device=self.device)
+        unsolved = torch.empty((pairs,), dtype=torch.int32, device=self.device)
+        self.use_torch_stream()
+        _check(self.lib.vstab_rectify_samples_batch(
+            self.handle, _dev_ptr(grid_flow), pairs, gh, gw, step, wh, v.ctypes.data if v is not None else None, readout,
+            _dev_ptr(blocked) if blocked is not None else None, _dev_ptr(point_pairs), _dev_ptr(counts), _dev_ptr(unsolved)),
+            "vstab_rectify_samples_batch")
+        return point_pairs, counts, unsolved
 
     def cover_extent_batch(self, matrices, src_size, out_size, offsets=None, subpix=None):
         """How far the warp's own coverage reaches around the canvas centre (vstab_cover_extent_batch; the rule is in

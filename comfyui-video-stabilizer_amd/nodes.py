@@ -947,6 +947,37 @@ class VideoStabilizerFlowRolling(io.ComfyNode):
                                    keep_fov, padding_color, rolling_shutter="auto" if float(readout) == 0.0 else float(readout))
 
 
+class VideoStabilizerFlowRollingRefit(io.ComfyNode):
+    """The Rolling Shutter node with the refit: the pair transitions are fitted a second time on flow samples corrected for
+    the readout, so that the fit no longer takes part of the skew for rotation and scale (rolling_shutter.py).  Not one of the
+    reference's nodes: it is listed by an extension but kept out of NODE_CLASSES."""
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        schema = io.Schema(
+            node_id="video_stabilizer_flow_rolling_refit",
+            display_name="Video Stabilizer Flow (Rolling Shutter, Refit)",
+            category="Video/Stabilization",
+            description=("Video Stabilizer Flow (Rolling Shutter) that also estimates the camera motion a second time on flow "
+                         "samples corrected for the sensor's readout."),
+        )
+        schema.inputs = VideoStabilizerFlowRolling.define_schema().inputs + [
+            io.Boolean.Input("refit", default=True, display_name="Refit",
+                             tooltip=("Fit the frame-to-frame motion again on flow samples corrected for the readout.  Off: "
+                                      "the Rolling Shutter node.")),
+        ]
+        schema.outputs = _estimator_outputs()
+        return schema
+
+    @classmethod
+    def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
+                strength: float, smooth: float, keep_fov: float, padding_color: str, readout: float = 0.0,
+                refit: bool = True) -> io.NodeOutput:
+        return _run_estimator_node("flow", frames, frame_rate, framing_mode, transform_mode, camera_lock, strength, smooth,
+                                   keep_fov, padding_color, rolling_shutter="auto" if float(readout) == 0.0 else float(readout),
+                                   rolling_refit=bool(refit))
+
+
 class VideoStabilizerFlowAnchored(io.ComfyNode):
     """The Flow node with drift correction: every frame is registered directly against a keyframe, so the error of the
     consecutive-pair estimates no longer adds up along the clip and a locked picture stays put (drift_correction.py).  Not
@@ -1199,3 +1230,6 @@ VideoStabilizerAmdAnchorExtension = _extend(
 VideoStabilizerAmdAnchorExposureExtension = _extend(
     VideoStabilizerAmdAnchorExtension, VideoStabilizerFlowAnchoredExposure, name="VideoStabilizerAmdAnchorExposureExtension",
     doc="The drift-free extension's twenty-two nodes plus Video Stabilizer Flow (Drift-Free, Exposure-Matched).")
+VideoStabilizerAmdRollingRefitExtension = _extend(
+    VideoStabilizerAmdAnchorExposureExtension, VideoStabilizerFlowRollingRefit, name="VideoStabilizerAmdRollingRefitExtension",
+    doc="The exposure-matched extension's twenty-three nodes plus Video Stabilizer Flow (Rolling Shutter, Refit).")

@@ -20,8 +20,17 @@ The round trip: `parse_block` reads the block back for Motion Apply (`apply_moti
 correction again on the run's source frames (`rolling_warp_batch`) or undoes it on the stabilized ones
 (`native.Context.rolling_unwarp_batch`, the closed-form inverse: tau is known from the output row).
 
+The refit (`rolling_refit=True`): the warp corrects rows, but the pair transitions in front of it were fitted on samples that
+the readout had sheared, and a similarity fit takes part of that shear for rotation and scale.  One pass between the first
+plan and the final one rectifies both ends of every flow sample with the first pass's own per-frame velocities, at working
+resolution (`native.Context.rectify_samples_batch`: the inverse's closed form at a point), fits the pairs again on them
+(`native.Context.points_fit_batch`, unchanged) and forms the plan again; the warp's velocities and the meta's come from that
+second plan.  `check_refit_request` and `refit_block` are its host side.
+
 Out of scope: perspective mode, `crop` framing and dynamic zoom, the mesh, temporal-fill, sharpness-transfer, subject and
-sharded paths, bicubic and motion-blur warps, a per-row homography mixture, readout tables per camera model.
+sharded paths, bicubic and motion-blur warps, a per-row homography mixture, readout tables per camera model; for the refit
+also a second readout estimate from the rectified residuals (which would drop the `f_k` factor), Classic's tracked corners,
+the images that drift correction registers, `plan_kernel`.
 """
 
 from __future__ import annotations
@@ -89,6 +98,60 @@ def check_pipeline(request, transform_mode: str, framing_mode: str, estimator: s
     if request == AUTO and estimator in _ESTIMATOR_LIMITS:
         raise ValueError(f"rolling_shutter='auto' is not supported with estimator {estimator!r}: {_ESTIMATOR_LIMITS[estimator]} "
                          "Give the readout as a number.")
+
+
+_REFIT_ESTIMATOR_LIMITS = {
+    "classic": "the Classic estimator tracks sparse corners: it has no grid of flow samples to rectify.",
+    "flow_phase_correlate": "phase correlation yields one global shift per pair: it has no grid of flow samples to rectify.",
+}
+
+
+def check_refit_request(value, request, estimator: str, drift=None) -> bool:
+    """rolling_refit, checked without the clip or a GPU -> whether the transitions are fitted again on readout-corrected
+    samples.  value: None or a bool; request: check_request's answer for rolling_shutter; drift: drift_correction's checked
+    request (None: off).  None / False -> False."""
+    if value is None:
+        return False
+    if not isinstance(value, (bool, np.bool_)):
+        raise ValueError(f"rolling_refit={value!r}: expected None or a bool")
+    if not value:
+        return False
+    if request is None:
+        raise ValueError("rolling_refit=True needs rolling_shutter: without a readout there is nothing to correct the samples for.")
+    if estimator in _REFIT_ESTIMATOR_LIMITS:
+        raise ValueError(f"rolling_refit is not supported with estimator {estimator!r}: {_REFIT_ESTIMATOR_LIMITS[estimator]}")
+    if drift is not None:
+        raise ValueError("rolling_refit is not supported with drift_correction: the keyframe alignment registers images that "
+                         "have not been corrected for the readout, and its poses overwrite the fit table.")
+    return True
+
+
+def transition_change_px(first, second, size) -> np.ndarray:
+    """Per pair, the largest displacement of the four corners of a w x h frame between two affine transitions [P,3,3] -> [P] px."""
+    A = np.asarray(first, dtype=np.float64).reshape(-1, 3, 3)
+    B = np.asarray(second, dtype=np.float64).reshape(-1, 3, 3)
+    w, h = int(size[0]), int(size[1])
+    corners = np.array([[0.0, 0.0, 1.0], [w - 1.0, 0.0, 1.0], [0.0, h - 1.0, 1.0], [w - 1.0, h - 1.0, 1.0]]).T
+    d = (np.matmul(A, corners) - np.matmul(B, corners))[:, :2]
+    return np.sqrt((d * d).sum(axis=1)).max(axis=1) if A.shape[0] else np.zeros(0)
+
+
+def refit_block(passes: int, first=None, second=None, confidences=None, segments=None, unsolved=None, size=None) -> Dict[str, Any]:
+    """meta["rolling_shutter"]["refit"].  passes 0 (a readout of 0: nothing was launched): zeros.  Else first / second: the
+    full-resolution transitions of the first pass and of the refit, confidences / segments: the refit plan's, unsolved: the
+    rectifier's per-pair counts.  pairs_refit: the pairs whose refit transition carries a measured motion."""
+    if not passes:
+        return {"passes": 0, "pairs_refit": 0, "samples_unsolved_max": 0, "transition_change_px_mean": 0.0,
+                "transition_change_px_max": 0.0}
+    change = transition_change_px(first, second, size)
+    unsolved = np.asarray(unsolved).reshape(-1)
+    return {
+        "passes": int(passes),
+        "pairs_refit": int(_available(confidences, segments, change.shape[0]).sum()),
+        "samples_unsolved_max": int(unsolved.max()) if unsolved.size else 0,
+        "transition_change_px_mean": float(change.mean()) if change.size else 0.0,
+        "transition_change_px_max": float(change.max()) if change.size else 0.0,
+    }
 
 
 def _available(confidences, segments, pairs: int) -> np.ndarray:

@@ -747,6 +747,43 @@ int vstab_rolling_unwarp_batch(vstab_ctx* ctx, const float* src, int n, int src_
 int vstab_row_residual_batch(vstab_ctx* ctx, const float* grid_flow, int pairs, int gh, int gw, int step, int work_h,
                              int work_w, const float* transitions, const uint8_t* blocked, float* residual, int32_t* count);
 
+/* vstab_rectify_samples_batch -- the flow grid's samples as point pairs whose two ends are corrected for the readout, so that
+ * the pair transitions can be fitted again on what a global shutter would have shown (rolling_refit; rolling_shutter.py).  The
+ * warp corrects rows; a fit on the raw samples has already taken part of the shear for rotation and scale.  For pair k and
+ * grid sample g = gy*gw + gx, in grid order:
+ *   - p = ((float)(gx*step), (float)(gy*step));  c = p + flow[k][g] in float32, the fit's own load (vstab_sample_fit_batch).
+ *   - the sample is ADMITTED iff it is blocked neither in frame k nor in frame k+1 (blocked == NULL: every sample is): the
+ *     estimation mask's rule.  A sample whose flow is not finite is admitted like any other.
+ *   - the RECTIFIED position of an observed point s of a frame with velocity V is q = s + e, with e exactly
+ *     vstab_rolling_unwarp_batch's e for (x, y) = s as fp64, hm1 = work_h - 1 and rho = readout -- tau, a..d, det, vx, vy, rx,
+ *     ry and e as stated there, every operation IEEE fp64 and rounded on its own, nothing fused -- with one addition: the row
+ *     that enters tau is clamped as the forward rule clamps yc, yr = (y < 0) ? 0 : y, yr = (yr > hm1) ? hm1 : yr (a NaN stays
+ *     a NaN), tau = rho * (yr / hm1 - 0.5); vx and vy take y itself.  VSTAB_ROLLING_UNWARP_MIN_DET and the non-finite test
+ *     apply unchanged: an UNSOLVED point gets e = (0, 0) and is counted.
+ *   - prev = p rectified with V[k], next = c rectified with V[k+1]; each coordinate of q is rounded once to float32.
+ *   - if c.x or c.y is not finite (a flow sample that is not), next = (NaN, NaN) -- vstab_lk_track_batch's "untracked" form --
+ *     its solve is not attempted and not counted; prev is written as for any sample.
+ *   - output, admitted samples only, compacted, grid order kept:
+ *       point_pairs dev [pairs, gh*gw, 4] f32 (prev.x, prev.y, next.x, next.y): vstab_points_fit_batch's input layout with
+ *                   max_points = gh*gw; the rows from counts[k] on are NaN (0x7fc00000, as the untracked form), so the whole
+ *                   array can be compared in bits
+ *       counts      dev [pairs] i32: admitted samples
+ *       unsolved    dev [pairs] u32: unsolved points, prev and next counted one each
+ * Invariant: readout == 0 or all-zero velocities give prev == p and next == c in bits (e is a zero of either sign, and
+ * neither p nor c is ever a negative zero).
+ * The refit is vstab_points_fit_batch on point_pairs and counts, unchanged.  Its thresholds are the Classic rule's -- fewer
+ * than 12 points or fewer than 8 finite ones give no candidate -- where the grid fit asks for 12 finite ones; on any real grid
+ * (thousands of samples) the difference is immaterial.  total_points is the admitted count, as in the masked grid fit, and
+ * the translation confidence finite / admitted.
+ *   grid_flow dev [pairs, gh, gw, 2] f32;  blocked dev [pairs+1, gh, gw] u8 or NULL: as for vstab_sample_fit_batch_masked
+ *   velocity  host [pairs+1, 6] f64 (V0..V5 per frame), px of the WORKING image per frame interval, staged by the call
+ *   readout in [-1, 1];  work_h >= 2;  gh == ceil(work_h / step);  gh*gw <= 16384, as the fit requires
+ * One workgroup per pair: an ordered block compaction of the admitted samples (the fit kernel's wavefront scan); the two
+ * frames' coefficients and the readout are uniform.  Asynchronous on the context's stream; timing kind "rectify". */
+int vstab_rectify_samples_batch(vstab_ctx* ctx, const float* grid_flow, int pairs, int gh, int gw, int step, int work_h,
+                                const double* velocity, double readout, const uint8_t* blocked, float* point_pairs,
+                                int32_t* counts, uint32_t* unsolved);
+
 /* ---- dynamic zoom (not a reference feature, off by default): how far a warp's own coverage reaches around the centre ----
  * A per-frame zoom that hides the frame's own border needs to know the largest centred rectangle of the canvas the warp
  * covers.  Closed-form geometry would drift from the warp at the nearest-rounding boundary and does not exist for a mesh,
