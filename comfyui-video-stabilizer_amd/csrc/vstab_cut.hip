@@ -15,25 +15,7 @@ constexpr int CUT_ROWS = 16;      // rows of a pair per workgroup (960x540: 34 w
 constexpr int CUT_THREADS = 256;
 constexpr int CUT_WAVES = CUT_THREADS / 64;
 
-struct CutMatrix {
-    double m[9];
-};
-
-// one pixel of the rule: returns 1 and *q (index into the TO image) if p = (x, y) lands inside
-__device__ __forceinline__ bool cut_lookup(const CutMatrix& A, int x, int y, int h, int w, int* q)
-{
-    const double dx = (double)x, dy = (double)y;
-    const double X = (A.m[0] * dx + A.m[1] * dy) + A.m[2];
-    const double Y = (A.m[3] * dx + A.m[4] * dy) + A.m[5];
-    const double W = (A.m[6] * dx + A.m[7] * dy) + A.m[8];
-    if (!(W > 0.0 && W <= 1.7976931348623157e308)) return false;   // w <= 0 or not finite
-    // (X / 1.0 is X: the division is skipped where it changes no bit)
-    const double qx = (W == 1.0) ? X : X / W, qy = (W == 1.0) ? Y : Y / W;
-    const double rx = rint(qx), ry = rint(qy);          // half-to-even; NaN / inf fail the comparisons below
-    if (!(rx >= 0.0 && rx <= (double)(w - 1) && ry >= 0.0 && ry <= (double)(h - 1))) return false;
-    *q = (int)ry * w + (int)rx;
-    return true;
-}
+// (the mapping of one pixel, vstab_pair_lookup, is in vstab_internal.h: the deflicker measures through the same one)
 
 // VEC: w % 16 == 0 and the base 16-byte aligned (every row then is)
 template <bool VEC>
@@ -44,7 +26,7 @@ __global__ __launch_bounds__(CUT_THREADS) void pair_residual_kernel(const uint8_
     __shared__ unsigned s_sum[CUT_WAVES], s_in[CUT_WAVES];
     const int pair = (int)blockIdx.x / tiles, tile = (int)blockIdx.x - pair * tiles;
     const int y0 = tile * CUT_ROWS, rows = min(CUT_ROWS, h - y0);
-    CutMatrix A;
+    PairMatrix A;
     for (int k = 0; k < 9; k++) A.m[k] = (double)mats[(size_t)pair * 9 + k];
     const uint8_t* __restrict__ from = gray + (size_t)pair * h * w;
     const uint8_t* __restrict__ to = from + (size_t)h * w;
@@ -60,7 +42,7 @@ __global__ __launch_bounds__(CUT_THREADS) void pair_residual_kernel(const uint8_
 #pragma unroll
             for (int k = 0; k < 16; k++) {
                 int q;
-                if (cut_lookup(A, x0 + k, y, h, w, &q)) {
+                if (vstab_pair_lookup(A, x0 + k, y, h, w, &q)) {
                     const int a = (int)((word[k >> 2] >> ((k & 3) * 8)) & 0xffu), b = (int)to[q];
                     acc += (unsigned)abs(a - b);
                     cnt += 1;
@@ -70,7 +52,7 @@ __global__ __launch_bounds__(CUT_THREADS) void pair_residual_kernel(const uint8_
             const int x1 = min(w, x0 + 16);
             for (int x = x0; x < x1; x++) {
                 int q;
-                if (cut_lookup(A, x, y, h, w, &q)) {
+                if (vstab_pair_lookup(A, x, y, h, w, &q)) {
                     acc += (unsigned)abs((int)row[x] - (int)to[q]);
                     cnt += 1;
                 }

@@ -222,6 +222,27 @@ __host__ __device__ inline bool vstab_invert3x3_hd(const double* S, double* D)
 }
 bool vstab_invert3x3(const double* S, double* D);
 
+// The pair mapping of the scene-cut score and of the deflicker's measurement (include/vstab.h states it once, under
+// vstab_pair_residual_batch): a pixel p = (x, y) of the FROM frame through the pair's transition, widened to fp64.
+struct PairMatrix {
+    double m[9];
+};
+// one pixel of the rule: returns true and *q (pixel index into the TO frame) if p lands inside
+__device__ __forceinline__ bool vstab_pair_lookup(const PairMatrix& A, int x, int y, int h, int w, int* q)
+{
+    const double dx = (double)x, dy = (double)y;
+    const double X = (A.m[0] * dx + A.m[1] * dy) + A.m[2];
+    const double Y = (A.m[3] * dx + A.m[4] * dy) + A.m[5];
+    const double W = (A.m[6] * dx + A.m[7] * dy) + A.m[8];
+    if (!(W > 0.0 && W <= 1.7976931348623157e308)) return false;   // w <= 0 or not finite
+    // (X / 1.0 is X: the division is skipped where it changes no bit)
+    const double qx = (W == 1.0) ? X : X / W, qy = (W == 1.0) ? Y : Y / W;
+    const double rx = rint(qx), ry = rint(qy);          // half-to-even; NaN / inf fail the comparisons below
+    if (!(rx >= 0.0 && rx <= (double)(w - 1) && ry >= 0.0 && ry <= (double)(h - 1))) return false;
+    *q = (int)ry * w + (int)rx;
+    return true;
+}
+
 // The warp kernels' per-(frame, sample) transform record and how it is filled from a float32 matrix
 // (cv::warpPerspective: M.convertTo(CV_64F), invert).
 struct WarpXform {

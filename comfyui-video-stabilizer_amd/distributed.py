@@ -217,7 +217,7 @@ def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, t
                       estimator: str = "flow", stats: Optional[Dict[str, float]] = None, want_meta: bool = True,
                       check_value_range: bool = True, temporal_fill: int = 0, estimation_mask=None, scene_cuts=None,
                       mesh_warp=None, dynamic_zoom=None, sharpness_transfer=None, rolling_shutter=None,
-                      drift_correction=None, drift_exposure=None, drift_mask=None):
+                      drift_correction=None, drift_exposure=None, drift_mask=None, deflicker=None, deflicker_mode=None):
     """Sharded equivalent of `_stabilize_frames` (flow.py:213-640).
 
     local_frames: device tensor [n_local (+1 halo for rank > 0 that owns frames), H, W, 3] float32 -- this rank's frames
@@ -279,6 +279,13 @@ def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, t
         ("drift_mask", drift_mask is not None and drift_mask is not False,
          f"stabilize_sharded does not support drift_mask={drift_mask!r}: the keyframe alignment it belongs to is not "
          "sharded; run the single-GPU pipeline for it"),
+        # a pair may straddle two ranks, and the log-gain chain and its box mean run through the whole clip
+        ("deflicker", deflicker is not None and deflicker is not False,
+         f"stabilize_sharded does not support deflicker={deflicker!r}: the deflicker is not sharded (a pair may straddle "
+         "two ranks, and the gain chain runs through the whole clip); run the single-GPU pipeline for it"),
+        ("deflicker_mode", deflicker_mode is not None,
+         f"stabilize_sharded does not support deflicker_mode={deflicker_mode!r}: the deflicker it belongs to is not sharded; "
+         "run the single-GPU pipeline for it"),
     )
     for _keyword, requested, message in refusals:
         if requested:

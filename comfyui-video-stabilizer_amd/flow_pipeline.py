@@ -21,6 +21,7 @@ from typing import Any, Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 
+from . import deflicker as deflicker_mod
 from . import dynamic_zoom as dynamic_zoom_mod
 from . import host_math as hm
 from . import mesh_warp as mesh_warp_mod
@@ -615,6 +616,20 @@ def _temporal_fill(ctx, device_frames, dst, mask, plan, meta, radius: int, blend
         feather=blend[0], exposure=blend[1])
 
 
+def _deflicker(ctx, device_frames, dst, mask, plan, meta, request, segments=None) -> None:
+    """Takes the exposure steps between consecutive frames out of the warped frames in place (deflicker.py) and adds
+    meta["deflicker"]; the mask and the other meta keys are unchanged.  request: deflicker.check_request's answer.  It measures
+    on the SOURCE frames through the plan's own full-resolution transitions -- whatever estimator, refit or drift correction
+    made them -- and applies to the frame's own pixels: padding keeps its colour.  `crop` framing has no mask: every pixel is
+    own."""
+    if request is None:
+        return
+    em = plan.estimated_motion
+    meta["deflicker"] = deflicker_mod.deflicker_on_device(
+        ctx, request, device_frames, dst, None if plan.framing_mode == "crop" else mask, np.asarray(em["matrices"], dtype=np.float32),
+        em["confidences"], plan.fps_effective, segments)
+
+
 def _sharpness_transfer(ctx, device_frames, dst, mask, plan, meta, sharp) -> None:
     """Pulls the own pixels of blurred frames towards what sharper neighbours show there, in place (sharpness_transfer.py), and
     adds meta["sharpness_transfer"]; mask and the other meta keys are unchanged.  sharp = (radius, alpha) or None:
@@ -832,6 +847,7 @@ class FlowRequest:
     drift: Optional[int] = None        # drift_correction.check_request: the keyframe spacing | None
     drift_exposure: bool = False       # drift_correction.check_options: the keyframe alignment estimates a gain and an offset
     drift_mask: bool = False           # ... and leaves out what the estimation mask's block grid names
+    deflicker: Any = None              # deflicker.check_request: Request | None
     refit: bool = False                # rolling_shutter.check_refit_request: the transitions are fitted again on rectified samples
 
     @property
@@ -893,8 +909,12 @@ def check_flow_request(framing_mode: str, transform_mode: str, estimator: str, k
     drift_exposure, drift_mask = drift_correction_mod.check_options(drift, kw.get("drift_exposure"), kw.get("drift_mask"),
                                                                     kw["estimation_mask"])
     refit = rolling_shutter_mod.check_refit_request(kw.get("rolling_refit"), rolling, estimator, drift)
+    deflicker = deflicker_mod.check_request(kw.get("deflicker"), kw.get("deflicker_mode"))
+    if deflicker is not None:
+        deflicker_mod.check_pipeline(estimator, temporal_fill, fill_blend[1], sharpness)
     return FlowRequest(estimator, temporal_fill, fill_blend, sharpness, handoff, zoom, scene, mesh, bool(kw["mesh_motion"]),
-                       bool(subject), rolling, spatial_fill, stability_report, mask_margin, drift, drift_exposure, drift_mask, refit)
+                       bool(subject), rolling, spatial_fill, stability_report, mask_margin, drift, drift_exposure, drift_mask,
+                       refit=refit, deflicker=deflicker)
 
 
 def _check_request_against_clip(request: FlowRequest, kw: Dict[str, Any], transform_mode: str, total_frames: int, size) -> None:
@@ -922,13 +942,17 @@ class FlowArgs(NamedTuple):
 
 
 def _finish(ctx, request: FlowRequest, plan, device_frames, dst, mask, meta, segments, keep_on_device: bool, verdict):
-    """Everything behind the warp, for either plan path: the five post-warp passes, then the result on the device or the host.
-    The ORDER is a correctness rule.  The sharpness transfer runs before the fills: a filled pixel gets mask 0 and would be
-    taken for an own one.  Temporal fill comes before spatial fill: seen pixels before invented ones.  The stability report
+    """Everything behind the warp, for either plan path: the six post-warp passes, then the result on the device or the host.
+    The ORDER is a correctness rule.  The deflicker runs first: it scales a frame's OWN pixels (padding keeps its colour), so it
+    has to see the warp's mask before a fill clears it, and the passes behind it -- the exposure match of the blended fill, the
+    fills themselves, the stability report -- then work on deflickered frames (the sharpness transfer and a hard temporal
+    fill, which would bring uncorrected neighbour pixels in, are refused with it).  The sharpness transfer runs before the
+    fills: a filled pixel gets mask 0 and would be taken for an own one.  Temporal fill comes before spatial fill: seen pixels before invented ones.  The stability report
     measures behind every fill; the spatial fill leaves the mask as it is, so its invented pixels stay out of it.  The mask
     hand-off runs last, so that every other pass has seen the true mask; it replaces only the mask that is returned.  Each
     pass adds its own meta block, in this order, and nothing else in the meta changes.
     segments: the shots under scene cuts, None for one continuous camera move (always on the device-plan path)."""
+    _deflicker(ctx, device_frames, dst, mask, plan, meta, request.deflicker, segments)
     _sharpness_transfer(ctx, device_frames, dst, mask, plan, meta, request.sharpness)
     _temporal_fill(ctx, device_frames, dst, mask, plan, meta, request.temporal_fill, request.fill_blend)
     _spatial_fill(ctx, dst, mask, plan, meta, request.spatial_fill)
@@ -1031,6 +1055,8 @@ def _stabilize_frames(
     mask_tapered=None,
     rolling_shutter=None,
     rolling_refit=None,
+    deflicker=None,
+    deflicker_mode=None,
     drift_correction=None,
     drift_exposure=None,
     drift_mask=None,
@@ -1150,7 +1176,21 @@ def _stabilize_frames(
     drift_mask=True (needs estimation_mask) leaves the pixels the estimation mask's block grid names, in the keyframe or in the
     frame, out of the alignment, and with it drift_correction accepts estimation_mask.  Both use the second form of the rule
     (include/vstab.h); meta["drift_correction"] gains `exposure` (the gains and offsets), `masked_fraction_mean` and
-    frames_kept["gain"].  None / False: the behaviour and meta without them, byte for byte, and nothing new is launched."""
+    frames_kept["gain"].  None / False: the behaviour and meta without them, byte for byte, and nothing new is launched.
+    deflicker, deflicker_mode (beyond the reference, None by default): True (a window of 1 s) or a window in seconds in (0, 60].
+    Auto exposure and auto white balance hunt while the camera shakes, and once the picture stands still the brightness steps
+    are what is left to see.  Every consecutive pair of SOURCE frames is compared through its own full-resolution transition on
+    a lattice of well-exposed pixels: the histogram of the registered 16-bit level ratios gives a median no moving subject
+    shifts while it owns less than half of the samples, the level sums inside a band around it give the pair's gain
+    (deflicker.py; include/vstab.h states both rules).  The log-gains are chained per shot -- and no further than a pair with
+    confidence 0 or too few samples --, the chain's box mean over the window is taken, and every frame's own pixels are
+    multiplied by exp(mean - chain), at most one stop: the high-pass, so a deliberate exposure ramp survives.
+    deflicker_mode None / "exposure" applies one gain to the three colours, "rgb" one per colour (white balance too).  It is
+    the first pass behind the warp, so the blended fill's exposure match, the fills and the stability report see
+    deflickered frames; padding keeps its colour.  Behind either plan path, with every camera estimator; not with estimator
+    "subject", sharpness_transfer, or temporal_fill without fill_exposure=True.  meta["deflicker"] reports every pair's gain,
+    every frame's correction and the chain's RMS step before and after.  None / False: the behaviour and meta without it, byte
+    for byte, and nothing new is launched.  Bypass paths ignore it."""
     kw = dict(locals())     # every argument by name (nothing else is local yet): the keyword extras are read from here
     request = check_flow_request(framing_mode, transform_mode, estimator, kw)
     estimator = request.estimator

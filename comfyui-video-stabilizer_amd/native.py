@@ -237,6 +237,12 @@ _SIGNATURES = {
     "vstab_mask_hold_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vstab_mask_grow_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vstab_pair_gain_hist_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vstab_pair_gain_sums_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vstab_apply_gain_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vstab_gftt_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p,
                   C.c_void_p]),
@@ -1304,6 +1310,82 @@ class Context:
             self.handle, _dev_ptr(a), _dev_ptr(mask_a) if mask_a is not None else None, _dev_ptr(b),
             _dev_ptr(mask_b) if mask_b is not None else None, n, h, w, _dev_ptr(sse), _dev_ptr(count)), "vstab_frame_sse_batch")
         return sse, count
+
+    # ------------------------------------------------------------------ deflicker
+    def _pair_gain_args(self, who, src, transitions, active):
+        """The arguments the two measuring entries share, checked -> (n, h, w, transitions f32 [n-1,9], active u8 [n-1] | None)."""
+        torch = self.torch
+        if not (isinstance(src, torch.Tensor) and src.dtype == torch.float32 and src.device == self.device and src.is_contiguous()):
+            raise ValueError(f"{who}: src must be a contiguous float32 tensor on {self.device}")
+        if src.dim() != 4 or src.shape[3] != 3 or src.shape[0] < 2:
+            raise ValueError(f"{who}: src of shape {tuple(src.shape)} is not [n,h,w,3] with n >= 2")
+        n, h, w = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
+        m = np.ascontiguousarray(transitions, dtype=np.float32)
+        if m.size != (n - 1) * 9:
+            raise ValueError(f"{who}: transitions {m.shape} are not [{n - 1},3,3] for {n} frames")
+        act = None
+        if active is not None:
+            act = np.ascontiguousarray(np.asarray(active) != 0, dtype=np.uint8)
+            if act.shape != (n - 1,):
+                raise ValueError(f"{who}: active of shape {act.shape} is not [{n - 1}]")
+        return n, h, w, m, act
+
+    def pair_gain_hist_batch(self, src, transitions, active=None):
+        """Deflicker, first pass (vstab_pair_gain_hist_batch; include/vstab.h states the rule): the histograms of the registered
+        level ratios of every consecutive pair.  src f32 [n,h,w,3] (device, contiguous, read only), transitions f32 [n-1,3,3] at
+        full resolution (x_{k+1} = A_k x_k), active [n-1] or None (a pair with 0 reads nothing and reports zeros)
+        -> (hist i32 [n-1,4,1024], stats i32 [n-1,2] = inside, well_exposed), device tensors."""
+        n, h, w, m, act = self._pair_gain_args("pair_gain_hist_batch", src, transitions, active)
+        torch = self.torch
+        hist = torch.empty((n - 1, 4, 1024), dtype=torch.int32, device=self.device)      # the library's u32, in torch's container
+        stats = torch.empty((n - 1, 2), dtype=torch.int32, device=self.device)
+        self.use_torch_stream()
+        _check(self.lib.vstab_pair_gain_hist_batch(self.handle, _dev_ptr(src), n, h, w, m.ctypes.data,
+                                                   act.ctypes.data if act is not None else None, _dev_ptr(hist), _dev_ptr(stats)),
+               "vstab_pair_gain_hist_batch")
+        return hist, stats
+
+    def pair_gain_sums_batch(self, src, transitions, band, active=None):
+        """Deflicker, second pass (vstab_pair_gain_sums_batch): count and level sums of the well-exposed lattice pixels whose
+        ratio bin lies in the pair's band.  src, transitions, active as above; band int [n-1,4,2], inclusive bins (lo > hi counts
+        nothing) -> sums i64 [n-1,4,3] = count, sum qa, sum qb, device tensor."""
+        n, h, w, m, act = self._pair_gain_args("pair_gain_sums_batch", src, transitions, active)
+        torch = self.torch
+        b = np.ascontiguousarray(band, dtype=np.int32)
+        if b.shape != (n - 1, 4, 2):
+            raise ValueError(f"pair_gain_sums_batch: band of shape {b.shape} is not [{n - 1},4,2]")
+        sums = torch.empty((n - 1, 4, 3), dtype=torch.int64, device=self.device)
+        self.use_torch_stream()
+        _check(self.lib.vstab_pair_gain_sums_batch(self.handle, _dev_ptr(src), n, h, w, m.ctypes.data,
+                                                   act.ctypes.data if act is not None else None, b.ctypes.data, _dev_ptr(sums)),
+               "vstab_pair_gain_sums_batch")
+        return sums
+
+    def apply_gain_batch(self, frames, gains, mask=None, want_count=True):
+        """Deflicker, the correction (vstab_apply_gain_batch; include/vstab.h states the rule): frames f32 [n,h,w,3] (device,
+        contiguous) are scaled IN PLACE by gains f32 [n,3], one float32 multiply per value; pixels with mask == 1.0f (mask f32
+        [n,h,w] or None: every pixel is own), channels with a gain of exactly 1 and NaNs are untouched; a value that the gain
+        would push above 1 is set to 1 and counted.  -> clamped i32 [n] (device) or None."""
+        torch = self.torch
+        for name, t in (("frames", frames), ("mask", mask)):
+            if t is None and name == "mask":
+                continue
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()):
+                raise ValueError(f"apply_gain_batch: {name} must be a contiguous float32 tensor on {self.device}")
+        if frames.dim() != 4 or frames.shape[3] != 3:
+            raise ValueError(f"apply_gain_batch: frames of shape {tuple(frames.shape)} are not [n,h,w,3]")
+        n, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+        if mask is not None and tuple(mask.shape) != (n, h, w):
+            raise ValueError(f"apply_gain_batch: mask of shape {tuple(mask.shape)} does not match the frames: expected {(n, h, w)}")
+        g = np.ascontiguousarray(gains, dtype=np.float32)
+        if g.shape != (n, 3):
+            raise ValueError(f"apply_gain_batch: gains of shape {g.shape} are not [{n},3]")
+        clamped = torch.empty((n,), dtype=torch.int32, device=self.device) if want_count else None
+        self.use_torch_stream()
+        _check(self.lib.vstab_apply_gain_batch(self.handle, _dev_ptr(frames), _dev_ptr(mask) if mask is not None else None, n, h, w,
+                                               g.ctypes.data, _dev_ptr(clamped) if clamped is not None else None),
+               "vstab_apply_gain_batch")
+        return clamped
 
     # ------------------------------------------------------------------ subject lock
     def mask_moments_batch(self, mask):

@@ -1145,6 +1145,100 @@ class VideoStabilizerMaskGrow(io.ComfyNode):
         return io.NodeOutput(_mask_out(out, 1))
 
 
+class VideoStabilizerDeflicker(io.ComfyNode):
+    """Takes the exposure steps between consecutive frames out of a stabilized clip (deflicker.py): measured on the ORIGINAL
+    frames through the stabilizer's own transitions, from the meta JSON alone, like the Temporal Fill node -- in front of which
+    it belongs, since a filled pixel is no longer marked as padding.  Without a meta the camera is taken to be locked off (a
+    tripod shot, a timelapse): identity transitions, and `frames_stabilized` may be `frames` itself.  Not one of the
+    reference's nodes: it is listed by VideoStabilizerAmdDeflickerExtension and kept out of NODE_CLASSES."""
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        schema = io.Schema(
+            node_id="video_stabilizer_deflicker",
+            display_name="Video Stabilizer Deflicker",
+            category="Video/Stabilization",
+            description=("Measures the exposure change between consecutive frames on registered pixels, robustly against moving "
+                         "subjects, and multiplies every frame by the high-pass of that chain; a deliberate exposure ramp stays."),
+        )
+        schema.inputs = [
+            io.Image.Input("frames", display_name="Frames", tooltip="The original (unstabilized) frames."),
+            io.Image.Input("frames_stabilized", display_name="Stabilized Frames",
+                           tooltip="The frames to correct; without a meta they may be the original frames themselves."),
+            io.Mask.Input("padding_mask", display_name="Padding Mask", optional=True,
+                          tooltip="The stabilizer's padding mask; padded pixels keep their colour.  Without it every pixel is own."),
+            JSONType.Input("meta", display_name="Motion Meta", optional=True,
+                           tooltip="A Flow / Classic stabilizer's meta.  Without it the camera is taken to be locked off."),
+            io.Float.Input("window", default=1.0, min=0.05, max=60.0, step=0.05, display_name="Window (s)",
+                           tooltip="The exposure chain is smoothed over this many seconds; what is faster is taken out."),
+            io.Combo.Input("mode", options=["exposure", "rgb"], default="exposure", display_name="Mode",
+                           tooltip="exposure: one gain for the three colours.  rgb: one per colour, which also steadies white balance."),
+        ]
+        schema.outputs = [
+            io.Image.Output("frames", display_name="Frames"),
+            io.String.Output("meta", display_name="Meta"),
+        ]
+        return schema
+
+    @classmethod
+    def execute(cls, frames: Any, frames_stabilized: Any, padding_mask: Any = None, meta: Any = None, window: float = 1.0,
+                mode: str = "exposure") -> io.NodeOutput:
+        import json
+
+        from . import deflicker, native, scene_cuts, temporal_fill
+        from .flow_pipeline import _fps_fields
+
+        # every check comes before any GPU work
+        request = deflicker.check_request(window, mode)
+        if request is None:
+            raise ValueError(f"deflicker: window={window!r} switches the node off; it needs a window in seconds in (0, 60]")
+        context = hm._normalize_video_input(frames)
+        out_context = context if frames_stabilized is frames else hm._normalize_video_input(frames_stabilized)
+        n = len(context.frames)
+        if n < 2 or len(out_context.frames) != n:
+            raise ValueError(f"deflicker: needs at least two frames and as many stabilized as original ones, got {n} original and "
+                             f"{len(out_context.frames)} stabilized frames")
+        segments = None
+        if meta is not None:
+            plan = temporal_fill.plan_from_meta(meta)   # ValueError naming the missing key
+            if len(plan["final_matrices"]) != n:
+                raise ValueError(f"deflicker: meta describes {len(plan['final_matrices'])} frames, got {n}")
+            if (context.width, context.height) != plan["source_size"] or (out_context.width, out_context.height) != plan["output_size"]:
+                raise ValueError(f"deflicker: frame sizes {(context.width, context.height)} -> "
+                                 f"{(out_context.width, out_context.height)} do not match the meta's "
+                                 f"{plan['source_size']} -> {plan['output_size']}")
+            transitions, confidences = plan["transitions"], plan["confidences"]
+            fps = meta.get("fps_effective")
+            if isinstance(meta.get("scene_cuts"), dict) and meta["scene_cuts"].get("cuts"):
+                segments = scene_cuts.segments_from_cuts(meta["scene_cuts"]["cuts"], n)
+        else:
+            transitions, confidences, fps = np.tile(np.eye(3, dtype=np.float32), (n - 1, 1, 1)), np.ones(n - 1), None
+        fps_effective = _fps_fields(context, fps)[0]
+        ctx = native.default_context()
+        torch = ctx.torch
+
+        def on_device(video):   # F0's value-range rule, as every node of the package applies it to its frames
+            batch = video.device_batch(ctx)
+            if video.range_pending and hm.resolve_value_range(video, hm.prefetch_peaks(ctx.frame_range(batch)), ctx):
+                batch = video.device_batch(ctx)
+            return batch
+
+        src = on_device(context)
+        # the correction works in place: on a copy, so the caller's tensor (another node's cached output) stays as it is
+        dst = (src if out_context is context else on_device(out_context)).clone()
+        mask = None
+        if padding_mask is not None:
+            mask = padding_mask if isinstance(padding_mask, torch.Tensor) else torch.from_numpy(np.asarray(padding_mask, dtype=np.float32))
+            mask = mask.to(device=ctx.device, dtype=torch.float32)
+            if mask.ndim == 4:
+                mask = mask[..., 0]
+            if tuple(mask.shape) != tuple(dst.shape[:3]):
+                raise ValueError(f"deflicker: padding_mask {tuple(mask.shape)} does not match the stabilized frames {tuple(dst.shape[:3])}")
+            mask = mask.contiguous()
+        block = deflicker.deflicker_on_device(ctx, request, src, dst, mask, transitions, confidences, fps_effective, segments)
+        return io.NodeOutput(_image_out(dst, out_context), json.dumps({"deflicker": block}))
+
+
 class VideoStabilizerAmdExtension(ComfyExtension):
     async def get_node_list(self) -> list:
         return list(NODE_CLASSES) + [VideoStabilizerTemporalFill]   # the six reference nodes + the temporal fill
@@ -1233,3 +1327,6 @@ VideoStabilizerAmdAnchorExposureExtension = _extend(
 VideoStabilizerAmdRollingRefitExtension = _extend(
     VideoStabilizerAmdAnchorExposureExtension, VideoStabilizerFlowRollingRefit, name="VideoStabilizerAmdRollingRefitExtension",
     doc="The exposure-matched extension's twenty-three nodes plus Video Stabilizer Flow (Rolling Shutter, Refit).")
+VideoStabilizerAmdDeflickerExtension = _extend(
+    VideoStabilizerAmdRollingRefitExtension, VideoStabilizerDeflicker, name="VideoStabilizerAmdDeflickerExtension",
+    doc="The refit extension's twenty-four nodes plus Video Stabilizer Deflicker.")

@@ -983,6 +983,66 @@ int vstab_mask_hold_batch(vstab_ctx* ctx, const float* mask, int n, int h, int w
 int vstab_mask_grow_batch(vstab_ctx* ctx, const float* mask, int n, int h, int w, int grow, int footprint, int feather,
                           float* out, uint32_t* count_out);
 
+/* ---- deflicker: registered exposure gains between consecutive frames, and their correction (beyond the reference, off by default) ----
+ * Auto exposure and auto white balance hunt while the camera shakes; once the picture stands still the brightness steps are
+ * what is left to see.  The transitions register consecutive frames, so frame k+1 can be compared with frame k pixel against
+ * the same scene point: what differs is exposure, not content.  Two measuring entries and one that applies per-frame gains;
+ * median, band, smoothing and the gains themselves are host arithmetic on the downloaded integers (deflicker.py).
+ *
+ * The measurement rule, for pair k (frames a = k, b = k + 1 of src) and its full-resolution transition A_k (float32 widened
+ * to fp64).  It uses integers only, so the result is the same in any order of summation:
+ *   - Lattice: the pixels p = (x, y) of frame a with x % S == S/2 && y % S == S/2, S = VSTAB_DEFLICKER_STRIDE.
+ *   - Mapping: vstab_pair_residual_batch's, literally (one device function serves both): X, Y, W in that association, W <= 0
+ *     or not finite excluded, q = (rint(X / W), rint(Y / W)) with ties to even.  p is INSIDE iff q lies in frame b
+ *     (0 <= qx <= w-1 and 0 <= qy <= h-1).  Nothing is interpolated: both values are stored pixels.
+ *   - Levels: qa_c = q(src[a, y, x, c]), qb_c = q(src[b, qy, qx, c]), q the blended fill's 16-bit quantiser
+ *     q(v) = v > 0 ? (v < 1 ? (uint32)(v * 65536.0f) : 65536) : 0 (a NaN gives 0).
+ *   - An inside pixel is WELL EXPOSED iff all six levels lie in [VSTAB_DEFLICKER_LO, VSTAB_DEFLICKER_HI]: clipped highlights
+ *     and crushed blacks break a gain model.
+ *   - Four ratio channels: 0..2 are r, g, b; channel 3 is the sum of the three levels in each frame (qa_3 = qa_0 + qa_1 + qa_2,
+ *     qb_3 likewise).  bin_c = min((qb_c * 256) / qa_c, 1023) in unsigned integer division: the ratio in units of 1/256.
+ *     qa_c >= 2048 and qb_3 * 256 <= 3 * 63488 * 256 < 2^26: everything fits 32 bits.
+ * vstab_pair_gain_hist_batch: hist[k, c, bin_c] += 1 for every well-exposed pixel and channel; stats[k] = {inside,
+ * well_exposed}.  vstab_pair_gain_sums_batch: sums[k, c] = {count, sum qa_c, sum qb_c} over the well-exposed pixels whose
+ * bin_c lies in band[k, c] = [lo, hi], both inclusive; lo > hi counts nothing.  The median of the histogram ignores a moving
+ * subject, a flash in part of the frame or a misregistered region while they own less than half of the samples; the second
+ * pass gives a fine estimate inside a band around that median.
+ *   src          dev  [n, h, w, 3] f32, read only (n >= 2)
+ *   transitions  host [n-1, 9] f32, full resolution, x_{k+1} = A_k x_k
+ *   active       host [n-1] u8 or NULL (all active): a pair with active == 0 reads nothing and reports zeros
+ *   hist         dev  [n-1, 4, 1024] u32;  stats dev [n-1, 2] u32;  sums dev [n-1, 4, 3] u64: zeroed by the call
+ *   band         host [n-1, 4, 2] i32
+ * h * w < 2^31.  A sum stays below 2^31 / 16 * 3 * 2^16 < 2^46.  Kernel (vstab_deflicker.hip): one body, two instantiations;
+ * a workgroup takes a share of one active pair's lattice, a lane a lattice pixel (a gather of 12 B at a 48-B pitch in frame
+ * a, 12 B wherever the transition points in frame b); the histogram is counted in LDS with integer atomics and its non-zero
+ * bins are flushed with global atomics, the sums go per thread -> wavefront shuffle -> LDS -> one 64-bit atomic per workgroup
+ * and number.  Asynchronous on the context's stream; timing kinds "gain_hist" and "gain_sums".
+ * The stride of 4 (1/16 of the pixels) and the level bounds 2048 / 63488 (1/32 from either end of the range) are
+ * choices, not calibrations; so are the band of 1/8, the minimum count of 256 and the clamp of the correction in deflicker.py.
+ *
+ * The apply rule, vstab_apply_gain_batch, per pixel of frame f and channel c with g = gains[f, c] and v the stored value:
+ *   - mask[f, y, x] == 1.0f: the pixel is untouched, so padding keeps its colour.  mask == NULL: every pixel is own.
+ *   - g == 1.0f exactly: the channel is untouched.  A frame whose three gains are all 1.0f is not read at all.
+ *   - v is a NaN: untouched (a NaN stays the NaN it was).
+ *   - otherwise out = v * g, one float32 multiply; if out > 1.0f && v <= 1.0f then out = 1.0f and the value counts in
+ *     clamped[f].  A value is never pushed out of range; one that already was out of range stays scaled.
+ *   frames  dev [n, h, w, 3] f32, in and out;  mask dev [n, h, w] f32 or NULL;  gains host [n, 3] f32
+ *   clamped dev [n] u32 or NULL, zeroed by the call.  n >= 1, h * w < 2^31.
+ * Kernel: shaped as frame_sse_kernel is.  A frame is read as the flat float array it is, a float4 per lane behind a scalar
+ * head of up to 3 floats where it does not start on a 16-byte boundary and a tail of up to 3; channel and pixel come from the
+ * flat index; only frames with a gain other than 1.0f get workgroups.  An in-place streaming pass of 24 B per pixel plus 4 B
+ * of mask, with ordinary (temporal) stores: the passes behind it read the frames again at once.  Timing kind "apply_gain". */
+#define VSTAB_DEFLICKER_STRIDE 4
+#define VSTAB_DEFLICKER_LO 2048
+#define VSTAB_DEFLICKER_HI 63488
+#define VSTAB_DEFLICKER_BINS 1024
+int vstab_pair_gain_hist_batch(vstab_ctx* ctx, const float* src, int n, int h, int w, const float* transitions,
+                               const uint8_t* active, uint32_t* hist, uint32_t* stats);
+int vstab_pair_gain_sums_batch(vstab_ctx* ctx, const float* src, int n, int h, int w, const float* transitions,
+                               const uint8_t* active, const int32_t* band, uint64_t* sums);
+int vstab_apply_gain_batch(vstab_ctx* ctx, float* frames, const float* mask, int n, int h, int w, const float* gains,
+                           uint32_t* clamped);
+
 /* ---- F6 / F9 host helper: element-wise libm over fp64 arrays (host pointers, no GPU involved) ----
  * nodes/stabilizer_utils.py:300-358 (_matrix_to_params / _params_to_matrix) call math.sqrt/atan2/log and
  * math.exp/cos/sin per frame; this runs the same libm functions over a whole clip in one call.
