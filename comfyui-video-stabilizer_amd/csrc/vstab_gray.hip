@@ -40,88 +40,91 @@ __device__ __forceinline__ int sat_u8_round(float v)
 // MI355X, profiles/r02_gray_forms.md: 256 x 1080p 1.09 -> 0.96 ms, 6.6 TB/s; 4K 0.82 -> 0.71 ms).  The launch picks a
 // workgroup size that divides the row into whole passes (640 threads for 1920 and 3840 columns).
 //
-// RANGE: the same pass also yields the largest sample of every source row it reads (NaN if the row holds one, as
-// numpy's max does) -- the value-range sniff of nodes/stabilizer_utils.py:127-131 (`float(arr.max()) > 1.5` per frame)
-// for free, instead of a second 24.9 MB read per frame.  Written per block to row_max[f * dh + y]; only valid when the
-// K x K boxes tile the whole source (the host checks dh * K == sh and dw * K == sw).
-template <int K, bool RANGE>
+// RANGE: the same pass also yields the largest sample of the source rows it reads (NaN if they hold one, as numpy's
+// max does) -- the value-range sniff of nodes/stabilizer_utils.py:127-131 (`float(arr.max()) > 1.5` per frame) --
+// instead of a second 24.9 MB read per frame.  Every wavefront writes its own partial to
+// row_max[((f * groups + g) * waves + wave)]: a DPP maximum (wave_max_lane63) and a ballot of the NaN flag, no LDS, no
+// barrier; frame_max_kernel reduces the groups * waves partials of a frame.  Only valid when the K x K boxes tile the
+// whole source (the host checks dh * K == sh and dw * K == sw).
+// G: consecutive output rows of one frame that a workgroup walks (the last group of a frame may be shorter); the
+// partial is then written once per G rows.
+// Measured on MI355X, 256 x 1080p (profiles/r28_range_tail.md): the probe is 19 VALU instructions per loop trip (97
+// against 78); stand-alone the sniff costs 0.03 ms (0.97-0.98 against 0.94 ms).  Inside the Flow step the RANGE pass with
+// G = 2 takes 1.00-1.08 ms, 40-70 us less than the earlier tail (two shuffle chains, LDS, a barrier and thread 0's loop
+// over the wavefronts, one row per workgroup); G = 2 is 16-50 us under G = 1 there and level with 4 and 6.  Without RANGE
+// two rows per workgroup are slower than one (0.97 against 0.94 ms), so that instantiation runs with G = 1.
+template <int K, bool RANGE, int G>
 __global__ __launch_bounds__(1024) void gray_area_int_kernel(const float* __restrict__ frames, uint8_t* __restrict__ out,
                                                              int n, int sh, int sw, int dh, int dw, int body,
                                                              float* __restrict__ row_max)
 {
-    __shared__ float s_max[16];
-    __shared__ int s_nan[16];
-    const int y = (int)blockIdx.x % dh, f = (int)blockIdx.x / dh;
-    const float* rowbase = frames + ((size_t)f * sh + (size_t)y * K) * sw * 3;
-    uint8_t* D = out + ((size_t)f * dh + y) * dw;
+    const int groups = (dh + G - 1) / G;
+    const int g = (int)blockIdx.x % groups, f = (int)blockIdx.x / groups;
+    const int y_end = (g * G + G < dh) ? g * G + G : dh;
     float vmax = -INFINITY;
     int has_nan = 0;
     const int used = dw * K;   // == sw on the fused path
     constexpr int U = 4 / K;   // columns per thread and pass: four 12-B loads in flight
     typedef float f3_t __attribute__((ext_vector_type(3), aligned(4)));
-    for (int sx0 = threadIdx.x; sx0 < used; sx0 += U * blockDim.x) {
-        f3_t px[U][K];
+    int y = g * G;
+    do {
+        const float* rowbase = frames + ((size_t)f * sh + (size_t)y * K) * sw * 3;
+        uint8_t* D = out + ((size_t)f * dh + y) * dw;
+        for (int sx0 = threadIdx.x; sx0 < used; sx0 += U * blockDim.x) {
+            f3_t px[U][K];
 #pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int sx = sx0 + u * blockDim.x;
-            if (sx < used) {
+            for (int u = 0; u < U; u++) {
+                const int sx = sx0 + u * blockDim.x;
+                if (sx < used) {
 #pragma unroll
-                for (int j = 0; j < K; j++)
-                    px[u][j] = __builtin_nontemporal_load(reinterpret_cast<const f3_t*>(rowbase + (size_t)j * sw * 3 + (size_t)sx * 3));
+                    for (int j = 0; j < K; j++)
+                        px[u][j] = __builtin_nontemporal_load(reinterpret_cast<const f3_t*>(rowbase + (size_t)j * sw * 3 + (size_t)sx * 3));
+                }
             }
-        }
 #pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int sx = sx0 + u * blockDim.x;
-            if (sx < used) {
-                const bool fused = sx < body;
-                int sum = 0;
+            for (int u = 0; u < U; u++) {
+                const int sx = sx0 + u * blockDim.x;
+                if (sx < used) {
+                    const bool fused = sx < body;
+                    int sum = 0;
 #pragma unroll
-                for (int j = 0; j < K; j++) {
-                    const float cr = px[u][j].x, cg = px[u][j].y, cb = px[u][j].z;
-                    sum += gray_u8(cr, cg, cb, fused);
-                    if (RANGE) {
-                        vmax = __builtin_fmaxf(vmax, __builtin_fmaxf(__builtin_fmaxf(cr, cg), cb));
-                        // per component: a sum probe would also fire on +inf next to -inf, where numpy's max is +inf.
-                        // (Round 5 tried the NaN-propagating v_maximum3_f32 and v_max3_f32 + a wavefront NaN mask through
-                        // inline asm -- 8 instead of ~70 VALU instructions per four pixels: both SLOWER, 1.27 vs 1.13 ms per
-                        // 256 x 1080p on one box; the asm statements keep the compiler from overlapping the next loads with
-                        // this arithmetic, which is what the pass lives on.  profiles/r05_dis_small_steps.md)
-                        has_nan |= ((cr != cr) | (cg != cg) | (cb != cb)) ? 1 : 0;
+                    for (int j = 0; j < K; j++) {
+                        const float cr = px[u][j].x, cg = px[u][j].y, cb = px[u][j].z;
+                        sum += gray_u8(cr, cg, cb, fused);
+                        if (RANGE) {
+                            vmax = __builtin_fmaxf(vmax, __builtin_fmaxf(__builtin_fmaxf(cr, cg), cb));
+                            // per component: a sum probe would also fire on +inf next to -inf, where numpy's max is +inf.
+                            // (Round 5 tried the NaN-propagating v_maximum3_f32 and v_max3_f32 + a wavefront NaN mask through
+                            // inline asm: both SLOWER, 1.27 vs 1.13 ms per 256 x 1080p on one box; the asm statements keep the
+                            // compiler from overlapping the next loads with this arithmetic, which is what the pass lives on.
+                            // profiles/r05_dis_small_steps.md)
+                            has_nan |= ((cr != cr) | (cg != cg) | (cb != cb)) ? 1 : 0;
+                        }
+                    }
+                    // the K lanes of a box sit in one quad (blockDim.x and `used` are multiples of K): integer adds, any order
+                    if (K >= 2) sum += __builtin_amdgcn_update_dpp(0, sum, 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
+                    if (K == 4) sum += __builtin_amdgcn_update_dpp(0, sum, 0x4E, 0xf, 0xf, false);   // quad_perm [2,3,0,1]
+                    if ((sx & (K - 1)) == 0) {
+                        int o;
+                        if (K == 1) o = sum;
+                        else if (K == 2) o = (sum + 2) >> 2;
+                        else o = sat_u8_round(sum * (1.f / (K * K)));
+                        D[sx / K] = (uint8_t)o;
                     }
                 }
-                // the K lanes of a box sit in one quad (blockDim.x and `used` are multiples of K): integer adds, any order
-                if (K >= 2) sum += __builtin_amdgcn_update_dpp(0, sum, 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
-                if (K == 4) sum += __builtin_amdgcn_update_dpp(0, sum, 0x4E, 0xf, 0xf, false);   // quad_perm [2,3,0,1]
-                if ((sx & (K - 1)) == 0) {
-                    int o;
-                    if (K == 1) o = sum;
-                    else if (K == 2) o = (sum + 2) >> 2;
-                    else o = sat_u8_round(sum * (1.f / (K * K)));
-                    D[sx / K] = (uint8_t)o;
-                }
             }
         }
-    }
+    } while (G > 1 && ++y < y_end);
     if (RANGE) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            vmax = __builtin_fmaxf(vmax, __shfl_down(vmax, off));
-            has_nan |= __shfl_down(has_nan, off);
-        }
-        const int nw = (blockDim.x + 63) >> 6;
-        if ((threadIdx.x & 63) == 0) { s_max[threadIdx.x >> 6] = vmax; s_nan[threadIdx.x >> 6] = has_nan; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            float m = s_max[0];
-            int nn = s_nan[0];
-            for (int k = 1; k < nw; k++) { m = __builtin_fmaxf(m, s_max[k]); nn |= s_nan[k]; }
-            row_max[(size_t)f * dh + y] = nn ? NAN : m;
-        }
+        // every lane of the wavefront is here (blockDim.x is a multiple of 64); lanes without a pixel hold -inf and 0
+        const float m = wave_max_lane63(vmax);
+        const bool any_nan = __ballot(has_nan) != 0;
+        const int waves = (int)blockDim.x >> 6, wave = (int)threadIdx.x >> 6;
+        if ((threadIdx.x & 63) == 63) row_max[((size_t)f * groups + g) * waves + wave] = any_nan ? NAN : m;
     }
 }
 
-// per-frame maximum of the per-row maxima (NaN wins, as in numpy): one workgroup per frame
+// per-frame maximum of the range passes' partial maxima, `rows` of them per frame (NaN wins, as in numpy): one workgroup per frame
 // host_max (optional): the maxima also go to coherent host memory -- by the LAST workgroup to finish (a device-scope count
 // finds it), as one coalesced store of all `gridDim.x` values followed by a release store of `target` into host_flag.  (One
 // store + one system-scope atomic per workgroup, the first form of this, serialised 256 PCIe round trips: 276 us.)
@@ -179,13 +182,12 @@ __global__ __launch_bounds__(256) void value_range_kernel(const float* __restric
     }
 }
 
-// per-row maximum of a clip without producing gray (Motion Apply has no estimation pass): one workgroup per source row
+// per-row maxima of a clip without producing gray (Motion Apply has no estimation pass): one workgroup of 4 wavefronts
+// per source row, one partial per wavefront in row_max[4 * row + wave]
 // VEC: pieces are a multiple of 4 floats and 16-B aligned (checked by the host); otherwise plain 4-B loads
 template <bool VEC>
 __global__ __launch_bounds__(256) void row_max_kernel(const float* __restrict__ frames, float* __restrict__ row_max, int row_floats)
 {
-    __shared__ float s_max[4];
-    __shared__ int s_nan[4];
     const float* S = frames + (size_t)blockIdx.x * row_floats;
     float vmax = -INFINITY;
     int has_nan = 0;
@@ -206,17 +208,10 @@ __global__ __launch_bounds__(256) void row_max_kernel(const float* __restrict__ 
             has_nan |= (v != v) ? 1 : 0;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        vmax = __builtin_fmaxf(vmax, __shfl_down(vmax, off));
-        has_nan |= __shfl_down(has_nan, off);
-    }
-    if ((threadIdx.x & 63) == 0) { s_max[threadIdx.x >> 6] = vmax; s_nan[threadIdx.x >> 6] = has_nan; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float m = __builtin_fmaxf(__builtin_fmaxf(s_max[0], s_max[1]), __builtin_fmaxf(s_max[2], s_max[3]));
-        row_max[blockIdx.x] = (s_nan[0] | s_nan[1] | s_nan[2] | s_nan[3]) ? NAN : m;
-    }
+    // one partial per wavefront, as in gray_area_int_kernel: no LDS, no barrier
+    const float m = wave_max_lane63(vmax);
+    const bool any_nan = __ballot(has_nan) != 0;
+    if ((threadIdx.x & 63) == 63) row_max[(size_t)blockIdx.x * 4 + (threadIdx.x >> 6)] = any_nan ? NAN : m;
 }
 
 // Generic integer ratio (kx, ky) on an already-gray image.
@@ -316,7 +311,7 @@ static int gray_run(vstab_ctx* ctx, const float* frames, int n, int src_h, int s
     const int body = src_w & ~7;
     KernelTimer timer(ctx, "gray");
     float* row_max = nullptr;
-    int range_rows = 0;   // rows of row_max per frame once the gray pass has filled it
+    int range_rows = 0;   // entries of row_max per frame once the gray pass has filled it
 
     // workgroup size: the multiple of 64 (<= 1024) that covers a row of `cols` columns in whole passes with the fewest
     // idle lane slots; ties go to the size nearest 640 (measured best for 1920 / 3840 columns)
@@ -327,18 +322,19 @@ static int gray_run(vstab_ctx* ctx, const float* frames, int n, int src_h, int s
             const long long cost = (long long)((cols + t - 1) / t) * t;
             if (best_cost < 0 || cost < best_cost || (cost == best_cost && std::abs(t - 640) < std::abs(best - 640))) { best = t; best_cost = cost; }
         }
-        if (const char* e = getenv("VSTAB_GRAY_THREADS")) best = atoi(e);   // A/B measurement (tools/gray_forms.py)
+        // A/B measurement (tools/gray_forms.py); whole wavefronts, as the kernel's quads and its per-wavefront partials need
+        if (const char* e = getenv("VSTAB_GRAY_THREADS")) best = std::min(1024, std::max(64, (atoi(e) + 63) / 64 * 64));
         return best;
     };
+    // output rows per workgroup: the RANGE pass walks two (measured against 1, 4 and 6 at 256 x 1080p, see the kernel)
+    constexpr int RANGE_ROWS = 2, PLAIN_ROWS = 1;
+#define LAUNCH_GRAY_G(K, RANGE, G, ROWS, OUT)                                                                             \
+    hipLaunchKernelGGL((gray_area_int_kernel<K, RANGE, G>), dim3((unsigned)(n * (((ROWS) + G - 1) / G))), dim3(threads), 0, st, frames, OUT, \
+                       n, src_h, src_w, (ROWS), src_w / K, body, row_max)
 #define LAUNCH_GRAY(K, ROWS, OUT)                                                                                         \
     do {                                                                                                                  \
-        const int threads = threads_for(src_w / K * K);                                                                   \
-        if (row_max)                                                                                                      \
-            hipLaunchKernelGGL((gray_area_int_kernel<K, true>), dim3((unsigned)(n * (ROWS))), dim3(threads), 0, st, frames, OUT, n, src_h, \
-                               src_w, (ROWS), src_w / K, body, row_max);                                                  \
-        else                                                                                                              \
-            hipLaunchKernelGGL((gray_area_int_kernel<K, false>), dim3((unsigned)(n * (ROWS))), dim3(threads), 0, st, frames, OUT, n, src_h, \
-                               src_w, (ROWS), src_w / K, body, row_max);                                                  \
+        if (row_max) LAUNCH_GRAY_G(K, true, RANGE_ROWS, ROWS, OUT);                                                       \
+        else LAUNCH_GRAY_G(K, false, PLAIN_ROWS, ROWS, OUT);                                                              \
         VSTAB_HIP(hipGetLastError());                                                                                     \
     } while (0)
 
@@ -349,12 +345,15 @@ static int gray_run(vstab_ctx* ctx, const float* frames, int n, int src_h, int s
     const bool fast = !same && std::fabs(scale_x - isx) < DBL_EPSILON && std::fabs(scale_y - isy) < DBL_EPSILON;
     const bool fused = fast && isx == isy && (isx == 2 || isx == 4);
     const int K = same ? 1 : (fused ? isx : 1);
+    const int threads = threads_for(src_w / K * K);   // the one launch of gray_area_int_kernel below, whichever it is
     if (frame_max) {
-        // the gray pass covers every source sample exactly when its K x K boxes tile the source
+        // the gray pass covers every source sample exactly when its K x K boxes tile the source; every wavefront of
+        // every row group leaves one partial
         const int rows = (same || !fused) ? src_h : work_h;
-        if (ctx->d_range.reserve(sizeof(float) * (size_t)n * rows)) return 1;
+        const int partials = (rows + RANGE_ROWS - 1) / RANGE_ROWS * (threads / 64);
+        if (ctx->d_range.reserve(sizeof(float) * (size_t)n * partials)) return 1;
         row_max = static_cast<float*>(ctx->d_range.ptr);
-        range_rows = rows;
+        range_rows = partials;
     }
     if (same) {
         LAUNCH_GRAY(1, work_h, gray);
@@ -395,6 +394,7 @@ static int gray_run(vstab_ctx* ctx, const float* frames, int n, int src_h, int s
         }
     }
 #undef LAUNCH_GRAY
+#undef LAUNCH_GRAY_G
     if (frame_max) {
         // the host's copy of the maxima: written by the kernel itself into coherent host memory (no copy, no event on the stream)
         if (ctx->peaks.reserve(sizeof(float) * (size_t)std::max(1024, n), st)) return 1;
@@ -469,13 +469,13 @@ extern "C" int vstab_frame_range(vstab_ctx* ctx, const float* frames, int n, int
     for (long long cand : {(long long)w * 3, (long long)w * 3 * 2, (long long)w * 3 * 4})
         if (cand % 4 == 0 && per_frame % cand == 0 && (reinterpret_cast<uintptr_t>(frames) % 16) == 0) { piece = cand; vec = true; break; }
     const long long pieces = per_frame / piece;
-    VSTAB_REQUIRE((long long)n * pieces < 0x7fffffffLL && piece < 0x7fffffffLL, "vstab_frame_range: clip too large");
-    if (ctx->d_range.reserve(sizeof(float) * (size_t)n * pieces)) return 1;
+    VSTAB_REQUIRE((long long)n * pieces < 0x7fffffffLL && pieces * 4 < 0x7fffffffLL && piece < 0x7fffffffLL, "vstab_frame_range: clip too large");
+    if (ctx->d_range.reserve(sizeof(float) * (size_t)n * pieces * 4)) return 1;   // row_max_kernel: 4 wavefronts per piece
     float* row_max = static_cast<float*>(ctx->d_range.ptr);
     KernelTimer timer(ctx, "range");
     if (vec) hipLaunchKernelGGL(row_max_kernel<true>, dim3((unsigned)(n * pieces)), dim3(256), 0, st, frames, row_max, (int)piece);
     else hipLaunchKernelGGL(row_max_kernel<false>, dim3((unsigned)(n * pieces)), dim3(256), 0, st, frames, row_max, (int)piece);
-    hipLaunchKernelGGL(frame_max_kernel, dim3((unsigned)n), dim3(256), 0, st, row_max, frame_max, (int)pieces, (float*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr, 0u);
+    hipLaunchKernelGGL(frame_max_kernel, dim3((unsigned)n), dim3(256), 0, st, row_max, frame_max, (int)(pieces * 4), (float*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr, 0u);
     VSTAB_HIP(hipGetLastError());
     return 0;
 }

@@ -311,6 +311,25 @@ __device__ __forceinline__ bool vstab_nn_covered(double qx, double qy, int sh, i
     return (unsigned)nx < (unsigned)sw && (unsigned)ny < (unsigned)sh;
 }
 
+// The maximum of v over the 64 lanes of a wavefront, valid in lane 63: a DPP scan inside each row of 16 lanes (row_shr
+// 1/2/4/8), then lane 15 of rows 0 and 2 into rows 1 and 3 (row_bcast:15), then lane 31 into rows 2 and 3 (row_bcast:31).
+// `old` is the lane's own value and bound_ctrl is off, so a lane without a source lane keeps what it has.  No LDS traffic
+// and no wait on it; float max is order-independent as long as the caller keeps NaN out of the result (the range passes
+// carry a NaN flag of their own).  Every lane of the wavefront must reach the call.
+__device__ __forceinline__ float wave_max_lane63(float v)
+{
+#define VSTAB_DPP_MAX(CTRL, ROW_MASK)                                                                                             \
+    v = __builtin_fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), (CTRL), (ROW_MASK), 0xf, false)))
+    VSTAB_DPP_MAX(0x111, 0xf);   // row_shr:1
+    VSTAB_DPP_MAX(0x112, 0xf);   // row_shr:2
+    VSTAB_DPP_MAX(0x114, 0xf);   // row_shr:4
+    VSTAB_DPP_MAX(0x118, 0xf);   // row_shr:8
+    VSTAB_DPP_MAX(0x142, 0xa);   // row_bcast:15 into rows 1 and 3
+    VSTAB_DPP_MAX(0x143, 0xc);   // row_bcast:31 into rows 2 and 3
+#undef VSTAB_DPP_MAX
+    return v;
+}
+
 // ---- the residual of the global fit at a grid sample and the median of a workgroup's residuals: the per-vertex form
 // (vstab_mesh.hip) and the per-row form (vstab_rolling.hip) ----
 __device__ __forceinline__ bool finite_f(float v) { return __builtin_fabsf(v) <= 3.4028234663852886e38f; }   // false for NaN
@@ -808,6 +827,8 @@ __global__ __launch_bounds__(256) void warp_kernel(Args a)
             block_count_add<2>(counts, {WITH_MASK ? a.pad_count : nullptr, a.unconverged}, frame);
         }
     } else {
+        // (the count is within the spread of repeated launches of the plain warp at 256 x 1080p, and so is a per-wavefront
+        // ballot form of it: tools/warp_count_cost.py, profiles/r28_range_tail.md)
         if (WITH_MASK && a.pad_count != nullptr) block_count_add<1>(padded, {a.pad_count}, frame);
     }
 }
