@@ -7,9 +7,9 @@
 // gradient; the two pixels beside the piece come as byte loads), maps each through the frame's matrix in fp64 (the rule's
 // association, nothing fused: -ffp-contract=off), rounds to Q5 half-to-even and reads the four taps of the frame's image
 // with byte loads.  A shake-sized matrix keeps those taps within a few rows of the pixel, so template and image cross HBM
-// about once: ~2 * h * w bytes per frame.  Everything that is summed is an integer, so lane order, wave order and the order
-// of the atomics do not show in the result: 17 lane sums (i64) -> wave reduction by shuffles -> LDS -> one 64-bit atomic
-// per workgroup and slot, only where the workgroup counted or capped a pixel.
+// about once: ~2 * h * w bytes per frame.  Everything that is summed is an integer: 17 lane sums (i64) -> BlockSums
+// (vstab_internal.h) -> thread k finishes slot k with one 64-bit atomic per workgroup, only where the workgroup counted or
+// capped a pixel.
 //
 // Bounds (max(h, w) <= 1024, required by the entry point): |gx|, |gy| <= 255; |u|, |q| <= 1023; so |J2|, |J3| <=
 // 2 * 255 * 1023 = 521730 < 2^19 (int32), |r| <= 261120 < 2^18, a product J_j J_k < 2^38 and J_k r < 2^37 (formed in 64
@@ -26,7 +26,6 @@ namespace {
 
 constexpr int ANCHOR_ROWS = 16;     // template rows per workgroup (960x540: 34 workgroups per frame)
 constexpr int ANCHOR_THREADS = 256;
-constexpr int ANCHOR_WAVES = ANCHOR_THREADS / 64;
 constexpr int ANCHOR_SLOTS = VSTAB_ANCHOR_SLOTS;
 constexpr int ANCHOR_EX_SLOTS = VSTAB_ANCHOR_EX_SLOTS;
 
@@ -145,12 +144,6 @@ __device__ __forceinline__ int byte_of(const uint4& v, int k)
     return (int)((word >> ((k & 3) * 8)) & 0xffu);
 }
 
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 // A workgroup's template pixels: `rows` rows from y_first, in 16-pixel pieces, one piece per lane and step.
 // pixel(x, y, t, l, r, up, dn) gets every pixel with 1 <= x <= w-2 and its four neighbours.
 // VEC: w % 16 == 0 and the base 16-byte aligned (every row of every frame then is)
@@ -188,7 +181,7 @@ __global__ __launch_bounds__(ANCHOR_THREADS) void anchor_sums_kernel(const uint8
                                                                       const int* __restrict__ anchors, int h, int w, int tiles,
                                                                       int cap1024, long long* __restrict__ out)
 {
-    __shared__ long long s_part[ANCHOR_WAVES][ANCHOR_SLOTS];
+    __shared__ BlockSums<long long, ANCHOR_SLOTS, ANCHOR_THREADS> s_sums;
     const int frame = (int)blockIdx.x / tiles, tile = (int)blockIdx.x - frame * tiles;
     const int anchor = anchors[frame];
     if (anchor < 0) return;                             // the whole workgroup: no barrier has been reached
@@ -201,23 +194,12 @@ __global__ __launch_bounds__(ANCHOR_THREADS) void anchor_sums_kernel(const uint8
     anchor_walk<VEC>(tmpl, y_first, rows, w, [&](int x, int y, int t, int l, int r, int up, int dn) {
         anchor_pixel(acc, R, img, x, y, h, w, cap1024, t, l, r, up, dn);
     });
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int slot = 0;
-    auto put = [&](long long lane_sum) {                // the slots in the order of the rule's step 10
-        const long long total = wave_sum(lane_sum);
-        if (lane == 0) s_part[wave][slot] = total;
-        slot += 1;
-    };
-    put(acc.count), put(acc.capped), put(acc.sum_abs);
-    put(acc.b0), put(acc.b1), put(acc.b2), put(acc.b3);
-    put(acc.h00), put(acc.h01), put(acc.h02), put(acc.h03), put(acc.h11), put(acc.h12), put(acc.h13), put(acc.h22), put(acc.h23), put(acc.h33);
+    s_sums.put({acc.count, acc.capped, acc.sum_abs,      // the slots in the order of the rule's step 10
+                acc.b0, acc.b1, acc.b2, acc.b3,
+                acc.h00, acc.h01, acc.h02, acc.h03, acc.h11, acc.h12, acc.h13, acc.h22, acc.h23, acc.h33});
     __syncthreads();
     if (threadIdx.x < ANCHOR_SLOTS) {
-        long long touched = 0, total = 0;
-        for (int k = 0; k < ANCHOR_WAVES; k++) {
-            touched += s_part[k][0] + s_part[k][1];
-            total += s_part[k][threadIdx.x];
-        }
+        const long long touched = s_sums.total(0) + s_sums.total(1), total = s_sums.total(threadIdx.x);
         if (touched) atomicAdd(reinterpret_cast<unsigned long long*>(out + (size_t)frame * ANCHOR_SLOTS + threadIdx.x), (unsigned long long)total);
     }
 }
@@ -230,7 +212,7 @@ __global__ __launch_bounds__(ANCHOR_THREADS) void anchor_sums_ex_kernel(const ui
                                                                          int cap1024, const uint8_t* __restrict__ blocked, int step,
                                                                          int gh, int gw, long long* __restrict__ out)
 {
-    __shared__ long long s_part[ANCHOR_WAVES][ANCHOR_EX_SLOTS];
+    __shared__ BlockSums<long long, ANCHOR_EX_SLOTS, ANCHOR_THREADS> s_sums;
     const int frame = (int)blockIdx.x / tiles, tile = (int)blockIdx.x - frame * tiles;
     const int anchor = params[frame];
     if (anchor < 0) return;                             // the whole workgroup: no barrier has been reached
@@ -245,25 +227,15 @@ __global__ __launch_bounds__(ANCHOR_THREADS) void anchor_sums_ex_kernel(const ui
     anchor_walk<VEC>(tmpl, y_first, rows, w, [&](int x, int y, int t, int l, int r, int up, int dn) {
         anchor_pixel_ex<MASK>(acc, R, f, img, x, y, h, w, cap1024, t, l, r, up, dn);
     });
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int slot = 0;
-    auto put = [&](long long lane_sum) {                // the slots in the order of the rule's output
-        const long long total = wave_sum(lane_sum);
-        if (lane == 0) s_part[wave][slot] = total;
-        slot += 1;
-    };
-    put(acc.count), put(acc.capped), put(acc.masked), put(acc.sum_abs);
+    long long v[ANCHOR_EX_SLOTS] = {acc.count, acc.capped, acc.masked, acc.sum_abs};   // the slots in the order of the rule's output
 #pragma unroll
-    for (int k = 0; k < 6; k++) put(acc.b[k]);
+    for (int k = 0; k < 6; k++) v[4 + k] = acc.b[k];
 #pragma unroll
-    for (int k = 0; k < 21; k++) put(acc.hh[k]);
+    for (int k = 0; k < 21; k++) v[10 + k] = acc.hh[k];
+    s_sums.put(v);
     __syncthreads();
     if (threadIdx.x < ANCHOR_EX_SLOTS) {
-        long long touched = 0, total = 0;
-        for (int k = 0; k < ANCHOR_WAVES; k++) {
-            touched += s_part[k][0] + s_part[k][1] + s_part[k][2];
-            total += s_part[k][threadIdx.x];
-        }
+        const long long touched = s_sums.total(0) + s_sums.total(1) + s_sums.total(2), total = s_sums.total(threadIdx.x);
         if (touched) atomicAdd(reinterpret_cast<unsigned long long*>(out + (size_t)frame * ANCHOR_EX_SLOTS + threadIdx.x), (unsigned long long)total);
     }
 }

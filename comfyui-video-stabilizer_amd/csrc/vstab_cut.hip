@@ -5,15 +5,14 @@
 // 16-byte load, maps each through the pair's transition (fp64 from the float32 matrix, the rule's association), rounds
 // half-to-even and looks the TO image up there with a byte load.  A shake-sized transition keeps those lookups within a
 // few rows of the pixel, so both images of a pair cross HBM about once: ~2 * h * w bytes per pair.  Everything that is
-// summed is an integer (|a - b| <= 255, counts), so lane order, wave order and the order of the atomics do not show in
-// the result: lane sums (u32) -> wave reduction by shuffles -> LDS -> one atomic per workgroup and array.
+// summed is an integer (|a - b| <= 255, counts): lane sums (u32) -> BlockSums (vstab_internal.h), totalled in 64 bits ->
+// one atomic per workgroup and array, skipped where the workgroup counted nothing.
 #include "vstab_internal.h"
 
 namespace {
 
 constexpr int CUT_ROWS = 16;      // rows of a pair per workgroup (960x540: 34 workgroups per pair, 3.75 loads per lane)
 constexpr int CUT_THREADS = 256;
-constexpr int CUT_WAVES = CUT_THREADS / 64;
 
 // (the mapping of one pixel, vstab_pair_lookup, is in vstab_internal.h: the deflicker measures through the same one)
 
@@ -23,7 +22,7 @@ __global__ __launch_bounds__(CUT_THREADS) void pair_residual_kernel(const uint8_
                                                                     int h, int w, int tiles, unsigned long long* __restrict__ sum_abs,
                                                                     unsigned* __restrict__ inside)
 {
-    __shared__ unsigned s_sum[CUT_WAVES], s_in[CUT_WAVES];
+    __shared__ BlockSums<unsigned, 2, CUT_THREADS> s_sums;      // |a - b|, inside
     const int pair = (int)blockIdx.x / tiles, tile = (int)blockIdx.x - pair * tiles;
     const int y0 = tile * CUT_ROWS, rows = min(CUT_ROWS, h - y0);
     PairMatrix A;
@@ -59,25 +58,12 @@ __global__ __launch_bounds__(CUT_THREADS) void pair_residual_kernel(const uint8_
             }
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        acc += __shfl_down(acc, off, 64);
-        cnt += __shfl_down(cnt, off, 64);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        s_sum[wave] = acc;
-        s_in[wave] = cnt;
-    }
+    s_sums.put({acc, cnt});
     __syncthreads();
     if (threadIdx.x == 0) {
-        unsigned long long total = 0;
-        unsigned count = 0;
-        for (int k = 0; k < CUT_WAVES; k++) {
-            total += s_sum[k];
-            count += s_in[k];
-        }
+        const unsigned count = s_sums.total(1);
         if (count) {
-            atomicAdd(&sum_abs[pair], total);
+            atomicAdd(&sum_abs[pair], s_sums.total<unsigned long long>(0));
             atomicAdd(&inside[pair], count);
         }
     }

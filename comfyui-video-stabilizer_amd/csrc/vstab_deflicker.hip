@@ -3,8 +3,8 @@
 // (vstab_apply_gain_batch).  Not a reference feature; both rules are stated in include/vstab.h.
 //
 //   pair_gain_kernel<false>  the ratio histograms: counted in LDS with integer atomics (16 KiB per workgroup), the non-zero
-//                            bins flushed with global atomics; inside / well-exposed counts per thread -> wave -> one atomic
-//   pair_gain_kernel<true>   the banded sums: per thread -> wave shuffle -> LDS -> one 64-bit atomic per workgroup and number
+//                            bins flushed with global atomics; inside / well-exposed counts through BlockSums (vstab_internal.h)
+//   pair_gain_kernel<true>   the banded sums: BlockSums, thread k finishes number k with one 64-bit atomic per workgroup
 //   apply_gain_kernel        shaped as frame_sse_kernel: the frame as a flat float array, float4 per lane behind a scalar
 //                            head, a scalar tail; channel and pixel from the flat index
 // One body serves both measurements, so that lattice, mapping, levels and bins cannot differ between the two passes.  A lane
@@ -16,7 +16,6 @@
 namespace {
 
 constexpr int DF_THREADS = 256;
-constexpr int DF_WAVES = DF_THREADS / 64;
 constexpr int DF_S = VSTAB_DEFLICKER_STRIDE;
 constexpr int DF_BINS = VSTAB_DEFLICKER_BINS;
 constexpr unsigned DF_LO = VSTAB_DEFLICKER_LO, DF_HI = VSTAB_DEFLICKER_HI;
@@ -41,8 +40,6 @@ __global__ __launch_bounds__(DF_THREADS) void pair_gain_kernel(const float* __re
                                                                unsigned* __restrict__ stats, unsigned long long* __restrict__ sums)
 {
     __shared__ unsigned s_hist[SUMS ? 1 : 4 * DF_BINS];
-    __shared__ unsigned long long s_sum[SUMS ? DF_WAVES * 12 : 1];
-    __shared__ unsigned s_stat[DF_WAVES * 2];
     const unsigned t = threadIdx.x;
     const unsigned slot_pair = blockIdx.x / blocks_per_pair, slot = blockIdx.x - slot_pair * blocks_per_pair;
     const DfPair& rec = recs[slot_pair];
@@ -96,8 +93,8 @@ __global__ __launch_bounds__(DF_THREADS) void pair_gain_kernel(const float* __re
         }
     }
 
-    const unsigned lane = t & 63u, wave = t >> 6;
     if (SUMS) {
+        __shared__ BlockSums<unsigned long long, 12, DF_THREADS> s_sum;
         unsigned long long v[12];
 #pragma unroll
         for (int c = 0; c < 4; c++) {
@@ -105,30 +102,18 @@ __global__ __launch_bounds__(DF_THREADS) void pair_gain_kernel(const float* __re
             v[3 * c + 1] = sa[c];
             v[3 * c + 2] = sb[c];
         }
-#pragma unroll
-        for (int k = 0; k < 12; k++) {
-            for (int s = 32; s > 0; s >>= 1) v[k] += __shfl_down(v[k], s, 64);
-            if (lane == 0) s_sum[wave * 12 + k] = v[k];
-        }
+        s_sum.put(v);
         __syncthreads();
         if (t < 12) {
-            unsigned long long total = 0ull;
-            for (int k = 0; k < DF_WAVES; k++) total += s_sum[k * 12 + t];
+            const unsigned long long total = s_sum.total(t);
             if (total) atomicAdd(&sums[(size_t)pair * 12 + t], total);      // (a zero count comes with zero sums)
         }
     } else {
-        for (int s = 32; s > 0; s >>= 1) {
-            inside += __shfl_down(inside, s, 64);
-            well += __shfl_down(well, s, 64);
-        }
-        if (lane == 0) {
-            s_stat[wave * 2] = inside;
-            s_stat[wave * 2 + 1] = well;
-        }
+        __shared__ BlockSums<unsigned, 2, DF_THREADS> s_stat;
+        s_stat.put({inside, well});
         __syncthreads();      // also: every lane's LDS atomics are done
         if (t < 2) {
-            unsigned total = 0u;
-            for (int k = 0; k < DF_WAVES; k++) total += s_stat[k * 2 + t];
+            const unsigned total = s_stat.total(t);
             if (total) atomicAdd(&stats[(size_t)pair * 2 + t], total);
         }
         unsigned* __restrict__ out = hist + (size_t)pair * 4 * DF_BINS;
@@ -171,7 +156,7 @@ __global__ __launch_bounds__(DF_THREADS) void apply_gain_kernel(float* __restric
                                                                 const AgFrame* __restrict__ recs, unsigned px, unsigned blocks_per_frame,
                                                                 unsigned* __restrict__ clamped_out)
 {
-    __shared__ unsigned s_cl[DF_WAVES];
+    __shared__ BlockSums<unsigned, 1, DF_THREADS> s_cl;
     const unsigned t = threadIdx.x;
     const unsigned slot_frame = blockIdx.x / blocks_per_frame, slot = blockIdx.x - slot_frame * blocks_per_frame;
     const AgFrame rec = recs[slot_frame];
@@ -225,12 +210,10 @@ __global__ __launch_bounds__(DF_THREADS) void apply_gain_kernel(float* __restric
     }
 
     if (clamped_out == nullptr) return;
-    for (int s = 32; s > 0; s >>= 1) clamped += __shfl_down(clamped, s, 64);
-    if ((t & 63u) == 0u) s_cl[t >> 6] = clamped;
+    s_cl.put({clamped});
     __syncthreads();
     if (t == 0) {
-        unsigned total = 0u;
-        for (int k = 0; k < DF_WAVES; k++) total += s_cl[k];
+        const unsigned total = s_cl.total(0);
         if (total) atomicAdd(&clamped_out[rec.frame], total);
     }
 }

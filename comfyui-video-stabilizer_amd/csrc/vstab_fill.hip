@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void sfill_pull0_kernel(const float* __restric
 {
     __shared__ float4 l1[SFILL_TILE_H / 2][SFILL_TILE_W / 2];
     __shared__ float4 l2[SFILL_TILE_H / 4][SFILL_TILE_W / 4];
-    __shared__ unsigned wave_holes[4];
+    __shared__ BlockSums<unsigned, 1, 256> s_holes;
     const int t = threadIdx.x, f = blockIdx.z;
     const int h = p.h[0], w = p.w[0];
     const size_t px = (size_t)h * w;
@@ -100,12 +100,11 @@ __global__ __launch_bounds__(256) void sfill_pull0_kernel(const float* __restric
         }
         l1[ly][lx] = c;   // cells outside the level are invalid taps of the level above
     }
-    // holes of the tile: wave shuffle, LDS, one atomic per workgroup
-    for (int s = 32; s > 0; s >>= 1) holes += __shfl_down(holes, s, 64);
-    if ((t & 63) == 0) wave_holes[t >> 6] = holes;
+    // holes of the tile: BlockSums (vstab_internal.h), one atomic per workgroup
+    s_holes.put({holes});
     __syncthreads();
     if (t == 0) {
-        const unsigned total = wave_holes[0] + wave_holes[1] + wave_holes[2] + wave_holes[3];
+        const unsigned total = s_holes.total(0);
         if (total) atomicAdd(&holes_out[f], total);
     }
     if (t < 128) {

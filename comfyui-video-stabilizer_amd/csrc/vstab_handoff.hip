@@ -27,7 +27,6 @@
 // `out` and the context's grow-only workspace (d_sfill, which the spatial fill uses inside its own calls only; calls on one
 // context are ordered on its stream), a chunk of frames at a time, at most 1 GiB, the last pass landing in `out`.
 // Between two feather passes the levels travel as float Q / 65536, whose quantisation gives Q back exactly.
-#define VSTAB_WARP_ARITHMETIC   // for block_count_add, which lives with the warp's tile shell
 #include "vstab_internal.h"
 
 #include <algorithm>

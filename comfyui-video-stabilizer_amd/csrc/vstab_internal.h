@@ -330,6 +330,78 @@ __device__ __forceinline__ float wave_max_lane63(float v)
     return v;
 }
 
+// ---- the block-level integer sum: THE tail of every pass that ends in exact integer sums ----
+// Integer addition is associative, so neither the order of lanes and waves nor the order of the atomics behind it shows in
+// a result.  The mechanism (shuffles, then LDS) is stated here and nowhere else.
+
+// NC sums of type T (unsigned, unsigned long long, long long) over an NT-thread workgroup.  The kernel declares one
+// `__shared__`; every thread calls put() with its own NC values (each wave's sums go to LDS); behind the kernel's own
+// __syncthreads() any thread reads total(c), slot c over the waves, accumulated in U.  Which thread finishes which slot, the
+// gate and the atomics stay with the kernel.  part[wave][slot]: threads that finish consecutive slots read consecutive
+// words.  An object is used once per kernel execution (a second put() would need a barrier in front of it).
+template <class T, int NC, int NT>
+struct BlockSums {
+    static_assert(NT % 64 == 0, "whole wavefronts");
+    T part[NT / 64][NC];
+    // The wave's sum of a slot is a __shfl_down chain 32 .. 1, valid in lane 0.  The chain stands in this loop and not in a
+    // function of its own: behind a `wave_sum(T)` the compiler allocates the plain warp's registers differently all through
+    // the kernel (profiles/r29_block_sums.md); written here, the benchmark's kernel is the same instruction sequence as before.
+    __device__ __forceinline__ void put(const T (&v)[NC])
+    {
+        if constexpr (NC >= 2 && NC <= 4) {
+            // a few slots: their chains side by side, so that one slot's shuffle latency hides another's (one after the other
+            // cost the temporal fill 1 %, profiles/r29_block_sums.md)
+            T s[NC];
+#pragma unroll
+            for (int c = 0; c < NC; c++) s[c] = v[c];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+                for (int c = 0; c < NC; c++) s[c] += __shfl_down(s[c], off);
+            }
+            if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+                for (int c = 0; c < NC; c++) part[threadIdx.x >> 6][c] = s[c];
+            }
+        } else {
+            // many slots: one after the other, a slot's registers are free once it is stored (side by side, the 17 / 31
+            // 64-bit slots of the anchor sums cost a wave per SIMD)
+#pragma unroll
+            for (int c = 0; c < NC; c++) {
+                T s = v[c];
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
+                if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][c] = s;
+            }
+        }
+    }
+    template <class U = T>
+    __device__ __forceinline__ U total(int c) const
+    {
+        U s = part[0][c];
+#pragma unroll
+        for (int k = 1; k < NT / 64; k++) s += part[k][c];
+        return s;
+    }
+};
+
+// Per-thread counts of an NT-thread block -> one atomic per counter and block, only if non-zero and asked for
+// (out[c] != nullptr); out[c] is a per-frame array.  All threads of the block call it (barrier).
+template <int NC, int NT = 256>
+__device__ __forceinline__ void block_count_add(const unsigned (&v)[NC], unsigned* const (&out)[NC], int frame)
+{
+    __shared__ BlockSums<unsigned, NC, NT> s_cnt;
+    s_cnt.put(v);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            const unsigned total = s_cnt.total(c);
+            if (total && out[c]) atomicAdd(out[c] + frame, total);
+        }
+    }
+}
+
 // ---- the residual of the global fit at a grid sample and the median of a workgroup's residuals: the per-vertex form
 // (vstab_mesh.hip) and the per-row form (vstab_rolling.hip) ----
 __device__ __forceinline__ bool finite_f(float v) { return __builtin_fabsf(v) <= 3.4028234663852886e38f; }   // false for NaN
@@ -575,35 +647,6 @@ struct TileShell {
         npx = active ? (int)((unsigned)(dw - x0 + TILE_TX - 1) / TILE_TX) : 0;   // pixels x0 + p*TILE_TX < dw (callers cap it at TILE_PX); active: dw > x0
     }
 };
-
-// Per-thread counts of an NT-thread block -> wave shuffle -> LDS -> one atomic per counter and block, only if non-zero
-// and asked for (out[c] != nullptr); out[c] is a per-frame array.
-template <int NC, int NT = 256>
-__device__ __forceinline__ void block_count_add(unsigned (&v)[NC], unsigned* const (&out)[NC], int frame)
-{
-    static_assert(NT % 64 == 0, "whole wavefronts");
-    constexpr int WAVES = NT / 64;
-    __shared__ unsigned s_cnt[NC][WAVES];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int c = 0; c < NC; c++) v[c] += __shfl_down(v[c], off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < NC; c++) s_cnt[c][threadIdx.x >> 6] = v[c];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int c = 0; c < NC; c++) {
-            unsigned total = s_cnt[c][0];
-#pragma unroll
-            for (int w = 1; w < WAVES; w++) total += s_cnt[c][w];
-            if (total && out[c]) atomicAdd(out[c] + frame, total);
-        }
-    }
-}
 
 // warp_pixel's displacement hook, of two kinds.  OUTPUT == false: a functor evaluated at the source position
 // q = (Xn * Wn, Yn * Wn) that gives the offset (cx, cy) taken off it before the roundings.  OUTPUT == true: `solve`, evaluated

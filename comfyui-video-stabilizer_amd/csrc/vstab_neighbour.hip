@@ -252,9 +252,9 @@ __global__ __launch_bounds__(256) void temporal_fill_kernel(FillArgs a, const Fi
 //   fill_gain_sums_kernel       integer sums of own and candidate values over the lattice x % 8 == 4 && y % 8 == 4 where
 //                               both see source content by the interior rule; the host turns them into one gain per
 //                               (frame, candidate, channel).  A workgroup = 256 lattice pixels of one (frame, candidate) pair, so
-//                               both records are block-uniform (scalar loads); per-thread values -> wave shuffle -> LDS -> one
-//                               64-bit atomic per sum, skipped where the workgroup counted nothing.  Nothing waits for
-//                               another workgroup, and integer sums do not depend on the order of the atomics.
+//                               both records are block-uniform (scalar loads); per-thread values -> BlockSums
+//                               (vstab_internal.h) -> one 64-bit atomic per sum, skipped where the workgroup counted nothing.
+//                               Nothing waits for another workgroup.
 //   temporal_fill_blend_kernel  the fill's tile, shell and candidate walk, with (a) the sample scaled by the candidate's gain
 //                               and (b) the own pixels within feather_px of the frame's tap-interior border cross-faded
 //                               towards the first valid candidate.  Whether an own pixel takes part costs its mask and its
@@ -279,9 +279,9 @@ struct GainArgs : NeighbourGeom {
 template <int INTERP>
 __global__ __launch_bounds__(256) void fill_gain_sums_kernel(GainArgs a, const FillCand* __restrict__ cands, const FillCand* __restrict__ own)
 {
-    constexpr int NS = 7, WAVES = 4;
+    constexpr int NS = 7;
     __shared__ __attribute__((aligned(16))) float s_cub[32 * 4];
-    __shared__ unsigned s_sum[NS][WAVES];
+    __shared__ BlockSums<unsigned, NS, 256> s_sums;
     const unsigned pair = blockIdx.x / a.blocks_per_pair;          // frame * K + k
     const unsigned chunk = blockIdx.x - pair * a.blocks_per_pair;
     const unsigned frame = pair / (unsigned)a.K;
@@ -323,25 +323,12 @@ __global__ __launch_bounds__(256) void fill_gain_sums_kernel(GainArgs a, const F
         }
     }
 
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int c = 0; c < NS; c++) v[c] += __shfl_down(v[c], off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < NS; c++) s_sum[c][threadIdx.x >> 6] = v[c];
-    }
+    s_sums.put(v);
     __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned total[NS];
+    if (threadIdx.x == 0 && s_sums.total(0) != 0u) {       // nothing counted: every sum is zero, no atomic
+        unsigned long long* out = a.sums + (size_t)pair * NS;
 #pragma unroll
-        for (int c = 0; c < NS; c++) total[c] = s_sum[c][0] + s_sum[c][1] + s_sum[c][2] + s_sum[c][3];
-        if (total[0] != 0u) {       // nothing counted: every sum is zero, no atomic
-            unsigned long long* out = a.sums + (size_t)pair * NS;
-#pragma unroll
-            for (int c = 0; c < NS; c++) atomicAdd(out + c, (unsigned long long)total[c]);
-        }
+        for (int c = 0; c < NS; c++) atomicAdd(out + c, s_sums.total<unsigned long long>(c));
     }
 }
 

@@ -186,7 +186,7 @@ __device__ __forceinline__ bool rectify_point(const RowInverseDisplacement& f, f
 __global__ __launch_bounds__(RECTIFY_THREADS) void rectify_kernel(RectifyArgs a)
 {
     __shared__ int s_wave[RECTIFY_WAVES];
-    __shared__ unsigned s_bad;
+    __shared__ BlockSums<unsigned, 1, RECTIFY_THREADS> s_bad;
     const int pair = (int)blockIdx.x, tid = (int)threadIdx.x;
     const float* __restrict__ G = a.grid + (size_t)pair * a.cells * 2;
     const uint8_t* __restrict__ B0 = a.blocked ? a.blocked + (size_t)pair * a.cells : nullptr;
@@ -195,7 +195,6 @@ __global__ __launch_bounds__(RECTIFY_THREADS) void rectify_kernel(RectifyArgs a)
     const double* __restrict__ V = a.velocity + (size_t)pair * 6;
     const RowInverseDisplacement prev{V[0], V[1], V[2], V[3], V[4], V[5], a.rho, a.hm1};
     const RowInverseDisplacement next{V[6], V[7], V[8], V[9], V[10], V[11], a.rho, a.hm1};
-    if (tid == 0) s_bad = 0u;
 
     const int per = (a.cells + RECTIFY_THREADS - 1) / RECTIFY_THREADS;
     const int g0 = min(tid * per, a.cells), g1 = min(g0 + per, a.cells);
@@ -235,11 +234,9 @@ __global__ __launch_bounds__(RECTIFY_THREADS) void rectify_kernel(RectifyArgs a)
     }
     for (int k = total + tid; k < a.cells; k += RECTIFY_THREADS)
         *reinterpret_cast<float4*>(out + (size_t)k * 4) = make_float4(nan, nan, nan, nan);
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) bad += __shfl_down(bad, s);
-    if ((tid & 63) == 0 && bad) atomicAdd(&s_bad, bad);      // an integer sum: the order does not matter
+    s_bad.put({bad});
     __syncthreads();
-    if (tid == 0) { a.counts[pair] = total; a.unsolved[pair] = s_bad; }
+    if (tid == 0) { a.counts[pair] = total; a.unsolved[pair] = s_bad.total(0); }
 }
 
 // Both directions: the checks, the preparation and the launch.  inverse: the row lever is the output's height, `unsolved` is

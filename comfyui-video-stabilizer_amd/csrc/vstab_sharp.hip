@@ -5,9 +5,8 @@
 //                           and of one more column and row (the halo the forward differences reach into) is computed once per
 //                           pixel into LDS as 32-bit words, rows 65 words apart so that the lanes of a wavefront, which read
 //                           consecutive words, never share a bank.  Both differences come from LDS.  A thread sums its 8
-//                           pixels in 64 bits -> wave shuffle -> LDS over the four waves -> one 64-bit atomic add per
-//                           workgroup and frame, skipped where the tile is flat.  Integer sums do not depend on the order of
-//                           the atomics, and nothing waits for another workgroup.
+//                           pixels in 64 bits -> BlockSums (vstab_internal.h) -> one 64-bit atomic add per workgroup and
+//                           frame, skipped where the tile is flat.  Nothing waits for another workgroup.
 // The pixel loads are non-temporal: a frame is read once by this pass, 12 B per pixel plus the halo (65 * 33 / (64 * 32) =
 // 1.05 reads per pixel, the halo from the cache).  The mask moments measured a tenth in their favour;
 // VSTAB_SHARPNESS_PLAIN (a build flag) restores plain loads for an A/B.  A pixel is three dwords at a 4-byte alignment,
@@ -43,7 +42,7 @@ __global__ __launch_bounds__(SH_THREADS) void frame_sharpness_kernel(const float
                                                                      unsigned tiles_per_frame, unsigned long long* __restrict__ energy)
 {
     __shared__ unsigned s_y[SH_WORDS];
-    __shared__ unsigned long long s_part[SH_THREADS / 64];
+    __shared__ BlockSums<unsigned long long, 1, SH_THREADS> s_energy;
     const unsigned t = threadIdx.x;
     const unsigned frame = blockIdx.x / tiles_per_frame, tile = blockIdx.x - frame * tiles_per_frame;
     const unsigned tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x;
@@ -86,11 +85,10 @@ __global__ __launch_bounds__(SH_THREADS) void frame_sharpness_kernel(const float
         }
     }
 
-    for (int s = 32; s > 0; s >>= 1) sum += __shfl_down(sum, s, 64);
-    if ((t & 63) == 0) s_part[t >> 6] = sum;
+    s_energy.put({sum});
     __syncthreads();
     if (t == 0) {
-        const unsigned long long total = s_part[0] + s_part[1] + s_part[2] + s_part[3];   // <= 2^11 * 2^33
+        const unsigned long long total = s_energy.total(0);   // <= 2^11 * 2^33
         if (total) atomicAdd(energy + frame, total);
     }
 }

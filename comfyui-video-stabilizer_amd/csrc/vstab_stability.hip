@@ -1,8 +1,8 @@
 // vstab_stability.hip -- masked squared error between frames as exact integers (the rule: include/vstab.h).
 //
 //   sse_zero_kernel   the call zeroes its own outputs (one launch instead of two fills on the stream)
-//   frame_sse_kernel  one launch over all pairs: per thread -> wave shuffle -> LDS -> one 64-bit and one 32-bit atomic per
-//                     workgroup and pair, skipped when the workgroup counted nothing
+//   frame_sse_kernel  one launch over all pairs: per thread -> two BlockSums (vstab_internal.h) behind one barrier -> one
+//                     64-bit and one 32-bit atomic per workgroup and pair, skipped when the workgroup counted nothing
 // A frame is read as the flat float array it is, in tiles of 3072 floats (1024 pixels), so that consecutive lanes load
 // consecutive addresses whatever the pixel stride (the warp kernel's lesson): float4 per lane where frame a[k] and
 // frame b[k] sit at the same offset from a 16-byte boundary (up to 3 head and 3 tail floats go one by one), one float per
@@ -42,8 +42,8 @@ __global__ __launch_bounds__(SSE_THREADS) void frame_sse_kernel(const float* a, 
                                                                 unsigned px, unsigned blocks_per_pair,
                                                                 unsigned long long* __restrict__ sse_out, unsigned* __restrict__ count_out)
 {
-    __shared__ unsigned long long wave_sse[SSE_THREADS / 64];
-    __shared__ unsigned wave_count[SSE_THREADS / 64];
+    __shared__ BlockSums<unsigned long long, 1, SSE_THREADS> s_sse;
+    __shared__ BlockSums<unsigned, 1, SSE_THREADS> s_count;
     const unsigned t = threadIdx.x;
     const unsigned pair = blockIdx.x / blocks_per_pair, slot = blockIdx.x - pair * blocks_per_pair;
     const size_t floats = (size_t)px * 3;
@@ -118,20 +118,14 @@ __global__ __launch_bounds__(SSE_THREADS) void frame_sse_kernel(const float* a, 
         }
     }
 
-    // wave shuffle, LDS over the four waves, one pair of atomics per workgroup -- none if it counted nothing (its sum is 0 then)
-    for (int s = 32; s > 0; s >>= 1) {
-        sse += __shfl_down(sse, s, 64);
-        count += __shfl_down(count, s, 64);
-    }
-    if ((t & 63) == 0) {
-        wave_sse[t >> 6] = sse;
-        wave_count[t >> 6] = count;
-    }
+    // one pair of atomics per workgroup -- none if it counted nothing (its sum is 0 then)
+    s_sse.put({sse});
+    s_count.put({count});
     __syncthreads();
     if (t == 0) {
-        const unsigned total = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
+        const unsigned total = s_count.total(0);
         if (total) {
-            atomicAdd(&sse_out[pair], wave_sse[0] + wave_sse[1] + wave_sse[2] + wave_sse[3]);
+            atomicAdd(&sse_out[pair], s_sse.total(0));
             atomicAdd(&count_out[pair], total);
         }
     }

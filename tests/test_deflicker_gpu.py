@@ -104,7 +104,7 @@ def test_hist_and_sums_equal_the_restatement(pkg, ctx, n, h, w):
 
 
 # ---- 2. the correction --------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n,h,w", [(2, 1, 1), (3, 3, 5), (3, 45, 67)])
+@pytest.mark.parametrize("n,h,w", [(2, 1, 1), (3, 3, 5), (3, 45, 67), (2, 13, 79)])      # 13 x 79: a tile of 1024 pixels and 3 more
 def test_apply_equals_the_restatement_in_bits(pkg, ctx, n, h, w):
     import torch
 

@@ -21,8 +21,8 @@ MASK_VALUES = np.array([0.0, 1.0, 0.5, np.nan, np.inf, 0.0, 0.0], np.float32)
 
 # (n, h, w): a single pixel; one row; frame sizes that are no multiple of 16 bytes (3 x 13 x 67 floats: frame k starts k floats
 # past the boundary); a frame of whole float4s (8 x 64 pixels, half a tile of 1024); 9 x 130 = one tile and a part; 37 x 253 =
-# ten tiles, a workgroup each
-SHAPES = [(1, 1, 1), (3, 1, 67), (3, 13, 67), (4, 8, 64), (2, 9, 130), (5, 37, 253)]
+# ten tiles, a workgroup each; 13 x 79 = one tile and three pixels: the second workgroup sums over two lanes of one wave
+SHAPES = [(1, 1, 1), (3, 1, 67), (3, 13, 67), (4, 8, 64), (2, 9, 130), (5, 37, 253), (2, 13, 79)]
 
 
 def _dev(ctx, x):

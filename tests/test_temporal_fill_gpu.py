@@ -81,7 +81,7 @@ SHAPES = [(3, 4, 37, 53, 37, 53, 1), (2, 5, 270, 481, 290, 500, 2), (3, 6, 61, 8
 
 
 @pytest.mark.parametrize("interp,subpix", MODES)
-@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("shape", SHAPES + [(2, 3, 9, 65, 9, 65, 1)])      # 9 x 65: the last 64 x 8 tile holds one (padded) pixel
 def test_kernel_matches_restatement(ctx, oracle, shape, interp, subpix):
     n, clip, sh, sw, dh, dw, K = shape
     src, dst, mask, mats, cand = _drawn_case(n, clip, sh, sw, dh, dw, K, seed=dh * 7 + K)
