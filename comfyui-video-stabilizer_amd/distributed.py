@@ -217,7 +217,8 @@ def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, t
                       estimator: str = "flow", stats: Optional[Dict[str, float]] = None, want_meta: bool = True,
                       check_value_range: bool = True, temporal_fill: int = 0, estimation_mask=None, scene_cuts=None,
                       mesh_warp=None, dynamic_zoom=None, sharpness_transfer=None, rolling_shutter=None,
-                      drift_correction=None, drift_exposure=None, drift_mask=None, deflicker=None, deflicker_mode=None):
+                      drift_correction=None, drift_exposure=None, drift_mask=None, deflicker=None, deflicker_mode=None,
+                      horizon_level=None, horizon_limit=None):
     """Sharded equivalent of `_stabilize_frames` (flow.py:213-640).
 
     local_frames: device tensor [n_local (+1 halo for rank > 0 that owns frames), H, W, 3] float32 -- this rank's frames
@@ -285,6 +286,13 @@ def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, t
          "two ranks, and the gain chain runs through the whole clip); run the single-GPU pipeline for it"),
         ("deflicker_mode", deflicker_mode is not None,
          f"stabilize_sharded does not support deflicker_mode={deflicker_mode!r}: the deflicker it belongs to is not sharded; "
+         "run the single-GPU pipeline for it"),
+        # the offset is a median over a whole shot: every rank's rolls would have to be gathered before the warp
+        ("horizon_level", horizon_level is not None,
+         f"stabilize_sharded does not support horizon_level={horizon_level!r}: the horizon level is not sharded (the roll "
+         "offset is a median over every rank's frames); run the single-GPU pipeline for it"),
+        ("horizon_limit", horizon_limit is not None,
+         f"stabilize_sharded does not support horizon_limit={horizon_limit!r}: the horizon level it belongs to is not sharded; "
          "run the single-GPU pipeline for it"),
     )
     for _keyword, requested, message in refusals:

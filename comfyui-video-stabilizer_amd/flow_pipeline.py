@@ -23,6 +23,7 @@ import numpy as np
 
 from . import deflicker as deflicker_mod
 from . import dynamic_zoom as dynamic_zoom_mod
+from . import horizon_level as horizon_level_mod
 from . import host_math as hm
 from . import mesh_warp as mesh_warp_mod
 from . import native
@@ -822,6 +823,21 @@ def _dynamic_zoom(ctx, zoom, plan, offsets, segments):
     return replace(plan, final_matrices=np.matmul(Z, np.asarray(plan.final_matrices, dtype=np.float32))), block
 
 
+# ---- horizon level (beyond the reference; horizon_level.py, the rule is in include/vstab.h) -----------------------------
+def _horizon_level(ctx, level, plan, gray, segments):
+    """-> (the plan with its final matrices levelled, meta["horizon_level"]).  One launch of the orientation histogram over
+    the estimation images the estimator made, then on the host: every frame's roll, the chain's roll from the plan's own
+    full-resolution transitions, one offset per shot (or a slowly varying one); L @ final in float32, like the zoom.  A clip
+    on which no frame is corrected (not observable) keeps its plan as it is."""
+    hist = ctx.orientation_hist_batch(gray, horizon_level_mod.MIN_MAG2).cpu().numpy()
+    em = plan.estimated_motion
+    L, block = horizon_level_mod.plan_level(level, hist, em["matrices"], em["confidences"], plan.final_matrices, plan.output_size,
+                                            plan.fps_effective, segments)
+    if L is None:
+        return plan, block
+    return replace(plan, final_matrices=np.matmul(L, np.asarray(plan.final_matrices, dtype=np.float32))), block
+
+
 # ---- the driver: one validated request, one record of the reference's arguments, one post-warp tail ----------------------
 @dataclass(frozen=True)
 class FlowRequest:
@@ -848,6 +864,7 @@ class FlowRequest:
     drift_exposure: bool = False       # drift_correction.check_options: the keyframe alignment estimates a gain and an offset
     drift_mask: bool = False           # ... and leaves out what the estimation mask's block grid names
     deflicker: Any = None              # deflicker.check_request: Request | None
+    level: Any = None                  # horizon_level.check_request: Request | None
     refit: bool = False                # rolling_shutter.check_refit_request: the transitions are fitted again on rectified samples
 
     @property
@@ -856,16 +873,19 @@ class FlowRequest:
         the vertex paths need the plan's own transitions before the warp can be queued; and dynamic-zoom calls: the zoom is
         formed from the plan's final matrices before the warp can be queued; and rolling-shutter calls: the velocities come
         from the plan's transitions before the warp can be queued; and drift-corrected calls: the keyframe alignment rewrites
-        the transitions before there is a plan."""
-        return not (self.scene is None and self.mesh is None and self.zoom is None and self.rolling is None and self.drift is None)
+        the transitions before there is a plan; and levelled calls: the roll is measured and the final matrices are turned
+        before the warp can be queued."""
+        return not (self.scene is None and self.mesh is None and self.zoom is None and self.rolling is None and self.drift is None
+                    and self.level is None)
 
     @property
     def kept_by_products(self) -> Tuple[str, ...]:
         """The estimator's by-products that stay alive behind the fits (its `*_out` keywords): the estimation images for the
-        scene-cut score and the keyframe alignment, the grid of flow samples for the vertex / row residuals.  (The estimation
-        mask's block grid, which drift_mask reads behind the fits, is made before the estimator runs and is held by the
-        call itself for all of its length: it is no by-product and needs no entry here.)"""
-        keep = ("gray_out",) if (self.scene is not None and self.scene.mode == "auto") or self.drift is not None else ()
+        scene-cut score, the keyframe alignment and the horizon level's histogram, the grid of flow samples for the vertex /
+        row residuals.  (The estimation mask's block grid, which drift_mask reads behind the fits, is made before the estimator
+        runs and is held by the call itself for all of its length: it is no by-product and needs no entry here.)"""
+        auto_cuts = self.scene is not None and self.scene.mode == "auto"
+        keep = ("gray_out",) if auto_cuts or self.drift is not None or self.level is not None else ()
         return keep + (("grid_out",) if self.mesh is not None or self.rolling == rolling_shutter_mod.AUTO or self.refit else ())
 
 
@@ -912,9 +932,12 @@ def check_flow_request(framing_mode: str, transform_mode: str, estimator: str, k
     deflicker = deflicker_mod.check_request(kw.get("deflicker"), kw.get("deflicker_mode"))
     if deflicker is not None:
         deflicker_mod.check_pipeline(estimator, temporal_fill, fill_blend[1], sharpness)
+    level = horizon_level_mod.check_request(kw.get("horizon_level"), kw.get("horizon_limit"))
+    if level is not None:
+        horizon_level_mod.check_pipeline(framing_mode, transform_mode, estimator, rolling)
     return FlowRequest(estimator, temporal_fill, fill_blend, sharpness, handoff, zoom, scene, mesh, bool(kw["mesh_motion"]),
                        bool(subject), rolling, spatial_fill, stability_report, mask_margin, drift, drift_exposure, drift_mask,
-                       refit=refit, deflicker=deflicker)
+                       refit=refit, deflicker=deflicker, level=level)
 
 
 def _check_request_against_clip(request: FlowRequest, kw: Dict[str, Any], transform_mode: str, total_frames: int, size) -> None:
@@ -1057,6 +1080,8 @@ def _stabilize_frames(
     rolling_refit=None,
     deflicker=None,
     deflicker_mode=None,
+    horizon_level=None,
+    horizon_limit=None,
     drift_correction=None,
     drift_exposure=None,
     drift_mask=None,
@@ -1190,7 +1215,19 @@ def _stabilize_frames(
     deflickered frames; padding keeps its colour.  Behind either plan path, with every camera estimator; not with estimator
     "subject", sharpness_transfer, or temporal_fill without fill_exposure=True.  meta["deflicker"] reports every pair's gain,
     every frame's correction and the chain's RMS step before and after.  None / False: the behaviour and meta without it, byte
-    for byte, and nothing new is launched.  Bypass paths ignore it."""
+    for byte, and nothing new is launched.  Bypass paths ignore it.
+    horizon_level, horizon_limit (beyond the reference, None by default): True levels every shot with one roll offset, a window
+    in seconds in (0, 60] lets that offset vary slowly (a camera that tips over).  Every other pass removes relative motion; a
+    clip shot 5 degrees off level comes out steady and 5 degrees off level.  The estimation images' gradient orientations,
+    folded modulo 90 degrees, are reduced to one histogram per frame (horizon_level.py; include/vstab.h states the rule); its
+    peak is the frame's roll, the chain of transitions supplies every frame's roll relative to its shot's first frame, and the
+    median of the differences -- per shot under scene_cuts -- is the one number taken from the picture content.  Every final
+    matrix is then turned about the canvas centre by what is left, at most horizon_limit degrees (None: 20, else in (0, 45):
+    structure gives the roll modulo 90 only), in front of the mesh warp and the dynamic zoom, and everything behind the plan
+    follows.  A shot without enough measurable frames is reported as not observable and is left as it is.  For crop_and_pad
+    framing and translation / similarity, not with estimator "subject" or rolling_shutter; meta["horizon_level"] reports every
+    frame's roll, confidence, offset and correction.  None: the behaviour and meta without it, byte for byte, and nothing new
+    is launched.  Bypass paths ignore it."""
     kw = dict(locals())     # every argument by name (nothing else is local yet): the keyword extras are read from here
     request = check_flow_request(framing_mode, transform_mode, estimator, kw)
     estimator = request.estimator
@@ -1303,7 +1340,9 @@ def _stabilize_frames(
         return hm.StabilizationResult(frames_out, masks_out, _attach_motion_meta(plan.bypass_meta, fps_effective, estimator))
 
     # ---- warp (F13) ------------------------------------------------------------
-    mesh_block = zoom_block = rolling_block = offsets = None
+    mesh_block = zoom_block = rolling_block = level_block = offsets = None
+    if request.level is not None:
+        plan, level_block = _horizon_level(ctx, request.level, plan, extras["gray_out"][0], segments)
     if mesh is not None:
         offsets, mesh_block = _mesh_offsets(ctx, mesh, plan, extras["grid_out"][0], blocked, working_size, size, segments, args)
     if zoom is not None:
@@ -1330,6 +1369,7 @@ def _stabilize_frames(
     pad_counts = _counts_to_host(counts)
     meta = complete_meta(meta, plan, pad_counts)
     blocks = {   # in the order the meta lists them
+        "horizon_level": level_block,
         "dynamic_zoom": None if zoom_block is None else dynamic_zoom_mod.finish_meta(zoom_block, pad_counts),
         "estimation_mask": None if mask_info is None else estimation_mask_meta(fit_records, *mask_info),
         "scene_cuts": scene_block,

@@ -25,6 +25,7 @@ MASK_HOLD_MAX, MASK_GROW_MAX, MASK_FEATHER_MAX = 16, 64, 64    # VSTAB_MASK_*_MA
 MODE_NAMES = ("translation", "similarity", "perspective")
 MESH_MAX_VERTS = 65      # vertices per axis of a mesh warp (64 cells; include/vstab.h)
 MESH_MIN_SAMPLES = 4     # VSTAB_MESH_MIN_SAMPLES
+ORIENTATION_K = 256      # VSTAB_ORIENTATION_K
 
 # Sub-pixel model used by the node path; see include/vstab.h (vstab_subpix) and DESIGN.md.
 DEFAULT_SUBPIX = os.environ.get("VSTAB_SUBPIX", "q5")
@@ -243,6 +244,7 @@ _SIGNATURES = {
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vstab_apply_gain_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vstab_orientation_hist_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p]),
     "vstab_gftt_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p,
                   C.c_void_p]),
@@ -1405,6 +1407,26 @@ class Context:
         _check(self.lib.vstab_mask_moments_batch(self.handle, _dev_ptr(mask), n, h, w, _dev_ptr(sums), _dev_ptr(bbox)),
                "vstab_mask_moments_batch")
         return sums, bbox
+
+    # ------------------------------------------------------------------ horizon level
+    def orientation_hist_batch(self, gray, min_mag2: int):
+        """The histogram of gradient orientations, folded modulo 90 degrees and weighted by the squared Scharr gradient, of every
+        frame of gray [n,h,w], u8, device, contiguous, as exact integers (include/vstab.h states the rule); pixels with a
+        squared gradient below min_mag2 (0 .. 2^32 - 1) are left out; nothing is written to the images.
+        -> hist i64 [n, 2 * ORIENTATION_K + 1], device tensor; bin k + ORIENTATION_K stands for atan(k / ORIENTATION_K)."""
+        torch = self.torch
+        if not (isinstance(gray, torch.Tensor) and gray.dtype == torch.uint8 and gray.device == self.device and gray.is_contiguous()):
+            raise ValueError(f"orientation_hist_batch: gray must be a contiguous uint8 tensor on {self.device}")
+        if gray.dim() != 3:
+            raise ValueError(f"orientation_hist_batch: gray of shape {tuple(gray.shape)} is not [n,h,w]")
+        if isinstance(min_mag2, bool) or not isinstance(min_mag2, (int, np.integer)) or not 0 <= int(min_mag2) <= 0xFFFFFFFF:
+            raise ValueError(f"orientation_hist_batch: min_mag2={min_mag2!r} is not an integer in [0, 2^32 - 1]")
+        n, h, w = int(gray.shape[0]), int(gray.shape[1]), int(gray.shape[2])
+        hist = torch.empty((n, 2 * ORIENTATION_K + 1), dtype=torch.int64, device=self.device)
+        self.use_torch_stream()
+        _check(self.lib.vstab_orientation_hist_batch(self.handle, _dev_ptr(gray), n, h, w, int(min_mag2), _dev_ptr(hist)),
+               "vstab_orientation_hist_batch")
+        return hist
 
     # ------------------------------------------------------------------ sharpness transfer
     def frame_sharpness_batch(self, frames):

@@ -1239,6 +1239,49 @@ class VideoStabilizerDeflicker(io.ComfyNode):
         return io.NodeOutput(_image_out(dst, out_context), json.dumps({"deflicker": block}))
 
 
+class VideoStabilizerFlowLevel(io.ComfyNode):
+    """The Flow node that also levels the picture: the roll of every frame is measured from the orientation of its edges,
+    one offset per shot -- or one that varies slowly -- is taken from it, and every frame is turned upright about the centre
+    (horizon_level.py).  Framing is fixed to crop_and_pad.  Not one of the reference's nodes: it is listed by an extension but
+    kept out of NODE_CLASSES."""
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        from .horizon_level import DEFAULT_LIMIT_DEG, LIMIT_MAX_DEG, WINDOW_MAX_S
+
+        schema = io.Schema(
+            node_id="video_stabilizer_flow_level",
+            display_name="Video Stabilizer Flow (Horizon Level)",
+            category="Video/Stabilization",
+            description=("Video Stabilizer Flow that also levels the horizon: a clip shot a few degrees off level comes out "
+                         "steady and upright."),
+        )
+        base = VideoStabilizerFlow.define_schema()
+        schema.inputs = [
+            io.Combo.Input("transform_mode", options=["translation", "similarity"], default="similarity",
+                           display_name="Transform Mode",
+                           tooltip=("Select the geometric model fitted to the optical flow.  A homography has no single roll, "
+                                    "so perspective is not offered."))
+            if s.id == "transform_mode" else s for s in base.inputs if s.id != "framing_mode"] + [
+            io.Float.Input("level_window", default=0.0, min=0.0, max=WINDOW_MAX_S, step=0.05, display_name="Level Window",
+                           tooltip=("Seconds over which the roll offset may vary, for a camera that slowly tips over.  0 takes "
+                                    "one offset for every shot.")),
+            io.Float.Input("level_limit", default=DEFAULT_LIMIT_DEG, min=0.5, max=LIMIT_MAX_DEG - 0.5, step=0.5,
+                           display_name="Level Limit",
+                           tooltip=("Largest correction in degrees.  Edges give the roll modulo 90 degrees only, so it stays "
+                                    "below 45.  The default has been tried on synthetic clips only.")),
+        ]
+        schema.outputs = _estimator_outputs()
+        return schema
+
+    @classmethod
+    def execute(cls, frames: Any, frame_rate: float, transform_mode: str, camera_lock: bool, strength: float, smooth: float,
+                keep_fov: float, padding_color: str, level_window: float = 0.0, level_limit: float = 20.0) -> io.NodeOutput:
+        return _run_estimator_node("flow", frames, frame_rate, "crop_and_pad", transform_mode, camera_lock, strength, smooth,
+                                   keep_fov, padding_color, horizon_level=True if float(level_window) == 0.0 else float(level_window),
+                                   horizon_limit=float(level_limit))
+
+
 class VideoStabilizerAmdExtension(ComfyExtension):
     async def get_node_list(self) -> list:
         return list(NODE_CLASSES) + [VideoStabilizerTemporalFill]   # the six reference nodes + the temporal fill
@@ -1330,3 +1373,6 @@ VideoStabilizerAmdRollingRefitExtension = _extend(
 VideoStabilizerAmdDeflickerExtension = _extend(
     VideoStabilizerAmdRollingRefitExtension, VideoStabilizerDeflicker, name="VideoStabilizerAmdDeflickerExtension",
     doc="The refit extension's twenty-four nodes plus Video Stabilizer Deflicker.")
+VideoStabilizerAmdLevelExtension = _extend(
+    VideoStabilizerAmdDeflickerExtension, VideoStabilizerFlowLevel, name="VideoStabilizerAmdLevelExtension",
+    doc="The deflicker extension's twenty-five nodes plus Video Stabilizer Flow (Horizon Level).")

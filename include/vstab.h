@@ -1043,6 +1043,37 @@ int vstab_pair_gain_sums_batch(vstab_ctx* ctx, const float* src, int n, int h, i
 int vstab_apply_gain_batch(vstab_ctx* ctx, float* frames, const float* mask, int n, int h, int w, const float* gains,
                            uint32_t* clamped);
 
+/* ---- horizon level: which way is up, per estimation image, as exact integers (beyond the reference, off by default) ----
+ * Everything else measures pairs; this measures one frame.  Man-made and natural structure is mostly vertical or horizontal,
+ * so the histogram of gradient orientations, folded modulo 90 degrees, peaks at the frame's roll (horizon_level.py finds
+ * the peak and turns it into one offset per shot on the host).  This entry point reduces every estimation image to 2K + 1
+ * integers, K = VSTAB_ORIENTATION_K.  The rule, for every pixel (x, y) with all eight neighbours (1 <= x <= w - 2,
+ * 1 <= y <= h - 2) of every frame g, all in integers:
+ *   gx = 3 * (g[y-1][x+1] - g[y-1][x-1]) + 10 * (g[y][x+1] - g[y][x-1]) + 3 * (g[y+1][x+1] - g[y+1][x-1])
+ *   gy = 3 * (g[y+1][x-1] - g[y-1][x-1]) + 10 * (g[y+1][x] - g[y-1][x]) + 3 * (g[y+1][x+1] - g[y-1][x+1])
+ *   m2 = gx * gx + gy * gy                      (|gx|, |gy| <= 4080: m2 < 2^26)
+ * (the Scharr derivative: the 3x3 Sobel weights 1 2 1 bias the orientation of a smooth edge by degrees, these by tenths).
+ * A pixel with m2 < min_mag2 or m2 == 0 adds nothing.  Otherwise, with a = |gx|, b = |gy|:
+ *   j = (2 * K * min(a, b) + max(a, b)) / (2 * max(a, b))     integer division: round(K * min / max), 0 .. K
+ *   k = sign(gx * gy) * (a >= b ? 1 : -1) * j
+ *   hist[frame][k + K] += m2
+ * The bins are uniform in the slope, so nothing transcendental runs on the device: bin k stands for the orientation
+ * atan(k / K), the gradient's direction folded into [-45, 45] degrees.  Bins -K and +K are the same orientation (a == b
+ * lands in one of them by the sign of gx * gy); the host folds them.  Content rotated by the point matrix
+ * [[c, -s], [s, c]] in pixel coordinates (x right, y down) puts its axis-aligned edges at +theta.
+ * Integer sums do not depend on the order of their reduction, so the result equals a NumPy restatement exactly; a frame's
+ * total is below 2^31 * 2^26: no wrap.
+ *   gray dev [n, h, w] u8, read only;  hist dev [n, 2K + 1] u64, 8-byte aligned.  The call presets its own output.
+ * n >= 1;  1 <= w, h <= 32768;  h * w < 2^31.  h < 3 or w < 3 is valid and gives an all-zero histogram.
+ * Kernel (vstab_level.hip, shaped as the scene-cut residual's is): one launch over all frames, a workgroup per 16 rows of a
+ * frame, a lane per 16 pixels of a row -- three aligned 16-byte loads and six halo bytes where w % 16 == 0 and gray is
+ * 16-byte aligned, byte loads otherwise; a lane merges its run of equal bins in a 64-bit register and adds it to its wave's
+ * copy of the histogram in LDS when the bin changes; behind a barrier the copies are summed and every non-zero bin goes out
+ * with one 64-bit atomic add per workgroup and frame.  Asynchronous on the context's stream; timing kind
+ * "orientation_hist". */
+#define VSTAB_ORIENTATION_K 256
+int vstab_orientation_hist_batch(vstab_ctx* ctx, const uint8_t* gray, int n, int h, int w, uint32_t min_mag2, uint64_t* hist);
+
 /* ---- F6 / F9 host helper: element-wise libm over fp64 arrays (host pointers, no GPU involved) ----
  * nodes/stabilizer_utils.py:300-358 (_matrix_to_params / _params_to_matrix) call math.sqrt/atan2/log and
  * math.exp/cos/sin per frame; this runs the same libm functions over a whole clip in one call.
