@@ -218,7 +218,7 @@ def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, t
                       check_value_range: bool = True, temporal_fill: int = 0, estimation_mask=None, scene_cuts=None,
                       mesh_warp=None, dynamic_zoom=None, sharpness_transfer=None, rolling_shutter=None,
                       drift_correction=None, drift_exposure=None, drift_mask=None, deflicker=None, deflicker_mode=None,
-                      horizon_level=None, horizon_limit=None):
+                      horizon_level=None, horizon_limit=None, plate_fill=None):
     """Sharded equivalent of `_stabilize_frames` (flow.py:213-640).
 
     local_frames: device tensor [n_local (+1 halo for rank > 0 that owns frames), H, W, 3] float32 -- this rank's frames
@@ -294,6 +294,10 @@ def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, t
         ("horizon_limit", horizon_limit is not None,
          f"stabilize_sharded does not support horizon_limit={horizon_limit!r}: the horizon level it belongs to is not sharded; "
          "run the single-GPU pipeline for it"),
+        # the median runs over every frame of a shot, and a rank holds a slice of it
+        ("plate_fill", plate_fill is not None and plate_fill is not False,
+         f"stabilize_sharded does not support plate_fill={plate_fill!r}: the clean plate is not sharded (the median runs over "
+         "every frame of a shot, and a rank holds a slice of it); run the single-GPU pipeline for it"),
     )
     for _keyword, requested, message in refusals:
         if requested:

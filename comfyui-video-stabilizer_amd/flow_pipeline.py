@@ -21,6 +21,7 @@ from typing import Any, Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 
+from . import clean_plate as clean_plate_mod
 from . import deflicker as deflicker_mod
 from . import dynamic_zoom as dynamic_zoom_mod
 from . import horizon_level as horizon_level_mod
@@ -644,6 +645,24 @@ def _sharpness_transfer(ctx, device_frames, dst, mask, plan, meta, sharp) -> Non
         np.asarray(em["matrices"], dtype=np.float32), em["confidences"], sharp[0], sharp[1])
 
 
+def _plate(ctx, dst, mask, plan, min_count, segments):
+    """-> (plate, count, sample table) of every shot, or None (clean_plate.py).  Formed from the frames as they stand behind the
+    deflicker and the sharpness transfer, under the warp's TRUE mask, before any fill: a filled pixel gets mask 0 and would vote
+    as an own one.  min_count: clean_plate.check_request's answer, None = off.  `crop` framing has no padding: nothing to do."""
+    if min_count is None or plan.framing_mode == "crop":
+        return None
+    return clean_plate_mod.plate_on_device(ctx, dst, mask, segments)
+
+
+def _plate_fill(ctx, dst, mask, meta, min_count, plate_state, segments) -> None:
+    """Fills what is still padding behind the temporal fill from its shot's plate in place (clean_plate.py) and adds
+    meta["plate_fill"]; a filled pixel's mask becomes 0 -- it was seen -- and the other meta keys keep describing the warp."""
+    if plate_state is None:
+        return
+    plate, count, table = plate_state
+    meta["plate_fill"] = clean_plate_mod.fill_and_report(ctx, dst, mask, plate, count, table, segments, min_count)
+
+
 def _spatial_fill(ctx, dst, mask, plan, meta, enabled: bool) -> None:
     """Fills what is still padding from each frame's own valid pixels in place (spatial_fill.py), as the very last pass on
     the outputs, and adds meta["spatial_fill"]; the mask and the other meta keys are unchanged.  `crop` framing has no
@@ -865,6 +884,7 @@ class FlowRequest:
     drift_mask: bool = False           # ... and leaves out what the estimation mask's block grid names
     deflicker: Any = None              # deflicker.check_request: Request | None
     level: Any = None                  # horizon_level.check_request: Request | None
+    plate: Optional[int] = None        # clean_plate.check_request: the plate fill's min_count | None
     refit: bool = False                # rolling_shutter.check_refit_request: the transitions are fitted again on rectified samples
 
     @property
@@ -935,9 +955,12 @@ def check_flow_request(framing_mode: str, transform_mode: str, estimator: str, k
     level = horizon_level_mod.check_request(kw.get("horizon_level"), kw.get("horizon_limit"))
     if level is not None:
         horizon_level_mod.check_pipeline(framing_mode, transform_mode, estimator, rolling)
+    plate = clean_plate_mod.check_request(kw.get("plate_fill"))
+    if plate is not None:
+        clean_plate_mod.check_pipeline(kw.get("camera_lock"), kw.get("strength"), estimator, zoom, level)
     return FlowRequest(estimator, temporal_fill, fill_blend, sharpness, handoff, zoom, scene, mesh, bool(kw["mesh_motion"]),
                        bool(subject), rolling, spatial_fill, stability_report, mask_margin, drift, drift_exposure, drift_mask,
-                       refit=refit, deflicker=deflicker, level=level)
+                       refit=refit, deflicker=deflicker, level=level, plate=plate)
 
 
 def _check_request_against_clip(request: FlowRequest, kw: Dict[str, Any], transform_mode: str, total_frames: int, size) -> None:
@@ -970,14 +993,18 @@ def _finish(ctx, request: FlowRequest, plan, device_frames, dst, mask, meta, seg
     has to see the warp's mask before a fill clears it, and the passes behind it -- the exposure match of the blended fill, the
     fills themselves, the stability report -- then work on deflickered frames (the sharpness transfer and a hard temporal
     fill, which would bring uncorrected neighbour pixels in, are refused with it).  The sharpness transfer runs before the
-    fills: a filled pixel gets mask 0 and would be taken for an own one.  Temporal fill comes before spatial fill: seen pixels before invented ones.  The stability report
+    fills: a filled pixel gets mask 0 and would be taken for an own one.  The clean plate is formed before any fill, for the same
+    reason, and fills between the two: seen nearby in time (temporal fill), then seen anywhere in the shot (plate fill), then
+    invented (spatial fill).  The stability report
     measures behind every fill; the spatial fill leaves the mask as it is, so its invented pixels stay out of it.  The mask
     hand-off runs last, so that every other pass has seen the true mask; it replaces only the mask that is returned.  Each
     pass adds its own meta block, in this order, and nothing else in the meta changes.
     segments: the shots under scene cuts, None for one continuous camera move (always on the device-plan path)."""
     _deflicker(ctx, device_frames, dst, mask, plan, meta, request.deflicker, segments)
     _sharpness_transfer(ctx, device_frames, dst, mask, plan, meta, request.sharpness)
+    plate_state = _plate(ctx, dst, mask, plan, request.plate, segments)
     _temporal_fill(ctx, device_frames, dst, mask, plan, meta, request.temporal_fill, request.fill_blend)
+    _plate_fill(ctx, dst, mask, meta, request.plate, plate_state, segments)
     _spatial_fill(ctx, dst, mask, plan, meta, request.spatial_fill)
     _stability_report(ctx, device_frames, dst, mask, plan, meta, request.stability_report, segments)
     mask = _mask_handoff(ctx, mask, plan, meta, request.handoff, segments)
@@ -1082,6 +1109,7 @@ def _stabilize_frames(
     deflicker_mode=None,
     horizon_level=None,
     horizon_limit=None,
+    plate_fill=None,
     drift_correction=None,
     drift_exposure=None,
     drift_mask=None,
@@ -1227,7 +1255,18 @@ def _stabilize_frames(
     follows.  A shot without enough measurable frames is reported as not observable and is left as it is.  For crop_and_pad
     framing and translation / similarity, not with estimator "subject" or rolling_shutter; meta["horizon_level"] reports every
     frame's roll, confidence, offset and correction.  None: the behaviour and meta without it, byte for byte, and nothing new
-    is launched.  Bypass paths ignore it."""
+    is launched.  Bypass paths ignore it.
+    plate_fill (beyond the reference, None by default): True, or the number of valid samples a plate pixel needs, an int in
+    1..256 (True is 1).  A locked shot registers every output frame to its shot's first frame, so the per-pixel median over
+    time of what the frames really show -- the samples under the warp's own mask, up to 256 frames per shot at the centres of
+    equal strata -- is one still image of the background with everything that moves taken out (clean_plate.py; include/vstab.h
+    states the rules).  It is formed before any fill, per shot under scene_cuts, and what is still padding behind
+    temporal_fill is taken from it, with its mask set to 0 as the temporal fill does, before spatial_fill invents the rest: the
+    border is one plate, not a patchwork that changes its donor from frame to frame.  Needs camera_lock=True at strength 1; not
+    with dynamic_zoom, a horizon_level window or estimator "subject", whose frames are not registered to each other (or not
+    on the background).  `padding_fraction_*` keep describing the warp; meta["plate_fill"] reports samples, what was filled,
+    what is left and what no frame of a shot saw.  None / False: the behaviour and meta without it, byte for byte, and nothing
+    new is launched.  `crop` framing has no padding; bypass paths ignore it."""
     kw = dict(locals())     # every argument by name (nothing else is local yet): the keyword extras are read from here
     request = check_flow_request(framing_mode, transform_mode, estimator, kw)
     estimator = request.estimator

@@ -26,6 +26,10 @@ MODE_NAMES = ("translation", "similarity", "perspective")
 MESH_MAX_VERTS = 65      # vertices per axis of a mesh warp (64 cells; include/vstab.h)
 MESH_MIN_SAMPLES = 4     # VSTAB_MESH_MIN_SAMPLES
 ORIENTATION_K = 256      # VSTAB_ORIENTATION_K
+PLATE_SAMPLES_MAX = 256  # VSTAB_PLATE_SAMPLES_MAX
+PLATE_REGISTER_MAX = 64  # VSTAB_PLATE_REGISTER_MAX: the widest row the register form of the median kernel takes
+# the sample counts at which vstab_plate_median_batch changes kernel: 4 / 8 / 16 / 32 / 64 key registers, then 128 / 256 LDS rows
+PLATE_PATH_STEPS = (4, 8, 16, 32, PLATE_REGISTER_MAX, 128)
 
 # Sub-pixel model used by the node path; see include/vstab.h (vstab_subpix) and DESIGN.md.
 DEFAULT_SUBPIX = os.environ.get("VSTAB_SUBPIX", "q5")
@@ -245,6 +249,14 @@ _SIGNATURES = {
     "vstab_apply_gain_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vstab_orientation_hist_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p]),
+    "vstab_plate_median_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vstab_plate_fill_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                  C.c_void_p]),
+    "vstab_plate_matte_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
+                  C.c_int, C.c_void_p, C.c_void_p]),
     "vstab_gftt_batch": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p,
                   C.c_void_p]),
@@ -1427,6 +1439,97 @@ class Context:
         _check(self.lib.vstab_orientation_hist_batch(self.handle, _dev_ptr(gray), n, h, w, int(min_mag2), _dev_ptr(hist)),
                "vstab_orientation_hist_batch")
         return hist
+
+    # ------------------------------------------------------------------ clean plate
+    def _plate_tensor(self, who, name, t, dtype, shape=None):
+        torch = self.torch
+        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == self.device and t.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be a contiguous {str(dtype).replace('torch.', '')} tensor on {self.device}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{who}: {name} of shape {tuple(t.shape)} is not {tuple(shape)}")
+
+    def _plate_frames(self, who, name, frames, mask, mask_optional=True):
+        """frames [n,h,w,3] and mask [n,h,w] | None, both f32, device, contiguous -> (n, h, w)."""
+        self._plate_tensor(who, name, frames, self.torch.float32)
+        if frames.dim() != 4 or frames.shape[3] != 3 or min(frames.shape) < 1:
+            raise ValueError(f"{who}: {name} of shape {tuple(frames.shape)} are not [n,h,w,3] with n, h, w >= 1")
+        n, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+        if mask is not None or not mask_optional:
+            self._plate_tensor(who, "mask", mask, self.torch.float32, (n, h, w))
+        return n, h, w
+
+    def _plate_inputs(self, who, plate, count, h, w, shot, n, min_count):
+        """plate [shots,h,w,3] f32 and count [shots,h,w] i32 (device), shot [n] | None, min_count -> (shots, shot i32 | None)."""
+        self._plate_tensor(who, "plate", plate, self.torch.float32)
+        if plate.dim() != 4 or tuple(plate.shape[1:]) != (h, w, 3) or plate.shape[0] < 1:
+            raise ValueError(f"{who}: plate of shape {tuple(plate.shape)} is not [shots,{h},{w},3]")
+        shots = int(plate.shape[0])
+        self._plate_tensor(who, "count", count, self.torch.int32, (shots, h, w))
+        if isinstance(min_count, (bool, np.bool_)) or not isinstance(min_count, (int, np.integer)) or not 1 <= int(min_count) <= PLATE_SAMPLES_MAX:
+            raise ValueError(f"{who}: min_count={min_count!r} is not an integer in 1..{PLATE_SAMPLES_MAX}")
+        sh = None
+        if shot is not None:
+            sh = np.ascontiguousarray(shot, dtype=np.int32).reshape(-1)
+            if sh.shape[0] != n or (np.diff(sh.astype(np.int64)) < 0).any() or sh.min() < 0 or sh.max() >= shots:
+                raise ValueError(f"{who}: shot of shape {np.shape(shot)} is not a non-decreasing sequence of n={n} shot numbers in 0..{shots - 1}")
+        elif shots != 1:
+            raise ValueError(f"{who}: shot=None means one shot, but plate holds {shots}")
+        return shots, sh
+
+    def plate_median_batch(self, frames, mask, sample_frame):
+        """Clean plate (vstab_plate_median_batch; include/vstab.h states the rule): the per-pixel, per-channel lower median over
+        the sampled frames of every shot, among the samples whose mask is <= 0.5.  frames f32 [n,h,w,3] and mask f32 [n,h,w] or
+        None (device, contiguous, read only), sample_frame int [shots,S], S in 1..256: strictly increasing frame indices per row,
+        then -1 padding (the library refuses anything else by name).  -> (plate f32 [shots,h,w,3], count i32 [shots,h,w])."""
+        who = "plate_median_batch"
+        n, h, w = self._plate_frames(who, "frames", frames, mask)
+        tab = np.ascontiguousarray(sample_frame, dtype=np.int32)
+        if tab.ndim != 2 or tab.shape[0] < 1:
+            raise ValueError(f"{who}: sample_frame of shape {tab.shape} is not [shots,S]")
+        shots, S = int(tab.shape[0]), int(tab.shape[1])
+        torch = self.torch
+        plate = torch.empty((shots, h, w, 3), dtype=torch.float32, device=self.device)
+        count = torch.empty((shots, h, w), dtype=torch.int32, device=self.device)
+        self.use_torch_stream()
+        _check(self.lib.vstab_plate_median_batch(self.handle, _dev_ptr(frames), _dev_ptr(mask) if mask is not None else None, n, h, w,
+                                                 tab.ctypes.data, shots, S, _dev_ptr(plate), _dev_ptr(count)), "vstab_plate_median_batch")
+        return plate, count
+
+    def plate_fill_batch(self, dst, mask, plate, count, shot, min_count):
+        """Fills what is still padding from the plate IN PLACE (vstab_plate_fill_batch): a pixel of frame i with
+        !(mask <= 0.5) and count[shot[i]] >= min_count takes the plate's colour and mask 0; every other pixel keeps its bits.
+        dst f32 [n,h,w,3], mask f32 [n,h,w], plate / count as plate_median_batch returns them, shot int [n] non-decreasing or None
+        (one shot), min_count an int in 1..256.  -> filled_count i32 [n], device tensor."""
+        who = "plate_fill_batch"
+        n, h, w = self._plate_frames(who, "dst", dst, mask, mask_optional=False)
+        shots, sh = self._plate_inputs(who, plate, count, h, w, shot, n, min_count)
+        filled = self.torch.empty((n,), dtype=self.torch.int32, device=self.device)
+        self.use_torch_stream()
+        _check(self.lib.vstab_plate_fill_batch(self.handle, _dev_ptr(dst), _dev_ptr(mask), n, h, w, _dev_ptr(plate), _dev_ptr(count),
+                                               sh.ctypes.data if sh is not None else None, shots, int(min_count), _dev_ptr(filled)),
+               "vstab_plate_fill_batch")
+        return filled
+
+    def plate_matte_batch(self, frames, mask, plate, count, shot, threshold, min_count):
+        """The difference matte against the plate (vstab_plate_matte_batch): 1.0 where the pixel is own (mask <= 0.5, or mask
+        None), count[shot[i]] >= min_count and some channel has !(|frame - plate| <= threshold), else 0.0.  Arguments as
+        plate_fill_batch; threshold a finite float >= 0; nothing is written to the inputs.
+        -> (matte f32 [n,h,w], matte_count i32 [n]), device tensors."""
+        who = "plate_matte_batch"
+        n, h, w = self._plate_frames(who, "frames", frames, mask)
+        shots, sh = self._plate_inputs(who, plate, count, h, w, shot, n, min_count)
+        if isinstance(threshold, (bool, np.bool_)) or not isinstance(threshold, (int, float, np.integer, np.floating)) \
+                or not (np.isfinite(threshold) and threshold >= 0):
+            raise ValueError(f"{who}: threshold={threshold!r} is not a finite number >= 0")
+        torch = self.torch
+        matte = torch.empty((n, h, w), dtype=torch.float32, device=self.device)
+        marked = torch.empty((n,), dtype=torch.int32, device=self.device)
+        self.use_torch_stream()
+        _check(self.lib.vstab_plate_matte_batch(self.handle, _dev_ptr(frames), _dev_ptr(mask) if mask is not None else None, n, h, w,
+                                                _dev_ptr(plate), _dev_ptr(count), sh.ctypes.data if sh is not None else None, shots,
+                                                float(np.float32(threshold)), int(min_count), _dev_ptr(matte), _dev_ptr(marked)),
+               "vstab_plate_matte_batch")
+        return matte, marked
 
     # ------------------------------------------------------------------ sharpness transfer
     def frame_sharpness_batch(self, frames):

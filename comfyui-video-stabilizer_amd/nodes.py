@@ -1282,6 +1282,102 @@ class VideoStabilizerFlowLevel(io.ComfyNode):
                                    horizon_limit=float(level_limit))
 
 
+class VideoStabilizerCleanPlate(io.ComfyNode):
+    """The clean plate of a REGISTERED clip (clean_plate.py) -- a tripod shot, or the output of a stabilizer run with camera
+    lock at strength 1 -- taken as one shot: the per-pixel median over time of what the frames show under their padding mask,
+    the frames with their leftover padding filled from it, and the matte of what differs from it.  Not one of the reference's
+    nodes: it is listed by VideoStabilizerAmdPlateExtension and kept out of NODE_CLASSES."""
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        from .clean_plate import DEFAULT_MATTE_MIN_COUNT, DEFAULT_MATTE_THRESHOLD, SAMPLES_MAX
+
+        schema = io.Schema(
+            node_id="video_stabilizer_clean_plate",
+            display_name="Video Stabilizer Clean Plate",
+            category="Video/Stabilization",
+            description=("The background of a locked shot with everything that moves taken out (the per-pixel median over time), "
+                         "the frames with their padding filled from it, and the difference matte."),
+        )
+        schema.inputs = [
+            io.Image.Input("frames", display_name="Frames", tooltip="A registered clip: a tripod shot or a camera-locked stabilizer output."),
+            io.Mask.Input("padding_mask", display_name="Padding Mask", optional=True,
+                          tooltip="[N,H,W], or [1,H,W] for every frame; padded pixels do not vote.  Without it every pixel is own."),
+            io.Boolean.Input("fill", default=True, display_name="Fill", tooltip="Fill the padded pixels from the plate and clear their mask."),
+            io.Int.Input("min_count", default=1, min=1, max=SAMPLES_MAX, step=1, display_name="Min Count",
+                         tooltip="Frames that must have seen a plate pixel before it fills anything."),
+            io.Float.Input("matte_threshold", default=DEFAULT_MATTE_THRESHOLD, min=0.0, max=1.0, step=0.01, display_name="Matte Threshold",
+                           tooltip="A pixel is matte where some channel differs from the plate by more than this.  A choice, not a calibration."),
+            io.Int.Input("matte_min_count", default=DEFAULT_MATTE_MIN_COUNT, min=1, max=SAMPLES_MAX, step=1, display_name="Matte Min Count",
+                         tooltip="Frames that must have seen a plate pixel before it can mark a matte.  A choice, not a calibration."),
+        ]
+        schema.outputs = [
+            io.Image.Output("plate", display_name="Plate"),
+            io.Image.Output("frames", display_name="Frames"),
+            io.Mask.Output("padding_mask", display_name="Padding Mask"),
+            io.Mask.Output("matte", display_name="Matte"),
+            io.String.Output("meta", display_name="Meta"),
+        ]
+        return schema
+
+    @classmethod
+    def execute(cls, frames: Any, padding_mask: Any = None, fill: bool = True, min_count: int = 1, matte_threshold: float = 0.1,
+                matte_min_count: int = 3) -> io.NodeOutput:
+        import json
+
+        from . import clean_plate, native
+
+        # every check comes before any GPU work
+        if not isinstance(fill, (bool, np.bool_)):
+            raise ValueError(f"clean plate: fill={fill!r} is not a bool")
+        for name, value in (("min_count", min_count), ("matte_min_count", matte_min_count)):
+            if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or not 1 <= int(value) <= clean_plate.SAMPLES_MAX:
+                raise ValueError(f"clean plate: {name}={value!r} is not an integer in 1..{clean_plate.SAMPLES_MAX}")
+        if isinstance(matte_threshold, bool) or not isinstance(matte_threshold, (int, float)) or not 0.0 <= matte_threshold <= 1.0:
+            raise ValueError(f"clean plate: matte_threshold={matte_threshold!r} is not a number in [0, 1]")
+        context = hm._normalize_video_input(frames)
+        n, h, w = len(context.frames), context.height, context.width
+        if n == 0:
+            raise ValueError("clean plate: socket 'frames' holds no frame")
+        shape = None
+        if padding_mask is not None:
+            if not (hasattr(padding_mask, "dtype") and hasattr(padding_mask, "shape")):
+                raise ValueError(f"clean plate: socket 'padding_mask' must be a floating-point MASK tensor, got {type(padding_mask).__name__}")
+            if "float" not in str(padding_mask.dtype):
+                raise ValueError(f"clean plate: socket 'padding_mask' must be a floating-point MASK, got {padding_mask.dtype}")
+            shape = tuple(int(v) for v in padding_mask.shape)
+            if len(shape) == 4 and shape[3] == 1:
+                shape = shape[:3]
+            if len(shape) != 3 or shape[1:] != (h, w) or shape[0] not in (1, n):
+                raise ValueError(f"clean plate: socket 'padding_mask' of shape {tuple(padding_mask.shape)} does not match "
+                                 f"socket 'frames' [{n},{h},{w},3]: expected [{n},{h},{w}] or [1,{h},{w}]")
+        ctx = native.default_context()
+        torch = ctx.torch
+        src = context.device_batch(ctx)
+        if context.range_pending and hm.resolve_value_range(context, hm.prefetch_peaks(ctx.frame_range(src)), ctx):
+            src = context.device_batch(ctx)      # F0's value-range rule, as every node of the package applies it to its frames
+        mask = None
+        if padding_mask is not None:
+            mask = padding_mask if isinstance(padding_mask, torch.Tensor) else torch.from_numpy(np.asarray(padding_mask))
+            # (a copy: the fill works in place, and the caller's tensor -- another node's cached output -- stays as it is)
+            mask = mask.to(device=ctx.device, dtype=torch.float32).reshape((shape[0], h, w)).expand(n, h, w).clone()
+        plate, count, table = clean_plate.plate_on_device(ctx, src, mask)
+        matte, matte_count = clean_plate.matte_on_device(ctx, src, mask, plate, count, None, float(matte_threshold), int(matte_min_count))
+        block = {"version": 1, "samples": int((table >= 0).sum()), "matte_threshold": float(matte_threshold),
+                 "matte_min_count": int(matte_min_count)}
+        pixels = np.float32(h * w)
+        share = (matte_count.cpu().numpy().astype(np.float32) / pixels).astype(np.float64)
+        block.update({"matte_fraction_mean": float(np.mean(share)), "matte_fraction_max": float(np.max(share))})
+        dst = src
+        if fill and mask is not None:
+            dst = src.clone()
+            block["plate_fill"] = clean_plate.fill_and_report(ctx, dst, mask, plate, count, table, None, int(min_count))
+        if mask is None:
+            mask = torch.zeros((n, h, w), dtype=torch.float32, device=ctx.device)
+        return io.NodeOutput(_image_out(plate, context), _image_out(dst, context), _mask_out(mask, 1), _mask_out(matte, 1),
+                             json.dumps({"clean_plate": block}))
+
+
 class VideoStabilizerAmdExtension(ComfyExtension):
     async def get_node_list(self) -> list:
         return list(NODE_CLASSES) + [VideoStabilizerTemporalFill]   # the six reference nodes + the temporal fill
@@ -1376,3 +1472,6 @@ VideoStabilizerAmdDeflickerExtension = _extend(
 VideoStabilizerAmdLevelExtension = _extend(
     VideoStabilizerAmdDeflickerExtension, VideoStabilizerFlowLevel, name="VideoStabilizerAmdLevelExtension",
     doc="The deflicker extension's twenty-five nodes plus Video Stabilizer Flow (Horizon Level).")
+VideoStabilizerAmdPlateExtension = _extend(
+    VideoStabilizerAmdLevelExtension, VideoStabilizerCleanPlate, name="VideoStabilizerAmdPlateExtension",
+    doc="The level extension's twenty-six nodes plus Video Stabilizer Clean Plate.")

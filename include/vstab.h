@@ -1074,6 +1074,64 @@ int vstab_apply_gain_batch(vstab_ctx* ctx, float* frames, const float* mask, int
 #define VSTAB_ORIENTATION_K 256
 int vstab_orientation_hist_batch(vstab_ctx* ctx, const uint8_t* gray, int n, int h, int w, uint32_t min_mag2, uint64_t* hist);
 
+/* ---- clean plate: the per-pixel temporal median of a registered shot, its fill and its matte (beyond the reference, off by default) ----
+ * Every other pass behind the warp looks at one frame, a pair or a window of neighbours.  A locked shot (camera_lock at
+ * strength 1) registers every output frame to its shot's first frame, so one pixel position shows one scene point all through
+ * the shot: the median over time of what the frames really show there is the background with everything that moves taken
+ * out, the ideal border is that one still image, and its difference to a frame is a matte of what moves.  A selection on
+ * integers is the same in any order, so all three results equal a NumPy restatement in bits.
+ *
+ * vstab_plate_median_batch -- 1. Plate, per shot s (row s of sample_frame) and pixel p:
+ *   - Sample j (a frame index of the row) of pixel p is VALID iff mask_j(p) <= 0.5f; a NaN mask is not valid (the stability
+ *     report's convention).  mask == NULL: every sample is valid.  count_s(p) = the number of valid samples.
+ *   - Per channel, the valid values are ordered by their float32 order keys: the total order of the sign-magnitude bits, -0.0f
+ *     below +0.0f (the mask hand-off's order); every NaN is first mapped to the largest key.
+ *   - plate_s(p, c) = the LOWER median, the element of 0-based rank (count - 1) / 2, returned with the sample's own bits; a
+ *     NaN returns as 0x7FC00000.  count == 0 gives 0.0f in all three channels.
+ *   - Nothing crosses from one row to another.
+ *   frames        dev  [n, h, w, 3] f32, read only;  mask dev [n, h, w] f32, read only, or NULL
+ *   sample_frame  host [shots, S] i32, S in 1..VSTAB_PLATE_SAMPLES_MAX: every row holds strictly increasing frame indices in
+ *                 0..n-1 followed by -1 padding only, and at least one index; anything else is refused by name
+ *   plate         dev  [shots, h, w, 3] f32;  count dev [shots, h, w] i32.  h * w < 2^31.
+ * Kernels (vstab_plate.hip): [h, w, 3] is a flat array of elements e with mask index e / 3, so consecutive lanes load
+ * consecutive floats of one frame and every frame and mask value crosses HBM once.  The widest row decides the form.  Up to
+ * VSTAB_PLATE_REGISTER_MAX samples: a lane per element, the keys in 4 / 8 / 16 / 32 / 64 registers.  Beyond: a workgroup of 256
+ * threads per 64 elements, the keys staged in LDS as [sample][element] in 128 / 256 rows (64 KiB at 256: two workgroups
+ * per CU), then 16 lanes x 4 quarters of the samples per element, their counts joined by two shuffles.  Both select the key of
+ * rank r as the largest v with #{key < v} <= r, from the top bit down: 32 counting passes.  A sample that is not valid is
+ * staged as the largest key, which r < count never reaches.  Asynchronous on the context's stream; timing kind "plate_median".
+ *
+ * vstab_plate_fill_batch -- 2. Plate fill, for frame i with s = shot[i] (shot == NULL: every frame is of shot 0):
+ *   - Pixel p is FILLED iff !(mask_i(p) <= 0.5f) && count_s(p) >= min_count.  A NaN mask pixel is filled.
+ *   - A filled pixel takes the plate's three floats, its mask becomes 0.0f -- it was seen, not invented: the temporal fill's
+ *     convention -- and it counts in filled_count[i].  Every other pixel keeps its bits in both tensors.
+ *   dst dev [n, h, w, 3] f32 and mask dev [n, h, w] f32, both in and out;  plate, count as above, read only
+ *   shot host [n] i32, non-decreasing, values in 0..shots-1, or NULL;  min_count in 1..VSTAB_PLATE_SAMPLES_MAX
+ *   filled_count dev [n] u32 or NULL, zeroed by the call.
+ *
+ * vstab_plate_matte_batch -- 3. Matte: matte_i(p) = 1.0f iff all three hold, else 0.0f:
+ *   - the pixel is own: mask_i(p) <= 0.5f, or mask == NULL;
+ *   - count_s(p) >= min_count;
+ *   - for some channel c, !(fabsf(f_c - plate_c) <= threshold): one float32 subtraction per channel, and a NaN on either side
+ *     reads as "differs" (the estimation mask's convention: the unknown is subject).
+ *   frames dev [n, h, w, 3] f32 and mask dev [n, h, w] f32 or NULL, read only;  threshold finite and >= 0
+ *   matte dev [n, h, w] f32;  matte_count dev [n] u32 or NULL, zeroed by the call: the pixels of frame i with matte 1.
+ * Kernels: streaming, workgroups per frame.  Where h * w is a multiple of 4 and every pointer is 16-byte aligned a lane takes
+ * four whole pixels with 16-byte accesses (the fill reads the mask first and touches neither the frame nor the plate where none
+ * of the four is padding); otherwise a lane takes one whole pixel -- never a single float of one, because the fill writes the
+ * mask value that decides the pixel's other two channels.  The per-frame counts go through BlockSums: one atomic add per
+ * workgroup and frame.  Asynchronous on the context's stream; timing kinds "plate_fill" and "plate_matte".
+ * The 256 samples are a choice, not a calibration (clean_plate.py holds the others). */
+#define VSTAB_PLATE_SAMPLES_MAX 256
+#define VSTAB_PLATE_REGISTER_MAX 64
+int vstab_plate_median_batch(vstab_ctx* ctx, const float* frames, const float* mask, int n, int h, int w,
+                             const int32_t* sample_frame, int shots, int S, float* plate, int32_t* count);
+int vstab_plate_fill_batch(vstab_ctx* ctx, float* dst, float* mask, int n, int h, int w, const float* plate, const int32_t* count,
+                           const int32_t* shot, int shots, int min_count, uint32_t* filled_count);
+int vstab_plate_matte_batch(vstab_ctx* ctx, const float* frames, const float* mask, int n, int h, int w, const float* plate,
+                            const int32_t* count, const int32_t* shot, int shots, float threshold, int min_count, float* matte,
+                            uint32_t* matte_count);
+
 /* ---- F6 / F9 host helper: element-wise libm over fp64 arrays (host pointers, no GPU involved) ----
  * nodes/stabilizer_utils.py:300-358 (_matrix_to_params / _params_to_matrix) call math.sqrt/atan2/log and
  * math.exp/cos/sin per frame; this runs the same libm functions over a whole clip in one call.
