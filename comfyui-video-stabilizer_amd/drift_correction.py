@@ -2,29 +2,29 @@
 frame i is a chain of i / S keyframe alignments instead of i consecutive-pair estimates whose bias adds up.
 
 The alignment is inverse-compositional Gauss-Newton on the estimation images the gray pass already made.  Its normal
-equations are exact integer sums over pixels (`native.Context.anchor_sums_batch`, csrc/vstab_anchor.hip; the rule is stated
-once, in include/vstab.h); everything here is float64 arithmetic on 17 numbers per frame, driven by a
-`sums_fn(anchor, R) -> int64 [N,17]` callable: the kernel in the pipeline, the NumPy restatement in the CPU suite.
+equations are exact integer sums over pixels (csrc/vstab_anchor.hip; the rule and its two forms are stated once, in
+include/vstab.h); everything here is float64 arithmetic on those numbers, driven by a `sums_fn` callable: the kernel in the
+pipeline, the NumPy restatement in the CPU suite.  The plain rule gives 17 numbers per frame
+(`native.Context.anchor_sums_batch`); exposure matching (`drift_exposure`) and the subject mask (`drift_mask`) use the second
+form (`native.Context.anchor_sums_ex_batch`, 31 numbers).  The plain rule is the second form at unit gain without a mask, so
+there is one loop, `refine_ex`, on the 31; `refine` puts the plain rule's 17 into their places among them.
 
 The update.  T is the template (the anchor's image), I the frame's, R maps an anchor pixel into the frame, and W(d) moves a
 template pixel p = (x, y) about the image centre c = ((w-1)/2, (h-1)/2):
     W(d): p -> p + (d0 + d2 xc - d3 yc,  d1 + d3 xc + d2 yc),   (xc, yc) = p - c.
-We look for d with T(W(d) p) = I(R p).  To first order T(W(d) p) = T(p) + grad T . (dW/dd) d, so with the central
-differences grad T = (gx / 2, gy / 2) and xc = u / 2, yc = q / 2 the true Jacobian is D J, D = diag(1/2, 1/2, 1/4, 1/4), of
-the rule's integer J, and the residual is r / 1024.  (D H D) d = D b / 1024 is H d' = b / 1024 with d' = D d, hence
-d = (2 d'0, 2 d'1, 4 d'2, 4 d'3).  Substituting p' = W(d) p gives I(R W(d)^-1 p') = T(p'): the update is R <- R W(d)^-1.
-
-Exposure matching (`drift_exposure`) and the subject mask (`drift_mask`) use the second form of the rule
-(`native.Context.anchor_sums_ex_batch`, 31 numbers per frame).  The model becomes I(R p) = g T(W(d) p) + o.  The kernel holds
-the integers G = 1024 g and O = 1024 o of the current estimate and forms r = v - G T - O with v = 1024 I(R p).  With the gain
-off by dg and the offset by do, I - g T - o = dg T + do + (g + dg) grad T . (dW/dd) d to first order; times 1024, and with
-the integer Jacobian as above, r = dG T + dO + (G + dG) (J[0..3] . d'), dG = 1024 dg, dO = 1024 do.  That is linear in
-theta = ((G + dG) d'_0..3, dG, dO) with the columns (J0, J1, J2, J3, T, 1): H6 theta = b6, d'_k = theta_k / (G + dG), and d
-and the update of R as above.  At G = 1024, dG = 0 the first four rows are H d' = b / 1024 again."""
+The model is I(R p) = g T(W(d) p) + o; the plain rule holds g = 1, o = 0.  The kernel has the integers G = 1024 g and
+O = 1024 o of the current estimate and forms r = v - G T - O with v = 1024 I(R p).  To first order T(W(d) p) = T(p) +
+grad T . (dW/dd) d, and with the central differences grad T = (gx / 2, gy / 2) and xc = u / 2, yc = q / 2 the true Jacobian
+is D J, D = diag(1/2, 1/2, 1/4, 1/4), of the rule's integer J: grad T . (dW/dd) d = J[0..3] . d' with d' = D d, hence
+d = (2 d'0, 2 d'1, 4 d'2, 4 d'3).  With the gain off by dg and the offset by do, I - g T - o = dg T + do + (g + dg) J . d';
+times 1024, r = dG T + dO + (G + dG) (J[0..3] . d'), dG = 1024 dg, dO = 1024 do.  That is linear in
+theta = ((G + dG) d'_0..3, dG, dO) with the columns (J0, J1, J2, J3, T, 1): H6 theta = b6 and d'_k = theta_k / (G + dG).
+Without exposure matching G = 1024 and dG = dO = 0 are held, and the first four rows are H d' = b / 1024.  Substituting
+p' = W(d) p gives I(R W(d)^-1 p') = g T(p') + o: the update is R <- R W(d)^-1."""
 
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
@@ -281,9 +281,9 @@ class Refinement:
     reason: List[Optional[str]]  # per frame: None = refined, else one of KEEP_REASONS
     launches: int
     iterations: int
-    sums_first: np.ndarray       # int64 [N,17] at the chained matrices
+    sums_first: np.ndarray       # int64 [N,17] (PLAIN_SLOTS) at the chained matrices: the launch the cost test starts from
     sums_final: np.ndarray       # int64 [N,17] at the refined ones (zeros where none was evaluated)
-    # the exposure-matched / masked form only (refine_ex); sums_first is then the launch the cost test starts from
+    # the exposure-matched / masked form only (None from `refine`)
     gain: Optional[np.ndarray] = None        # int64 [N]: G per frame, 1024 where the frame was kept or has no anchor
     offset: Optional[np.ndarray] = None      # int64 [N]: O per frame
     masked_first: Optional[np.ndarray] = None    # int64 [N]: the masked pixels of that launch
@@ -291,67 +291,29 @@ class Refinement:
 
 
 def refine(sums_fn, work_mats, sched: Schedule, mode: str, size) -> Refinement:
-    """Gauss-Newton on every anchored frame at once: at most MAX_ITERATIONS launches that solve, converged frames drop out
-    (anchor -1), one more launch evaluates the result, then the four tests that keep a frame's chained matrix."""
-    if mode not in MODES:
-        raise ValueError(f"drift correction: mode {mode!r} is not one of {MODES}")
-    w, h = size
-    anchor = sched.anchor
-    n = anchor.shape[0]
-    R0 = chained(work_mats, sched)
-    R = R0.copy()
-    reason: List[Optional[str]] = [None if a >= 0 else "no_anchor" for a in anchor.tolist()]
-    active = anchor >= 0
-    first = np.zeros((n, SLOTS), np.int64)
-    launches = iterations = 0
-    for it in range(MAX_ITERATIONS):
-        if not active.any():
-            break
-        sums = np.asarray(sums_fn(np.where(active, anchor, -1), R.reshape(n, 6)), dtype=np.int64).reshape(n, SLOTS)
-        launches += 1
-        iterations += 1
-        if it == 0:
-            first = sums.copy()
-        for i in np.nonzero(active)[0].tolist():
-            d = solve_update(sums[i], mode)
-            if d is None:
-                reason[i], active[i] = "singular", False
-                continue
-            new = (_affine3(sampled_at(R[i], size)) @ np.linalg.inv(warp_matrix(d, size)))[:2]
-            moved = corner_distance(new, R[i], size)
-            R[i] = new
-            if moved < CONVERGED_PX:
-                active[i] = False
-    final = np.zeros((n, SLOTS), np.int64)
-    evaluate = np.array([r is None for r in reason])
-    if evaluate.any():
-        final = np.asarray(sums_fn(np.where(evaluate, anchor, -1), R.reshape(n, 6)), dtype=np.int64).reshape(n, SLOTS)
-        launches += 1
-    need = MIN_OVERLAP * (w - 2) * (h - 2)
-    for i in np.nonzero(evaluate)[0].tolist():
-        count0, sum0, count1, sum1 = int(first[i, 0]), int(first[i, 2]), int(final[i, 0]), int(final[i, 2])
-        if count1 < need:
-            reason[i] = "overlap"
-        elif sum1 * count0 > sum0 * count1:          # the mean |r| went up: integers, no division
-            reason[i] = "cost"
-        elif corner_distance(R[i], R0[i], size) > MAX_CORRECTION_PX:
-            reason[i] = "step"
-    for i, r in enumerate(reason):
-        if r is not None:
-            R[i] = R0[i]
-    return Refinement(R, R0, reason, launches, iterations, first, final)
+    """The plain rule: sums_fn(anchor, R) -> int64 [N,17], taken at RESIDUAL_CAP.  It is the second form at G = 1024, O = 0
+    without a mask, so its 17 numbers go to their places among the 31 and `refine_ex` runs without exposure."""
+    n = sched.anchor.shape[0]
+
+    def sums_ex_fn(anchor, R, gain, offset, cap):
+        sums = np.zeros((n, SLOTS_EX), np.int64)
+        sums[:, PLAIN_SLOTS] = np.asarray(sums_fn(anchor, R), dtype=np.int64).reshape(n, SLOTS)
+        return sums
+
+    return replace(refine_ex(sums_ex_fn, work_mats, sched, mode, size, exposure=False), gain=None, offset=None, masked_first=None)
 
 
 def refine_ex(sums_fn, work_mats, sched: Schedule, mode: str, size, exposure: bool) -> Refinement:
-    """`refine` on the 31 numbers of the second form: sums_fn(anchor, R, gain, offset, cap) -> int64 [N,31], with or without
-    a mask behind it.  The kernel always sees the integers held here: G <- rint(G + dG), O <- rint(O + dO) after every solve.
+    """Gauss-Newton on every anchored frame at once, on the 31 numbers of the second form: sums_fn(anchor, R, gain, offset,
+    cap) -> int64 [N,31], with or without a mask behind it.  At most MAX_ITERATIONS launches that solve, converged frames
+    drop out (anchor -1), one more launch evaluates the result, then the tests that keep a frame's chained matrix.
+    The kernel always sees the integers held here: G <- rint(G + dG), O <- rint(O + dO) after every solve.
     exposure: the first launch is the bootstrap.  At G = 1024 an exposure step pushes most pixels over the cap before any gain
     is known, so that launch runs with BOOTSTRAP_CAP (which caps nothing) and only its gain and offset are taken: uncapped sums
     hold every moving subject, so the motion they give is not applied, and R stays the chained matrix.  Every later launch and
     the evaluating one run with RESIDUAL_CAP.  The second launch is therefore the chained matrix under the estimated exposure,
-    and the cost test compares it with the last launch, both under the same cap (`before_launch` = 2), as `refine` compares
-    its first launch with its last.  Without exposure the gain stays 1024 / 0 and the tests are `refine`'s, on the first
-    launch."""
+    and the cost test compares it with the last launch, both under the same cap (`before_launch` = 2).  Without exposure the
+    gain stays 1024 / 0, every launch runs with RESIDUAL_CAP and the cost test starts from the first launch."""
     if mode not in MODES:
         raise ValueError(f"drift correction: mode {mode!r} is not one of {MODES}")
     w, h = size
@@ -496,7 +458,8 @@ def correct(sums_fn, fit_records: np.ndarray, selection, segments, total_frames:
             exposure: bool = False, masked: bool = False):
     """Everything between the estimator's fit table and the plan: schedule, refinement, poses.
     selection: (work_mats, modes, confidences, ...) as select_transitions returns them.
-    exposure / masked: sums_fn is the second form's, sums_fn(anchor, R, gain, offset, cap) -> int64 [N,31].
+    sums_fn: the plain rule's, sums_fn(anchor, R) -> int64 [N,17]; with exposure or masked the second form's,
+    sums_fn(anchor, R, gain, offset, cap) -> int64 [N,31].
     -> (the fit table with the corrected transitions, path_deltas f64 [N-1,P], meta["drift_correction"])."""
     work_mats, modes, confidences = selection[0], selection[1], selection[2]
     work = working_size if working_size is not None else size

@@ -820,16 +820,15 @@ def _drift_correction(ctx, spacing, fit_records, gray, segments, total_frames, t
     else:
         selection = _select_per_segment(table, transform_mode, segments)
 
-    def sums_fn(anchor, R):
-        return ctx.anchor_sums_batch(gray, anchor, R, drift_correction_mod.RESIDUAL_CAP)
+    second_form = exposure or blocked is not None
 
-    def sums_ex_fn(anchor, R, gain, offset, cap):
-        return ctx.anchor_sums_ex_batch(gray, anchor, R, cap, gain, offset, blocked, SAMPLE_STEP)
+    def sums_fn(anchor, R, gain=None, offset=None, cap=drift_correction_mod.RESIDUAL_CAP):
+        if second_form:
+            return ctx.anchor_sums_ex_batch(gray, anchor, R, cap, gain, offset, blocked, SAMPLE_STEP)
+        return ctx.anchor_sums_batch(gray, anchor, R, cap)       # the faster kernel
 
-    if exposure or blocked is not None:
-        return drift_correction_mod.correct(sums_ex_fn, table, selection, segments, total_frames, transform_mode, size, working_size,
-                                            spacing, exposure=exposure, masked=blocked is not None)
-    return drift_correction_mod.correct(sums_fn, table, selection, segments, total_frames, transform_mode, size, working_size, spacing)
+    return drift_correction_mod.correct(sums_fn, table, selection, segments, total_frames, transform_mode, size, working_size, spacing,
+                                        exposure=exposure, masked=blocked is not None)
 
 
 # ---- dynamic zoom (beyond the reference; dynamic_zoom.py, the rule is in include/vstab.h) -------------------------------

@@ -781,75 +781,60 @@ class Context:
         in include/vstab.h).  gray u8 [N,h,w] (device), anchor int [N] (-1: no anchor), R f64 [N,6] or [N,2,3] (anchor pixel ->
         frame pixel, working resolution), cap 0..255 -> int64 [N,17] on the host: integers, equal to the NumPy restatement
         exactly."""
-        torch = self.torch
-        if gray.dtype != torch.uint8 or gray.dim() != 3:
-            raise ValueError("anchor_sums_batch expects a uint8 [N,h,w] tensor")
-        if gray.device != self.device or not gray.is_contiguous():   # (a contiguous view keeps its own, possibly unaligned, base)
-            gray = gray.to(self.device).contiguous()
-        n, h, w = (int(v) for v in gray.shape)
-        if n < 1:
-            raise ValueError("anchor_sums_batch needs at least one frame")
-        a = np.ascontiguousarray(anchor, dtype=np.int32).reshape(-1)
-        m = np.ascontiguousarray(R, dtype=np.float64)
-        if a.size != n or m.size != n * 6:
-            raise ValueError(f"anchor_sums_batch: anchor {a.shape} / R {m.shape} are not [{n}] / [{n},6] for {n} frames")
-        if a.size and (a.min() < -1 or a.max() >= n):
-            raise ValueError(f"anchor_sums_batch: an anchor outside -1..{n - 1}")
-        if max(h, w) > 1024:
-            raise ValueError(f"anchor_sums_batch: {w}x{h} image larger than 1024 on a side")
-        if int(cap) != cap or not 0 <= int(cap) <= 255:
-            raise ValueError(f"anchor_sums_batch: cap {cap!r} is not an integer in 0..255")
-        out = torch.empty((n, 17), dtype=torch.int64, device=self.device)
-        self.use_torch_stream()
-        _check(self.lib.vstab_anchor_sums_batch(self.handle, _dev_ptr(gray), n, h, w, a.ctypes.data, m.ctypes.data, int(cap),
-                                                _dev_ptr(out)), "vstab_anchor_sums_batch")
-        return out.cpu().numpy()
+        return self._anchor_sums(False, gray, anchor, R, cap)
 
     def anchor_sums_ex_batch(self, gray, anchor, R, cap, gain=None, offset=None, blocked=None, step=8):
         """Drift correction, exposure-matched and masked (vstab_anchor_sums_ex_batch; the rule is in include/vstab.h).  gray,
         anchor, R, cap as anchor_sums_batch; gain, offset int [N] in units of 1/1024 (None: 1024 / 0 for every frame), blocked
         u8 [N,gh,gw] on the device (mask_block_grid at `step`) or None -> int64 [N,31] on the host: integers, equal to the
         NumPy restatement exactly."""
+        return self._anchor_sums(True, gray, anchor, R, cap, gain, offset, blocked, step)
+
+    def _anchor_sums(self, ex, gray, anchor, R, cap, gain=None, offset=None, blocked=None, step=8):
+        """Both forms of the rule: the checks they share, then the second form's own (ex), then the call."""
         torch = self.torch
+        who = "anchor_sums_ex_batch" if ex else "anchor_sums_batch"
         if gray.dtype != torch.uint8 or gray.dim() != 3:
-            raise ValueError("anchor_sums_ex_batch expects a uint8 [N,h,w] tensor")
+            raise ValueError(f"{who} expects a uint8 [N,h,w] tensor")
         if gray.device != self.device or not gray.is_contiguous():   # (a contiguous view keeps its own, possibly unaligned, base)
             gray = gray.to(self.device).contiguous()
         n, h, w = (int(v) for v in gray.shape)
         if n < 1:
-            raise ValueError("anchor_sums_ex_batch needs at least one frame")
+            raise ValueError(f"{who} needs at least one frame")
         a = np.ascontiguousarray(anchor, dtype=np.int32).reshape(-1)
         m = np.ascontiguousarray(R, dtype=np.float64)
         if a.size != n or m.size != n * 6:
-            raise ValueError(f"anchor_sums_ex_batch: anchor {a.shape} / R {m.shape} are not [{n}] / [{n},6] for {n} frames")
+            raise ValueError(f"{who}: anchor {a.shape} / R {m.shape} are not [{n}] / [{n},6] for {n} frames")
         if a.size and (a.min() < -1 or a.max() >= n):
-            raise ValueError(f"anchor_sums_ex_batch: an anchor outside -1..{n - 1}")
+            raise ValueError(f"{who}: an anchor outside -1..{n - 1}")
         if max(h, w) > 1024:
-            raise ValueError(f"anchor_sums_ex_batch: {w}x{h} image larger than 1024 on a side")
+            raise ValueError(f"{who}: {w}x{h} image larger than 1024 on a side")
         if int(cap) != cap or not 0 <= int(cap) <= 255:
-            raise ValueError(f"anchor_sums_ex_batch: cap {cap!r} is not an integer in 0..255")
-        g = np.full(n, 1024, np.int32) if gain is None else np.ascontiguousarray(gain, dtype=np.int64).reshape(-1)
-        o = np.zeros(n, np.int32) if offset is None else np.ascontiguousarray(offset, dtype=np.int64).reshape(-1)
-        if g.size != n or o.size != n:
-            raise ValueError(f"anchor_sums_ex_batch: gain {g.shape} / offset {o.shape} are not [{n}] for {n} frames")
-        if g.min() < 256 or g.max() > 4096:
-            raise ValueError("anchor_sums_ex_batch: a gain outside 256..4096")
-        if np.abs(o).max() > 1 << 20:
-            raise ValueError("anchor_sums_ex_batch: an offset outside -2^20..2^20")
-        g, o = g.astype(np.int32), o.astype(np.int32)
-        if int(step) != step or int(step) < 1:
-            raise ValueError(f"anchor_sums_ex_batch: step {step!r} is not a positive integer")
-        step = int(step)
-        gh, gw = (h + step - 1) // step, (w + step - 1) // step
-        if blocked is not None:
-            if blocked.dtype != torch.uint8 or tuple(blocked.shape) != (n, gh, gw):
-                raise ValueError(f"anchor_sums_ex_batch: blocked {tuple(blocked.shape)} {blocked.dtype} is not uint8 [{n},{gh},{gw}]")
-            blocked = blocked.to(self.device).contiguous()
-        out = torch.empty((n, 31), dtype=torch.int64, device=self.device)
+            raise ValueError(f"{who}: cap {cap!r} is not an integer in 0..255")
+        args = (int(cap),)
+        if ex:
+            g = np.full(n, 1024, np.int32) if gain is None else np.ascontiguousarray(gain, dtype=np.int64).reshape(-1)
+            o = np.zeros(n, np.int32) if offset is None else np.ascontiguousarray(offset, dtype=np.int64).reshape(-1)
+            if g.size != n or o.size != n:
+                raise ValueError(f"{who}: gain {g.shape} / offset {o.shape} are not [{n}] for {n} frames")
+            if g.min() < 256 or g.max() > 4096:
+                raise ValueError(f"{who}: a gain outside 256..4096")
+            if np.abs(o).max() > 1 << 20:
+                raise ValueError(f"{who}: an offset outside -2^20..2^20")
+            g, o = g.astype(np.int32), o.astype(np.int32)
+            if int(step) != step or int(step) < 1:
+                raise ValueError(f"{who}: step {step!r} is not a positive integer")
+            step = int(step)
+            gh, gw = (h + step - 1) // step, (w + step - 1) // step
+            if blocked is not None:
+                if blocked.dtype != torch.uint8 or tuple(blocked.shape) != (n, gh, gw):
+                    raise ValueError(f"{who}: blocked {tuple(blocked.shape)} {blocked.dtype} is not uint8 [{n},{gh},{gw}]")
+                blocked = blocked.to(self.device).contiguous()
+            args = (g.ctypes.data, o.ctypes.data, int(cap), _dev_ptr(blocked) if blocked is not None else None, step, gh, gw)
+        out = torch.empty((n, 31 if ex else 17), dtype=torch.int64, device=self.device)
         self.use_torch_stream()
-        _check(self.lib.vstab_anchor_sums_ex_batch(self.handle, _dev_ptr(gray), n, h, w, a.ctypes.data, m.ctypes.data, g.ctypes.data,
-                                                   o.ctypes.data, int(cap), _dev_ptr(blocked) if blocked is not None else None, step,
-                                                   gh, gw, _dev_ptr(out)), "vstab_anchor_sums_ex_batch")
+        _check(getattr(self.lib, "vstab_" + who)(self.handle, _dev_ptr(gray), n, h, w, a.ctypes.data, m.ctypes.data, *args, _dev_ptr(out)),
+               "vstab_" + who)
         return out.cpu().numpy()
 
     # ------------------------------------------------------------------ mesh warp
