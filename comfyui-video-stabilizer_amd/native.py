@@ -315,6 +315,44 @@ def load_library():
     return _lib
 
 
+def _check(rc: int, what: str) -> None:
+    if rc != 0:
+        msg = load_library().vstab_last_error()
+        raise VstabError(f"{what} failed ({rc}): {msg.decode('utf-8', 'replace') if msg else 'unknown error'}")
+
+
+def _host_arg(full, v):
+    """One argument of vstab_<...> as ctypes takes it: an array as its host address, None, ctypes objects and Python scalars
+    as they are.  The caller hands over the array itself, so it is referenced for the whole call."""
+    if isinstance(v, np.ndarray):
+        if not v.flags.c_contiguous:
+            raise VstabError(f"{full}: an array argument of shape {v.shape} is not contiguous")
+        return v.ctypes.data
+    return v
+
+
+def _host_call(name, *args):
+    """vstab_<name>(*args) for the entry points that take no context: Context._call without handle and stream."""
+    full = "vstab_" + name
+    _check(getattr(load_library(), full)(*[_host_arg(full, v) for v in args]), full)
+
+
+def _int_in(who, name, v, lo, hi, span=None):
+    """v as an int if it is an integer (a bool is not one) in lo..hi, else a ValueError; span: the range as the text spells it."""
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError(f"{who}: {name}={v!r} is not an integer in {span or f'{lo}..{hi}'}")
+    return int(v)
+
+
+def _shot_sequence(seq, n, refusal, shots=None):
+    """seq -> contiguous i32 [n] if it is a non-decreasing sequence of n integers (in 0..shots-1 where `shots` is given),
+    else ValueError(refusal)."""
+    s = np.ascontiguousarray(seq, dtype=np.int32).reshape(-1)
+    if s.shape[0] != n or (np.diff(s.astype(np.int64)) < 0).any() or (shots is not None and (s.min() < 0 or s.max() >= shots)):
+        raise ValueError(refusal)
+    return s
+
+
 HOST_OPS = {"sqrt": 0, "atan2": 1, "log": 2, "exp": 3, "cos": 4, "sin": 5}
 
 
@@ -323,8 +361,7 @@ def host_math(op: str, a, b=None) -> np.ndarray:
     a = np.ascontiguousarray(a, dtype=np.float64)
     out = np.empty_like(a)
     bb = np.ascontiguousarray(b, dtype=np.float64) if b is not None else None
-    rc = load_library().vstab_host_math(HOST_OPS[op], a.ctypes.data, bb.ctypes.data if bb is not None else None, a.size, out.ctypes.data)
-    _check(rc, "vstab_host_math")
+    _host_call("host_math", HOST_OPS[op], a, bb, a.size, out)
     return out
 
 
@@ -338,16 +375,13 @@ def transitions_to_params(work_mats, base_mode: str, source_size=None, working_s
     count = m.shape[0]
     full = np.empty((count, 9), np.float32)
     params = np.empty((count, PARAM_COUNT[base_mode]), np.float64)
+    up = down = None
     if working_size is not None:
         sx = working_size[0] / float(source_size[0])
         sy = working_size[1] / float(source_size[1])
         up = np.array([1.0 / sx, 1.0 / sy, 1.0], np.float64)
         down = np.array([sx, sy, 1.0], np.float64)
-        up_p, down_p = up.ctypes.data, down.ctypes.data
-    else:
-        up_p = down_p = None
-    _check(load_library().vstab_transitions_to_params(m.ctypes.data, count, MODES[base_mode], up_p, down_p, full.ctypes.data,
-                                                      params.ctypes.data), "vstab_transitions_to_params")
+    _host_call("transitions_to_params", m, count, MODES[base_mode], up, down, full, params)
     return full.reshape(count, 3, 3), params
 
 
@@ -355,8 +389,7 @@ def params_to_matrices(params, base_mode: str) -> np.ndarray:
     """_params_to_matrix for a clip (vstab_params_to_matrices): f64 [N,K] -> f32 [N,3,3]."""
     p = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, PARAM_COUNT[base_mode])
     out = np.empty((p.shape[0], 3, 3), np.float32)
-    _check(load_library().vstab_params_to_matrices(p.ctypes.data, p.shape[0], MODES[base_mode], out.ctypes.data),
-           "vstab_params_to_matrices")
+    _host_call("params_to_matrices", p, p.shape[0], MODES[base_mode], out)
     return out
 
 
@@ -365,8 +398,7 @@ def bounding_boxes(matrices, width: int, height: int):
     m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(-1, 9)
     mins = np.empty((m.shape[0], 2), np.float64)
     maxs = np.empty((m.shape[0], 2), np.float64)
-    _check(load_library().vstab_bounding_boxes(m.ctypes.data, m.shape[0], float(width), float(height), mins.ctypes.data,
-                                               maxs.ctypes.data), "vstab_bounding_boxes")
+    _host_call("bounding_boxes", m, m.shape[0], float(width), float(height), mins, maxs)
     return mins, maxs
 
 
@@ -377,24 +409,12 @@ def blur_sample_matrices(matrices64, first: int, count: int, blur: float, sample
     ts = np.ascontiguousarray(np.linspace(0.0, float(blur), int(samples), dtype=np.float64))
     per_frame = 1 if m.shape[0] <= 1 else int(samples)
     out = np.zeros((int(count), per_frame, 3, 3), np.float32)
-    rc = load_library().vstab_blur_sample_matrices(m.ctypes.data, m.shape[0], int(first), int(count), ts.ctypes.data, int(samples),
-                                                   out.ctypes.data)
-    _check(rc, "vstab_blur_sample_matrices")
+    _host_call("blur_sample_matrices", m, m.shape[0], int(first), int(count), ts, int(samples), out)
     return out
-
-
-def _check(rc: int, what: str) -> None:
-    if rc != 0:
-        msg = load_library().vstab_last_error()
-        raise VstabError(f"{what} failed ({rc}): {msg.decode('utf-8', 'replace') if msg else 'unknown error'}")
 
 
 def _coded_transfers():
     return os.environ.get("VSTAB_XFER_CODED", "1") not in ("0", "false", "False")
-
-
-def _dev_ptr(t) -> int:
-    return int(t.data_ptr())
 
 
 class Context:
@@ -436,18 +456,45 @@ class Context:
             s = self._side_stream = self.torch.cuda.Stream(device=self.device)
         return s
 
+    def _call(self, name, *args, stream=True, check=True):
+        """The one path into the library: vstab_<name>(handle, *args), after use_torch_stream() unless stream=False (an entry
+        point that launches nothing, or whose caller has just set the stream), the status handed to _check (check=False: the
+        value is returned as it is, for the entry point that returns an address and the query that may fail).  A tensor goes
+        as its device address and an array as its host address: callers pass the object, not its address, so every buffer
+        is referenced for the whole call.  None, ctypes objects and Python scalars go as they are.  A tensor or array that is
+        not contiguous, or a tensor on another device, is refused here whatever the method checked before."""
+        full = "vstab_" + name
+        fn = getattr(self.lib, full)
+        if stream:
+            self.use_torch_stream()
+        tensor = self.torch.Tensor
+        converted = [self.handle]
+        for v in args:
+            if v is None or type(v) is int or type(v) is float:     # (most arguments: sizes and flags)
+                converted.append(v)
+            elif isinstance(v, tensor):
+                if v.device != self.device or not v.is_contiguous():
+                    raise VstabError(f"{full}: a tensor argument of shape {tuple(v.shape)} on {v.device} is not contiguous on {self.device}")
+                converted.append(v.data_ptr())
+            else:
+                converted.append(_host_arg(full, v))
+        rc = fn(*converted)
+        if check:
+            _check(rc, full)
+        return rc
+
     def use_torch_stream(self) -> None:
         stream = self.torch.cuda.current_stream(self.device)
-        _check(self.lib.vstab_set_stream(self.handle, C.c_void_p(stream.cuda_stream)), "vstab_set_stream")
+        self._call("set_stream", C.c_void_p(stream.cuda_stream), stream=False)
 
     def synchronize(self) -> None:
-        _check(self.lib.vstab_synchronize(self.handle), "vstab_synchronize")
+        self._call("synchronize", stream=False)
 
     def set_timing(self, enabled: bool, detail: bool = False, warp_only: bool = False) -> None:
         """detail: also bracket the stages inside a DIS call (a measurement pass of its own: see vstab.h).
         warp_only: events around the warp launches only (what a timed loop keeps: an event pair costs the stream ~10 us)."""
         level = 0 if not enabled else (3 if warp_only else (2 if detail else 1))
-        _check(self.lib.vstab_set_timing(self.handle, level), "vstab_set_timing")
+        self._call("set_timing", level, stream=False)
 
     def dis_stage_ms(self) -> Dict[str, Any]:
         """Milliseconds of the stages of the last DIS call under set_timing(True, detail=True):
@@ -455,7 +502,7 @@ class Context:
         pyramid index (2 = the finest of the default configuration)."""
         def ms(kind):
             out = C.c_float()
-            return float(out.value) if self.lib.vstab_last_kernel_ms(self.handle, kind.encode(), C.byref(out)) == 0 else None
+            return float(out.value) if self._call("last_kernel_ms", kind.encode(), C.byref(out), stream=False, check=False) == 0 else None
 
         res: Dict[str, Any] = {"prep": ms("dis_prep"), "pis4": {}, "level": {}, "final": ms("dis_final")}
         for lvl in range(16):
@@ -471,13 +518,13 @@ class Context:
 
     def last_kernel_ms(self, kind: str) -> float:
         out = C.c_float()
-        _check(self.lib.vstab_last_kernel_ms(self.handle, kind.encode(), C.byref(out)), "vstab_last_kernel_ms")
+        self._call("last_kernel_ms", kind.encode(), C.byref(out), stream=False)
         return float(out.value)
 
     def kernel_ms_stats(self, kind: str):
         """(total ms, launches) of all calls of `kind` since set_timing(True)."""
         total, launches = C.c_double(), C.c_int()
-        _check(self.lib.vstab_kernel_ms_stats(self.handle, kind.encode(), C.byref(total), C.byref(launches)), "vstab_kernel_ms_stats")
+        self._call("kernel_ms_stats", kind.encode(), C.byref(total), C.byref(launches), stream=False)
         return float(total.value), int(launches.value)
 
     # ------------------------------------------------------------------ helpers
@@ -491,6 +538,31 @@ class Context:
             frames = frames.to(self.device, non_blocking=True)
         return frames.contiguous()
 
+    def _frames3(self, who, frames):
+        """The frame intake of the passes that move or convert their input: frames [N,H,W,3] (device or host, any float
+        type) -> (contiguous f32 device tensor, n, h, w); anything but three channels is refused."""
+        src = self._as_device_frames(frames)
+        n, h, w, ch = src.shape
+        if ch != 3:
+            raise VstabError(f"{who} expects 3-channel frames, got {ch}")
+        return src, n, h, w
+
+    def _tensor(self, who, name, t, dtype, *, shape=None, optional=False, exc=ValueError, text=None):
+        """The strict check of the passes that refuse what they are not handed ready: `t` is a contiguous `dtype` tensor on
+        this device (and of `shape`, where given), or None where optional.  exc: the class this caller raises; text: the
+        caller's own refusal where it is not the common one."""
+        if t is None and optional:
+            return
+        torch = self.torch
+        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == self.device and t.is_contiguous()):
+            raise exc(text or f"{who}: {name} must be a contiguous {str(dtype).replace('torch.', '')} tensor on {self.device}")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise exc(text or f"{who}: {name} of shape {tuple(t.shape)} is not {tuple(shape)}")
+
+    def _new(self, shape, dtype, want=True):
+        """A fresh device tensor for the library to write, or None (a NULL pointer: the output is not wanted)."""
+        return self.torch.empty(tuple(shape), dtype=dtype, device=self.device) if want else None
+
     # ------------------------------------------------------------------ node-boundary transfers
     def upload(self, host_tensor):
         """CPU tensor (pageable) -> new device tensor through the library's pinned ring.  float32 tensors take
@@ -499,14 +571,14 @@ class Context:
         `last_upload_coded` = (chunks that crossed as bytes, chunks) of the most recent call."""
         torch = self.torch
         src = host_tensor.contiguous()
-        dst = torch.empty(src.shape, dtype=src.dtype, device=self.device)
-        self.use_torch_stream()
+        dst = self._new(src.shape, src.dtype)
+        host = C.c_void_p(src.data_ptr())   # (a torch tensor in host memory: `src` holds it for the call)
         if src.dtype == torch.float32 and _coded_transfers():
             coded = C.c_size_t(0)
-            _check(self.lib.vstab_upload_f32_coded(self.handle, src.data_ptr(), _dev_ptr(dst), src.numel(), C.byref(coded)), "vstab_upload_f32_coded")
+            self._call("upload_f32_coded", host, dst, src.numel(), C.byref(coded))
             self.last_upload_coded = (int(coded.value), -(-src.numel() // (32 << 20)))
         else:
-            _check(self.lib.vstab_upload(self.handle, src.data_ptr(), _dev_ptr(dst), src.numel() * src.element_size()), "vstab_upload")
+            self._call("upload", host, dst, src.numel() * src.element_size())
             self.last_upload_coded = (0, -(-src.numel() // (32 << 20)))
         return dst
 
@@ -517,9 +589,8 @@ class Context:
         src = host_tensor.contiguous()
         if src.dtype != torch.uint8 or src.device.type != "cpu":
             raise VstabError("upload_u8_as_f32: a uint8 CPU tensor is required")
-        dst = torch.empty(src.shape, dtype=torch.float32, device=self.device)
-        self.use_torch_stream()
-        _check(self.lib.vstab_upload_u8_as_f32(self.handle, src.data_ptr(), _dev_ptr(dst), src.numel()), "vstab_upload_u8_as_f32")
+        dst = self._new(src.shape, torch.float32)
+        self._call("upload_u8_as_f32", C.c_void_p(src.data_ptr()), dst, src.numel())
         return dst
 
     def download(self, device_tensor, mask=False, levels=1):
@@ -530,38 +601,38 @@ class Context:
         torch = self.torch
         src = device_tensor.contiguous()
         dst = torch.empty(src.shape, dtype=src.dtype)
-        self.use_torch_stream()
+        host = C.c_void_p(dst.data_ptr())   # (a torch tensor in host memory: `dst` holds it for the call)
         if mask and src.dtype == torch.float32 and _coded_transfers():
             coded = C.c_int(0)
-            _check(self.lib.vstab_download_mask_levels(self.handle, _dev_ptr(src), dst.data_ptr(), src.numel(), max(1, min(255, int(levels))),
-                                                       C.byref(coded)), "vstab_download_mask_levels")
+            self._call("download_mask_levels", src, host, src.numel(), max(1, min(255, int(levels))), C.byref(coded))
             self.last_download_coded = bool(coded.value)
         else:
-            _check(self.lib.vstab_download(self.handle, _dev_ptr(src), dst.data_ptr(), src.numel() * src.element_size()), "vstab_download")
+            self._call("download", src, host, src.numel() * src.element_size())
             self.last_download_coded = False
         return dst
 
     # ------------------------------------------------------------------ warp
+    def _warp_out(self, n, out_size, border, want_mask, out=None, out_mask=None):
+        """The output side every warp prepares alike: the sizes, the border colour and the dst / mask tensors (`out` /
+        `out_mask` are taken instead of fresh ones where given).  -> ((out_h, out_w), border f32 [3], dst, mask | None)"""
+        f32 = self.torch.float32
+        out_w, out_h = int(out_size[0]), int(out_size[1])
+        b = np.ascontiguousarray(border, dtype=np.float32).reshape(3)
+        dst = out if out is not None else self._new((n, out_h, out_w, 3), f32)
+        mask = out_mask if want_mask and out_mask is not None else self._new((n, out_h, out_w), f32, want_mask)
+        return (out_h, out_w), b, dst, mask
+
     def _warp_io(self, who, frames, out_size, border, want_mask, want_count, out=None, out_mask=None, counts=None):
         """What warp_batch, warp_batch_planned and mesh_warp_batch prepare alike: the source on the device, the sizes, the border colour and the
         dst / mask / counts tensors (`out` / `out_mask` / `counts` are taken instead of fresh ones where given and fitting).
         -> (src, (n, sh, sw), (out_h, out_w), border f32 [3], dst, mask | None, counts | None)"""
-        torch = self.torch
-        src = self._as_device_frames(frames)
-        n, sh, sw, ch = src.shape
-        if ch != 3:
-            raise VstabError(f"{who} expects 3-channel frames, got {ch}")
-        out_w, out_h = int(out_size[0]), int(out_size[1])
-        b = np.ascontiguousarray(border, dtype=np.float32).reshape(3)
-        dst = out if out is not None else torch.empty((n, out_h, out_w, 3), dtype=torch.float32, device=self.device)
-        mask = None
-        if want_mask:
-            mask = out_mask if out_mask is not None else torch.empty((n, out_h, out_w), dtype=torch.float32, device=self.device)
+        src, n, sh, sw = self._frames3(who, frames)
+        out_hw, b, dst, mask = self._warp_out(n, out_size, border, want_mask, out, out_mask)
         if not (want_count and want_mask):
             counts = None
         elif counts is None or counts.shape[0] != n:
-            counts = torch.empty((n,), dtype=torch.int32, device=self.device)
-        return src, (n, sh, sw), (out_h, out_w), b, dst, mask, counts
+            counts = self._new((n,), self.torch.int32)
+        return src, (n, sh, sw), out_hw, b, dst, mask, counts
 
     def warp_batch(self, frames, matrices, out_size, interp="bilinear", border=(0.0, 0.0, 0.0),
                    subpix=None, want_mask=True, want_count=False, out=None, out_mask=None):
@@ -569,15 +640,7 @@ class Context:
         src, (n, sh, sw), (out_h, out_w), b, dst, mask, counts = self._warp_io(
             "warp_batch", frames, out_size, border, want_mask, want_count, out, out_mask)
         m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(n, 9)
-        self.use_torch_stream()
-        _check(
-            self.lib.vstab_warp_batch(
-                self.handle, _dev_ptr(src), n, sh, sw, m.ctypes.data, out_h, out_w, INTERP[interp], b.ctypes.data,
-                SUBPIX[subpix or DEFAULT_SUBPIX], _dev_ptr(dst), _dev_ptr(mask) if mask is not None else None,
-                _dev_ptr(counts) if counts is not None else None,
-            ),
-            "vstab_warp_batch",
-        )
+        self._call("warp_batch", src, n, sh, sw, m, out_h, out_w, INTERP[interp], b, SUBPIX[subpix or DEFAULT_SUBPIX], dst, mask, counts)
         if counts is not None and out is None:
             counts._vstab_fetch = lambda n=n: self.last_pad_counts(n)   # valid until the next warp with counts of this context
         return dst, mask, counts
@@ -586,31 +649,15 @@ class Context:
                         border=(0.0, 0.0, 0.0), subpix=None, want_mask=True, out=None, out_mask=None, clip_first=0):
         """frames = frames [clip_first, clip_first + n) of the clip whose motion matrices are `matrices64` [total,3,3]
         (total == n and clip_first == 0 for a whole clip; a shard passes the replicated table of the whole clip)."""
-        torch = self.torch
-        src = self._as_device_frames(frames)
-        n, sh, sw, ch = src.shape
-        if ch != 3:
-            raise VstabError(f"warp_blur_batch expects 3-channel frames, got {ch}")
-        out_w, out_h = int(out_size[0]), int(out_size[1])
+        src, n, sh, sw = self._frames3("warp_blur_batch", frames)
         m = np.ascontiguousarray(matrices64, dtype=np.float64).reshape(-1, 9)
         total = m.shape[0]
         if clip_first < 0 or clip_first + n > total:
             raise VstabError(f"warp_blur_batch: frames [{clip_first}, {clip_first + n}) outside a clip of {total} matrices")
         ts = np.ascontiguousarray(np.linspace(0.0, float(blur), int(samples), dtype=np.float64))
-        b = np.ascontiguousarray(border, dtype=np.float32).reshape(3)
-        dst = out if out is not None else torch.empty((n, out_h, out_w, 3), dtype=torch.float32, device=self.device)
-        mask = None
-        if want_mask:
-            mask = out_mask if out_mask is not None else torch.empty((n, out_h, out_w), dtype=torch.float32, device=self.device)
-        self.use_torch_stream()
-        _check(
-            self.lib.vstab_warp_blur_clip_batch(
-                self.handle, _dev_ptr(src), n, sh, sw, m.ctypes.data, total, int(clip_first), ts.ctypes.data, int(samples),
-                out_h, out_w, INTERP[interp], b.ctypes.data, SUBPIX[subpix or DEFAULT_SUBPIX], _dev_ptr(dst),
-                _dev_ptr(mask) if mask is not None else None,
-            ),
-            "vstab_warp_blur_clip_batch",
-        )
+        (out_h, out_w), b, dst, mask = self._warp_out(n, out_size, border, want_mask, out, out_mask)
+        self._call("warp_blur_clip_batch", src, n, sh, sw, m, total, int(clip_first), ts, int(samples), out_h, out_w, INTERP[interp], b,
+                   SUBPIX[subpix or DEFAULT_SUBPIX], dst, mask)
         return dst, mask
 
     # ------------------------------------------------------------------ estimation
@@ -618,45 +665,37 @@ class Context:
         """frames [N,H,W,3] f32 -> gray u8 [N,work_h,work_w] (work_size=(w,h) or None for full size).
         want_range: also the per-frame maximum sample (device f32 [N], NaN-propagating) from the same pass."""
         torch = self.torch
-        src = self._as_device_frames(frames)
-        n, sh, sw, ch = src.shape
-        if ch != 3:
-            raise VstabError(f"gray_downscale expects 3-channel frames, got {ch}")
+        src, n, sh, sw = self._frames3("gray_downscale", frames)
         ww, wh = (sw, sh) if work_size is None else (int(work_size[0]), int(work_size[1]))
-        gray = torch.empty((n, wh, ww), dtype=torch.uint8, device=self.device)
-        self.use_torch_stream()
+        gray = self._new((n, wh, ww), torch.uint8)
         if want_range:
-            peaks = torch.empty((n,), dtype=torch.float32, device=self.device)
-            _check(self.lib.vstab_gray_downscale_range(self.handle, _dev_ptr(src), n, sh, sw, wh, ww, _dev_ptr(gray), _dev_ptr(peaks)),
-                   "vstab_gray_downscale_range")
+            peaks = self._new((n,), torch.float32)
+            self._call("gray_downscale_range", src, n, sh, sw, wh, ww, gray, peaks)
             # the host's copy needs no transfer: the kernel mirrors the maxima into coherent host memory and this fetch waits
             # for that kernel alone (host_math.apply_value_range uses it; valid until the next range pass of this context)
             peaks._vstab_fetch = lambda n=n: self.last_frame_peaks(n)
             return gray, peaks
-        _check(self.lib.vstab_gray_downscale(self.handle, _dev_ptr(src), n, sh, sw, wh, ww, _dev_ptr(gray)),
-               "vstab_gray_downscale")
+        self._call("gray_downscale", src, n, sh, sw, wh, ww, gray)
         return gray
 
     def last_pad_counts(self, n: int) -> np.ndarray:
         """Host copy of the padded-pixel counts of the latest warp_batch / warp_batch_planned(want_count=True) over n frames."""
         out = np.empty((int(n),), np.uint32)
-        _check(self.lib.vstab_last_pad_counts(self.handle, int(n), out.ctypes.data), "vstab_last_pad_counts")
+        self._call("last_pad_counts", int(n), out, stream=False)
         return out.astype(np.int64)
 
     def last_frame_peaks(self, n: int) -> np.ndarray:
         """Host copy of the per-frame maxima of the latest gray_downscale(..., want_range=True) over n frames."""
         out = np.empty((int(n),), np.float32)
-        _check(self.lib.vstab_last_frame_peaks(self.handle, int(n), out.ctypes.data), "vstab_last_frame_peaks")
+        self._call("last_frame_peaks", int(n), out, stream=False)
         return out
 
     def frame_range(self, frames):
         """Per-frame maximum sample of frames [N,H,W,3] f32 on the device (NaN-propagating) -> device f32 [N]."""
-        torch = self.torch
         src = self._as_device_frames(frames)
         n, sh, sw, ch = src.shape
-        peaks = torch.empty((n,), dtype=torch.float32, device=self.device)
-        self.use_torch_stream()
-        _check(self.lib.vstab_frame_range(self.handle, _dev_ptr(src), n, sh, sw * ch // 3, _dev_ptr(peaks)), "vstab_frame_range")
+        peaks = self._new((n,), self.torch.float32)
+        self._call("frame_range", src, n, sh, sw * ch // 3, peaks)
         return peaks
 
     def apply_value_range(self, frames, peaks):
@@ -667,16 +706,19 @@ class Context:
         n, sh, sw, ch = src.shape
         out = torch.empty_like(src)
         peaks = peaks.to(device=self.device, dtype=torch.float32).contiguous()
-        self.use_torch_stream()
-        _check(self.lib.vstab_apply_value_range(self.handle, _dev_ptr(src), n, sh, sw * ch // 3, _dev_ptr(peaks), _dev_ptr(out)),
-               "vstab_apply_value_range")
+        self._call("apply_value_range", src, n, sh, sw * ch // 3, peaks, out)
         return out
+
+    def _flow_outputs(self, pairs, h, w, sample_step, want_full, want_grid):
+        """-> (flow [pairs,h,w,2] | None, grid_flow [pairs,gh,gw,2] | None) for the two dense estimators to write."""
+        gh, gw = (h + sample_step - 1) // sample_step, (w + sample_step - 1) // sample_step
+        f32 = self.torch.float32
+        return self._new((pairs, h, w, 2), f32, want_full), self._new((pairs, gh, gw, 2), f32, want_grid)
 
     def dis_flow_batch(self, gray, sample_step=8, want_full=False, want_grid=True, clip_start=True):
         """gray u8 [N,h,w] (device) -> (flow [N-1,h,w,2] | None, grid_flow [N-1,gh,gw,2] | None).
         clip_start=False: these frames are a later shard of a clip (see vstab_dis_set_clip_start)."""
-        torch = self.torch
-        _check(self.lib.vstab_dis_set_clip_start(self.handle, 1 if clip_start else 0), "vstab_dis_set_clip_start")
+        self._call("dis_set_clip_start", 1 if clip_start else 0, stream=False)
         if gray.device != self.device:
             gray = gray.to(self.device)
         gray = gray.contiguous()
@@ -684,17 +726,8 @@ class Context:
         pairs = n - 1
         if pairs < 1:
             raise VstabError("dis_flow_batch needs at least two frames")
-        gh, gw = (h + sample_step - 1) // sample_step, (w + sample_step - 1) // sample_step
-        flow = torch.empty((pairs, h, w, 2), dtype=torch.float32, device=self.device) if want_full else None
-        grid = torch.empty((pairs, gh, gw, 2), dtype=torch.float32, device=self.device) if want_grid else None
-        self.use_torch_stream()
-        _check(
-            self.lib.vstab_dis_flow_batch(
-                self.handle, _dev_ptr(gray), n, h, w, _dev_ptr(flow) if flow is not None else None,
-                _dev_ptr(grid) if grid is not None else None, int(sample_step),
-            ),
-            "vstab_dis_flow_batch",
-        )
+        flow, grid = self._flow_outputs(pairs, h, w, sample_step, want_full, want_grid)
+        self._call("dis_flow_batch", gray, n, h, w, flow, grid, int(sample_step))
         return flow, grid
 
     def tvl1_flow_batch(self, gray, params=None, sample_step=8, want_full=False, want_grid=True, want_iterations=False):
@@ -717,19 +750,9 @@ class Context:
         else:
             prm = tvl1_params(**params)
         pairs = n - 1
-        gh, gw = (h + sample_step - 1) // sample_step, (w + sample_step - 1) // sample_step
-        flow = torch.empty((pairs, h, w, 2), dtype=torch.float32, device=self.device) if want_full else None
-        grid = torch.empty((pairs, gh, gw, 2), dtype=torch.float32, device=self.device) if want_grid else None
-        iters = (torch.empty((pairs, max(prm.nscales, 1), max(prm.warps, 1)), dtype=torch.int32, device=self.device)
-                 if want_iterations else None)
-        self.use_torch_stream()
-        _check(
-            self.lib.vstab_tvl1_flow_batch(
-                self.handle, _dev_ptr(gray), n, h, w, C.byref(prm), _dev_ptr(flow) if flow is not None else None,
-                _dev_ptr(grid) if grid is not None else None, int(sample_step), _dev_ptr(iters) if iters is not None else None,
-            ),
-            "vstab_tvl1_flow_batch",
-        )
+        flow, grid = self._flow_outputs(pairs, h, w, sample_step, want_full, want_grid)
+        iters = self._new((pairs, max(prm.nscales, 1), max(prm.warps, 1)), torch.int32, want_iterations)
+        self._call("tvl1_flow_batch", gray, n, h, w, C.byref(prm), flow, grid, int(sample_step), iters)
         return flow, grid, iters
 
     def mask_block_grid(self, mask, n_frames, working_size, step, margin):
@@ -749,10 +772,8 @@ class Context:
         n_masks, sh, sw = (int(v) for v in mask.shape)
         ww, wh = (sw, sh) if working_size is None else (int(working_size[0]), int(working_size[1]))
         gh, gw = (wh + step - 1) // step, (ww + step - 1) // step
-        blocked = torch.empty((int(n_frames), gh, gw), dtype=torch.uint8, device=self.device)
-        self.use_torch_stream()
-        _check(self.lib.vstab_mask_block_grid(self.handle, _dev_ptr(mask), n_masks, int(n_frames), sh, sw, wh, ww, int(step),
-                                              int(margin), _dev_ptr(blocked)), "vstab_mask_block_grid")
+        blocked = self._new((int(n_frames), gh, gw), torch.uint8)
+        self._call("mask_block_grid", mask, n_masks, int(n_frames), sh, sw, wh, ww, int(step), int(margin), blocked)
         return blocked
 
     def pair_residual_batch(self, gray, transitions):
@@ -769,11 +790,9 @@ class Context:
         m = np.ascontiguousarray(transitions, dtype=np.float32)
         if m.size != (n - 1) * 9:
             raise ValueError(f"pair_residual_batch: transitions {m.shape} are not [{n - 1},3,3] for {n} frames")
-        sums = torch.empty((n - 1,), dtype=torch.int64, device=self.device)      # the library's u64 / u32, in torch's containers
-        inside = torch.empty((n - 1,), dtype=torch.int32, device=self.device)
-        self.use_torch_stream()
-        _check(self.lib.vstab_pair_residual_batch(self.handle, _dev_ptr(gray), n, h, w, m.ctypes.data, _dev_ptr(sums),
-                                                  _dev_ptr(inside)), "vstab_pair_residual_batch")
+        sums = self._new((n - 1,), torch.int64)      # the library's u64 / u32, in torch's containers
+        inside = self._new((n - 1,), torch.int32)
+        self._call("pair_residual_batch", gray, n, h, w, m, sums, inside)
         return sums.cpu().numpy(), inside.cpu().numpy().astype(np.int64)
 
     def anchor_sums_batch(self, gray, anchor, R, cap):
@@ -809,7 +828,7 @@ class Context:
             raise ValueError(f"{who}: an anchor outside -1..{n - 1}")
         if max(h, w) > 1024:
             raise ValueError(f"{who}: {w}x{h} image larger than 1024 on a side")
-        if int(cap) != cap or not 0 <= int(cap) <= 255:
+        if int(cap) != cap or not 0 <= int(cap) <= 255:      # (an integral float passes: not _int_in's set)
             raise ValueError(f"{who}: cap {cap!r} is not an integer in 0..255")
         args = (int(cap),)
         if ex:
@@ -822,7 +841,7 @@ class Context:
             if np.abs(o).max() > 1 << 20:
                 raise ValueError(f"{who}: an offset outside -2^20..2^20")
             g, o = g.astype(np.int32), o.astype(np.int32)
-            if int(step) != step or int(step) < 1:
+            if int(step) != step or int(step) < 1:           # (as cap)
                 raise ValueError(f"{who}: step {step!r} is not a positive integer")
             step = int(step)
             gh, gw = (h + step - 1) // step, (w + step - 1) // step
@@ -830,11 +849,9 @@ class Context:
                 if blocked.dtype != torch.uint8 or tuple(blocked.shape) != (n, gh, gw):
                     raise ValueError(f"{who}: blocked {tuple(blocked.shape)} {blocked.dtype} is not uint8 [{n},{gh},{gw}]")
                 blocked = blocked.to(self.device).contiguous()
-            args = (g.ctypes.data, o.ctypes.data, int(cap), _dev_ptr(blocked) if blocked is not None else None, step, gh, gw)
-        out = torch.empty((n, 31 if ex else 17), dtype=torch.int64, device=self.device)
-        self.use_torch_stream()
-        _check(getattr(self.lib, "vstab_" + who)(self.handle, _dev_ptr(gray), n, h, w, a.ctypes.data, m.ctypes.data, *args, _dev_ptr(out)),
-               "vstab_" + who)
+            args = (g, o, int(cap), blocked, step, gh, gw)
+        out = self._new((n, 31 if ex else 17), torch.int64)
+        self._call(who, gray, n, h, w, a, m, *args, out)
         return out.cpu().numpy()
 
     # ------------------------------------------------------------------ mesh warp
@@ -853,24 +870,26 @@ class Context:
         mw, mh = self._check_mesh("mesh_residual_batch", mw, mh)
         grid_flow, blocked, pairs, gh, gw, step, wh, ww, m = self._residual_inputs(
             "mesh_residual_batch", grid_flow, step, work_size, transitions, blocked)
-        residual = torch.empty((pairs, mh, mw, 2), dtype=torch.float32, device=self.device)
-        count = torch.empty((pairs, mh, mw), dtype=torch.int32, device=self.device)
-        self.use_torch_stream()
-        _check(self.lib.vstab_mesh_residual_batch(
-            self.handle, _dev_ptr(grid_flow), pairs, gh, gw, step, wh, ww, m.ctypes.data,
-            _dev_ptr(blocked) if blocked is not None else None, mw, mh, _dev_ptr(residual), _dev_ptr(count)),
-            "vstab_mesh_residual_batch")
+        residual = self._new((pairs, mh, mw, 2), torch.float32)
+        count = self._new((pairs, mh, mw), torch.int32)
+        self._call("mesh_residual_batch", grid_flow, pairs, gh, gw, step, wh, ww, m, blocked, mw, mh, residual, count)
         return residual, count
 
-    def _residual_inputs(self, who, grid_flow, step, work_size, transitions, blocked):
-        """What mesh_residual_batch and row_residual_batch check alike: the grid flow, its grid against the working size at
-        `step`, the transitions.  -> (grid_flow, blocked, pairs, gh, gw, step, work_h, work_w, transitions f32)"""
+    def _grid_inputs(self, who, grid_flow, step, work_size, blocked):
+        """What the passes over a flow grid check alike: the grid flow, `blocked`, the grid against the working size at `step`.
+        -> (grid_flow, blocked, pairs, gh, gw, step, work_h, work_w)"""
         if grid_flow.dtype != self.torch.float32 or grid_flow.dim() != 4 or grid_flow.shape[3] != 2:
             raise ValueError(f"{who} expects a float32 [P,gh,gw,2] tensor")
         grid_flow, blocked, pairs, gh, gw = self._fit_inputs(grid_flow, blocked)
         ww, wh, step = int(work_size[0]), int(work_size[1]), int(step)
         if step < 1 or (gh, gw) != ((wh + step - 1) // step, (ww + step - 1) // step):
             raise ValueError(f"{who}: a grid of {gw}x{gh} samples is not a {ww}x{wh} image at step {step}")
+        return grid_flow, blocked, pairs, gh, gw, step, wh, ww
+
+    def _residual_inputs(self, who, grid_flow, step, work_size, transitions, blocked):
+        """What mesh_residual_batch and row_residual_batch check alike: the grid flow, its grid against the working size at
+        `step`, the transitions.  -> (grid_flow, blocked, pairs, gh, gw, step, work_h, work_w, transitions f32)"""
+        grid_flow, blocked, pairs, gh, gw, step, wh, ww = self._grid_inputs(who, grid_flow, step, work_size, blocked)
         m = np.ascontiguousarray(transitions, dtype=np.float32)
         if m.size != pairs * 9:
             raise ValueError(f"{who}: transitions {m.shape} are not [{pairs},3,3]")
@@ -899,19 +918,11 @@ class Context:
         the entry point's own arguments, between subpix and dst (a tensor goes as its device pointer, an array as its host
         pointer); want_second: () for a forward form, (flag,) for an inverse, whose second counter i32 [N] | None is appended
         to (dst, mask, counts)."""
-        torch = self.torch
         src, (n, sh, sw), (out_h, out_w), b, dst, mask, counts = self._warp_io(name, frames, out_size, border, want_mask, want_count)
         own = own(n)
-        second = tuple(torch.empty((n,), dtype=torch.int32, device=self.device) if want else None for want in want_second)
+        second = tuple(self._new((n,), self.torch.int32, want) for want in want_second)
         m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(n, 9)
-
-        def arg(v):
-            return _dev_ptr(v) if isinstance(v, torch.Tensor) else v.ctypes.data if isinstance(v, np.ndarray) else v
-
-        self.use_torch_stream()
-        _check(getattr(self.lib, "vstab_" + name)(
-            self.handle, _dev_ptr(src), n, sh, sw, m.ctypes.data, out_h, out_w, b.ctypes.data, SUBPIX[subpix or DEFAULT_SUBPIX],
-            *(arg(v) for v in own), _dev_ptr(dst), *(arg(v) for v in (mask, counts) + second)), "vstab_" + name)
+        self._call(name, src, n, sh, sw, m, out_h, out_w, b, SUBPIX[subpix or DEFAULT_SUBPIX], *own, dst, mask, counts, *second)
         return (dst, mask, counts) + second
 
     def mesh_unwarp_batch(self, frames, matrices, out_size, offsets, border=(0.0, 0.0, 0.0), subpix=None, want_mask=True,
@@ -964,13 +975,9 @@ class Context:
         torch = self.torch
         grid_flow, blocked, pairs, gh, gw, step, wh, ww, m = self._residual_inputs(
             "row_residual_batch", grid_flow, step, work_size, transitions, blocked)
-        residual = torch.empty((pairs, gh, 2), dtype=torch.float32, device=self.device)
-        count = torch.empty((pairs, gh), dtype=torch.int32, device=self.device)
-        self.use_torch_stream()
-        _check(self.lib.vstab_row_residual_batch(
-            self.handle, _dev_ptr(grid_flow), pairs, gh, gw, step, wh, ww, m.ctypes.data,
-            _dev_ptr(blocked) if blocked is not None else None, _dev_ptr(residual), _dev_ptr(count)),
-            "vstab_row_residual_batch")
+        residual = self._new((pairs, gh, 2), torch.float32)
+        count = self._new((pairs, gh), torch.int32)
+        self._call("row_residual_batch", grid_flow, pairs, gh, gw, step, wh, ww, m, blocked, residual, count)
         return residual, count
 
     def rectify_samples_batch(self, grid_flow, step, work_size, velocity, readout, blocked=None):
@@ -981,21 +988,12 @@ class Context:
         device tensors: what points_fit_batch takes."""
         torch = self.torch
         who = "rectify_samples_batch"
-        if grid_flow.dtype != torch.float32 or grid_flow.dim() != 4 or grid_flow.shape[3] != 2:
-            raise ValueError(f"{who} expects a float32 [P,gh,gw,2] tensor")
-        grid_flow, blocked, pairs, gh, gw = self._fit_inputs(grid_flow, blocked)
-        ww, wh, step = int(work_size[0]), int(work_size[1]), int(step)
-        if step < 1 or (gh, gw) != ((wh + step - 1) // step, (ww + step - 1) // step):
-            raise ValueError(f"{who}: a grid of {gw}x{gh} samples is not a {ww}x{wh} image at step {step}")
+        grid_flow, blocked, pairs, gh, gw, step, wh, ww = self._grid_inputs(who, grid_flow, step, work_size, blocked)
         v, readout = self._rolling_inputs(who, velocity, readout, pairs + 1, null_ok=True)
-        point_pairs = torch.empty((pairs, gh * gw, 4), dtype=torch.float32, device=self.device)
-        counts = torch.empty((pairs,), dtype=torch.int32, device=self.device)
-        unsolved = torch.empty((pairs,), dtype=torch.int32, device=self.device)
-        self.use_torch_stream()
-        _check(self.lib.vstab_rectify_samples_batch(
-            self.handle, _dev_ptr(grid_flow), pairs, gh, gw, step, wh, v.ctypes.data if v is not None else None, readout,
-            _dev_ptr(blocked) if blocked is not None else None, _dev_ptr(point_pairs), _dev_ptr(counts), _dev_ptr(unsolved)),
-            "vstab_rectify_samples_batch")
+        point_pairs = self._new((pairs, gh * gw, 4), torch.float32)
+        counts = self._new((pairs,), torch.int32)
+        unsolved = self._new((pairs,), torch.int32)
+        self._call(who, grid_flow, pairs, gh, gw, step, wh, v, readout, blocked, point_pairs, counts, unsolved)
         return point_pairs, counts, unsolved
 
     def cover_extent_batch(self, matrices, src_size, out_size, offsets=None, subpix=None):
@@ -1003,7 +1001,6 @@ class Context:
         include/vstab.h): matrices f32 [N,3,3] forward, src_size / out_size (w, h), offsets f32 [N,mh,mw,2] (host or device) for
         the mesh warp's coverage or None for the plain warp's -> uint32 [N] on the host: per frame the minimum of
         e = max(|2x-(w-1)|*(h-1), |2y-(h-1)|*(w-1)) over the pixels the warp would leave uncovered, 0xFFFFFFFF if there is none."""
-        torch = self.torch
         m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(-1, 9)
         n = m.shape[0]
         sw, sh = int(src_size[0]), int(src_size[1])
@@ -1011,11 +1008,8 @@ class Context:
         mw = mh = 0
         if offsets is not None:
             offsets, mw, mh = self._mesh_offsets("cover_extent_batch", offsets, n)
-        extent = torch.empty((max(n, 1),), dtype=torch.int32, device=self.device)
-        self.use_torch_stream()
-        _check(self.lib.vstab_cover_extent_batch(
-            self.handle, m.ctypes.data, n, sh, sw, oh, ow, SUBPIX[subpix or DEFAULT_SUBPIX],
-            _dev_ptr(offsets) if offsets is not None else None, mw, mh, _dev_ptr(extent)), "vstab_cover_extent_batch")
+        extent = self._new((max(n, 1),), self.torch.int32)
+        self._call("cover_extent_batch", m, n, sh, sw, oh, ow, SUBPIX[subpix or DEFAULT_SUBPIX], offsets, mw, mh, extent)
         return extent[:n].cpu().numpy().view(np.uint32)
 
     def _fit_inputs(self, grid_flow, blocked):
@@ -1035,20 +1029,9 @@ class Context:
         blocked (u8 [P+1,gh,gw], mask_block_grid): the fit uses the samples blocked in neither frame of a pair."""
         grid_flow, blocked, pairs, gh, gw = self._fit_inputs(grid_flow, blocked)
         table = np.zeros((pairs, 3), FIT_DTYPE)
-        self.use_torch_stream()
-        if blocked is not None:
-            _check(
-                self.lib.vstab_sample_fit_batch_masked(
-                    self.handle, _dev_ptr(grid_flow), pairs, gh, gw, int(step), MODES[requested_mode], _dev_ptr(blocked),
-                    table.ctypes.data),
-                "vstab_sample_fit_batch_masked",
-            )
-            return table
-        _check(
-            self.lib.vstab_sample_fit_batch(
-                self.handle, _dev_ptr(grid_flow), pairs, gh, gw, int(step), MODES[requested_mode], table.ctypes.data),
-            "vstab_sample_fit_batch",
-        )
+        masked = () if blocked is None else (blocked,)      # the masked entry point takes it in front of the table
+        self._call("sample_fit_batch_masked" if masked else "sample_fit_batch", grid_flow, pairs, gh, gw, int(step),
+                   MODES[requested_mode], *masked, table)
         return table
 
     def sample_fit_batch_begin(self, grid_flow, step, requested_mode, blocked=None):
@@ -1056,35 +1039,29 @@ class Context:
         their download is queued; sample_fit_batch_end(pairs) collects the host table.  Work queued in between (the
         device plan, the warp) does not delay that download."""
         grid_flow, blocked, pairs, gh, gw = self._fit_inputs(grid_flow, blocked)
-        self.use_torch_stream()
-        if blocked is not None:
-            _check(self.lib.vstab_sample_fit_batch_begin_masked(self.handle, _dev_ptr(grid_flow), pairs, gh, gw, int(step),
-                                                                MODES[requested_mode], _dev_ptr(blocked)),
-                   "vstab_sample_fit_batch_begin_masked")
-        else:
-            _check(self.lib.vstab_sample_fit_batch_begin(self.handle, _dev_ptr(grid_flow), pairs, gh, gw, int(step), MODES[requested_mode]),
-                   "vstab_sample_fit_batch_begin")
+        masked = () if blocked is None else (blocked,)
+        self._call("sample_fit_batch_begin_masked" if masked else "sample_fit_batch_begin", grid_flow, pairs, gh, gw, int(step),
+                   MODES[requested_mode], *masked)
         self._fit_grid = (grid_flow, blocked)   # keep the inputs alive until the kernels have run
         return pairs
 
     def fit_records_device(self) -> int:
         """Device address of the records of the last sample_fit_batch_begin ([pairs*3] vstab_fit_record)."""
-        ptr = self.lib.vstab_fit_records_device(self.handle)
+        ptr = self._call("fit_records_device", stream=False, check=False)
         if not ptr:
             raise VstabError("fit_records_device: no fit is pending")
         return int(ptr)
 
     def sample_fit_batch_end(self, pairs):
         table = np.zeros((pairs, 3), FIT_DTYPE)
-        _check(self.lib.vstab_sample_fit_batch_end(self.handle, int(pairs), table.ctypes.data), "vstab_sample_fit_batch_end")
+        self._call("sample_fit_batch_end", int(pairs), table, stream=False)
         self._fit_grid = None
         return table
 
     # ------------------------------------------------------------------ speculative device plan (F6-F12, crop_and_pad)
     def fit_records_copy(self, dst, pairs):
         """The pending fit's device records into `dst` (device uint8 tensor of >= pairs * 3 records), stream-ordered."""
-        self.use_torch_stream()
-        _check(self.lib.vstab_fit_records_copy(self.handle, _dev_ptr(dst), int(pairs)), "vstab_fit_records_copy")
+        self._call("fit_records_copy", dst, int(pairs))
 
     def flow_plan_device(self, records_ptr, pairs, requested_mode, source_size, working_size, smooth, fps, strength, camera_lock,
                          seg_pairs=None, seg_rows=0, warp_frames=0, framing="crop_and_pad"):
@@ -1103,20 +1080,16 @@ class Context:
             up = np.array([1.0 / sx, 1.0 / sy, 1.0], np.float64)
             down = np.array([sx, sy, 1.0], np.float64)
         seg = np.ascontiguousarray(seg_pairs, np.int32) if seg_pairs is not None else None
-        self.use_torch_stream()
         if warp_frames:
             # registered right in front of the plan call, with every argument already built: the library hands the pointer to
             # THAT call's kernel only (and drops it if the call is refused), so no stale registration can outlive the tensor
-            counts = self.torch.empty((int(warp_frames),), dtype=self.torch.int32, device=self.device)
-            _check(self.lib.vstab_flow_plan_zero_counts(self.handle, _dev_ptr(counts), int(warp_frames)), "vstab_flow_plan_zero_counts")
+            counts = self._new((int(warp_frames),), self.torch.int32)
+            self._call("flow_plan_zero_counts", counts, int(warp_frames))
             self._planned_counts = counts
-        _check(self.lib.vstab_flow_plan_device(
-            self.handle, C.c_void_p(int(records_ptr)), int(pairs), MODES[requested_mode],
-            up.ctypes.data if up is not None else None, down.ctypes.data if down is not None else None,
-            float(smooth), float(fps), float(strength), 1 if camera_lock else 0, int(source_size[0]), int(source_size[1]),
-            len(seg) if seg is not None else 0, seg.ctypes.data if seg is not None else None, int(seg_rows),
-            1 if framing == "expand" else 0),
-            "vstab_flow_plan_device")
+        self._call("flow_plan_device", C.c_void_p(int(records_ptr)), int(pairs), MODES[requested_mode], up, down,
+                   float(smooth), float(fps), float(strength), 1 if camera_lock else 0, int(source_size[0]), int(source_size[1]),
+                   0 if seg is None else len(seg), seg, int(seg_rows), 1 if framing == "expand" else 0,
+                   stream=not warp_frames)      # (the registration has just set the stream)
 
     @staticmethod
     def expand_canvas(region):
@@ -1135,8 +1108,7 @@ class Context:
         path = np.zeros((frames, params), np.float64)
         target = np.zeros((frames, params), np.float64)
         region = np.zeros(4, np.float64)
-        _check(self.lib.vstab_flow_plan_result(self.handle, int(frames), final.ctypes.data, path.ctypes.data, target.ctypes.data,
-                                               region.ctypes.data), "vstab_flow_plan_result")
+        self._call("flow_plan_result", int(frames), final, path, target, region, stream=False)
         return final, path, target, region
 
     def warp_batch_planned(self, frames, first, out_size, border=(0.0, 0.0, 0.0), subpix=None, want_mask=True, want_count=False):
@@ -1147,11 +1119,8 @@ class Context:
             self._planned_counts = None
         src, (n, sh, sw), (out_h, out_w), b, dst, mask, counts = self._warp_io(
             "warp_batch_planned", frames, out_size, border, want_mask, want_count, counts=handed)
-        self.use_torch_stream()
-        _check(self.lib.vstab_warp_batch_planned(
-            self.handle, _dev_ptr(src), int(first), n, sh, sw, out_h, out_w, INTERP["bilinear"], b.ctypes.data,
-            SUBPIX[subpix or DEFAULT_SUBPIX], _dev_ptr(dst), _dev_ptr(mask) if mask is not None else None,
-            _dev_ptr(counts) if counts is not None else None), "vstab_warp_batch_planned")
+        self._call("warp_batch_planned", src, int(first), n, sh, sw, out_h, out_w, INTERP["bilinear"], b,
+                   SUBPIX[subpix or DEFAULT_SUBPIX], dst, mask, counts)
         if counts is not None:
             counts._vstab_fetch = lambda n=n: self.last_pad_counts(n)   # valid until the next warp with counts of this context
         return dst, mask, counts
@@ -1168,16 +1137,11 @@ class Context:
             raise VstabError(f"temporal_fill_batch: mask must be a contiguous float32 tensor on {self.device}")
         src, (total, sh, sw), (n, out_h, out_w, k), m, cf, _ = self._neighbour_io(
             "temporal_fill_batch", clip_frames, matrices, cand_frame, None, dst, mask, subpix, accepts_exact=True)
-        filled_from = torch.empty((n, out_h, out_w), dtype=torch.int8, device=self.device) if want_filled_from else None
-        fill_count = torch.empty((n,), dtype=torch.int32, device=self.device) if want_counts else None
-        pad_count = torch.empty((n,), dtype=torch.int32, device=self.device) if want_counts else None
-        self.use_torch_stream()
-        _check(self.lib.vstab_temporal_fill_batch(
-            self.handle, _dev_ptr(src), total, sh, sw, int(first), n, m.ctypes.data, cf.ctypes.data, k, out_h, out_w,
-            INTERP[interp], SUBPIX[subpix or DEFAULT_SUBPIX], _dev_ptr(dst), _dev_ptr(mask),
-            _dev_ptr(filled_from) if filled_from is not None else None,
-            _dev_ptr(fill_count) if fill_count is not None else None,
-            _dev_ptr(pad_count) if pad_count is not None else None), "vstab_temporal_fill_batch")
+        filled_from = self._new((n, out_h, out_w), torch.int8, want_filled_from)
+        fill_count = self._new((n,), torch.int32, want_counts)
+        pad_count = self._new((n,), torch.int32, want_counts)
+        self._call("temporal_fill_batch", src, total, sh, sw, int(first), n, m, cf, k, out_h, out_w, INTERP[interp],
+                   SUBPIX[subpix or DEFAULT_SUBPIX], dst, mask, filled_from, fill_count, pad_count)
         return filled_from, fill_count, pad_count
 
     def _neighbour_io(self, who, clip_frames, matrices, cand_frame, own_matrices, dst, mask, subpix, accepts_exact=False):
@@ -1185,17 +1149,11 @@ class Context:
         checked in one place.  own_matrices None: the entry takes none; mask None: the entry's own affair; accepts_exact: the
         entry (the plain fill) has the 'exact' sub-pixel mode besides 'q5'."""
         torch = self.torch
-        src = self._as_device_frames(clip_frames)
-        total, sh, sw, ch = src.shape
-        if ch != 3:
-            raise VstabError(f"{who} expects 3-channel frames, got {ch}")
+        src, total, sh, sw = self._frames3(who, clip_frames)
         if not accepts_exact and (subpix or DEFAULT_SUBPIX) != "q5":
             raise VstabError(f"{who}: sub-pixel mode {(subpix or DEFAULT_SUBPIX)!r} is not supported; the entry is 'q5' only")
-        for name, t in (("dst", dst), ("mask", mask)):
-            if t is None and name == "mask":
-                continue
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()):
-                raise VstabError(f"{who}: {name} must be a contiguous float32 tensor on {self.device}")
+        self._tensor(who, "dst", dst, torch.float32, exc=VstabError)
+        self._tensor(who, "mask", mask, torch.float32, optional=True, exc=VstabError)
         if dst.dim() != 4 or dst.shape[3] != 3 or (mask is not None and mask.numel() * 3 != dst.numel()):
             raise VstabError(f"{who}: dst {tuple(dst.shape)} / mask {tuple(mask.shape) if mask is not None else None} do not match")
         n, out_h, out_w = int(dst.shape[0]), int(dst.shape[1]), int(dst.shape[2])
@@ -1220,11 +1178,9 @@ class Context:
         -> sums i64 [n,K,7] device tensor: count, own r g b, candidate r g b (see temporal_fill.gains_from_sums)."""
         src, (total, sh, sw), (n, out_h, out_w, k), m, cf, own = self._neighbour_io(
             "fill_gain_sums", clip_frames, matrices, cand_frame, own_matrices, dst, None, subpix)
-        sums = self.torch.empty((n, k, 7), dtype=self.torch.int64, device=self.device)
-        self.use_torch_stream()
-        _check(self.lib.vstab_fill_gain_sums(
-            self.handle, _dev_ptr(src), total, sh, sw, int(first), n, m.ctypes.data, cf.ctypes.data, k, own.ctypes.data, out_h,
-            out_w, INTERP[interp], SUBPIX["q5"], _dev_ptr(dst), _dev_ptr(sums)), "vstab_fill_gain_sums")
+        sums = self._new((n, k, 7), self.torch.int64)
+        self._call("fill_gain_sums", src, total, sh, sw, int(first), n, m, cf, k, own, out_h, out_w, INTERP[interp], SUBPIX["q5"],
+                   dst, sums)
         return sums
 
     def temporal_fill_blend_batch(self, clip_frames, matrices, cand_frame, own_matrices, gains, dst, mask, feather_px=0, first=0,
@@ -1237,20 +1193,16 @@ class Context:
         torch = self.torch
         src, (total, sh, sw), (n, out_h, out_w, k), m, cf, own = self._neighbour_io(
             "temporal_fill_blend_batch", clip_frames, matrices, cand_frame, own_matrices, dst, mask, subpix)
-        if mask is None:
+        if mask is None:     # (a text of its own, without the device: not _tensor's)
             raise VstabError("temporal_fill_blend_batch: mask must be a contiguous float32 tensor")
         g = np.ascontiguousarray(gains, dtype=np.float32)
         if g.size != n * k * 3:
             raise VstabError(f"temporal_fill_blend_batch: gains {g.shape} are not [n={n}, K={k}, 3]")
         feather_px = int(feather_px)
-        filled_from = torch.empty((n, out_h, out_w), dtype=torch.int8, device=self.device) if want_filled_from else None
-        counts = [torch.empty((n,), dtype=torch.int32, device=self.device) if want_counts else None for _ in range(3)]
-        self.use_torch_stream()
-        _check(self.lib.vstab_temporal_fill_blend_batch(
-            self.handle, _dev_ptr(src), total, sh, sw, int(first), n, m.ctypes.data, cf.ctypes.data, k, own.ctypes.data,
-            g.ctypes.data, feather_px, out_h, out_w, INTERP[interp], SUBPIX["q5"], _dev_ptr(dst), _dev_ptr(mask),
-            _dev_ptr(filled_from) if filled_from is not None else None,
-            *[_dev_ptr(c) if c is not None else None for c in counts]), "vstab_temporal_fill_blend_batch")
+        filled_from = self._new((n, out_h, out_w), torch.int8, want_filled_from)
+        counts = [self._new((n,), torch.int32, want_counts) for _ in range(3)]
+        self._call("temporal_fill_blend_batch", src, total, sh, sw, int(first), n, m, cf, k, own, g, feather_px, out_h, out_w,
+                   INTERP[interp], SUBPIX["q5"], dst, mask, filled_from, *counts)
         return filled_from, counts[0], counts[1], counts[2]
 
     # ------------------------------------------------------------------ spatial fill
@@ -1260,9 +1212,8 @@ class Context:
         chunk_frames: frames per pass over the workspace, 0 = automatic; the result does not depend on it.
         -> (hole_count i32 [n] | None, fill_count i32 [n] | None), device tensors."""
         torch = self.torch
-        for name, t in (("dst", dst), ("mask", mask)):
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()):
-                raise VstabError(f"spatial_fill_batch: {name} must be a contiguous float32 tensor on {self.device}")
+        self._tensor("spatial_fill_batch", "dst", dst, torch.float32, exc=VstabError)
+        self._tensor("spatial_fill_batch", "mask", mask, torch.float32, exc=VstabError)
         if dst.dim() != 4 or dst.shape[3] != 3 or mask.dim() not in (3, 4) or mask.numel() * 3 != dst.numel() \
                 or tuple(mask.shape[:3]) != tuple(dst.shape[:3]):
             raise VstabError(f"spatial_fill_batch: dst {tuple(dst.shape)} / mask {tuple(mask.shape)} do not match")
@@ -1270,15 +1221,11 @@ class Context:
         if chunk_frames < 0:
             raise VstabError(f"spatial_fill_batch: chunk_frames={chunk_frames} is negative")
         n, h, w = int(dst.shape[0]), int(dst.shape[1]), int(dst.shape[2])
-        hole_count = torch.empty((n,), dtype=torch.int32, device=self.device) if want_counts else None
-        fill_count = torch.empty((n,), dtype=torch.int32, device=self.device) if want_counts else None
+        hole_count = self._new((n,), torch.int32, want_counts)
+        fill_count = self._new((n,), torch.int32, want_counts)
         if n == 0 or h == 0 or w == 0:
             return hole_count, fill_count
-        self.use_torch_stream()
-        _check(self.lib.vstab_spatial_fill_batch(
-            self.handle, _dev_ptr(dst), _dev_ptr(mask), n, h, w, chunk_frames,
-            _dev_ptr(hole_count) if hole_count is not None else None,
-            _dev_ptr(fill_count) if fill_count is not None else None), "vstab_spatial_fill_batch")
+        self._call("spatial_fill_batch", dst, mask, n, h, w, chunk_frames, hole_count, fill_count)
         return hole_count, fill_count
 
     # ------------------------------------------------------------------ stability report
@@ -1289,10 +1236,7 @@ class Context:
         -> (sse i64 [n], count i32 [n]), device tensors."""
         torch = self.torch
         for name, t in (("a", a), ("b", b), ("mask_a", mask_a), ("mask_b", mask_b)):
-            if t is None and name.startswith("mask"):
-                continue
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()):
-                raise ValueError(f"frame_sse_batch: {name} must be a contiguous float32 tensor on {self.device}")
+            self._tensor("frame_sse_batch", name, t, torch.float32, optional=name.startswith("mask"))
         if a.dim() != 4 or a.shape[3] != 3:
             raise ValueError(f"frame_sse_batch: a of shape {tuple(a.shape)} is not [n,h,w,3]")
         if tuple(b.shape) != tuple(a.shape):
@@ -1302,20 +1246,15 @@ class Context:
                 raise ValueError(f"frame_sse_batch: {name} of shape {tuple(t.shape)} does not match the frames: expected "
                                  f"{tuple(a.shape[:3])}")
         n, h, w = int(a.shape[0]), int(a.shape[1]), int(a.shape[2])
-        sse = torch.empty((n,), dtype=torch.int64, device=self.device)
-        count = torch.empty((n,), dtype=torch.int32, device=self.device)
-        self.use_torch_stream()
-        _check(self.lib.vstab_frame_sse_batch(
-            self.handle, _dev_ptr(a), _dev_ptr(mask_a) if mask_a is not None else None, _dev_ptr(b),
-            _dev_ptr(mask_b) if mask_b is not None else None, n, h, w, _dev_ptr(sse), _dev_ptr(count)), "vstab_frame_sse_batch")
+        sse = self._new((n,), torch.int64)
+        count = self._new((n,), torch.int32)
+        self._call("frame_sse_batch", a, mask_a, b, mask_b, n, h, w, sse, count)
         return sse, count
 
     # ------------------------------------------------------------------ deflicker
     def _pair_gain_args(self, who, src, transitions, active):
         """The arguments the two measuring entries share, checked -> (n, h, w, transitions f32 [n-1,9], active u8 [n-1] | None)."""
-        torch = self.torch
-        if not (isinstance(src, torch.Tensor) and src.dtype == torch.float32 and src.device == self.device and src.is_contiguous()):
-            raise ValueError(f"{who}: src must be a contiguous float32 tensor on {self.device}")
+        self._tensor(who, "src", src, self.torch.float32)
         if src.dim() != 4 or src.shape[3] != 3 or src.shape[0] < 2:
             raise ValueError(f"{who}: src of shape {tuple(src.shape)} is not [n,h,w,3] with n >= 2")
         n, h, w = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
@@ -1335,13 +1274,9 @@ class Context:
         full resolution (x_{k+1} = A_k x_k), active [n-1] or None (a pair with 0 reads nothing and reports zeros)
         -> (hist i32 [n-1,4,1024], stats i32 [n-1,2] = inside, well_exposed), device tensors."""
         n, h, w, m, act = self._pair_gain_args("pair_gain_hist_batch", src, transitions, active)
-        torch = self.torch
-        hist = torch.empty((n - 1, 4, 1024), dtype=torch.int32, device=self.device)      # the library's u32, in torch's container
-        stats = torch.empty((n - 1, 2), dtype=torch.int32, device=self.device)
-        self.use_torch_stream()
-        _check(self.lib.vstab_pair_gain_hist_batch(self.handle, _dev_ptr(src), n, h, w, m.ctypes.data,
-                                                   act.ctypes.data if act is not None else None, _dev_ptr(hist), _dev_ptr(stats)),
-               "vstab_pair_gain_hist_batch")
+        hist = self._new((n - 1, 4, 1024), self.torch.int32)      # the library's u32, in torch's container
+        stats = self._new((n - 1, 2), self.torch.int32)
+        self._call("pair_gain_hist_batch", src, n, h, w, m, act, hist, stats)
         return hist, stats
 
     def pair_gain_sums_batch(self, src, transitions, band, active=None):
@@ -1349,15 +1284,11 @@ class Context:
         ratio bin lies in the pair's band.  src, transitions, active as above; band int [n-1,4,2], inclusive bins (lo > hi counts
         nothing) -> sums i64 [n-1,4,3] = count, sum qa, sum qb, device tensor."""
         n, h, w, m, act = self._pair_gain_args("pair_gain_sums_batch", src, transitions, active)
-        torch = self.torch
         b = np.ascontiguousarray(band, dtype=np.int32)
         if b.shape != (n - 1, 4, 2):
             raise ValueError(f"pair_gain_sums_batch: band of shape {b.shape} is not [{n - 1},4,2]")
-        sums = torch.empty((n - 1, 4, 3), dtype=torch.int64, device=self.device)
-        self.use_torch_stream()
-        _check(self.lib.vstab_pair_gain_sums_batch(self.handle, _dev_ptr(src), n, h, w, m.ctypes.data,
-                                                   act.ctypes.data if act is not None else None, b.ctypes.data, _dev_ptr(sums)),
-               "vstab_pair_gain_sums_batch")
+        sums = self._new((n - 1, 4, 3), self.torch.int64)
+        self._call("pair_gain_sums_batch", src, n, h, w, m, act, b, sums)
         return sums
 
     def apply_gain_batch(self, frames, gains, mask=None, want_count=True):
@@ -1366,11 +1297,8 @@ class Context:
         [n,h,w] or None: every pixel is own), channels with a gain of exactly 1 and NaNs are untouched; a value that the gain
         would push above 1 is set to 1 and counted.  -> clamped i32 [n] (device) or None."""
         torch = self.torch
-        for name, t in (("frames", frames), ("mask", mask)):
-            if t is None and name == "mask":
-                continue
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()):
-                raise ValueError(f"apply_gain_batch: {name} must be a contiguous float32 tensor on {self.device}")
+        self._tensor("apply_gain_batch", "frames", frames, torch.float32)
+        self._tensor("apply_gain_batch", "mask", mask, torch.float32, optional=True)
         if frames.dim() != 4 or frames.shape[3] != 3:
             raise ValueError(f"apply_gain_batch: frames of shape {tuple(frames.shape)} are not [n,h,w,3]")
         n, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
@@ -1379,11 +1307,8 @@ class Context:
         g = np.ascontiguousarray(gains, dtype=np.float32)
         if g.shape != (n, 3):
             raise ValueError(f"apply_gain_batch: gains of shape {g.shape} are not [{n},3]")
-        clamped = torch.empty((n,), dtype=torch.int32, device=self.device) if want_count else None
-        self.use_torch_stream()
-        _check(self.lib.vstab_apply_gain_batch(self.handle, _dev_ptr(frames), _dev_ptr(mask) if mask is not None else None, n, h, w,
-                                               g.ctypes.data, _dev_ptr(clamped) if clamped is not None else None),
-               "vstab_apply_gain_batch")
+        clamped = self._new((n,), torch.int32, want_count)
+        self._call("apply_gain_batch", frames, mask, n, h, w, g, clamped)
         return clamped
 
     # ------------------------------------------------------------------ subject lock
@@ -1393,16 +1318,13 @@ class Context:
         written to it.  -> (sums i64 [n,3] = count, sum_x, sum_y;  bbox i32 [n,4] = x0, y0, x1, y1 inclusive, four -1 for a
         frame without a subject pixel), device tensors."""
         torch = self.torch
-        if not (isinstance(mask, torch.Tensor) and mask.dtype == torch.float32 and mask.device == self.device and mask.is_contiguous()):
-            raise ValueError(f"mask_moments_batch: mask must be a contiguous float32 tensor on {self.device}")
+        self._tensor("mask_moments_batch", "mask", mask, torch.float32)
         if mask.dim() != 3:
             raise ValueError(f"mask_moments_batch: mask of shape {tuple(mask.shape)} is not [n,h,w]")
         n, h, w = int(mask.shape[0]), int(mask.shape[1]), int(mask.shape[2])
-        sums = torch.empty((n, 3), dtype=torch.int64, device=self.device)
-        bbox = torch.empty((n, 4), dtype=torch.int32, device=self.device)
-        self.use_torch_stream()
-        _check(self.lib.vstab_mask_moments_batch(self.handle, _dev_ptr(mask), n, h, w, _dev_ptr(sums), _dev_ptr(bbox)),
-               "vstab_mask_moments_batch")
+        sums = self._new((n, 3), torch.int64)
+        bbox = self._new((n, 4), torch.int32)
+        self._call("mask_moments_batch", mask, n, h, w, sums, bbox)
         return sums, bbox
 
     # ------------------------------------------------------------------ horizon level
@@ -1412,51 +1334,37 @@ class Context:
         squared gradient below min_mag2 (0 .. 2^32 - 1) are left out; nothing is written to the images.
         -> hist i64 [n, 2 * ORIENTATION_K + 1], device tensor; bin k + ORIENTATION_K stands for atan(k / ORIENTATION_K)."""
         torch = self.torch
-        if not (isinstance(gray, torch.Tensor) and gray.dtype == torch.uint8 and gray.device == self.device and gray.is_contiguous()):
-            raise ValueError(f"orientation_hist_batch: gray must be a contiguous uint8 tensor on {self.device}")
+        self._tensor("orientation_hist_batch", "gray", gray, torch.uint8)
         if gray.dim() != 3:
             raise ValueError(f"orientation_hist_batch: gray of shape {tuple(gray.shape)} is not [n,h,w]")
-        if isinstance(min_mag2, bool) or not isinstance(min_mag2, (int, np.integer)) or not 0 <= int(min_mag2) <= 0xFFFFFFFF:
-            raise ValueError(f"orientation_hist_batch: min_mag2={min_mag2!r} is not an integer in [0, 2^32 - 1]")
+        min_mag2 = _int_in("orientation_hist_batch", "min_mag2", min_mag2, 0, 0xFFFFFFFF, span="[0, 2^32 - 1]")
         n, h, w = int(gray.shape[0]), int(gray.shape[1]), int(gray.shape[2])
-        hist = torch.empty((n, 2 * ORIENTATION_K + 1), dtype=torch.int64, device=self.device)
-        self.use_torch_stream()
-        _check(self.lib.vstab_orientation_hist_batch(self.handle, _dev_ptr(gray), n, h, w, int(min_mag2), _dev_ptr(hist)),
-               "vstab_orientation_hist_batch")
+        hist = self._new((n, 2 * ORIENTATION_K + 1), torch.int64)
+        self._call("orientation_hist_batch", gray, n, h, w, min_mag2, hist)
         return hist
 
     # ------------------------------------------------------------------ clean plate
-    def _plate_tensor(self, who, name, t, dtype, shape=None):
-        torch = self.torch
-        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == self.device and t.is_contiguous()):
-            raise ValueError(f"{who}: {name} must be a contiguous {str(dtype).replace('torch.', '')} tensor on {self.device}")
-        if shape is not None and tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{who}: {name} of shape {tuple(t.shape)} is not {tuple(shape)}")
-
     def _plate_frames(self, who, name, frames, mask, mask_optional=True):
         """frames [n,h,w,3] and mask [n,h,w] | None, both f32, device, contiguous -> (n, h, w)."""
-        self._plate_tensor(who, name, frames, self.torch.float32)
+        self._tensor(who, name, frames, self.torch.float32)
         if frames.dim() != 4 or frames.shape[3] != 3 or min(frames.shape) < 1:
             raise ValueError(f"{who}: {name} of shape {tuple(frames.shape)} are not [n,h,w,3] with n, h, w >= 1")
         n, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
-        if mask is not None or not mask_optional:
-            self._plate_tensor(who, "mask", mask, self.torch.float32, (n, h, w))
+        self._tensor(who, "mask", mask, self.torch.float32, shape=(n, h, w), optional=mask_optional)
         return n, h, w
 
     def _plate_inputs(self, who, plate, count, h, w, shot, n, min_count):
         """plate [shots,h,w,3] f32 and count [shots,h,w] i32 (device), shot [n] | None, min_count -> (shots, shot i32 | None)."""
-        self._plate_tensor(who, "plate", plate, self.torch.float32)
+        self._tensor(who, "plate", plate, self.torch.float32)
         if plate.dim() != 4 or tuple(plate.shape[1:]) != (h, w, 3) or plate.shape[0] < 1:
             raise ValueError(f"{who}: plate of shape {tuple(plate.shape)} is not [shots,{h},{w},3]")
         shots = int(plate.shape[0])
-        self._plate_tensor(who, "count", count, self.torch.int32, (shots, h, w))
-        if isinstance(min_count, (bool, np.bool_)) or not isinstance(min_count, (int, np.integer)) or not 1 <= int(min_count) <= PLATE_SAMPLES_MAX:
-            raise ValueError(f"{who}: min_count={min_count!r} is not an integer in 1..{PLATE_SAMPLES_MAX}")
+        self._tensor(who, "count", count, self.torch.int32, shape=(shots, h, w))
+        _int_in(who, "min_count", min_count, 1, PLATE_SAMPLES_MAX)
         sh = None
         if shot is not None:
-            sh = np.ascontiguousarray(shot, dtype=np.int32).reshape(-1)
-            if sh.shape[0] != n or (np.diff(sh.astype(np.int64)) < 0).any() or sh.min() < 0 or sh.max() >= shots:
-                raise ValueError(f"{who}: shot of shape {np.shape(shot)} is not a non-decreasing sequence of n={n} shot numbers in 0..{shots - 1}")
+            sh = _shot_sequence(shot, n, f"{who}: shot of shape {np.shape(shot)} is not a non-decreasing sequence of n={n} shot "
+                                         f"numbers in 0..{shots - 1}", shots)
         elif shots != 1:
             raise ValueError(f"{who}: shot=None means one shot, but plate holds {shots}")
         return shots, sh
@@ -1472,12 +1380,9 @@ class Context:
         if tab.ndim != 2 or tab.shape[0] < 1:
             raise ValueError(f"{who}: sample_frame of shape {tab.shape} is not [shots,S]")
         shots, S = int(tab.shape[0]), int(tab.shape[1])
-        torch = self.torch
-        plate = torch.empty((shots, h, w, 3), dtype=torch.float32, device=self.device)
-        count = torch.empty((shots, h, w), dtype=torch.int32, device=self.device)
-        self.use_torch_stream()
-        _check(self.lib.vstab_plate_median_batch(self.handle, _dev_ptr(frames), _dev_ptr(mask) if mask is not None else None, n, h, w,
-                                                 tab.ctypes.data, shots, S, _dev_ptr(plate), _dev_ptr(count)), "vstab_plate_median_batch")
+        plate = self._new((shots, h, w, 3), self.torch.float32)
+        count = self._new((shots, h, w), self.torch.int32)
+        self._call(who, frames, mask, n, h, w, tab, shots, S, plate, count)
         return plate, count
 
     def plate_fill_batch(self, dst, mask, plate, count, shot, min_count):
@@ -1488,11 +1393,8 @@ class Context:
         who = "plate_fill_batch"
         n, h, w = self._plate_frames(who, "dst", dst, mask, mask_optional=False)
         shots, sh = self._plate_inputs(who, plate, count, h, w, shot, n, min_count)
-        filled = self.torch.empty((n,), dtype=self.torch.int32, device=self.device)
-        self.use_torch_stream()
-        _check(self.lib.vstab_plate_fill_batch(self.handle, _dev_ptr(dst), _dev_ptr(mask), n, h, w, _dev_ptr(plate), _dev_ptr(count),
-                                               sh.ctypes.data if sh is not None else None, shots, int(min_count), _dev_ptr(filled)),
-               "vstab_plate_fill_batch")
+        filled = self._new((n,), self.torch.int32)
+        self._call(who, dst, mask, n, h, w, plate, count, sh, shots, int(min_count), filled)
         return filled
 
     def plate_matte_batch(self, frames, mask, plate, count, shot, threshold, min_count):
@@ -1506,14 +1408,9 @@ class Context:
         if isinstance(threshold, (bool, np.bool_)) or not isinstance(threshold, (int, float, np.integer, np.floating)) \
                 or not (np.isfinite(threshold) and threshold >= 0):
             raise ValueError(f"{who}: threshold={threshold!r} is not a finite number >= 0")
-        torch = self.torch
-        matte = torch.empty((n, h, w), dtype=torch.float32, device=self.device)
-        marked = torch.empty((n,), dtype=torch.int32, device=self.device)
-        self.use_torch_stream()
-        _check(self.lib.vstab_plate_matte_batch(self.handle, _dev_ptr(frames), _dev_ptr(mask) if mask is not None else None, n, h, w,
-                                                _dev_ptr(plate), _dev_ptr(count), sh.ctypes.data if sh is not None else None, shots,
-                                                float(np.float32(threshold)), int(min_count), _dev_ptr(matte), _dev_ptr(marked)),
-               "vstab_plate_matte_batch")
+        matte = self._new((n, h, w), self.torch.float32)
+        marked = self._new((n,), self.torch.int32)
+        self._call(who, frames, mask, n, h, w, plate, count, sh, shots, float(np.float32(threshold)), int(min_count), matte, marked)
         return matte, marked
 
     # ------------------------------------------------------------------ sharpness transfer
@@ -1521,16 +1418,12 @@ class Context:
         """The gradient energy of every frame of frames [n,h,w,3], f32, device, contiguous, as one exact integer per frame
         (include/vstab.h states the rule: 16-bit fixed-point luma, forward differences, sum of squares); nothing is written
         to the frames.  -> energy i64 [n], device tensor."""
-        torch = self.torch
-        if not (isinstance(frames, torch.Tensor) and frames.dtype == torch.float32 and frames.device == self.device and frames.is_contiguous()):
-            raise ValueError(f"frame_sharpness_batch: frames must be a contiguous float32 tensor on {self.device}")
+        self._tensor("frame_sharpness_batch", "frames", frames, self.torch.float32)
         if frames.dim() != 4 or frames.shape[3] != 3:
             raise ValueError(f"frame_sharpness_batch: frames of shape {tuple(frames.shape)} are not [n,h,w,3]")
         n, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
-        energy = torch.empty((n,), dtype=torch.int64, device=self.device)
-        self.use_torch_stream()
-        _check(self.lib.vstab_frame_sharpness_batch(self.handle, _dev_ptr(frames), n, h, w, _dev_ptr(energy)),
-               "vstab_frame_sharpness_batch")
+        energy = self._new((n,), self.torch.int64)
+        self._call("frame_sharpness_batch", frames, n, h, w, energy)
         return energy
 
     def sharp_transfer_batch(self, clip_frames, matrices, cand_frame, ratio, alpha, dst, mask=None, first=0, interp="bilinear",
@@ -1545,19 +1438,14 @@ class Context:
         r = np.ascontiguousarray(ratio, dtype=np.float32)
         if r.shape != (n, k):
             raise VstabError(f"sharp_transfer_batch: ratio {r.shape} is not [n={n}, K={k}]")
-        counts = self.torch.empty((n,), dtype=self.torch.int32, device=self.device) if want_counts else None
-        self.use_torch_stream()
-        _check(self.lib.vstab_sharp_transfer_batch(
-            self.handle, _dev_ptr(src), total, sh, sw, int(first), n, m.ctypes.data, cf.ctypes.data, k, r.ctypes.data, float(alpha),
-            out_h, out_w, INTERP[interp], SUBPIX["q5"], _dev_ptr(dst), _dev_ptr(mask) if mask is not None else None,
-            _dev_ptr(counts) if counts is not None else None), "vstab_sharp_transfer_batch")
+        counts = self._new((n,), self.torch.int32, want_counts)
+        self._call("sharp_transfer_batch", src, total, sh, sw, int(first), n, m, cf, k, r, float(alpha), out_h, out_w,
+                   INTERP[interp], SUBPIX["q5"], dst, mask, counts)
         return counts
 
     # ------------------------------------------------------------------ mask hand-off
     def _handoff_mask(self, who, mask):
-        torch = self.torch
-        if not (isinstance(mask, torch.Tensor) and mask.dtype == torch.float32 and mask.device == self.device and mask.is_contiguous()):
-            raise ValueError(f"{who}: mask must be a contiguous float32 tensor on {self.device}")
+        self._tensor(who, "mask", mask, self.torch.float32)
         if mask.dim() != 3 or min(mask.shape) < 1:
             raise ValueError(f"{who}: mask of shape {tuple(mask.shape)} is not [n,h,w] with n, h, w >= 1")
         return int(mask.shape[0]), int(mask.shape[1]), int(mask.shape[2])
@@ -1567,17 +1455,13 @@ class Context:
         of its own that belong to the same shot (include/vstab.h states the rule; a NaN reads as 1.0, hold = 0 returns the
         input's bits).  shots: None (one shot) or a non-decreasing integer sequence [n].  -> a new device tensor [n,h,w]."""
         n, h, w = self._handoff_mask("mask_hold_batch", mask)
-        if isinstance(hold, (bool, np.bool_)) or not isinstance(hold, (int, np.integer)) or not 0 <= int(hold) <= MASK_HOLD_MAX:
-            raise ValueError(f"mask_hold_batch: hold={hold!r} is not an integer in 0..{MASK_HOLD_MAX}")
+        hold = _int_in("mask_hold_batch", "hold", hold, 0, MASK_HOLD_MAX)
         shot = None
         if shots is not None:
-            shot = np.ascontiguousarray(shots, dtype=np.int32).reshape(-1)
-            if shot.shape[0] != n or (np.diff(shot.astype(np.int64)) < 0).any():
-                raise ValueError(f"mask_hold_batch: shots of shape {np.shape(shots)} is not a non-decreasing sequence of n={n} integers")
+            shot = _shot_sequence(shots, n, f"mask_hold_batch: shots of shape {np.shape(shots)} is not a non-decreasing sequence of "
+                                            f"n={n} integers")
         out = self.torch.empty_like(mask)
-        self.use_torch_stream()
-        _check(self.lib.vstab_mask_hold_batch(self.handle, _dev_ptr(mask), n, h, w, int(hold), shot.ctypes.data if shot is not None else None,
-                                              _dev_ptr(out)), "vstab_mask_hold_batch")
+        self._call("mask_hold_batch", mask, n, h, w, hold, shot, out)
         return out
 
     def mask_grow_batch(self, mask, grow, tapered=True, feather=0, want_count=False, out=None):
@@ -1586,25 +1470,20 @@ class Context:
         = the square one, feather an int in 0..64.  `out`: a tensor like mask to write into (it must not share memory with
         mask), None for a new one.  -> out, or (out, count i32 [n] of pixels > 0.5, a device tensor) with want_count."""
         n, h, w = self._handoff_mask("mask_grow_batch", mask)
-        if isinstance(grow, (bool, np.bool_)) or not isinstance(grow, (int, np.integer)) or not -MASK_GROW_MAX <= int(grow) <= MASK_GROW_MAX:
-            raise ValueError(f"mask_grow_batch: grow={grow!r} is not an integer in -{MASK_GROW_MAX}..{MASK_GROW_MAX}")
-        if isinstance(feather, (bool, np.bool_)) or not isinstance(feather, (int, np.integer)) or not 0 <= int(feather) <= MASK_FEATHER_MAX:
-            raise ValueError(f"mask_grow_batch: feather={feather!r} is not an integer in 0..{MASK_FEATHER_MAX}")
+        grow = _int_in("mask_grow_batch", "grow", grow, -MASK_GROW_MAX, MASK_GROW_MAX)
+        feather = _int_in("mask_grow_batch", "feather", feather, 0, MASK_FEATHER_MAX)
         if not isinstance(tapered, (bool, np.bool_)):
             raise ValueError(f"mask_grow_batch: tapered={tapered!r} is not a bool")
         torch = self.torch
         if out is None:
             out = torch.empty_like(mask)
-        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == self.device and out.is_contiguous()
-                  and tuple(out.shape) == tuple(mask.shape)):
-            raise ValueError(f"mask_grow_batch: out must be a contiguous float32 tensor of shape {tuple(mask.shape)} on {self.device}")
-        elif out.data_ptr() < mask.data_ptr() + mask.numel() * 4 and mask.data_ptr() < out.data_ptr() + out.numel() * 4:
-            raise ValueError("mask_grow_batch: out shares memory with mask: a tile's halo would read pixels already written")
-        count = torch.empty((n,), dtype=torch.int32, device=self.device) if want_count else None
-        self.use_torch_stream()
-        _check(self.lib.vstab_mask_grow_batch(self.handle, _dev_ptr(mask), n, h, w, int(grow), GROW_TAPERED if tapered else GROW_SQUARE,
-                                              int(feather), _dev_ptr(out), _dev_ptr(count) if count is not None else None),
-               "vstab_mask_grow_batch")
+        else:
+            self._tensor("mask_grow_batch", "out", out, torch.float32, shape=mask.shape, text="mask_grow_batch: out must be a "
+                         f"contiguous float32 tensor of shape {tuple(mask.shape)} on {self.device}")
+            if out.data_ptr() < mask.data_ptr() + mask.numel() * 4 and mask.data_ptr() < out.data_ptr() + out.numel() * 4:
+                raise ValueError("mask_grow_batch: out shares memory with mask: a tile's halo would read pixels already written")
+        count = self._new((n,), torch.int32, want_count)
+        self._call("mask_grow_batch", mask, n, h, w, grow, GROW_TAPERED if tapered else GROW_SQUARE, feather, out, count)
         return (out, count) if want_count else out
 
     # ------------------------------------------------------------------ Classic estimator (sparse features + LK)
@@ -1617,10 +1496,7 @@ class Context:
         n, h, w = gray.shape
         corners = torch.zeros((n, int(max_corners), 2), dtype=torch.float32, device=self.device)
         counts = torch.zeros((n,), dtype=torch.int32, device=self.device)
-        self.use_torch_stream()
-        _check(self.lib.vstab_gftt_batch(self.handle, _dev_ptr(gray), n, h, w, int(max_corners), float(quality),
-                                         float(min_distance), int(block_size), _dev_ptr(corners), _dev_ptr(counts)),
-               "vstab_gftt_batch")
+        self._call("gftt_batch", gray, n, h, w, int(max_corners), float(quality), float(min_distance), int(block_size), corners, counts)
         return corners, counts
 
     def lk_track_batch(self, gray, points, counts, win=31, max_level=3, max_count=50, epsilon=0.01, want_raw=False):
@@ -1635,15 +1511,11 @@ class Context:
         points = points[:pairs].contiguous()
         counts = counts[:pairs].contiguous()
         max_pts = int(points.shape[1])
-        out = torch.empty((pairs, max_pts, 4), dtype=torch.float32, device=self.device)
+        out = self._new((pairs, max_pts, 4), torch.float32)
         nxt = torch.zeros((pairs, max_pts, 2), dtype=torch.float32, device=self.device) if want_raw else None
         status = torch.zeros((pairs, max_pts), dtype=torch.uint8, device=self.device) if want_raw else None
-        self.use_torch_stream()
-        _check(self.lib.vstab_lk_track_batch(self.handle, _dev_ptr(gray), n, h, w, _dev_ptr(points), _dev_ptr(counts), max_pts,
-                                             int(win), int(max_level), int(max_count), float(epsilon), _dev_ptr(out),
-                                             _dev_ptr(nxt) if nxt is not None else None,
-                                             _dev_ptr(status) if status is not None else None),
-               "vstab_lk_track_batch")
+        self._call("lk_track_batch", gray, n, h, w, points, counts, max_pts, int(win), int(max_level), int(max_count), float(epsilon),
+                   out, nxt, status)
         return (out, nxt, status) if want_raw else out
 
     def points_fit_batch(self, point_pairs, counts, requested_mode):
@@ -1652,10 +1524,7 @@ class Context:
         counts = counts[: point_pairs.shape[0]].contiguous()
         pairs, max_pts, _ = point_pairs.shape
         table = np.zeros((pairs, 3), FIT_DTYPE)
-        self.use_torch_stream()
-        _check(self.lib.vstab_points_fit_batch(self.handle, _dev_ptr(point_pairs), _dev_ptr(counts), pairs, max_pts,
-                                               MODES[requested_mode], table.ctypes.data),
-               "vstab_points_fit_batch")
+        self._call("points_fit_batch", point_pairs, counts, pairs, max_pts, MODES[requested_mode], table)
         return table
 
     # ------------------------------------------------------------------ fallback estimator (phase correlation)
@@ -1672,9 +1541,7 @@ class Context:
             raise ValueError("phase_correlate_batch needs at least two frames")
         table = np.zeros((n - 1, 3), FIT_DTYPE)
         shifts = np.zeros((n - 1, 3), np.float64)
-        self.use_torch_stream()
-        _check(self.lib.vstab_phase_correlate_batch(self.handle, _dev_ptr(gray), n, h, w, table.ctypes.data, shifts.ctypes.data),
-               "vstab_phase_correlate_batch")
+        self._call("phase_correlate_batch", gray, n, h, w, table, shifts)
         return table, shifts
 
     def crop_analysis(self, matrices, src_size, out_size):
@@ -1685,9 +1552,7 @@ class Context:
         ow, oh = int(out_size[0]), int(out_size[1])
         bbox = np.zeros((n, 4), np.int32)
         common = np.zeros((oh, ow), np.uint8)
-        self.use_torch_stream()
-        _check(self.lib.vstab_crop_analysis(self.handle, m.ctypes.data, n, sh, sw, oh, ow, bbox.ctypes.data, common.ctypes.data),
-               "vstab_crop_analysis")
+        self._call("crop_analysis", m, n, sh, sw, oh, ow, bbox, common)
         return bbox, common
 
     def common_coverage(self, matrices, src_size, out_size):
@@ -1696,9 +1561,7 @@ class Context:
         sw, sh = int(src_size[0]), int(src_size[1])
         ow, oh = int(out_size[0]), int(out_size[1])
         common = np.zeros((oh, ow), np.uint8)
-        self.use_torch_stream()
-        _check(self.lib.vstab_common_coverage(self.handle, m.ctypes.data, m.shape[0], sh, sw, oh, ow, common.ctypes.data),
-               "vstab_common_coverage")
+        self._call("common_coverage", m, m.shape[0], sh, sw, oh, ow, common)
         return common.astype(bool)
 
     def trajectory(self, deltas, smooth, fps, strength, camera_lock):
@@ -1707,11 +1570,7 @@ class Context:
         p = d.shape[1]
         path = np.zeros((n, p), np.float64)
         target = np.zeros((n, p), np.float64)
-        _check(
-            self.lib.vstab_trajectory(self.handle, d.ctypes.data, n, p, float(smooth), float(fps), float(strength),
-                                      1 if camera_lock else 0, path.ctypes.data, target.ctypes.data),
-            "vstab_trajectory",
-        )
+        self._call("trajectory", d, n, p, float(smooth), float(fps), float(strength), 1 if camera_lock else 0, path, target, stream=False)
         return path, target
 
 

@@ -37,15 +37,51 @@ def test_integration_doc_names_every_entry_point():
     assert not missing, f"INTEGRATION.md does not mention {missing}"
 
 
-def header_prototypes():
-    """(name, [parameter type strings]) of every `int vstab_*(...)` prototype in include/vstab.h."""
+def header_prototypes(any_return=False):
+    """(name, [parameter type strings]) of every `int vstab_*(...)` prototype in include/vstab.h; any_return: of every
+    prototype whatever it returns, as (name, [parameter type strings], return type string)."""
     text = re.sub(r"/\*.*?\*/", " ", (ROOT / "include" / "vstab.h").read_text(), flags=re.S)
     text = re.sub(r"//[^\n]*", " ", text)
     out = []
-    for m in re.finditer(r"\bint\s+(vstab_[a-z0-9_]+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S):
-        params = [p.strip() for p in m.group(2).replace("\n", " ").split(",")]
-        out.append((m.group(1), [] if params == ["void"] else params))
+    for m in re.finditer(r"^[ \t]*((?:const\s+)?\w+(?:\s*\*)?)\s*\b(vstab_[a-z0-9_]+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S | re.M):
+        params = [p.strip() for p in m.group(3).replace("\n", " ").split(",")]
+        params = [] if params == ["void"] else params
+        if any_return:
+            out.append((m.group(2), params, m.group(1)))
+        elif m.group(1) == "int":
+            out.append((m.group(2), params))
     return out
+
+
+def _ctypes_class(ctype):
+    """The class of one _SIGNATURES entry under the rule of test_signature_table_matches_the_header."""
+    if ctype in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(ctype, ctypes._Pointer):
+        return "pointer"
+    return {ctypes.c_double: "double", ctypes.c_float: "float", ctypes.c_size_t: "size_t", ctypes.c_uint32: "uint32_t",
+            ctypes.c_int: "int", ctypes.c_int32: "int"}[ctype]
+
+
+def _header_class(ptxt):
+    """The class of one parameter (or return) type string of the header under the same rule."""
+    if "*" in ptxt:
+        return "pointer"
+    base = ptxt.replace("const ", "").split()[0]
+    return base if base in ("double", "float", "size_t", "uint32_t") else "int"
+
+
+def test_signature_table_matches_the_header(pkg):
+    """native._SIGNATURES restates every prototype of include/vstab.h by hand, and a wrong entry is undefined behaviour that
+    no other test sees: for every prototype the number of parameters agrees and each parameter's class does -- a type with
+    `*` is a pointer type (c_void_p, c_char_p, POINTER(...)), double is c_double, float is c_float, size_t is c_size_t,
+    uint32_t is c_uint32, every other scalar is c_int or c_int32; a restype of None is `void`."""
+    from vstab_amd import native
+
+    protos = {name: (params, ret) for name, params, ret in header_prototypes(any_return=True)}
+    assert set(protos) == set(native._SIGNATURES) == set(header_symbols()) and len(protos) >= 82
+    for name, (restype, argtypes) in native._SIGNATURES.items():
+        params, ret = protos[name]
+        assert [_ctypes_class(a) for a in argtypes] == [_header_class(p) for p in params], name
+        assert ("void" if restype is None else _ctypes_class(restype)) == ("void" if ret == "void" else _header_class(ret)), name
 
 
 def test_null_context_is_rejected_before_any_gpu_work(pkg):
