@@ -1,4 +1,4 @@
-// vstab_fit.hip -- F4+F5: model fit on the grid-sampled flow, one 256-thread block per frame pair.
+// vstab_fit.hip -- F4+F5: model fit on the grid-sampled flow, one block of FIT_THREADS (512) threads per frame pair.
 //
 // Replaces nodes/video_stabilizer_flow.py:141-210 of the reference: the stride-8 sampling of the
 // dense flow, cv2.estimateAffinePartial2D (RANSAC 2.0 px / 2000 / 0.992 + 10 LM iterations),
@@ -7,13 +7,13 @@
 //
 // RANSAC keeps OpenCV's sequential semantics (RNG seeded with 2^64-1, adaptive iteration count)
 // but runs data-parallel: one lane replays the RNG and draws a batch of K minimal samples, K lanes
-// build the K models, all 256 lanes score every model against every sample in one pass over the
+// build the K models, all lanes score every model against every sample in one pass over the
 // points (integer inlier counts -> order independent), then one lane replays OpenCV's
 // "best so far / update niters" loop over the batch.  The final least-squares refit is the closed
 // form of what the 10 LM iterations converge to (the similarity problem is linear): fp64 sums
-// reduced in a fixed tree, 4x4 solve on one lane.
-#include "vstab_internal.h"
-#include <cmath>
+// reduced in a fixed tree, 4x4 solve on one lane.  The RANSAC skeleton, the sample walk and the
+// block sum are shared with the homography kernel (vstab_fit_common.h).
+#include "vstab_fit_common.h"
 
 namespace {
 
@@ -21,7 +21,7 @@ namespace {
 // threads a SIMD held one wavefront and nothing hid that latency (0.21 ms per clip); 512 or 1024 threads: 0.16 ms
 // (512 is the default: at 1024 the 128-register cap spills 560 B per thread into scratch -- 238 MB of HBM writes per
 // launch in the PMC view -- for no gain)
-// (tools/fit_phases.py: validity scan 32 us, RANSAC +32, least squares + residual +43, the two medians +44; what is
+// (per phase, cumulative: validity scan 32 us, RANSAC +32, least squares + residual +43, the two medians +44; what is
 // left is the ~60 workgroup barriers between short passes and the single-lane sections).
 #ifndef VSTAB_FIT_THREADS
 #define VSTAB_FIT_THREADS 512
@@ -32,41 +32,6 @@ static_assert(FIT_THREADS >= 256 && FIT_THREADS % 64 == 0 && FIT_THREADS <= 1024
 constexpr int RANSAC_BATCH = 16;   // typical clips converge in < 10 iterations; 16 keeps the scoring loop in registers
 constexpr int MAX_SORT = 16384;
 
-struct Rng { unsigned long long state; };
-__device__ __forceinline__ unsigned rng_next(Rng& r)
-{
-    r.state = (unsigned long long)(unsigned)r.state * 4164903690ULL + (unsigned)(r.state >> 32);
-    return (unsigned)r.state;
-}
-__device__ __forceinline__ int rng_uniform(Rng& r, int a, int b) { return a == b ? a : (int)(rng_next(r) % (unsigned)(b - a) + a); }
-
-__device__ int ransac_update_num_iters(double p, double ep, int modelPoints, int maxIters)
-{
-    p = p > 0. ? p : 0.; p = p < 1. ? p : 1.;
-    ep = ep > 0. ? ep : 0.; ep = ep < 1. ? ep : 1.;
-    double num = 1. - p > 2.2250738585072014e-308 ? 1. - p : 2.2250738585072014e-308;
-    double denom = 1. - pow(1. - ep, (double)modelPoints);
-    if (denom < 2.2250738585072014e-308) return 0;
-    num = log(num);
-    denom = log(denom);
-    return denom >= 0 || -num >= maxIters * (-denom) ? maxIters : (int)__builtin_rint(num / denom);
-}
-
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T* scratch /* >= FIT_WAVES */)
-{
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_down(v, s);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    T total = scratch[0];
-#pragma unroll
-    for (int i = 1; i < FIT_WAVES; i++) total += scratch[i];
-    __syncthreads();
-    return total;
-}
-
 struct FitArgs {
     const float* grid_flow;   // [pairs][gh][gw][2]
     int* vmap;                // [pairs][gh*gw] compacted index -> grid index
@@ -76,22 +41,6 @@ struct FitArgs {
     int cap;
     const uint8_t* blocked;   // masked grid mode only: [pairs+1][gh*gw], non-zero = sample blocked in that frame
 };
-
-// gw > 0: stride-`step` grid over a flow field (F = [gh][gw][2] displacements, flow.py:141-147);
-// gw == 0: explicit point pairs (F = [cap][4]: prev.x, prev.y, next.x, next.y; untracked points carry NaN)
-__device__ __forceinline__ void load_point(const float* __restrict__ F, int gw, int step, int g, float& px, float& py, float& cx, float& cy)
-{
-    if (gw == 0) {
-        const float4 v = *reinterpret_cast<const float4*>(F + (size_t)g * 4);
-        px = v.x; py = v.y; cx = v.z; cy = v.w;
-        return;
-    }
-    const int gy = g / gw, gx = g - gy * gw;
-    px = (float)(gx * step);
-    py = (float)(gy * step);
-    cx = px + F[(size_t)g * 2];
-    cy = py + F[(size_t)g * 2 + 1];
-}
 
 __device__ void identity_record(vstab_fit_record& r, int nv, int total)
 {
@@ -175,8 +124,8 @@ __global__ __launch_bounds__(FIT_THREADS) void fit_kernel(FitArgs a)
     const int scan = points ? a.counts[pair] : a.gh * a.gw;
     const uint8_t* __restrict__ B0 = MASKED ? a.blocked + (size_t)pair * a.cap : nullptr;
     const uint8_t* __restrict__ B1 = MASKED ? B0 + a.cap : nullptr;
-    const float* __restrict__ F = a.grid_flow + (size_t)pair * a.cap * (points ? 4 : 2);
     int* __restrict__ vmap = a.vmap + (size_t)pair * a.cap;
+    const Samples smp{a.grid_flow + (size_t)pair * a.cap * (points ? 4 : 2), vmap, a.gw, a.step};
     vstab_fit_record* out = a.out + (size_t)pair * 3;
 
     // ---- validity scan (ordered compaction, flow.py:150-152) ----
@@ -185,7 +134,7 @@ __global__ __launch_bounds__(FIT_THREADS) void fit_kernel(FitArgs a)
     int local = 0, admitted = 0;
     for (int g = g0; g < g1; g++) {
         float px, py, cx, cy;
-        load_point(F, a.gw, a.step, g, px, py, cx, cy);
+        smp.load(g, px, py, cx, cy);
         if (MASKED) {
             const bool adm = (B0[g] | B1[g]) == 0;
             admitted += adm ? 1 : 0;
@@ -195,7 +144,7 @@ __global__ __launch_bounds__(FIT_THREADS) void fit_kernel(FitArgs a)
         }
     }
     int total = scan;
-    if (MASKED) total = block_sum(admitted, s_redi);
+    if (MASKED) total = block_sum<FIT_WAVES>(admitted, s_redi);
     {   // exclusive prefix sum of `local` over the block: wavefront scan, then the wavefront totals
         int incl = local;
 #pragma unroll
@@ -216,7 +165,7 @@ __global__ __launch_bounds__(FIT_THREADS) void fit_kernel(FitArgs a)
         int o = s_scan[tid];
         for (int g = g0; g < g1; g++) {
             float px, py, cx, cy;
-            load_point(F, a.gw, a.step, g, px, py, cx, cy);
+            smp.load(g, px, py, cx, cy);
             if ((!MASKED || (B0[g] | B1[g]) == 0) && isfinite(cx) && isfinite(cy)) vmap[o++] = g;
         }
     }
@@ -245,8 +194,8 @@ __global__ __launch_bounds__(FIT_THREADS) void fit_kernel(FitArgs a)
             __syncthreads();
             if (tid < RANSAC_BATCH) {
                 float x1f, y1f, X1f, Y1f, x2f, y2f, X2f, Y2f;
-                load_point(F, a.gw, a.step, vmap[s_idx[tid][0]], x1f, y1f, X1f, Y1f);
-                load_point(F, a.gw, a.step, vmap[s_idx[tid][1]], x2f, y2f, X2f, Y2f);
+                smp.load(vmap[s_idx[tid][0]], x1f, y1f, X1f, Y1f);
+                smp.load(vmap[s_idx[tid][1]], x2f, y2f, X2f, Y2f);
                 const double x1 = x1f, y1 = y1f, x2 = x2f, y2 = y2f, X1 = X1f, Y1 = Y1f, X2 = X2f, Y2 = Y2f;
                 const double d = 1. / ((x1 - x2) * (x1 - x2) + (y1 - y2) * (y1 - y2));
                 const double S0 = d * ((X1 - X2) * (x1 - x2) + (Y1 - Y2) * (y1 - y2));
@@ -259,66 +208,33 @@ __global__ __launch_bounds__(FIT_THREADS) void fit_kernel(FitArgs a)
             }
             __syncthreads();
             // score every model of the batch in one pass over the points
-            int cnt[RANSAC_BATCH];
-#pragma unroll
-            for (int c = 0; c < RANSAC_BATCH; c++) cnt[c] = 0;
-            for (int k = tid; k < nv; k += FIT_THREADS) {
-                float px, py, cx, cy;
-                load_point(F, a.gw, a.step, vmap[k], px, py, cx, cy);
-#pragma unroll
-                for (int c = 0; c < RANSAC_BATCH; c++) {
-                    const float ea = s_modelf[c][0] * px + s_modelf[c][1] * py + s_modelf[c][2] - cx;
-                    const float eb = s_modelf[c][3] * px + s_modelf[c][4] * py + s_modelf[c][5] - cy;
-                    cnt[c] += (ea * ea + eb * eb <= thr) ? 1 : 0;
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < RANSAC_BATCH; c++) {
-                int v = cnt[c];
-#pragma unroll
-                for (int s = 32; s > 0; s >>= 1) v += __shfl_down(v, s);
-                if ((tid & 63) == 0 && v) atomicAdd(&s_cnt[c], v);
-            }
+            ransac_score_batch<RANSAC_BATCH, FIT_THREADS>(smp, nv, thr, s_cnt, [&](int c, float px, float py, float cx, float cy) {
+                return affine_err2(s_modelf[c], px, py, cx, cy);
+            });
             __syncthreads();
-            if (tid == 0) {
-                int niters = s_ctl[1], iter = s_ctl[2], maxGood = s_ctl[3];
-                int c = 0;
-                for (; c < RANSAC_BATCH && iter < niters; c++, iter++) {
-                    const int good = s_cnt[c];
-                    if (good > (maxGood > 1 ? maxGood : 1)) {
-                        for (int k = 0; k < 6; k++) s_best[k] = s_model[c][k];
-                        maxGood = good;
-                        niters = ransac_update_num_iters(0.992, (double)(nv - good) / nv, 2, niters);
-                    }
-                }
-                s_ctl[1] = niters; s_ctl[2] = iter; s_ctl[3] = maxGood;
-                s_ctl[0] = (iter >= niters) ? 1 : 0;
-            }
+            // every 2-point sample has a model (all solved, none failed)
+            if (tid == 0) ransac_replay<RANSAC_BATCH, 6, 2, 1>(s_ctl, s_cnt, s_model, s_best, nv, [](int) { return RANSAC_SOLVED; });
             __syncthreads();
             if (s_ctl[0]) break;
         }
         const int maxGood = s_ctl[3];
         if (maxGood > 0) {
             // inliers of the best minimal-sample model -> closed-form least squares (what the LM refinement converges to)
-            const float F0 = (float)s_best[0], F1 = (float)s_best[1], F2 = (float)s_best[2];
-            const float F3 = (float)s_best[3], F4 = (float)s_best[4], F5 = (float)s_best[5];
+            const float Bf[6] = {(float)s_best[0], (float)s_best[1], (float)s_best[2], (float)s_best[3], (float)s_best[4], (float)s_best[5]};
             double sxx = 0, sx = 0, sy = 0, sX = 0, sY = 0, sxX = 0, syX = 0;
             int ninl = 0;
-            for (int k = tid; k < nv; k += FIT_THREADS) {
-                float px, py, cx, cy;
-                load_point(F, a.gw, a.step, vmap[k], px, py, cx, cy);
-                const float ea = F0 * px + F1 * py + F2 - cx;
-                const float eb = F3 * px + F4 * py + F5 - cy;
-                if (ea * ea + eb * eb <= thr) {
+            smp.for_each_valid<FIT_THREADS>(nv, [&](int, float px, float py, float cx, float cy) {
+                if (affine_err2(Bf, px, py, cx, cy) <= thr) {
                     const double x = px, y = py, X = cx, Y = cy;
                     sxx += x * x + y * y; sx += x; sy += y; sX += X; sY += Y;
                     sxX += x * X + y * Y; syX += x * Y - y * X;
                     ninl++;
                 }
-            }
-            sxx = block_sum(sxx, s_red); sx = block_sum(sx, s_red); sy = block_sum(sy, s_red);
-            sX = block_sum(sX, s_red); sY = block_sum(sY, s_red); sxX = block_sum(sxX, s_red); syX = block_sum(syX, s_red);
-            ninl = block_sum(ninl, s_redi);
+            });
+            sxx = block_sum<FIT_WAVES>(sxx, s_red); sx = block_sum<FIT_WAVES>(sx, s_red); sy = block_sum<FIT_WAVES>(sy, s_red);
+            sX = block_sum<FIT_WAVES>(sX, s_red); sY = block_sum<FIT_WAVES>(sY, s_red);
+            sxX = block_sum<FIT_WAVES>(sxX, s_red); syX = block_sum<FIT_WAVES>(syX, s_red);
+            ninl = block_sum<FIT_WAVES>(ninl, s_redi);
             if (tid == 0) {
                 // normal equations of [x -y 1 0; y x 0 1] (a, b, tx, ty) = (X, Y)
                 double A[4][5] = {{sxx, 0, sx, sy, sxX}, {0, sxx, -sy, sx, syX}, {sx, -sy, (double)ninl, 0, sX}, {sy, sx, 0, (double)ninl, sY}};
@@ -347,13 +263,11 @@ __global__ __launch_bounds__(FIT_THREADS) void fit_kernel(FitArgs a)
             __syncthreads();
             const double M0 = s_best[0], M1 = s_best[1], M2 = s_best[2], M3 = s_best[3], M4 = s_best[4], M5 = s_best[5];
             double res = 0;
-            for (int k = tid; k < nv; k += FIT_THREADS) {
-                float px, py, cx, cy;
-                load_point(F, a.gw, a.step, vmap[k], px, py, cx, cy);
+            smp.for_each_valid<FIT_THREADS>(nv, [&](int, float px, float py, float cx, float cy) {
                 const double x = px, y = py;
                 res += fabs(x * M0 + y * M1 + M2 - (double)cx) + fabs(x * M3 + y * M4 + M5 - (double)cy);
-            }
-            res = block_sum(res, s_red);
+            });
+            res = block_sum<FIT_WAVES>(res, s_red);
             if (tid == 0) {
                 vstab_fit_record& r = out[VSTAB_MODE_SIMILARITY];
                 r.computed = 1;
@@ -376,11 +290,9 @@ __global__ __launch_bounds__(FIT_THREADS) void fit_kernel(FitArgs a)
     {
         float med[2];
         for (int axis = 0; axis < 2; axis++) {
-            for (int k = tid; k < nv; k += FIT_THREADS) {
-                float px, py, cx, cy;
-                load_point(F, a.gw, a.step, vmap[k], px, py, cx, cy);
+            smp.for_each_valid<FIT_THREADS>(nv, [&](int k, float px, float py, float cx, float cy) {
                 s_sort[k] = sort_key(axis == 0 ? cx - px : cy - py);
-            }
+            });
             __syncthreads();
             const int mid = nv / 2;
             const unsigned hi = radix_select(s_sort, nv, mid, s_hist, s_sel);
@@ -390,8 +302,8 @@ __global__ __launch_bounds__(FIT_THREADS) void fit_kernel(FitArgs a)
                 // lower middle element: the largest key below `hi` if exactly `mid` keys are smaller, else a duplicate of `hi`
                 int less = 0;
                 unsigned below = 0;
-                for (int k = tid; k < nv; k += FIT_THREADS) {
-                    const unsigned key = s_sort[k];
+                for (int i = tid; i < nv; i += FIT_THREADS) {   // over the keys, not the samples
+                    const unsigned key = s_sort[i];
                     if (key < hi) { less++; below = key > below ? key : below; }
                 }
 #pragma unroll
@@ -412,12 +324,10 @@ __global__ __launch_bounds__(FIT_THREADS) void fit_kernel(FitArgs a)
         }
         const float tx = med[0], ty = med[1];
         double res = 0;
-        for (int k = tid; k < nv; k += FIT_THREADS) {
-            float px, py, cx, cy;
-            load_point(F, a.gw, a.step, vmap[k], px, py, cx, cy);
+        smp.for_each_valid<FIT_THREADS>(nv, [&](int, float px, float py, float cx, float cy) {
             res += (double)__builtin_fabsf((px + tx) - cx) + (double)__builtin_fabsf((py + ty) - cy);
-        }
-        res = block_sum(res, s_red);
+        });
+        res = block_sum<FIT_WAVES>(res, s_red);
         if (tid == 0) {
             vstab_fit_record& r = out[VSTAB_MODE_TRANSLATION];
             r.computed = 1; r.accepted = 1;
@@ -478,44 +388,40 @@ static int run_fit(vstab_ctx* ctx, const float* data, const int* counts, int pai
     return vstab_check_device_status(ctx, "vstab_sample_fit_batch");
 }
 
+// The argument checks of the five entry points, in one order and one wording.  `have`: the call's pointer arguments are all
+// there.  A point table has no gw and no step: its entry passes gh = max_points and the dummies gw = 1, step = 1, which make
+// `gw > 0 && step > 0` vacuous (its size test is `pairs > 0 && max_points > 0`) and gh * gw its point count, and its own noun
+// for the last message.
+static int fit_check(const char* who, vstab_ctx* ctx, bool have, int pairs, int gh, int gw, int step, int requested_mode,
+                     const char* noun = "sample points")
+{
+    VSTAB_REQUIRE(ctx != nullptr, "%s: ctx is NULL", who);
+    VSTAB_REQUIRE(have, "%s: NULL pointer argument", who);
+    VSTAB_REQUIRE(pairs > 0 && gh > 0 && gw > 0 && step > 0, "%s: non-positive size", who);
+    VSTAB_REQUIRE(requested_mode >= VSTAB_MODE_TRANSLATION && requested_mode <= VSTAB_MODE_PERSPECTIVE, "%s: unknown mode %d", who, requested_mode);
+    VSTAB_REQUIRE((long long)gh * gw <= MAX_SORT, "%s: %d %s exceed the supported %d", who, gh * gw, noun, MAX_SORT);
+    return 0;
+}
+
 extern "C" int vstab_sample_fit_batch(vstab_ctx* ctx, const float* grid_flow, int pairs, int gh, int gw, int step,
                                       int requested_mode, vstab_fit_record* results)
 {
-    VSTAB_REQUIRE(ctx != nullptr, "vstab_sample_fit_batch: ctx is NULL");
-    VSTAB_REQUIRE(grid_flow && results, "vstab_sample_fit_batch: NULL pointer argument");
-    VSTAB_REQUIRE(pairs > 0 && gh > 0 && gw > 0 && step > 0, "vstab_sample_fit_batch: non-positive size");
-    VSTAB_REQUIRE(requested_mode >= VSTAB_MODE_TRANSLATION && requested_mode <= VSTAB_MODE_PERSPECTIVE, "vstab_sample_fit_batch: unknown mode %d", requested_mode);
-    VSTAB_REQUIRE((long long)gh * gw <= MAX_SORT, "vstab_sample_fit_batch: %d sample points exceed the supported %d", gh * gw, MAX_SORT);
+    if (int rc = fit_check("vstab_sample_fit_batch", ctx, grid_flow && results, pairs, gh, gw, step, requested_mode)) return rc;
     return run_fit(ctx, grid_flow, nullptr, pairs, gh, gw, step, gh * gw, requested_mode, results);
 }
 
 extern "C" int vstab_sample_fit_batch_begin(vstab_ctx* ctx, const float* grid_flow, int pairs, int gh, int gw, int step,
                                             int requested_mode)
 {
-    VSTAB_REQUIRE(ctx != nullptr, "vstab_sample_fit_batch_begin: ctx is NULL");
-    VSTAB_REQUIRE(grid_flow != nullptr, "vstab_sample_fit_batch_begin: NULL pointer argument");
-    VSTAB_REQUIRE(pairs > 0 && gh > 0 && gw > 0 && step > 0, "vstab_sample_fit_batch_begin: non-positive size");
-    VSTAB_REQUIRE(requested_mode >= VSTAB_MODE_TRANSLATION && requested_mode <= VSTAB_MODE_PERSPECTIVE, "vstab_sample_fit_batch_begin: unknown mode %d", requested_mode);
-    VSTAB_REQUIRE((long long)gh * gw <= MAX_SORT, "vstab_sample_fit_batch_begin: %d sample points exceed the supported %d", gh * gw, MAX_SORT);
+    if (int rc = fit_check("vstab_sample_fit_batch_begin", ctx, grid_flow != nullptr, pairs, gh, gw, step, requested_mode)) return rc;
     return run_fit(ctx, grid_flow, nullptr, pairs, gh, gw, step, gh * gw, requested_mode, nullptr);
 }
 
 // The masked forms: the same checks and the same run, with the block grid handed to the kernel's masked instance.
-static int masked_check(const char* who, vstab_ctx* ctx, const float* grid_flow, const uint8_t* blocked, int pairs, int gh, int gw, int step,
-                        int requested_mode)
-{
-    VSTAB_REQUIRE(ctx != nullptr, "%s: ctx is NULL", who);
-    VSTAB_REQUIRE(grid_flow && blocked, "%s: NULL pointer argument", who);
-    VSTAB_REQUIRE(pairs > 0 && gh > 0 && gw > 0 && step > 0, "%s: non-positive size", who);
-    VSTAB_REQUIRE(requested_mode >= VSTAB_MODE_TRANSLATION && requested_mode <= VSTAB_MODE_PERSPECTIVE, "%s: unknown mode %d", who, requested_mode);
-    VSTAB_REQUIRE((long long)gh * gw <= MAX_SORT, "%s: %d sample points exceed the supported %d", who, gh * gw, MAX_SORT);
-    return 0;
-}
-
 extern "C" int vstab_sample_fit_batch_masked(vstab_ctx* ctx, const float* grid_flow, int pairs, int gh, int gw, int step,
                                              int requested_mode, const uint8_t* blocked, vstab_fit_record* results)
 {
-    if (int rc = masked_check("vstab_sample_fit_batch_masked", ctx, grid_flow, blocked, pairs, gh, gw, step, requested_mode)) return rc;
+    if (int rc = fit_check("vstab_sample_fit_batch_masked", ctx, grid_flow && blocked, pairs, gh, gw, step, requested_mode)) return rc;
     VSTAB_REQUIRE(results != nullptr, "vstab_sample_fit_batch_masked: NULL pointer argument");
     return run_fit(ctx, grid_flow, nullptr, pairs, gh, gw, step, gh * gw, requested_mode, results, blocked);
 }
@@ -523,7 +429,7 @@ extern "C" int vstab_sample_fit_batch_masked(vstab_ctx* ctx, const float* grid_f
 extern "C" int vstab_sample_fit_batch_begin_masked(vstab_ctx* ctx, const float* grid_flow, int pairs, int gh, int gw, int step,
                                                    int requested_mode, const uint8_t* blocked)
 {
-    if (int rc = masked_check("vstab_sample_fit_batch_begin_masked", ctx, grid_flow, blocked, pairs, gh, gw, step, requested_mode)) return rc;
+    if (int rc = fit_check("vstab_sample_fit_batch_begin_masked", ctx, grid_flow && blocked, pairs, gh, gw, step, requested_mode)) return rc;
     return run_fit(ctx, grid_flow, nullptr, pairs, gh, gw, step, gh * gw, requested_mode, nullptr, blocked);
 }
 
@@ -559,10 +465,7 @@ extern "C" int vstab_sample_fit_batch_end(vstab_ctx* ctx, int pairs, vstab_fit_r
 extern "C" int vstab_points_fit_batch(vstab_ctx* ctx, const float* point_pairs, const int* counts, int pairs, int max_points,
                                       int requested_mode, vstab_fit_record* results)
 {
-    VSTAB_REQUIRE(ctx != nullptr, "vstab_points_fit_batch: ctx is NULL");
-    VSTAB_REQUIRE(point_pairs && counts && results, "vstab_points_fit_batch: NULL pointer argument");
-    VSTAB_REQUIRE(pairs > 0 && max_points > 0, "vstab_points_fit_batch: non-positive size");
-    VSTAB_REQUIRE(requested_mode >= VSTAB_MODE_TRANSLATION && requested_mode <= VSTAB_MODE_PERSPECTIVE, "vstab_points_fit_batch: unknown mode %d", requested_mode);
-    VSTAB_REQUIRE(max_points <= MAX_SORT, "vstab_points_fit_batch: %d points per pair exceed the supported %d", max_points, MAX_SORT);
+    if (int rc = fit_check("vstab_points_fit_batch", ctx, point_pairs && counts && results, pairs, max_points, 1, 1, requested_mode,
+                           "points per pair")) return rc;
     return run_fit(ctx, point_pairs, counts, pairs, 0, 0, 1, max_points, requested_mode, results);
 }

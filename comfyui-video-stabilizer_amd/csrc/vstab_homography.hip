@@ -8,9 +8,9 @@
 // RNG and draws a batch of 16 samples, 16 lanes run the 16 Jacobi solves, all lanes score the batch in one
 // pass over the points, one lane replays the "best so far / update niters" loop.  The normal equations of
 // the refit and of every LM step are fp64 block reductions; the 8x8 solves run on one lane (Gaussian
-// elimination instead of OpenCV's eigen-solve: same solution to ~1e-13).
-#include "vstab_internal.h"
-#include <cmath>
+// elimination instead of OpenCV's eigen-solve: same solution to ~1e-13).  The RANSAC skeleton, the sample
+// walk and the block sum are shared with the similarity fit (vstab_fit_common.h).
+#include "vstab_fit_common.h"
 
 #define VSTAB_HAVE_HOMOGRAPHY 1
 
@@ -18,42 +18,7 @@ namespace {
 
 constexpr int HT = 256;
 constexpr int HBATCH = 16;
-
-struct Rng { unsigned long long state; };
-__device__ __forceinline__ unsigned rng_next(Rng& r)
-{
-    r.state = (unsigned long long)(unsigned)r.state * 4164903690ULL + (unsigned)(r.state >> 32);
-    return (unsigned)r.state;
-}
-__device__ __forceinline__ int rng_uniform(Rng& r, int a, int b) { return a == b ? a : (int)(rng_next(r) % (unsigned)(b - a) + a); }
-
-__device__ int update_num_iters(double p, double ep, int modelPoints, int maxIters)
-{
-    p = p > 0. ? p : 0.; p = p < 1. ? p : 1.;
-    ep = ep > 0. ? ep : 0.; ep = ep < 1. ? ep : 1.;
-    double num = 1. - p > 2.2250738585072014e-308 ? 1. - p : 2.2250738585072014e-308;
-    double denom = 1. - pow(1. - ep, (double)modelPoints);
-    if (denom < 2.2250738585072014e-308) return 0;
-    num = log(num);
-    denom = log(denom);
-    return denom >= 0 || -num >= maxIters * (-denom) ? maxIters : (int)__builtin_rint(num / denom);
-}
-
-// gw > 0: stride-`step` grid over a flow field (F = [gh][gw][2] displacements, flow.py:141-147);
-// gw == 0: explicit point pairs (F = [cap][4]: prev.x, prev.y, next.x, next.y; untracked points carry NaN)
-__device__ __forceinline__ void load_point(const float* __restrict__ F, int gw, int step, int g, float& px, float& py, float& cx, float& cy)
-{
-    if (gw == 0) {
-        const float4 v = *reinterpret_cast<const float4*>(F + (size_t)g * 4);
-        px = v.x; py = v.y; cx = v.z; cy = v.w;
-        return;
-    }
-    const int gy = g / gw, gx = g - gy * gw;
-    px = (float)(gx * step);
-    py = (float)(gy * step);
-    cx = px + F[(size_t)g * 2];
-    cy = py + F[(size_t)g * 2 + 1];
-}
+constexpr int HWAVES = HT / 64;
 
 // JacobiImpl_ of OpenCV (core/src/lapack.cpp) for a symmetric n x n fp64 matrix; eigenvalues sorted descending,
 // eigenvectors are the rows of V.
@@ -269,19 +234,6 @@ __device__ bool check_subset(const float* ms1, const float* ms2)
     return negative == 0 || negative == 4;
 }
 
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T* scratch)
-{
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_down(v, s);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const T total = ((scratch[0] + scratch[1]) + scratch[2]) + scratch[3];
-    __syncthreads();
-    return total;
-}
-
 // N block sums at once: the same wavefront shuffle tree and the same ((w0 + w1) + w2) + w3 order as N calls of block_sum
 // -- the same bits -- behind two barriers instead of 3 N (the normal equations of an LM step are 44 sums: 132 barriers).
 // part: LDS [HT / 64][N]; out: LDS [N], valid for every thread on return.
@@ -347,20 +299,15 @@ struct HArgs {
 
 // residuals + (optionally) the normal equations of HomographyRefineCallback for parameters h[8] over the inliers
 // (inlier test against Hbest in f32, threshold thr).  Returns S = |r|^2; JtJ (36 upper entries) / Jtr (8) if wanted.
-__device__ double lm_accumulate(const HArgs& a, const float* F, const int* vmap, int nv, const float* Hbf, float thr, const double* h,
+__device__ double lm_accumulate(const Samples& samples, int nv, const float* Hbf, float thr, const double* h,
                                 bool want_jac, double* JtJ /*64*/, double* Jtr /*8*/, double* rinf, double* s_red, double* s_part /*[4][45]*/,
                                 double* s_sum /*[45]*/)
 {
     double acc[45];
     for (int i = 0; i < 45; i++) acc[i] = 0;
     double S = 0, rmax = 0;
-    for (int k = threadIdx.x; k < nv; k += HT) {
-        float px, py, cx, cy;
-        load_point(F, a.gw, a.step, vmap[k], px, py, cx, cy);
-        const float ww = 1.f / (Hbf[6] * px + Hbf[7] * py + 1.f);
-        const float ex = (Hbf[0] * px + Hbf[1] * py + Hbf[2]) * ww - cx;
-        const float ey = (Hbf[3] * px + Hbf[4] * py + Hbf[5]) * ww - cy;
-        if (!(ex * ex + ey * ey <= thr)) continue;
+    samples.for_each_valid<HT>(nv, [&](int, float px, float py, float cx, float cy) {
+        if (!(reproj_err2(Hbf, px, py, cx, cy) <= thr)) return;
         const double Mx = px, My = py;
         double w = h[6] * Mx + h[7] * My + 1.;
         w = fabs(w) > 2.220446049250313e-16 ? 1. / w : 0;
@@ -377,8 +324,8 @@ __device__ double lm_accumulate(const HArgs& a, const float* F, const int* vmap,
                 for (int q = p; q < 8; q++) acc[idx++] += J0[p] * J0[q] + J1[p] * J1[q];
             for (int p = 0; p < 8; p++) acc[36 + p] += J0[p] * r0 + J1[p] * r1;
         }
-    }
-    S = block_sum(S, s_red);
+    });
+    S = block_sum<HWAVES>(S, s_red);
     // max via sum trick is not possible: reduce rmax with shuffles
     for (int s = 32; s > 0; s >>= 1) rmax = fmax(rmax, __shfl_down(rmax, s));
     __syncthreads();
@@ -428,8 +375,7 @@ __global__ __launch_bounds__(HT) void homography_kernel(HArgs a)
     const bool prof_ = a.dbg && blockIdx.x == 7 && threadIdx.x == 0;
 #endif
     const bool points = a.gw == 0;
-    const float* __restrict__ F = a.grid_flow + (size_t)pair * a.cap * (points ? 4 : 2);
-    const int* __restrict__ vmap = a.vmap + (size_t)pair * a.cap;
+    const Samples smp{a.grid_flow + (size_t)pair * a.cap * (points ? 4 : 2), a.vmap + (size_t)pair * a.cap, a.gw, a.step};
     vstab_fit_record* out = a.out + (size_t)pair * 3 + VSTAB_MODE_PERSPECTIVE;
     const int nv = a.out[(size_t)pair * 3].valid_points;
     // flow.py:153-154 / classic.py:84-86,102-103 (record stays "not computed")
@@ -456,7 +402,7 @@ __global__ __launch_bounds__(HT) void homography_kernel(HArgs a)
                             for (int q = 0; q < i; q++) dup |= (idx[q] == v);
                         } while (dup);
                         idx[i] = v;
-                        load_point(F, a.gw, a.step, vmap[v], ms1[i * 2], ms1[i * 2 + 1], ms2[i * 2], ms2[i * 2 + 1]);
+                        smp.load(smp.vmap[v], ms1[i * 2], ms1[i * 2 + 1], ms2[i * 2], ms2[i * 2 + 1]);
                     }
                     if (check_subset(ms1, ms2)) {
                         for (int i = 0; i < 4; i++) s_idx[c][i] = idx[i];
@@ -480,7 +426,7 @@ __global__ __launch_bounds__(HT) void homography_kernel(HArgs a)
                 ws.go = 0;
                 if (s_idx[grp][0] >= 0) {
                     float ms1[8], ms2[8];
-                    for (int i = 0; i < 4; i++) load_point(F, a.gw, a.step, vmap[s_idx[grp][i]], ms1[i * 2], ms1[i * 2 + 1], ms2[i * 2], ms2[i * 2 + 1]);
+                    for (int i = 0; i < 4; i++) smp.load(smp.vmap[s_idx[grp][i]], ms1[i * 2], ms1[i * 2 + 1], ms2[i * 2], ms2[i * 2 + 1]);
                     ws.go = homography_4pt_setup(ws, ms1, ms2) ? 1 : 0;
                 }
             }
@@ -497,45 +443,14 @@ __global__ __launch_bounds__(HT) void homography_kernel(HArgs a)
         }
         __syncthreads();
         H_MARK(1);
-        int cnt[HBATCH];
-#pragma unroll
-        for (int c = 0; c < HBATCH; c++) cnt[c] = 0;
-        for (int k = tid; k < nv; k += HT) {
-            float px, py, cx, cy;
-            load_point(F, a.gw, a.step, vmap[k], px, py, cx, cy);
-#pragma unroll
-            for (int c = 0; c < HBATCH; c++) {
-                const float ww = 1.f / (s_modelf[c][6] * px + s_modelf[c][7] * py + 1.f);
-                const float dx = (s_modelf[c][0] * px + s_modelf[c][1] * py + s_modelf[c][2]) * ww - cx;
-                const float dy = (s_modelf[c][3] * px + s_modelf[c][4] * py + s_modelf[c][5]) * ww - cy;
-                cnt[c] += (dx * dx + dy * dy <= thr) ? 1 : 0;
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < HBATCH; c++) {
-            int v = cnt[c];
-#pragma unroll
-            for (int s = 32; s > 0; s >>= 1) v += __shfl_down(v, s);
-            if ((tid & 63) == 0 && v) atomicAdd(&s_cnt[c], v);
-        }
+        ransac_score_batch<HBATCH, HT>(smp, nv, thr, s_cnt, [&](int c, float px, float py, float cx, float cy) {
+            return reproj_err2(s_modelf[c], px, py, cx, cy);
+        });
         __syncthreads();
         H_MARK(2);
-        if (tid == 0) {
-            int niters = s_ctl[1], iter = s_ctl[2], maxGood = s_ctl[3];
-            bool stop = false;
-            for (int c = 0; c < HBATCH && iter < niters; c++, iter++) {
-                if (s_idx[c][0] < 0) { stop = true; break; }   // getSubset failed: iter == 0 -> no model, else break
-                if (!s_ok[c]) continue;                         // runKernel returned 0 models
-                const int good = s_cnt[c];
-                if (good > (maxGood > 3 ? maxGood : 3)) {
-                    for (int k = 0; k < 9; k++) s_best[k] = s_model[c][k];
-                    maxGood = good;
-                    niters = update_num_iters(0.992, (double)(nv - good) / nv, 4, niters);
-                }
-            }
-            s_ctl[1] = niters; s_ctl[2] = iter; s_ctl[3] = maxGood;
-            s_ctl[0] = (stop || iter >= niters) ? 1 : 0;
-        }
+        if (tid == 0) ransac_replay<HBATCH, 9, 4, 3>(s_ctl, s_cnt, s_model, s_best, nv, [&](int c) {
+            return s_idx[c][0] < 0 ? RANSAC_FAILED : s_ok[c] ? RANSAC_SOLVED : RANSAC_NONE;
+        });
         __syncthreads();
         H_MARK(3);
         if (s_ctl[0]) break;
@@ -550,40 +465,27 @@ __global__ __launch_bounds__(HT) void homography_kernel(HArgs a)
     for (int k = 0; k < 8; k++) Hbf[k] = (float)s_best[k];
     double c0 = 0, c1 = 0, c2 = 0, c3 = 0;
     int ninl = 0;
-    for (int k = tid; k < nv; k += HT) {
-        float px, py, cx, cy;
-        load_point(F, a.gw, a.step, vmap[k], px, py, cx, cy);
-        const float ww = 1.f / (Hbf[6] * px + Hbf[7] * py + 1.f);
-        const float ex = (Hbf[0] * px + Hbf[1] * py + Hbf[2]) * ww - cx;
-        const float ey = (Hbf[3] * px + Hbf[4] * py + Hbf[5]) * ww - cy;
-        if (ex * ex + ey * ey <= thr) { c0 += cx; c1 += cy; c2 += px; c3 += py; ninl++; }
-    }
-    double cmx = block_sum(c0, s_red), cmy = block_sum(c1, s_red), cMx = block_sum(c2, s_red), cMy = block_sum(c3, s_red);
-    ninl = block_sum(ninl, s_redi);
+    smp.for_each_valid<HT>(nv, [&](int, float px, float py, float cx, float cy) {
+        if (reproj_err2(Hbf, px, py, cx, cy) <= thr) { c0 += cx; c1 += cy; c2 += px; c3 += py; ninl++; }
+    });
+    double cmx = block_sum<HWAVES>(c0, s_red), cmy = block_sum<HWAVES>(c1, s_red);
+    double cMx = block_sum<HWAVES>(c2, s_red), cMy = block_sum<HWAVES>(c3, s_red);
+    ninl = block_sum<HWAVES>(ninl, s_redi);
     cmx /= ninl; cmy /= ninl; cMx /= ninl; cMy /= ninl;
     c0 = c1 = c2 = c3 = 0;
-    for (int k = tid; k < nv; k += HT) {
-        float px, py, cx, cy;
-        load_point(F, a.gw, a.step, vmap[k], px, py, cx, cy);
-        const float ww = 1.f / (Hbf[6] * px + Hbf[7] * py + 1.f);
-        const float ex = (Hbf[0] * px + Hbf[1] * py + Hbf[2]) * ww - cx;
-        const float ey = (Hbf[3] * px + Hbf[4] * py + Hbf[5]) * ww - cy;
-        if (ex * ex + ey * ey <= thr) { c0 += fabs(cx - cmx); c1 += fabs(cy - cmy); c2 += fabs(px - cMx); c3 += fabs(py - cMy); }
-    }
-    double smx = block_sum(c0, s_red), smy = block_sum(c1, s_red), sMx = block_sum(c2, s_red), sMy = block_sum(c3, s_red);
+    smp.for_each_valid<HT>(nv, [&](int, float px, float py, float cx, float cy) {
+        if (reproj_err2(Hbf, px, py, cx, cy) <= thr) { c0 += fabs(cx - cmx); c1 += fabs(cy - cmy); c2 += fabs(px - cMx); c3 += fabs(py - cMy); }
+    });
+    double smx = block_sum<HWAVES>(c0, s_red), smy = block_sum<HWAVES>(c1, s_red);
+    double sMx = block_sum<HWAVES>(c2, s_red), sMy = block_sum<HWAVES>(c3, s_red);
     const double deps = 2.220446049250313e-16;
     const bool degenerate = fabs(smx) < deps || fabs(smy) < deps || fabs(sMx) < deps || fabs(sMy) < deps;
     if (!degenerate) {
         smx = ninl / smx; smy = ninl / smy; sMx = ninl / sMx; sMy = ninl / sMy;
         double acc[45];
         for (int i = 0; i < 45; i++) acc[i] = 0;
-        for (int k = tid; k < nv; k += HT) {
-            float px, py, cx, cy;
-            load_point(F, a.gw, a.step, vmap[k], px, py, cx, cy);
-            const float ww = 1.f / (Hbf[6] * px + Hbf[7] * py + 1.f);
-            const float ex = (Hbf[0] * px + Hbf[1] * py + Hbf[2]) * ww - cx;
-            const float ey = (Hbf[3] * px + Hbf[4] * py + Hbf[5]) * ww - cy;
-            if (!(ex * ex + ey * ey <= thr)) continue;
+        smp.for_each_valid<HT>(nv, [&](int, float px, float py, float cx, float cy) {
+            if (!(reproj_err2(Hbf, px, py, cx, cy) <= thr)) return;
             const double x = (cx - cmx) * smx, y = (cy - cmy) * smy;
             const double X = (px - cMx) * sMx, Y = (py - cMy) * sMy;
             const double Lx[9] = {X, Y, 1, 0, 0, 0, -x * X, -x * Y, -x};
@@ -591,7 +493,7 @@ __global__ __launch_bounds__(HT) void homography_kernel(HArgs a)
             int idx = 0;
             for (int j = 0; j < 9; j++)
                 for (int q = j; q < 9; q++) acc[idx++] += Lx[j] * Lx[q] + Ly[j] * Ly[q];
-        }
+        });
         H_MARK(4);
         double* s_LtL = s_ws[0].A;   // the refit reuses slot 0 (the batch solves are finished)
         block_sum_many<45>(acc, s_part, s_sum);
@@ -619,7 +521,7 @@ __global__ __launch_bounds__(HT) void homography_kernel(HArgs a)
     double x[8];
     for (int i = 0; i < 8; i++) x[i] = s_best[i];
     double rinf;
-    double S = lm_accumulate(a, F, vmap, nv, Hbf, thr, x, true, s_A, s_v, &rinf, s_red, s_part, s_sum);
+    double S = lm_accumulate(smp, nv, Hbf, thr, x, true, s_A, s_v, &rinf, s_red, s_part, s_sum);
     __shared__ double s_D[8];
     if (tid == 0) { for (int i = 0; i < 8; i++) s_D[i] = s_A[i * 8 + i]; s_lm[0] = 1.0; s_lm[1] = 0.75; }
     __syncthreads();
@@ -639,7 +541,7 @@ __global__ __launch_bounds__(HT) void homography_kernel(HArgs a)
         double xd[8];
         for (int i = 0; i < 8; i++) xd[i] = s_x[i];
         double rinf_d;
-        const double Sd = lm_accumulate(a, F, vmap, nv, Hbf, thr, xd, false, nullptr, nullptr, &rinf_d, s_red, s_part, s_sum);
+        const double Sd = lm_accumulate(smp, nv, Hbf, thr, xd, false, nullptr, nullptr, &rinf_d, s_red, s_part, s_sum);
         H_MARK(9);
         if (tid == 0) {
             double dS = 0, tdv = 0;
@@ -681,7 +583,7 @@ __global__ __launch_bounds__(HT) void homography_kernel(HArgs a)
             S = Sd;
             for (int i = 0; i < 8; i++) x[i] = xd[i];
             __syncthreads();
-            S = lm_accumulate(a, F, vmap, nv, Hbf, thr, x, true, s_A, s_v, &rinf, s_red, s_part, s_sum);
+            S = lm_accumulate(smp, nv, Hbf, thr, x, true, s_A, s_v, &rinf, s_red, s_part, s_sum);
         }
         __syncthreads();
         H_MARK(11);
@@ -692,13 +594,11 @@ __global__ __launch_bounds__(HT) void homography_kernel(HArgs a)
     }
     // ---- record (flow.py:171-175: confidence = inliers/valid, residual uses the affine part of H only)
     double res = 0;
-    for (int k = tid; k < nv; k += HT) {
-        float px, py, cx, cy;
-        load_point(F, a.gw, a.step, vmap[k], px, py, cx, cy);
+    smp.for_each_valid<HT>(nv, [&](int, float px, float py, float cx, float cy) {
         const double X = px, Y = py;
         res += fabs(X * x[0] + Y * x[1] + x[2] - (double)cx) + fabs(X * x[3] + Y * x[4] + x[5] - (double)cy);
-    }
-    res = block_sum(res, s_red);
+    });
+    res = block_sum<HWAVES>(res, s_red);
     H_MARK(12);
     if (tid == 0) {
         out->computed = 1;
