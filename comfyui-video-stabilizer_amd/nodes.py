@@ -1,24 +1,41 @@
-"""ComfyUI V3 node classes: `Video Stabilizer Flow` and `Video Stabilizer Motion Apply`.
+"""ComfyUI V3 node classes and the extensions that list them.
 
-Socket ids, order, defaults and output names are those of the reference
-(nodes/video_stabilizer_flow.py:643-763, nodes/video_stabilizer_motion_apply.py:29-129; pinned by
-scripts/check_node_schema.py:28-64) so existing graphs keep working when this package replaces it.
+The six nodes of the reference (NODE_CLASSES: Classic, Flow, Motion Apply, the two shake generators, Inverse) keep its socket
+ids, order, defaults and output names (nodes/video_stabilizer_flow.py:643-763, nodes/video_stabilizer_motion_apply.py:29-129;
+pinned by scripts/check_node_schema.py:28-64), so existing graphs keep working when this package replaces it.
+
+The other 21 are this package's own, in three families:
+- Flow variants (`_FlowVariant`): the Flow node plus the sockets of one `_stabilize_frames` feature.  A variant states its
+  texts, its sockets and one function from their values to the keyword extras; the schema and `execute` are made from that.
+  The two Motion Apply variants (`_ApplyVariant`) are stated the same way over `apply_motion`.
+- Post-warp nodes (fills, sharpness transfer, deflicker, clean plate, stability report, mask grow), which take frames and
+  masks in through one intake: `_device_frames`, `_stabilizer_mask`, `_check_clip_and_mask` / `_place_socket_mask`,
+  `_check_clips_against_plan`.
+- The extension classes, one per feature, made from the ordered table `_EXTENSION_CHAIN`.
+
+tests/test_node_surface_cpu.py pins every schema, the registration, what each variant hands on and every refusal that
+precedes the GPU work; DESIGN.md ("Adding a node") says how a new one is written.
 """
 
 from __future__ import annotations
 
-from typing import Any
-
+import inspect
+import json
 import os
+from typing import Any
 
 import numpy as np
 
-from . import host_math as hm
+from . import clean_plate, deflicker, host_math as hm, mask_handoff, native, scene_cuts, sharpness_transfer, spatial_fill
+from . import stability, temporal_fill
 from .apply_pipeline import apply_motion
 from .meta_v2 import resolve_motion_meta
 from .comfy_compat import ComfyExtension, ProgressBar, io
-from .flow_pipeline import _stabilize_frames
-from .shake_generator import STYLES, ShakeRecipe, generate_shake_motion_meta
+from .dynamic_zoom import DEFAULT_WINDOW_S, DEFAULT_ZOOM_LIMIT, WINDOW_MAX_S, ZOOM_LIMIT_MAX, ZOOM_LIMIT_MIN
+from .flow_pipeline import _fps_fields, _stabilize_frames
+from .horizon_level import DEFAULT_LIMIT_DEG, LIMIT_MAX_DEG, WINDOW_MAX_S as LEVEL_WINDOW_MAX_S
+from .mesh_warp import CELLS_MAX, CELLS_MIN, DEFAULT_CELLS
+from .shake_generator import FIELD_RANGE, STYLES, ShakeRecipe, generate_shake_motion_meta
 
 JSONType = io.Custom("JSON")
 
@@ -71,11 +88,25 @@ def _estimator_inputs(transform_tip: str, lock_tip: str, framing_tip: str, stren
     ]
 
 
+def _schema(node_id: str, display_name: str, description: str, **extra) -> io.Schema:
+    """The shell of every node's schema; define_schema fills in `inputs` and `outputs`, with fresh sockets on every call."""
+    return io.Schema(node_id=node_id, display_name=display_name, category="Video/Stabilization", description=description, **extra)
+
+
 def _estimator_outputs() -> list:
     return [
         io.Image.Output("frames_stabilized", display_name="Stabilized Frames"),
         io.Mask.Output("padding_mask", display_name="Padding Mask"),
         JSONType.Output("meta", display_name="Motion Meta"),
+    ]
+
+
+def _clip_outputs() -> list:
+    """Frames, padding mask and meta, as Motion Apply names them."""
+    return [
+        io.Image.Output("frames", display_name="Frames"),
+        io.Mask.Output("padding_mask", display_name="Padding Mask"),
+        JSONType.Output("meta", display_name="Meta"),
     ]
 
 
@@ -95,15 +126,9 @@ class VideoStabilizerFlow(io.ComfyNode):
 
     @classmethod
     def define_schema(cls) -> io.Schema:
-        schema = io.Schema(
-            node_id="video_stabilizer_flow",
-            display_name="Video Stabilizer Flow",
-            category="Video/Stabilization",
-            description=(
-                "Video stabilization using dense optical flow with configurable transforms and framing, "
-                "emitting stabilized frames, a padding mask, and motion diagnostics (MI355X build)."
-            ),
-        )
+        schema = _schema("video_stabilizer_flow", "Video Stabilizer Flow",
+                         description=("Video stabilization using dense optical flow with configurable transforms and framing, "
+                                      "emitting stabilized frames, a padding mask, and motion diagnostics (MI355X build)."))
         schema.inputs = _estimator_inputs(
             transform_tip="Select the geometric model fitted to the optical flow.",
             lock_tip="Aggressively pull the motion curve toward a locked tripod-like solution.",
@@ -127,15 +152,9 @@ class VideoStabilizerClassic(io.ComfyNode):
 
     @classmethod
     def define_schema(cls) -> io.Schema:
-        schema = io.Schema(
-            node_id="video_stabilizer_classic",
-            display_name="Video Stabilizer Classic",
-            category="Video/Stabilization",
-            description=(
-                "Video stabilization using sparse feature tracking with configurable transforms and framing, "
-                "emitting both stabilized frames and a padding mask (MI355X build)."
-            ),
-        )
+        schema = _schema("video_stabilizer_classic", "Video Stabilizer Classic",
+                         description=("Video stabilization using sparse feature tracking with configurable transforms and framing, "
+                                      "emitting both stabilized frames and a padding mask (MI355X build)."))
         schema.inputs = _estimator_inputs(
             transform_tip="Select the geometric model used to estimate camera motion.",
             lock_tip="Treat the shot as tripod-like by aggressively damping motion.",
@@ -158,12 +177,8 @@ class VideoStabilizerMotionApply(io.ComfyNode):
 
     @classmethod
     def define_schema(cls) -> io.Schema:
-        schema = io.Schema(
-            node_id="video_stabilizer_motion_apply",
-            display_name="Video Stabilizer Motion Apply",
-            category="Video/Stabilization",
-            description="Applies motion metadata to frames and emits a padding mask.",
-        )
+        schema = _schema("video_stabilizer_motion_apply", "Video Stabilizer Motion Apply",
+                         description="Applies motion metadata to frames and emits a padding mask.")
         schema.inputs = [
             io.Image.Input("frames", display_name="Frames"),
             JSONType.Input("motion_meta", display_name="Motion Meta"),
@@ -180,11 +195,7 @@ class VideoStabilizerMotionApply(io.ComfyNode):
                            display_name="Blur Quality",
                            tooltip="Draft is faster. High and Ultra average more shutter samples for smoother blur."),
         ]
-        schema.outputs = [
-            io.Image.Output("frames", display_name="Frames"),
-            io.Mask.Output("padding_mask", display_name="Padding Mask"),
-            JSONType.Output("meta", display_name="Meta"),
-        ]
+        schema.outputs = _clip_outputs()
         return schema
 
     @classmethod
@@ -220,14 +231,9 @@ class VideoStabilizerInverse(io.ComfyNode):
 
     @classmethod
     def define_schema(cls) -> io.Schema:
-        schema = io.Schema(
-            node_id="video_stabilizer_inverse",
-            display_name="Video Stabilizer Inverse",
-            category="Video/Stabilization",
-            description=("Deprecated: use Video Stabilizer Motion Apply. Restores stabilized frames to the original "
-                         "canvas using stabilization metadata, and emits a padding mask for areas without source pixels."),
-            is_deprecated=True,
-        )
+        schema = _schema("video_stabilizer_inverse", "Video Stabilizer Inverse",
+                         description=("Deprecated: use Video Stabilizer Motion Apply. Restores stabilized frames to the original "
+                                      "canvas using stabilization metadata, and emits a padding mask for areas without source pixels."), is_deprecated=True)
         schema.inputs = [
             io.Image.Input("frames", display_name="Frames"),
             JSONType.Input("meta", display_name="Meta"),
@@ -297,12 +303,8 @@ class VideoStabilizerShakeGenerator(io.ComfyNode):
 
     @classmethod
     def define_schema(cls) -> io.Schema:
-        schema = io.Schema(
-            node_id="video_stabilizer_shake_generator",
-            display_name="Video Stabilizer Shake Generator",
-            category="Video/Stabilization",
-            description="Generates deterministic shake motion metadata; it does not alter input frames.",
-        )
+        schema = _schema("video_stabilizer_shake_generator", "Video Stabilizer Shake Generator",
+                         description="Generates deterministic shake motion metadata; it does not alter input frames.")
         schema.inputs = _shake_common_inputs([
             io.Combo.Input("style", options=list(STYLES.keys()), default="handheld", display_name="Style")])
         schema.outputs = [JSONType.Output("motion_meta", display_name="Motion Meta")]
@@ -326,14 +328,8 @@ class VideoStabilizerShakeGeneratorManual(io.ComfyNode):
 
     @classmethod
     def define_schema(cls) -> io.Schema:
-        from .shake_generator import FIELD_RANGE
-
-        schema = io.Schema(
-            node_id="video_stabilizer_shake_generator_manual",
-            display_name="Video Stabilizer Shake Generator Manual",
-            category="Video/Stabilization",
-            description="Generates deterministic shake motion metadata from manual absolute values.",
-        )
+        schema = _schema("video_stabilizer_shake_generator_manual", "Video Stabilizer Shake Generator Manual",
+                         description="Generates deterministic shake motion metadata from manual absolute values.")
         base = STYLES["handheld"]
         fields = []
         for name, step, label in _MANUAL_FIELDS:
@@ -352,6 +348,76 @@ class VideoStabilizerShakeGeneratorManual(io.ComfyNode):
         return _shake_block(frames_context, frame_rate, recipe, amount, speed, seed, "shake_generator_manual", "manual")
 
 
+# ---- the post-warp nodes' intake: who = the node's message prefix ("temporal fill", "padding fill", ...)
+
+def _device_frames(video, ctx):
+    """A clip's frames on the device under F0's value-range rule, as the stabilizer applies it: a float frame whose peak exceeds
+    1.5 is 0..255 and is divided by 255."""
+    batch = video.device_batch(ctx)
+    if video.range_pending and hm.resolve_value_range(video, hm.prefetch_peaks(ctx.frame_range(batch)), ctx):
+        batch = video.device_batch(ctx)
+    return batch
+
+
+def _check_clips_against_plan(who: str, plan: dict, context, out_context) -> None:
+    """The original and the stabilized clip against temporal_fill.plan_from_meta: frame count, then source -> output size."""
+    n = len(plan["final_matrices"])
+    if len(context.frames) != n or len(out_context.frames) != n:
+        raise ValueError(f"{who}: meta describes {n} frames, got {len(context.frames)} original and "
+                         f"{len(out_context.frames)} stabilized frames")
+    if (context.width, context.height) != plan["source_size"] or (out_context.width, out_context.height) != plan["output_size"]:
+        raise ValueError(f"{who}: frame sizes {(context.width, context.height)} -> "
+                         f"{(out_context.width, out_context.height)} do not match the meta's "
+                         f"{plan['source_size']} -> {plan['output_size']}")
+
+
+def _stabilizer_mask(who: str, padding_mask: Any, dst, ctx, copy: bool = False):
+    """The stabilizer's own padding mask (a tensor or an array, [N,H,W] or [N,H,W,1]) as a contiguous float32 device tensor of
+    the stabilized frames' shape, which is all it may have.  copy: a private one, for a node that writes the mask -- the
+    caller's tensor (another node's cached output) stays as it is."""
+    torch = ctx.torch
+    mask = padding_mask if isinstance(padding_mask, torch.Tensor) else torch.from_numpy(np.asarray(padding_mask, dtype=np.float32))
+    mask = mask.to(device=ctx.device, dtype=torch.float32)
+    if mask.ndim == 4:
+        mask = mask[..., 0]
+    if tuple(mask.shape) != tuple(dst.shape[:3]):
+        raise ValueError(f"{who}: padding_mask {tuple(mask.shape)} does not match the stabilized frames {tuple(dst.shape[:3])}")
+    mask = mask.contiguous()
+    return mask.clone() if copy else mask
+
+
+def _check_clip_and_mask(who: str, context, padding_mask: Any, optional: bool = True):
+    """The checks of a `frames` / `padding_mask` socket pair, all before any GPU work: the mask of any node, [N,H,W], [1,H,W] for
+    every frame, or either with a trailing axis of 1.  -> (n, h, w), the mask's leading size (None without a mask)."""
+    n, h, w = len(context.frames), context.height, context.width
+    if n == 0:
+        raise ValueError(f"{who}: socket 'frames' holds no frame")
+    if padding_mask is None and optional:
+        return (n, h, w), None
+    if not (hasattr(padding_mask, "dtype") and hasattr(padding_mask, "shape")):
+        raise ValueError(f"{who}: socket 'padding_mask' must be a floating-point MASK tensor, got {type(padding_mask).__name__}")
+    if "float" not in str(padding_mask.dtype):
+        raise ValueError(f"{who}: socket 'padding_mask' must be a floating-point MASK, got {padding_mask.dtype}")
+    shape = tuple(int(v) for v in padding_mask.shape)
+    if len(shape) == 4 and shape[3] == 1:
+        shape = shape[:3]
+    if len(shape) != 3 or shape[1:] != (h, w) or shape[0] not in (1, n):
+        raise ValueError(f"{who}: socket 'padding_mask' of shape {tuple(padding_mask.shape)} does not match socket "
+                         f"'frames' [{n},{h},{w},3]: expected [{n},{h},{w}] or [1,{h},{w}]")
+    return (n, h, w), shape[0]
+
+
+def _place_socket_mask(padding_mask: Any, lead: int, dims, ctx, copy: bool = False):
+    """A mask that passed _check_clip_and_mask as a float32 [N,H,W] device tensor (None without a mask).  copy: a private one,
+    for a node that writes the mask; otherwise a mask that is already in place is handed on as it is."""
+    if lead is None:
+        return None
+    torch = ctx.torch
+    mask = padding_mask if isinstance(padding_mask, torch.Tensor) else torch.from_numpy(np.asarray(padding_mask))
+    mask = mask.to(device=ctx.device, dtype=torch.float32).reshape((lead,) + tuple(dims[1:])).expand(*dims)
+    return mask.clone() if copy else mask.contiguous()
+
+
 class VideoStabilizerTemporalFill(io.ComfyNode):
     """Fills the padding of a Flow / Classic result from neighbouring frames (temporal_fill.py), from the meta JSON alone:
     `stabilization_warp` gives the applied matrices, `estimated_motion.per_transition` the frame-to-frame motion.  Not one
@@ -359,13 +425,9 @@ class VideoStabilizerTemporalFill(io.ComfyNode):
 
     @classmethod
     def define_schema(cls) -> io.Schema:
-        schema = io.Schema(
-            node_id="video_stabilizer_temporal_fill",
-            display_name="Video Stabilizer Temporal Fill",
-            category="Video/Stabilization",
-            description=("Fills padded pixels of stabilized frames with what neighbouring frames saw there, using the "
-                         "stabilizer's own motion metadata; the remaining mask marks what no frame within the radius saw."),
-        )
+        schema = _schema("video_stabilizer_temporal_fill", "Video Stabilizer Temporal Fill",
+                         description=("Fills padded pixels of stabilized frames with what neighbouring frames saw there, using the "
+                                      "stabilizer's own motion metadata; the remaining mask marks what no frame within the radius saw."))
         schema.inputs = [
             io.Image.Input("frames", display_name="Frames", tooltip="The original (unstabilized) frames."),
             io.Image.Input("frames_stabilized", display_name="Stabilized Frames"),
@@ -375,11 +437,7 @@ class VideoStabilizerTemporalFill(io.ComfyNode):
                          tooltip="Frames before and after each frame that may supply its missing pixels."),
             io.Combo.Input("interpolation", options=["bilinear", "bicubic"], default="bilinear", display_name="Interpolation"),
         ]
-        schema.outputs = [
-            io.Image.Output("frames", display_name="Frames"),
-            io.Mask.Output("padding_mask", display_name="Padding Mask"),
-            JSONType.Output("meta", display_name="Meta"),
-        ]
+        schema.outputs = _clip_outputs()
         return schema
 
     @classmethod
@@ -391,37 +449,18 @@ class VideoStabilizerTemporalFill(io.ComfyNode):
     def _fill(cls, frames: Any, frames_stabilized: Any, padding_mask: Any, meta: dict, radius: int, interpolation: str,
               feather=None, exposure: bool = False) -> io.NodeOutput:
         """The node's work; feather / exposure are the blended node's two sockets (None / False: the plain fill)."""
-        from . import native, temporal_fill
-
         plan = temporal_fill.plan_from_meta(meta)   # ValueError naming the missing key, before any GPU work
         feather, exposure = temporal_fill.check_blend_request(int(radius), feather, exposure)
         if interpolation not in native.INTERP:
             raise ValueError(f"Unknown interpolation {interpolation!r}; expected 'bilinear' or 'bicubic'.")
         context = hm._normalize_video_input(frames)
         out_context = hm._normalize_video_input(frames_stabilized)
-        n = len(plan["final_matrices"])
-        if len(context.frames) != n or len(out_context.frames) != n:
-            raise ValueError(f"temporal fill: meta describes {n} frames, got {len(context.frames)} original and "
-                             f"{len(out_context.frames)} stabilized frames")
-        if (context.width, context.height) != plan["source_size"] or (out_context.width, out_context.height) != plan["output_size"]:
-            raise ValueError(f"temporal fill: frame sizes {(context.width, context.height)} -> "
-                             f"{(out_context.width, out_context.height)} do not match the meta's "
-                             f"{plan['source_size']} -> {plan['output_size']}")
+        _check_clips_against_plan("temporal fill", plan, context, out_context)
         ctx = native.default_context()
-        torch = ctx.torch
-        src = context.device_batch(ctx)
-        if context.range_pending:   # F0's value-range rule, as the stabilizer applied it to these frames
-            if hm.resolve_value_range(context, hm.prefetch_peaks(ctx.frame_range(src)), ctx):
-                src = context.device_batch(ctx)
+        src = _device_frames(context, ctx)
         # the fill works in place: on copies, so the caller's tensors (another node's cached outputs) stay as they are
         dst = out_context.device_batch(ctx).clone()
-        mask = padding_mask if isinstance(padding_mask, torch.Tensor) else torch.from_numpy(np.asarray(padding_mask, dtype=np.float32))
-        mask = mask.to(device=ctx.device, dtype=torch.float32)
-        if mask.ndim == 4:
-            mask = mask[..., 0]
-        if tuple(mask.shape) != tuple(dst.shape[:3]):
-            raise ValueError(f"temporal fill: padding_mask {tuple(mask.shape)} does not match the stabilized frames {tuple(dst.shape[:3])}")
-        mask = mask.contiguous().clone()
+        mask = _stabilizer_mask("temporal fill", padding_mask, dst, ctx, copy=True)
         block = temporal_fill.fill_on_device(ctx, src, dst, mask, plan["final_matrices"], plan["transitions"],
                                              plan["confidences"], int(radius), interp=interpolation, feather=feather,
                                              exposure=exposure)
@@ -437,13 +476,9 @@ class VideoStabilizerTemporalFillBlend(VideoStabilizerTemporalFill):
 
     @classmethod
     def define_schema(cls) -> io.Schema:
-        schema = io.Schema(
-            node_id="video_stabilizer_temporal_fill_blend",
-            display_name="Video Stabilizer Temporal Fill (Blended)",
-            category="Video/Stabilization",
-            description=("Video Stabilizer Temporal Fill whose filled pixels are matched to the frame's exposure and fade into "
-                         "the frame's own content over a feather, instead of meeting it at a hard cut."),
-        )
+        schema = _schema("video_stabilizer_temporal_fill_blend", "Video Stabilizer Temporal Fill (Blended)",
+                         description=("Video Stabilizer Temporal Fill whose filled pixels are matched to the frame's exposure and fade into "
+                                      "the frame's own content over a feather, instead of meeting it at a hard cut."))
         base = VideoStabilizerTemporalFill.define_schema()
         schema.inputs = list(base.inputs) + [
             io.Int.Input("feather", default=16, min=0, max=64, display_name="Feather",
@@ -472,13 +507,9 @@ class VideoStabilizerSharpnessTransfer(io.ComfyNode):
 
     @classmethod
     def define_schema(cls) -> io.Schema:
-        schema = io.Schema(
-            node_id="video_stabilizer_sharpness_transfer",
-            display_name="Video Stabilizer Sharpness Transfer",
-            category="Video/Stabilization",
-            description=("Pulls the pixels of frames a camera jolt blurred towards what sharper neighbouring frames show there, "
-                         "using the stabilizer's own motion metadata; frames with no sharper neighbour pass through unchanged."),
-        )
+        schema = _schema("video_stabilizer_sharpness_transfer", "Video Stabilizer Sharpness Transfer",
+                         description=("Pulls the pixels of frames a camera jolt blurred towards what sharper neighbouring frames show there, "
+                                      "using the stabilizer's own motion metadata; frames with no sharper neighbour pass through unchanged."))
         schema.inputs = [
             io.Image.Input("frames", display_name="Frames", tooltip="The original (unstabilized) frames."),
             io.Image.Input("frames_stabilized", display_name="Stabilized Frames"),
@@ -498,132 +529,146 @@ class VideoStabilizerSharpnessTransfer(io.ComfyNode):
 
     @classmethod
     def execute(cls, frames: Any, frames_stabilized: Any, meta: dict, radius: int, alpha: float, padding_mask: Any = None) -> io.NodeOutput:
-        import json
-
-        from . import native, sharpness_transfer, temporal_fill
-
         plan = temporal_fill.plan_from_meta(meta)   # ValueError naming the missing key, before any GPU work
         radius, alpha = sharpness_transfer.check_request(radius, alpha) or (0, 0.0)
         if radius == 0:
             raise ValueError("sharpness transfer: radius=0 transfers nothing; the node needs a radius in 1..16")
         context = hm._normalize_video_input(frames)
         out_context = hm._normalize_video_input(frames_stabilized)
-        n = len(plan["final_matrices"])
-        if len(context.frames) != n or len(out_context.frames) != n:
-            raise ValueError(f"sharpness transfer: meta describes {n} frames, got {len(context.frames)} original and "
-                             f"{len(out_context.frames)} stabilized frames")
-        if (context.width, context.height) != plan["source_size"] or (out_context.width, out_context.height) != plan["output_size"]:
-            raise ValueError(f"sharpness transfer: frame sizes {(context.width, context.height)} -> "
-                             f"{(out_context.width, out_context.height)} do not match the meta's "
-                             f"{plan['source_size']} -> {plan['output_size']}")
+        _check_clips_against_plan("sharpness transfer", plan, context, out_context)
         ctx = native.default_context()
-        torch = ctx.torch
-        src = context.device_batch(ctx)
-        if context.range_pending:   # F0's value-range rule, as the stabilizer applied it to these frames
-            if hm.resolve_value_range(context, hm.prefetch_peaks(ctx.frame_range(src)), ctx):
-                src = context.device_batch(ctx)
+        src = _device_frames(context, ctx)
         # the transfer works in place: on a copy, so the caller's tensor (another node's cached output) stays as it is
         dst = out_context.device_batch(ctx).clone()
-        mask = None
-        if padding_mask is not None:
-            mask = padding_mask if isinstance(padding_mask, torch.Tensor) else torch.from_numpy(np.asarray(padding_mask, dtype=np.float32))
-            mask = mask.to(device=ctx.device, dtype=torch.float32)
-            if mask.ndim == 4:
-                mask = mask[..., 0]
-            if tuple(mask.shape) != tuple(dst.shape[:3]):
-                raise ValueError(f"sharpness transfer: padding_mask {tuple(mask.shape)} does not match the stabilized frames "
-                                 f"{tuple(dst.shape[:3])}")
-            mask = mask.contiguous()
+        mask = None if padding_mask is None else _stabilizer_mask("sharpness transfer", padding_mask, dst, ctx)
         block = sharpness_transfer.transfer_on_device(ctx, src, dst, mask, plan["final_matrices"], plan["transitions"],
                                                       plan["confidences"], radius, alpha)
         return io.NodeOutput(_image_out(dst, out_context), json.dumps({"sharpness_transfer": block}))
 
 
-class VideoStabilizerFlowMasked(io.ComfyNode):
+def _variant_schema(cls, inputs: list, outputs: list) -> io.Schema:
+    schema = _schema(*cls.NODE)
+    schema.inputs, schema.outputs = inputs, outputs
+    return schema
+
+
+# the nine sockets of _estimator_inputs, which are _run_estimator_node's arguments behind the estimator
+_ESTIMATOR_ARGS = ("frames", "frame_rate", "framing_mode", "transform_mode", "camera_lock", "strength", "smooth", "keep_fov",
+                   "padding_color")
+
+
+class _FlowVariant(io.ComfyNode):
+    """An estimator node with the sockets of one `_stabilize_frames` feature.  A subclass states, next to its docstring:
+
+    NODE       (node id, display name, description)
+    ESTIMATOR  the estimator it runs
+    BASE       the node whose inputs it starts from
+    FIXED      {socket id: value}: base sockets it does not show, and what the pipeline gets in their place
+    sockets()  its own sockets, fresh on every call; one with a base socket's id takes that socket's place, the others follow
+    extras()   from the values of every socket behind the base nine (its parameters: their ids in the schema's order, with a
+               default where a caller may leave one out) to the keyword extras of _stabilize_frames
+
+    and gets its schema and an `execute` with the sockets as parameters, positional or by keyword, which hands on through the
+    module's _run_estimator_node as it is at the time of the call."""
+
+    ESTIMATOR = "flow"
+    BASE = VideoStabilizerFlow
+    FIXED: dict = {}
+
+    @staticmethod
+    def sockets() -> list:
+        return []
+
+    def __init_subclass__(cls, **kwargs) -> None:
+        super().__init_subclass__(**kwargs)
+        cls.FIXED = {**getattr(cls.BASE, "FIXED", {}), **cls.FIXED}
+        positional = inspect.Parameter.POSITIONAL_OR_KEYWORD
+        signature = inspect.Signature([inspect.Parameter(name, positional) for name in ("cls",) + _ESTIMATOR_ARGS if name not in cls.FIXED]
+                                      + list(inspect.signature(cls.extras).parameters.values()))
+
+        def execute(cls, *args, **kwargs) -> io.NodeOutput:
+            given = signature.bind(cls, *args, **kwargs)
+            given.apply_defaults()
+            values = {**cls.FIXED, **given.arguments}
+            del values["cls"]
+            nine = [values.pop(name) for name in _ESTIMATOR_ARGS]
+            return _run_estimator_node(cls.ESTIMATOR, *nine, **cls.extras(**values))
+
+        execute.__signature__ = signature
+        cls.execute = classmethod(execute)
+
+    @classmethod
+    def define_schema(cls) -> io.Schema:
+        inputs = {s.id: s for s in cls.BASE.define_schema().inputs}   # in order: a replaced socket keeps its place
+        inputs.update((s.id, s) for s in cls.sockets())
+        return _variant_schema(cls, [s for s in inputs.values() if s.id not in cls.FIXED], _estimator_outputs())
+
+
+def _two_model_transform_mode(tooltip: str, default: str = "similarity"):
+    """`transform_mode` of a variant that cannot run a perspective fit."""
+    return io.Combo.Input("transform_mode", options=["translation", "similarity"], default=default, display_name="Transform Mode",
+                          tooltip=tooltip)
+
+
+class VideoStabilizerFlowMasked(_FlowVariant):
     """The Flow node with an estimation mask: the pixels of `exclude_mask` (a segmentation of the moving subject, or one mask
     for a burnt-in logo) take no part in the camera-motion fit.  Not one of the reference's nodes: it is registered by the
     extension but kept out of NODE_CLASSES."""
 
-    @classmethod
-    def define_schema(cls) -> io.Schema:
-        schema = io.Schema(
-            node_id="video_stabilizer_flow_masked",
-            display_name="Video Stabilizer Flow (Masked)",
-            category="Video/Stabilization",
-            description=("Video Stabilizer Flow that estimates the camera motion from the pixels outside a mask, so that a "
-                         "moving subject in front of the camera does not become the motion that is removed."),
-        )
-        base = VideoStabilizerFlow.define_schema()
-        schema.inputs = list(base.inputs) + [
+    NODE = ("video_stabilizer_flow_masked", "Video Stabilizer Flow (Masked)",
+            "Video Stabilizer Flow that estimates the camera motion from the pixels outside a mask, so that a "
+            "moving subject in front of the camera does not become the motion that is removed.")
+
+    @staticmethod
+    def sockets() -> list:
+        return [
             io.Mask.Input("exclude_mask", display_name="Exclude Mask",
                           tooltip=("Per-frame mask (or one mask for the whole clip) at the frames' resolution; values above "
                                    "0.5 mark pixels the motion estimate must not use.")),
             io.Int.Input("mask_margin", default=16, min=0, max=64, display_name="Mask Margin",
                          tooltip="Safety margin around the mask, in pixels of the estimation image (long side 960)."),
         ]
-        schema.outputs = _estimator_outputs()
-        return schema
 
-    @classmethod
-    def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
-                strength: float, smooth: float, keep_fov: float, padding_color: str, exclude_mask: Any,
-                mask_margin: int) -> io.NodeOutput:
-        return _run_estimator_node("flow", frames, frame_rate, framing_mode, transform_mode, camera_lock, strength, smooth,
-                                   keep_fov, padding_color, estimation_mask=exclude_mask, mask_margin=int(mask_margin))
+    @staticmethod
+    def extras(exclude_mask, mask_margin) -> dict:
+        return dict(estimation_mask=exclude_mask, mask_margin=int(mask_margin))
 
 
-class VideoStabilizerFlowScenes(io.ComfyNode):
+class VideoStabilizerFlowScenes(_FlowVariant):
     """The Flow node on an edited clip: hard cuts are found from the motion-compensated residual of every pair
     (scene_cuts.py) and every shot is stabilized on its own path, under one common framing.  Not one of the reference's
     nodes: it is listed by an extension but kept out of NODE_CLASSES."""
 
-    @classmethod
-    def define_schema(cls) -> io.Schema:
-        from .scene_cuts import DEFAULT_CUT_THRESHOLD
+    NODE = ("video_stabilizer_flow_scenes", "Video Stabilizer Flow (Scene-Aware)",
+            "Video Stabilizer Flow that detects hard cuts and stabilizes each shot separately, so that a cut "
+            "neither enters the camera path nor pushes the frames on both sides of it out of place.")
 
-        schema = io.Schema(
-            node_id="video_stabilizer_flow_scenes",
-            display_name="Video Stabilizer Flow (Scene-Aware)",
-            category="Video/Stabilization",
-            description=("Video Stabilizer Flow that detects hard cuts and stabilizes each shot separately, so that a cut "
-                         "neither enters the camera path nor pushes the frames on both sides of it out of place."),
-        )
-        base = VideoStabilizerFlow.define_schema()
-        schema.inputs = list(base.inputs) + [
-            io.Float.Input("cut_threshold", default=DEFAULT_CUT_THRESHOLD, min=0.0, max=255.0, step=0.1, display_name="Cut Threshold",
+    @staticmethod
+    def sockets() -> list:
+        return [
+            io.Float.Input("cut_threshold", default=scene_cuts.DEFAULT_CUT_THRESHOLD, min=0.0, max=255.0, step=0.1, display_name="Cut Threshold",
                            tooltip=("Mean absolute difference (0..255) of two consecutive frames after motion compensation at "
                                     "and above which the pair is a cut.  0 uses the default, which was calibrated on "
                                     "synthetic clips only: lower it if cuts between similar scenes are missed.")),
         ]
-        schema.outputs = _estimator_outputs()
-        return schema
 
-    @classmethod
-    def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
-                strength: float, smooth: float, keep_fov: float, padding_color: str, cut_threshold: float) -> io.NodeOutput:
-        return _run_estimator_node("flow", frames, frame_rate, framing_mode, transform_mode, camera_lock, strength, smooth,
-                                   keep_fov, padding_color, scene_cuts="auto",
-                                   cut_threshold=float(cut_threshold) if cut_threshold else None)
+    @staticmethod
+    def extras(cut_threshold) -> dict:
+        return dict(scene_cuts="auto", cut_threshold=float(cut_threshold) if cut_threshold else None)
 
 
-class VideoStabilizerFlowMesh(io.ComfyNode):
+class VideoStabilizerFlowMesh(_FlowVariant):
     """The Flow node with a mesh warp behind the global fit: the residual motion one matrix per frame cannot express
     (parallax, rolling-shutter skew, lens breathing) is measured per mesh vertex and smoothed like the global path
     (mesh_warp.py).  Not one of the reference's nodes: it is listed by an extension but kept out of NODE_CLASSES."""
 
-    @classmethod
-    def define_schema(cls) -> io.Schema:
-        from .mesh_warp import CELLS_MAX, CELLS_MIN, DEFAULT_CELLS
+    NODE = ("video_stabilizer_flow_mesh", "Video Stabilizer Flow (Mesh)",
+            "Video Stabilizer Flow that also removes the slow local wobble a single global transform per frame "
+            "leaves behind, with a coarse mesh of per-vertex corrections.")
 
-        schema = io.Schema(
-            node_id="video_stabilizer_flow_mesh",
-            display_name="Video Stabilizer Flow (Mesh)",
-            category="Video/Stabilization",
-            description=("Video Stabilizer Flow that also removes the slow local wobble a single global transform per frame "
-                         "leaves behind, with a coarse mesh of per-vertex corrections."),
-        )
-        base = VideoStabilizerFlow.define_schema()
-        schema.inputs = list(base.inputs) + [
+    @staticmethod
+    def sockets() -> list:
+        return [
             io.Int.Input("mesh_cols", default=DEFAULT_CELLS[0], min=CELLS_MIN, max=CELLS_MAX, display_name="Mesh Columns",
                          tooltip="Cells of the mesh across the frame."),
             io.Int.Input("mesh_rows", default=DEFAULT_CELLS[1], min=CELLS_MIN, max=CELLS_MAX, display_name="Mesh Rows",
@@ -632,81 +677,258 @@ class VideoStabilizerFlowMesh(io.ComfyNode):
                            tooltip=("Largest per-vertex correction in pixels, per axis.  0 uses the default, 1/64 of the frame's "
                                     "width, which has been tried on synthetic clips only: lower it if the picture warps.")),
         ]
-        schema.outputs = _estimator_outputs()
-        return schema
 
-    @classmethod
-    def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
-                strength: float, smooth: float, keep_fov: float, padding_color: str, mesh_cols: int, mesh_rows: int,
-                max_shift: float) -> io.NodeOutput:
-        return _run_estimator_node("flow", frames, frame_rate, framing_mode, transform_mode, camera_lock, strength, smooth,
-                                   keep_fov, padding_color, mesh_warp=(int(mesh_cols), int(mesh_rows)),
-                                   mesh_max_shift=float(max_shift) if max_shift else None)
+    @staticmethod
+    def extras(mesh_cols, mesh_rows, max_shift) -> dict:
+        return dict(mesh_warp=(int(mesh_cols), int(mesh_rows)), mesh_max_shift=float(max_shift) if max_shift else None)
 
 
-class VideoStabilizerFlowMeshMotion(io.ComfyNode):
+class VideoStabilizerFlowMeshMotion(_FlowVariant):
     """The Flow (Mesh) node that also records its per-vertex offsets in the meta (mesh_motion=True), so that Motion Apply
     (Mesh) can apply the same warp to a companion clip or undo it.  Not one of the reference's nodes: it is listed by an
     extension but kept out of NODE_CLASSES."""
 
+    NODE = ("video_stabilizer_flow_mesh_motion", "Video Stabilizer Flow (Mesh Motion)",
+            "Video Stabilizer Flow (Mesh) whose meta also carries the mesh's per-vertex offsets, which Video "
+            "Stabilizer Motion Apply (Mesh) needs to repeat or undo the warp.")
+    BASE = VideoStabilizerFlowMesh
+
+    @staticmethod
+    def extras(mesh_cols, mesh_rows, max_shift) -> dict:
+        return dict(VideoStabilizerFlowMesh.extras(mesh_cols, mesh_rows, max_shift), mesh_motion=True)
+
+
+class VideoStabilizerFlowZoom(_FlowVariant):
+    """The Flow node with a dynamic zoom instead of padding: every frame is zoomed about the centre just enough to hide
+    its own border, and the zoom is smoothed over a window so that it never pumps (dynamic_zoom.py).  Framing is fixed to
+    crop_and_pad.  Not one of the reference's nodes: it is listed by an extension but kept out of NODE_CLASSES."""
+
+    NODE = ("video_stabilizer_flow_zoom", "Video Stabilizer Flow (Dynamic Zoom)",
+            "Video Stabilizer Flow whose borders are hidden by a per-frame zoom that follows the shake: calm "
+            "stretches keep their field of view, only the shaky ones are zoomed in.")
+    FIXED = {"framing_mode": "crop_and_pad"}
+
+    @staticmethod
+    def sockets() -> list:
+        return [
+            io.Float.Input("zoom_window", default=DEFAULT_WINDOW_S, min=0.05, max=WINDOW_MAX_S, step=0.05, display_name="Zoom Window",
+                           tooltip=("Seconds over which the zoom is smoothed: it starts rising this long before a shake and "
+                                    "settles this long after it.  The default has been tried on synthetic clips only.")),
+            io.Float.Input("zoom_limit", default=DEFAULT_ZOOM_LIMIT, min=ZOOM_LIMIT_MIN, max=ZOOM_LIMIT_MAX, step=0.05,
+                           display_name="Zoom Limit",
+                           tooltip=("Largest zoom factor.  Frames that would need more keep some padding, which the padding "
+                                    "mask and the meta report.  The default has been tried on synthetic clips only.")),
+        ]
+
+    @staticmethod
+    def extras(zoom_window, zoom_limit) -> dict:
+        return dict(dynamic_zoom=float(zoom_window), zoom_limit=float(zoom_limit))
+
+
+class VideoStabilizerFlowSubject(_FlowVariant):
+    """The Flow node locked on a subject: `subject_mask` (a per-frame segmentation of a person, face, product or vehicle) is
+    reduced to the subject's centroid and area in every frame (subject_lock.py), and those -- not the camera's motion -- are
+    what the trajectory steadies: with Camera Lock the subject stays where frame 0 shows it.  Not one of the reference's
+    nodes: it is listed by an extension but kept out of NODE_CLASSES."""
+
+    NODE = ("video_stabilizer_subject", "Video Stabilizer Flow (Subject Lock)",
+            "Video Stabilizer Flow that stabilizes on a masked subject instead of the background: the subject is "
+            "held still (Camera Lock) or followed smoothly, without the drift of integrated optical flow.")
+    ESTIMATOR = "subject"
+
+    @staticmethod
+    def sockets() -> list:
+        return [
+            _two_model_transform_mode("translation follows the subject's centroid; similarity also its size (the square root "
+                                      "of the mask's area ratio), without rotation.", default="translation"),
+            io.Mask.Input("subject_mask", display_name="Subject Mask",
+                          tooltip=("Per-frame mask of the subject at the frames' resolution; values above 0.5 are the subject. "
+                                   "Frames without a subject are interpolated from their neighbours.")),
+        ]
+
+    @staticmethod
+    def extras(subject_mask) -> dict:
+        return dict(subject_mask=subject_mask)
+
+
+class VideoStabilizerFlowRolling(_FlowVariant):
+    """The Flow node with the rolling-shutter correction: the final warp samples every source row where a sensor read out
+    row by row showed it, so the lean and wobble that remain once the shake is gone ("jello") are taken out with it
+    (rolling_shutter.py).  Readout 0 estimates the sensor's readout time from the clip.  Not one of the reference's nodes: it
+    is listed by an extension but kept out of NODE_CLASSES."""
+
+    NODE = ("video_stabilizer_flow_rolling", "Video Stabilizer Flow (Rolling Shutter)",
+            "Video Stabilizer Flow that also removes the skew and wobble of a rolling shutter: each row is "
+            "corrected for the time at which the sensor read it.")
+
+    @staticmethod
+    def sockets() -> list:
+        return [
+            _two_model_transform_mode("Select the geometric model fitted to the optical flow.  The row correction is a closed "
+                                      "form of an affine image velocity, so perspective is not offered."),
+            io.Float.Input("readout", default=0.0, min=-1.0, max=1.0, step=0.01, display_name="Readout",
+                           tooltip=("Readout time of the sensor as a fraction of the frame interval; negative for a sensor "
+                                    "read from the bottom up.  0 estimates it from the clip, which needs a clip whose "
+                                    "camera accelerates; the meta reports what was found.")),
+        ]
+
+    @staticmethod
+    def extras(readout=0.0) -> dict:
+        return dict(rolling_shutter="auto" if float(readout) == 0.0 else float(readout))
+
+
+class VideoStabilizerFlowRollingRefit(_FlowVariant):
+    """The Rolling Shutter node with the refit: the pair transitions are fitted a second time on flow samples corrected for
+    the readout, so that the fit no longer takes part of the skew for rotation and scale (rolling_shutter.py).  Not one of the
+    reference's nodes: it is listed by an extension but kept out of NODE_CLASSES."""
+
+    NODE = ("video_stabilizer_flow_rolling_refit", "Video Stabilizer Flow (Rolling Shutter, Refit)",
+            "Video Stabilizer Flow (Rolling Shutter) that also estimates the camera motion a second time on flow "
+            "samples corrected for the sensor's readout.")
+    BASE = VideoStabilizerFlowRolling
+
+    @staticmethod
+    def sockets() -> list:
+        return [
+            io.Boolean.Input("refit", default=True, display_name="Refit",
+                             tooltip=("Fit the frame-to-frame motion again on flow samples corrected for the readout.  Off: "
+                                      "the Rolling Shutter node.")),
+        ]
+
+    @staticmethod
+    def extras(readout=0.0, refit=True) -> dict:
+        return dict(VideoStabilizerFlowRolling.extras(readout), rolling_refit=bool(refit))
+
+
+class VideoStabilizerFlowAnchored(_FlowVariant):
+    """The Flow node with drift correction: every frame is registered directly against a keyframe, so the error of the
+    consecutive-pair estimates no longer adds up along the clip and a locked picture stays put (drift_correction.py).  Not
+    one of the reference's nodes: it is listed by an extension but kept out of NODE_CLASSES."""
+
+    NODE = ("video_stabilizer_flow_anchored", "Video Stabilizer Flow (Drift-Free)",
+            "Video Stabilizer Flow that registers every frame against a keyframe, so that the small error of "
+            "each pair estimate does not accumulate into a creeping picture.")
+
+    @staticmethod
+    def sockets() -> list:
+        return [
+            _two_model_transform_mode("Select the geometric model fitted to the optical flow.  The keyframe alignment updates "
+                                      "a shift, a zoom and a rotation, so perspective is not offered."),
+            io.Int.Input("keyframe_spacing", default=32, min=2, max=4096, step=1, display_name="Keyframe Spacing",
+                         tooltip=("Frames between two keyframes.  Every frame is aligned to the latest keyframe before it and "
+                                  "every keyframe to the previous one; the meta reports how many frames were refined.")),
+        ]
+
+    @staticmethod
+    def extras(keyframe_spacing=32) -> dict:
+        return dict(drift_correction=int(keyframe_spacing))
+
+
+class VideoStabilizerFlowAnchoredExposure(_FlowVariant):
+    """The Drift-Free node for handheld footage: the keyframe alignment also estimates a gain and an offset per frame, so that
+    auto-exposure does not defeat it, and leaves the pixels of an optional `exclude_mask` out (drift_correction.py).  Not one
+    of the reference's nodes: it is listed by an extension but kept out of NODE_CLASSES."""
+
+    NODE = ("video_stabilizer_flow_anchored_exposure", "Video Stabilizer Flow (Drift-Free, Exposure-Matched)",
+            "Video Stabilizer Flow (Drift-Free) whose keyframe alignment follows the camera's auto-exposure and "
+            "ignores a masked moving subject.")
+    BASE = VideoStabilizerFlowAnchored
+
+    @staticmethod
+    def sockets() -> list:
+        return [
+            io.Boolean.Input("match_exposure", default=True, display_name="Match Exposure",
+                             tooltip=("Estimate a brightness gain and offset of every frame against its keyframe next to the "
+                                      "motion; the meta reports them.")),
+            io.Mask.Input("exclude_mask", display_name="Exclude Mask", optional=True,
+                          tooltip=("Per-frame mask (or one mask for the whole clip) at the frames' resolution; values above "
+                                   "0.5 mark pixels neither the motion estimate nor the keyframe alignment may use.")),
+            io.Int.Input("mask_margin", default=16, min=0, max=64, display_name="Mask Margin",
+                         tooltip="Safety margin around the mask, in pixels of the estimation image (long side 960)."),
+        ]
+
+    @staticmethod
+    def extras(keyframe_spacing=32, match_exposure=True, exclude_mask=None, mask_margin=16) -> dict:
+        masked = {} if exclude_mask is None else dict(estimation_mask=exclude_mask, mask_margin=int(mask_margin), drift_mask=True)
+        return dict(VideoStabilizerFlowAnchored.extras(keyframe_spacing), drift_exposure=True if match_exposure else None, **masked)
+
+
+class VideoStabilizerFlowLevel(_FlowVariant):
+    """The Flow node that also levels the picture: the roll of every frame is measured from the orientation of its edges,
+    one offset per shot -- or one that varies slowly -- is taken from it, and every frame is turned upright about the centre
+    (horizon_level.py).  Framing is fixed to crop_and_pad.  Not one of the reference's nodes: it is listed by an extension but
+    kept out of NODE_CLASSES."""
+
+    NODE = ("video_stabilizer_flow_level", "Video Stabilizer Flow (Horizon Level)",
+            "Video Stabilizer Flow that also levels the horizon: a clip shot a few degrees off level comes out "
+            "steady and upright.")
+    FIXED = {"framing_mode": "crop_and_pad"}
+
+    @staticmethod
+    def sockets() -> list:
+        return [
+            _two_model_transform_mode("Select the geometric model fitted to the optical flow.  A homography has no single roll, "
+                                      "so perspective is not offered."),
+            io.Float.Input("level_window", default=0.0, min=0.0, max=LEVEL_WINDOW_MAX_S, step=0.05, display_name="Level Window",
+                           tooltip=("Seconds over which the roll offset may vary, for a camera that slowly tips over.  0 takes "
+                                    "one offset for every shot.")),
+            io.Float.Input("level_limit", default=DEFAULT_LIMIT_DEG, min=0.5, max=LIMIT_MAX_DEG - 0.5, step=0.5,
+                           display_name="Level Limit",
+                           tooltip=("Largest correction in degrees.  Edges give the roll modulo 90 degrees only, so it stays "
+                                    "below 45.  The default has been tried on synthetic clips only.")),
+        ]
+
+    @staticmethod
+    def extras(level_window=0.0, level_limit=DEFAULT_LIMIT_DEG) -> dict:
+        return dict(horizon_level=True if float(level_window) == 0.0 else float(level_window), horizon_limit=float(level_limit))
+
+
+class _ApplyVariant(io.ComfyNode):
+    """Motion Apply for a run whose warp is more than one matrix per frame.  A subclass states NODE as a Flow variant does and
+    REPLAY, the keyword of apply_motion that selects its replay.  Bilinear, no motion blur."""
+
+    REPLAY: dict = {}
+
     @classmethod
     def define_schema(cls) -> io.Schema:
-        base = VideoStabilizerFlowMesh.define_schema()
-        schema = io.Schema(
-            node_id="video_stabilizer_flow_mesh_motion",
-            display_name="Video Stabilizer Flow (Mesh Motion)",
-            category="Video/Stabilization",
-            description=("Video Stabilizer Flow (Mesh) whose meta also carries the mesh's per-vertex offsets, which Video "
-                         "Stabilizer Motion Apply (Mesh) needs to repeat or undo the warp."),
-        )
-        schema.inputs = list(base.inputs)
-        schema.outputs = _estimator_outputs()
-        return schema
-
-    @classmethod
-    def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
-                strength: float, smooth: float, keep_fov: float, padding_color: str, mesh_cols: int, mesh_rows: int,
-                max_shift: float) -> io.NodeOutput:
-        return _run_estimator_node("flow", frames, frame_rate, framing_mode, transform_mode, camera_lock, strength, smooth,
-                                   keep_fov, padding_color, mesh_warp=(int(mesh_cols), int(mesh_rows)),
-                                   mesh_max_shift=float(max_shift) if max_shift else None, mesh_motion=True)
-
-
-class VideoStabilizerMotionApplyMesh(io.ComfyNode):
-    """Motion Apply for a mesh-warped run (apply_motion's mesh=True): on the run's source frames (or a companion clip of
-    their size) it applies the recorded matrices and mesh again, on its stabilized frames it restores the original camera
-    motion through the mesh warp's per-pixel inverse.  Bilinear, no motion blur.  Not one of the reference's nodes."""
-
-    @classmethod
-    def define_schema(cls) -> io.Schema:
-        schema = io.Schema(
-            node_id="video_stabilizer_motion_apply_mesh",
-            display_name="Video Stabilizer Motion Apply (Mesh)",
-            category="Video/Stabilization",
-            description=("Applies or undoes the motion of a Video Stabilizer Flow (Mesh Motion) run, per-vertex mesh "
-                         "corrections included, and emits a padding mask."),
-        )
-        schema.inputs = [
+        return _variant_schema(cls, [
             io.Image.Input("frames", display_name="Frames"),
             JSONType.Input("meta", display_name="Meta"),
             io.Combo.Input("framing_mode", options=["crop_and_pad", "expand"], default="crop_and_pad",
                            display_name="Framing Mode"),
             io.Color.Input("padding_color", default="#7F7F7F", display_name="Padding Color",
                            tooltip="HEX padding color used where warping exposes empty pixels."),
-        ]
-        schema.outputs = [
-            io.Image.Output("frames", display_name="Frames"),
-            io.Mask.Output("padding_mask", display_name="Padding Mask"),
-            JSONType.Output("meta", display_name="Meta"),
-        ]
-        return schema
+        ], _clip_outputs())
 
     @classmethod
     def execute(cls, frames: Any, meta: dict, framing_mode: str, padding_color: str) -> io.NodeOutput:
         context = hm._normalize_video_input(frames)
         result = apply_motion(context, meta, hm._parse_padding_color(padding_color), framing_mode=framing_mode,
-                              interpolation="bilinear", keep_on_device=True, mesh=True)
+                              interpolation="bilinear", keep_on_device=True, **cls.REPLAY)
         return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
+
+
+class VideoStabilizerMotionApplyMesh(_ApplyVariant):
+    """Motion Apply for a mesh-warped run (apply_motion's mesh=True): on the run's source frames (or a companion clip of
+    their size) it applies the recorded matrices and mesh again, on its stabilized frames it restores the original camera
+    motion through the mesh warp's per-pixel inverse.  Bilinear, no motion blur.  Not one of the reference's nodes."""
+
+    NODE = ("video_stabilizer_motion_apply_mesh", "Video Stabilizer Motion Apply (Mesh)",
+            "Applies or undoes the motion of a Video Stabilizer Flow (Mesh Motion) run, per-vertex mesh "
+            "corrections included, and emits a padding mask.")
+    REPLAY = {"mesh": True}
+
+
+class VideoStabilizerMotionApplyRolling(_ApplyVariant):
+    """Motion Apply for a rolling-shutter run (apply_motion's rolling=True): on the run's source frames (or a companion clip
+    of their size) it applies the recorded matrices and row correction again, on its stabilized frames it restores the
+    original camera motion and skew through the rolling warp's closed-form inverse.  Bilinear, no motion blur.  Not one of the
+    reference's nodes: it is listed by an extension but kept out of NODE_CLASSES."""
+
+    NODE = ("video_stabilizer_motion_apply_rolling", "Video Stabilizer Motion Apply (Rolling Shutter)",
+            "Applies or undoes the motion of a Video Stabilizer Flow (Rolling Shutter) run, per-row readout "
+            "correction included, and emits a padding mask.")
+    REPLAY = {"rolling": True}
 
 
 class VideoStabilizerPaddingFill(io.ComfyNode):
@@ -717,14 +939,10 @@ class VideoStabilizerPaddingFill(io.ComfyNode):
 
     @classmethod
     def define_schema(cls) -> io.Schema:
-        schema = io.Schema(
-            node_id="video_stabilizer_padding_fill",
-            display_name="Video Stabilizer Padding Fill",
-            category="Video/Stabilization",
-            description=("Fills the padding a stabilizer left with a smooth continuation of each frame's own content "
-                         "(push-pull), a far better start for an in-painter than a flat colour; the padding mask still "
-                         "marks the invented pixels."),
-        )
+        schema = _schema("video_stabilizer_padding_fill", "Video Stabilizer Padding Fill",
+                         description=("Fills the padding a stabilizer left with a smooth continuation of each frame's own content "
+                                      "(push-pull), a far better start for an in-painter than a flat colour; the padding mask still "
+                                      "marks the invented pixels."))
         schema.inputs = [
             io.Image.Input("frames", display_name="Frames", tooltip="Stabilized frames with padding."),
             io.Mask.Input("padding_mask", display_name="Padding Mask", tooltip="[N,H,W], or [1,H,W] for every frame."),
@@ -737,35 +955,12 @@ class VideoStabilizerPaddingFill(io.ComfyNode):
 
     @classmethod
     def execute(cls, frames: Any, padding_mask: Any) -> io.NodeOutput:
-        import json
-
-        from . import native, spatial_fill
-
         context = hm._normalize_video_input(frames)
-        n, h, w = len(context.frames), context.height, context.width
-        # every check comes before any GPU work
-        if n == 0:
-            raise ValueError("padding fill: socket 'frames' holds no frame")
-        if not (hasattr(padding_mask, "dtype") and hasattr(padding_mask, "shape")):
-            raise ValueError(f"padding fill: socket 'padding_mask' must be a floating-point MASK tensor, got {type(padding_mask).__name__}")
-        if "float" not in str(padding_mask.dtype):
-            raise ValueError(f"padding fill: socket 'padding_mask' must be a floating-point MASK, got {padding_mask.dtype}")
-        shape = tuple(int(v) for v in padding_mask.shape)
-        if len(shape) == 4 and shape[3] == 1:
-            shape = shape[:3]
-        if len(shape) != 3 or shape[1:] != (h, w) or shape[0] not in (1, n):
-            raise ValueError(f"padding fill: socket 'padding_mask' of shape {tuple(padding_mask.shape)} does not match socket "
-                             f"'frames' [{n},{h},{w},3]: expected [{n},{h},{w}] or [1,{h},{w}]")
+        dims, lead = _check_clip_and_mask("padding fill", context, padding_mask, optional=False)
         ctx = native.default_context()
-        torch = ctx.torch
-        src = context.device_batch(ctx)
-        if context.range_pending:   # F0's value-range rule, as every node of the package applies it to its frames
-            if hm.resolve_value_range(context, hm.prefetch_peaks(ctx.frame_range(src)), ctx):
-                src = context.device_batch(ctx)
         # the fill works in place: on a copy, so the caller's tensor (another node's cached output) stays as it is
-        dst = src.clone()
-        mask = padding_mask if isinstance(padding_mask, torch.Tensor) else torch.from_numpy(np.asarray(padding_mask))
-        mask = mask.to(device=ctx.device, dtype=torch.float32).reshape((shape[0], h, w)).expand(n, h, w).contiguous()
+        dst = _device_frames(context, ctx).clone()
+        mask = _place_socket_mask(padding_mask, lead, dims, ctx)
         block = spatial_fill.fill_on_device(ctx, dst, mask)
         return io.NodeOutput(_image_out(dst, context), json.dumps({"spatial_fill": block}))
 
@@ -777,13 +972,9 @@ class VideoStabilizerStabilityReport(io.ComfyNode):
 
     @classmethod
     def define_schema(cls) -> io.Schema:
-        schema = io.Schema(
-            node_id="video_stabilizer_stability_report",
-            display_name="Video Stabilizer Stability Report",
-            category="Video/Stabilization",
-            description=("Mean PSNR between consecutive frames (ITF) over the pixels both frames really show; with the "
-                         "unstabilized clip connected, also its ITF and the gain in dB."),
-        )
+        schema = _schema("video_stabilizer_stability_report", "Video Stabilizer Stability Report",
+                         description=("Mean PSNR between consecutive frames (ITF) over the pixels both frames really show; with the "
+                                      "unstabilized clip connected, also its ITF and the gain in dB."))
         schema.inputs = [
             io.Image.Input("frames", display_name="Frames", tooltip="The clip to measure, e.g. stabilized frames."),
             io.Mask.Input("padding_mask", display_name="Padding Mask", optional=True,
@@ -796,296 +987,16 @@ class VideoStabilizerStabilityReport(io.ComfyNode):
 
     @classmethod
     def execute(cls, frames: Any, padding_mask: Any = None, reference_frames: Any = None) -> io.NodeOutput:
-        import json
-
-        from . import native, stability
-
         context = hm._normalize_video_input(frames)
-        n, h, w = len(context.frames), context.height, context.width
-        # every check comes before any GPU work
-        if n == 0:
-            raise ValueError("stability report: socket 'frames' holds no frame")
-        shape = None
-        if padding_mask is not None:
-            if not (hasattr(padding_mask, "dtype") and hasattr(padding_mask, "shape")):
-                raise ValueError(f"stability report: socket 'padding_mask' must be a floating-point MASK tensor, got {type(padding_mask).__name__}")
-            if "float" not in str(padding_mask.dtype):
-                raise ValueError(f"stability report: socket 'padding_mask' must be a floating-point MASK, got {padding_mask.dtype}")
-            shape = tuple(int(v) for v in padding_mask.shape)
-            if len(shape) == 4 and shape[3] == 1:
-                shape = shape[:3]
-            if len(shape) != 3 or shape[1:] != (h, w) or shape[0] not in (1, n):
-                raise ValueError(f"stability report: socket 'padding_mask' of shape {tuple(padding_mask.shape)} does not match "
-                                 f"socket 'frames' [{n},{h},{w},3]: expected [{n},{h},{w}] or [1,{h},{w}]")
+        dims, lead = _check_clip_and_mask("stability report", context, padding_mask)
         reference = None if reference_frames is None else hm._normalize_video_input(reference_frames)
         if reference is not None and len(reference.frames) == 0:
             raise ValueError("stability report: socket 'reference_frames' holds no frame")
         ctx = native.default_context()
-        torch = ctx.torch
-
-        def on_device(video):   # F0's value-range rule, as every node of the package applies it to its frames
-            batch = video.device_batch(ctx)
-            if video.range_pending and hm.resolve_value_range(video, hm.prefetch_peaks(ctx.frame_range(batch)), ctx):
-                batch = video.device_batch(ctx)
-            return batch
-
-        mask = None
-        if padding_mask is not None:
-            mask = padding_mask if isinstance(padding_mask, torch.Tensor) else torch.from_numpy(np.asarray(padding_mask))
-            mask = mask.to(device=ctx.device, dtype=torch.float32).reshape((shape[0], h, w)).expand(n, h, w).contiguous()
-        after = stability.itf(on_device(context), mask, ctx=ctx)
-        before = None if reference is None else stability.itf(on_device(reference), None, ctx=ctx)
+        mask = _place_socket_mask(padding_mask, lead, dims, ctx)
+        after = stability.itf(_device_frames(context, ctx), mask, ctx=ctx)
+        before = None if reference is None else stability.itf(_device_frames(reference, ctx), None, ctx=ctx)
         return io.NodeOutput(json.dumps({"stability": stability.report_block(before, after)}))
-
-
-class VideoStabilizerFlowZoom(io.ComfyNode):
-    """The Flow node with a dynamic zoom instead of padding: every frame is zoomed about the centre just enough to hide
-    its own border, and the zoom is smoothed over a window so that it never pumps (dynamic_zoom.py).  Framing is fixed to
-    crop_and_pad.  Not one of the reference's nodes: it is listed by an extension but kept out of NODE_CLASSES."""
-
-    @classmethod
-    def define_schema(cls) -> io.Schema:
-        from .dynamic_zoom import DEFAULT_WINDOW_S, DEFAULT_ZOOM_LIMIT, WINDOW_MAX_S, ZOOM_LIMIT_MAX, ZOOM_LIMIT_MIN
-
-        schema = io.Schema(
-            node_id="video_stabilizer_flow_zoom",
-            display_name="Video Stabilizer Flow (Dynamic Zoom)",
-            category="Video/Stabilization",
-            description=("Video Stabilizer Flow whose borders are hidden by a per-frame zoom that follows the shake: calm "
-                         "stretches keep their field of view, only the shaky ones are zoomed in."),
-        )
-        base = VideoStabilizerFlow.define_schema()
-        schema.inputs = [s for s in base.inputs if s.id != "framing_mode"] + [
-            io.Float.Input("zoom_window", default=DEFAULT_WINDOW_S, min=0.05, max=WINDOW_MAX_S, step=0.05, display_name="Zoom Window",
-                           tooltip=("Seconds over which the zoom is smoothed: it starts rising this long before a shake and "
-                                    "settles this long after it.  The default has been tried on synthetic clips only.")),
-            io.Float.Input("zoom_limit", default=DEFAULT_ZOOM_LIMIT, min=ZOOM_LIMIT_MIN, max=ZOOM_LIMIT_MAX, step=0.05,
-                           display_name="Zoom Limit",
-                           tooltip=("Largest zoom factor.  Frames that would need more keep some padding, which the padding "
-                                    "mask and the meta report.  The default has been tried on synthetic clips only.")),
-        ]
-        schema.outputs = _estimator_outputs()
-        return schema
-
-    @classmethod
-    def execute(cls, frames: Any, frame_rate: float, transform_mode: str, camera_lock: bool, strength: float, smooth: float,
-                keep_fov: float, padding_color: str, zoom_window: float, zoom_limit: float) -> io.NodeOutput:
-        return _run_estimator_node("flow", frames, frame_rate, "crop_and_pad", transform_mode, camera_lock, strength, smooth,
-                                   keep_fov, padding_color, dynamic_zoom=float(zoom_window), zoom_limit=float(zoom_limit))
-
-
-class VideoStabilizerFlowSubject(io.ComfyNode):
-    """The Flow node locked on a subject: `subject_mask` (a per-frame segmentation of a person, face, product or vehicle) is
-    reduced to the subject's centroid and area in every frame (subject_lock.py), and those -- not the camera's motion -- are
-    what the trajectory steadies: with Camera Lock the subject stays where frame 0 shows it.  Not one of the reference's
-    nodes: it is listed by an extension but kept out of NODE_CLASSES."""
-
-    @classmethod
-    def define_schema(cls) -> io.Schema:
-        schema = io.Schema(
-            node_id="video_stabilizer_subject",
-            display_name="Video Stabilizer Flow (Subject Lock)",
-            category="Video/Stabilization",
-            description=("Video Stabilizer Flow that stabilizes on a masked subject instead of the background: the subject is "
-                         "held still (Camera Lock) or followed smoothly, without the drift of integrated optical flow."),
-        )
-        base = VideoStabilizerFlow.define_schema()
-        schema.inputs = [
-            io.Combo.Input("transform_mode", options=["translation", "similarity"], default="translation",
-                           display_name="Transform Mode",
-                           tooltip=("translation follows the subject's centroid; similarity also its size (the square root "
-                                    "of the mask's area ratio), without rotation."))
-            if s.id == "transform_mode" else s for s in base.inputs] + [
-            io.Mask.Input("subject_mask", display_name="Subject Mask",
-                          tooltip=("Per-frame mask of the subject at the frames' resolution; values above 0.5 are the subject. "
-                                   "Frames without a subject are interpolated from their neighbours.")),
-        ]
-        schema.outputs = _estimator_outputs()
-        return schema
-
-    @classmethod
-    def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
-                strength: float, smooth: float, keep_fov: float, padding_color: str, subject_mask: Any) -> io.NodeOutput:
-        return _run_estimator_node("subject", frames, frame_rate, framing_mode, transform_mode, camera_lock, strength, smooth,
-                                   keep_fov, padding_color, subject_mask=subject_mask)
-
-
-class VideoStabilizerFlowRolling(io.ComfyNode):
-    """The Flow node with the rolling-shutter correction: the final warp samples every source row where a sensor read out
-    row by row showed it, so the lean and wobble that remain once the shake is gone ("jello") are taken out with it
-    (rolling_shutter.py).  Readout 0 estimates the sensor's readout time from the clip.  Not one of the reference's nodes: it
-    is listed by an extension but kept out of NODE_CLASSES."""
-
-    @classmethod
-    def define_schema(cls) -> io.Schema:
-        schema = io.Schema(
-            node_id="video_stabilizer_flow_rolling",
-            display_name="Video Stabilizer Flow (Rolling Shutter)",
-            category="Video/Stabilization",
-            description=("Video Stabilizer Flow that also removes the skew and wobble of a rolling shutter: each row is "
-                         "corrected for the time at which the sensor read it."),
-        )
-        base = VideoStabilizerFlow.define_schema()
-        schema.inputs = [
-            io.Combo.Input("transform_mode", options=["translation", "similarity"], default="similarity",
-                           display_name="Transform Mode",
-                           tooltip=("Select the geometric model fitted to the optical flow.  The row correction is a closed "
-                                    "form of an affine image velocity, so perspective is not offered."))
-            if s.id == "transform_mode" else s for s in base.inputs] + [
-            io.Float.Input("readout", default=0.0, min=-1.0, max=1.0, step=0.01, display_name="Readout",
-                           tooltip=("Readout time of the sensor as a fraction of the frame interval; negative for a sensor "
-                                    "read from the bottom up.  0 estimates it from the clip, which needs a clip whose "
-                                    "camera accelerates; the meta reports what was found.")),
-        ]
-        schema.outputs = _estimator_outputs()
-        return schema
-
-    @classmethod
-    def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
-                strength: float, smooth: float, keep_fov: float, padding_color: str, readout: float = 0.0) -> io.NodeOutput:
-        return _run_estimator_node("flow", frames, frame_rate, framing_mode, transform_mode, camera_lock, strength, smooth,
-                                   keep_fov, padding_color, rolling_shutter="auto" if float(readout) == 0.0 else float(readout))
-
-
-class VideoStabilizerFlowRollingRefit(io.ComfyNode):
-    """The Rolling Shutter node with the refit: the pair transitions are fitted a second time on flow samples corrected for
-    the readout, so that the fit no longer takes part of the skew for rotation and scale (rolling_shutter.py).  Not one of the
-    reference's nodes: it is listed by an extension but kept out of NODE_CLASSES."""
-
-    @classmethod
-    def define_schema(cls) -> io.Schema:
-        schema = io.Schema(
-            node_id="video_stabilizer_flow_rolling_refit",
-            display_name="Video Stabilizer Flow (Rolling Shutter, Refit)",
-            category="Video/Stabilization",
-            description=("Video Stabilizer Flow (Rolling Shutter) that also estimates the camera motion a second time on flow "
-                         "samples corrected for the sensor's readout."),
-        )
-        schema.inputs = VideoStabilizerFlowRolling.define_schema().inputs + [
-            io.Boolean.Input("refit", default=True, display_name="Refit",
-                             tooltip=("Fit the frame-to-frame motion again on flow samples corrected for the readout.  Off: "
-                                      "the Rolling Shutter node.")),
-        ]
-        schema.outputs = _estimator_outputs()
-        return schema
-
-    @classmethod
-    def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
-                strength: float, smooth: float, keep_fov: float, padding_color: str, readout: float = 0.0,
-                refit: bool = True) -> io.NodeOutput:
-        return _run_estimator_node("flow", frames, frame_rate, framing_mode, transform_mode, camera_lock, strength, smooth,
-                                   keep_fov, padding_color, rolling_shutter="auto" if float(readout) == 0.0 else float(readout),
-                                   rolling_refit=bool(refit))
-
-
-class VideoStabilizerFlowAnchored(io.ComfyNode):
-    """The Flow node with drift correction: every frame is registered directly against a keyframe, so the error of the
-    consecutive-pair estimates no longer adds up along the clip and a locked picture stays put (drift_correction.py).  Not
-    one of the reference's nodes: it is listed by an extension but kept out of NODE_CLASSES."""
-
-    @classmethod
-    def define_schema(cls) -> io.Schema:
-        schema = io.Schema(
-            node_id="video_stabilizer_flow_anchored",
-            display_name="Video Stabilizer Flow (Drift-Free)",
-            category="Video/Stabilization",
-            description=("Video Stabilizer Flow that registers every frame against a keyframe, so that the small error of "
-                         "each pair estimate does not accumulate into a creeping picture."),
-        )
-        base = VideoStabilizerFlow.define_schema()
-        schema.inputs = [
-            io.Combo.Input("transform_mode", options=["translation", "similarity"], default="similarity",
-                           display_name="Transform Mode",
-                           tooltip=("Select the geometric model fitted to the optical flow.  The keyframe alignment updates "
-                                    "a shift, a zoom and a rotation, so perspective is not offered."))
-            if s.id == "transform_mode" else s for s in base.inputs] + [
-            io.Int.Input("keyframe_spacing", default=32, min=2, max=4096, step=1, display_name="Keyframe Spacing",
-                         tooltip=("Frames between two keyframes.  Every frame is aligned to the latest keyframe before it and "
-                                  "every keyframe to the previous one; the meta reports how many frames were refined.")),
-        ]
-        schema.outputs = _estimator_outputs()
-        return schema
-
-    @classmethod
-    def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
-                strength: float, smooth: float, keep_fov: float, padding_color: str, keyframe_spacing: int = 32) -> io.NodeOutput:
-        return _run_estimator_node("flow", frames, frame_rate, framing_mode, transform_mode, camera_lock, strength, smooth,
-                                   keep_fov, padding_color, drift_correction=int(keyframe_spacing))
-
-
-class VideoStabilizerFlowAnchoredExposure(io.ComfyNode):
-    """The Drift-Free node for handheld footage: the keyframe alignment also estimates a gain and an offset per frame, so that
-    auto-exposure does not defeat it, and leaves the pixels of an optional `exclude_mask` out (drift_correction.py).  Not one
-    of the reference's nodes: it is listed by an extension but kept out of NODE_CLASSES."""
-
-    @classmethod
-    def define_schema(cls) -> io.Schema:
-        schema = io.Schema(
-            node_id="video_stabilizer_flow_anchored_exposure",
-            display_name="Video Stabilizer Flow (Drift-Free, Exposure-Matched)",
-            category="Video/Stabilization",
-            description=("Video Stabilizer Flow (Drift-Free) whose keyframe alignment follows the camera's auto-exposure and "
-                         "ignores a masked moving subject."),
-        )
-        schema.inputs = list(VideoStabilizerFlowAnchored.define_schema().inputs) + [
-            io.Boolean.Input("match_exposure", default=True, display_name="Match Exposure",
-                             tooltip=("Estimate a brightness gain and offset of every frame against its keyframe next to the "
-                                      "motion; the meta reports them.")),
-            io.Mask.Input("exclude_mask", display_name="Exclude Mask", optional=True,
-                          tooltip=("Per-frame mask (or one mask for the whole clip) at the frames' resolution; values above "
-                                   "0.5 mark pixels neither the motion estimate nor the keyframe alignment may use.")),
-            io.Int.Input("mask_margin", default=16, min=0, max=64, display_name="Mask Margin",
-                         tooltip="Safety margin around the mask, in pixels of the estimation image (long side 960)."),
-        ]
-        schema.outputs = _estimator_outputs()
-        return schema
-
-    @classmethod
-    def execute(cls, frames: Any, frame_rate: float, framing_mode: str, transform_mode: str, camera_lock: bool,
-                strength: float, smooth: float, keep_fov: float, padding_color: str, keyframe_spacing: int = 32,
-                match_exposure: bool = True, exclude_mask: Any = None, mask_margin: int = 16) -> io.NodeOutput:
-        masked = {} if exclude_mask is None else dict(estimation_mask=exclude_mask, mask_margin=int(mask_margin), drift_mask=True)
-        return _run_estimator_node("flow", frames, frame_rate, framing_mode, transform_mode, camera_lock, strength, smooth,
-                                   keep_fov, padding_color, drift_correction=int(keyframe_spacing),
-                                   drift_exposure=True if match_exposure else None, **masked)
-
-
-class VideoStabilizerMotionApplyRolling(io.ComfyNode):
-    """Motion Apply for a rolling-shutter run (apply_motion's rolling=True): on the run's source frames (or a companion clip
-    of their size) it applies the recorded matrices and row correction again, on its stabilized frames it restores the
-    original camera motion and skew through the rolling warp's closed-form inverse.  Bilinear, no motion blur.  Not one of the
-    reference's nodes: it is listed by an extension but kept out of NODE_CLASSES."""
-
-    @classmethod
-    def define_schema(cls) -> io.Schema:
-        schema = io.Schema(
-            node_id="video_stabilizer_motion_apply_rolling",
-            display_name="Video Stabilizer Motion Apply (Rolling Shutter)",
-            category="Video/Stabilization",
-            description=("Applies or undoes the motion of a Video Stabilizer Flow (Rolling Shutter) run, per-row readout "
-                         "correction included, and emits a padding mask."),
-        )
-        schema.inputs = [
-            io.Image.Input("frames", display_name="Frames"),
-            JSONType.Input("meta", display_name="Meta"),
-            io.Combo.Input("framing_mode", options=["crop_and_pad", "expand"], default="crop_and_pad",
-                           display_name="Framing Mode"),
-            io.Color.Input("padding_color", default="#7F7F7F", display_name="Padding Color",
-                           tooltip="HEX padding color used where warping exposes empty pixels."),
-        ]
-        schema.outputs = [
-            io.Image.Output("frames", display_name="Frames"),
-            io.Mask.Output("padding_mask", display_name="Padding Mask"),
-            JSONType.Output("meta", display_name="Meta"),
-        ]
-        return schema
-
-    @classmethod
-    def execute(cls, frames: Any, meta: dict, framing_mode: str, padding_color: str) -> io.NodeOutput:
-        context = hm._normalize_video_input(frames)
-        result = apply_motion(context, meta, hm._parse_padding_color(padding_color), framing_mode=framing_mode,
-                              interpolation="bilinear", keep_on_device=True, rolling=True)
-        return io.NodeOutput(_image_out(result.frames, context), _mask_out(result.masks), result.meta)
 
 
 NODE_CLASSES = [VideoStabilizerClassic, VideoStabilizerFlow, VideoStabilizerMotionApply, VideoStabilizerShakeGenerator,
@@ -1100,13 +1011,9 @@ class VideoStabilizerMaskGrow(io.ComfyNode):
 
     @classmethod
     def define_schema(cls) -> io.Schema:
-        schema = io.Schema(
-            node_id="video_stabilizer_mask_grow",
-            display_name="Video Stabilizer Mask Grow",
-            category="Video/Stabilization",
-            description=("Grows (or shrinks) a padding mask as GrowMask does, on the GPU, optionally holds it over neighbouring "
-                         "frames so the repaint region stands still, and feathers its edge outwards."),
-        )
+        schema = _schema("video_stabilizer_mask_grow", "Video Stabilizer Mask Grow",
+                         description=("Grows (or shrinks) a padding mask as GrowMask does, on the GPU, optionally holds it over neighbouring "
+                                      "frames so the repaint region stands still, and feathers its edge outwards."))
         schema.inputs = [
             io.Mask.Input("mask", display_name="Mask", tooltip="[N,H,W] or [H,W]."),
             io.Int.Input("expand", default=5, min=-64, max=64, step=1, display_name="Expand",
@@ -1123,8 +1030,6 @@ class VideoStabilizerMaskGrow(io.ComfyNode):
 
     @classmethod
     def execute(cls, mask: Any, expand: int = 5, tapered_corners: bool = True, feather: int = 0, hold: int = 0) -> io.NodeOutput:
-        from . import mask_handoff, native
-
         # every check comes before any GPU work
         request = mask_handoff.check_request(expand, feather, hold, tapered_corners)
         if not (hasattr(mask, "dtype") and hasattr(mask, "shape")):
@@ -1154,13 +1059,9 @@ class VideoStabilizerDeflicker(io.ComfyNode):
 
     @classmethod
     def define_schema(cls) -> io.Schema:
-        schema = io.Schema(
-            node_id="video_stabilizer_deflicker",
-            display_name="Video Stabilizer Deflicker",
-            category="Video/Stabilization",
-            description=("Measures the exposure change between consecutive frames on registered pixels, robustly against moving "
-                         "subjects, and multiplies every frame by the high-pass of that chain; a deliberate exposure ramp stays."),
-        )
+        schema = _schema("video_stabilizer_deflicker", "Video Stabilizer Deflicker",
+                         description=("Measures the exposure change between consecutive frames on registered pixels, robustly against moving "
+                                      "subjects, and multiplies every frame by the high-pass of that chain; a deliberate exposure ramp stays."))
         schema.inputs = [
             io.Image.Input("frames", display_name="Frames", tooltip="The original (unstabilized) frames."),
             io.Image.Input("frames_stabilized", display_name="Stabilized Frames",
@@ -1183,11 +1084,6 @@ class VideoStabilizerDeflicker(io.ComfyNode):
     @classmethod
     def execute(cls, frames: Any, frames_stabilized: Any, padding_mask: Any = None, meta: Any = None, window: float = 1.0,
                 mode: str = "exposure") -> io.NodeOutput:
-        import json
-
-        from . import deflicker, native, scene_cuts, temporal_fill
-        from .flow_pipeline import _fps_fields
-
         # every check comes before any GPU work
         request = deflicker.check_request(window, mode)
         if request is None:
@@ -1203,10 +1099,7 @@ class VideoStabilizerDeflicker(io.ComfyNode):
             plan = temporal_fill.plan_from_meta(meta)   # ValueError naming the missing key
             if len(plan["final_matrices"]) != n:
                 raise ValueError(f"deflicker: meta describes {len(plan['final_matrices'])} frames, got {n}")
-            if (context.width, context.height) != plan["source_size"] or (out_context.width, out_context.height) != plan["output_size"]:
-                raise ValueError(f"deflicker: frame sizes {(context.width, context.height)} -> "
-                                 f"{(out_context.width, out_context.height)} do not match the meta's "
-                                 f"{plan['source_size']} -> {plan['output_size']}")
+            _check_clips_against_plan("deflicker", plan, context, out_context)   # (the sizes: both clips have the plan's n frames)
             transitions, confidences = plan["transitions"], plan["confidences"]
             fps = meta.get("fps_effective")
             if isinstance(meta.get("scene_cuts"), dict) and meta["scene_cuts"].get("cuts"):
@@ -1215,71 +1108,12 @@ class VideoStabilizerDeflicker(io.ComfyNode):
             transitions, confidences, fps = np.tile(np.eye(3, dtype=np.float32), (n - 1, 1, 1)), np.ones(n - 1), None
         fps_effective = _fps_fields(context, fps)[0]
         ctx = native.default_context()
-        torch = ctx.torch
-
-        def on_device(video):   # F0's value-range rule, as every node of the package applies it to its frames
-            batch = video.device_batch(ctx)
-            if video.range_pending and hm.resolve_value_range(video, hm.prefetch_peaks(ctx.frame_range(batch)), ctx):
-                batch = video.device_batch(ctx)
-            return batch
-
-        src = on_device(context)
+        src = _device_frames(context, ctx)
         # the correction works in place: on a copy, so the caller's tensor (another node's cached output) stays as it is
-        dst = (src if out_context is context else on_device(out_context)).clone()
-        mask = None
-        if padding_mask is not None:
-            mask = padding_mask if isinstance(padding_mask, torch.Tensor) else torch.from_numpy(np.asarray(padding_mask, dtype=np.float32))
-            mask = mask.to(device=ctx.device, dtype=torch.float32)
-            if mask.ndim == 4:
-                mask = mask[..., 0]
-            if tuple(mask.shape) != tuple(dst.shape[:3]):
-                raise ValueError(f"deflicker: padding_mask {tuple(mask.shape)} does not match the stabilized frames {tuple(dst.shape[:3])}")
-            mask = mask.contiguous()
+        dst = (src if out_context is context else _device_frames(out_context, ctx)).clone()
+        mask = None if padding_mask is None else _stabilizer_mask("deflicker", padding_mask, dst, ctx)
         block = deflicker.deflicker_on_device(ctx, request, src, dst, mask, transitions, confidences, fps_effective, segments)
         return io.NodeOutput(_image_out(dst, out_context), json.dumps({"deflicker": block}))
-
-
-class VideoStabilizerFlowLevel(io.ComfyNode):
-    """The Flow node that also levels the picture: the roll of every frame is measured from the orientation of its edges,
-    one offset per shot -- or one that varies slowly -- is taken from it, and every frame is turned upright about the centre
-    (horizon_level.py).  Framing is fixed to crop_and_pad.  Not one of the reference's nodes: it is listed by an extension but
-    kept out of NODE_CLASSES."""
-
-    @classmethod
-    def define_schema(cls) -> io.Schema:
-        from .horizon_level import DEFAULT_LIMIT_DEG, LIMIT_MAX_DEG, WINDOW_MAX_S
-
-        schema = io.Schema(
-            node_id="video_stabilizer_flow_level",
-            display_name="Video Stabilizer Flow (Horizon Level)",
-            category="Video/Stabilization",
-            description=("Video Stabilizer Flow that also levels the horizon: a clip shot a few degrees off level comes out "
-                         "steady and upright."),
-        )
-        base = VideoStabilizerFlow.define_schema()
-        schema.inputs = [
-            io.Combo.Input("transform_mode", options=["translation", "similarity"], default="similarity",
-                           display_name="Transform Mode",
-                           tooltip=("Select the geometric model fitted to the optical flow.  A homography has no single roll, "
-                                    "so perspective is not offered."))
-            if s.id == "transform_mode" else s for s in base.inputs if s.id != "framing_mode"] + [
-            io.Float.Input("level_window", default=0.0, min=0.0, max=WINDOW_MAX_S, step=0.05, display_name="Level Window",
-                           tooltip=("Seconds over which the roll offset may vary, for a camera that slowly tips over.  0 takes "
-                                    "one offset for every shot.")),
-            io.Float.Input("level_limit", default=DEFAULT_LIMIT_DEG, min=0.5, max=LIMIT_MAX_DEG - 0.5, step=0.5,
-                           display_name="Level Limit",
-                           tooltip=("Largest correction in degrees.  Edges give the roll modulo 90 degrees only, so it stays "
-                                    "below 45.  The default has been tried on synthetic clips only.")),
-        ]
-        schema.outputs = _estimator_outputs()
-        return schema
-
-    @classmethod
-    def execute(cls, frames: Any, frame_rate: float, transform_mode: str, camera_lock: bool, strength: float, smooth: float,
-                keep_fov: float, padding_color: str, level_window: float = 0.0, level_limit: float = 20.0) -> io.NodeOutput:
-        return _run_estimator_node("flow", frames, frame_rate, "crop_and_pad", transform_mode, camera_lock, strength, smooth,
-                                   keep_fov, padding_color, horizon_level=True if float(level_window) == 0.0 else float(level_window),
-                                   horizon_limit=float(level_limit))
 
 
 class VideoStabilizerCleanPlate(io.ComfyNode):
@@ -1290,25 +1124,19 @@ class VideoStabilizerCleanPlate(io.ComfyNode):
 
     @classmethod
     def define_schema(cls) -> io.Schema:
-        from .clean_plate import DEFAULT_MATTE_MIN_COUNT, DEFAULT_MATTE_THRESHOLD, SAMPLES_MAX
-
-        schema = io.Schema(
-            node_id="video_stabilizer_clean_plate",
-            display_name="Video Stabilizer Clean Plate",
-            category="Video/Stabilization",
-            description=("The background of a locked shot with everything that moves taken out (the per-pixel median over time), "
-                         "the frames with their padding filled from it, and the difference matte."),
-        )
+        schema = _schema("video_stabilizer_clean_plate", "Video Stabilizer Clean Plate",
+                         description=("The background of a locked shot with everything that moves taken out (the per-pixel median over time), "
+                                      "the frames with their padding filled from it, and the difference matte."))
         schema.inputs = [
             io.Image.Input("frames", display_name="Frames", tooltip="A registered clip: a tripod shot or a camera-locked stabilizer output."),
             io.Mask.Input("padding_mask", display_name="Padding Mask", optional=True,
                           tooltip="[N,H,W], or [1,H,W] for every frame; padded pixels do not vote.  Without it every pixel is own."),
             io.Boolean.Input("fill", default=True, display_name="Fill", tooltip="Fill the padded pixels from the plate and clear their mask."),
-            io.Int.Input("min_count", default=1, min=1, max=SAMPLES_MAX, step=1, display_name="Min Count",
+            io.Int.Input("min_count", default=1, min=1, max=clean_plate.SAMPLES_MAX, step=1, display_name="Min Count",
                          tooltip="Frames that must have seen a plate pixel before it fills anything."),
-            io.Float.Input("matte_threshold", default=DEFAULT_MATTE_THRESHOLD, min=0.0, max=1.0, step=0.01, display_name="Matte Threshold",
+            io.Float.Input("matte_threshold", default=clean_plate.DEFAULT_MATTE_THRESHOLD, min=0.0, max=1.0, step=0.01, display_name="Matte Threshold",
                            tooltip="A pixel is matte where some channel differs from the plate by more than this.  A choice, not a calibration."),
-            io.Int.Input("matte_min_count", default=DEFAULT_MATTE_MIN_COUNT, min=1, max=SAMPLES_MAX, step=1, display_name="Matte Min Count",
+            io.Int.Input("matte_min_count", default=clean_plate.DEFAULT_MATTE_MIN_COUNT, min=1, max=clean_plate.SAMPLES_MAX, step=1, display_name="Matte Min Count",
                          tooltip="Frames that must have seen a plate pixel before it can mark a matte.  A choice, not a calibration."),
         ]
         schema.outputs = [
@@ -1323,10 +1151,6 @@ class VideoStabilizerCleanPlate(io.ComfyNode):
     @classmethod
     def execute(cls, frames: Any, padding_mask: Any = None, fill: bool = True, min_count: int = 1, matte_threshold: float = 0.1,
                 matte_min_count: int = 3) -> io.NodeOutput:
-        import json
-
-        from . import clean_plate, native
-
         # every check comes before any GPU work
         if not isinstance(fill, (bool, np.bool_)):
             raise ValueError(f"clean plate: fill={fill!r} is not a bool")
@@ -1336,36 +1160,16 @@ class VideoStabilizerCleanPlate(io.ComfyNode):
         if isinstance(matte_threshold, bool) or not isinstance(matte_threshold, (int, float)) or not 0.0 <= matte_threshold <= 1.0:
             raise ValueError(f"clean plate: matte_threshold={matte_threshold!r} is not a number in [0, 1]")
         context = hm._normalize_video_input(frames)
-        n, h, w = len(context.frames), context.height, context.width
-        if n == 0:
-            raise ValueError("clean plate: socket 'frames' holds no frame")
-        shape = None
-        if padding_mask is not None:
-            if not (hasattr(padding_mask, "dtype") and hasattr(padding_mask, "shape")):
-                raise ValueError(f"clean plate: socket 'padding_mask' must be a floating-point MASK tensor, got {type(padding_mask).__name__}")
-            if "float" not in str(padding_mask.dtype):
-                raise ValueError(f"clean plate: socket 'padding_mask' must be a floating-point MASK, got {padding_mask.dtype}")
-            shape = tuple(int(v) for v in padding_mask.shape)
-            if len(shape) == 4 and shape[3] == 1:
-                shape = shape[:3]
-            if len(shape) != 3 or shape[1:] != (h, w) or shape[0] not in (1, n):
-                raise ValueError(f"clean plate: socket 'padding_mask' of shape {tuple(padding_mask.shape)} does not match "
-                                 f"socket 'frames' [{n},{h},{w},3]: expected [{n},{h},{w}] or [1,{h},{w}]")
+        dims, lead = _check_clip_and_mask("clean plate", context, padding_mask)
         ctx = native.default_context()
-        torch = ctx.torch
-        src = context.device_batch(ctx)
-        if context.range_pending and hm.resolve_value_range(context, hm.prefetch_peaks(ctx.frame_range(src)), ctx):
-            src = context.device_batch(ctx)      # F0's value-range rule, as every node of the package applies it to its frames
-        mask = None
-        if padding_mask is not None:
-            mask = padding_mask if isinstance(padding_mask, torch.Tensor) else torch.from_numpy(np.asarray(padding_mask))
-            # (a copy: the fill works in place, and the caller's tensor -- another node's cached output -- stays as it is)
-            mask = mask.to(device=ctx.device, dtype=torch.float32).reshape((shape[0], h, w)).expand(n, h, w).clone()
+        src = _device_frames(context, ctx)
+        # (a copy: the fill works in place, and the caller's tensor -- another node's cached output -- stays as it is)
+        mask = _place_socket_mask(padding_mask, lead, dims, ctx, copy=True)
         plate, count, table = clean_plate.plate_on_device(ctx, src, mask)
         matte, matte_count = clean_plate.matte_on_device(ctx, src, mask, plate, count, None, float(matte_threshold), int(matte_min_count))
         block = {"version": 1, "samples": int((table >= 0).sum()), "matte_threshold": float(matte_threshold),
                  "matte_min_count": int(matte_min_count)}
-        pixels = np.float32(h * w)
+        pixels = np.float32(dims[1] * dims[2])
         share = (matte_count.cpu().numpy().astype(np.float32) / pixels).astype(np.float64)
         block.update({"matte_fraction_mean": float(np.mean(share)), "matte_fraction_max": float(np.max(share))})
         dst = src
@@ -1373,7 +1177,7 @@ class VideoStabilizerCleanPlate(io.ComfyNode):
             dst = src.clone()
             block["plate_fill"] = clean_plate.fill_and_report(ctx, dst, mask, plate, count, table, None, int(min_count))
         if mask is None:
-            mask = torch.zeros((n, h, w), dtype=torch.float32, device=ctx.device)
+            mask = ctx.torch.zeros(dims, dtype=ctx.torch.float32, device=ctx.device)
         return io.NodeOutput(_image_out(plate, context), _image_out(dst, context), _mask_out(mask, 1), _mask_out(matte, 1),
                              json.dumps({"clean_plate": block}))
 
@@ -1417,61 +1221,50 @@ def _extend(base: type, *added_nodes: type, name: str, doc: str) -> type:
     return type(name, (base,), {"__doc__": doc, "__module__": __name__, "get_node_list": get_node_list})
 
 
-VideoStabilizerAmdMaskedExtension = _extend(
-    VideoStabilizerAmdExtension, VideoStabilizerFlowMasked, name="VideoStabilizerAmdMaskedExtension",
-    doc="What comfy_entrypoint() hands to ComfyUI: the base extension's seven nodes plus Video Stabilizer Flow (Masked).")
-VideoStabilizerAmdScenesExtension = _extend(
-    VideoStabilizerAmdMaskedExtension, VideoStabilizerFlowScenes, name="VideoStabilizerAmdScenesExtension",
-    doc="The masked extension's eight nodes plus Video Stabilizer Flow (Scene-Aware).")
-VideoStabilizerAmdMeshExtension = _extend(
-    VideoStabilizerAmdScenesExtension, VideoStabilizerFlowMesh, name="VideoStabilizerAmdMeshExtension",
-    doc="The scene-aware extension's nine nodes plus Video Stabilizer Flow (Mesh).")
-VideoStabilizerAmdMeshApplyExtension = _extend(
-    VideoStabilizerAmdMeshExtension, VideoStabilizerFlowMeshMotion, VideoStabilizerMotionApplyMesh,
-    name="VideoStabilizerAmdMeshApplyExtension",
-    doc="The mesh extension's ten nodes plus the two of the mesh round trip: Flow (Mesh Motion) and Motion Apply (Mesh).")
-VideoStabilizerAmdFillExtension = _extend(
-    VideoStabilizerAmdMeshApplyExtension, VideoStabilizerPaddingFill, name="VideoStabilizerAmdFillExtension",
-    doc="The mesh round trip extension's twelve nodes plus Video Stabilizer Padding Fill.")
-VideoStabilizerAmdReportExtension = _extend(
-    VideoStabilizerAmdFillExtension, VideoStabilizerStabilityReport, name="VideoStabilizerAmdReportExtension",
-    doc="The fill extension's thirteen nodes plus Video Stabilizer Stability Report.")
-VideoStabilizerAmdZoomExtension = _extend(
-    VideoStabilizerAmdReportExtension, VideoStabilizerFlowZoom, name="VideoStabilizerAmdZoomExtension",
-    doc="The report extension's fourteen nodes plus Video Stabilizer Flow (Dynamic Zoom).")
-VideoStabilizerAmdSubjectExtension = _extend(
-    VideoStabilizerAmdZoomExtension, VideoStabilizerFlowSubject, name="VideoStabilizerAmdSubjectExtension",
-    doc="The zoom extension's fifteen nodes plus Video Stabilizer Flow (Subject Lock).")
-VideoStabilizerAmdFillBlendExtension = _extend(
-    VideoStabilizerAmdSubjectExtension, VideoStabilizerTemporalFillBlend, name="VideoStabilizerAmdFillBlendExtension",
-    doc="The subject extension's sixteen nodes plus Video Stabilizer Temporal Fill (Blended).")
-VideoStabilizerAmdSharpnessExtension = _extend(
-    VideoStabilizerAmdFillBlendExtension, VideoStabilizerSharpnessTransfer, name="VideoStabilizerAmdSharpnessExtension",
-    doc="The blended-fill extension's seventeen nodes plus Video Stabilizer Sharpness Transfer.")
-VideoStabilizerAmdHandoffExtension = _extend(
-    VideoStabilizerAmdSharpnessExtension, VideoStabilizerMaskGrow, name="VideoStabilizerAmdHandoffExtension",
-    doc="The sharpness extension's eighteen nodes plus Video Stabilizer Mask Grow.")
-VideoStabilizerAmdRollingExtension = _extend(
-    VideoStabilizerAmdHandoffExtension, VideoStabilizerFlowRolling, name="VideoStabilizerAmdRollingExtension",
-    doc="The hand-off extension's nineteen nodes plus Video Stabilizer Flow (Rolling Shutter).")
-VideoStabilizerAmdRollingApplyExtension = _extend(
-    VideoStabilizerAmdRollingExtension, VideoStabilizerMotionApplyRolling, name="VideoStabilizerAmdRollingApplyExtension",
-    doc="The rolling-shutter extension's twenty nodes plus Video Stabilizer Motion Apply (Rolling Shutter).")
-VideoStabilizerAmdAnchorExtension = _extend(
-    VideoStabilizerAmdRollingApplyExtension, VideoStabilizerFlowAnchored, name="VideoStabilizerAmdAnchorExtension",
-    doc="The rolling round trip extension's twenty-one nodes plus Video Stabilizer Flow (Drift-Free).")
-VideoStabilizerAmdAnchorExposureExtension = _extend(
-    VideoStabilizerAmdAnchorExtension, VideoStabilizerFlowAnchoredExposure, name="VideoStabilizerAmdAnchorExposureExtension",
-    doc="The drift-free extension's twenty-two nodes plus Video Stabilizer Flow (Drift-Free, Exposure-Matched).")
-VideoStabilizerAmdRollingRefitExtension = _extend(
-    VideoStabilizerAmdAnchorExposureExtension, VideoStabilizerFlowRollingRefit, name="VideoStabilizerAmdRollingRefitExtension",
-    doc="The exposure-matched extension's twenty-three nodes plus Video Stabilizer Flow (Rolling Shutter, Refit).")
-VideoStabilizerAmdDeflickerExtension = _extend(
-    VideoStabilizerAmdRollingRefitExtension, VideoStabilizerDeflicker, name="VideoStabilizerAmdDeflickerExtension",
-    doc="The refit extension's twenty-four nodes plus Video Stabilizer Deflicker.")
-VideoStabilizerAmdLevelExtension = _extend(
-    VideoStabilizerAmdDeflickerExtension, VideoStabilizerFlowLevel, name="VideoStabilizerAmdLevelExtension",
-    doc="The deflicker extension's twenty-five nodes plus Video Stabilizer Flow (Horizon Level).")
-VideoStabilizerAmdPlateExtension = _extend(
-    VideoStabilizerAmdLevelExtension, VideoStabilizerCleanPlate, name="VideoStabilizerAmdPlateExtension",
-    doc="The level extension's twenty-six nodes plus Video Stabilizer Clean Plate.")
+# One extension class per feature, each made from the one before it: (class name, added nodes, docstring), oldest first.  A new
+# feature adds a row at the end; comfy_entrypoint() keeps returning the first.
+_EXTENSION_CHAIN = [
+    ("VideoStabilizerAmdMaskedExtension", [VideoStabilizerFlowMasked],
+     "What comfy_entrypoint() hands to ComfyUI: the base extension's seven nodes plus Video Stabilizer Flow (Masked)."),
+    ("VideoStabilizerAmdScenesExtension", [VideoStabilizerFlowScenes],
+     "The masked extension's eight nodes plus Video Stabilizer Flow (Scene-Aware)."),
+    ("VideoStabilizerAmdMeshExtension", [VideoStabilizerFlowMesh],
+     "The scene-aware extension's nine nodes plus Video Stabilizer Flow (Mesh)."),
+    ("VideoStabilizerAmdMeshApplyExtension", [VideoStabilizerFlowMeshMotion, VideoStabilizerMotionApplyMesh],
+     "The mesh extension's ten nodes plus the two of the mesh round trip: Flow (Mesh Motion) and Motion Apply (Mesh)."),
+    ("VideoStabilizerAmdFillExtension", [VideoStabilizerPaddingFill],
+     "The mesh round trip extension's twelve nodes plus Video Stabilizer Padding Fill."),
+    ("VideoStabilizerAmdReportExtension", [VideoStabilizerStabilityReport],
+     "The fill extension's thirteen nodes plus Video Stabilizer Stability Report."),
+    ("VideoStabilizerAmdZoomExtension", [VideoStabilizerFlowZoom],
+     "The report extension's fourteen nodes plus Video Stabilizer Flow (Dynamic Zoom)."),
+    ("VideoStabilizerAmdSubjectExtension", [VideoStabilizerFlowSubject],
+     "The zoom extension's fifteen nodes plus Video Stabilizer Flow (Subject Lock)."),
+    ("VideoStabilizerAmdFillBlendExtension", [VideoStabilizerTemporalFillBlend],
+     "The subject extension's sixteen nodes plus Video Stabilizer Temporal Fill (Blended)."),
+    ("VideoStabilizerAmdSharpnessExtension", [VideoStabilizerSharpnessTransfer],
+     "The blended-fill extension's seventeen nodes plus Video Stabilizer Sharpness Transfer."),
+    ("VideoStabilizerAmdHandoffExtension", [VideoStabilizerMaskGrow],
+     "The sharpness extension's eighteen nodes plus Video Stabilizer Mask Grow."),
+    ("VideoStabilizerAmdRollingExtension", [VideoStabilizerFlowRolling],
+     "The hand-off extension's nineteen nodes plus Video Stabilizer Flow (Rolling Shutter)."),
+    ("VideoStabilizerAmdRollingApplyExtension", [VideoStabilizerMotionApplyRolling],
+     "The rolling-shutter extension's twenty nodes plus Video Stabilizer Motion Apply (Rolling Shutter)."),
+    ("VideoStabilizerAmdAnchorExtension", [VideoStabilizerFlowAnchored],
+     "The rolling round trip extension's twenty-one nodes plus Video Stabilizer Flow (Drift-Free)."),
+    ("VideoStabilizerAmdAnchorExposureExtension", [VideoStabilizerFlowAnchoredExposure],
+     "The drift-free extension's twenty-two nodes plus Video Stabilizer Flow (Drift-Free, Exposure-Matched)."),
+    ("VideoStabilizerAmdRollingRefitExtension", [VideoStabilizerFlowRollingRefit],
+     "The exposure-matched extension's twenty-three nodes plus Video Stabilizer Flow (Rolling Shutter, Refit)."),
+    ("VideoStabilizerAmdDeflickerExtension", [VideoStabilizerDeflicker],
+     "The refit extension's twenty-four nodes plus Video Stabilizer Deflicker."),
+    ("VideoStabilizerAmdLevelExtension", [VideoStabilizerFlowLevel],
+     "The deflicker extension's twenty-five nodes plus Video Stabilizer Flow (Horizon Level)."),
+    ("VideoStabilizerAmdPlateExtension", [VideoStabilizerCleanPlate],
+     "The level extension's twenty-six nodes plus Video Stabilizer Clean Plate."),
+]
+
+_latest = VideoStabilizerAmdExtension
+for _name, _added, _doc in _EXTENSION_CHAIN:
+    _latest = globals()[_name] = _extend(_latest, *_added, name=_name, doc=_doc)
+del _latest, _name, _added, _doc
