@@ -238,6 +238,10 @@ def stabilize_sharded(ctx, local_frames, total_frames: int, framing_mode: str, t
         ("estimator", estimator == "subject",
          "stabilize_sharded does not support estimator 'subject': the subject lock is not sharded (its mask "
          "is not distributed with each rank's frames); run the single-GPU pipeline for a subject lock"),
+        # the chain of positions runs through the whole clip, from the key frame in both directions
+        ("estimator", estimator == "track",
+         "stabilize_sharded does not support estimator 'track': the template track is not sharded (every frame "
+         "starts from the position of the frame before it, which may lie on another rank); run the single-GPU pipeline for it"),
         # the mask would have to be sharded with the frames, halo frame included
         ("estimation_mask", estimation_mask is not None,
          "stabilize_sharded does not support estimation_mask: the sharded path does not distribute a mask "

@@ -36,6 +36,7 @@ from . import sharpness_transfer as sharpness_transfer_mod
 from . import spatial_fill as spatial_fill_mod
 from . import stability as stability_mod
 from . import subject_lock as subject_lock_mod
+from . import template_track as template_track_mod
 from . import temporal_fill as temporal_fill_mod
 from .comfy_compat import ProgressBar, check_interrupt
 from .meta_v2 import applied_motion_meta_from_arrays, applied_motion_meta_from_stabilization_warp
@@ -70,8 +71,11 @@ class _gc_paused:
 #
 # "subject" (subject_lock.py, beyond the reference) measures no camera at all: its transitions are those of a masked
 # subject's centroid and area, so that everything behind the fit table holds the subject still instead of the background.
+#
+# "track" (template_track.py, beyond the reference) is the subject lock without a mask: the subject is one box in one frame,
+# followed through the estimation images by a fixed-template search; its transitions are the subject's as well.
 _META_SOURCE = {"flow": "estimated_flow", "flow_phase_correlate": "estimated_flow", "flow_tvl1": "estimated_flow",
-                "classic": "estimated_classic", "subject": "estimated_subject"}
+                "classic": "estimated_classic", "subject": "estimated_subject", "track": "estimated_subject"}
 _PHASE_REASON = "DIS unavailable (disabled by VSTAB_FLOW_BACKEND); cv2.optflow missing; using phase correlation."
 _TVL1_REASON = "DIS unavailable (disabled by the caller); using TV-L1."
 
@@ -98,6 +102,8 @@ def _backend_fields(estimator: str) -> Dict[str, Any]:
         return {"flow_backend": "TVL1", "flow_fallback_reason": _TVL1_REASON}
     if estimator == "subject":
         return {"flow_backend": "subject_mask", "flow_fallback_reason": None}
+    if estimator == "track":
+        return {"flow_backend": "template_track", "flow_fallback_reason": None}
     return {}
 
 
@@ -250,9 +256,21 @@ def estimate_transitions_subject(ctx, device_frames, working_size, transform_mod
     return table
 
 
+def estimate_transitions_track(ctx, device_frames, working_size, transform_mode: str, clip_start: bool = True, peaks_out=None,
+                               gray_out=None, track=None):
+    """Template track (template_track.py): the estimation images as every camera estimator makes them (the owed F0 peaks come
+    from that pass, as for DIS), one call that follows the box through them on the device (HIP), 92 bytes per frame to the
+    host, the candidate fits from the box's centres.  track: {"request": (box, key, radius)}; receives "block",
+    meta["template_track"]."""
+    gray = _gray(ctx, device_frames, working_size, peaks_out, gray_out)
+    size = (int(device_frames.shape[2]), int(device_frames.shape[1]))
+    table, track["block"] = template_track_mod.estimate_on_device(ctx, gray, track["request"], size, working_size)
+    return table
+
+
 _ESTIMATORS.update({"flow": estimate_transitions, "flow_phase_correlate": estimate_transitions_phase,
                     "flow_tvl1": estimate_transitions_tvl1, "classic": estimate_transitions_classic,
-                    "subject": estimate_transitions_subject})
+                    "subject": estimate_transitions_subject, "track": estimate_transitions_track})
 
 
 def _fps_fields(context: hm.VideoContext, frame_rate) -> Tuple[float, Optional[float]]:
@@ -884,6 +902,7 @@ class FlowRequest:
     deflicker: Any = None              # deflicker.check_request: Request | None
     level: Any = None                  # horizon_level.check_request: Request | None
     plate: Optional[int] = None        # clean_plate.check_request: the plate fill's min_count | None
+    track: Any = None                  # template_track.check_request: (box, key, radius) | None
     refit: bool = False                # rolling_shutter.check_refit_request: the transitions are fitted again on rectified samples
 
     @property
@@ -924,6 +943,8 @@ def check_flow_request(framing_mode: str, transform_mode: str, estimator: str, k
     if estimator not in _META_SOURCE:
         raise ValueError(f"Unknown estimator {estimator!r}; expected 'flow' or 'classic'.")
     subject = subject_lock_mod.check_request(kw["subject_mask"], transform_mode, estimator)
+    track = template_track_mod.check_request(kw.get("track_box"), kw.get("track_key", 0), kw.get("track_radius"), estimator,
+                                             transform_mode)
     temporal_fill = int(kw["temporal_fill"])
     if not 0 <= temporal_fill <= temporal_fill_mod.MAX_RADIUS:
         raise ValueError(f"temporal_fill={temporal_fill} outside [0, {temporal_fill_mod.MAX_RADIUS}]")
@@ -957,19 +978,28 @@ def check_flow_request(framing_mode: str, transform_mode: str, estimator: str, k
     plate = clean_plate_mod.check_request(kw.get("plate_fill"))
     if plate is not None:
         clean_plate_mod.check_pipeline(kw.get("camera_lock"), kw.get("strength"), estimator, zoom, level)
+    if track is not None:   # (behind every keyword's own check: a malformed value keeps its own message)
+        template_track_mod.check_pipeline({
+            "scene_cuts": scene, "estimation_mask": kw["estimation_mask"], "mesh_warp": mesh, "temporal_fill": temporal_fill,
+            "sharpness_transfer": sharpness, "rolling_shutter": rolling, "drift_correction": drift, "deflicker": deflicker,
+            "horizon_level": level, "plate_fill": plate})
     return FlowRequest(estimator, temporal_fill, fill_blend, sharpness, handoff, zoom, scene, mesh, bool(kw["mesh_motion"]),
                        bool(subject), rolling, spatial_fill, stability_report, mask_margin, drift, drift_exposure, drift_mask,
-                       refit=refit, deflicker=deflicker, level=level, plate=plate)
+                       refit=refit, deflicker=deflicker, level=level, plate=plate, track=track)
 
 
 def _check_request_against_clip(request: FlowRequest, kw: Dict[str, Any], transform_mode: str, total_frames: int, size) -> None:
-    """The three checks that need the clip's length and size, run as soon as they are known."""
+    """The four checks that need the clip's length and size, run as soon as they are known."""
     if kw["estimation_mask"] is not None:
         check_estimation_mask_shape(kw["estimation_mask"], total_frames, size)
     if request.scene is not None and request.scene.mode == "given":
         scene_cuts_mod.check_given_cuts(request.scene.cuts, total_frames)
     if request.subject:
         subject_lock_mod.check_request(kw["subject_mask"], transform_mode, request.estimator, total_frames, size)
+    if request.track is not None:
+        box, key, _ = request.track
+        template_track_mod.check_against_clip(box, key, total_frames, size)
+        template_track_mod.working_box(box, size, hm._working_estimation_size(*size) or size)
 
 
 class FlowArgs(NamedTuple):
@@ -1109,6 +1139,9 @@ def _stabilize_frames(
     horizon_level=None,
     horizon_limit=None,
     plate_fill=None,
+    track_box=None,
+    track_key: int = 0,
+    track_radius=None,
     drift_correction=None,
     drift_exposure=None,
     drift_mask=None,
@@ -1265,7 +1298,19 @@ def _stabilize_frames(
     with dynamic_zoom, a horizon_level window or estimator "subject", whose frames are not registered to each other (or not
     on the background).  `padding_fraction_*` keep describing the warp; meta["plate_fill"] reports samples, what was filled,
     what is left and what no frame of a shot saw.  None / False: the behaviour and meta without it, byte for byte, and nothing
-    new is launched.  `crop` framing has no padding; bypass paths ignore it."""
+    new is launched.  `crop` framing has no padding; bypass paths ignore it.
+    track_box, track_key, track_radius (beyond the reference, None / 0 / None by default; with estimator="track" only, and
+    track_box required by it): the subject lock without a mask.  track_box = (x, y, width, height), ints in full-resolution
+    pixels, is a rectangle around the subject in frame track_key; its content in the estimation image of that frame is the
+    template, and one device pass follows it through the clip, forwards and backwards from the key frame, by an exhaustive
+    zero-mean SSD search within track_radius working pixels (None: 24, else an int in 1..48) of the previous position, in
+    exact integers (template_track.py; include/vstab_track.h states the rule).  A parabola through the costs beside the pick
+    refines the position, 1 - sqrt(J_best / J_T) is the confidence, frames below 0.3 are lost: interpolated and reported with
+    confidence 0.  The transitions are the subject's, and everything behind the fit table follows as for the subject lock:
+    camera_lock=True pins the subject where frame 0 shows it.  For translation only, without scene_cuts, estimation_mask,
+    subject_mask, mesh_warp, temporal_fill, sharpness_transfer, rolling_shutter, drift_correction, deflicker, horizon_level or
+    plate_fill; meta["template_track"] reports positions, confidences and lost frames.  track_box=None with any other
+    estimator: the behaviour and meta without it, byte for byte, and nothing new is launched.  Bypass paths ignore them."""
     kw = dict(locals())     # every argument by name (nothing else is local yet): the keyword extras are read from here
     request = check_flow_request(framing_mode, transform_mode, estimator, kw)
     estimator = request.estimator
@@ -1340,6 +1385,8 @@ def _stabilize_frames(
     # the estimator's keyword arguments, built here and nowhere else: the block grid or the subject's mask (never both: the
     # checks refuse it), and a fresh list for every by-product that has to stay alive behind the fits
     extras = {"subject": {"mask": subject_lock_mod.mask_on_device(ctx, subject_mask)}} if request.subject else {}
+    if request.track is not None:
+        extras["track"] = {"request": request.track}
     if blocked is not None:
         extras["blocked"] = blocked
 
@@ -1413,6 +1460,7 @@ def _stabilize_frames(
         "scene_cuts": scene_block,
         "mesh_warp": mesh_block,
         "subject_lock": extras["subject"]["block"] if request.subject else None,
+        "template_track": extras["track"]["block"] if request.track is not None else None,
         "rolling_shutter": rolling_block,
         "drift_correction": drift_block,
     }

@@ -286,6 +286,24 @@ _SIGNATURES = {
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
+# include/vstab_track.h, the second public header of the same library: a table of its own, applied by load_library() beside
+# the one above and not part of EXPORTED_SYMBOLS (which is what include/vstab.h declares)
+_TRACK_SIGNATURES = {
+    "vstab_track_template_batch": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+TRACK_SENTINEL = (1 << 64) - 1     # VSTAB_TRACK_SENTINEL
+TRACK_RADIUS_MAX = 48              # VSTAB_TRACK_RADIUS_MAX
+TRACK_MIN_BOX = 8                  # VSTAB_TRACK_MIN_BOX
+TRACK_MAX_SAMPLES = 4096           # VSTAB_TRACK_MAX_SAMPLES
+
+
+def track_work_words(radius: int) -> int:
+    """VSTAB_TRACK_WORK_WORDS(radius): the 64-bit words of scratch vstab_track_template_batch needs."""
+    d = 2 * int(radius) + 1
+    return TRACK_MAX_SAMPLES // 8 + 2 * (d * d + 2 * d)
+
 _lib = None
 
 
@@ -305,7 +323,7 @@ def load_library():
         import torch  # noqa: F401
 
         lib = C.CDLL(str(LIB_PATH))
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in {**_SIGNATURES, **_TRACK_SIGNATURES}.items():
             fn = getattr(lib, name)  # AttributeError here means the ABI and the header diverged
             fn.restype = res
             fn.argtypes = args
@@ -1326,6 +1344,35 @@ class Context:
         bbox = self._new((n, 4), torch.int32)
         self._call("mask_moments_batch", mask, n, h, w, sums, bbox)
         return sums, bbox
+
+    # ------------------------------------------------------------------ template track
+    def track_template_batch(self, gray, box, stride, radius, key, want_surface=False):
+        """One box followed through a clip by a fixed-template search (include/vstab_track.h states the rule): gray [n,h,w], u8,
+        device, contiguous; box = (bx, by, bw, bh) inside frame `key`, in pixels of gray; stride = ceil(max(bw, bh) / 64);
+        radius in 1..48.  Nothing is written to gray.  -> (tsums i64 [3] = samples, sum T, sum T^2;  pos i32 [n,2] = (x, y) of
+        the box;  best u64 [n];  near u64 [n,9], the 3 x 3 costs around the pick;  surface u64 [n,2R+1,2R+1] | None), device
+        tensors; the 64-bit costs as torch.int64 bit patterns (the sentinel 2^64 - 1 reads -1; `.cpu().numpy().view(np.uint64)`)."""
+        torch = self.torch
+        who = "track_template_batch"
+        self._tensor(who, "gray", gray, torch.uint8)
+        if gray.dim() != 3:
+            raise ValueError(f"{who}: gray of shape {tuple(gray.shape)} is not [n,h,w]")
+        n, h, w = int(gray.shape[0]), int(gray.shape[1]), int(gray.shape[2])
+        if len(box) != 4:
+            raise ValueError(f"{who}: box={box!r} is not (bx, by, bw, bh)")
+        bx, by, bw, bh = (_int_in(who, name, v, 0, 1 << 30) for name, v in zip(("bx", "by", "bw", "bh"), box))
+        stride = _int_in(who, "stride", stride, 1, 1 << 30)
+        radius = _int_in(who, "radius", radius, 1, TRACK_RADIUS_MAX)
+        key = _int_in(who, "key", key, 0, max(n - 1, 0))
+        d = 2 * radius + 1
+        tsums = self._new((3,), torch.int64)
+        pos = self._new((n, 2), torch.int32)
+        best = self._new((n,), torch.int64)
+        near = self._new((n, 9), torch.int64)
+        surface = self._new((n, d, d), torch.int64, bool(want_surface))
+        work = self._new((track_work_words(radius),), torch.int64)
+        self._call("track_template_batch", gray, n, h, w, bx, by, bw, bh, stride, radius, key, tsums, pos, best, near, surface, work)
+        return tsums, pos, best, near, surface
 
     # ------------------------------------------------------------------ horizon level
     def orientation_hist_batch(self, gray, min_mag2: int):
