@@ -18,8 +18,8 @@
 //     [P, h, w]; the working set at the finest level (240x135) is L2/Infinity-Cache resident
 //   * nothing here is a contraction: no MFMA
 #include "vstab_internal.h"
+#include "vstab_area.h"
 #include <cstdlib>
-#include <cfloat>
 #include <algorithm>
 #include <cmath>
 #include <memory>
@@ -41,25 +41,12 @@ struct LevelGeom {
     int w, h, ws, hs;
 };
 
-unsigned grid_for(long long items, int block = 256)
-{
-    long long b = (items + block - 1) / block;
-    const long long cap = 256LL * 32;
-    if (b > cap) b = cap;
-    if (b < 1) b = 1;
-    return (unsigned)b;
-}
-
 // blocks along x of a (blocks, frames) grid: enough to cover a frame, but no more than keeps the whole grid near
 // 8192 workgroups (a thread then strides over a few elements instead of the launch paying for tens of thousands of
 // one-element workgroups)
 dim3 frame_grid(long long per_frame, int frames, int block = 256)
 {
-    long long b = (per_frame + block - 1) / block;
-    const long long cap = std::max(1LL, (256LL * 32) / std::max(frames, 1));
-    if (b > cap) b = cap;
-    if (b < 1) b = 1;
-    return dim3((unsigned)b, (unsigned)frames);
+    return dim3(capped_grid(per_frame, std::max(1LL, (256LL * 32) / std::max(frames, 1)), block), (unsigned)frames);
 }
 
 // The per-frame preparation kernels run on a (blocks, frames) grid: blockIdx.y is the frame (or pair) and the element
@@ -68,15 +55,8 @@ dim3 frame_grid(long long per_frame, int frames, int block = 256)
 #define FRAME_STRIDE(t, per_frame) \
     for (unsigned t = blockIdx.x * blockDim.x + threadIdx.x; t < (unsigned)(per_frame); t += gridDim.x * blockDim.x)
 
-__device__ __forceinline__ int d_ceil(double v) { int i = (int)v; return i + (i < v); }
-__device__ __forceinline__ int d_floor(double v) { int i = (int)v; return i - (i > v); }
 __device__ __forceinline__ int f_floor(float v) { int i = (int)v; return i - (i > v); }
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ int sat_u8_round(float v)
-{
-    int i = (int)__builtin_rintf(v);
-    return i < 0 ? 0 : (i > 255 ? 255 : i);
-}
 __device__ __forceinline__ int reflect101(int p, int len)
 {
     if (len == 1) return 0;
@@ -87,128 +67,66 @@ __device__ __forceinline__ int reflect101(int p, int len)
     return p;
 }
 
-// ---- INTER_AREA u8 -> u8, any ratio >= 1 (tables computed on the fly, OpenCV's order) ----
-struct AreaAxis { int n; int si[8]; float a[8]; };
+// ---- a level's preparation, per element: the rules of pad_replicate / sobel / tensor_h / tensor_v_kernel below and of
+// pyramid_tail_kernel's preparation block (which reads the level from LDS and keeps the intermediate planes there) ----
 
-__device__ __forceinline__ void area_axis(int d, int ssize, double scale, AreaAxis& ax)
+// sample (y, x) of the image padded by DIS_BORDER replicated samples on every side
+__device__ __forceinline__ uint8_t pad_replicate_px(const uint8_t* img, int h, int w, int y, int x)
 {
-    const double fsx1 = d * scale, fsx2 = fsx1 + scale;
-    const double cell = scale < ssize - fsx1 ? scale : ssize - fsx1;
-    int sx1 = d_ceil(fsx1), sx2 = d_floor(fsx2);
-    sx2 = sx2 < ssize - 1 ? sx2 : ssize - 1;
-    sx1 = sx1 < sx2 ? sx1 : sx2;
-    int k = 0;
-    if (sx1 - fsx1 > 1e-3) { ax.si[k] = sx1 - 1; ax.a[k++] = (float)((sx1 - fsx1) / cell); }
-    for (int sx = sx1; sx < sx2 && k < 7; sx++) { ax.si[k] = sx; ax.a[k++] = (float)(1.0 / cell); }
-    if (fsx2 - sx2 > 1e-3 && k < 8) {
-        double a = fsx2 - sx2;
-        a = a < 1. ? a : 1.;
-        a = a < cell ? a : cell;
-        ax.si[k] = sx2; ax.a[k++] = (float)(a / cell);
-    }
-    ax.n = k;
+    return img[(unsigned)(clampi(y - DIS_BORDER, 0, h - 1) * w + clampi(x - DIS_BORDER, 0, w - 1))];
 }
 
-// mode 0: exact 2x2, 1: exact kx x ky integer boxes, 2: general, 3: exact 4x4 boxes on dword-aligned rows (the 960x540 ->
-// 240x135 level of every 1080p / 4K clip: four dword loads and four v_sad_u8 per output instead of sixteen byte loads)
-__global__ __launch_bounds__(256) void area_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n, int sh,
-                                                      int sw, int dh, int dw, int mode, int kx, int ky, double scale_x,
-                                                      double scale_y)
+// 3 x 3 Sobel pair of pixel (y, x), BORDER_REFLECT_101
+__device__ __forceinline__ void sobel_px(const uint8_t* img, int h, int w, int y, int x, int& gx, int& gy)
 {
-    const int f = blockIdx.y;
-    const uint8_t* S = src + (size_t)f * sh * sw;
-    uint8_t* D = dst + (size_t)f * dh * dw;
-    FRAME_STRIDE(t, dh * dw) {
-        const int y = (int)(t / (unsigned)dw), x = (int)(t - (unsigned)y * (unsigned)dw);
-        int o;
-        if (mode == 0) {
-            const uint8_t* s0 = S + (size_t)(2 * y) * sw + 2 * x;
-            o = (s0[0] + s0[1] + s0[sw] + s0[sw + 1] + 2) >> 2;
-        } else if (mode == 3) {
-            const unsigned* p = reinterpret_cast<const unsigned*>(S + (size_t)(4 * y) * sw + 4 * x);
-            const int rs = sw >> 2;
-            unsigned sum = 0;
+    const uint8_t* r0 = img + (unsigned)(reflect101(y - 1, h) * w);
+    const uint8_t* r1 = img + (unsigned)(y * w);
+    const uint8_t* r2 = img + (unsigned)(reflect101(y + 1, h) * w);
+    const int xl = reflect101(x - 1, w), xr = reflect101(x + 1, w);
+    gx = (r0[xr] + 2 * r1[xr] + r2[xr]) - (r0[xl] + 2 * r1[xl] + r2[xl]);
+    gy = (r2[xl] + 2 * r2[x] + r2[xr]) - (r0[xl] + 2 * r0[x] + r0[xr]);
+}
+
+// precomputeStructureTensor, horizontal sums of one patch column position: OpenCV keeps five f32 running sums per row
+// (`sum += x[j]*x[j] - x[j-8]*x[j-8]`, integer increments added to a float).  Every value such a sum ever takes is an
+// integer below 2^24 (8 terms of at most 1020^2: Sobel of u8 is within +-1020), so each of those float additions is exact
+// and the running sum equals the plain integer window sum -- computed here independently per output, no sequential chain
+// (the vertical pass, whose sums exceed 2^24, does keep OpenCV's order).  xr / yr: the PSZ gradients of the window.
+struct WindowSums { int xx, yy, xy, x, y; };
+__device__ __forceinline__ WindowSums window_sums(const short* xr, const short* yr)
+{
+    WindowSums s = {0, 0, 0, 0, 0};
 #pragma unroll
-            for (int j = 0; j < 4; j++) sum = __builtin_amdgcn_sad_u8(p[(size_t)j * rs], 0u, sum);
-            o = sat_u8_round((int)sum * (1.f / 16));
-        } else if (mode == 1) {
-            int sum = 0;
-            for (int j = 0; j < ky; j++)
-                for (int i = 0; i < kx; i++) sum += S[(size_t)(y * ky + j) * sw + x * kx + i];
-            o = sat_u8_round(sum * (1.f / (kx * ky)));
-        } else {
-            AreaAxis ax, ay;
-            area_axis(x, sw, scale_x, ax);
-            area_axis(y, sh, scale_y, ay);
-            float sum = 0.f;
-            for (int j = 0; j < ay.n; j++) {
-                const uint8_t* row = S + (size_t)ay.si[j] * sw;
-                float buf = 0.f;
-                for (int k = 0; k < ax.n; k++) buf += row[ax.si[k]] * ax.a[k];
-                const float term = ay.a[j] * buf;
-                sum = (j == 0) ? term : sum + term;
+    for (int j = 0; j < PSZ; j++) {
+        const int gx = xr[j], gy = yr[j];
+        s.xx += gx * gx; s.yy += gy * gy; s.xy += gx * gy; s.x += gx; s.y += gy;
+    }
+    return s;
+}
+
+// vertical running sums of one column of horizontal sums a[i * ws], i < h, into o[is * ws]: the last PSZ rows stay in
+// registers (the row that leaves the window is not read twice), and the PSZ loads of a chunk are independent of the
+// running sum: OpenCV's additions in OpenCV's order
+__device__ __forceinline__ void tensor_column_walk(const float* a, float* o, int h, int ws)
+{
+    float ring[PSZ];
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < PSZ; i++) { ring[i] = a[(size_t)i * ws]; sum += ring[i]; }
+    o[0] = sum;
+    int is = 1;
+    for (int i0 = PSZ; i0 < h; i0 += PSZ) {
+        float v[PSZ];
+#pragma unroll
+        for (int k = 0; k < PSZ; k++) v[k] = (i0 + k < h) ? a[(size_t)(i0 + k) * ws] : 0.f;
+#pragma unroll
+        for (int k = 0; k < PSZ; k++) {
+            if (i0 + k < h) {
+                sum += (v[k] - ring[k]);
+                ring[k] = v[k];
+                if ((k + 1) % PSTR == 0) { o[(size_t)is * ws] = sum; is++; }   // (i - PSZ + 1) % PSTR == 0 for i = i0 + k, i0 a multiple of PSZ
             }
-            o = sat_u8_round(sum);
         }
-        D[t] = (uint8_t)o;
-    }
-}
-
-// General ratio with the tap tables in LDS: one workgroup per (frame, AREA_ROWS output rows) forms the column table once
-// and one row table per output row (area_axis is fp64 with three divisions: per output pixel, as in mode 2 above, it
-// made the three small pyramid levels of a 1080p clip cost more than the 4x4 level that reads sixteen times the bytes).
-// Same taps, same f32 sums in the same order as mode 2.
-constexpr int AREA_ROWS = 32, AREA_MAX_COLS = 1024;
-struct AreaTaps { int n, first; float a[8]; };   // the taps of an output sample are consecutive source samples
-
-// area_axis without the indexed tap arrays (which live in scratch memory): a leading partial sample, full samples, a
-// trailing partial one.  The host admits ratios below 6, so the k < 7 / k < 8 guards of area_axis never cut a run short.
-__device__ __forceinline__ void area_taps(int d, int ssize, double scale, AreaTaps& t)
-{
-    const double fsx1 = d * scale, fsx2 = fsx1 + scale;
-    const double cell = scale < ssize - fsx1 ? scale : ssize - fsx1;
-    int sx1 = d_ceil(fsx1), sx2 = d_floor(fsx2);
-    sx2 = sx2 < ssize - 1 ? sx2 : ssize - 1;
-    sx1 = sx1 < sx2 ? sx1 : sx2;
-    const int lead = (sx1 - fsx1 > 1e-3) ? 1 : 0;
-    const int k_end = lead + (sx2 - sx1);
-    const bool tail = fsx2 - sx2 > 1e-3;
-    double at = fsx2 - sx2;
-    at = at < 1. ? at : 1.;
-    at = at < cell ? at : cell;
-    const float a_lead = (float)((sx1 - fsx1) / cell), a_full = (float)(1.0 / cell), a_tail = (float)(at / cell);
-    t.n = k_end + (tail ? 1 : 0);
-    t.first = sx1 - lead;
-#pragma unroll
-    for (int k = 0; k < 8; k++) t.a[k] = (k < lead) ? a_lead : (k < k_end) ? a_full : (k == k_end && tail) ? a_tail : 0.f;
-}
-
-__global__ __launch_bounds__(256) void area_general_rows_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n, int sh,
-                                                                int sw, int dh, int dw, double scale_x, double scale_y)
-{
-    __shared__ AreaTaps s_x[AREA_MAX_COLS];
-    __shared__ AreaTaps s_y[AREA_ROWS];
-    const int groups = (dh + AREA_ROWS - 1) / AREA_ROWS;
-    const int f = (int)blockIdx.x / groups, y0 = ((int)blockIdx.x % groups) * AREA_ROWS;
-    const int rows = min(AREA_ROWS, dh - y0);
-    for (int x = threadIdx.x; x < dw; x += blockDim.x) area_taps(x, sw, scale_x, s_x[x]);
-    if ((int)threadIdx.x < rows) area_taps(y0 + (int)threadIdx.x, sh, scale_y, s_y[threadIdx.x]);
-    __syncthreads();
-    const uint8_t* S = src + (size_t)f * sh * sw;
-    uint8_t* D = dst + ((size_t)f * dh + y0) * dw;
-    for (int t = threadIdx.x; t < rows * dw; t += blockDim.x) {
-        const int ry = t / dw, x = t - ry * dw;
-        const AreaTaps& ax = s_x[x];
-        const AreaTaps& ay = s_y[ry];
-        float sum = 0.f;
-        for (int j = 0; j < ay.n; j++) {
-            const uint8_t* row = S + (size_t)(ay.first + j) * sw + ax.first;
-            float buf = 0.f;
-            for (int k = 0; k < ax.n; k++) buf += row[k] * ax.a[k];
-            const float term = ay.a[j] * buf;
-            sum = (j == 0) ? term : sum + term;
-        }
-        D[t] = (uint8_t)sat_u8_round(sum);
     }
 }
 
@@ -217,8 +135,8 @@ __global__ __launch_bounds__(256) void area_general_rows_kernel(const uint8_t* _
 // previous: as separate launches they are three latency-bound kernels in a row on the call's stream (28 + 16 + 6 us per
 // 256-frame clip, profiles/r05_dis_small_steps.md).  One workgroup per frame keeps the chain on chip: the finest level is
 // read into LDS once, every further level is formed from the previous one's LDS copy (tap tables of a level computed once
-// per workgroup, as in area_general_rows_kernel) and written to both LDS and its plane.  Per output the same taps, the same
-// f32 sums in the same order as area_u8_kernel's modes 0 / 1 / 2 (whichever launch_area would pick for that level).
+// per workgroup, as in area_general_rows_kernel) and written to both LDS and its plane.  Per output it is vstab_area.h's
+// area_px on the path plan_area names for that level, as in vstab_area_resize_u8.
 constexpr int TAIL_MAX_LEVELS = 8;
 #ifdef VSTAB_FUSED_TRACE
 #define TAIL_MARK(i) do { if (prof_) { const long long now_ = wall_clock64(); a.dbg[i] += now_ - tprev_; tprev_ = now_; } } while (0)
@@ -278,13 +196,13 @@ __global__ __launch_bounds__(1024) void pyramid_tail_kernel(TailArgs a)
     for (int l = 0; l < a.levels; l++) {
         const TailLevel& L = a.lv[l];
         const int dh = L.h, dw = L.w;
-        if (L.mode == 2) {
+        if (L.mode == AREA_GENERAL) {
             for (int x = threadIdx.x; x < dw; x += blockDim.x) area_taps(x, sw, L.scale_x, s_x[x]);
             for (int y = threadIdx.x; y < dh; y += blockDim.x) area_taps(y, sh, L.scale_y, s_y[y]);
             __syncthreads();
         }
         uint8_t* D = L.dst + (size_t)f * dh * dw;
-        if (L.mode == 2 && L.kx <= 4 && L.ky <= 4 && dw <= (int)blockDim.x) {
+        if (L.mode == AREA_GENERAL && L.kx <= 4 && L.ky <= 4 && dw <= (int)blockDim.x) {
             // General ratio with at most four taps per axis (any halving step: ratio 2 .. 2.1): a thread keeps its COLUMN's taps
             // in registers and walks down the rows; the sixteen candidate source bytes of an output are read together
             // (clamped addresses) and the absent taps are skipped by selects -- the same products added in the same order as
@@ -317,28 +235,7 @@ __global__ __launch_bounds__(1024) void pyramid_tail_kernel(TailArgs a)
         } else
         for (int t = threadIdx.x; t < dh * dw; t += blockDim.x) {
             const int y = t / dw, x = t - y * dw;
-            int o;
-            if (L.mode == 0) {
-                const unsigned char* s0 = cur + (2 * y) * sw + 2 * x;
-                o = (s0[0] + s0[1] + s0[sw] + s0[sw + 1] + 2) >> 2;
-            } else if (L.mode == 1) {
-                int sum = 0;
-                for (int j = 0; j < L.ky; j++)
-                    for (int i = 0; i < L.kx; i++) sum += cur[(y * L.ky + j) * sw + x * L.kx + i];
-                o = sat_u8_round(sum * (1.f / (L.kx * L.ky)));
-            } else {
-                const AreaTaps& ax = s_x[x];
-                const AreaTaps& ay = s_y[y];
-                float sum = 0.f;
-                for (int j = 0; j < ay.n; j++) {
-                    const unsigned char* row = cur + (ay.first + j) * sw + ax.first;
-                    float buf = 0.f;
-                    for (int k = 0; k < ax.n; k++) buf += row[k] * ax.a[k];
-                    const float term = ay.a[j] * buf;
-                    sum = (j == 0) ? term : sum + term;
-                }
-                o = sat_u8_round(sum);
-            }
+            const int o = area_px(L.mode, L.kx, L.ky, x, y, s_x[x], s_y[y], [=](int row, int col) { return (int)cur[row * sw + col]; });
             nxt[t] = (unsigned char)o;
             D[t] = (uint8_t)o;
         }
@@ -358,18 +255,14 @@ __global__ __launch_bounds__(1024) void pyramid_tail_kernel(TailArgs a)
         uint8_t* E = a.prep_ext + (size_t)f * he * we;
         for (int t = threadIdx.x; t < he * we; t += blockDim.x) {
             const int y = t / we, x = t - y * we;
-            E[t] = cur[clampi(y - DIS_BORDER, 0, h - 1) * w + clampi(x - DIS_BORDER, 0, w - 1)];
+            E[t] = pad_replicate_px(cur, h, w, y, x);
         }
         short* Dx = a.prep_ix + (size_t)f * h * w;
         short* Dy = a.prep_iy + (size_t)f * h * w;
         for (int t = threadIdx.x; t < h * w; t += blockDim.x) {
             const int y = t / w, x = t - y * w;
-            const unsigned char* r0 = cur + reflect101(y - 1, h) * w;
-            const unsigned char* r1 = cur + y * w;
-            const unsigned char* r2 = cur + reflect101(y + 1, h) * w;
-            const int xl = reflect101(x - 1, w), xr = reflect101(x + 1, w);
-            const int gx = (r0[xr] + 2 * r1[xr] + r2[xr]) - (r0[xl] + 2 * r1[xl] + r2[xl]);
-            const int gy = (r2[xl] + 2 * r2[x] + r2[xr]) - (r0[xl] + 2 * r0[x] + r0[xr]);
+            int gx, gy;
+            sobel_px(cur, h, w, y, x, gx, gy);
             Dx[t] = (short)gx; Dy[t] = (short)gy;
             lx[t] = (short)gx; ly[t] = (short)gy;
         }
@@ -377,42 +270,15 @@ __global__ __launch_bounds__(1024) void pyramid_tail_kernel(TailArgs a)
         const int aplane = h * ws;
         for (int t = threadIdx.x; t < h * ws; t += blockDim.x) {
             const int row = t / ws, js = t - row * ws;
-            const short* xr = lx + row * w + js * PSTR;
-            const short* yr = ly + row * w + js * PSTR;
-            int s_xx = 0, s_yy = 0, s_xy = 0, s_x = 0, s_y = 0;
-#pragma unroll
-            for (int j = 0; j < PSZ; j++) {
-                const int gx = xr[j], gy = yr[j];
-                s_xx += gx * gx; s_yy += gy * gy; s_xy += gx * gy; s_x += gx; s_y += gy;
-            }
-            laux[t] = (float)s_xx; laux[aplane + t] = (float)s_yy; laux[2 * aplane + t] = (float)s_xy;
-            laux[3 * aplane + t] = (float)s_x; laux[4 * aplane + t] = (float)s_y;
+            const WindowSums s = window_sums(lx + row * w + js * PSTR, ly + row * w + js * PSTR);
+            laux[t] = (float)s.xx; laux[aplane + t] = (float)s.yy; laux[2 * aplane + t] = (float)s.xy;
+            laux[3 * aplane + t] = (float)s.x; laux[4 * aplane + t] = (float)s.y;
         }
         __syncthreads();
         const size_t oplane = (size_t)a.n * hs * ws;
         for (int t = threadIdx.x; t < 5 * ws; t += blockDim.x) {
             const int k = t / ws, j = t - k * ws;
-            const float* av = laux + k * aplane + j;
-            float* o = a.prep_tensor + k * oplane + (size_t)f * hs * ws + j;
-            float ring[PSZ];
-            float sum = 0.f;
-#pragma unroll
-            for (int i = 0; i < PSZ; i++) { ring[i] = av[i * ws]; sum += ring[i]; }
-            o[0] = sum;
-            int is = 1;
-            for (int i0 = PSZ; i0 < h; i0 += PSZ) {
-                float v[PSZ];
-#pragma unroll
-                for (int q = 0; q < PSZ; q++) v[q] = (i0 + q < h) ? av[(i0 + q) * ws] : 0.f;
-#pragma unroll
-                for (int q = 0; q < PSZ; q++) {
-                    if (i0 + q < h) {
-                        sum += (v[q] - ring[q]);
-                        ring[q] = v[q];
-                        if ((q + 1) % PSTR == 0) { o[(size_t)is * ws] = sum; is++; }
-                    }
-                }
-            }
+            tensor_column_walk(laux + k * aplane + j, a.prep_tensor + k * oplane + (size_t)f * hs * ws + j, h, ws);
         }
 #ifdef VSTAB_FUSED_TRACE
         __syncthreads();
@@ -429,8 +295,7 @@ __global__ __launch_bounds__(256) void pad_replicate_kernel(const uint8_t* __res
     uint8_t* D = dst + (size_t)f * he * we;
     FRAME_STRIDE(t, he * we) {
         const int y = (int)(t / (unsigned)we), x = (int)(t - (unsigned)y * (unsigned)we);
-        const int sx = clampi(x - DIS_BORDER, 0, w - 1), sy = clampi(y - DIS_BORDER, 0, h - 1);
-        D[t] = S[(unsigned)(sy * w + sx)];
+        D[t] = pad_replicate_px(S, h, w, y, x);
     }
 }
 
@@ -442,22 +307,14 @@ __global__ __launch_bounds__(256) void sobel_kernel(const uint8_t* __restrict__ 
     short* Dy = Iy + (size_t)f * h * w;
     FRAME_STRIDE(t, h * w) {
         const int y = (int)(t / (unsigned)w), x = (int)(t - (unsigned)y * (unsigned)w);
-        const uint8_t* r0 = S + (unsigned)(reflect101(y - 1, h) * w);
-        const uint8_t* r1 = S + (unsigned)(y * w);
-        const uint8_t* r2 = S + (unsigned)(reflect101(y + 1, h) * w);
-        const int xl = reflect101(x - 1, w), xr = reflect101(x + 1, w);
-        const int gx = (r0[xr] + 2 * r1[xr] + r2[xr]) - (r0[xl] + 2 * r1[xl] + r2[xl]);
-        const int gy = (r2[xl] + 2 * r2[x] + r2[xr]) - (r0[xl] + 2 * r0[x] + r0[xr]);
+        int gx, gy;
+        sobel_px(S, h, w, y, x, gx, gy);
         Dx[t] = (short)gx;
         Dy[t] = (short)gy;
     }
 }
 
-// precomputeStructureTensor, horizontal sums of every patch column position (frame, row, js): OpenCV keeps five f32
-// running sums per row (`sum += x[j]*x[j] - x[j-8]*x[j-8]`, integer increments added to a float).  Every value such a
-// sum ever takes is an integer below 2^24 (8 terms of at most 1020^2: Sobel of u8 is within +-1020), so each of those
-// float additions is exact and the running sum equals the plain integer window sum -- computed here independently per
-// output, no sequential chain (the vertical pass, whose sums exceed 2^24, does keep OpenCV's order).
+// window_sums of every patch column position (frame, row, js)
 __global__ __launch_bounds__(256) void tensor_h_kernel(const short* __restrict__ Ix, const short* __restrict__ Iy, float* __restrict__ aux,
                                                        int n, int h, int w, int ws)
 {
@@ -468,50 +325,20 @@ __global__ __launch_bounds__(256) void tensor_h_kernel(const short* __restrict__
     float* A = aux + (size_t)f * h * ws;
     FRAME_STRIDE(t, h * ws) {
         const int row = (int)(t / (unsigned)ws), js = (int)(t - (unsigned)row * (unsigned)ws);
-        const short* xr = Fx + (unsigned)(row * w + js * PSTR);
-        const short* yr = Fy + (unsigned)(row * w + js * PSTR);
-        int s_xx = 0, s_yy = 0, s_xy = 0, s_x = 0, s_y = 0;
-#pragma unroll
-        for (int j = 0; j < PSZ; j++) {
-            const int gx = xr[j], gy = yr[j];
-            s_xx += gx * gx; s_yy += gy * gy; s_xy += gx * gy; s_x += gx; s_y += gy;
-        }
+        const WindowSums s = window_sums(Fx + (unsigned)(row * w + js * PSTR), Fy + (unsigned)(row * w + js * PSTR));
         float* o = A + t;
-        o[0] = (float)s_xx; o[plane] = (float)s_yy; o[2 * plane] = (float)s_xy; o[3 * plane] = (float)s_x; o[4 * plane] = (float)s_y;
+        o[0] = (float)s.xx; o[plane] = (float)s.yy; o[2 * plane] = (float)s.xy; o[3 * plane] = (float)s.x; o[4 * plane] = (float)s.y;
     }
 }
 
-// vertical running sums: one thread per (quantity, frame, js)
+// tensor_column_walk: one thread per (quantity, frame, js)
 __global__ __launch_bounds__(64) void tensor_v_kernel(const float* __restrict__ aux, float* __restrict__ out, int n, int h, int ws, int hs)
 {
     // grid (column blocks, frames, 5 quantities): no index arithmetic beyond the column
     const size_t aplane = (size_t)n * h * ws, oplane = (size_t)n * hs * ws;
     const int f = blockIdx.y, k = blockIdx.z;
-    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < ws; j += gridDim.x * blockDim.x) {
-        const float* a = aux + k * aplane + (size_t)f * h * ws + j;
-        float* o = out + k * oplane + (size_t)f * hs * ws + j;
-        // the last PSZ rows stay in registers (the row that leaves the window is not read twice), and the PSZ loads of a
-        // chunk are independent of the running sum: same additions in the same order
-        float ring[PSZ];
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < PSZ; i++) { ring[i] = a[(size_t)i * ws]; sum += ring[i]; }
-        o[0] = sum;
-        int is = 1;
-        for (int i0 = PSZ; i0 < h; i0 += PSZ) {
-            float v[PSZ];
-#pragma unroll
-            for (int k = 0; k < PSZ; k++) v[k] = (i0 + k < h) ? a[(size_t)(i0 + k) * ws] : 0.f;
-#pragma unroll
-            for (int k = 0; k < PSZ; k++) {
-                if (i0 + k < h) {
-                    sum += (v[k] - ring[k]);
-                    ring[k] = v[k];
-                    if ((k + 1) % PSTR == 0) { o[(size_t)is * ws] = sum; is++; }   // (i - PSZ + 1) % PSTR == 0 for i = i0 + k, i0 a multiple of PSZ
-                }
-            }
-        }
-    }
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < ws; j += gridDim.x * blockDim.x)
+        tensor_column_walk(aux + k * aplane + (size_t)f * h * ws + j, out + k * oplane + (size_t)f * hs * ws + j, h, ws);
 }
 
 // ---- patch inverse search ------------------------------------------------------------------
@@ -1526,35 +1353,6 @@ struct Carver {
     }
 };
 
-// cv::resize(INTER_AREA) picks its path from the ratios: exact 2 x 2, exact integer boxes, or the general tap tables
-struct AreaPlan { double scale_x, scale_y; int isx, isy, mode; };
-int plan_area(int sh, int sw, int dh, int dw, AreaPlan& pl)
-{
-    pl.scale_x = 1. / ((double)dw / sw); pl.scale_y = 1. / ((double)dh / sh);
-    pl.isx = (int)std::lrint(pl.scale_x); pl.isy = (int)std::lrint(pl.scale_y);
-    const bool fast = std::fabs(pl.scale_x - pl.isx) < DBL_EPSILON && std::fabs(pl.scale_y - pl.isy) < DBL_EPSILON;
-    VSTAB_REQUIRE(pl.scale_x >= 1.0 && pl.scale_y >= 1.0 && pl.scale_x < 6.0 && pl.scale_y < 6.0, "dis: area ratio %.3fx%.3f unsupported", pl.scale_x, pl.scale_y);
-    pl.mode = fast ? ((pl.isx == 2 && pl.isy == 2) ? 0 : 1) : 2;
-    return 0;
-}
-
-int launch_area(hipStream_t st, const uint8_t* src, uint8_t* dst, int n, int sh, int sw, int dh, int dw)
-{
-    AreaPlan pl;
-    if (int rc = plan_area(sh, sw, dh, dw, pl)) return rc;
-    const double scale_x = pl.scale_x, scale_y = pl.scale_y;
-    const int isx = pl.isx, isy = pl.isy;
-    int mode = pl.mode;
-    if (mode == 1 && isx == 4 && isy == 4 && sw % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 3) == 0) mode = 3;
-    const long long row_groups = (long long)n * ((dh + AREA_ROWS - 1) / AREA_ROWS);
-    if (mode == 2 && dw <= AREA_MAX_COLS && row_groups < 0x7fffffffLL)
-        hipLaunchKernelGGL(area_general_rows_kernel, dim3((unsigned)row_groups), dim3(256), 0, st, src, dst, n, sh, sw, dh, dw, scale_x, scale_y);
-    else
-        hipLaunchKernelGGL(area_u8_kernel, frame_grid((long long)dh * dw, n), dim3(256), 0, st, src, dst, n, sh, sw, dh, dw, mode, isx, isy, scale_x, scale_y);
-    VSTAB_HIP(hipGetLastError());
-    return 0;
-}
-
 }  // namespace
 
 // DISOpticalFlowImpl::calc scale selection incl. autoSelectPatchSizeAndScales (finest 2 -> default branch)
@@ -1643,7 +1441,7 @@ static int dis_run(vstab_ctx* ctx, const uint8_t* gray, int n, int h, int w, int
     auto prep_timer = std::make_unique<KernelTimer>(ctx, "dis_prep", KernelTimer::DETAIL);
     bool coarsest_prepared = false;   // pyramid_tail_kernel also formed the coarsest level's padded copy, gradients and tensor
     {
-        if (launch_area(st, gray, I[FINEST], n, h, w, G[FINEST].h, G[FINEST].w)) return 1;
+        if (int rc = vstab_area_resize_u8(st, gray, I[FINEST], n, h, w, G[FINEST].h, G[FINEST].w)) return rc;
         // the levels above the finest: one launch (pyramid_tail_kernel) where the finest level and its successor fit one
         // workgroup's LDS -- every clip whose working size is DIS's usual <= 960 px -- else one launch per level
         // (VSTAB_DIS_PYRAMID_TAIL=0 forces the latter: A/B measurement, tests)
@@ -1674,11 +1472,12 @@ static int dis_run(vstab_ctx* ctx, const uint8_t* gray, int n, int h, int w, int
             }
             ta.src = I[FINEST]; ta.n = n; ta.h0 = G[FINEST].h; ta.w0 = G[FINEST].w; ta.levels = tail_levels;
             for (int i = FINEST + 1; i <= coarsest; i++) {
-                AreaPlan pl;
-                if (int rc = plan_area(G[i - 1].h, G[i - 1].w, G[i].h, G[i].w, pl)) return rc;
+                const AreaPlan pl = plan_area(G[i - 1].h, G[i - 1].w, G[i].h, G[i].w);
+                // a halving step: far below what the kernel's eight-weight records hold
+                VSTAB_REQUIRE(pl.scale_x < AREA_TAPS_RATIO && pl.scale_y < AREA_TAPS_RATIO, "dis: area ratio %.3fx%.3f unsupported", pl.scale_x, pl.scale_y);
                 TailLevel& tl = ta.lv[i - FINEST - 1];
                 tl.dst = I[i]; tl.h = G[i].h; tl.w = G[i].w; tl.mode = pl.mode; tl.kx = pl.isx; tl.ky = pl.isy;
-                if (pl.mode == 2) {   // general ratio: kx / ky = the most taps an output can have along the axis (floor(scale) + 2)
+                if (pl.mode == AREA_GENERAL) {   // general ratio: kx / ky = the most taps an output can have along the axis (floor(scale) + 2)
                     tl.kx = (int)std::floor(pl.scale_x) + 2; tl.ky = (int)std::floor(pl.scale_y) + 2;
                 }
                 tl.scale_x = pl.scale_x; tl.scale_y = pl.scale_y;
@@ -1689,7 +1488,7 @@ static int dis_run(vstab_ctx* ctx, const uint8_t* gray, int n, int h, int w, int
             VSTAB_HIP(hipGetLastError());
         } else {
             for (int i = FINEST + 1; i <= coarsest; i++)
-                if (launch_area(st, I[i - 1], I[i], n, G[i - 1].h, G[i - 1].w, G[i].h, G[i].w)) return 1;
+                if (int rc = vstab_area_resize_u8(st, I[i - 1], I[i], n, G[i - 1].h, G[i - 1].w, G[i].h, G[i].w)) return rc;
         }
     }
     if (two_streams) {

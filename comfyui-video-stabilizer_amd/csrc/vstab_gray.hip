@@ -9,10 +9,9 @@
 // fma(b, 0.114, fma(g, 0.587, r*0.299)) and an unfused scalar tail for the last (w % 8) pixels
 // of a row; then v = gray*255 (f32), clip to [0,255], truncate.
 #include "vstab_internal.h"
+#include "vstab_area.h"
 #include "vstab_wait.h"
 #include <algorithm>
-#include <cfloat>
-#include <cmath>
 
 namespace {
 
@@ -25,12 +24,6 @@ __device__ __forceinline__ int gray_u8(float r, float g, float b, bool fused)
     float v = y * 255.0f;
     v = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);
     return (int)v;
-}
-
-__device__ __forceinline__ int sat_u8_round(float v)
-{
-    int i = (int)__builtin_rintf(v);
-    return i < 0 ? 0 : (i > 255 ? 255 : i);
 }
 
 // Integer-ratio INTER_AREA (K x K boxes) fused with the gray conversion. K == 1: gray only.
@@ -214,93 +207,6 @@ __global__ __launch_bounds__(256) void row_max_kernel(const float* __restrict__ 
     if ((threadIdx.x & 63) == 63) row_max[(size_t)blockIdx.x * 4 + (threadIdx.x >> 6)] = any_nan ? NAN : m;
 }
 
-// Generic integer ratio (kx, ky) on an already-gray image.
-__global__ __launch_bounds__(256) void area_int_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n,
-                                                          int sh, int sw, int dh, int dw, int kx, int ky)
-{
-    const long long total = (long long)n * dh * dw;
-    const float scale = 1.f / (kx * ky);
-    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
-        const int x = (int)(t % dw);
-        const long long r = t / dw;
-        const int y = (int)(r % dh);
-        const int f = (int)(r / dh);
-        const uint8_t* S = src + ((size_t)f * sh + (size_t)y * ky) * sw + (size_t)x * kx;
-        int sum = 0;
-        for (int j = 0; j < ky; j++)
-            for (int i = 0; i < kx; i++) sum += S[(size_t)j * sw + i];
-        int o;
-        if (kx == 2 && ky == 2) o = (sum + 2) >> 2;
-        else o = sat_u8_round(sum * scale);
-        dst[t] = (uint8_t)o;
-    }
-}
-
-struct AreaTabEntry { int si; float alpha; };
-
-// General INTER_AREA (non-integer ratio): f32 accumulation in OpenCV's order.
-__global__ __launch_bounds__(256) void area_general_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n,
-                                                              int sh, int sw, int dh, int dw,
-                                                              const AreaTabEntry* __restrict__ xtab, const int* __restrict__ xstart,
-                                                              const AreaTabEntry* __restrict__ ytab, const int* __restrict__ ystart)
-{
-    const long long total = (long long)n * dh * dw;
-    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
-        const int x = (int)(t % dw);
-        const long long r = t / dw;
-        const int y = (int)(r % dh);
-        const int f = (int)(r / dh);
-        const uint8_t* S = src + (size_t)f * sh * sw;
-        float sum = 0.f;
-        const int j0 = ystart[y], j1 = ystart[y + 1];
-        const int k0 = xstart[x], k1 = xstart[x + 1];
-        for (int j = j0; j < j1; j++) {
-            const uint8_t* row = S + (size_t)ytab[j].si * sw;
-            float buf = 0.f;
-            for (int k = k0; k < k1; k++) buf += row[xtab[k].si] * xtab[k].alpha;
-            const float term = ytab[j].alpha * buf;
-            sum = (j == j0) ? term : sum + term;
-        }
-        dst[t] = (uint8_t)sat_u8_round(sum);
-    }
-}
-
-int ceil_d(double v) { int i = (int)v; return i + (i < v); }
-int floor_d(double v) { int i = (int)v; return i - (i > v); }
-
-// computeResizeAreaTab of OpenCV's resize.cpp
-void build_area_tab(int ssize, int dsize, double scale, std::vector<AreaTabEntry>& tab, std::vector<int>& start)
-{
-    tab.clear();
-    start.assign((size_t)dsize + 1, 0);
-    for (int dx = 0; dx < dsize; dx++) {
-        start[dx] = (int)tab.size();
-        double fsx1 = dx * scale, fsx2 = fsx1 + scale;
-        double cellWidth = scale < ssize - fsx1 ? scale : ssize - fsx1;
-        int sx1 = ceil_d(fsx1), sx2 = floor_d(fsx2);
-        sx2 = sx2 < ssize - 1 ? sx2 : ssize - 1;
-        sx1 = sx1 < sx2 ? sx1 : sx2;
-        if (sx1 - fsx1 > 1e-3) tab.push_back({sx1 - 1, (float)((sx1 - fsx1) / cellWidth)});
-        for (int sx = sx1; sx < sx2; sx++) tab.push_back({sx, (float)(1.0 / cellWidth)});
-        if (fsx2 - sx2 > 1e-3) {
-            double a = fsx2 - sx2;
-            a = a < 1. ? a : 1.;
-            a = a < cellWidth ? a : cellWidth;
-            tab.push_back({sx2, (float)(a / cellWidth)});
-        }
-    }
-    start[dsize] = (int)tab.size();
-}
-
-unsigned grid_for(long long items)
-{
-    long long b = (items + 255) / 256;
-    const long long cap = 256LL * 16;  // 256 CUs x 16 blocks, grid-stride beyond that
-    if (b > cap) b = cap;
-    if (b < 1) b = 1;
-    return (unsigned)b;
-}
-
 }  // namespace
 
 static int gray_run(vstab_ctx* ctx, const float* frames, int n, int src_h, int src_w, int work_h, int work_w, uint8_t* gray,
@@ -338,13 +244,11 @@ static int gray_run(vstab_ctx* ctx, const float* frames, int n, int src_h, int s
         VSTAB_HIP(hipGetLastError());                                                                                     \
     } while (0)
 
-    // cv::resize: scale = 1/(dsize/ssize); integer-ratio fast path when both are integers within DBL_EPSILON
-    const double scale_x = 1. / ((double)work_w / src_w), scale_y = 1. / ((double)work_h / src_h);
-    const int isx = (int)std::lrint(scale_x), isy = (int)std::lrint(scale_y);
+    // the fused kernel forms the exact 2 x 2 and 4 x 4 boxes itself; every other working size is a resize of the full-size gray
+    const AreaPlan pl = plan_area(src_h, src_w, work_h, work_w);
     const bool same = (work_h == src_h && work_w == src_w);
-    const bool fast = !same && std::fabs(scale_x - isx) < DBL_EPSILON && std::fabs(scale_y - isy) < DBL_EPSILON;
-    const bool fused = fast && isx == isy && (isx == 2 || isx == 4);
-    const int K = same ? 1 : (fused ? isx : 1);
+    const bool fused = !same && pl.mode != AREA_GENERAL && pl.isx == pl.isy && (pl.isx == 2 || pl.isx == 4);
+    const int K = fused ? pl.isx : 1;
     const int threads = threads_for(src_w / K * K);   // the one launch of gray_area_int_kernel below, whichever it is
     if (frame_max) {
         // the gray pass covers every source sample exactly when its K x K boxes tile the source; every wavefront of
@@ -367,31 +271,7 @@ static int gray_run(vstab_ctx* ctx, const float* frames, int n, int src_h, int s
         if (ctx->d_gray_tmp.reserve(full)) return 1;
         uint8_t* tmp = static_cast<uint8_t*>(ctx->d_gray_tmp.ptr);
         LAUNCH_GRAY(1, src_h, tmp);
-        const long long out_items = (long long)n * work_h * work_w;
-        if (fast) {
-            hipLaunchKernelGGL(area_int_u8_kernel, dim3(grid_for(out_items)), dim3(256), 0, st, tmp, gray, n, src_h, src_w, work_h, work_w, isx, isy);
-            VSTAB_HIP(hipGetLastError());
-        } else {
-            std::vector<AreaTabEntry> xtab, ytab;
-            std::vector<int> xstart, ystart;
-            build_area_tab(src_w, work_w, scale_x, xtab, xstart);
-            build_area_tab(src_h, work_h, scale_y, ytab, ystart);
-            // pack the four tables into one staged upload
-            const size_t b_xt = xtab.size() * sizeof(AreaTabEntry), b_yt = ytab.size() * sizeof(AreaTabEntry);
-            const size_t b_xs = xstart.size() * sizeof(int), b_ys = ystart.size() * sizeof(int);
-            std::vector<unsigned char> blob(b_xt + b_yt + b_xs + b_ys);
-            memcpy(blob.data(), xtab.data(), b_xt);
-            memcpy(blob.data() + b_xt, ytab.data(), b_yt);
-            memcpy(blob.data() + b_xt + b_yt, xstart.data(), b_xs);
-            memcpy(blob.data() + b_xt + b_yt + b_xs, ystart.data(), b_ys);
-            void* d_blob = nullptr;
-            if (vstab_stage_params(ctx, blob.data(), blob.size(), &d_blob)) return 1;
-            unsigned char* db = static_cast<unsigned char*>(d_blob);
-            hipLaunchKernelGGL(area_general_u8_kernel, dim3(grid_for(out_items)), dim3(256), 0, st, tmp, gray, n, src_h, src_w, work_h, work_w,
-                               reinterpret_cast<const AreaTabEntry*>(db), reinterpret_cast<const int*>(db + b_xt + b_yt),
-                               reinterpret_cast<const AreaTabEntry*>(db + b_xt), reinterpret_cast<const int*>(db + b_xt + b_yt + b_xs));
-            VSTAB_HIP(hipGetLastError());
-        }
+        if (int rc = vstab_area_resize_u8(st, tmp, gray, n, src_h, src_w, work_h, work_w)) return rc;
     }
 #undef LAUNCH_GRAY
 #undef LAUNCH_GRAY_G
@@ -487,7 +367,7 @@ extern "C" int vstab_apply_value_range(vstab_ctx* ctx, const float* frames, int 
     VSTAB_REQUIRE(n > 0 && h > 0 && w > 0, "vstab_apply_value_range: non-positive size");
     VSTAB_HIP(hipSetDevice(ctx->device));
     const long long per_frame = (long long)h * w * 3, total = per_frame * n;
-    hipLaunchKernelGGL(value_range_kernel, dim3(grid_for(total)), dim3(256), 0, ctx->stream, frames, out, frame_max, per_frame, total);
+    hipLaunchKernelGGL(value_range_kernel, dim3(capped_grid(total, 256LL * 16)), dim3(256), 0, ctx->stream, frames, out, frame_max, per_frame, total);
     VSTAB_HIP(hipGetLastError());
     return 0;
 }

@@ -165,6 +165,10 @@ int vstab_check_device_status(vstab_ctx* ctx, const char* who);
 // Upload `bytes` of host data through the pinned staging buffer; returns device pointer.
 int vstab_stage_params(vstab_ctx* ctx, const void* host, size_t bytes, void** dev_out);
 
+// cv2.resize(..., INTER_AREA) of n gray images [sh][sw] -> [dh][dw] on `st`, any ratio >= 1 (vstab_area.hip; the rule
+// itself is vstab_area.h): the gray pass's and the DIS pyramid's resize.
+int vstab_area_resize_u8(hipStream_t st, const uint8_t* src, uint8_t* dst, int n, int sh, int sw, int dh, int dw);
+
 // Brackets the kernels of one API call with HIP events recorded on the call's stream (no host
 // sync here: vstab_last_kernel_ms waits for the stop event when the number is asked for).
 EventPair* vstab_timer_slot(vstab_ctx* ctx, const char* kind);

@@ -16,6 +16,10 @@ CASES = [
     (2, 90, 150, (50, 30)),     # exact 3x -> generic integer path
     (2, 72, 128, (96, 54)),     # 1.333x -> general area path (720p -> 960x540 in miniature)
     (1, 67, 121, (60, 33)),     # ragged general ratio
+    (1, 70, 130, (20, 11)),     # 6.5 x 6.36: above the eight-weight limit of the LDS tap tables -> run form
+    (1, 12, 1400, (1050, 9)),   # general ratio, wider than the column table -> run form
+    (1, 9, 1366, (1025, 7)),    # one column past the column table, a different ratio per axis
+    (2, 60, 90, (30, 30)),      # 3x2 boxes, two frames
 ]
 
 
